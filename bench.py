@@ -6,7 +6,8 @@ synthetic input resident in HBM: BASELINE.json configs[1] -- 65 536 independent 
 exponentiation, the reference's bls.Pairing) per GPU.  W untimed steps, then exactly K timed steps bracketed by barrier +
 synchronize on both sides, MAX over ranks, one JSON line from rank 0.  Units shard across GPUs with no data-path collective
 (weak scaling: 64k pairings per GPU).  After the timed region the output is compared with the oracle and the run FAILS on a
-mismatch.
+mismatch.  `--dump-outputs DIR` writes that output of the last timed step to DIR/*.npy first (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Two launch styles, same numbers at N = 1:
   * under torch.distributed.run (RANK / WORLD_SIZE in the environment): one process per GPU, RCCL through torch.distributed;
@@ -484,6 +485,26 @@ def compact_line(d, detail_file=None):
     return line
 
 
+DUMP_ROWS = 16384                  # headline rows --dump-outputs keeps: 16 384 x 144 float64 = 18.9 MB (the limit is 64 MB)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, fq12):
+    """--dump-outputs: the Fq12 results of the headline's LAST timed step as a caller of blsmi_pairing_batch_dev receives them ((n, 72) uint64,
+    the reference's in-memory FQ12), so that two builds can be compared output for output.  All rows when n <= DUMP_ROWS, else a fixed seeded
+    sample in increasing order (pairing_rows.npy says which).  float64 cannot hold a uint64, so every limb is split into its two 32-bit halves,
+    low half first: pairing_fq12.npy is (rows, 144) and exact."""
+    import torch
+    n = fq12.shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    got = fq12.index_select(0, torch.from_numpy(rows).to(fq12.device)).cpu().numpy()
+    words = np.ascontiguousarray(got).view(np.uint32)                      # little-endian: low half of each limb first
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pairing_fq12.npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, "pairing_rows.npy"), rows.astype(np.float64))
+    print("bench.py: outputs of the last timed step (%d of %d rows) written to %s" % (len(rows), n, out_dir), file=sys.stderr)
+
+
 def write_detail(d):
     """the full record of a run: bench_detail.json at the repo root, and under gpurun_out/ (what a gpurun call brings back)"""
     rel = "bench_detail.json"
@@ -928,7 +949,10 @@ def main():
     ap.add_argument("--no-aggregate", action="store_true")
     ap.add_argument("--no-ref-shapes", action="store_true")
     ap.add_argument("--no-msm", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the headline's results of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # The contract is ONE line on stdout.  Libraries print banners there (RCCL announces its version when the first
     # communicator is built), so stdout is pointed at stderr until the JSON line is ready.
@@ -1028,6 +1052,8 @@ def main():
     prof = read_profile(lib)                                               # the calling thread's device (device 0 / this rank), all timed steps
     dt = max_over_ranks(E, dt)
     total_gpus = world * ndev
+    if args.dump_outputs and rank == 0:                                    # before the parity gate: a build that fails it still leaves its outputs
+        dump_outputs(args.dump_outputs, bufs[0][2])
 
     # parity gate, outside the timed region, on every rank and device: a fast kernel with different results is not a result
     from oracle import refcpu as RC

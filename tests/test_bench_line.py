@@ -100,11 +100,37 @@ def test_line_of_a_multi_device_run_names_the_collective_leg():
     assert len(json.dumps(line, separators=(",", ":"))) < 4096
 
 
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs: the (n, 72) uint64 Fq12 rows come back exactly from the float64 32-bit halves; a batch larger than DUMP_ROWS is
+    sampled with a fixed seed (the same rows every run), and the files stay far below 64 MB"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(7)
+    for n in (66, 65536):
+        a = rng.integers(-(1 << 63), (1 << 63) - 1, size=(n, 72), dtype=np.int64, endpoint=True)
+        rows = []
+        for k in range(2):
+            d = tmp_path / ("%d_%d" % (n, k))
+            bench.dump_outputs(str(d), torch.from_numpy(a))
+            w, r = np.load(d / "pairing_fq12.npy"), np.load(d / "pairing_rows.npy")
+            assert w.dtype == np.float64 and r.dtype == np.float64 and w.shape == (min(n, bench.DUMP_ROWS), 144) and r.shape == (w.shape[0],)
+            h = w.astype(np.uint64).reshape(-1, 72, 2)
+            assert np.array_equal(h[..., 0] | (h[..., 1] << np.uint64(32)), a.view(np.uint64)[r.astype(np.int64)])
+            assert sum(f.stat().st_size for f in d.iterdir()) < 64 << 20
+            rows.append(r)
+        assert np.array_equal(rows[0], rows[1]) and np.all(np.diff(rows[0]) > 0)
+        if n <= bench.DUMP_ROWS:
+            assert np.array_equal(rows[0], np.arange(n))
+
+
 @pytest.mark.gpu
-def test_bench_command_prints_one_parsable_line():
-    """the driver's command at its smallest: the LAST stdout line parses, is < 4 KB and names every config"""
+def test_bench_command_prints_one_parsable_line(tmp_path):
+    """the driver's command at its smallest: the LAST stdout line parses, is < 4 KB and names every config; --dump-outputs leaves the last
+    timed step's results"""
+    import numpy as np
     env = dict(os.environ)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
     assert len(lines) == 1, "stdout must carry exactly one line, got %d" % len(lines)
@@ -120,6 +146,9 @@ def test_bench_command_prints_one_parsable_line():
         assert j["configs"][k]["cpu_baseline"]["value"] > 0 and j["configs"][k]["roofline"]["kernel"]
     detail = json.load(open(os.path.join(ROOT, j["detail"])))
     assert detail["value"] == j["value"] and "reference_shapes" in detail
+    w, r = np.load(dump / "pairing_fq12.npy"), np.load(dump / "pairing_rows.npy")
+    assert w.shape == (bench.DUMP_ROWS, 144) and w.dtype == np.float64 and r.shape == (bench.DUMP_ROWS,) and 0 <= r.min() and r.max() < 65536
+    assert np.all(w == np.floor(w)) and 0 <= w.min() and w.max() < 2 ** 32 and w.any()
 
 
 @pytest.mark.gpu

@@ -293,12 +293,11 @@ def test_every_c_call_passes_the_headers_types_in_order():
             _check_call_types("mutant", good.replace(a, b), protos)
 
 
-def test_nothing_newer_than_the_references_go_directive():
-    """/root/reference/go.mod:15 says `go 1.13`: with -tags blsmi the shim is compiled in that language version.  unsafe.Slice / unsafe.Add /
-    unsafe.String (1.17 / 1.20), generics and `any` (1.18), //go:build-only constraints (1.17), min / max / clear (1.21) must not appear."""
-    gomod = "/root/reference/go.mod"
-    if os.path.exists(gomod):                                            # (not on the GPU box; the directive is quoted in the shims' headers)
-        assert re.search(r"^go 1\.13$", open(gomod).read(), flags=re.M)
+def test_nothing_newer_than_the_references_go_directive(kats):
+    """The reference's go.mod:15 says `go 1.13` (tests/golden/reference_kats.json, tools/extract_reference_kats.py): with -tags blsmi the shim is
+    compiled in that language version.  unsafe.Slice / unsafe.Add / unsafe.String (1.17 / 1.20), generics and `any` (1.18), //go:build-only
+    constraints (1.17), min / max / clear (1.21) must not appear."""
+    assert kats["go_directive"] == "1.13"
     deny = [r"unsafe\.Slice", r"unsafe\.Add", r"unsafe\.String", r"unsafe\.SliceData", r"\bany\b", r"func \w+\[", r"\bclear\(", r"\bmin\(", r"\bmax\(",
             r"atomic\.(Int|Uint|Bool|Pointer)\d*\b", r"\bcgo\.Handle\b", r"0[bo][0-9]"]            # (0b / 0o literals are 1.13 itself: kept out for 1.12 readers too)
     srcs = _go_sources()

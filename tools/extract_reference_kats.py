@@ -2,8 +2,8 @@
 """Collect the known-answer vectors the reference's own tests hold for the verify path into
 tests/golden/reference_kats.json (DATA only: inputs + expected outputs, as decimal/hex strings).
 
-Runs only in the build container (reads /root/reference/*_test.go); the JSON travels.
-Sources (file:line under /root/reference):
+usage: python tools/extract_reference_kats.py <checkout of the reference>  (reads its *_test.go); the JSON is what the tests use.
+Sources (file:line in the reference):
   pairing_test.go:9-58      e(G1gen, G2gen) -- 12 Fq coefficients ("against Relic")
   hash_test.go:12-26        HashG1("the message to be signed")
   hash_test.go:48-62        HashG2 vector (declared; not enforced upstream because g2.go:141-143)
@@ -14,9 +14,12 @@ Sources (file:line under /root/reference):
   primitivefuncs_test.go:25-262  carry tables + 768-bit product vector
   g2pubs/bls_test.go:323-347, g1pubs/bls_test.go:411-433  DeriveSecretKey, invalid-pubkey hex
   g1.go:25-26, g2.go:26-29  generators
+  go.mod:15                 the `go` directive (the language version the cgo shims under shim/ are held to)
 """
-import json, re, pathlib
-REF = pathlib.Path("/root/reference")
+import json, re, pathlib, sys
+if len(sys.argv) != 2:
+    sys.exit("usage: %s <checkout of the reference>" % sys.argv[0])
+REF = pathlib.Path(sys.argv[1])
 def rd(p): return (REF / p).read_text()
 
 def func_body(src, name):
@@ -95,6 +98,7 @@ K["mont_images"] = {
   "b_coeff": reprs(re.search(r"var BCoeff = .*", g1).group(0))[0],
 }
 K["mont_images"] = {k: ([[str(x) for x in row] for row in v] if isinstance(v[0], list) else [str(x) for x in v]) for k, v in K["mont_images"].items()}
+K["go_directive"] = re.search(r"^go (\S+)$", rd("go.mod"), re.M).group(1)
 out = pathlib.Path(__file__).resolve().parent.parent / "tests" / "golden" / "reference_kats.json"
 out.write_text(json.dumps(K, indent=1) + "\n")
 print("wrote", out, {k: (len(v) if hasattr(v, "__len__") else 1) for k, v in K.items()})

@@ -1,6 +1,6 @@
 """First and later latency of a 1 000-tuple g2pubs verify call in a fresh process (scratch growth, lazy kernel loading)."""
-import sys, time, hashlib
-sys.path.insert(0, "/root/repo")
+import os, sys, time, hashlib
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from bls_amd import engine as eng
 eng.init(0)

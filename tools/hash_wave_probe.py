@@ -1,5 +1,5 @@
-import time, sys
-sys.path.insert(0, "/root/repo")
+import os, time, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bls_amd import engine as eng
 eng.init(0)
 def best(f,r=4):

@@ -1,6 +1,6 @@
 """Cost of bringing the library up in a fresh process: dlopen + blsmi_init (streams, generator tables, level programs), first calls."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 t0 = time.perf_counter()
 from bls_amd import _native
 lib = _native.load()

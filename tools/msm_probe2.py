@@ -1,5 +1,5 @@
-import sys, json, ctypes, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, json, ctypes, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from bls_amd import engine, _native
 engine.init(0); lib = _native.load()

@@ -1,7 +1,7 @@
 """Do two VerifyAggregate calls that run side by side on two streams (their hash and Miller-loop kernels interleaving on the SIMDs) finish
 sooner than one after the other?  2 x 2^19 messages resident."""
-import hashlib, sys, threading, time
-sys.path.insert(0, "/root/repo")
+import os, hashlib, sys, threading, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from bls_amd import engine as eng
 eng.init(0)
