@@ -6,6 +6,7 @@
 #include "lat_programs.h"
 #include "util_dev.h"
 #include "prepared.h"
+#include "route.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>
@@ -46,6 +47,7 @@ static int inflate_programs() {                                           // cal
 }
 
 namespace {
+using namespace blsmi_route;
 // Host state.  The library drives a LIST of devices from one process (blsmi_init_devices; blsmi_init binds a single one).
 // Every entry point leases one call context (a non-blocking stream, a grow-only scratch buffer and timing events) from
 // the pool of one device, so calls from several OS threads (cgo pins one per goroutine call) run concurrently on
@@ -153,6 +155,7 @@ struct Ctx {
     Device* dev = nullptr;
     // what this call put on its device and what the device carried from OTHER calls when it first asked (call_load: the layout choice)
     bool load_set = false; size_t load_n = 0, load_others = 0;
+    Tuning tune;                        // the options the call started with (CtxLease): every kernel choice of the call reads these (route.h)
     // per-kernel timing (blsmi_set_profiling): events recorded between the major kernels of the call that holds this context
     std::vector<hipEvent_t> pev; std::vector<const char*> pname; size_t pused = 0;
     bool pclosed = false;               // the call's closing mark is already recorded (on a caller-supplied stream, by UseStream)
@@ -284,18 +287,16 @@ int init_device(Device& d) {            // caller holds g_mu
     }
     return BLSMI_OK;
 }
-// Latency path (k_lat.hip): batches of at most g_lat_max tuples run one tuple per WAVE instead of one per lane pair.
-// (2 048 waves fit the chip at once; beyond a few thousand tuples the lane-pair kernels win on throughput.)
 // per-call opt-out of the endomorphism ladders (the *_ex entry points with BLSMI_MUL_ANY_POINT): set on every thread that works for such a call
 thread_local bool tl_mul_any = false;
 struct MulAny { bool saved; explicit MulAny(bool on) : saved(tl_mul_any) { tl_mul_any = on; } ~MulAny() { tl_mul_any = saved; } };
-std::atomic<bool> g_mul_subgroup{true}; // scalar multiplication through the endomorphisms (multiplicands in the subgroup); BLSMI_MUL_GENERIC=1 / blsmi_set_mul_assume_subgroup(0): plain ladder
-std::atomic<size_t> g_lat_max{8192};    // BLSMI_LAT_MAX, blsmi_set_latency_threshold (read by every call, written rarely).  The two paths meet at ~10 000 tuples
+std::atomic<bool> g_mul_subgroup{Tuning{}.mul_subgroup}; // scalar multiplication through the endomorphisms (multiplicands in the subgroup); BLSMI_MUL_GENERIC=1 / blsmi_set_mul_assume_subgroup(0): plain ladder
+std::atomic<size_t> g_lat_max{Tuning{}.lat_max};    // BLSMI_LAT_MAX, blsmi_set_latency_threshold (read by every call, written rarely).  The two paths meet at ~10 000 tuples
                                         // for pairings and verifies alike (tools/crossover.py: 8192 pairings 8.4 ms against 10.7, 16 384: 16.4 against 11.3)
 // Three layouts by batch size (pairings and verifies alike; tools/midsize.py): one tuple per WAVE up to min(g_lat_max, g_quad_min) tuples,
 // one per lane QUAD up to g_quad_max (16 384 tuples = one wave on every SIMD), one per lane PAIR beyond (65 536 fill the chip twice over).
-std::atomic<size_t> g_quad_max{16384};  // BLSMI_QUAD_MAX, blsmi_set_quad_threshold (0: no quad kernels)
-std::atomic<size_t> g_quad_min{5632};   // BLSMI_QUAD_MIN: the quad kernels take over from the latency path here already (pairings: 5.9 ms flat against 1 ms per 1 024 tuples; verifies 8.7 against 1.5)
+std::atomic<size_t> g_quad_max{Tuning{}.quad_max};  // BLSMI_QUAD_MAX, blsmi_set_quad_threshold (0: no quad kernels)
+std::atomic<size_t> g_quad_min{Tuning{}.quad_min};   // BLSMI_QUAD_MIN: the quad kernels take over from the latency path here already (pairings: 5.9 ms flat against 1 ms per 1 024 tuples; verifies 8.7 against 1.5)
 // The thresholds above are a LONE caller's: one tuple per wave finishes 4 096 pairings in 4.3 ms where the quad kernels take their flat 6 ms.
 // Callers that arrive together are a different matter (tools/midsize_concurrency.py): the latency path saturates the chip at 1.04 M pairings/s
 // whatever the number of calls in flight (its waves are bounded by LDS, 9 per CU), the quad kernels at 2.8 M/s (two 8 192-tuple calls take
@@ -303,54 +304,37 @@ std::atomic<size_t> g_quad_min{5632};   // BLSMI_QUAD_MIN: the quad kernels take
 // tuples plus those of the other calls in flight pass the lone crossover (floor 1 536: four callers x 2 048 pairings 7.9 -> 6.1 ms a call; at 1 024
 // the sum never passes the crossover with four contexts).  A call registers its tuples at its first layout question and
 // keeps the answer's input for its whole life (one call never sees two different loads); ~CtxLease takes them off again.
-std::atomic<bool> g_crowd_quad{true};        // BLSMI_CROWD_QUAD / blsmi_set_option("crowd_quad")
-std::atomic<size_t> g_crowd_floor{1536};     // BLSMI_CROWD_FLOOR / blsmi_set_option("crowd_floor")
-std::atomic<size_t> g_assume_load{0};        // blsmi_set_option("assume_load"): test hook, tuples pretended to be in flight from other calls
+std::atomic<bool> g_crowd_quad{Tuning{}.crowd_quad};        // BLSMI_CROWD_QUAD / blsmi_set_option("crowd_quad")
+std::atomic<size_t> g_crowd_floor{Tuning{}.crowd_floor};     // BLSMI_CROWD_FLOOR / blsmi_set_option("crowd_floor")
+std::atomic<size_t> g_assume_load{Tuning{}.assume_load};        // blsmi_set_option("assume_load"): test hook, tuples pretended to be in flight from other calls
 inline size_t call_load(size_t n) {
     Ctx* c = tl_ctx;
     if (!c || !c->dev) return 0;
     if (!c->load_set) { c->load_others = c->dev->load.fetch_add(n, std::memory_order_relaxed); c->load_n = n; c->load_set = true; }
-    return c->load_others + g_assume_load.load(std::memory_order_relaxed);
+    return c->load_others + c->tune.assume_load;
 }
 // A fourth layout between the wave and the quad (round 6, k_pairing_row.hip): one tuple per DPP ROW of sixteen lanes.  g_row_min .. g_row_max
 // tuples (2 048 .. 8 192) of a LONE caller take it: 4 096 tuples are one wave on every SIMD there (a quarter of the SIMDs in the quad layout, four waves of
 // 3.3 x the instructions on the one-tuple-per-wave path).  When other calls are in flight on the device the choice above stands (the quad
 // kernels spend fewer lane-instructions per tuple: 12.6 M against 18 M).  blsmi_set_row_threshold / BLSMI_ROW_MIN / BLSMI_ROW_MAX; max 0: off.
-std::atomic<size_t> g_hash_row_min{2048}, g_hash_row_max{4096};   // blsmi_set_option("hash_row_min" / "hash_row_max"): HashG2 of this many messages clears its cofactor in the lane-row layout (k_clear_h2_row; max 0: never)
-std::atomic<size_t> g_hash_quad_min{4097}, g_hash_quad_max{16384};   // "hash_quad_min" / "hash_quad_max": ... four lanes per message (k_clear_h2_quad)
-std::atomic<size_t> g_hash_oct_min{2048}, g_hash_oct_max{7168};   // "hash_oct_min" / "hash_oct_max": ... eight lanes per message (k_clear_h2_oct, oct_g2.inc); takes precedence over the row and quad tails
-std::atomic<size_t> g_hash_g1_quad_min{1280}, g_hash_g1_quad_max{32768};   // "hash_g1_quad_min" / "hash_g1_quad_max": HashG1's tail four lanes per message (k_hash_g1_finish_quad)
-std::atomic<size_t> g_swu_row_max{4096};   // "swu_row_max": the SWU maps of HashG1 / HashG2 run a ROW of sixteen lanes per map (k_swu_g?_rows) above BLSMI_SWU_WAVE_MAX and up to here; 0: never
-std::atomic<size_t> g_row_side_piece{0};   // "row_side_piece": the side stream runs its row kernel in launches of this many tuples (0, the default: one launch -- pieces measured slower, verify_host.inc)
-std::atomic<size_t> g_row_side_lds{0};   // "row_side_lds": bytes of (unused) LDS per workgroup of the side kernel of a call of more than 4 096 tuples -- 40960: four workgroups a CU, a wave slot of every SIMD left to the hash; measured slower (verify_host.inc); 0, the default: none
-std::atomic<bool> g_row_side_g2pubs{true};   // "row_side_g2pubs": ... for g2pubs too (the signature side over the generator's table as a kernel of its own; measured, see verify_host.inc)
-std::atomic<bool> g_row_side{true};     // BLSMI_ROW_SIDE / blsmi_set_option("row_side"): a Verify in the row layout runs its signature side beside the hash (verify_host.inc)
-std::atomic<size_t> g_row_min{2048};   // (tools/midsize4.py: 2 048 pairings 2.08 against 2.21 ms on the wave path, g1pubs verifies 4.45 against 4.72, g2pubs 3.66 against 3.57; 1 024: 2.05 against 1.54)
-std::atomic<size_t> g_row_max{8192};   // (8 192 pairings 4.0 ms against the quad kernels' flat 5.7; 12 288: 6+ against 5.7)
-// pairing_only: blsmi_pairing_batch has no hash beside its two kernels, and there the row kernels stay ahead of the quad kernels' flat 5.7 ms up to 12 288 tuples
-// (three waves per SIMD: 5.34 ms; verifies cross at ~10 000: 12 288 g2pubs verifies 8.96 against 7.95 ms) -- half again the general maximum
-inline bool use_row(size_t n, bool pairing_only = false) {
-    const bool crowd = g_crowd_quad.load(std::memory_order_relaxed) && n >= g_crowd_floor.load(std::memory_order_relaxed);
-    const size_t others = crowd ? call_load(n) : 0;                        // (every sizeable call is counted, whatever layout it takes itself)
-    size_t hi = g_row_max.load(std::memory_order_relaxed);
-    if (pairing_only) hi += hi / 2;
-    if (!g_pair_layout || hi == 0 || n > hi || n < g_row_min.load(std::memory_order_relaxed)) return false;
-    const size_t lone = std::min(g_lat_max.load(), g_quad_min.load());
-    return !(others > 0 && n + others > lone);
-}
-inline bool use_quad(size_t n) {
-    // every sizeable call is counted, whatever layout it takes itself (a 65 536-tuple call in flight is load for the 3 000-tuple call beside it)
-    const bool crowd = g_crowd_quad.load(std::memory_order_relaxed) && n >= g_crowd_floor.load(std::memory_order_relaxed);
-    const size_t others = crowd ? call_load(n) : 0;
-    if (!g_pair_layout || n > g_quad_max) return false;
-    if (use_row(n)) return false;
-    const size_t lone = std::min(g_lat_max.load(), g_quad_min.load());
-    return n > lone || (crowd && n + others > lone);
-}
-inline bool use_lat(size_t n) { return n <= g_lat_max && !use_quad(n) && !use_row(n); }
+std::atomic<size_t> g_hash_row_min{Tuning{}.hash_row_min}, g_hash_row_max{Tuning{}.hash_row_max};   // blsmi_set_option("hash_row_min" / "hash_row_max"): HashG2 of this many messages clears its cofactor in the lane-row layout (k_clear_h2_row; max 0: never)
+std::atomic<size_t> g_hash_quad_min{Tuning{}.hash_quad_min}, g_hash_quad_max{Tuning{}.hash_quad_max};   // "hash_quad_min" / "hash_quad_max": ... four lanes per message (k_clear_h2_quad)
+std::atomic<size_t> g_hash_oct_min{Tuning{}.hash_oct_min}, g_hash_oct_max{Tuning{}.hash_oct_max};   // "hash_oct_min" / "hash_oct_max": ... eight lanes per message (k_clear_h2_oct, oct_g2.inc); takes precedence over the row and quad tails
+std::atomic<size_t> g_hash_g1_quad_min{Tuning{}.hash_g1_quad_min}, g_hash_g1_quad_max{Tuning{}.hash_g1_quad_max};   // "hash_g1_quad_min" / "hash_g1_quad_max": HashG1's tail four lanes per message (k_hash_g1_finish_quad)
+std::atomic<size_t> g_swu_row_max{Tuning{}.swu_row_max};   // "swu_row_max": the SWU maps of HashG1 / HashG2 run a ROW of sixteen lanes per map (k_swu_g?_rows) above BLSMI_SWU_WAVE_MAX and up to here; 0: never
+std::atomic<bool> g_row_side_g2pubs{Tuning{}.row_side_g2pubs};   // "row_side_g2pubs": ... for g2pubs too (the signature side over the generator's table as a kernel of its own: 4 096 tuples 3.23 against 3.55 ms, verify_host.inc)
+std::atomic<bool> g_row_side{Tuning{}.row_side};     // BLSMI_ROW_SIDE / blsmi_set_option("row_side"): a Verify in the row layout runs its signature side beside the hash (verify_host.inc)
+std::atomic<size_t> g_row_min{Tuning{}.row_min};   // (tools/midsize4.py: 2 048 pairings 2.08 against 2.21 ms on the wave path, g1pubs verifies 4.45 against 4.72, g2pubs 3.66 against 3.57; 1 024: 2.05 against 1.54)
+std::atomic<size_t> g_row_max{Tuning{}.row_max};   // (8 192 pairings 4.0 ms against the quad kernels' flat 5.7; 12 288: 6+ against 5.7)
+// A Pairing call's row range reaches half again as far (route.h: pairing_layout): with no hash beside its two kernels the row kernels stay ahead of the
+// quad kernels' flat 5.7 ms up to 12 288 tuples (three waves per SIMD: 5.34 ms; verifies cross at ~10 000: 12 288 g2pubs verifies 8.96 against 7.95 ms).
 inline unsigned qblocks(size_t n) { return (unsigned)((n + QT - 1) / QT); }
 inline unsigned rblocks(size_t n) { return (unsigned)((n + RT - 1) / RT); }
-inline bool mul_subgroup() { return !tl_mul_any && g_mul_subgroup.load(std::memory_order_relaxed); }
+// The options of the call this thread serves: the snapshot CtxLease took (tuning_now)
+inline const Tuning& tune() { return tl_ctx->tune; }
+// what the layout questions of a call of n tuples see of the other calls on its device (a crowded call registers its own tuples: call_load)
+inline size_t route_load(size_t n) { return crowded(n, tune()) ? call_load(n) : 0; }
+inline bool mul_subgroup() { return !tl_mul_any && tune().mul_subgroup; }
 inline u32 lat_lds_bytes(size_t prog_offset) { u32 nslot; memcpy(&nslot, blsmi_lat_blob + prog_offset + 8, 4); return nslot * 80; }   // k_lat.hip: SLOT_WORDS * 4
 // ---- the environment is read ONCE, at initialisation (under g_mu), never from an entry point ---------------------------------------
 // getenv racing a setenv in another thread is undefined (glibc), and a variable read per call silently changes what a concurrent caller
@@ -369,11 +353,11 @@ struct EnvCfg {
     size_t combine_max = 1024; int combine_wait_us = 150, combine_inflight_max = 2; bool combine_debug = false;   // BLSMI_COMBINE_*
     char rccl_path[512] = {0};          // BLSMI_RCCL_PATH: librccl for a process that has none mapped yet (a Go binary has no torch to bring it)
 } g_env;
-std::atomic<bool> g_agg_cofactor_pow{true};    // BLSMI_AGG_COFACTOR_POW / blsmi_set_option("agg_cofactor_pow")
-std::atomic<bool> g_msm_sort{true};            // BLSMI_MSM_SORT / blsmi_set_option("msm_sort")
-std::atomic<bool> g_lat_rolled{true};          // BLSMI_LAT_ROLLED / blsmi_set_option("lat_rolled"): 0 = small Pairing calls take the STRAIGHT-LINE copy of their level program (pairing1s) instead of the one with rolled squaring runs (A/B)
+std::atomic<bool> g_agg_cofactor_pow{Tuning{}.agg_cofactor_pow};    // BLSMI_AGG_COFACTOR_POW / blsmi_set_option("agg_cofactor_pow")
+std::atomic<bool> g_msm_sort{Tuning{}.msm_sort};            // BLSMI_MSM_SORT / blsmi_set_option("msm_sort")
+std::atomic<bool> g_lat_rolled{Tuning{}.lat_rolled};          // BLSMI_LAT_ROLLED / blsmi_set_option("lat_rolled"): 0 = small Pairing calls take the STRAIGHT-LINE copy of their level program (pairing1s) instead of the one with rolled squaring runs (A/B)
 std::atomic<size_t> g_combine_mid_max{8192};  // BLSMI_COMBINE_MID_MAX / blsmi_set_option("combine_mid_max"): concurrent Verify calls of BLSMI_COMBINE_MAX <= n < this many tuples merge into one launch (verify_host.inc); 0: never
-std::atomic<bool> g_dup_force_sort{false};     // BLSMI_DUP_FORCE_SORT / blsmi_set_option("dup_force_sort"): test hook, the duplicate screen's fallback on every call
+std::atomic<bool> g_dup_force_sort{Tuning{}.dup_force_sort};     // BLSMI_DUP_FORCE_SORT / blsmi_set_option("dup_force_sort"): test hook, the duplicate screen's fallback on every call
 // Options a caller has set through the API (blsmi_set_option, blsmi_set_*_threshold, blsmi_set_mul_assume_subgroup) keep their values when the library
 // (re-)initialises: the environment and the defaults apply only to what was never set explicitly (a set_option before the first entry point,
 // or before a re-initialisation after blsmi_shutdown, was silently overwritten here).
@@ -405,6 +389,22 @@ void load_env() {                       // caller holds g_mu; runs once per init
     if (!is_explicit(X_LAT_ROLLED)) { const char* v = getenv("BLSMI_LAT_ROLLED"); g_lat_rolled = !(v && v[0] == '0'); }
     if (!is_explicit(X_CROWD_QUAD)) { const char* v = getenv("BLSMI_CROWD_QUAD"); g_crowd_quad = !(v && v[0] == '0'); }
     if (!is_explicit(X_CROWD_FLOOR)) if (const char* v = getenv("BLSMI_CROWD_FLOOR")) g_crowd_floor = (size_t)strtoull(v, nullptr, 10);
+}
+// The options as they stand now, copied out of the atomics above and the settings fixed at initialisation: the only place that reads the
+// atomics for a call.  CtxLease takes one such snapshot per call; each call's every kernel choice reads it (tune(), route.h), so that an
+// option set while calls are in flight applies to the calls that start after it, and never to half of one.
+Tuning tuning_now() {
+    constexpr auto rx = std::memory_order_relaxed;
+    Tuning t;
+    t.lat_max = g_lat_max.load(rx); t.quad_max = g_quad_max.load(rx); t.quad_min = g_quad_min.load(rx); t.row_min = g_row_min.load(rx); t.row_max = g_row_max.load(rx);
+    t.crowd_quad = g_crowd_quad.load(rx); t.crowd_floor = g_crowd_floor.load(rx); t.assume_load = g_assume_load.load(rx);
+    t.hash_row_min = g_hash_row_min.load(rx); t.hash_row_max = g_hash_row_max.load(rx); t.hash_quad_min = g_hash_quad_min.load(rx); t.hash_quad_max = g_hash_quad_max.load(rx);
+    t.hash_oct_min = g_hash_oct_min.load(rx); t.hash_oct_max = g_hash_oct_max.load(rx); t.hash_g1_quad_min = g_hash_g1_quad_min.load(rx); t.hash_g1_quad_max = g_hash_g1_quad_max.load(rx);
+    t.swu_row_max = g_swu_row_max.load(rx); t.row_side = g_row_side.load(rx); t.row_side_g2pubs = g_row_side_g2pubs.load(rx);
+    t.agg_cofactor_pow = g_agg_cofactor_pow.load(rx); t.msm_sort = g_msm_sort.load(rx); t.lat_rolled = g_lat_rolled.load(rx); t.dup_force_sort = g_dup_force_sort.load(rx);
+    t.mul_subgroup = g_mul_subgroup.load(rx); t.pair_layout = g_pair_layout; t.use_gen_lines = g_use_gen_lines; t.hash_g2_pair = g_env.hash_g2_pair; t.hash_g1_split = g_env.hash_g1_split;
+    t.swu_wave_max = g_env.swu_wave_max; t.sig_side_max = g_env.sig_side_max; t.fixed_wave_max = g_env.fixed_wave_max;
+    return t;
 }
 // devs[0..ndev): HIP ordinals.  Caller holds g_mu.
 int ensure_init_list(const int* devs, int ndev) {
@@ -522,6 +522,7 @@ struct CtxLease {
         c->busy = true; c->dev->leased++; c->dev->leases++;
         c->pused = 0; c->pclosed = false;
         c->load_set = false; c->load_n = 0; c->load_others = 0;
+        c->tune = tuning_now();
         c->arena.reset();                                                   // the temporaries of the context's previous call (its streams are idle: see the destructor)
         outer = tl_ctx;
         tl_ctx = mine = c;
@@ -820,59 +821,39 @@ bool jac_host_is_infinity(const uint8_t* rec, size_t wire_bytes) {
 }  // namespace
 
 // ---- pairing ------------------------------------------------------------------------------------
-static int pairing_dev(const void* d_g1, const void* d_g2, void* d_out, size_t n, hipStream_t s, int mode) {
+// mode 0: Pairing, 1: MillerLoop; lay: the call's pairing layout (route.h: pairing_layout)
+static int pairing_dev(const void* d_g1, const void* d_g2, void* d_out, size_t n, hipStream_t s, int mode, Layout lay) {
     if (n == 0) return BLSMI_OK;
-    if (mode == 0 && use_lat(n)) {                                         // small call: one pairing per wave (k_lat.hip)
-        const size_t prog = g_lat_rolled.load(std::memory_order_relaxed) ? (size_t)LAT_PAIRING1_OFFSET : (size_t)LAT_PAIRING1S_OFFSET;   // the same pairing, its squaring runs unrolled (A/B partner)
-        prof_mark(prog == LAT_PAIRING1_OFFSET ? "k_lat:pairing1" : "k_lat:pairing1s");
+    if (lay == Layout::wave) {   // small call: one pairing per wave (k_lat.hip; pairing1s: its squaring runs unrolled, A/B partner), MillerLoop: the reference's steps
+        const size_t prog = mode ? (size_t)LAT_MILLER1X_OFFSET : tune().lat_rolled ? (size_t)LAT_PAIRING1_OFFSET : (size_t)LAT_PAIRING1S_OFFSET;
+        prof_mark(mode ? "k_lat:miller1x" : prog == LAT_PAIRING1_OFFSET ? "k_lat:pairing1" : "k_lat:pairing1s");
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog,
                            (const u8*)d_g1, (size_t)96, (const u8*)d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
                            (const u8*)nullptr, (u8*)nullptr, (u64*)d_out, n);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return BLSMI_OK;
+    } else {
+        HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
+        i32* f = reinterpret_cast<i32*>(g_ws.p);
+        const unsigned pblocks = (unsigned)((n + PT - 1) / PT);
+        const bool pairl = lay == Layout::pair;
+        if (lay == Layout::row) {                                          // a few thousand tuples: sixteen lanes per tuple, one wave per SIMD at 4 096 tuples
+            prof_mark("k_miller1h_row");
+            hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
+            prof_mark("k_final_exp_row");
+            hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
+        } else if (lay == Layout::quad) {                                  // mid-size batch: four lanes per tuple, one wave per SIMD at 16 384 tuples
+            prof_mark("k_miller1h_quad");
+            hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
+            prof_mark("k_final_exp_quad");
+            hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
+        } else {                                                           // mode 1 (MillerLoop): the reference's steps; mode 0 (Pairing): the homogeneous steps
+            prof_mark(pairl ? (mode ? "k_miller1_pair" : "k_miller1h_pair") : (mode ? "k_miller1" : "k_miller1h"));
+            if (pairl) hipLaunchKernelGGL(mode ? k_miller1_pair : k_miller1h_pair, dim3(pblocks), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
+            else hipLaunchKernelGGL(mode ? k_miller1 : k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
+            prof_mark(pairl ? "k_final_exp_pair" : "k_final_exp");
+            if (pairl) hipLaunchKernelGGL(k_final_exp_pair, dim3(pblocks), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
+            else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
+        }
     }
-    if (mode == 1 && n <= g_lat_max) {                                     // small MillerLoop call: the reference's steps as a level program
-        prof_mark("k_lat:miller1x");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1X_OFFSET), s, (const u8*)g_gens.lat + LAT_MILLER1X_OFFSET,
-                           (const u8*)d_g1, (size_t)96, (const u8*)d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, (u64*)d_out, n);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return BLSMI_OK;
-    }
-    HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
-    i32* f = reinterpret_cast<i32*>(g_ws.p);
-    const unsigned pblocks = (unsigned)((n + PT - 1) / PT);
-    if (mode == 0 && use_row(n, true)) {                                   // a few thousand tuples: sixteen lanes per tuple, one wave per SIMD at 4 096 tuples
-        prof_mark("k_miller1h_row");
-        hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-        prof_mark("k_final_exp_row");
-        hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return BLSMI_OK;
-    }
-    if (mode == 0 && use_quad(n)) {                                        // mid-size batch: four lanes per tuple, one wave per SIMD at 16 384 tuples
-        prof_mark("k_miller1h_quad");
-        hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-        prof_mark("k_final_exp_quad");
-        hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return BLSMI_OK;
-    }
-    // mode 1 (MillerLoop): the reference's steps; mode 0 (Pairing): the homogeneous steps
-    prof_mark(g_pair_layout ? (mode ? "k_miller1_pair" : "k_miller1h_pair") : (mode ? "k_miller1" : "k_miller1h"));
-    if (g_pair_layout) hipLaunchKernelGGL(mode ? k_miller1_pair : k_miller1h_pair, dim3(pblocks), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-    else hipLaunchKernelGGL(mode ? k_miller1 : k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-    prof_mark(g_pair_layout ? "k_final_exp_pair" : "k_final_exp");
-    if (g_pair_layout) hipLaunchKernelGGL(k_final_exp_pair, dim3(pblocks), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
-    else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));      // blocking entry point: results are ready on return
@@ -924,8 +905,8 @@ BLSMI_API int blsmi_set_mul_assume_subgroup(int on) {
 }
 // Run-time switches of code paths that produce identical results (A/B tests, soaks): name = "agg_cofactor_pow" (large g2pubs aggregates
 // raise their Miller product to 1 - x instead of clearing n hash points), "msm_sort" (device radix sort against the exact histogram passes),
-// "dup_force_sort" (the duplicate screen's host-sort fallback on every call).  value: 0 / 1.  Atomic: a call in flight sees the old or the new
-// value, never a torn one; the verdicts do not depend on them.
+// "dup_force_sort" (the duplicate screen's host-sort fallback on every call); the layout switches (include/blsmi.h).  Each call reads every option
+// once, when it starts (tuning_now): a change applies to the calls that start after it.  The verdicts do not depend on them.
 BLSMI_API int blsmi_set_option(const char* name, long long value) {
     if (!name) return BLSMI_E_ARG;
     const std::string n(name);
@@ -936,8 +917,6 @@ BLSMI_API int blsmi_set_option(const char* name, long long value) {
     else if (n == "crowd_quad") { set_explicit(X_CROWD_QUAD); g_crowd_quad.store(value != 0); }
     else if (n == "row_side") { set_explicit(X_ROW_SIDE); g_row_side.store(value != 0); }
     else if (n == "row_side_g2pubs") g_row_side_g2pubs.store(value != 0);
-    else if (n == "row_side_lds") g_row_side_lds.store((size_t)std::min(65536LL, std::max(0LL, value)));
-    else if (n == "row_side_piece") g_row_side_piece.store((size_t)std::max(0LL, value));
     else if (n == "hash_row_min") g_hash_row_min.store((size_t)std::max(0LL, value));
     else if (n == "hash_row_max") g_hash_row_max.store((size_t)std::max(0LL, value));
     else if (n == "swu_row_max") g_swu_row_max.store((size_t)std::max(0LL, value));
@@ -983,7 +962,7 @@ BLSMI_API int blsmi_pairing_batch_dev(const void* d_g1, const void* d_g2, void* 
     if (!d_g1 || !d_g2 || !d_out) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
-    return pairing_dev(d_g1, d_g2, d_out, n, g_stream, 0);
+    return pairing_dev(d_g1, d_g2, d_out, n, g_stream, 0, pairing_layout(0, n, tune(), route_load(n)));
 }
 // host-buffer form: independent tuples, split over the devices by contiguous block, no exchange at all
 static int pairing_host(const uint8_t* g1, const uint8_t* g2, uint64_t* out, size_t n, int mode, bool jac = false) {
@@ -998,7 +977,7 @@ static int pairing_host(const uint8_t* g1, const uint8_t* g2, uint64_t* out, siz
         if (rc) return rc;
         rc = upload_points(192, jac, g2 + rec_bytes(192, jac) * lo, b.p, m, g_stream);
         if (rc) return rc;
-        rc = pairing_dev(a.p, b.p, o.p, m, g_stream, mode);
+        rc = pairing_dev(a.p, b.p, o.p, m, g_stream, mode, pairing_layout(mode, m, tune(), route_load(m)));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(out + 72 * lo, o.p, 576 * m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
@@ -1022,7 +1001,7 @@ BLSMI_API int blsmi_pairing_batch_jac_dev(const void* d_g1_jac, const void* d_g2
     int rc = jac_to_wire_dev(96, d_g1_jac, a.p, nullptr, n, g_stream);
     if (!rc) rc = jac_to_wire_dev(192, d_g2_jac, b.p, nullptr, n, g_stream);
     if (rc) return rc;
-    return pairing_dev(a.p, b.p, d_out, n, g_stream, 0);
+    return pairing_dev(a.p, b.p, d_out, n, g_stream, 0, pairing_layout(0, n, tune(), route_load(n)));
 }
 // G?Projective.ToAffine().SerializeBytes() (g1.go:322-340 + 157-167, g2.go:365-386 + 172-186) for n points: wire records (all zero for
 // the point at infinity) and the infinity flags
@@ -1053,25 +1032,16 @@ BLSMI_API int blsmi_final_exponentiation_batch(const uint64_t* in, uint64_t* out
     DBuf i, f, o;
     HIPCHK(i.alloc(576 * n)); HIPCHK(o.alloc(576 * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
     HIPCHK(hipMemcpyAsync(i.p, in, 576 * n, hipMemcpyHostToDevice, g_stream));
-    if (use_row(n)) {                                                      // a few thousand values: sixteen lanes per value (k_pairing_row.hip), 1.2 ms up to 4 096
-        hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, i.as<u64>(), f.as<i32>(), n);
-        hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), o.as<u64>(), n, 0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, o.p, 576 * n, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        return BLSMI_OK;
-    }
-    if (n <= g_lat_max) {                                                  // small call: one final exponentiation per wave (k_lat.hip)
+    const Layout lay = final_exp_layout(n, tune(), route_load(n));
+    if (lay == Layout::wave)                                               // small call: one final exponentiation per wave (k_lat.hip)
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_FINALEXP1_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_FINALEXP1_OFFSET,
                            (const u8*)i.p, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
                            (const u8*)nullptr, (u8*)nullptr, o.as<u64>(), n);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, o.p, 576 * n, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        return BLSMI_OK;
+    else {                                                                 // a few thousand values: sixteen lanes per value (k_pairing_row.hip), 1.2 ms up to 4 096
+        hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, i.as<u64>(), f.as<i32>(), n);
+        if (lay == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), o.as<u64>(), n, 0);
+        else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, g_stream, f.as<i32>(), o.as<u64>(), n, 0);
     }
-    hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, i.as<u64>(), f.as<i32>(), n);
-    hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, g_stream, f.as<i32>(), o.as<u64>(), n, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, o.p, 576 * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1153,7 +1123,7 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
         // the generator as the common multiplicand (PrivToPub): the device's fixed-base table -- 32 mixed additions, no doublings.
         // Small calls: one scalar per wave (the 32 table entries meet in a tree of additions across the lanes).
         const i32* table = PB == 96 ? g_gens.fixed1 : g_gens.fixed2;
-        if (m <= g_env.fixed_wave_max && m <= g_lat_max) {
+        if (m <= g_env.fixed_wave_max && m <= tune().lat_max) {
             prof_mark(PB == 96 ? "k_g1_mul_fixed_wave" : "k_g2_mul_fixed_wave");
             if (PB == 96) hipLaunchKernelGGL(k_g1_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
             else hipLaunchKernelGGL(k_g2_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
@@ -1166,7 +1136,7 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
     }
-    if (m <= g_lat_max && mul_subgroup()) { // small call: one multiplication per wave (k_lat.hip, SEL levels over the decomposed scalar)
+    if (m <= tune().lat_max && mul_subgroup()) { // small call: one multiplication per wave (k_lat.hip, SEL levels over the decomposed scalar)
         const size_t prog = PB == 96 ? LAT_MUL1_OFFSET : LAT_MUL2_OFFSET;
         DBuf good, rec; HIPCHK(good.alloc(m, s)); HIPCHK(rec.alloc(64 * m, s));
         hipLaunchKernelGGL(k_glv_recode, dim3(nblocks(m)), dim3(WG), 0, s, d_scalars, PB == 96 ? 1 : 2, rec.as<u8>(), m);
@@ -1281,13 +1251,14 @@ static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, si
     HIPCHK(b0.alloc(sizeof(i32) * words * half)); HIPCHK(b1.alloc(sizeof(i32) * words * ((half + 1) / 2)));
     // jac: d_pts are the reference's in-memory Jacobian records (144 / 288 bytes, d_inf unused: z == 0 says it).  Many points: level 0 adds
     // them as they are (k_g?_sum0_jac: no inversion anywhere before the one at the end); few: they become wire records for the level programs
-    if (jac && half <= g_lat_max) {
+    const bool lat = half <= tune().lat_max;
+    if (jac && lat) {
         HIPCHK(wire.alloc((size_t)PB * n));
         int rc = jac_to_wire_dev(PB, d_pts, wire.p, nullptr, n, s);
         if (rc) return rc;
         d_pts = wire.as<u8>(); d_inf = nullptr; jac = false;
     }
-    if (half <= g_lat_max) {
+    if (lat) {
         // few points: every addition of the tree as a level program, one per wave (k_lat.hip: sum0 / sum1 / sumfin; complete
         // projective formulas, two product levels per addition) -- ~10 us a level instead of ~70-140
         const size_t p0 = W == 3 ? LAT_SUM0_1_OFFSET : LAT_SUM0_2_OFFSET, p1 = W == 3 ? LAT_SUM1_1_OFFSET : LAT_SUM1_2_OFFSET, pf = W == 3 ? LAT_SUMFIN_1_OFFSET : LAT_SUMFIN_2_OFFSET;
@@ -1480,7 +1451,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     // grouping the 16 n items by bucket: a device radix sort (msm.inc: k_msm_items, k_util.hip); BLSMI_MSM_SORT=0 at start-up or
     // blsmi_set_option("msm_sort", 0) (the tests cross-check the two) takes the exact histogram + scan + atomic scatter instead
     const size_t nitems = (size_t)16 * n;
-    bool sort_mode = nitems < ((size_t)1 << 31) && g_msm_sort.load(std::memory_order_relaxed);   // (the sort counts its items in an int: 2^27 points and beyond take the exact passes)
+    bool sort_mode = nitems < ((size_t)1 << 31) && tune().msm_sort;   // (the sort counts its items in an int: 2^27 points and beyond take the exact passes)
     DBuf skey[2], sval[2];
     if (sort_mode) {
         // the sort's ping-pong buffers are 256 bytes per point (4 x 16 n words) on top of everything else: when they do not fit, the exact passes
@@ -1564,7 +1535,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     prof_mark(W == 6 ? (pairk ? "k_g2_msm_fold2_pair" : "k_g2_msm_fold2") : "k_g1_msm_fold2");
     i32* src = ch0.as<i32>(); i32* dst = ch1.as<i32>();
     int narr = 2, m = 0;
-    const bool lat_tail = g_lat_max > 0 && per_win_chunks == ((size_t)1 << 13) && K == 8;   // the tail runs as a latency program (k_lat.hip), which reads the inter-kernel record form
+    const bool lat_tail = tune().lat_max > 0 && per_win_chunks == ((size_t)1 << 13) && K == 8;   // the tail runs as a latency program (k_lat.hip), which reads the inter-kernel record form
     for (size_t len = per_win_chunks; len > 1; len /= 2, narr++, m++) {
         const size_t lanes = (size_t)(narr + 1) * nbw * (len / 2);
         const int io = (lat_tail && len == 2) ? 1 : 0;                     // the last level writes what the tail program reads

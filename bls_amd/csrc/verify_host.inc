@@ -13,12 +13,9 @@ inline Kind kind_of(int kind) { return kind == 0 ? Kind{192, 96, 96} : Kind{96, 
 // Prepared public keys (k_prepared_pair.hip, g2pubs only): tables of blsmi_prep::WORDS i32 each on the device, and per tuple
 // the index of its key's table (null: tuple t uses table t).
 struct PrepKeys { const i32* tables; const u32* idx; };
-// whether a batch of n tuples reads the tables in its Miller loops; otherwise (small batches on the latency programs, the
-// single-lane layout) the keys' affine records are gathered out of the tables and the ordinary path runs
-// (mid-size batches run in the lane-quad layout, which has no table-reading kernels: there, too, the keys' records are gathered -- the quad
-// kernels recompute the lines and still finish well ahead of the lane-pair kernels reading them: 16 384 verifies 8.3 against ~12 ms)
-inline bool prep_tables_serve(size_t n) { return g_pair_layout && g_use_gen_lines && n > g_lat_max && !use_quad(n); }
-inline bool prep_tables_serve_aggregate(size_t n) { return g_pair_layout && g_use_gen_lines && n > g_lat_max && (n + 1) / 2 > g_quad_max; }
+// Only the lane-pair kernels read the tables in their Miller loops (route.h: prepared_tables_serve); every other layout gathers the keys'
+// affine records out of the tables and runs the ordinary path (the quad kernels recompute the lines and still finish well ahead of the
+// lane-pair kernels reading them: 16 384 verifies 8.3 against ~12 ms)
 int prep_gather_keys(const PrepKeys& prep, DBuf& pk, size_t n, hipStream_t s) {
     HIPCHK(pk.alloc((size_t)192 * n, s));
     prof_mark("k_prepared_gather_keys");
@@ -30,33 +27,23 @@ int prep_gather_keys(const PrepKeys& prep, DBuf& pk, size_t n, hipStream_t s) {
 // g1_clear == false (kind 0 only): the hash points WITHOUT their cofactor clearing (hash.cuh: swu_finish_g1), always on the throughput kernels --
 // for a large g2pubs VerifyAggregate, which raises the product of its Miller values to 1 - x instead (agg_pow_wanted)
 // d_special (may be null; with g1_clear == false): a device int that gets bit 1 when some message's mapped points cancel (hash.cuh: swu_finish_g1)
-// beside_side: the signature side's row kernel runs beside this hash on a side stream (verify_sig_side_start): the maps then stay a lane each -- few waves at a raised
-// priority, the chip left to the side kernel -- instead of a row of sixteen lanes each (4 096 g2pubs verifies 3.27 against 3.50 ms, tools/prio_ab.py)
-int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h, size_t n, hipStream_t s, bool g1_clear = true, int* d_special = nullptr, bool beside_side = false) {
+// r: the route of the hash (route.h: hash_route; hash_route_alone below for a hash that is the whole call)
+int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h, size_t n, hipStream_t s, const HashRoute& r, bool g1_clear = true, int* d_special = nullptr) {
     dim3 g(nblocks(n)), w(WG), g2(nblocks(2 * n));
-    // a call in the lane-row layout (2 048 .. 8 192 tuples, blsmi.hip: use_row) hashes on the latency programs while they beat the mid-size kernels'
+    // a call in the lane-row layout (2 048 .. 8 192 tuples) hashes on the latency programs while they beat the mid-size kernels'
     // flat times (tools/midsize4.py: HashG1 two lanes + finish 1.5 ms, k_hash_g2_pair 2.9 ms; the programs take 0.27 / 0.53 ms per 1 024 messages on top of the maps)
     // HashG2 of 2 048 .. 4 096 messages (round 6): the maps and the isogeny a lane pair per message (k_hash_g2_front, an eighth of the SIMDs), then the cofactor
-    // clearing -- two thirds of the hash -- sixteen lanes per message on every SIMD (k_clear_h2_row)
-    // ... or EIGHT lanes per message (k_clear_h2_oct, oct_g2.inc: the homogeneous formulas' levels are four and six products wide)
-    const bool g2_oct_tail = kind == 1 && g_pair_layout && g_env.hash_g2_pair && n >= g_hash_oct_min.load(std::memory_order_relaxed) && n <= g_hash_oct_max.load(std::memory_order_relaxed);
-    const bool g2_row_tail = !g2_oct_tail && kind == 1 && g_pair_layout && g_env.hash_g2_pair && n >= g_hash_row_min.load(std::memory_order_relaxed) && n <= g_hash_row_max.load(std::memory_order_relaxed);
-    // 4 097 .. 16 384 messages: the same split with four lanes per message (k_clear_h2_quad, quad_g2.inc): 16 384 messages are one wave on every SIMD
-    const bool g2_quad_tail = kind == 1 && g_pair_layout && g_env.hash_g2_pair && !g2_row_tail && !g2_oct_tail && n >= g_hash_quad_min.load(std::memory_order_relaxed) && n <= g_hash_quad_max.load(std::memory_order_relaxed);
-    // HashG1 of 1 280 .. 32 768 messages: the tail behind the two-lane maps four lanes per message (k_hash_g1_finish_quad)
-    const bool g1_quad_tail = kind == 0 && g1_clear && g_env.hash_g1_split && n <= 2 * g_quad_max && n >= g_hash_g1_quad_min.load(std::memory_order_relaxed) && n <= g_hash_g1_quad_max.load(std::memory_order_relaxed);
-    const size_t lat_hash_max = g2_oct_tail || g2_row_tail || g2_quad_tail || g1_quad_tail ? 0 : use_row(n) ? (kind == 0 ? (size_t)3584 : (size_t)3072) : g_lat_max / 2;
-    if (n <= lat_hash_max && n <= g_lat_max / 2 && g1_clear && !use_quad(n)) {   // (a call that takes the quad kernels because the device is crowded hashes on the throughput kernels too)
+    // clearing -- two thirds of the hash -- sixteen lanes per message on every SIMD (k_clear_h2_row), EIGHT (k_clear_h2_oct, oct_g2.inc: the homogeneous
+    // formulas' levels are four and six products wide) or four (k_clear_h2_quad, quad_g2.inc: 16 384 messages are one wave on every SIMD)
+    const bool waves = r.swu == Swu::waves, rows = r.swu == Swu::rows;
+    if (r.path == HashPath::lat) {
         // small batch: one lane per SWU map (the two maps of a message side by side; for the *WithDomain search two candidates
         // per round), then the curve arithmetic after the maps as a level program, one message per wave (k_lat.hip);
         // messages the program flags (good == 0) are redone by the one-lane kernel
         const size_t rec = kind == 0 ? 192 : kind == 1 ? 384 : 192;
         const size_t prog = kind == 0 ? LAT_HASHFIN1_OFFSET : kind == 1 ? LAT_HASHFIN2_OFFSET : LAT_COFAC2_OFFSET;
         DBuf pts, good; HIPCHK(pts.alloc(rec * n, s)); HIPCHK(good.alloc(n, s));
-        // the smallest calls: one WAVE per SWU map, its exponentiation with one limb per lane (fp_row.cuh); 2 n waves
-        const size_t wave_max = g_env.swu_wave_max;
-        const bool waves = n <= (kind == 2 ? wave_max / 4 : wave_max);       // the *WithDomain search takes eight waves a message
-        const bool rows = !waves && !beside_side && kind != 2 && n <= g_swu_row_max.load(std::memory_order_relaxed);   // a row of sixteen lanes per map, four maps per wave (k_hash.hip)
+        // the smallest calls: one WAVE per SWU map, its exponentiation with one limb per lane (fp_row.cuh); then a row of sixteen lanes per map (k_hash.hip)
         prof_mark(kind == 0 ? (waves ? "k_swu_g1_waves" : rows ? "k_swu_g1_rows" : "k_swu_g1_two_lanes") : kind == 1 ? (waves ? "k_swu_g2_waves" : rows ? "k_swu_g2_rows" : "k_swu_g2_two_lanes") : (waves ? "k_tai_g2_waves8" : "k_tai_g2_lanes8"));
         if (rows && kind == 0) hipLaunchKernelGGL(k_swu_g1_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
         else if (rows) hipLaunchKernelGGL(k_swu_g2_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
@@ -80,14 +67,12 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     }
     // HashG1 of a mid-size batch (up to twice the quad threshold: 32 768 messages are one wave per SIMD in the two-lane kernel): the two
     // SWU maps of a message on two lanes, then the tail one message per lane -- k_hash_g1 alone leaves most SIMDs without a wave there
-    const bool g1_split = g_env.hash_g1_split;
-    if (kind == 0 && g1_split && n <= 2 * g_quad_max) {
+    if (r.path == HashPath::g1_lane || r.path == HashPath::g1_quad) {
         DBuf pts; HIPCHK(pts.alloc((size_t)192 * n, s));
-        const bool rows = !beside_side && n > g_env.swu_wave_max && n <= g_swu_row_max.load(std::memory_order_relaxed);
         prof_mark(rows ? "k_swu_g1_rows" : "k_swu_g1_two_lanes");
         if (rows) hipLaunchKernelGGL(k_swu_g1_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
         else hipLaunchKernelGGL(k_swu_g1_two_lanes, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        if (g1_quad_tail) {                                                 // four lanes per message (k_hash_quad.hip, quad_g1.inc); exceptions redone a message per lane
+        if (r.path == HashPath::g1_quad) {                                 // four lanes per message (k_hash_quad.hip, quad_g1.inc); exceptions redone a message per lane
             DBuf good; HIPCHK(good.alloc(n, s));
             prof_mark("k_hash_g1_finish_quad");
             hipLaunchKernelGGL(k_hash_g1_finish_quad, dim3(qblocks(n)), w, 0, s, (const u8*)pts.as<u8>(), good.as<u8>(), d_h, n);
@@ -104,11 +89,11 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
         return BLSMI_OK;
     }
     // HashG2 of a large batch: a lane pair per message, two waves per SIMD (k_hash_pair.hip); BLSMI_HASH_G2_PAIR=0 keeps the one-lane kernel
-    const bool g2_pair = g_env.hash_g2_pair;
-    if (kind == 1 && g2_pair) {
+    if (kind == 1 && r.path != HashPath::plain) {
         const unsigned redo_every = g_env.hash_g2_pair_redo_every;
         DBuf good; HIPCHK(good.alloc(n, s));
-        if (g2_oct_tail || g2_row_tail || g2_quad_tail) {
+        const bool g2_oct_tail = r.path == HashPath::g2_oct, g2_row_tail = r.path == HashPath::g2_row;
+        if (r.path != HashPath::g2_pair) {
             DBuf jb; HIPCHK(jb.alloc(sizeof(i32) * 6 * NL_IO * n, s));
             prof_mark("k_hash_g2_front");
             hipLaunchKernelGGL(k_hash_g2_front, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, good.as<u8>(), jb.as<i32>(), n, redo_every);
@@ -152,11 +137,13 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
-// n single-pair Miller loops MillerLoop(g1_i, g2_i) into the SoA buffer f, in the configured lane layout
+// A hash that is the whole call (HashG1 / HashG2 entry points) takes the route a Verify of as many tuples gives its hash
+inline HashRoute hash_route_alone(int kind, size_t n) { return hash_route(kind, n, verify_layout(n, tune(), route_load(n)), true, false, tune()); }
 // one level of the Fq12 product tree: dst[t] = src[t] * src[t + half] (a missing partner counts as 1), SoA buffers of cur / half records
 void launch_prod_level(const i32* src, i32* dst, size_t cur, size_t half, hipStream_t s) {
-    prof_mark(half <= g_lat_max ? "k_lat:mul12raw" : "k_fq12_prod_level");
-    if (half <= g_lat_max)                                                 // few products: one per wave (k_lat.hip, "mul12raw"), ~5 us instead of ~80
+    const bool lat = half <= tune().lat_max;
+    prof_mark(lat ? "k_lat:mul12raw" : "k_fq12_prod_level");
+    if (lat)                                                               // few products: one per wave (k_lat.hip, "mul12raw"), ~5 us instead of ~80
         hipLaunchKernelGGL(k_lat, dim3((unsigned)half), dim3(64), lat_lds_bytes(LAT_MUL12RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MUL12RAW_OFFSET,
                            (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, half, reinterpret_cast<const u8*>(src), cur,
                            (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(dst), half);
@@ -164,64 +151,41 @@ void launch_prod_level(const i32* src, i32* dst, size_t cur, size_t half, hipStr
         hipLaunchKernelGGL(k_fq12_prod_level, dim3(nblocks(half)), dim3(WG), 0, s, src, dst, cur, half);
     prof_mark(nullptr);
 }
-// Returns how many Fq12 values it left in f: n, or ceil(n / 2) when two tuples shared a loop.
-size_t launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, const PrepKeys* prep = nullptr) {
-    if (prep) {                                                            // d_g2 unused: the lines come from the keys' tables (caller checked prep_tables_serve)
-        const size_t m = (n + 1) / 2;
+// The Miller loops of an aggregate in the layout of its route (route.h: aggregate_route), which also says how many Fq12 values they leave
+// in f: n, or ceil(n / 2) when two tuples share a loop.  prep: the keys' tables (only where r.tables; d_g2 is unused then).
+void launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, const AggregateRoute& r, const PrepKeys* prep) {
+    const size_t m = r.records;
+    if (r.tables) {
         prof_mark("k_miller1x2_prep_pair");
         hipLaunchKernelGGL(k_miller1x2_prep_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, d_g1, prep->tables, prep->idx, f, n, m);
-        return m;
+        return;
     }
-    const bool quad2 = g_pair_layout && n > g_lat_max && (n + 1) / 2 <= g_quad_max;   // mid-size aggregate: two consecutive tuples per lane QUAD (k_pairing_quad.hip)
-    const bool row1 = n <= g_lat_max && use_row(n);                        // a few thousand signers: one Miller loop per lane ROW (k_pairing_row.hip), n values as on the wave path
-    prof_mark(row1 ? "k_miller1s_row" : n <= g_lat_max ? "k_lat:miller1raw" : quad2 ? "k_miller1x2_quad" : g_pair_layout ? "k_miller1x2_pair" : "k_miller1h");
-    if (row1) {
+    const Layout l = r.layout;
+    prof_mark(l == Layout::row ? "k_miller1s_row" : l == Layout::wave ? "k_lat:miller1raw" : l == Layout::quad ? "k_miller1x2_quad" : l == Layout::pair ? "k_miller1x2_pair" : "k_miller1h");
+    if (l == Layout::row)                                                  // a few thousand signers: one Miller loop per lane ROW (k_pairing_row.hip), n values as on the wave path
         hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, (size_t)96, d_g2, (size_t)192, f, n, (const i32*)nullptr, (size_t)0, n);
-        return n;
-    }
-    if (n <= g_lat_max) {                                                  // small aggregate: one Miller loop per wave (any Miller value serves a product that is final-exponentiated)
+    else if (l == Layout::wave)                                            // small aggregate: one Miller loop per wave (any Miller value serves a product that is final-exponentiated)
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MILLER1RAW_OFFSET,
                            d_g1, (size_t)96, d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
                            (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
-        return n;
-    }
-    if (quad2) {
-        const size_t m = (n + 1) / 2;
+    else if (l == Layout::quad)                                            // mid-size aggregate: two consecutive tuples per lane QUAD (k_pairing_quad.hip)
         hipLaunchKernelGGL(k_miller1x2_quad, dim3(qblocks(m)), dim3(WG), 0, s, d_g1, d_g2, f, n, m);
-        return m;
-    }
-    if (g_pair_layout) {                                                   // two consecutive tuples per lane pair, one 2-pair loop
-        const size_t m = (n + 1) / 2;
+    else if (l == Layout::pair)                                            // two consecutive tuples per lane pair, one 2-pair loop
         hipLaunchKernelGGL(k_miller1x2_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, d_g1, d_g2, f, n, m);
-        return m;
-    }
-    hipLaunchKernelGGL(k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
-    return n;
+    else
+        hipLaunchKernelGGL(k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
 }
-// Small Verify calls (the Go API's shape: one tuple per call): the signature side's Miller loop -- MillerLoop(-sig, G2One) for g2pubs,
-// MillerLoop(-G1One, sig) for g1pubs -- needs nothing of the message, so it runs on a side stream WHILE the message is hashed (program
-// "miller1rawn", one wave per tuple, values left in f), and the pair stage is one Miller loop, one product and the final exponentiation
-// (program "verify1s") instead of the two-pair loop: a lone g2pubs Verify 2.17 -> 2.03 ms.  It pays while the side kernel's waves find idle
-// SIMDs beside the hash kernels (tools/side_max_probe.py): up to 48 tuples per call for g2pubs (its G1 hash is short: -0.13 ms up to 24
-// tuples, -0.04 at 48, +0.07 at 64), up to 320 for g1pubs (-0.12 .. -0.16 ms; +0.35 at 384).  BLSMI_SIG_SIDE_MAX overrides both (0 = never).
-// The lane-row layout (2 048 .. 8 192 tuples, round 6) splits the same way with its own kernels: the hash kernels of such a call leave most SIMDs
-// idle (HashG1: 128-256 waves for 1.5 ms; HashG2 2.9 ms), the signature side's row kernel (k_miller1s_row: 0.75 ms over the generator's table,
-// 1.0 ms over a signature in G2) fills them, and the pair stage is ONE Miller loop times that value (k_miller1m_row).  "row_side" (BLSMI_ROW_SIDE) 0: off.
-// Measured (tools/midsize4.py, profiles/r06_midsize4.log): it pays where the signature is the VARIABLE G2 point -- g1pubs: 2 304 tuples 5.97 -> 5.21 ms,
-// 4 096: 6.45 -> 6.10, 8 192: 9.12 -> 8.66 -- and not for g2pubs (the generator's table lines ride along in the two-pair loop for 0.54 ms; as a kernel of
-// their own they take 0.75 ms and slow the hash beside them: 4.37 ms either way), so kind 0 keeps the two-pair loop.  The same split in the lane-QUAD
-// layout (VERDICT r05 item 4) was built and measured (profiles/r06_sig_side_quad_experiment.log): g1pubs 8 192 tuples 9.85 -> 8.75 ms -- where the row
-// layout serves anyway (8.69) -- but 12 288: 9.90 -> 10.87 and 16 384: 9.96 -> 11.14 ms: the quad kernels hold the whole register file of every SIMD
-// (one wave each at 16 384 tuples), so the hash kernel's waves wait for them (k_hash_g2_pair 2.99 -> 7.47 ms).  Removed again.
-inline bool sig_side_row(int kind, size_t n) { return (kind != 0 || g_row_side_g2pubs.load(std::memory_order_relaxed)) && g_row_side.load(std::memory_order_relaxed) && use_row(n); }
-inline bool sig_side_wanted(int kind, size_t n) {
-    if (n > 0 && sig_side_row(kind, n)) return true;
-    const size_t lim = g_env.sig_side_max >= 0 ? (size_t)g_env.sig_side_max : (kind == 0 ? (size_t)48 : (size_t)320);
-    return n > 0 && n <= lim && use_lat(n);
-}
+// The signature side's Miller loop -- MillerLoop(-sig, G2One) for g2pubs, MillerLoop(-G1One, sig) for g1pubs -- needs nothing of the message,
+// so it runs on a side stream WHILE the message is hashed (route.h: sig_side), its values left in f.  Small calls: program "miller1rawn", one
+// wave per tuple, then "verify1s" (one Miller loop, the product, the final exponentiation): a lone g2pubs Verify 2.17 -> 2.03 ms while the side
+// waves find idle SIMDs (up to 48 g2pubs / 320 g1pubs tuples, tools/side_max_probe.py).  The row layout: k_miller1s_row beside the hash, then
+// k_miller1m_row (g1pubs 4 096 tuples 6.45 -> 6.10 ms, tools/midsize4.py; g2pubs with "row_side_g2pubs" and the hash's maps a lane each beside
+// it: 3.55 -> 3.23 ms, profiles/r06c_variants.log).  Measured and dropped: the side kernel in pieces or with LDS reserved (r06f_side_lds.log),
+// the split in the quad layout (r06_sig_side_quad_experiment.log) -- DESIGN 3e.
 // after: a stream whose enqueued work produces d_sigs (null: d_sigs is complete, or host_sigs is given and copied here, on the side stream)
 // sigs_jac: host_sigs are in-memory Jacobian records (converted into d_sigs on the side stream, blsmi.hip: upload_points)
-int verify_sig_side_start(int kind, void* d_sigs, const uint8_t* host_sigs, i32* f, size_t n, hipStream_t after, bool sigs_jac = false) {
+// side: the call's signature side (route.h: sig_side), wave or row
+int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host_sigs, i32* f, size_t n, hipStream_t after, bool sigs_jac = false) {
     const Kind k = kind_of(kind);
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t st = tl_ctx->aux[0];
@@ -229,37 +193,24 @@ int verify_sig_side_start(int kind, void* d_sigs, const uint8_t* host_sigs, i32*
     if (host_sigs) { int rc = upload_points(k.sig_bytes, sigs_jac, host_sigs, d_sigs, n, st); if (rc) return rc; }
     const u8* tp = kind == 0 ? (const u8*)d_sigs : g_gens.g1; const size_t sp = kind == 0 ? 96 : 0;
     const u8* tq = kind == 0 ? g_gens.g2 : (const u8*)d_sigs; const size_t sq = kind == 0 ? 0 : 192;
-    if (sig_side_row(kind, n)) {
-        // "row_side_piece" > 0: in pieces of that many tuples, one launch after the other.  Measured with pieces of 4 096 (one wave per SIMD, so that the hash kernels'
-        // waves always find a free slot beside a call of 8 192): SLOWER -- a piece of 2 048 tuples takes the 1.0 ms a piece of 4 096 takes (a lone wave per SIMD is
-        // bound by its own latency), so 6 144 tuples cost 2.0 ms in two pieces against 1.6 in one launch: g2pubs 5 120 / 6 144 / 8 192 tuples 5.48 / 5.51 / 5.55 ms in
-        // pieces, 4.91 / 5.15 / 5.37 in one launch; g1pubs 6.35 / 7.06 / 7.11 against 6.08 / 6.54 / 6.60 (tools/prio_ab.py, profiles/r06c_variants.log).  Default 0.
-        // "row_side_lds" > 0, the other way to keep a wave slot of every SIMD free for the hash: the side kernel's workgroups (one wave each) ask for 40 KB of LDS they never
-        // touch, so four fit a CU.  k_hash_g2_front then runs its 1.16 ms also beside a call of 8 192 (2.06 without), but the side kernel becomes the critical path and the
-        // tail behind the front pays instead: g1pubs 5 120 / 6 144 / 8 192 tuples 6.21 / 6.59 / 7.02 ms against 6.08 / 6.54 / 6.59, g2pubs 5.57 / 5.71 / 6.15 against
-        // 4.93 / 5.09 / 5.36 (tools/prio_ab.py, profiles/r06f_side_lds.log).  Default 0.
-        const size_t piece = g_row_side_piece.load(std::memory_order_relaxed);
-        const unsigned lds = n > 4096 ? (unsigned)g_row_side_lds.load(std::memory_order_relaxed) : 0u;
-        for (size_t first = 0; first < n; first += piece ? piece : n) {
-            const size_t end = piece ? std::min(n, first + piece) : n;
-            hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(end - first)), dim3(WG), lds, st, tp, sp, tq, sq, f, n, (kind == 0 && g_use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, first, end);
-        }
-    } else
-    hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), st, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
-                       tp, sp, tq, sq, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
+    if (side == Side::row)
+        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, tp, sp, tq, sq, f, n, (kind == 0 && g_use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
+    else
+        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), st, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
+                           tp, sp, tq, sq, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(tl_ctx->join[0], st));
     return BLSMI_OK;
 }
 // The two-pairing comparison of n tuples whose hashes h are on the device: 2-pair Miller loop, final exponentiation, == 1.
 // CompareTwoPairings(sig, G2One, h, pub) (g2pubs/bls.go:161)  /  CompareTwoPairings(G1One, sig, pub, h) (g1pubs/bls.go:167, 173)
-// sig_side: the signature side's Miller values are on their way into f (verify_sig_side_start); only with use_lat(n)
-int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_sigs, const void* d_inf_in, void* d_ok, i32* f, size_t n, hipStream_t s, const PrepKeys* prep = nullptr, bool sig_side = false) {
+// r: the call's route (route.h: verify_route); r.side != none: the signature side's Miller values are on their way into f (verify_sig_side_start)
+int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_sigs, const void* d_inf_in, void* d_ok, i32* f, size_t n, hipStream_t s, const VerifyRoute& r, const PrepKeys* prep = nullptr) {
     dim3 g(nblocks(n)), w(WG), gp((unsigned)((n + PT - 1) / PT));
-    if (sig_side) HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[0], 0));       // (also orders the side stream's copy of the signatures before the flag kernel below)
+    if (r.side != Side::none) HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[0], 0));       // (also orders the side stream's copy of the signatures before the flag kernel below)
     DBuf gathered;
-    if (prep && kind == 0 && prep_tables_serve(n)) {                       // both pairs read their lines: the generator's table and the key's
+    if (prep && r.tables) {                       // both pairs read their lines: the generator's table and the key's
         DBuf fl; HIPCHK(fl.alloc(n, s));
         hipLaunchKernelGGL(k_flag_prepared, g, w, 0, s, prep->tables, prep->idx, (const u8*)d_sigs, 24, (const u8*)d_inf_in, fl.as<u8>(), (int*)nullptr, n);
         prof_mark("k_miller2_prep_pair");
@@ -283,30 +234,30 @@ int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_
     const i32* pre_pair = pre ? g_gens.lines_pair : nullptr;               // ... in the limbs of the lane-pair / lane-quad kernels
     const u8* a1 = kind == 0 ? d_h : (const u8*)d_pks;
     const u8* b1 = kind == 0 ? (const u8*)d_pks : d_h;
-    if (sig_side && sig_side_row(kind, n)) {                        // lane-row layout, the signature side's Miller value already in f: the other pair's loop times it
+    if (r.side == Side::row) {                                             // lane-row layout, the signature side's Miller value already in f: the other pair's loop times it
         prof_mark("k_miller1m_row");
         hipLaunchKernelGGL(k_miller1m_row, dim3(rblocks(n)), w, 0, s, a1, (size_t)96, b1, (size_t)192, f, n);
         prof_mark("k_final_exp_is_one_row");
         hipLaunchKernelGGL(k_final_exp_is_one_row, dim3(rblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else if (sig_side) {                                                 // small call, the signature side already under way: one Miller loop, the product, the final exponentiation
+    } else if (r.side == Side::wave) {                                     // small call, the signature side already under way: one Miller loop, the product, the final exponentiation
         prof_mark("k_lat:verify1s");
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_VERIFY1S_OFFSET), s, (const u8*)g_gens.lat + LAT_VERIFY1S_OFFSET,
                            a1, (size_t)96, b1, (size_t)192, (const u8*)nullptr, (size_t)0, reinterpret_cast<const u8*>(f), n, (const u8*)d_inf, (u8*)d_ok, (u64*)nullptr, n);
-    } else if (use_lat(n)) {                                               // small call: one Verify per wave (k_lat.hip)
+    } else if (r.layout == Layout::wave) {                                 // small call: one Verify per wave (k_lat.hip)
         prof_mark("k_lat:verify2");
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_VERIFY2_OFFSET), s, (const u8*)g_gens.lat + LAT_VERIFY2_OFFSET,
                            a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, (const u8*)d_inf, (u8*)d_ok, (u64*)nullptr, n);
-    } else if (use_row(n)) {                                               // a few thousand tuples: sixteen lanes per tuple (k_pairing_row.hip)
+    } else if (r.layout == Layout::row) {                                  // a few thousand tuples: sixteen lanes per tuple (k_pairing_row.hip)
         prof_mark("k_miller2_row");
         hipLaunchKernelGGL(k_miller2_row, dim3(rblocks(n)), w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
         prof_mark("k_final_exp_is_one_row");
         hipLaunchKernelGGL(k_final_exp_is_one_row, dim3(rblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else if (use_quad(n)) {                                              // mid-size batch: four lanes per tuple (k_pairing_quad.hip)
+    } else if (r.layout == Layout::quad) {                                 // mid-size batch: four lanes per tuple (k_pairing_quad.hip)
         prof_mark("k_miller2_quad");
         hipLaunchKernelGGL(k_miller2_quad, dim3(qblocks(n)), w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
         prof_mark("k_final_exp_is_one_quad");
         hipLaunchKernelGGL(k_final_exp_is_one_quad, dim3(qblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else if (g_pair_layout) {
+    } else if (r.layout == Layout::pair) {
         prof_mark("k_miller2_pair");
         hipLaunchKernelGGL(k_miller2_pair, gp, w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
         prof_mark("k_final_exp_is_one_pair");
@@ -328,12 +279,12 @@ int verify_batch_dev(int kind, const void* d_msgs, const void* d_off, const void
     const Kind k = kind_of(kind);
     DBuf h, f;
     HIPCHK(h.alloc((size_t)k.h_bytes * n, s)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n, s));
-    const bool side = sig_side_wanted(kind, n) && !(prep && kind == 0 && prep_tables_serve(n));
-    if (side) { int rc = verify_sig_side_start(kind, const_cast<void*>(d_sigs), nullptr, f.as<i32>(), n, s); if (rc) return rc; }   // (after s: a caller's stream may still be producing the signatures)
-    int rc = hash_dev(kind, d_msgs, d_off, h.as<u8>(), n, s, true, nullptr, side && kind == 0 && sig_side_row(kind, n));
+    const VerifyRoute r = verify_route(kind, n, prep != nullptr, true, tune(), route_load(n));
+    if (r.side != Side::none) { int rc = verify_sig_side_start(kind, r.side, const_cast<void*>(d_sigs), nullptr, f.as<i32>(), n, s); if (rc) return rc; }   // (after s: a caller's stream may still be producing the signatures)
+    int rc = hash_dev(kind, d_msgs, d_off, h.as<u8>(), n, s, r.hash);
     if (rc) return rc;
     if (before_pair) HIPCHK(hipStreamWaitEvent(s, before_pair, 0));
-    rc = verify_pair_stage(kind, h.as<u8>(), d_pks, d_sigs, d_inf, d_ok, f.as<i32>(), n, s, prep, side);
+    rc = verify_pair_stage(kind, h.as<u8>(), d_pks, d_sigs, d_inf, d_ok, f.as<i32>(), n, s, r, prep);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     return BLSMI_OK;
@@ -360,18 +311,19 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
     DBuf h, f;
     HIPCHK(h.alloc((size_t)k.h_bytes * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
     // a small call: the signatures go first, on the side stream that runs their Miller loops beside the hash (verify_sig_side_start)
-    const bool side = sig_side_wanted(kind, n) && !(prep_tables && kind == 0 && prep_tables_serve(n));
-    if (side) { int rc = verify_sig_side_start(kind, ds.p, sigs, f.as<i32>(), n, nullptr, (fmt & FMT_SIG_JAC) != 0); if (rc) return rc; }
+    const VerifyRoute r = verify_route(kind, n, prep_tables != nullptr, true, tune(), route_load(n));
+    const bool side = r.side != Side::none;
+    if (side) { int rc = verify_sig_side_start(kind, r.side, ds.p, sigs, f.as<i32>(), n, nullptr, (fmt & FMT_SIG_JAC) != 0); if (rc) return rc; }
     if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream, true, nullptr, side && kind == 0 && sig_side_row(kind, n));
+    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream, r.hash);
     if (rc) return rc;
     if (prep_tables) { if (prep_idx) HIPCHK(hipMemcpyAsync(dp.p, prep_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, g_stream)); }
     else { rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); if (rc) return rc; }   // (in-memory points: ToAffine on the device, after the hash)
     if (!side) { rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, g_stream); if (rc) return rc; }
     if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, g_stream));
     const PrepKeys prep{prep_tables, prep_idx ? dp.as<u32>() : nullptr};
-    rc = verify_pair_stage(kind, h.as<u8>(), prep_tables ? nullptr : dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, g_stream, prep_tables ? &prep : nullptr, side);
+    rc = verify_pair_stage(kind, h.as<u8>(), prep_tables ? nullptr : dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, g_stream, r, prep_tables ? &prep : nullptr);
     if (rc) return rc;
     if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, g_stream, (const u8*)dok.as<u8>(), d_bitmap_slice, n);
     std::vector<uint8_t> tmp;
@@ -660,11 +612,12 @@ const uint64_t* dup_key() {
     } } key;
     return key.k;
 }
-bool has_duplicates(const uint8_t* msgs, const uint64_t* off, size_t n) {
+// force_sort: the "dup_force_sort" test hook -- the fallback path on every call
+bool has_duplicates(const uint8_t* msgs, const uint64_t* off, size_t n, bool force_sort) {
     if (n == 0) return false;
     if (n >= 0xffffffffull) return true;                                   // not representable: treat as failure
     for (size_t i = 0; i < n; i++) if (off[i + 1] == off[i]) return true; // bytes.Equal(m, nil) holds for an empty m
-    if (g_dup_force_sort.load(std::memory_order_relaxed)) return has_duplicates_sorted(msgs, off, n);   // test hook: the fallback path on every call
+    if (force_sort) return has_duplicates_sorted(msgs, off, n);
     const uint64_t* key = dup_key();
     size_t cap = 16;
     while (cap < 2 * n) cap <<= 1;
@@ -691,8 +644,8 @@ bool has_duplicates(const uint8_t* msgs, const uint64_t* off, size_t n) {
     return false;
 }
 // the same verdict; an allocation failure inside (a million-entry table) is reported instead of unwinding through the C ABI
-int has_duplicates_rc(const uint8_t* msgs, const uint64_t* off, size_t n, bool* dup) {
-    try { *dup = has_duplicates(msgs, off, n); return BLSMI_OK; }
+int has_duplicates_rc(const uint8_t* msgs, const uint64_t* off, size_t n, bool* dup, bool force_sort) {
+    try { *dup = has_duplicates(msgs, off, n, force_sort); return BLSMI_OK; }
     catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     catch (...) { return BLSMI_E_ARG; }
 }
@@ -709,20 +662,22 @@ int aggregate_shard_dev(int kind, const void* d_msgs, const void* d_off_or_domai
                         const std::function<int()>& after_hash = {}, const PrepKeys* prep = nullptr, bool g1_clear = true) {
     const Kind k = kind_of(kind);
     DBuf gathered;
-    if (prep && !(kind == 0 && prep_tables_serve_aggregate(n))) { int rc = prep_gather_keys(*prep, gathered, n, s); if (rc) return rc; d_pks = gathered.as<u8>(); prep = nullptr; }
+    const AggregateRoute r = aggregate_route(kind, n, prep != nullptr, g1_clear, tune(), route_load(n));   // the buffers are sized by the route the loops run by
+    if (prep && !r.tables) { int rc = prep_gather_keys(*prep, gathered, n, s); if (rc) return rc; d_pks = gathered.as<u8>(); prep = nullptr; }
     const size_t words = (size_t)12 * NL;
     DBuf h, fr0, fr1, flags, any;
-    const size_t nrec = (g_pair_layout && n > g_lat_max) ? (n + 1) / 2 : n;   // two tuples share a loop in k_miller1x2_pair
+    const size_t nrec = r.records;
     HIPCHK(h.alloc((size_t)k.h_bytes * n, s));
     HIPCHK(fr0.alloc(sizeof(i32) * words * nrec, s)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((nrec + 1) / 2), s)); HIPCHK(flags.alloc(n, s)); HIPCHK(any.alloc(sizeof(int), s));
     HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
-    int rc = hash_dev(kind, d_msgs, d_off_or_domain, h.as<u8>(), n, s, g1_clear, g1_clear ? nullptr : any.as<int>());   // *bad bit 1: a hash point the uncleared path does not cover
+    int rc = hash_dev(kind, d_msgs, d_off_or_domain, h.as<u8>(), n, s, r.hash, g1_clear, g1_clear ? nullptr : any.as<int>());   // *bad bit 1: a hash point the uncleared path does not cover
     if (rc) return rc;
     if (after_hash) { rc = after_hash(); if (rc) return rc; }
     if (prep) hipLaunchKernelGGL(k_flag_prepared, dim3(nblocks(n)), dim3(WG), 0, s, prep->tables, prep->idx, (const u8*)nullptr, 0, (const u8*)nullptr, flags.as<u8>(), any.as<int>(), n);
     else hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, d_pks, k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)nullptr, flags.as<u8>(), any.as<int>(), n);
     // Pairing(h_i, pk_i) (g2pubs) / Pairing(pk_i, h_i) (g1pubs): Miller loops only, then the product tree
-    size_t cur = launch_miller1(kind == 0 ? h.as<u8>() : d_pks, kind == 0 ? d_pks : h.as<u8>(), fr0.as<i32>(), n, s, prep);
+    launch_miller1(kind == 0 ? h.as<u8>() : d_pks, kind == 0 ? d_pks : h.as<u8>(), fr0.as<i32>(), n, s, r, prep);
+    size_t cur = nrec;
     i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
     while (cur > 1) {
         const size_t half = (cur + 1) / 2;
@@ -763,10 +718,7 @@ int aggregate_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain
 // exponentiation of the Miller product (program "powc12raw", 0.3 ms).  The verdict is the reference's; BLSMI_AGG_COFACTOR_POW=0 at start-up, or
 // blsmi_set_option("agg_cofactor_pow", 0), keeps the cleared hash points.
 constexpr size_t AGG_POW_MIN = 65536;
-inline bool agg_pow_wanted(int kind, size_t n) {
-    if (kind != 0 || n < AGG_POW_MIN || g_lat_max == 0) return false;
-    return g_agg_cofactor_pow.load(std::memory_order_relaxed);
-}
+inline bool agg_pow_wanted(int kind, size_t n, const Tuning& t) { return kind == 0 && n >= AGG_POW_MIN && t.lat_max != 0 && t.agg_cofactor_pow; }
 // d_prod (180 words, device representation) -> d_out = d_prod^(1 - x), on g_stream
 int aggregate_pow_c(const i32* d_prod, i32* d_out) {
     prof_mark("k_lat:powc12raw");
@@ -855,11 +807,12 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
     const size_t pk_in = rec_bytes(k.pk_bytes, fmt & FMT_PK_JAC);
     const size_t words = (size_t)12 * NL;
     const ShardPlan plan = plan_shards(n, 64);
-    const bool powc = !no_powc && agg_pow_wanted(kind, n);                 // hash points without their cofactor clearing, the product raised to 1 - x instead
+    const Tuning t = tuning_now();                                         // what holds across the shards' threads is decided here, once
+    const bool powc = !no_powc && agg_pow_wanted(kind, n, t);              // hash points without their cofactor clearing, the product raised to 1 - x instead
     check_dups = check_dups && n > 0;
     bool dup = false;
     if (check_dups && n <= DUP_INLINE_MAX) {                               // small: screened here, no thread, no device work
-        int rc = has_duplicates_rc(msgs, off_or_domain, n, &dup);
+        int rc = has_duplicates_rc(msgs, off_or_domain, n, &dup, t.dup_force_sort);
         if (rc) return rc;
         if (dup) return BLSMI_OK;
         check_dups = false;
@@ -877,7 +830,7 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
             if (rc) return rc;
             if (check_dups) { HIPCHK(hipMemcpyAsync(&dupflag, ddup.p, sizeof dupflag, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); }
         }
-        if (check_dups && g_dup_force_sort.load(std::memory_order_relaxed)) dupflag |= 2;     // test hook: take the fallback on every call
+        if (check_dups && t.dup_force_sort) dupflag |= 2;     // test hook: take the fallback on every call
         if (dupflag & 2) {                                                 // the device table gave up (k_util.hip): the reference's sort, on the host
             bool d = false;
             try { d = has_duplicates_sorted(msgs, off_or_domain, n); } catch (...) { return BLSMI_E_NOMEM; }
@@ -907,8 +860,8 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
     int dup_rc = BLSMI_OK;
     std::thread dup_thread;
     if (check_dups) {
-        try { dup_thread = std::thread([&] { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup); }); }
-        catch (...) { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup); }   // no thread to be had: screen here
+        try { dup_thread = std::thread([&] { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup, t.dup_force_sort); }); }
+        catch (...) { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup, t.dup_force_sort); }   // no thread to be had: screen here
     }
     std::vector<int> bad(plan.nshards, 0);
     rc = BLSMI_OK;
@@ -979,7 +932,7 @@ int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_doma
     *ok = 0;
     if ((fmt & FMT_SIG_JAC) ? jac_host_is_infinity(sig, k.sig_bytes) : all_zero(sig, k.sig_bytes)) return BLSMI_OK;
     const size_t words = (size_t)12 * NL;
-    const bool powc = !no_powc && agg_pow_wanted(kind, n);
+    const bool powc = !no_powc && agg_pow_wanted(kind, n, tune());
     DBuf prod, ddup; HIPCHK(prod.alloc(sizeof(i32) * words)); HIPCHK(ddup.alloc(sizeof(int)));
     SigSide ss;
     { int rc = sig_side_start(kind, sig, ss, fmt); if (rc) return rc; }
@@ -994,7 +947,7 @@ int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_doma
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(g_stream));
     }
-    if (check_dups && kind != 2 && n && g_dup_force_sort.load(std::memory_order_relaxed)) dupflag |= 2;   // test hook: take the fallback on every call
+    if (check_dups && kind != 2 && n && tune().dup_force_sort) dupflag |= 2;   // test hook: take the fallback on every call
     if (dupflag & 2) {                                                     // the device table gave up (k_util.hip): fetch the messages, the reference's sort on the host
         try {
             std::vector<uint64_t> off(n + 1);
@@ -1084,7 +1037,7 @@ int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, siz
     HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dout.alloc((size_t)OB * n));
     if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
-    int rc = hash_dev(kernel_kind, dm.p, doff.p, dout.as<u8>(), n, g_stream);
+    int rc = hash_dev(kernel_kind, dm.p, doff.p, dout.as<u8>(), n, g_stream, hash_route_alone(kernel_kind, n));
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1094,7 +1047,7 @@ int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, siz
 // group 1 / 2 = G1 / G2.  Small batches take the subgroup test (check == 1) as a level program of the latency path.
 int decompress_dev(int group, const u8* d_in, int check, u8* d_out, u8* d_inf, u8* d_err, size_t n, hipStream_t s) {
     dim3 g(nblocks(n)), w(WG);
-    const bool lat = check == 1 && n <= g_lat_max;
+    const bool lat = check == 1 && n <= tune().lat_max;
     const int kcheck = lat ? 0 : check;
     const size_t wave_max = g_env.swu_wave_max;
     const bool waves = kcheck == 0 && n <= wave_max;                       // the smallest calls: one wave per point, its square root with one limb per lane (fp_row.cuh)
@@ -1158,7 +1111,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     // 131 072 tuples: their one-lane kernels put one or two waves on a SIMD and the kernels with 256 registers a lane share it
     // (BLSMI_SIDE_MAX; a larger batch fills the chip by itself and stays on one stream).
     const size_t side_max = g_env.side_max;
-    const bool side = n <= std::max((size_t)g_lat_max, side_max);
+    const bool side = n <= std::max(tune().lat_max, side_max);
     hipStream_t spk = g_stream, ssg = g_stream;
     if (side) {
         HIPCHK(tl_ctx->ensure_aux());
@@ -1175,7 +1128,8 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     const Kind kk = kind_of(kind);
     DBuf h, f;
     HIPCHK(h.alloc((size_t)kk.h_bytes * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream);          // on the main stream, beside the decompressions
+    const VerifyRoute r = verify_route(kind, n, false, false, tune(), route_load(n));   // (no signature side: the signatures are still being decompressed)
+    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream, r.hash);  // on the main stream, beside the decompressions
     if (rc) return rc;
     if (side) {
         HIPCHK(hipEventRecord(tl_ctx->join[0], spk)); HIPCHK(hipEventRecord(tl_ctx->join[1], ssg));
@@ -1183,7 +1137,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     }
     hipLaunchKernelGGL(k_merge_flags, g, w, 0, g_stream, ipk.as<u8>(), epk.as<u8>(), isg.as<u8>(), esg.as<u8>(), dfl.as<u8>(), n);
     HIPCHK(hipGetLastError());
-    rc = verify_pair_stage(kind, h.as<u8>(), dp.p, ds.p, dfl.p, dok.p, f.as<i32>(), n, g_stream);
+    rc = verify_pair_stage(kind, h.as<u8>(), dp.p, ds.p, dfl.p, dok.p, f.as<i32>(), n, g_stream, r);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, g_stream));
     if (err_pk) HIPCHK(hipMemcpyAsync(err_pk, epk.p, n, hipMemcpyDeviceToHost, g_stream));
@@ -1221,7 +1175,7 @@ static int aggregate_partial_host(int kind, const uint8_t* msgs, const uint64_t*
     else {
         // a large g2pubs shard pairs the hash points before their cofactor clearing and raises ITS product to 1 - x (agg_pow_wanted): the
         // value differs from prod ML(H(m_i), pk_i) only by what the final exponentiation removes, which is all a partial product is used for
-        bool powc = agg_pow_wanted(kind, n);
+        bool powc = agg_pow_wanted(kind, n, tune());
         int rc = aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), &b, nullptr, !powc);
         if (rc) return rc;
         if (b & 2) { powc = false; b = 0; rc = aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), &b, nullptr, true); if (rc) return rc; }   // a message the uncleared path does not cover: cleared hash points
@@ -1371,7 +1325,7 @@ int sign_host(int kind, const uint8_t* msgs, const void* off_or_domain, size_t o
             HIPCHK(hipMemcpyAsync(doff.p, rel.data(), sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));                        // (rel goes out of scope)
         }
-        int rc = hash_dev(kind, dm.p, doff.p, dh.as<u8>(), m, g_stream);
+        int rc = hash_dev(kind, dm.p, doff.p, dh.as<u8>(), m, g_stream, hash_route_alone(kind, m));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(dk.p, sks + 32 * lo, 32 * m, hipMemcpyHostToDevice, g_stream));   // the keys travel while the hash runs
         if (OB == 96) rc = mul_dev_core<96>(k_g1_mul, dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
@@ -1567,9 +1521,10 @@ BLSMI_API int blsmi_pairing_batch_prepared_dev(const void* d_g1, const void* d_p
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
     const PrepKeys prep{(const i32*)d_prepared, (const u32*)d_key_idx};
-    if (!(g_pair_layout && n > g_lat_max) || use_quad(n)) {                // small call: the latency program on the keys' affine records; mid-size: the quad kernels on them
+    const Layout lay = pairing_layout(0, n, tune(), route_load(n));
+    if (!prepared_tables_serve(Call::pairing, lay, tune())) {              // the layouts without table-reading kernels run on the keys' affine records
         DBuf pk; int rc = prep_gather_keys(prep, pk, n, g_stream); if (rc) return rc;
-        return pairing_dev(d_g1, pk.p, d_out, n, g_stream, 0);
+        return pairing_dev(d_g1, pk.p, d_out, n, g_stream, 0, lay);
     }
     HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
     i32* f = reinterpret_cast<i32*>(g_ws.p);

@@ -128,10 +128,11 @@ int blsmi_prefer_cpu(int shape, size_t n);
  * BLSMI_COMBINE_MAX / _WAIT_US / _INFLIGHT / _DEBUG (merging of concurrent one-tuple Verify calls).  A/B switches between code paths with
  * identical results: BLSMI_LAYOUT, BLSMI_GEN_LINES, BLSMI_HASH_G1_SPLIT, BLSMI_HASH_G2_PAIR, BLSMI_HASH_G2_PAIR_REDO_EVERY, BLSMI_COFAC2_PAIR,
  * BLSMI_SWU_WAVE_MAX, BLSMI_SIG_SIDE_MAX, BLSMI_SIDE_MAX, BLSMI_FIXED_WAVE_MAX, BLSMI_MSM_BUCKET_MIN, and the ones that can ALSO be
- * switched while running (atomically; a call in flight sees the old or the new value), through blsmi_set_option(name, value):
+ * switched while running through blsmi_set_option(name, value) (as the thresholds above: every call reads every option ONCE, when it starts,
+ * so a change applies to the calls that start after it and never to part of a call in flight):
  *   "agg_cofactor_pow" (BLSMI_AGG_COFACTOR_POW, default 1), "msm_sort" (BLSMI_MSM_SORT, default 1), "dup_force_sort" (BLSMI_DUP_FORCE_SORT, 0),
  *   "lat_rolled" (BLSMI_LAT_ROLLED, default 1; 0: small Pairing calls run the straight-line copy of their level program instead of the one
- *   whose squaring runs are loops), "row_side" (BLSMI_ROW_SIDE, default 1: a g1pubs Verify in the row layout runs its signature side beside the hash),
+ *   whose squaring runs are loops), "row_side" (BLSMI_ROW_SIDE, default 1: a Verify in the row layout runs its signature side beside the hash -- g1pubs, and g2pubs with "row_side_g2pubs"),
  *   "hash_row_min" / "hash_row_max" (defaults 2048 / 4096; no environment name): HashG2 of that many messages clears its cofactor sixteen lanes per message
  *   (k_hash_g2_front + k_clear_h2_row, 2.9 -> 2.2 ms for 3 072 messages) instead of a lane pair per message; "hash_quad_min" / "hash_quad_max" (4097 / 16384):
  *   four lanes per message (k_clear_h2_quad, 3.0 -> 2.4 ms for 16 384 messages: 16 384 g1pubs verifies 10.1 -> 9.3 ms); max 0: never.
@@ -139,9 +140,8 @@ int blsmi_prefer_cpu(int shape, size_t n);
  *   over the two above where its range covers the count: 4 096 g1pubs verifies 4.45 -> 4.05 ms, 6 144: 6.54 -> 5.94).
  *   "swu_row_max" (4096): the SWU maps of HashG1 / HashG2 of BLSMI_SWU_WAVE_MAX < n <= swu_row_max messages run a row of sixteen lanes per map (k_swu_g?_rows:
  *   k_swu_g1 0.54 -> 0.24 ms up to 2 048 messages) unless the signature side's kernel runs beside the hash; 0: never.
- *   "row_side_g2pubs" (1): a g2pubs Verify in the row layout runs its signature side beside the hash as g1pubs does ("row_side"); "row_side_piece" (0 = one launch): the side
- *   kernel in launches of that many tuples (measured slower: a piece of 2 048 tuples takes the time of a piece of 4 096); "row_side_lds" (0): bytes of unused LDS per
- *   workgroup of that kernel when the call has more than 4 096 tuples (40960 keeps a wave slot of every SIMD free for the hash; measured slower too).
+ *   "row_side_g2pubs" (1): g2pubs too (its side kernel over the generator's prepared lines, the hash's maps a lane each beside it: 4 096 g2pubs verifies
+ *   3.23 against 3.55 ms in the two-pair loop, 8 192: 5.37 against 5.71; 0: the two-pair loop).
  *   "hash_g1_quad_min" / "hash_g1_quad_max" (1280 / 32768): HashG1 of that many messages runs its tail -- sum, 11-isogeny, cofactor -- four lanes per message
  *   (k_hash_g1_finish_quad: 0.96 -> 0.48 ms; 4 096 g2pubs verifies 4.35 -> 3.78 ms, 16 384: 8.10 -> 7.57 ms).
  * Layout by what the DEVICE carries (blsmi 0.6): the hand-overs above are a lone caller's.  Calls that arrive together share the chip, and

@@ -145,7 +145,7 @@ def _g1pubs_tuples(n, seed, every):
 
 @pytest.mark.parametrize("side", [1, 0])
 @pytest.mark.parametrize("group", ["g2pubs", "g1pubs"])
-def test_verify_in_the_row_layout(eng, group, side):
+def test_row_layout_verify_verdicts(eng, group, side):
     """Verify of both packages forced into the row kernels: the oracle's verdict table, ragged sizes.  side = 1 (the default): the signature side's
     Miller loop on a side stream beside the hash (k_miller1s_row; g2pubs: over the generator's prepared lines), then k_miller1m_row times that value;
     side = 0: one two-pair loop (k_miller2_row).  k_final_exp_is_one_row either way"""
@@ -158,14 +158,11 @@ def test_verify_in_the_row_layout(eng, group, side):
         for m in (1, 4, 5, 13):
             ok, _ = fn(msgs[:m], b"".join(pks[:m]), b"".join(sigs[:m]))
             assert list(ok) == expect[:m], (group, m, side)
-        eng.set_option("row_side_piece", 4)                                  # the side kernel in pieces: 4 + 4 + 4 + 1 tuples
-        ok, _ = fn(msgs, b"".join(pks), b"".join(sigs))
-        assert list(ok) == expect, (group, side, "pieces")
     finally:
-        eng.set_row_threshold(*eng.ROW_DEFAULT); eng.set_option("row_side", 1); eng.set_option("row_side_piece", 0)
+        eng.set_row_threshold(*eng.ROW_DEFAULT); eng.set_option("row_side", 1)
 
 
-def test_row_layout_at_its_design_size(eng):
+def test_row_layout_pairings_and_verifies_at_4096(eng):
     """4 096 pairings (1 024 waves: one per SIMD) on the DEFAULT thresholds take the row kernels: every record against the lane-pair
     kernels' output, a spread sample against the oracle; 4 096 g2pubs verifies with a corruption schedule likewise"""
     n = 4096
@@ -206,17 +203,15 @@ def test_row_layout_at_its_design_size(eng):
     prof = bench.read_profile(lib)
     assert "k_miller1m_row" in prof and "k_final_exp_is_one_row" in prof, prof     # (the signature side beside the hash: verify_host.inc, verify_sig_side_start)
     assert list(ok) == expect
-    try:                                                                    # the side kernel in ragged pieces (as a call of more than 4 096 tuples runs it), and the two-pair loop
-        eng.set_option("row_side_piece", 1000)
-        ok2, _ = eng.g2pubs_verify_batch(msgs, allpk.reshape(-1), sigs.reshape(-1))
+    try:                                                                    # the two-pair loop
         eng.set_option("row_side_g2pubs", 0)
         lib.blsmi_set_profiling(1); bench.read_profile(lib)
         ok3, _ = eng.g2pubs_verify_batch(msgs, allpk.reshape(-1), sigs.reshape(-1))
         lib.blsmi_set_profiling(0)
         assert "k_miller2_row" in bench.read_profile(lib)
     finally:
-        eng.set_option("row_side_piece", 0); eng.set_option("row_side_g2pubs", 1)
-    assert list(ok2) == expect and list(ok3) == expect
+        eng.set_option("row_side_g2pubs", 1)
+    assert list(ok3) == expect
     for i in (0, 6, 4095):
         assert RC.g2pubs.verify(msgs[i], allpk[i].tobytes(), sigs[i].tobytes()) == expect[i]
 
@@ -408,3 +403,57 @@ def test_hash_g1_tail_four_lanes_per_message(eng):
     want, _ = finish(1)
     got, redone = finish(2)
     assert redone == 2 and np.array_equal(got, want)
+
+
+def test_options_switched_while_calls_run(eng):
+    """A call reads every option once, when it starts (route.h; blsmi.hip: CtxLease): one thread flips the latency threshold (8 192 <-> 16 384),
+    the row layout (default <-> off) and "row_side" while another makes 21 calls -- g1pubs and g2pubs Verify of 3 000 tuples with every 7th
+    key wrong, g2pubs VerifyAggregate of 10 000 signers (sized and run by one answer) -- and every verdict is the expected one"""
+    import threading
+    xs = P.XORShift(6111)
+    nk = 64
+    skb = b"".join(sk_bytes(xs) for _ in range(nk))
+    n = 3000
+    sets = {}
+    for group in ("g2pubs", "g1pubs"):
+        msgs = [b"switched %s %d" % (group.encode(), i) for i in range(n)]
+        if group == "g2pubs":
+            pk, _ = eng.g2_mul_generator_batch(skb, nk); h = eng.hash_g1_batch(msgs); sg, _ = eng.g1_mul_batch(h.reshape(-1), (skb * (n // nk + 1))[:32 * n], n)
+        else:
+            pk, _ = eng.g1_mul_generator_batch(skb, nk); h = eng.hash_g2_batch(msgs); sg, _ = eng.g2_mul_batch(h.reshape(-1), (skb * (n // nk + 1))[:32 * n], n)
+        allpk = np.stack([pk[(i + (1 if i % 7 == 6 else 0)) % nk] for i in range(n)])
+        sets[group] = (msgs, allpk.reshape(-1).copy(), sg.reshape(-1).copy(), [i % 7 != 6 for i in range(n)])
+    na = 10000
+    amsgs = [b"switched aggregate %d" % i for i in range(na)]
+    pk, _ = eng.g2_mul_generator_batch(skb, nk); h = eng.hash_g1_batch(amsgs); sg, _ = eng.g1_mul_batch(h.reshape(-1), (skb * (na // nk + 1))[:32 * na], na)
+    apk = np.ascontiguousarray(np.stack([pk[i % nk] for i in range(na)]))
+    agg = eng.g1_sum(sg.reshape(-1), na)
+    done = threading.Event()
+    flips = [0]
+
+    def flip():
+        while not done.is_set():
+            k = flips[0]
+            eng.set_latency_threshold(16384 if k % 2 else 8192)
+            eng.set_row_threshold(*(eng.ROW_DEFAULT if k % 3 else (0, 0)))
+            eng.set_option("row_side", k % 5 != 0)
+            flips[0] += 1
+            done.wait(0.0003)
+    got, want = [], []
+    t = threading.Thread(target=flip)
+    t.start()
+    try:
+        for i in range(21):
+            if i % 3 == 2:
+                got.append(eng.g2pubs_verify_aggregate(amsgs, apk.reshape(-1), agg)); want.append(True)
+            else:
+                msgs, pks, sigs, expect = sets["g2pubs" if i % 3 == 0 else "g1pubs"]
+                fn = eng.g2pubs_verify_batch if i % 3 == 0 else eng.g1pubs_verify_batch
+                ok, _ = fn(msgs, pks, sigs)
+                got.append(list(ok)); want.append(expect)
+    finally:
+        done.set(); t.join()
+        eng.set_latency_threshold(8192); eng.set_row_threshold(*eng.ROW_DEFAULT); eng.set_option("row_side", 1)
+    assert flips[0] > 21
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, i
