@@ -5,19 +5,23 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  A step is o
 synthetic input resident in HBM: BASELINE.json configs[1] -- 65 536 independent pairings (Miller loop + final
 exponentiation, the reference's bls.Pairing) per GPU.  W untimed steps, then exactly K timed steps bracketed by barrier +
 synchronize on both sides, MAX over ranks, one JSON line from rank 0.  Units shard across GPUs with no data-path collective
-(weak scaling: 64k pairings per GPU).  After the timed region the output is compared with the oracle and the run FAILS on a
-mismatch.  `--dump-outputs DIR` writes that output of the last timed step to DIR/*.npy first (dump_outputs); the inputs are seeded, so two
-builds run with the same arguments can be compared output for output.
+(weak scaling: 64k pairings per GPU).  `--dump-outputs DIR` writes the output of the last timed step to DIR/*.npy (dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the line (its roofline and valu objects
+come from the timed steps' own kernel events and the committed counter files, no run of their own).  `--full` adds everything else,
+after the timed region: the parity gate (rows of the output against the oracle; the run FAILS on a mismatch), the CPU baselines,
+the other BASELINE configs and their rooflines, the mid-size batches, the split host entry points and the reference shapes.
 
 Two launch styles, same numbers at N = 1:
   * under torch.distributed.run (RANK / WORLD_SIZE in the environment): one process per GPU, RCCL through torch.distributed;
   * plain `python bench.py --gpus N`: ONE process drives N devices through the library (blsmi_init_devices(N)) -- the
     deployment the Go API implies (one process, one call, g2pubs/bls.go:159, 240).  The headline step runs one resident
-    65 536-pairing batch per device concurrently (blsmi_pairing_batch_dev routes by buffer ownership); `inlibrary_bench`
-    times the split HOST entry points -- N x 65 536 pairings, N x 65 536 verifies with the library's own ncclAllReduce of
-    the bitmap inside every timed call, and the 2^20-signature VerifyAggregate with its ncclAllGather of partial products.
+    65 536-pairing batch per device concurrently (blsmi_pairing_batch_dev routes by buffer ownership); with --full,
+    `inlibrary_bench` times the split HOST entry points -- N x 65 536 pairings, N x 65 536 verifies with the library's own
+    ncclAllReduce of the bitmap inside every timed call, and the 2^20-signature VerifyAggregate with its ncclAllGather of partial products.
 
-Every BASELINE config has an entry under `configs` (value, roofline of its dominant kernel, CPU baseline of the same shape):
+With --full, every BASELINE config has an entry under `configs` (value, roofline of its dominant kernel, CPU baseline of the same shape):
   configs[0]  1 000 g2pubs.Verify tuples on the CPU restatement of the reference (plumbing), the GPU verdicts beside it
   configs[1]  the headline (65 536 pairings per GPU)
   configs[2]  2^20-point G1 and G2 scalar multiplication and MSM, inputs resident (blsmi_g*_mul_batch_dev / _msm_dev)
@@ -448,7 +452,8 @@ def compact_line(d, detail_file=None):
     v = d.get("valu") or {}
     line["valu"] = _pick(v, ("frac", "frac_mix", "lane_instructions_per_pairing", "achieved", "peak", "unit"))
     line["counters"] = _pick(d.get("counters", {}), ("file", "stale"))
-    line["self_check"] = _pick(d.get("self_check", {}), ("rows_per_device", "passed"))
+    if "self_check" in d:
+        line["self_check"] = _pick(d["self_check"], ("rows_per_device", "passed"))
     line["configs"] = compact_configs(d)
     vb = d.get("verify_bench")
     if isinstance(vb, dict) and "error" not in vb:
@@ -944,8 +949,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairings", type=int, default=PAIRINGS_PER_GPU, help="pairings per GPU per step")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the parity gate against the oracle, the CPU baselines and every other "
+                                                        "leg (the --no-* options below leave parts of that out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify-extra", action="store_true", help="headline only: skip every other leg")
+    ap.add_argument("--no-verify-extra", action="store_true", help="with --full: skip every leg but the parity gate and the headline's CPU baseline")
     ap.add_argument("--no-aggregate", action="store_true")
     ap.add_argument("--no-ref-shapes", action="store_true")
     ap.add_argument("--no-msm", action="store_true")
@@ -1006,7 +1013,7 @@ def main():
     lib = _native.load()
     E.engine, E.lib = engine, lib
     E.ctr = profile_counters()
-    E.cpu = (world == 1 and single_process_devices == 1 and not args.no_cpu_baseline)
+    E.cpu = (args.full and world == 1 and single_process_devices == 1 and not args.no_cpu_baseline)
     n = args.pairings
     ndev = len(E.devs)
 
@@ -1055,22 +1062,25 @@ def main():
     if args.dump_outputs and rank == 0:                                    # before the parity gate: a build that fails it still leaves its outputs
         dump_outputs(args.dump_outputs, bufs[0][2])
 
-    # parity gate, outside the timed region, on every rank and device: a fast kernel with different results is not a result
-    from oracle import refcpu as RC
-    # one whole workgroup's rows (the first 64 tuples) + 8 rows spread over the batch; the full 65 536 rows: tests/test_gpu_fullsize.py
-    idx = sorted((set(range(64)) | {64, n // 3, n // 2, n // 2 + 1, n - 130, n - 65, n - 2, n - 1}) & set(range(n)))
-    want = RC.pairing_batch(g1[idx].tobytes(), g2[idx].tobytes(), len(idx))
-    good, bad_at = True, None
-    for di, (_, _, o) in enumerate(bufs):
-        got = o[idx].cpu().numpy().view(np.uint64)
-        if not np.array_equal(got, want):
-            good, bad_at = False, (di, [idx[k] for k in range(len(idx)) if not np.array_equal(got[k], want[k])][:4])
-    flag = torch.tensor([0 if good else 1], dtype=torch.int32, device=E.dev)
-    if E.use_dist:
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-    if int(flag.item()):
-        print("bench.py: SELF-CHECK FAILED: device output differs from the oracle's Pairing() (rank %d, device/row %s)" % (rank, bad_at), file=sys.stderr)
-        sys.exit(3)
+    self_check = None
+    if args.full:
+        # parity gate, outside the timed region, on every rank and device: a fast kernel with different results is not a result
+        from oracle import refcpu as RC
+        # one whole workgroup's rows (the first 64 tuples) + 8 rows spread over the batch; the full 65 536 rows: tests/test_gpu_fullsize.py
+        idx = sorted((set(range(64)) | {64, n // 3, n // 2, n // 2 + 1, n - 130, n - 65, n - 2, n - 1}) & set(range(n)))
+        want = RC.pairing_batch(g1[idx].tobytes(), g2[idx].tobytes(), len(idx))
+        good, bad_at = True, None
+        for di, (_, _, o) in enumerate(bufs):
+            got = o[idx].cpu().numpy().view(np.uint64)
+            if not np.array_equal(got, want):
+                good, bad_at = False, (di, [idx[k] for k in range(len(idx)) if not np.array_equal(got[k], want[k])][:4])
+        flag = torch.tensor([0 if good else 1], dtype=torch.int32, device=E.dev)
+        if E.use_dist:
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        if int(flag.item()):
+            print("bench.py: SELF-CHECK FAILED: device output differs from the oracle's Pairing() (rank %d, device/row %s)" % (rank, bad_at), file=sys.stderr)
+            sys.exit(3)
+        self_check = {"rows_per_device": len(idx), "against": "oracle Pairing() (oracle/refcpu.c), bit-exact 576-byte Fq12", "passed": True}
     checksum = int(bufs[0][2][::997].sum().item()) & 0xffffffff
 
     extras = {}
@@ -1099,9 +1109,9 @@ def main():
         return {"pairings_per_s": round(n * args.steps / dtp, 1), "ms_per_step": round(dtp / args.steps * 1e3, 3), "prepare_ms_once": round(t_prep * 1e3, 3),
                 "prepare_points_per_s": round(n / t_prep, 1), "roofline": roofline_of(profiled(lib, stp), n, BYTES["pairing"], E.ctr, lambda k: 2 * n),
                 "note": "G2AffineToPrepared once (blsmi_g2_prepare_batch_dev, the reference's BenchmarkG2Prepare shape), then Pairing over the resident tables; same Fq12 bits as the headline"}
-    if rank == 0 and ndev == 1 and world == 1 and not args.no_verify_extra:
+    if args.full and rank == 0 and ndev == 1 and world == 1 and not args.no_verify_extra:
         leg("pairing_prepared", pairing_prepared_leg)
-    if not args.no_verify_extra:
+    if args.full and not args.no_verify_extra:
         if ndev == 1:                                                      # rank style (or one device): all ranks take part in the collectives
             leg("verify_bench", lambda: verify_bench(E))
             if not args.no_aggregate:
@@ -1174,7 +1184,6 @@ def main():
             "config": {"workload": "configs[1]: %d independent pairings (Miller loop + final exponentiation = bls.Pairing) per GPU per step, inputs resident in HBM, output bit-exact Fq12" % n,
                        "pairings_per_gpu": n, "parallelism": "shard%d" % total_gpus,
                        "layout": "one tuple per lane" if suffix == "" else "lane pair per tuple (one Fq2 coefficient per lane), 2 waves/SIMD"},
-            "self_check": {"rows_per_device": len(idx), "against": "oracle Pairing() (oracle/refcpu.c), bit-exact 576-byte Fq12", "passed": True},
             "roofline": roof,
             "valu": {"bound": "int32 VALU issue (v_mad_i64_i32): %d SIMDs x %d lanes / %.0f cycles x %.1f GHz" % (SIMDS, LANES, CYCLES_PER_VALU, CLOCK_GHZ),
                      "lane_instructions_per_pairing": None if lane_instr is None else round(lane_instr),
@@ -1192,8 +1201,10 @@ def main():
                          "note": "traffic / VALU counts are read from this committed rocprofv3 PMC round; stale = a kernel source changed since it was taken"},
             "checksum": checksum,
         }
+        if self_check:
+            line["self_check"] = self_check
         line.update(extras)
-        if world == 1 and ndev == 1 and not args.no_verify_extra and not args.no_ref_shapes:
+        if args.full and world == 1 and ndev == 1 and not args.no_verify_extra and not args.no_ref_shapes:
             try:
                 from tools import reference_shapes
                 line["reference_shapes"] = reference_shapes.run(engine)

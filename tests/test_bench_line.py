@@ -1,6 +1,7 @@
-"""bench.py's stdout contract: ONE JSON line the driver can keep whole (< 4 KB), with the headline, its roofline and CPU baseline
-and five compact config entries; everything else goes to bench_detail.json.  The formatter is exercised here with synthetic legs
-(worst-case long strings and kernel lists); the -m gpu test runs the real command and parses its last stdout line."""
+"""bench.py's stdout contract: ONE JSON line the driver can keep whole (< 4 KB), with the headline and its roofline and, with --full,
+the CPU baseline and five compact config entries; everything else goes to bench_detail.json.  The formatter is exercised here with
+synthetic legs (worst-case long strings and kernel lists); the -m gpu tests run the real command, plain and --full, and parse its last
+stdout line."""
 import json
 import os
 import subprocess
@@ -100,6 +101,23 @@ def test_line_of_a_multi_device_run_names_the_collective_leg():
     assert len(json.dumps(line, separators=(",", ":"))) < 4096
 
 
+# what only `bench.py --full` runs and records
+FULL_ONLY = ("self_check", "cpu_baseline", "pairing_prepared", "verify_bench", "aggregate_bench", "msm_bench", "g2pubs_aggregate_dev_bench",
+             "g1pubs_aggregate_bench", "config0", "mid_batches", "inlibrary_bench", "reference_shapes")
+
+
+def test_line_of_a_plain_run_carries_the_headline_alone():
+    d = _detail()
+    for k in FULL_ONLY:
+        d.pop(k)
+    line = bench.compact_line(d, "bench_detail.json")
+    back = json.loads(json.dumps(line, separators=(",", ":")))
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline", "valu", "counters"):
+        assert k in back, k
+    assert list(back["configs"]) == ["1"] and back["configs"]["1"]["value"] == d["value"]
+    assert not set(FULL_ONLY) & set(back) and "leg_errors" not in back
+
+
 def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
     """--dump-outputs: the (n, 72) uint64 Fq12 rows come back exactly from the float64 32-bit halves; a batch larger than DUMP_ROWS is
     sampled with a fixed seed (the same rows every run), and the files stay far below 64 MB"""
@@ -125,12 +143,12 @@ def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_command_prints_one_parsable_line(tmp_path):
-    """the driver's command at its smallest: the LAST stdout line parses, is < 4 KB and names every config; --dump-outputs leaves the last
-    timed step's results"""
+    """the driver's command at its smallest, with --full: the LAST stdout line parses, is < 4 KB and names every config; --dump-outputs
+    leaves the last timed step's results"""
     import numpy as np
     env = dict(os.environ)
     dump = tmp_path / "outputs"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
     assert len(lines) == 1, "stdout must carry exactly one line, got %d" % len(lines)
@@ -152,15 +170,36 @@ def test_bench_command_prints_one_parsable_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_command_runs_the_headline_alone(tmp_path):
+    """the command without --full: the same headline line and dump, and nothing that only --full runs (parity gate, CPU baselines, other legs)"""
+    import numpy as np
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=dict(os.environ), cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    j = json.loads(lines[0])
+    assert j["metric"].startswith("BLS12-381 pairings/sec") and j["unit"] == "pairings/s" and j["higher_is_better"] is True and j["dtype"].startswith("int32")
+    assert j["value"] > 1e6 and j["steps"] == 2 and j["warmup"] == 1 and j["n_gpus"] == 1
+    assert abs(j["value"] - 65536 / (j["ms_per_step"] * 1e-3)) / j["value"] < 0.01
+    assert j["roofline"]["kernel"].startswith("k_") and j["roofline"]["kernel_ms"] > 0
+    assert list(j["configs"]) == ["1"] and "leg_errors" not in j
+    detail = json.load(open(os.path.join(ROOT, j["detail"])))
+    assert detail["value"] == j["value"] and not set(FULL_ONLY) & set(detail)
+    w, r = np.load(dump / "pairing_fq12.npy"), np.load(dump / "pairing_rows.npy")
+    assert w.shape == (bench.DUMP_ROWS, 144) and r.shape == (bench.DUMP_ROWS,) and w.any()
+
+
+@pytest.mark.gpu
 def test_two_logical_devices_through_the_bench_command():
-    """Multi-device readiness without the hardware: `python bench.py --gpus 2` as the driver would run it on an N-GPU node,
+    """Multi-device readiness without the hardware: `python bench.py --full --gpus 2` as the driver would run it on an N-GPU node,
     on ONE GPU under the BLSMI_DEVICE_ALIAS test hook -- two logical devices behind the C ABI, the headline step on both, the split host entry
     points with the bitmap exchange, the sharded 2^20-signature VerifyAggregate with its partial-product exchange.  The line must parse and say
     that these are logical devices (no scaling curve is claimed)."""
     env = dict(os.environ)
     env["BLSMI_DEVICE_ALIAS"] = "0,0"
     env.pop("BLSMI_SHARDS", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
     assert len(lines) == 1 and len(lines[0]) < 4096

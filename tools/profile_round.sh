@@ -1,5 +1,5 @@
 #!/bin/bash
-# Reproduces the rocprofv3 evidence under profiles/: per-kernel durations of the default bench.py run -- every leg, i.e. every
+# Reproduces the rocprofv3 evidence under profiles/: per-kernel durations of the bench.py --full run -- every leg, i.e. every
 # BASELINE config -- (--kernel-trace --stats) and, in separate passes as the MI355X guide prescribes, the HBM traffic and SQ
 # counters of the same command.
 # usage (on the GPU box, from the repo root): tools/profile_round.sh <tag> [commit]      e.g. r03a 3271d4e
@@ -9,7 +9,7 @@ TAG=${1:-r03zh}
 export BLSMI_COMMIT=${2:-unknown}
 R=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-ref-shapes"
+B="python $R/bench.py --full --no-cpu-baseline --no-ref-shapes"
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$TAG -o kt -- $B --steps 3 --warmup 1 > $R/gpurun_out/${TAG}_bench_stdout.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $R/gpurun_out/pmc_fetch_$TAG -o pmc -- $B --steps 2 --warmup 0 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $R/gpurun_out/pmc_write_$TAG -o pmc -- $B --steps 2 --warmup 0 > /dev/null 2>&1
