@@ -26,6 +26,10 @@
 #include <atomic>
 #include <thread>
 #include <random>
+#include <cerrno>
+#include <fcntl.h>
+#include <unistd.h>
+#include <sys/syscall.h>
 
 // The level programs of the latency path (gen_lat.py -> lat_programs.bin, 19 MB of 32-byte job descriptors), embedded in the host
 // object zlib-compressed (lat_programs.z, 1.3 MB) and inflated once when the library initialises.
@@ -63,7 +67,7 @@ std::mutex g_coll_mu;
 std::condition_variable g_cv;          // a context was released (lease waiters and shutdown both wait here: notify_all)
 bool g_pair_layout = true;              // lane-pair pairing kernels (two lanes per tuple); BLSMI_LAYOUT=single for one tuple per lane
 bool g_ready = false;
-char g_version[200] = "blsmi 0.7 (uninitialised)";
+char g_version[200] = "blsmi 0.8 (uninitialised)";
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "blsmi: %s failed: %s\n", #x, hipGetErrorString(e_)); return BLSMI_E_HIP; } } while (0)
 
@@ -357,11 +361,12 @@ std::atomic<bool> g_agg_cofactor_pow{Tuning{}.agg_cofactor_pow};    // BLSMI_AGG
 std::atomic<bool> g_msm_sort{Tuning{}.msm_sort};            // BLSMI_MSM_SORT / blsmi_set_option("msm_sort")
 std::atomic<bool> g_lat_rolled{Tuning{}.lat_rolled};          // BLSMI_LAT_ROLLED / blsmi_set_option("lat_rolled"): 0 = small Pairing calls take the STRAIGHT-LINE copy of their level program (pairing1s) instead of the one with rolled squaring runs (A/B)
 std::atomic<size_t> g_combine_mid_max{8192};  // BLSMI_COMBINE_MID_MAX / blsmi_set_option("combine_mid_max"): concurrent Verify calls of BLSMI_COMBINE_MAX <= n < this many tuples merge into one launch (verify_host.inc); 0: never
+std::atomic<size_t> g_rlc_min{Tuning{}.rlc_min};     // BLSMI_RLC_MIN / blsmi_set_option("rlc_min"): the randomised batch verification takes the per-tuple path below this many tuples (verify_host.inc)
 std::atomic<bool> g_dup_force_sort{Tuning{}.dup_force_sort};     // BLSMI_DUP_FORCE_SORT / blsmi_set_option("dup_force_sort"): test hook, the duplicate screen's fallback on every call
 // Options a caller has set through the API (blsmi_set_option, blsmi_set_*_threshold, blsmi_set_mul_assume_subgroup) keep their values when the library
 // (re-)initialises: the environment and the defaults apply only to what was never set explicitly (a set_option before the first entry point,
 // or before a re-initialisation after blsmi_shutdown, was silently overwritten here).
-enum { X_AGG_POW, X_MSM_SORT, X_DUP_SORT, X_LAT_ROLLED, X_CROWD_QUAD, X_COMBINE_MID, X_CROWD_FLOOR, X_ROW_SIDE, X_LAT_MAX, X_QUAD_MAX, X_ROW, X_MUL_SUBGROUP };
+enum { X_AGG_POW, X_MSM_SORT, X_DUP_SORT, X_LAT_ROLLED, X_CROWD_QUAD, X_COMBINE_MID, X_CROWD_FLOOR, X_ROW_SIDE, X_LAT_MAX, X_QUAD_MAX, X_ROW, X_MUL_SUBGROUP, X_RLC_MIN };
 std::atomic<unsigned> g_explicit{0};
 inline void set_explicit(int bit) { g_explicit.fetch_or(1u << bit, std::memory_order_relaxed); }
 inline bool is_explicit(int bit) { return (g_explicit.load(std::memory_order_relaxed) >> bit) & 1u; }
@@ -389,6 +394,7 @@ void load_env() {                       // caller holds g_mu; runs once per init
     if (!is_explicit(X_LAT_ROLLED)) { const char* v = getenv("BLSMI_LAT_ROLLED"); g_lat_rolled = !(v && v[0] == '0'); }
     if (!is_explicit(X_CROWD_QUAD)) { const char* v = getenv("BLSMI_CROWD_QUAD"); g_crowd_quad = !(v && v[0] == '0'); }
     if (!is_explicit(X_CROWD_FLOOR)) if (const char* v = getenv("BLSMI_CROWD_FLOOR")) g_crowd_floor = (size_t)strtoull(v, nullptr, 10);
+    if (!is_explicit(X_RLC_MIN)) g_rlc_min = num("BLSMI_RLC_MIN", Tuning{}.rlc_min);
 }
 // The options as they stand now, copied out of the atomics above and the settings fixed at initialisation: the only place that reads the
 // atomics for a call.  CtxLease takes one such snapshot per call; each call's every kernel choice reads it (tune(), route.h), so that an
@@ -404,6 +410,7 @@ Tuning tuning_now() {
     t.agg_cofactor_pow = g_agg_cofactor_pow.load(rx); t.msm_sort = g_msm_sort.load(rx); t.lat_rolled = g_lat_rolled.load(rx); t.dup_force_sort = g_dup_force_sort.load(rx);
     t.mul_subgroup = g_mul_subgroup.load(rx); t.pair_layout = g_pair_layout; t.use_gen_lines = g_use_gen_lines; t.hash_g2_pair = g_env.hash_g2_pair; t.hash_g1_split = g_env.hash_g1_split;
     t.swu_wave_max = g_env.swu_wave_max; t.sig_side_max = g_env.sig_side_max; t.fixed_wave_max = g_env.fixed_wave_max;
+    t.rlc_min = g_rlc_min.load(rx);
     return t;
 }
 // devs[0..ndev): HIP ordinals.  Caller holds g_mu.
@@ -459,7 +466,7 @@ int ensure_init_list(const int* devs, int ndev) {
     HIPCHK(hipSetDevice(g_dev[0].id));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, g_dev[0].id));
-    snprintf(g_version, sizeof g_version, "blsmi 0.7 %s CUs=%d devices=%d shards=%d%s", prop.gcnArchName, prop.multiProcessorCount, g_ndev, g_nshards, g_alias ? " ALIASED-DEVICES(test hook: host-staged collectives)" : g_have_comm ? " rccl" : "");
+    snprintf(g_version, sizeof g_version, "blsmi 0.8 %s CUs=%d devices=%d shards=%d%s", prop.gcnArchName, prop.multiProcessorCount, g_ndev, g_nshards, g_alias ? " ALIASED-DEVICES(test hook: host-staged collectives)" : g_have_comm ? " rccl" : "");
     g_ready = true;
     return BLSMI_OK;
 }
@@ -929,6 +936,7 @@ BLSMI_API int blsmi_set_option(const char* name, long long value) {
     else if (n == "combine_mid_max") { set_explicit(X_COMBINE_MID); g_combine_mid_max.store((size_t)std::max(0LL, value)); }
     else if (n == "crowd_floor") { set_explicit(X_CROWD_FLOOR); g_crowd_floor.store((size_t)std::max(0LL, value)); }
     else if (n == "assume_load") g_assume_load.store((size_t)std::max(0LL, value));
+    else if (n == "rlc_min") { set_explicit(X_RLC_MIN); g_rlc_min.store((size_t)std::max(0LL, value)); }
     else return BLSMI_E_ARG;
     return BLSMI_OK;
 }
@@ -1061,7 +1069,7 @@ BLSMI_API int blsmi_debug_op(int op_in, const uint64_t* a, const uint64_t* b, ui
     const bool rowstep = op >= BLSMI_OP_ROW_DBL_STEP && op <= BLSMI_OP_ROW_CLEAR_H2;
     if (rowstep && !rowl && !quadg2) return BLSMI_E_ARG;
     if (rowl && !rowstep && (pairl || op < BLSMI_OP_FQ12_MUL || op > BLSMI_OP_FQ12_MUL_BY_014 || op == BLSMI_OP_FQ12_CYCLO_RUN16)) return BLSMI_E_ARG;
-    int width = op < 16 ? 1 : op < 32 ? 2 : op < 48 ? 6 : op < 64 ? 12 : rowstep ? 12 : (op == BLSMI_OP_G1_DOUBLE || op == BLSMI_OP_G1_ADD || op == BLSMI_OP_SWU_G1) ? 3 : 6;
+    int width = op < 16 ? 1 : op < 32 ? 2 : op < 48 ? 6 : op < 64 ? 12 : rowstep ? 12 : (op == BLSMI_OP_G1_DOUBLE || op == BLSMI_OP_G1_ADD || op == BLSMI_OP_SWU_G1 || op == BLSMI_OP_G1_MUL_U64) ? 3 : 6;
     if (n && (!a || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
@@ -1372,12 +1380,14 @@ struct MsmKernels {
     void (*final)(const i32*, int, int, u8*, i32*);
 };
 template <int PB, int W>
-static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s) {
+// nbits: the scalars' width -- 256, or 64 for the randomised batch verification's scalars (verify_host.inc: rlc_sig_sum), whose
+// 32-byte records are zero above bit 64: four windows instead of sixteen, the Horner tail 48 doublings instead of 240
+static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s, int nbits = 256) {
     // 16-bit windows: n / 2^16 points per bucket, and a 255-bit scalar still fills 15 bits of the top window (a window
     // size that leaves the top window a few bits wide would pile every point into a handful of buckets there)
     const int c = 16;
     const int K = 16;                                                      // buckets per chunk lane: 2^12 chunk lanes per window keep every SIMD busy
-    const int nwin = (256 + c - 1) / c;
+    const int nwin = (nbits + c - 1) / c;
     const size_t B1 = (size_t)1 << c, nb = B1 * nwin, per_win = B1 / K, nct = per_win * nwin;
     const size_t jw = (size_t)W * NL + 1;                                  // words of one Jacobian SoA record
     DBuf hist, offs, cursor, idx, buckets, ch0, ch1, dmax;

@@ -36,10 +36,22 @@ BLSMI_DEV void debug_curve(int dbl, const u64* a, const u64* b, u64* out, size_t
     reinterpret_cast<F*>(&ro)[0] = r.x; reinterpret_cast<F*>(&ro)[1] = r.y; reinterpret_cast<F*>(&ro)[2] = r.z;
     rec_store<W>(out, t, ro);
 }
+template <class F> BLSMI_DEV Jac<F> mul_u64_jac(const Aff<F>& p, u64 k);
+// BLSMI_OP_G1_MUL_U64: the Jacobian point of a, made affine, times the 64-bit scalar in word 0 of b's record (mul_u64_jac: the ladder of k_g1_mul_u64)
+BLSMI_DEV void debug_g1_mul_u64(const u64* a, const u64* b, u64* out, size_t t) {
+    Rec<3> ra = rec_load<3>(a, t), ro;
+    Jac<FpS> p;
+    p.x = reinterpret_cast<FpS*>(&ra)[0]; p.y = reinterpret_cast<FpS*>(&ra)[1]; p.z = reinterpret_cast<FpS*>(&ra)[2]; p.inf = f_is_zero(p.z) ? -1 : 0;
+    Jac<FpS> r = mul_u64_jac<FpS>(jac_to_affine(p), b[(size_t)18 * t]);
+    if (r.inf) r.z = field_consts<FpS>::zero();
+    reinterpret_cast<FpS*>(&ro)[0] = r.x; reinterpret_cast<FpS*>(&ro)[1] = r.y; reinterpret_cast<FpS*>(&ro)[2] = r.z;
+    rec_store<3>(out, t, ro);
+}
 KERNEL k_debug_curve(int op, const u64* a, const u64* b, u64* out, size_t n) {
     const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
     if (t >= n) return;
-    if (op == BLSMI_OP_G1_DOUBLE || op == BLSMI_OP_G1_ADD) debug_curve<FpS, 3>(op == BLSMI_OP_G1_DOUBLE, a, b, out, t);
+    if (op == BLSMI_OP_G1_MUL_U64) debug_g1_mul_u64(a, b, out, t);
+    else if (op == BLSMI_OP_G1_DOUBLE || op == BLSMI_OP_G1_ADD) debug_curve<FpS, 3>(op == BLSMI_OP_G1_DOUBLE, a, b, out, t);
     else debug_curve<Fp2S, 6>(op == BLSMI_OP_G2_DOUBLE, a, b, out, t);
 }
 // ------------------------------------------------------------------------------------------------
@@ -93,6 +105,43 @@ KERNEL k_mul_finish(const u8* good, const u8* pts, size_t pt_stride, int rec_wor
 }
 KERNEL2 k_g1_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_batch_body<FpS, 96>(pts, pt_stride, scalars, out, out_inf, n); }
 KERNEL k_g2_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_batch_body<Fp2S, 192>(pts, pt_stride, scalars, out, out_inf, n); }
+// 64-bit scalars (the randomised batch verification, verify_host.inc: rlc_shard): the fixed 4-bit window of mul_batch_body over 16 nibbles --
+// 60 doublings and 15 additions after the 14 of the table, uniform control flow for all 64 lanes.  A plain ladder, not the endomorphisms:
+// the hash points of the cofactor-power route and a caller's keys need not lie in the subgroup, and the product is exact for any curve point.
+// Affine output with one inversion per lane, as mul_batch_body: k_g1_jac_to_affine is the same inversion per lane behind a second launch
+// and a Jacobian buffer, so folding it in here saves the round trip.  Infinity is not special-cased: the caller flags it (zero records).
+template <class F>
+BLSMI_DEV Jac<F> mul_u64_jac(const Aff<F>& p, u64 k) {
+    Jac<F> tab[16];
+    tab[0] = jac_zero<F>();
+    tab[1] = to_jac(p);
+    for (int j = 2; j < 16; j++) tab[j] = jac_add_affine(tab[j - 1], p);
+    Jac<F> res = tab[(u32)(k >> 60)];
+    for (int nib = 14; nib >= 0; nib--) {
+        res = jac_double(res); res = jac_double(res); res = jac_double(res); res = jac_double(res);
+        res = jac_add(res, tab[(u32)(k >> (4 * nib)) & 15]);
+    }
+    return res;
+}
+template <class F, int PB>
+__device__ void mul_u64_body(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) {
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    const size_t tt = t < n ? t : n - 1;
+    const Aff<F> a = jac_to_affine(mul_u64_jac<F>(load_aff<F>(pts + (size_t)PB * tt), scalars[tt]));
+    if (t < n) { store_aff(out + (size_t)PB * t, a); out_inf[t] = a.inf ? 1 : 0; }
+}
+KERNEL2 k_g1_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) { mul_u64_body<FpS, 96>(pts, scalars, out, out_inf, n); }
+KERNEL k_g2_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) { mul_u64_body<Fp2S, 192>(pts, scalars, out, out_inf, n); }
+// 64-bit scalars as the 32-byte big-endian records the bucket MSM's digit passes read (msm.inc: msm_digit)
+KERNEL k_scalar_u64_to_be32(const u64* r, u8* out, size_t n) {
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (t >= n) return;
+    const u64 k = r[t];
+    u32* o = reinterpret_cast<u32*>(out + (size_t)32 * t);
+#pragma unroll
+    for (int i = 0; i < 6; i++) o[i] = 0;
+    o[6] = __builtin_bswap32((u32)(k >> 32)); o[7] = __builtin_bswap32((u32)k);
+}
 // The same multiplications through the curve endomorphisms (glv.cuh): half (G1) / a quarter (G2) of the doublings.  For points of
 // the prime-order subgroup -- the default of the scalar-multiplication entry points, see blsmi_set_mul_assume_subgroup.
 template <class F, int PB>

@@ -115,6 +115,9 @@ __global__ void k_good_to_flag(const u8* good, i32* flag);
 __global__ void k_mul_finish(const u8* good, const u8* pts, size_t pt_stride, int rec_words, u8* out, u8* out_inf, size_t n);
 __global__ void k_g1_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
+__global__ void k_g1_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
+__global__ void k_g2_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
+__global__ void k_scalar_u64_to_be32(const u64* r, u8* out, size_t n);
 __global__ void k_glv_recode(const u8* scalars, int group, u8* rec, size_t n);
 __global__ void k_g1_mul_glv(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul_glv(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);

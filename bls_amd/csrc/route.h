@@ -20,6 +20,7 @@ struct Tuning {
     bool pair_layout = true, use_gen_lines = true, hash_g2_pair = true, hash_g1_split = true;   // fixed at initialisation (environment)
     size_t swu_wave_max = 512, fixed_wave_max = 2048;
     long long sig_side_max = -1;                                           // -1: the per-package defaults (sig_side)
+    size_t rlc_min = 32768;                                                // randomised batch verification: below this many tuples, the per-tuple path
 };
 
 // One tuple per WAVE (k_lat.hip), per DPP ROW of sixteen lanes, per lane QUAD, per lane PAIR, or per lane (BLSMI_LAYOUT=single, and the

@@ -965,6 +965,234 @@ int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_doma
     if (powc) { DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * words)); int rc = aggregate_pow_c(prod.as<i32>(), pc.as<i32>()); if (rc) return rc; return aggregate_tail(kind, pc.as<i32>(), ss, ok); }
     return aggregate_tail(kind, prod.as<i32>(), ss, ok);
 }
+// ---- randomised batch verification (blsmi 0.8: blsmi_g?pubs_verify_batch_rlc) ------------------------------------------------------
+// Small-exponent batch verification (Bellare, Garay, Rabin 1998): with random nonzero 64-bit r_i, ONE equation stands for the n of a batch --
+//     g2pubs: e(sum r_i sig_i, G2gen) == prod e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, sum r_i sig_i) == prod e(r_i pk_i, H(m_i))
+// It holds when every tuple is valid; with an invalid tuple among them it holds with probability at most 2^-64 over the r_i (keys and
+// signatures in the prime-order subgroups, as Deserialize guarantees).  n Miller loops, the product tree and ONE final exponentiation (the
+// VerifyAggregate machinery), plus a 64-bit multiplication per tuple (k_g1_mul_u64: r_i H_i for g2pubs, r_i pk_i for g1pubs -- both in G1)
+// and a 64-bit MSM over the signatures, which runs on the side stream beside the hash.  When the check fails, or a point at infinity
+// meets it, the shard computes the per-tuple verdicts of verify_batch from the buffers already on the device.
+//
+// The scalars: nonzero 64-bit words from the OS (getrandom, /dev/urandom), fresh for every call; no state is kept between calls.
+int rlc_draw_scalars(uint64_t* r, size_t n) {
+    uint8_t* p = reinterpret_cast<uint8_t*>(r);
+    size_t want = 8 * n, got = 0;
+#ifdef SYS_getrandom
+    while (got < want) {
+        const long k = syscall(SYS_getrandom, p + got, std::min(want - got, (size_t)1 << 20), 0);
+        if (k > 0) got += (size_t)k;
+        else if (k < 0 && errno == EINTR) continue;
+        else break;
+    }
+#endif
+    if (got < want) {
+        const int fd = open("/dev/urandom", O_RDONLY | O_CLOEXEC);
+        if (fd < 0) return BLSMI_E_RNG;
+        while (got < want) {
+            const ssize_t k = read(fd, p + got, want - got);
+            if (k > 0) got += (size_t)k;
+            else if (k < 0 && errno == EINTR) continue;
+            else break;
+        }
+        close(fd);
+        if (got < want) return BLSMI_E_RNG;
+    }
+    for (size_t i = 0; i < n; i++)                                         // a zero word (probability 2^-64 each) is drawn again
+        while (r[i] == 0) { int rc = rlc_draw_scalars(&r[i], 1); if (rc) return rc; }
+    return BLSMI_OK;
+}
+// The signature side's sum, sum_i r_i sig_i over the n signatures on the device (any curve points): affine at d_sum, infinity flag (int32)
+// at d_flag, on g_stream.  From RLC_MSM_BUCKET_MIN signatures the bucket method of msm_bucket_dev over the scalars' 64 bits (four
+// 16-bit windows); below, or when the digits are skewed (a caller's scalars), per-signature 64-bit ladders and the tree sum.
+constexpr size_t RLC_MSM_BUCKET_MIN = 8192;
+int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum, i32* d_flag) {
+    hipStream_t s = g_stream;
+    if (n >= RLC_MSM_BUCKET_MIN) {
+        DBuf sc; HIPCHK(sc.alloc((size_t)32 * n));
+        hipLaunchKernelGGL(k_scalar_u64_to_be32, dim3(nblocks(n)), dim3(WG), 0, s, d_r, sc.as<u8>(), n);
+        const int rc = kind == 0 ? msm_bucket_dev<96, 3>(g_mk1, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64)
+                                 : msm_bucket_dev<192, 6>(g_mk2, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
+        if (rc != BLSMI_E_SKEW) return rc;
+    }
+    const size_t pb = kind == 0 ? 96 : 192;
+    DBuf m, inf; HIPCHK(m.alloc(pb * n)); HIPCHK(inf.alloc(n));
+    prof_mark(kind == 0 ? "k_g1_mul_u64" : "k_g2_mul_u64");
+    if (kind == 0) hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
+    else hipLaunchKernelGGL(k_g2_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
+                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
+}
+// sig_side_start for a signature already on the device (the sum above, read in place): MillerLoop(-sig, G2gen) / MillerLoop(-G1gen, sig)
+// into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
+int sig_side_start_dev(int kind, const u8* d_sig, SigSide& ss) {
+    HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
+    const u8* tp = kind == 0 ? d_sig : g_gens.g1;
+    const u8* tq = kind == 0 ? g_gens.g2 : d_sig;
+    prof_mark("k_lat:miller1rawn");
+    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
+                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(ss.ml.p), (size_t)1);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(tl_ctx->join[0], g_stream));
+    return BLSMI_OK;
+}
+// the context's stream pointed at another of its streams for a stretch of one call (the kernels and their profile marks go there)
+struct OnStream { hipStream_t saved; explicit OnStream(hipStream_t s) : saved(tl_ctx->stream) { tl_ctx->stream = s; } ~OnStream() { tl_ctx->stream = saved; } };
+
+// One shard on the leased context (tune(): the call's snapshot).  ok: n verdict bytes (host, may be null); d_bitmap_slice as in
+// verify_batch_leased; *held = true when the combined check held and every verdict is 1.  r: n nonzero scalars (host).
+int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+              const uint64_t* r, uint8_t* ok, size_t n, int fmt, bool* held, u8* d_bitmap_slice = nullptr) {
+    *held = false;
+    if (n == 0) return BLSMI_OK;
+    const Kind k = kind_of(kind);
+    const Tuning& t = tune();
+    const size_t load = route_load(n);
+    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
+    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    HIPCHK(tl_ctx->ensure_aux());
+    hipStream_t st = tl_ctx->aux[0];
+    DBuf dm, doff, dp, ds, di, dr, dok, h, scaled, sinf, flags, any, sum, sflag, fr0, fr1, pc, dokb;
+    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
+    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * n));
+    HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(flags.alloc(n)); HIPCHK(any.alloc(sizeof(int)));
+    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
+    // the signatures go first, on the side stream (pageable copies block the host: the hash is queued behind the first of them only)
+    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
+    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
+    HIPCHK(hipMemcpyAsync(dr.p, r, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
+    bool powc = agg_pow_wanted(kind, n, t);                                // g2pubs from AGG_POW_MIN: uncleared hash points, the product raised to 1 - x
+    bool sig_side = false, cleared = !powc;
+    SigSide ss;
+    int bad = 0, sum_inf = 0, verdict = 0;
+    // the tuple side: hash, scale, Miller loops, product tree (+ the cofactor power); then the signature side on the side stream; then the tail
+    auto combined_check = [&]() -> int {
+        const AggregateRoute ar = aggregate_route(kind, n, false, !powc, t, load);
+        const size_t nrec = ar.records;
+        HIPCHK(fr0.alloc(sizeof(i32) * words * nrec)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((nrec + 1) / 2)));
+        HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
+        int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, ar.hash, !powc, powc ? any.as<int>() : nullptr);   // *bad bit 1: a hash point the uncleared path does not cover
+        if (rc) return rc;
+        cleared = !powc;
+        if (!sig_side) {                                                   // (first attempt) the keys travel while the messages are hashed
+            rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);
+            if (rc) return rc;
+            if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
+        }
+        hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
+                           (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
+        // r_i H_i (g2pubs; h itself stays for the fallback) / r_i pk_i (g1pubs); a scaled point at infinity is flagged like an input
+        const u8* src1 = kind == 0 ? h.as<u8>() : dp.as<u8>();
+        prof_mark("k_g1_mul_u64");
+        hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, src1, (const u64*)dr.as<u64>(), scaled.as<u8>(), sinf.as<u8>(), n);
+        prof_mark(nullptr);
+        hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)scaled.as<u8>(), 24, (const u8*)nullptr, 0, (const u8*)sinf.as<u8>(), flags.as<u8>(), any.as<int>(), n);
+        launch_miller1(scaled.as<u8>(), kind == 0 ? dp.as<u8>() : h.as<u8>(), fr0.as<i32>(), n, s, ar, nullptr);
+        size_t cur = nrec;
+        i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
+        while (cur > 1) { const size_t half = (cur + 1) / 2; launch_prod_level(src, dst, cur, half, s); std::swap(src, dst); cur = half; }
+        HIPCHK(hipGetLastError());
+        if (powc) { HIPCHK(pc.alloc(sizeof(i32) * words)); rc = aggregate_pow_c(src, pc.as<i32>()); if (rc) return rc; src = pc.as<i32>(); }
+        HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (!sig_side) {                                                   // sum r_i sig_i and its Miller loop, beside the tuple side
+            sig_side = true;
+            HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+            OnStream on(st);
+            rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
+            if (rc) return rc;
+        }
+        return aggregate_tail(kind, src, ss, &verdict);                    // waits for the side stream; synchronises s
+    };
+    int rc = combined_check();
+    if (rc) return rc;
+    if (!(bad & 1) && (bad & 2)) { powc = false; rc = combined_check(); if (rc) return rc; }   // an uncovered hash point: once more with the cleared points
+    *held = verdict == 1 && bad == 0 && sum_inf == 0;
+    if (*held) HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
+    else {
+        // the per-tuple verdicts of verify_batch, from the inputs on the device (the hash again where h holds uncleared points)
+        const VerifyRoute vr = verify_route(kind, n, false, false, t, load);
+        if (!cleared) { rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
+        DBuf f; HIPCHK(f.alloc(sizeof(i32) * words * n));
+        rc = verify_pair_stage(kind, h.as<u8>(), dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, s, vr);
+        if (rc) return rc;
+    }
+    if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, s, (const u8*)dok.as<u8>(), d_bitmap_slice, n);
+    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+// The host entry points.  scalars (may be null: drawn here) are checked for zeros first; below the call's rlc_min the per-tuple path runs
+// directly.  A split call (plan_shards) runs one combined check per shard, each with its own fallback; the bitmap comes together as in
+// verify_batch_direct.  *combined (may be null) = 1 when every verdict came from a combined check that held.
+int verify_batch_rlc_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                          const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    if (n && (!msgs || !off_or_domain || !pks || !sigs)) return BLSMI_E_ARG;
+    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
+    const Tuning t = tuning_now();                                         // the call's options, once: every shard routes by this snapshot
+    if (n < t.rlc_min) return verify_batch_direct(kind, msgs, off_or_domain, pks, sigs, inf_flags, ok, ok_bitmap, n, fmt);
+    std::vector<uint64_t> drawn;
+    if (!scalars) {
+        try { drawn.resize(n); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+        int rc = rlc_draw_scalars(drawn.data(), n);
+        if (rc) return rc;
+        scalars = drawn.data();
+    }
+    const Kind k = kind_of(kind);
+    const ShardPlan plan = plan_shards(n, 64);
+    std::vector<uint8_t> tmp;
+    if (!ok && ok_bitmap && plan.nshards == 1) { tmp.resize(n); ok = tmp.data(); }
+    std::unique_ptr<bool[]> held(new bool[plan.nshards]());
+    std::unique_lock<std::mutex> coll_lk(g_coll_mu, std::defer_lock);
+    const size_t bm = (n + 7) / 8;
+    if (plan.nshards > 1 && ok_bitmap) { coll_lk.lock(); int rc = coll_reserve_all(bm, true); if (rc) return rc; }
+    int rc = run_shards(plan, [&](int sh, size_t lo, size_t hi) -> int {
+        tl_ctx->tune = t;
+        const size_t m = hi - lo;
+        std::vector<uint64_t> off_sub;
+        const uint8_t* mp; const uint64_t* op;
+        if (kind == 2) { mp = msgs + 32 * lo; op = off_or_domain; }
+        else {
+            off_sub.resize(m + 1);
+            for (size_t i = 0; i <= m; i++) off_sub[i] = off_or_domain[lo + i] - off_or_domain[lo];
+            mp = msgs + off_or_domain[lo]; op = off_sub.data();
+        }
+        u8* slice = (plan.nshards > 1 && ok_bitmap) ? reinterpret_cast<u8*>(tl_ctx->dev->coll.p) + lo / 8 : nullptr;
+        return rlc_shard(kind, mp, op, pks + rec_bytes(k.pk_bytes, fmt & FMT_PK_JAC) * lo, sigs + rec_bytes(k.sig_bytes, fmt & FMT_SIG_JAC) * lo,
+                         inf_flags ? inf_flags + lo : nullptr, scalars + lo, ok ? ok + lo : nullptr, m, fmt, &held[sh], slice);
+    });
+    if (rc) return rc;
+    if (ok_bitmap) {
+        if (plan.nshards == 1) pack_bitmap(ok, ok_bitmap, n);
+        else {
+            rc = allreduce_bitmap(bm);
+            if (rc) return rc;
+            HIPCHK(hipSetDevice(g_dev[0].id));
+            HIPCHK(hipMemcpyAsync(ok_bitmap, g_dev[0].coll.p, bm, hipMemcpyDeviceToHost, g_dev[0].coll_stream));
+            HIPCHK(hipStreamSynchronize(g_dev[0].coll_stream));
+        }
+    }
+    bool all = true;
+    for (int i = 0; i < plan.nshards; i++) all = all && held[i];
+    if (combined) *combined = all ? 1 : 0;
+    return BLSMI_OK;
+}
+
 // VerifyAggregateCommon: AggregatePublicKeys (sum) then one Verify (g2pubs/bls.go:275-278)
 // fmt (blsmi.hip: FMT_*): bit 0 -- d_pks / pks are in-memory Jacobian records (summed as they are: k_g?_sum0_jac), bit 1 -- so is the signature
 int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uint8_t* msg, size_t msg_len, const uint8_t* domain, const uint8_t* sig, int* ok, int fmt = 0);
@@ -1376,6 +1604,19 @@ BLSMI_API int blsmi_g1pubs_verify_with_domain_batch(const uint8_t* msgs32, const
     if (!domain) return BLSMI_E_ARG;
     return verify_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, ok, ok_bitmap, n);
 }
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(0, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(1, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                         const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    if (n && !domain) return BLSMI_E_ARG;
+    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
 BLSMI_API int blsmi_g2pubs_verify_batch_dev(const void* d_msgs, const void* d_off, const void* d_pks, const void* d_sigs, const void* d_inf, void* d_ok, size_t n, void* stream) {
     if (n == 0) return BLSMI_OK;
     if (!d_msgs || !d_off || !d_pks || !d_sigs || !d_ok) return BLSMI_E_ARG;
@@ -1626,6 +1867,19 @@ BLSMI_API int blsmi_g1pubs_verify_batch_jac(const uint8_t* msgs, const uint64_t*
 BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t n) {
     if (!domain) return BLSMI_E_ARG;
     return verify_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, ok, ok_bitmap, n, FMT_JAC);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                             uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    if (n && !domain) return BLSMI_E_ARG;
+    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
 }
 BLSMI_API int blsmi_g2pubs_verify_aggregate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t sig[18], size_t n, int* ok) {
     return verify_aggregate_host(0, msgs, off, JACP(pks), JACP(sig), n, ok, true, FMT_JAC);

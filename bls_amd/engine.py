@@ -14,7 +14,7 @@ class BlsmiError(RuntimeError):
     pass
 
 
-_ERR = {-1: "no usable HIP device", -2: "HIP runtime call failed", -3: "bad argument", -4: "out of memory", -5: "RCCL unavailable or collective failed"}
+_ERR = {-1: "no usable HIP device", -2: "HIP runtime call failed", -3: "bad argument", -4: "out of memory", -5: "RCCL unavailable or collective failed", -6: "OS random source failed"}
 
 
 def _check(rc, what):
@@ -529,6 +529,54 @@ def g1pubs_verify_batch(msgs, pks, sigs, inf_flags=None):
     return _verify_batch(_lib().blsmi_g1pubs_verify_batch, 96, 192, msgs, pks, sigs, inf_flags)
 
 
+# ---- randomised batch verification (blsmi 0.8): one pairing check per batch, per-tuple verdicts only when it fails ---------------
+def _scalars(scalars, n):
+    """caller scalars (n nonzero 64-bit integers) as a uint64 array, or None: the library draws fresh ones"""
+    if scalars is None:
+        return None, None
+    r = np.ascontiguousarray(np.asarray([int(x) for x in scalars], dtype=np.uint64))
+    if r.shape != (n,):
+        raise ValueError("need one scalar per tuple")
+    return r, r.ctypes.data_as(_u64p)
+
+
+def _verify_batch_rlc(fn, pkb, sgb, msgs, pks, sigs, inf_flags, scalars):
+    n = len(msgs)
+    buf, off = _msgs(msgs)
+    p, s = _u8(pks, pkb * n), _u8(sigs, sgb * n)
+    f = _u8(inf_flags, n) if inf_flags is not None else None
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(fn(_p8(buf), off.ctypes.data_as(_u64p), _p8(p), _p8(s), _p8(f), pr, _p8(ok), _p8(bitmap), C.c_size_t(n), C.byref(comb)), "verify_batch_rlc")
+    return ok.astype(bool), bitmap, comb.value
+
+
+def g2pubs_verify_batch_rlc(msgs, pks, sigs, inf_flags=None, scalars=None):
+    """blsmi_g2pubs_verify_batch_rlc -> (ok, bitmap, combined): verify_batch's verdicts from one combined pairing check (combined == 1)
+    or, when it fails, from the per-tuple path (combined == 0).  scalars: n nonzero 64-bit integers, or None (the library draws them)."""
+    return _verify_batch_rlc(_lib().blsmi_g2pubs_verify_batch_rlc, 192, 96, msgs, pks, sigs, inf_flags, scalars)
+
+
+def g1pubs_verify_batch_rlc(msgs, pks, sigs, inf_flags=None, scalars=None):
+    return _verify_batch_rlc(_lib().blsmi_g1pubs_verify_batch_rlc, 96, 192, msgs, pks, sigs, inf_flags, scalars)
+
+
+def g1pubs_verify_with_domain_batch_rlc(msgs32, domain8, pks, sigs, inf_flags=None, scalars=None):
+    """-> (ok, combined)"""
+    n = len(msgs32)
+    buf = _u8(b"".join(bytes(m) for m in msgs32), 32 * n)
+    d, p, s = _u8(domain8, 8), _u8(pks, 96 * n), _u8(sigs, 192 * n)
+    f = _u8(inf_flags, n) if inf_flags is not None else None
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(_lib().blsmi_g1pubs_verify_with_domain_batch_rlc(_p8(buf), _p8(d), _p8(p), _p8(s), _p8(f), pr, _p8(ok), None, C.c_size_t(n), C.byref(comb)),
+           "verify_with_domain_batch_rlc")
+    return ok.astype(bool), comb.value
+
+
 def verify_serialized_batch(group, msgs, pks, sigs, check_subgroup=True):
     """Deserialize + Verify in one device pass: compressed keys / signatures as Serialize() emits them.
     Returns (ok, err_pk, err_sig); err_* are the per-element deserialisation error codes (0 = fine)."""
@@ -667,7 +715,7 @@ OPS = dict(FQ_MUL=1, FQ_SQR=2, FQ_ADD=3, FQ_SUB=4, FQ_NEG=5, FQ_INV=6, FQ_SQRT=7
            FQ6_MUL=32, FQ6_SQR=33, FQ6_INV=34, FQ6_FROB1=35, FQ6_MUL_BY_1=36, FQ6_MUL_BY_01=37,
            FQ12_MUL=48, FQ12_SQR=49, FQ12_INV=50, FQ12_FROB1=51, FQ12_FROB2=52, FQ12_FROB3=53, FQ12_CYCLO_SQR=54, FQ12_CYCLO_RUN16=55,
            FQ12_MUL_BY_014=56, FQ12_MUL_BY_LINE_PAIR=57,
-           G1_DOUBLE=64, G1_ADD=65, G2_DOUBLE=66, G2_ADD=67, SWU_G1=68, SWU_G2=69,
+           G1_DOUBLE=64, G1_ADD=65, G2_DOUBLE=66, G2_ADD=67, SWU_G1=68, SWU_G2=69, G1_MUL_U64=70,
            ROW_DBL_STEP=80, ROW_DBL_STEP_REF=81, ROW_ADD_STEP=82, ROW_ADD_STEP_REF=83, ROW_G2_DOUBLE=84, ROW_G2_ADD=85, ROW_CLEAR_H2=86)
 
 
@@ -714,7 +762,7 @@ LANE_ROW = 0x400           # BLSMI_OP_LANE_ROW
 
 def debug_op(name, a, b=None, lane_pair=False, raw_flag=False, lane_quad=False, lane_row=False):
     op = OPS[name]
-    width = 1 if op < 16 else 2 if op < 32 else 6 if op < 48 else 12 if op < 64 or op >= 80 else (3 if op in (64, 65, 68) else 6)
+    width = 1 if op < 16 else 2 if op < 32 else 6 if op < 48 else 12 if op < 64 or op >= 80 else (3 if op in (64, 65, 68, 70) else 6)
     a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 6 * width)
     n = a.shape[0]
     out = np.zeros_like(a)
@@ -809,6 +857,42 @@ def g1pubs_verify_with_domain_batch_jac(msgs32, domain8, pks, sigs):
     ok = np.zeros(n, dtype=np.uint8)
     _check(_lib().blsmi_g1pubs_verify_with_domain_batch_jac(_p8(buf), _p8(d), pp, ps, _p8(ok), None, C.c_size_t(n)), "verify_with_domain_batch_jac")
     return ok.astype(bool)
+
+
+def _verify_batch_rlc_jac(fn, pkb, sgb, msgs, pks, sigs, scalars):
+    n = len(msgs)
+    buf, off = _msgs(msgs)
+    p, pp = _j64(pks, pkb * n)
+    s, ps = _j64(sigs, sgb * n)
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(fn(_p8(buf), off.ctypes.data_as(_u64p), pp, ps, pr, _p8(ok), _p8(bitmap), C.c_size_t(n), C.byref(comb)), "verify_batch_rlc_jac")
+    return ok.astype(bool), bitmap, comb.value
+
+
+def g2pubs_verify_batch_rlc_jac(msgs, pks, sigs, scalars=None):
+    """blsmi_g2pubs_verify_batch_rlc_jac over in-memory points -> (ok, bitmap, combined)"""
+    return _verify_batch_rlc_jac(_lib().blsmi_g2pubs_verify_batch_rlc_jac, 288, 144, msgs, pks, sigs, scalars)
+
+
+def g1pubs_verify_batch_rlc_jac(msgs, pks, sigs, scalars=None):
+    return _verify_batch_rlc_jac(_lib().blsmi_g1pubs_verify_batch_rlc_jac, 144, 288, msgs, pks, sigs, scalars)
+
+
+def g1pubs_verify_with_domain_batch_rlc_jac(msgs32, domain8, pks, sigs, scalars=None):
+    """-> (ok, combined)"""
+    n = len(msgs32)
+    buf = _u8(b"".join(bytes(m) for m in msgs32), 32 * n)
+    d = _u8(domain8, 8)
+    p, pp = _j64(pks, 144 * n)
+    s, ps = _j64(sigs, 288 * n)
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(_lib().blsmi_g1pubs_verify_with_domain_batch_rlc_jac(_p8(buf), _p8(d), pp, ps, pr, _p8(ok), None, C.c_size_t(n), C.byref(comb)), "verify_with_domain_batch_rlc_jac")
+    return ok.astype(bool), comb.value
 
 
 def _verify_aggregate_jac(fn, pkb, sgb, msgs, pks, sig):

@@ -118,6 +118,23 @@ def VerifyBatch(msgs, pubs, sigs):
     return [bool(x) for x in ok]
 
 
+def VerifyBatchRandomized(msgs, pubs, sigs, scalars=None):
+    """VerifyBatch's verdicts from ONE pairing check over the batch with random 64-bit weights (small-exponent batch verification):
+    every tuple True when it holds, the per-tuple verdicts when it fails.  Keys and signatures must lie in the prime-order subgroups
+    (Deserialize* guarantees it).  scalars: n nonzero 64-bit integers for tests -- soundness is then the caller's; None draws fresh ones."""
+    n = len(msgs)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok, _, _ = engine.g2pubs_verify_batch_rlc_jac(msgs, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars)
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok, _, _ = engine.g2pubs_verify_batch_rlc(msgs, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars)
+    return [bool(x) for x in ok]
+
+
 class PreparedKeys:
     """The reference's G2Prepared of n public keys, kept in device memory the library owns."""
 

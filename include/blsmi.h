@@ -36,6 +36,7 @@ extern "C" {
 #define BLSMI_E_ARG (-3)        /* bad argument (null pointer with n > 0, ...) */
 #define BLSMI_E_NOMEM (-4)
 #define BLSMI_E_RCCL (-5)       /* librccl could not be loaded, or a collective failed (multi-GPU only) */
+#define BLSMI_E_RNG (-6)        /* the OS random source (getrandom, /dev/urandom) failed: no scalars were drawn (blsmi 0.8, *_verify_batch_rlc) */
 
 /* Bind the calling process to ONE device (HIP ordinal >= 0) and create the library's streams and tables.
  * Idempotent; every other host entry point calls it lazily with device 0. */
@@ -71,7 +72,8 @@ void blsmi_shutdown(void);
  * before binding by hand.  0.5 adds blsmi_trim / blsmi_held_bytes, the *_ex forms of mul / msm (per-call BLSMI_MUL_ANY_POINT),
  * blsmi_prefer_cpu, blsmi_debug_device_leases and the BLSMI_DEVICE_ALIAS test hook; no existing prototype changes.  0.6 adds the *_jac forms
  * (the reference's in-memory Jacobian / Montgomery points at the boundary); no existing prototype changes.  0.7 adds blsmi_set_row_threshold (the lane-row layout for
- * 2 048 .. 8 192 tuples), the "row_side" / "hash_row_min" / "hash_row_max" / "hash_quad_min" / "hash_quad_max" / "hash_oct_min" / "hash_oct_max" / "hash_g1_quad_min" / "hash_g1_quad_max" options and BLSMI_OP_LANE_ROW / BLSMI_OP_ROW_*_STEP / BLSMI_OP_ROW_G2_* / BLSMI_OP_ROW_CLEAR_H2 for blsmi_debug_op; no existing prototype changes. */
+ * 2 048 .. 8 192 tuples), the "row_side" / "hash_row_min" / "hash_row_max" / "hash_quad_min" / "hash_quad_max" / "hash_oct_min" / "hash_oct_max" / "hash_g1_quad_min" / "hash_g1_quad_max" options and BLSMI_OP_LANE_ROW / BLSMI_OP_ROW_*_STEP / BLSMI_OP_ROW_G2_* / BLSMI_OP_ROW_CLEAR_H2 for blsmi_debug_op; no existing prototype changes.  0.8 adds the randomised batch verification (blsmi_g?pubs_*verify*_batch_rlc[_jac]),
+ * the "rlc_min" option, BLSMI_E_RNG and BLSMI_OP_G1_MUL_U64; no existing prototype changes. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -131,6 +133,7 @@ int blsmi_prefer_cpu(int shape, size_t n);
  * switched while running through blsmi_set_option(name, value) (as the thresholds above: every call reads every option ONCE, when it starts,
  * so a change applies to the calls that start after it and never to part of a call in flight):
  *   "agg_cofactor_pow" (BLSMI_AGG_COFACTOR_POW, default 1), "msm_sort" (BLSMI_MSM_SORT, default 1), "dup_force_sort" (BLSMI_DUP_FORCE_SORT, 0),
+ *   "rlc_min" (BLSMI_RLC_MIN, default 32768): the randomised batch verification (*_verify_batch_rlc) of fewer tuples runs the per-tuple path,
  *   "lat_rolled" (BLSMI_LAT_ROLLED, default 1; 0: small Pairing calls run the straight-line copy of their level program instead of the one
  *   whose squaring runs are loops), "row_side" (BLSMI_ROW_SIDE, default 1: a Verify in the row layout runs its signature side beside the hash -- g1pubs, and g2pubs with "row_side_g2pubs"),
  *   "hash_row_min" / "hash_row_max" (defaults 2048 / 4096; no environment name): HashG2 of that many messages clears its cofactor sixteen lanes per message
@@ -351,6 +354,40 @@ int blsmi_g1pubs_verify_aggregate_jac(const uint8_t *msgs, const uint64_t *off, 
 int blsmi_g1pubs_verify_aggregate_with_domain_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t sig[36], size_t n, int *ok);
 int blsmi_g1pubs_verify_aggregate_common_jac(const uint8_t *msg, size_t msg_len, const uint64_t *pks /* n*18 */, const uint64_t sig[36], size_t n, int *ok);
 int blsmi_g1pubs_verify_aggregate_common_with_domain_jac(const uint8_t msg32[32], const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t sig[36], size_t n, int *ok);
+/* ---- randomised batch verification (blsmi 0.8) ------------------------------------------------------------------------------
+ * One pairing check per batch (small-exponent batch verification, Bellare-Garay-Rabin 1998): with random nonzero 64-bit r_i,
+ *     g2pubs: e(sum r_i sig_i, G2gen) == prod e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, sum r_i sig_i) == prod e(r_i pk_i, H(m_i))
+ * n Miller loops, a product tree and ONE final exponentiation instead of 2n Miller loops and n final exponentiations.
+ * Same arguments and results as the verify_batch entry point each mirrors, plus `scalars` and `combined`:
+ *   - combined check holds: ok[i] = 1 for every tuple, none checked on its own.  Every invalid tuple among them makes it hold with
+ *     probability at most 2^-64 over the r_i.
+ *   - it fails: the per-tuple verdicts of verify_batch, computed from the inputs already on the device (the failing call costs about a
+ *     verify_batch on top of the combined check).  Bisection is not attempted.
+ *   - a key or signature at infinity (inf_flags, the all-zero record, or z = 0 in the in-memory forms) gets ok[i] = 0 as in verify_batch;
+ *     any point at infinity on the combined path (an input, a scaled r_i H_i / r_i pk_i, the sum) sends the call (or its shard) to the
+ *     per-tuple path.
+ *   - scalars (n, may be NULL): NULL draws n fresh nonzero 64-bit scalars per call from the OS (getrandom(2), else /dev/urandom;
+ *     BLSMI_E_RNG when neither works).  Caller scalars: a zero among them is BLSMI_E_ARG, and the soundness of the check is then the
+ *     CALLER's responsibility (the scalars must be unpredictable to whoever made the signatures); they exist so that tests can pin the arithmetic.
+ *   - combined (may be NULL): 1 when every verdict came from a combined check that held; 0 when the call, or any shard of a split call,
+ *     took the per-tuple path (the check failed, a point at infinity, fewer than "rlc_min" tuples) and for n = 0.
+ * PRECONDITION: soundness is stated for keys and signatures in the prime-order subgroups -- what Deserialize guarantees (g1.go:185-197,
+ * g2.go:219-230).  The arithmetic itself (a plain 64-bit ladder, the any-point bucket MSM) is exact for any curve point.
+ * Below blsmi_set_option("rlc_min", n) / BLSMI_RLC_MIN tuples the per-tuple path runs directly (combined = 0).  These calls never join
+ * the request combiner of verify_batch; a large call is split over the devices like verify_batch, one combined check per shard. */
+int blsmi_g2pubs_verify_batch_rlc(const uint8_t *msgs, const uint64_t *off, const uint8_t *pks /* n*192 */, const uint8_t *sigs /* n*96 */, const uint8_t *inf_flags,
+                                  const uint64_t *scalars /* n, may be NULL */, uint8_t *ok /* n, may be NULL */, uint8_t *ok_bitmap /* may be NULL */, size_t n, int *combined);
+int blsmi_g1pubs_verify_batch_rlc(const uint8_t *msgs, const uint64_t *off, const uint8_t *pks /* n*96 */, const uint8_t *sigs /* n*192 */, const uint8_t *inf_flags,
+                                  const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_with_domain_batch_rlc(const uint8_t *msgs32, const uint8_t domain[8], const uint8_t *pks, const uint8_t *sigs, const uint8_t *inf_flags,
+                                              const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+/* in-memory forms (the shims' VerifyBatchRandomized), shaped like blsmi_g?pubs_verify_batch_jac */
+int blsmi_g2pubs_verify_batch_rlc_jac(const uint8_t *msgs, const uint64_t *off, const uint64_t *pks /* n*36 */, const uint64_t *sigs /* n*18 */,
+                                      const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_batch_rlc_jac(const uint8_t *msgs, const uint64_t *off, const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
+                                      const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
+                                                  const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
 /* device-pointer forms (every buffer on ONE of the library's devices; `stream` as in blsmi_pairing_batch_dev): the points resident in HBM as the
  * Go side holds them.  d_ok: n verdict bytes on the device. */
 int blsmi_pairing_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, void *d_out_fq12, size_t n, void *stream);
@@ -426,6 +463,7 @@ enum blsmi_debug_op {
     BLSMI_OP_FQ12_MUL_BY_014 /* fq12.go:32-47, (c0, c1, c4) = b[0..5] */, BLSMI_OP_FQ12_MUL_BY_LINE_PAIR /* a * (014 element b[0..5]) * (014 element b[6..11]) through the fused two-line product */,
     BLSMI_OP_G1_DOUBLE = 64, BLSMI_OP_G1_ADD, BLSMI_OP_G2_DOUBLE, BLSMI_OP_G2_ADD,
     BLSMI_OP_SWU_G1 = 68 /* t in word 0 of a 3-Fq record -> (x, y, 0) */, BLSMI_OP_SWU_G2 /* t in words 0-1 of a 6-Fq record -> (x, y, 0) */,
+    BLSMI_OP_G1_MUL_U64 = 70 /* blsmi 0.8: the Jacobian G1 point a times the 64-bit scalar in word 0 of b's record, by the plain ladder of the randomised batch verification */,
     /* with BLSMI_OP_LANE_ROW only: one step of the homogeneous Miller loop on a 12-Fq record (X, Y, Z of the running point: Fq2 each; xq, yq of Q:
      * Fq2 each; xP, yP: Fq each) -> (X3, Y3, Z3, c0, c1, c4): the new point and the line at P.  _REF: the lane-pair routine the row form restates */
     BLSMI_OP_ROW_DBL_STEP = 80, BLSMI_OP_ROW_DBL_STEP_REF, BLSMI_OP_ROW_ADD_STEP, BLSMI_OP_ROW_ADD_STEP_REF,

@@ -121,6 +121,27 @@ func VerifyBatch(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) []bool {
 	return out
 }
 
+// VerifyBatchRandomized gives VerifyBatch's verdicts from ONE pairing check over the whole batch (small-exponent batch
+// verification: the library draws fresh random 64-bit weights per call; INTEGRATION.md 2g).  When the check holds every tuple is
+// true; when it fails the library computes the per-tuple verdicts.  Keys and signatures must lie in the prime-order subgroups,
+// as Deserialize* leaves them.
+func VerifyBatchRandomized(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_batch_rlc_jac(u8(m), &off[0], u64(pk), u64(sg), nil, u8(ok), nil, C.size_t(n), nil), "g1pubs_verify_batch_rlc_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // Verify keeps the upstream signature (g1pubs/bls.go:165).
 func Verify(m []byte, pub *PublicKey, sig *Signature) bool {
 	return VerifyBatch([][]byte{m}, []*PublicKey{pub}, []*Signature{sig})[0]
@@ -143,6 +164,24 @@ func VerifyWithDomainBatch(msgs [][32]byte, pubs []*PublicKey, sigs []*Signature
 	ok := make([]byte, n)
 	must(C.blsmi_g1pubs_verify_with_domain_batch_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
 		u64(pk), u64(sg), u8(ok), nil, C.size_t(n)), "g1pubs_verify_with_domain_batch_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// VerifyWithDomainBatchRandomized gives VerifyWithDomainBatch's verdicts from one pairing check (VerifyBatchRandomized).
+func VerifyWithDomainBatchRandomized(msgs [][32]byte, pubs []*PublicKey, sigs []*Signature, domain [8]byte) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_with_domain_batch_rlc_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
+		u64(pk), u64(sg), nil, u8(ok), nil, C.size_t(n), nil), "g1pubs_verify_with_domain_batch_rlc_jac")
 	for i := range ok {
 		out[i] = ok[i] != 0
 	}

@@ -124,6 +124,27 @@ func VerifyBatch(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) []bool {
 	return out
 }
 
+// VerifyBatchRandomized gives VerifyBatch's verdicts from ONE pairing check over the whole batch (small-exponent batch
+// verification: the library draws fresh random 64-bit weights per call; INTEGRATION.md 2g).  When the check holds every tuple is
+// true; when it fails the library computes the per-tuple verdicts.  Keys and signatures must lie in the prime-order subgroups,
+// as Deserialize* leaves them.
+func VerifyBatchRandomized(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g2pubs_verify_batch_rlc_jac(u8(m), &off[0], u64(pk), u64(sg), nil, u8(ok), nil, C.size_t(n), nil), "g2pubs_verify_batch_rlc_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // Verify keeps the upstream signature (g2pubs/bls.go:159).  A lone Verify is faster on the device than on
 // one CPU core (2.0 ms against 3.7 ms): blsmi_prefer_cpu(BLSMI_SHAPE_VERIFY, 1) is 0, so there is no CPU branch.
 func Verify(m []byte, pub *PublicKey, sig *Signature) bool {
