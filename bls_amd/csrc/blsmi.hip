@@ -1062,13 +1062,17 @@ BLSMI_API int blsmi_debug_op(int op_in, const uint64_t* a, const uint64_t* b, ui
     const bool quadl = (op_in & BLSMI_OP_LANE_QUAD) != 0;                 // ... the Fq12 op in the lane-quad layout
     const bool rowl = (op_in & BLSMI_OP_LANE_ROW) != 0;                   // ... in the lane-row layout
     const int op = op_in & ~(BLSMI_OP_LANE_PAIR | BLSMI_OP_LANE_QUAD | BLSMI_OP_LANE_ROW);
-    if (pairl && (op < 16 || op >= 64)) return BLSMI_E_ARG;
+    const bool mstep = op == BLSMI_OP_ROW_DBL_STEP || op == BLSMI_OP_ROW_ADD_STEP;   // also in the pair / quad layouts: their own Miller-loop steps
+    const bool fexp = op == BLSMI_OP_FQ12_FINAL_EXP;                     // pair / quad only
+    if (pairl && (op < 16 || (op >= 64 && !mstep))) return BLSMI_E_ARG;
+    if (fexp && pairl == quadl) return BLSMI_E_ARG;
     const bool quadg2 = quadl && op >= BLSMI_OP_ROW_G2_DOUBLE && op <= BLSMI_OP_ROW_CLEAR_H2;   // quad_g2.inc
-    if (quadl && !quadg2 && (pairl || rowl || op < BLSMI_OP_FQ12_MUL || op > BLSMI_OP_FQ12_MUL_BY_014)) return BLSMI_E_ARG;
+    if (quadl && !quadg2 && (pairl || rowl || ((op < BLSMI_OP_FQ12_MUL || op > BLSMI_OP_FQ12_MUL_BY_014) && !fexp && !mstep))) return BLSMI_E_ARG;
     if (quadg2 && (pairl || rowl)) return BLSMI_E_ARG;
     const bool rowstep = op >= BLSMI_OP_ROW_DBL_STEP && op <= BLSMI_OP_ROW_CLEAR_H2;
-    if (rowstep && !rowl && !quadg2) return BLSMI_E_ARG;
-    if (rowl && !rowstep && (pairl || op < BLSMI_OP_FQ12_MUL || op > BLSMI_OP_FQ12_MUL_BY_014 || op == BLSMI_OP_FQ12_CYCLO_RUN16)) return BLSMI_E_ARG;
+    if (rowstep && !rowl && !quadg2 && !(mstep && (pairl || quadl))) return BLSMI_E_ARG;
+    if (rowl && (pairl || quadl)) return BLSMI_E_ARG;
+    if (rowl && !rowstep && (op < BLSMI_OP_FQ12_MUL || op > BLSMI_OP_FQ12_MUL_BY_014 || op == BLSMI_OP_FQ12_CYCLO_RUN16)) return BLSMI_E_ARG;
     int width = op < 16 ? 1 : op < 32 ? 2 : op < 48 ? 6 : op < 64 ? 12 : rowstep ? 12 : (op == BLSMI_OP_G1_DOUBLE || op == BLSMI_OP_G1_ADD || op == BLSMI_OP_SWU_G1 || op == BLSMI_OP_G1_MUL_U64) ? 3 : 6;
     if (n && (!a || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
@@ -1083,6 +1087,7 @@ BLSMI_API int blsmi_debug_op(int op_in, const uint64_t* a, const uint64_t* b, ui
     if (rowl) hipLaunchKernelGGL(k_debug_row, dim3(rblocks(n)), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
     else if (quadg2) hipLaunchKernelGGL(k_debug_quad_g2, dim3(qblocks(n)), w, 0, g_stream, op, da.as<u64>(), dout.as<u64>(), n);
     else if (quadl) hipLaunchKernelGGL(k_debug_quad, dim3(qblocks(n)), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
+    else if (pairl && fexp) hipLaunchKernelGGL(k_debug_final_exp_pair, dim3((unsigned)((n + PT - 1) / PT)), w, 0, g_stream, da.as<u64>(), dout.as<u64>(), n);
     else if (pairl) hipLaunchKernelGGL(k_debug_pairl, dim3((unsigned)((n + WG / 2 - 1) / (WG / 2))), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
     else if (op < 16) hipLaunchKernelGGL(k_debug_fq, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), dflag.as<u8>(), n);
     else if (op < 32) hipLaunchKernelGGL(k_debug_fq2, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), dflag.as<u8>(), n);

@@ -31,8 +31,9 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 typedef uint8_t u8;
 
-// Two builds of this header.  Default: 15 x 27-bit limbs, R = 2^405 -- every kernel family but one.  With -DBLSMI_LIMBS28 (the lane-pair and
-// lane-quad pairing kernels): 14 x 28-bit limbs, R = 2^392: 196 instead of 225 multiply-adds per product -- the lane-pair Fq2 product
+// Two builds of this header.  Default: 15 x 27-bit limbs, R = 2^405.  With -DBLSMI_LIMBS28 (the units listed in bls_amd/_native.py:_LIMBS28_UNITS --
+// every kernel unit but k_pairing_single, k_fe_single, k_fq12_single, k_lat and k_util; the single-lane Fq / Fq2 / Fq6 ops of k_wire.hip and
+// k_curve.hip and the lane-row kernels included): 14 x 28-bit limbs, R = 2^392: 196 instead of 225 multiply-adds per product -- the lane-pair Fq2 product
 // 3 236 against 3 738 ns per call (tools/ubench_core28.hip, profiles/r04_ubench_core28.log) -- paid for with head-room: R / q is 2 560
 // instead of 2^24, so a stored value may be no larger than 11 q and a VALUE REDUCTION (fp_reduce) replaces the limb normalisation at
 // some results.  The bound V counts units of q / VU so that a Montgomery product (|value| < 1.41 q) is "3 halves" rather than "2 q":
@@ -573,8 +574,8 @@ BLSMI_DEV FpS fp_from_mont384_words(const u32 w[12]) {
 }
 // ---- the 27-bit-limb kernels' form of a value, at kernel boundaries ------------------------------------------------------------
 // Buffers that cross between kernels (the Miller-loop -> final-exponentiation hand-off, the Fq12 product tree, prepared lines) hold
-// field elements as the 15 x 27-bit limbs of the Montgomery(2^405) form -- the format of every kernel family but the 28-bit pairing
-// kernels, which convert where they load and store (6 elements per lane and kernel: ~0.1 % of a pairing).  x R27 = x R28 2^13.
+// field elements as the 15 x 27-bit limbs of the Montgomery(2^405) form -- the format of the 27-bit units; the 28-bit units (above)
+// convert where they load and store (6 elements per lane and kernel: ~0.1 % of a pairing).  x R27 = x R28 2^13.
 constexpr int NL_IO = 15;              // words per field element in those buffers (either build)
 constexpr i32 MASK27 = (1 << 27) - 1;
 #ifdef BLSMI_LIMBS28

@@ -9,3 +9,17 @@
 
 #define BLSMI_PAIR_FE_ONLY
 #include "pair_kernels.inc"
+
+// unit-level access (blsmi_debug_op, BLSMI_OP_LANE_PAIR | BLSMI_OP_FQ12_FINAL_EXP): pairing.go:79-129 on k_debug_pairl's 12-Fq records,
+// through the same assembly-blob cores as k_final_exp_pair
+KERNEL_PAIR k_debug_final_exp_pair(const u64* a, u64* out, size_t n) {
+    const int par = threadIdx.x & 1;
+    const size_t t0 = (size_t)blockIdx.x * PT + (threadIdx.x >> 1);
+    const size_t t = t0 < n ? t0 : n - 1;                                 // both lanes of a pair stay active (DPP partner exchange)
+    P2::Fp12S f;
+    FpS* c = reinterpret_cast<FpS*>(&f);
+    for (int j = 0; j < 6; j++) c[j] = load_m384(a + (size_t)6 * (12 * t + 2 * j + par));
+    P2::final_exponentiation(f);
+    if (t0 < n)
+        for (int j = 0; j < 6; j++) store_m384(out + (size_t)6 * (12 * t + 2 * j + par), c[j]);
+}

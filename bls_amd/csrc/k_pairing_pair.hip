@@ -16,6 +16,16 @@ __global__ void __launch_bounds__(WG, BLSMI_PAIR_WAVES) k_debug_pairl(int op, co
     const int par = threadIdx.x & 1;
     const size_t t0 = (size_t)blockIdx.x * (WG / 2) + (threadIdx.x >> 1);
     const size_t t = t0 < n ? t0 : n - 1;                                 // both lanes of a pair stay active (DPP partner exchange)
+    if (op == BLSMI_OP_ROW_DBL_STEP || op == BLSMI_OP_ROW_ADD_STEP) {         // the homogeneous steps of k_miller1h_pair on k_debug_row's 12-Fq record
+        P2::Fp12S x; pair_rec_load<6>(reinterpret_cast<FpS*>(&x), a, t, par);
+        P2::G2Proj r; r.x = x.c0.c0; r.y = x.c0.c1; r.z = x.c0.c2;
+        const FpS px = load_m384(a + (size_t)6 * (12 * t + 10)), py = load_m384(a + (size_t)6 * (12 * t + 11));
+        P2::Fp2S o0, o1, o2;
+        if (op == BLSMI_OP_ROW_DBL_STEP) P2::doubling_step_h(r, o0, o1, o2); else P2::addition_step_h(r, x.c1.c0, x.c1.c1, o0, o1, o2);
+        const FpS res[6] = {r.x.c, r.y.c, r.z.c, o2.c, P2::fp2_store(P2::fp2_mul_fp(o1, px)).c, P2::fp2_store(P2::fp2_mul_fp(o0, py)).c};
+        if (t0 < n) pair_rec_store<6>(out, t, par, res);
+        return;
+    }
     if (op < 32) {
         P2::Fp2S x, y, r; pair_rec_load<1>(&x.c, a, t, par); y = x; if (b) pair_rec_load<1>(&y.c, b, t, par);
         switch (op) {

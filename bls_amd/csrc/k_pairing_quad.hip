@@ -124,9 +124,21 @@ KERNEL_QUAD k_debug_quad(int op, const u64* a, const u64* b, u64* out, size_t n)
     P2::Fp12S x, y;
     FpS* cx = reinterpret_cast<FpS*>(&x); FpS* cy = reinterpret_cast<FpS*>(&y);
     for (int j = 0; j < 6; j++) { cx[j] = load_m384(a + (size_t)6 * (12 * t + 2 * j + par)); cy[j] = b ? load_m384(b + (size_t)6 * (12 * t + 2 * j + par)) : cx[j]; }
+    if (op == BLSMI_OP_ROW_DBL_STEP || op == BLSMI_OP_ROW_ADD_STEP) {         // the steps of miller_loop_q on k_debug_row's 12-Fq record; both pairs hold the point
+        P2::G2Proj s; s.x = x.c0.c0; s.y = x.c0.c1; s.z = x.c0.c2;
+        const FpS px = load_m384(a + (size_t)6 * (12 * t + 10)), py = load_m384(a + (size_t)6 * (12 * t + 11));
+        P2::Fp2S o0, o1, o2, c0, c1;
+        if (op == BLSMI_OP_ROW_DBL_STEP) P2::doubling_step_q(s, o0, o1, o2); else P2::addition_step_h(s, x.c1.c0, x.c1.c1, o0, o1, o2);
+        P2::line_at_q(o0, o1, px, py, c0, c1);                               // c1 = o1 P.x, c0 = o0 P.y (ell_q's order)
+        const FpS res[6] = {s.x.c, s.y.c, s.z.c, o2.c, c1.c, c0.c};
+        if (t0 < n && (threadIdx.x & 2) == 0)
+            for (int j = 0; j < 6; j++) store_m384(out + (size_t)6 * (12 * t + 2 * j + par), res[j]);
+        return;
+    }
     const P2::Q12 qx = P2::q12_from_pair(x), qy = P2::q12_from_pair(y);
     P2::Q12 r;
     switch (op) {
+        case BLSMI_OP_FQ12_FINAL_EXP: r = qx; P2::final_exponentiation_q(r); break;
         case BLSMI_OP_FQ12_MUL: P2::q12_mul(r, qx, qy); break;
         case BLSMI_OP_FQ12_SQR: P2::q12_sqr(r, qx); break;
         case BLSMI_OP_FQ12_INV: P2::q12_inv(r, qx); break;

@@ -171,7 +171,9 @@ int blsmi_last_kernel_ms(float *miller_ms, float *final_exp_ms);
 int blsmi_last_profile(char *out, size_t cap);
 /* Miller loop only (pairing.go:16-75 with one pair per tuple), same output format */
 int blsmi_miller_loop_batch(const uint8_t *g1_aff, const uint8_t *g2_aff, uint64_t *out_fq12, size_t n);
-/* Final exponentiation only (pairing.go:79-129) on n Fq12 values in the output format */
+/* Final exponentiation only (pairing.go:79-129) on n Fq12 values in the output format.  Zero, the one value without an inverse, has no
+ * result in the reference (nil, pairing.go:83); here it gives the zero Fq12, on every layout (wave, row, single lane, and the pair / quad
+ * kernels of BLSMI_OP_FQ12_FINAL_EXP), since zero times the inversion's output is zero in the easy part. */
 int blsmi_final_exponentiation_batch(const uint64_t *in_fq12, uint64_t *out_fq12, size_t n);
 
 /* ---- scalar multiplication and point sums (g1.go:80-90, g2.go:92-102, AggregatePublicKeys /
@@ -461,20 +463,22 @@ enum blsmi_debug_op {
     BLSMI_OP_FQ6_MUL_BY_1 /* fq6.go:40-57, c1 = b[0..1] */, BLSMI_OP_FQ6_MUL_BY_01 /* fq6.go:60-90, (c0, c1) = b[0..3] */,
     BLSMI_OP_FQ12_MUL = 48, BLSMI_OP_FQ12_SQR, BLSMI_OP_FQ12_INV, BLSMI_OP_FQ12_FROB1, BLSMI_OP_FQ12_FROB2, BLSMI_OP_FQ12_FROB3, BLSMI_OP_FQ12_CYCLO_SQR, BLSMI_OP_FQ12_CYCLO_RUN16 /* 16 squarings in compressed form + decompression */,
     BLSMI_OP_FQ12_MUL_BY_014 /* fq12.go:32-47, (c0, c1, c4) = b[0..5] */, BLSMI_OP_FQ12_MUL_BY_LINE_PAIR /* a * (014 element b[0..5]) * (014 element b[6..11]) through the fused two-line product */,
+    BLSMI_OP_FQ12_FINAL_EXP = 58 /* with BLSMI_OP_LANE_PAIR (k_fe_pair.hip, the cores of k_final_exp_pair) or BLSMI_OP_LANE_QUAD only: pairing.go:79-129; zero gives zero */,
     BLSMI_OP_G1_DOUBLE = 64, BLSMI_OP_G1_ADD, BLSMI_OP_G2_DOUBLE, BLSMI_OP_G2_ADD,
     BLSMI_OP_SWU_G1 = 68 /* t in word 0 of a 3-Fq record -> (x, y, 0) */, BLSMI_OP_SWU_G2 /* t in words 0-1 of a 6-Fq record -> (x, y, 0) */,
     BLSMI_OP_G1_MUL_U64 = 70 /* blsmi 0.8: the Jacobian G1 point a times the 64-bit scalar in word 0 of b's record, by the plain ladder of the randomised batch verification */,
-    /* with BLSMI_OP_LANE_ROW only: one step of the homogeneous Miller loop on a 12-Fq record (X, Y, Z of the running point: Fq2 each; xq, yq of Q:
-     * Fq2 each; xP, yP: Fq each) -> (X3, Y3, Z3, c0, c1, c4): the new point and the line at P.  _REF: the lane-pair routine the row form restates */
+    /* with BLSMI_OP_LANE_ROW: one step of the homogeneous Miller loop on a 12-Fq record (X, Y, Z of the running point: Fq2 each; xq, yq of Q:
+     * Fq2 each; xP, yP: Fq each) -> (X3, Y3, Z3, c0, c1, c4): the new point and the line at P.  _REF: the lane-pair routine the row form restates.
+     * DBL_STEP / ADD_STEP also with BLSMI_OP_LANE_PAIR (doubling_step_h / addition_step_h) and BLSMI_OP_LANE_QUAD (doubling_step_q / addition_step_h) */
     BLSMI_OP_ROW_DBL_STEP = 80, BLSMI_OP_ROW_DBL_STEP_REF, BLSMI_OP_ROW_ADD_STEP, BLSMI_OP_ROW_ADD_STEP_REF,
     /* with BLSMI_OP_LANE_ROW only: G2 Jacobian arithmetic of the row layout's HashG2 tail (row_g2.inc) on a 12-Fq record (X1, Y1, Z1, X2, Y2, Z2: Fq2 each)
      * -> (X3, Y3, Z3, 0, 0, 0): g2.go:389-443 of the first point, g2.go:446-529 of both WITHOUT the special cases (infinity or equal x give Z3 = 0),
      * hash.go:368-389 of the first point */
     BLSMI_OP_ROW_G2_DOUBLE = 84, BLSMI_OP_ROW_G2_ADD, BLSMI_OP_ROW_CLEAR_H2
 };
-#define BLSMI_OP_LANE_PAIR 0x100 /* OR into an FQ2 / FQ6 / FQ12 op: run it in the lane-pair layout of the pairing kernels */
-#define BLSMI_OP_LANE_QUAD 0x200 /* OR into an FQ12 op: run it in the lane-quad layout (four lanes per tuple, k_pairing_quad.hip) */
-#define BLSMI_OP_LANE_ROW 0x400  /* OR into an FQ12 op (not CYCLO_RUN16): run it in the lane-row layout (sixteen lanes per tuple, k_pairing_row.hip) */
+#define BLSMI_OP_LANE_PAIR 0x100 /* OR into an FQ2 / FQ6 / FQ12 op or ROW_DBL_STEP / ROW_ADD_STEP: run it in the lane-pair layout of the pairing kernels */
+#define BLSMI_OP_LANE_QUAD 0x200 /* OR into an FQ12 op (not MUL_BY_LINE_PAIR) or ROW_DBL_STEP / ROW_ADD_STEP: run it in the lane-quad layout (four lanes per tuple, k_pairing_quad.hip) */
+#define BLSMI_OP_LANE_ROW 0x400  /* OR into an FQ12 op (not CYCLO_RUN16, MUL_BY_LINE_PAIR or FINAL_EXP): run it in the lane-row layout (sixteen lanes per tuple, k_pairing_row.hip) */
 int blsmi_debug_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, uint8_t *flag /* n, may be NULL */, size_t n);
 /* G2AffineToPrepared (g2.go:650-801) of one affine G2 point: 68 line-coefficient triples, each Fq2 as 12 LE uint64 Montgomery(2^384)
  * limbs, in Miller-loop order.  mode 0: computed by the one-tuple-per-lane doubling/addition steps; 1: by the lane-pair

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from gpu_common import P, RC, pack, rand_fq, rand_g1, rand_g2, sk_bytes
+from miller_steps import step_records
 
 pytestmark = pytest.mark.gpu
 OCT_MAX_DEFAULT = 7168                                                          # blsmi.hip: g_hash_oct_max
@@ -68,7 +69,7 @@ def test_fq12_ops_in_lane_row_layout(eng):
 def test_miller_loop_steps_in_lane_row_layout(eng):
     """one doubling step and one mixed addition step of the homogeneous Miller loop (pairing_body.inc: doubling_step_h_i, addition_step_h) on random
     projective points: the row form (two / four product times over the eight pairs) against the lane-pair routine run by every pair alike --
-    same new point, same line at P, canonical bits"""
+    same new point, same line at P, canonical bits -- and both against the Python statement of the steps (tests/miller_steps.py)"""
     xs = P.XORShift(6105)
     recs = _rand_rec(xs, 9, 12)                                            # (X, Y, Z, xq, yq, xP | yP): any field elements do, the formulas are polynomial
     for name in ("ROW_DBL_STEP", "ROW_ADD_STEP"):
@@ -76,6 +77,8 @@ def test_miller_loop_steps_in_lane_row_layout(eng):
         ref, _ = eng.debug_op(name + "_REF", recs, lane_row=True)
         bad = [what for k, what in enumerate(("X3", "Y3", "Z3", "c0", "c1", "c4")) if not np.array_equal(got[:, 12 * k:12 * k + 12], ref[:, 12 * k:12 * k + 12])]
         assert not bad, (name, bad)
+        want = step_records("dbl" if name == "ROW_DBL_STEP" else "add", recs)     # ... and both against the Python statement of the steps
+        assert np.array_equal(got, want) and np.array_equal(ref, want), name
 
 
 def test_pairing_on_the_four_paths_agrees_with_the_oracle(eng):
