@@ -93,3 +93,33 @@ def point_sum(points, group):
 def all_in_memory(points):
     """True when every point of a call is held as an in-memory Jacobian record: the call takes the *_jac entry point"""
     return len(points) > 0 and all(p.jac is not None for p in points)
+
+
+def flatten_committees(committees):
+    """committees (lists of Points) -> (every point in order, the m + 1 segment offsets): the idx = NULL form of the committee entry points
+    (blsmi_g?_sum_segmented, *_verify_aggregate_common*_batch)"""
+    pts = [p for c in committees for p in c]
+    return pts, engine.seg_offsets([len(c) for c in committees])
+
+
+def committee_sums(committees, group):
+    """[point_sum(c, group) for c in committees] as one segmented sum on the device"""
+    if not committees:
+        return []
+    pts, off = flatten_committees(committees)
+    if all_in_memory(pts):
+        fn = engine.g1_sum_segmented_jac if group == 1 else engine.g2_sum_segmented_jac
+        out, inf = fn(b"".join(p.jac for p in pts), len(pts), None, off)
+    else:
+        fn = engine.g1_sum_segmented if group == 1 else engine.g2_sum_segmented
+        out, inf = fn(b"".join(p.bytes_or_zero() for p in pts), len(pts), None, off, [1 if p.infinity else 0 for p in pts])
+    pb = 96 if group == 1 else 192
+    return [Point(None if inf[j] else out[pb * j:pb * (j + 1)], group) for j in range(len(committees))]
+
+
+def committee_batch_args(committees, sigs):
+    """the flattened keys and the signatures of a batch of VerifyAggregateCommon: (jac, keys bytes, npk, offsets, signature bytes)"""
+    keys, off = flatten_committees(committees)
+    if all_in_memory(keys + sigs):
+        return True, b"".join(p.jac for p in keys), len(keys), off, b"".join(s.jac for s in sigs)
+    return False, b"".join(p.bytes_or_zero() for p in keys), len(keys), off, b"".join(s.bytes_or_zero() for s in sigs)

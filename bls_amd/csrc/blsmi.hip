@@ -67,7 +67,7 @@ std::mutex g_coll_mu;
 std::condition_variable g_cv;          // a context was released (lease waiters and shutdown both wait here: notify_all)
 bool g_pair_layout = true;              // lane-pair pairing kernels (two lanes per tuple); BLSMI_LAYOUT=single for one tuple per lane
 bool g_ready = false;
-char g_version[200] = "blsmi 0.8 (uninitialised)";
+char g_version[200] = "blsmi 0.9 (uninitialised)";
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "blsmi: %s failed: %s\n", #x, hipGetErrorString(e_)); return BLSMI_E_HIP; } } while (0)
 
@@ -362,11 +362,12 @@ std::atomic<bool> g_msm_sort{Tuning{}.msm_sort};            // BLSMI_MSM_SORT / 
 std::atomic<bool> g_lat_rolled{Tuning{}.lat_rolled};          // BLSMI_LAT_ROLLED / blsmi_set_option("lat_rolled"): 0 = small Pairing calls take the STRAIGHT-LINE copy of their level program (pairing1s) instead of the one with rolled squaring runs (A/B)
 std::atomic<size_t> g_combine_mid_max{8192};  // BLSMI_COMBINE_MID_MAX / blsmi_set_option("combine_mid_max"): concurrent Verify calls of BLSMI_COMBINE_MAX <= n < this many tuples merge into one launch (verify_host.inc); 0: never
 std::atomic<size_t> g_rlc_min{Tuning{}.rlc_min};     // BLSMI_RLC_MIN / blsmi_set_option("rlc_min"): the randomised batch verification takes the per-tuple path below this many tuples (verify_host.inc)
+std::atomic<size_t> g_segsum_chunk{Tuning{}.segsum_chunk};     // BLSMI_SEGSUM_CHUNK / blsmi_set_option("segsum_chunk"): positions per lane of the segmented sums (0: automatic, verify_host.inc)
 std::atomic<bool> g_dup_force_sort{Tuning{}.dup_force_sort};     // BLSMI_DUP_FORCE_SORT / blsmi_set_option("dup_force_sort"): test hook, the duplicate screen's fallback on every call
 // Options a caller has set through the API (blsmi_set_option, blsmi_set_*_threshold, blsmi_set_mul_assume_subgroup) keep their values when the library
 // (re-)initialises: the environment and the defaults apply only to what was never set explicitly (a set_option before the first entry point,
 // or before a re-initialisation after blsmi_shutdown, was silently overwritten here).
-enum { X_AGG_POW, X_MSM_SORT, X_DUP_SORT, X_LAT_ROLLED, X_CROWD_QUAD, X_COMBINE_MID, X_CROWD_FLOOR, X_ROW_SIDE, X_LAT_MAX, X_QUAD_MAX, X_ROW, X_MUL_SUBGROUP, X_RLC_MIN };
+enum { X_AGG_POW, X_MSM_SORT, X_DUP_SORT, X_LAT_ROLLED, X_CROWD_QUAD, X_COMBINE_MID, X_CROWD_FLOOR, X_ROW_SIDE, X_LAT_MAX, X_QUAD_MAX, X_ROW, X_MUL_SUBGROUP, X_RLC_MIN, X_SEGSUM_CHUNK };
 std::atomic<unsigned> g_explicit{0};
 inline void set_explicit(int bit) { g_explicit.fetch_or(1u << bit, std::memory_order_relaxed); }
 inline bool is_explicit(int bit) { return (g_explicit.load(std::memory_order_relaxed) >> bit) & 1u; }
@@ -395,6 +396,7 @@ void load_env() {                       // caller holds g_mu; runs once per init
     if (!is_explicit(X_CROWD_QUAD)) { const char* v = getenv("BLSMI_CROWD_QUAD"); g_crowd_quad = !(v && v[0] == '0'); }
     if (!is_explicit(X_CROWD_FLOOR)) if (const char* v = getenv("BLSMI_CROWD_FLOOR")) g_crowd_floor = (size_t)strtoull(v, nullptr, 10);
     if (!is_explicit(X_RLC_MIN)) g_rlc_min = num("BLSMI_RLC_MIN", Tuning{}.rlc_min);
+    if (!is_explicit(X_SEGSUM_CHUNK)) g_segsum_chunk = num("BLSMI_SEGSUM_CHUNK", Tuning{}.segsum_chunk);
 }
 // The options as they stand now, copied out of the atomics above and the settings fixed at initialisation: the only place that reads the
 // atomics for a call.  CtxLease takes one such snapshot per call; each call's every kernel choice reads it (tune(), route.h), so that an
@@ -411,6 +413,7 @@ Tuning tuning_now() {
     t.mul_subgroup = g_mul_subgroup.load(rx); t.pair_layout = g_pair_layout; t.use_gen_lines = g_use_gen_lines; t.hash_g2_pair = g_env.hash_g2_pair; t.hash_g1_split = g_env.hash_g1_split;
     t.swu_wave_max = g_env.swu_wave_max; t.sig_side_max = g_env.sig_side_max; t.fixed_wave_max = g_env.fixed_wave_max;
     t.rlc_min = g_rlc_min.load(rx);
+    t.segsum_chunk = g_segsum_chunk.load(rx);
     return t;
 }
 // devs[0..ndev): HIP ordinals.  Caller holds g_mu.
@@ -466,7 +469,7 @@ int ensure_init_list(const int* devs, int ndev) {
     HIPCHK(hipSetDevice(g_dev[0].id));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, g_dev[0].id));
-    snprintf(g_version, sizeof g_version, "blsmi 0.8 %s CUs=%d devices=%d shards=%d%s", prop.gcnArchName, prop.multiProcessorCount, g_ndev, g_nshards, g_alias ? " ALIASED-DEVICES(test hook: host-staged collectives)" : g_have_comm ? " rccl" : "");
+    snprintf(g_version, sizeof g_version, "blsmi 0.9 %s CUs=%d devices=%d shards=%d%s", prop.gcnArchName, prop.multiProcessorCount, g_ndev, g_nshards, g_alias ? " ALIASED-DEVICES(test hook: host-staged collectives)" : g_have_comm ? " rccl" : "");
     g_ready = true;
     return BLSMI_OK;
 }
@@ -937,6 +940,7 @@ BLSMI_API int blsmi_set_option(const char* name, long long value) {
     else if (n == "crowd_floor") { set_explicit(X_CROWD_FLOOR); g_crowd_floor.store((size_t)std::max(0LL, value)); }
     else if (n == "assume_load") g_assume_load.store((size_t)std::max(0LL, value));
     else if (n == "rlc_min") { set_explicit(X_RLC_MIN); g_rlc_min.store((size_t)std::max(0LL, value)); }
+    else if (n == "segsum_chunk") { set_explicit(X_SEGSUM_CHUNK); g_segsum_chunk.store((size_t)std::max(0LL, value)); }
     else return BLSMI_E_ARG;
     return BLSMI_OK;
 }

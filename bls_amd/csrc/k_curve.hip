@@ -330,6 +330,88 @@ __device__ void sum_final_body(const i32* src, u8* out, i32* out_inf) {
 KERNEL2 k_g1_sum_final(const i32* src, u8* out, i32* out_inf) { sum_final_body<FpS, 96>(src, out, out_inf); }
 KERNEL k_g2_sum_final(const i32* src, u8* out, i32* out_inf) { sum_final_body<Fp2S, 192>(src, out, out_inf); }
 
+// ---- segmented sums: m sums over ragged, index-addressed subsets of one point table (the committees of a batch of
+// VerifyAggregateCommon, blsmi 0.9).  The host cuts every segment into chunks of at most K positions (verify_host.inc: segsum_plan).
+// Pass 1 gives each chunk one lane (G2 affine: a lane pair, k_msm_pair.hip) that gathers its points through the index slice and adds
+// them, as the MSM's bucket pass does (msm.inc: msm_bucket_body); fold passes add each segment's partials K at a time until at most 64
+// are left; the final kernel adds those in a shuffle tree across one wave per segment.  No lane performs more than K (fold: max(K, 2))
+// dependent additions.  Chunk c covers positions [ch_lo[c], ch_lo[c] + ch_cnt[c]) of segment ch_seg[c]; its partial goes to slot c of
+// a Jacobian SoA array.  An index >= npk is skipped and marks its segment bad (bad[seg] = 1; every writer stores the same value).
+template <class F, int PB>
+__device__ void segsum_chunk_body(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg,
+                                  u8* bad, i32* part, size_t nch) {
+    const size_t c = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (c >= nch) return;
+    const u64 lo = ch_lo[c];
+    const u32 cnt = ch_cnt[c];
+    Jac<F> acc = jac_zero<F>();
+    for (u32 k = 0; k < cnt; k++) {
+        const u64 i = idx ? (u64)idx[lo + k] : lo + k;
+        if (i >= npk) { bad[ch_seg[c]] = 1; continue; }
+        Aff<F> a = load_aff<F>(pts + (size_t)PB * i);
+        if (in_inf && in_inf[i]) a.inf = -1;
+        acc = jac_add_affine(acc, a);
+    }
+    jac_soa_store(part, nch, c, acc);
+}
+// pass 1 over the reference's in-memory Jacobian records (device_io.cuh: load_jac_m384, z == 0 is infinity): jac_add, no inversion
+template <class F>
+__device__ void segsum_chunk_jac_body(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg,
+                                      u8* bad, i32* part, size_t nch) {
+    constexpr int RW = 18 * (sizeof(F) / sizeof(FpS));
+    const size_t c = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (c >= nch) return;
+    const u64 lo = ch_lo[c];
+    const u32 cnt = ch_cnt[c];
+    Jac<F> acc = jac_zero<F>();
+    for (u32 k = 0; k < cnt; k++) {
+        const u64 i = idx ? (u64)idx[lo + k] : lo + k;
+        if (i >= npk) { bad[ch_seg[c]] = 1; continue; }
+        acc = jac_add(acc, load_jac_m384<F>(pts + (size_t)RW * i));
+    }
+    jac_soa_store(part, nch, c, acc);
+}
+KERNEL2 k_g1_segsum_chunk(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    segsum_chunk_body<FpS, 96>(pts, in_inf, npk, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
+}
+KERNEL2 k_g1_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    segsum_chunk_jac_body<FpS>(pts, npk, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
+}
+KERNEL k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    segsum_chunk_jac_body<Fp2S>(pts, npk, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
+}
+// fold: chunk c adds the ch_cnt[c] >= 1 consecutive partials of src from ch_lo[c] on
+KERNEL2 k_g1_segsum_fold(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch) {
+    const size_t c = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (c >= nch) return;
+    const u64 lo = ch_lo[c];
+    const u32 cnt = ch_cnt[c];
+    Jac<FpS> acc = jac_soa_load<FpS>(src, nsrc, lo);
+    for (u32 k = 1; k < cnt; k++) acc = jac_add(acc, jac_soa_load<FpS>(src, nsrc, lo + k));
+    jac_soa_store(dst, nch, c, acc);
+}
+// final: one wave per segment, lane l takes partial l of the seg_cnt[j] <= 64 from seg_lo[j] on; lane 0 writes the affine record and
+// out_inf[j] = bad_code (a bad index: record zeroed; 2 for the sums, 1 as the tuple flag of a verify), 1 (infinity, the empty segment
+// included) or 0
+template <class F, int PB>
+__device__ void segsum_final_body(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf) {
+    const size_t j = blockIdx.x;
+    const u32 lane = threadIdx.x;
+    Jac<F> acc = jac_zero<F>();
+    if (lane < seg_cnt[j]) acc = jac_soa_load<F>(src, nsrc, seg_lo[j] + lane);
+#pragma unroll 1
+    for (int off = WG / 2; off >= 1; off >>= 1) acc = jac_add(acc, jac_shfl_down(acc, off));
+    Aff<F> a = jac_to_affine(acc);
+    if (lane == 0) {
+        const bool b = bad[j] != 0;
+        if (b) a.inf = -1;                                                 // store_aff: the all-zero record
+        store_aff(out + (size_t)PB * j, a);
+        out_inf[j] = b ? bad_code : a.inf ? 1 : 0;
+    }
+}
+KERNEL2 k_g1_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf) { segsum_final_body<FpS, 96>(src, nsrc, seg_lo, seg_cnt, bad, bad_code, out, out_inf); }
+KERNEL k_g2_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf) { segsum_final_body<Fp2S, 192>(src, nsrc, seg_lo, seg_cnt, bad, bad_code, out, out_inf); }
+
 #include "msm.inc"
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -127,3 +127,32 @@ __global__ void __launch_bounds__(WG, 2) k_g2_msm_fold2_pair(const i32* src, i32
         } else pair_soa_store(dst, total, t, par, v);
     }
 }
+// Pass 1 and the fold of the G2 segmented sum (k_curve.hip: segsum_chunk_body) in the lane-pair layout: a lane pair per chunk, as
+// k_g2_msm_bucket_pair has per bucket.  The partials are the one-lane kernels' records (jac_soa_store), read by k_g2_segsum_final.
+__global__ void __launch_bounds__(WG, 2) k_g2_segsum_chunk_pair(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt,
+                                                                const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    const int par = threadIdx.x & 1;
+    const size_t c = (size_t)blockIdx.x * (WG / 2) + (threadIdx.x >> 1);
+    const size_t cc = c < nch ? c : nch - 1;                               // both lanes of a pair stay active
+    const u64 lo = ch_lo[cc];
+    const u32 cnt = c < nch ? ch_cnt[cc] : 0;
+    P2::G2JacP acc = jac_zero<P2::Fp2S>();
+    for (u32 k = 0; k < cnt; k++) {
+        const u64 i = idx ? (u64)idx[lo + k] : lo + k;                     // (uniform per pair)
+        if (i >= npk) { if (!par) bad[ch_seg[cc]] = 1; continue; }
+        P2::G2AffP a = pair_load_g2(pts + (size_t)192 * i, par);
+        if (in_inf && in_inf[i]) a.inf = -1;
+        acc = jac_add_affine(acc, a);
+    }
+    if (c < nch) pair_soa_store(part, nch, c, par, acc);
+}
+__global__ void __launch_bounds__(WG, 2) k_g2_segsum_fold_pair(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch) {
+    const int par = threadIdx.x & 1;
+    const size_t c = (size_t)blockIdx.x * (WG / 2) + (threadIdx.x >> 1);
+    const size_t cc = c < nch ? c : nch - 1;
+    const u64 lo = ch_lo[cc];
+    const u32 cnt = c < nch ? ch_cnt[cc] : 1;
+    P2::G2JacP acc = pair_soa_load(src, nsrc, lo, par);
+    for (u32 k = 1; k < cnt; k++) acc = jac_add(acc, pair_soa_load(src, nsrc, lo + k, par));
+    if (c < nch) pair_soa_store(dst, nch, c, par, acc);
+}

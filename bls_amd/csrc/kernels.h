@@ -136,6 +136,12 @@ __global__ void k_g1_sum(const i32* src, i32* dst, size_t n, size_t half);
 __global__ void k_g2_sum(const i32* src, i32* dst, size_t n, size_t half);
 __global__ void k_g1_sum_final(const i32* src, u8* out, i32* out_inf);
 __global__ void k_g2_sum_final(const i32* src, u8* out, i32* out_inf);
+__global__ void k_g1_segsum_chunk(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g1_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g1_segsum_fold(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch);
+__global__ void k_g1_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);
+__global__ void k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g2_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);
 __global__ void k_g2_mul_pair(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul_glv_pair(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 // k_msm_pair.hip
@@ -145,6 +151,8 @@ __global__ void k_g2_msm_chunk_pair(const i32* buckets, i32* chunks, int c, int 
 __global__ void k_g2_msm_fold_pair(const i32* src, i32* dst, size_t seg, size_t half, int nwin);
 __global__ void k_g2_msm_chunk2_pair(const i32* buckets, i32* out, int c, int K, size_t nb, size_t nct);
 __global__ void k_g2_msm_fold2_pair(const i32* src, i32* dst, int narr, int nwin, size_t len, int io);
+__global__ void k_g2_segsum_chunk_pair(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g2_segsum_fold_pair(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch);
 // msm.inc
 __global__ void k_msm_hist(const u8* scalars, size_t n, int c, int nwin, u32* hist);
 __global__ void k_msm_scan(const u32* hist, u32* offs, u32* cursor, int c);

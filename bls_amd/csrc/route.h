@@ -21,6 +21,7 @@ struct Tuning {
     size_t swu_wave_max = 512, fixed_wave_max = 2048;
     long long sig_side_max = -1;                                           // -1: the per-package defaults (sig_side)
     size_t rlc_min = 32768;                                                // randomised batch verification: below this many tuples, the per-tuple path
+    size_t segsum_chunk = 0;                                               // segmented sums: positions per chunk and lane (0: from the total count, verify_host.inc: segsum_auto_chunk)
 };
 
 // One tuple per WAVE (k_lat.hip), per DPP ROW of sixteen lanes, per lane QUAD, per lane PAIR, or per lane (BLSMI_LAYOUT=single, and the

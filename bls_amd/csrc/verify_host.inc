@@ -1967,3 +1967,279 @@ BLSMI_API int blsmi_g2pubs_verify_aggregate_prepared_jac(const uint8_t* msgs, co
     return verify_aggregate_dev(0, dm.p, doff.p, nullptr, JACP(sig), n, ok, true, &prep, FMT_SIG_JAC);
 }
 #undef JACP
+
+// ---- segmented sums and batches of VerifyAggregateCommon (blsmi 0.9; include/blsmi.h "committees") ------------------------------------
+// m sums over ragged, index-addressed subsets of one key table: segment j is {pts[idx[k]] : seg_off[j] <= k < seg_off[j + 1]} (idx null:
+// the positions themselves).  The chunk plan is built here from seg_off (k_curve.hip: segsum_chunk_body): pass 1 cuts every segment into
+// chunks of at most K positions, a lane (G2 affine: a lane pair) per chunk; each fold pass cuts every segment's partials into chunks of at
+// most max(K, 2) until no segment has more than 64; the final kernel adds those across one wave per segment.
+// K: the "segsum_chunk" option, 0 = from the total count T.  Eight positions per lane while that still leaves 2^16 chunks (below, the
+// passes are latency-bound: the chain of 8 + 8 + ... dependent additions is what a call waits for), then doubled up to 64.
+namespace {
+size_t segsum_auto_chunk(size_t total) {
+    size_t K = 8;
+    while (total / K > ((size_t)1 << 16) && K < 64) K *= 2;
+    return K;
+}
+struct SegPlan {
+    size_t m = 0, K = 0, nch1 = 0;
+    struct Fold { size_t nsrc, nch, lo, cnt; };                            // lo / cnt: byte offsets of the pass's chunk arrays in `blob`
+    std::vector<Fold> folds;
+    size_t ch_lo = 0, ch_cnt = 0, ch_seg = 0, seg_lo = 0, seg_cnt = 0, nlast = 0;
+    std::vector<uint8_t> blob;                                             // every array of the plan, uploaded in one copy
+    template <class T> size_t put(const std::vector<T>& v) {
+        const size_t at = (blob.size() + 7) & ~(size_t)7;
+        blob.resize(at + sizeof(T) * v.size());
+        if (!v.empty()) memcpy(blob.data() + at, v.data(), sizeof(T) * v.size());
+        return at;
+    }
+};
+// the host forms' checks (BLSMI_E_ARG before any device work): offsets from 0, non-decreasing; every index below npk
+int segsum_check(size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m) {
+    if (!seg_off || seg_off[0] != 0) return BLSMI_E_ARG;
+    for (size_t j = 0; j < m; j++) if (seg_off[j + 1] < seg_off[j]) return BLSMI_E_ARG;
+    const uint64_t total = seg_off[m];
+    if (!idx) return total <= npk ? BLSMI_OK : BLSMI_E_ARG;
+    for (uint64_t k = 0; k < total; k++) if (idx[k] >= npk) return BLSMI_E_ARG;
+    return BLSMI_OK;
+}
+void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p) {
+    p.m = m; p.K = K;
+    std::vector<uint64_t> lo, part_lo(m);
+    std::vector<uint32_t> cnt, seg, part_cnt(m);
+    for (size_t j = 0; j < m; j++) {
+        const uint64_t a = seg_off[j], len = seg_off[j + 1] - a;
+        part_lo[j] = lo.size();
+        for (uint64_t c = 0; c < len; c += K) { lo.push_back(a + c); cnt.push_back((uint32_t)std::min<uint64_t>(K, len - c)); seg.push_back((uint32_t)j); }
+        part_cnt[j] = (uint32_t)(lo.size() - part_lo[j]);
+    }
+    p.nch1 = lo.size();
+    p.ch_lo = p.put(lo); p.ch_cnt = p.put(cnt); p.ch_seg = p.put(seg);
+    size_t nsrc = p.nch1;
+    const size_t Kf = std::max<size_t>(K, 2);
+    while (m && *std::max_element(part_cnt.begin(), part_cnt.end()) > 64) {
+        lo.clear(); cnt.clear();
+        for (size_t j = 0; j < m; j++) {
+            const uint64_t a = part_lo[j], len = part_cnt[j];
+            part_lo[j] = lo.size();
+            for (uint64_t c = 0; c < len; c += Kf) { lo.push_back(a + c); cnt.push_back((uint32_t)std::min<uint64_t>(Kf, len - c)); }
+            part_cnt[j] = (uint32_t)(lo.size() - part_lo[j]);
+        }
+        p.folds.push_back({nsrc, lo.size(), p.put(lo), p.put(cnt)});
+        nsrc = lo.size();
+    }
+    p.nlast = nsrc;
+    p.seg_lo = p.put(part_lo); p.seg_cnt = p.put(part_cnt);
+}
+// The segmented sum on the device, everything on stream s, not synchronised (the temporaries come from the call's arena, `p.blob` is read
+// by the copy: both stay alive until the caller synchronises).  group 1 / 2; jac: d_pts are in-memory Jacobian records (no d_in_inf).
+// d_out: m affine records, d_out_inf: m bytes (1 infinity, bad_code for a segment with an index >= npk, 0 otherwise).
+int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_t npk, const u32* d_idx, const SegPlan& p, u8* d_out, u8* d_out_inf,
+               u8 bad_code, hipStream_t s) {
+    const size_t m = p.m;
+    if (m == 0) return BLSMI_OK;
+    const size_t words = (size_t)(group == 1 ? 3 : 6) * NL + 1;
+    DBuf plan, bad, a, b;
+    HIPCHK(plan.alloc(p.blob.size())); HIPCHK(bad.alloc(m));
+    HIPCHK(hipMemcpyAsync(plan.p, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(bad.p, 0, m, s));
+    auto at64 = [&](size_t off) { return reinterpret_cast<const u64*>(plan.as<u8>() + off); };
+    auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(plan.as<u8>() + off); };
+    HIPCHK(a.alloc(sizeof(i32) * words * p.nch1));
+    const size_t n1 = p.nch1;
+    if (n1) {
+        if (group == 1 && jac) hipLaunchKernelGGL(k_g1_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        else if (group == 1) hipLaunchKernelGGL(k_g1_segsum_chunk, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        else if (jac) hipLaunchKernelGGL(k_g2_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        else hipLaunchKernelGGL(k_g2_segsum_chunk_pair, dim3((unsigned)((n1 + PT - 1) / PT)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+    }
+    i32* src = a.as<i32>();
+    for (const SegPlan::Fold& f : p.folds) {
+        DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * f.nch));
+        if (group == 1) hipLaunchKernelGGL(k_g1_segsum_fold, dim3(nblocks(f.nch)), dim3(WG), 0, s, (const i32*)src, f.nsrc, at64(f.lo), at32(f.cnt), d.as<i32>(), f.nch);
+        else hipLaunchKernelGGL(k_g2_segsum_fold_pair, dim3((unsigned)((f.nch + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)src, f.nsrc, at64(f.lo), at32(f.cnt), d.as<i32>(), f.nch);
+        src = d.as<i32>();
+    }
+    if (group == 1) hipLaunchKernelGGL(k_g1_segsum_final, dim3((unsigned)m), dim3(WG), 0, s, (const i32*)src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), (const u8*)bad.as<u8>(), bad_code, d_out, d_out_inf);
+    else hipLaunchKernelGGL(k_g2_segsum_final, dim3((unsigned)m), dim3(WG), 0, s, (const i32*)src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), (const u8*)bad.as<u8>(), bad_code, d_out, d_out_inf);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+size_t segsum_chunk_of(size_t total) { const size_t K = tune().segsum_chunk; return K ? K : segsum_auto_chunk(total); }
+// host forms: everything checked here first, then one lease
+int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m,
+                       uint8_t* out, uint8_t* out_inf) {
+    if (m == 0) return BLSMI_OK;
+    if (!out || !out_inf || (npk && !pts)) return BLSMI_E_ARG;
+    int rc = segsum_check(npk, idx, seg_off, m);
+    if (rc) return rc;
+    const size_t pb = group == 1 ? 96 : 192, pin = rec_bytes(pb, jac), total = seg_off[m];
+    LOCK_AND_INIT();
+    SegPlan plan;
+    segsum_plan(seg_off, m, segsum_chunk_of(total), plan);
+    DBuf dp, di, dx, dout, dinf;
+    HIPCHK(dp.alloc(pin * npk)); HIPCHK(di.alloc(npk)); HIPCHK(dx.alloc(sizeof(uint32_t) * total)); HIPCHK(dout.alloc(pb * m)); HIPCHK(dinf.alloc(m));
+    if (npk) HIPCHK(hipMemcpyAsync(dp.p, pts, pin * npk, hipMemcpyHostToDevice, g_stream));
+    if (in_inf && !jac && npk) HIPCHK(hipMemcpyAsync(di.p, in_inf, npk, hipMemcpyHostToDevice, g_stream));
+    if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
+    rc = segsum_dev(group, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, pb * m, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(out_inf, dinf.p, m, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+// the m + 1 offsets of a _dev call, fetched to the host (those calls synchronise anyway) and checked: from 0, non-decreasing
+int segsum_fetch_offsets(const void* d_seg_off, size_t m, std::vector<uint64_t>& off) {
+    off.resize(m + 1);
+    HIPCHK(hipMemcpyAsync(off.data(), d_seg_off, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    if (off[0] != 0) return BLSMI_E_ARG;
+    for (size_t j = 0; j < m; j++) if (off[j + 1] < off[j]) return BLSMI_E_ARG;
+    return BLSMI_OK;
+}
+int sum_segmented_dev_api(int group, const void* d_pts, const void* d_in_inf, size_t npk, const void* d_idx, const void* d_seg_off, size_t m,
+                          void* d_out, void* d_out_inf, void* stream) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_seg_off || !d_out || !d_out_inf || (npk && !d_pts)) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    std::vector<uint64_t> off;
+    int rc = segsum_fetch_offsets(d_seg_off, m, off);
+    if (rc) return rc;
+    SegPlan plan;
+    segsum_plan(off.data(), m, segsum_chunk_of(off[m]), plan);
+    rc = segsum_dev(group, false, d_pts, (const u8*)d_in_inf, npk, (const u32*)d_idx, plan, (u8*)d_out, (u8*)d_out_inf, 2, g_stream);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_g1_sum_segmented(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(1, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf);
+}
+BLSMI_API int blsmi_g2_sum_segmented(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(2, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf);
+}
+BLSMI_API int blsmi_g1_sum_segmented_jac(const uint64_t* pts_jac, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(1, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, npk, idx, seg_off, m, out, out_inf);
+}
+BLSMI_API int blsmi_g2_sum_segmented_jac(const uint64_t* pts_jac, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(2, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, npk, idx, seg_off, m, out, out_inf);
+}
+BLSMI_API int blsmi_g1_sum_segmented_dev(const void* d_pts, const void* d_in_inf, size_t npk, const void* d_idx, const void* d_seg_off, size_t m, void* d_out, void* d_out_inf, void* stream) {
+    return sum_segmented_dev_api(1, d_pts, d_in_inf, npk, d_idx, d_seg_off, m, d_out, d_out_inf, stream);
+}
+BLSMI_API int blsmi_g2_sum_segmented_dev(const void* d_pts, const void* d_in_inf, size_t npk, const void* d_idx, const void* d_seg_off, size_t m, void* d_out, void* d_out_inf, void* stream) {
+    return sum_segmented_dev_api(2, d_pts, d_in_inf, npk, d_idx, d_seg_off, m, d_out, d_out_inf, stream);
+}
+
+// Item j of a batch: VerifyAggregateCommon(sig_j, committee j, msg_j) -- the committee's sum (the segmented sum above, on aux[1], while the
+// m messages are hashed), its flags (infinity, empty, bad index) as bit 0 of the tuple flags, then the m Verify()s of verify_batch_dev,
+// routed by m as any batch of m tuples.  One lease, one device.  The caller holds the lease; every buffer is on its device.
+namespace {
+int agg_common_batch_dev(int kind, const void* d_msgs, const void* d_off_or_domain, const void* d_pks, size_t npk, const u32* d_idx, const SegPlan& plan,
+                         const void* d_sigs, void* d_ok, bool pks_jac) {
+    const Kind k = kind_of(kind);
+    const size_t m = plan.m;
+    DBuf dagg, dinf;
+    HIPCHK(dagg.alloc((size_t)k.pk_bytes * m)); HIPCHK(dinf.alloc(m));
+    HIPCHK(tl_ctx->ensure_aux());
+    hipStream_t side = tl_ctx->aux[1];
+    HIPCHK(hipEventRecord(tl_ctx->fork, g_stream)); HIPCHK(hipStreamWaitEvent(side, tl_ctx->fork, 0));   // (the keys and indices may still be arriving on g_stream)
+    int rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, pks_jac, d_pks, nullptr, npk, d_idx, plan, dagg.as<u8>(), dinf.as<u8>(), 1, side);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(tl_ctx->join[1], side));
+    return verify_batch_dev(kind, d_msgs, d_off_or_domain, dagg.p, d_sigs, dinf.p, d_ok, m, g_stream, nullptr, tl_ctx->join[1]);   // synchronises
+}
+int agg_common_batch_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off,
+                          const uint8_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m, int fmt = 0) {
+    if (m == 0) return BLSMI_OK;
+    if (!sigs || !off_or_domain || (!ok && !ok_bitmap) || (npk && !pks)) return BLSMI_E_ARG;
+    if (kind != 2) {                                                       // message offsets: from 0, non-decreasing
+        if (off_or_domain[0] != 0) return BLSMI_E_ARG;
+        for (size_t j = 0; j < m; j++) if (off_or_domain[j + 1] < off_or_domain[j]) return BLSMI_E_ARG;
+    }
+    const size_t msg_bytes = kind == 2 ? 32 * m : (size_t)off_or_domain[m];
+    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (m + 1);
+    if (msg_bytes && !msgs) return BLSMI_E_ARG;
+    int rc = segsum_check(npk, idx, seg_off, m);
+    if (rc) return rc;
+    const Kind k = kind_of(kind);
+    const bool pj = (fmt & FMT_PK_JAC) != 0;
+    const size_t pin = rec_bytes(k.pk_bytes, pj), total = seg_off[m];
+    { std::lock_guard<std::mutex> lk(g_mu); int rc0 = ensure_init_default(); if (rc0) return rc0; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    SegPlan plan;
+    segsum_plan(seg_off, m, segsum_chunk_of(total), plan);
+    DBuf dp, dx, dm, doff, ds, dok;
+    HIPCHK(dp.alloc(pin * npk)); HIPCHK(dx.alloc(sizeof(uint32_t) * total)); HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes));
+    HIPCHK(ds.alloc((size_t)k.sig_bytes * m)); HIPCHK(dok.alloc(m));
+    if (npk) HIPCHK(hipMemcpyAsync(dp.p, pks, pin * npk, hipMemcpyHostToDevice, g_stream));
+    if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
+    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
+    rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, m, g_stream);
+    if (rc) return rc;
+    rc = agg_common_batch_dev(kind, dm.p, doff.p, dp.p, npk, idx ? dx.as<u32>() : nullptr, plan, ds.p, dok.p, pj);
+    if (rc) return rc;
+    std::vector<uint8_t> tmp;
+    uint8_t* dst = ok;
+    if (!dst) { tmp.resize(m); dst = tmp.data(); }
+    HIPCHK(hipMemcpyAsync(dst, dok.p, m, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
+    if (ok_bitmap) pack_bitmap(dst, ok_bitmap, m);
+    return BLSMI_OK;
+}
+template <int KIND>
+static int agg_common_batch_dev_api(const void* d_msgs, const void* d_off_or_domain, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off,
+                                    const void* d_sigs, void* d_ok, size_t m, void* stream) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_msgs || !d_off_or_domain || !d_seg_off || !d_sigs || !d_ok || (npk && !d_pks)) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    std::vector<uint64_t> off;
+    int rc = segsum_fetch_offsets(d_seg_off, m, off);
+    if (rc) return rc;
+    SegPlan plan;
+    segsum_plan(off.data(), m, segsum_chunk_of(off[m]), plan);
+    return agg_common_batch_dev(KIND, d_msgs, d_off_or_domain, d_pks, npk, (const u32*)d_idx, plan, d_sigs, d_ok, false);
+}
+}  // namespace
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch(const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off,
+                                                         const uint8_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(0, msgs, msg_off, pks, npk, idx, seg_off, sigs, ok, ok_bitmap, m);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch(const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off,
+                                                         const uint8_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(1, msgs, msg_off, pks, npk, idx, seg_off, sigs, ok, ok_bitmap, m);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, size_t npk, const uint32_t* idx,
+                                                                     const uint64_t* seg_off, const uint8_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, npk, idx, seg_off, sigs, ok, ok_bitmap, m);
+}
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch_jac(const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off,
+                                                             const uint64_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(0, msgs, msg_off, reinterpret_cast<const uint8_t*>(pks), npk, idx, seg_off, reinterpret_cast<const uint8_t*>(sigs), ok, ok_bitmap, m, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_jac(const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off,
+                                                             const uint64_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(1, msgs, msg_off, reinterpret_cast<const uint8_t*>(pks), npk, idx, seg_off, reinterpret_cast<const uint8_t*>(sigs), ok, ok_bitmap, m, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, size_t npk, const uint32_t* idx,
+                                                                         const uint64_t* seg_off, const uint64_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t m) {
+    return agg_common_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), reinterpret_cast<const uint8_t*>(pks), npk, idx, seg_off,
+                                 reinterpret_cast<const uint8_t*>(sigs), ok, ok_bitmap, m, FMT_JAC);
+}
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch_dev(const void* d_msgs, const void* d_msg_off, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off,
+                                                             const void* d_sigs, void* d_ok, size_t m, void* stream) {
+    return agg_common_batch_dev_api<0>(d_msgs, d_msg_off, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_dev(const void* d_msgs, const void* d_msg_off, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off,
+                                                             const void* d_sigs, void* d_ok, size_t m, void* stream) {
+    return agg_common_batch_dev_api<1>(d_msgs, d_msg_off, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
+}
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const void* d_msgs32, const void* d_domain, const void* d_pks, size_t npk, const void* d_idx,
+                                                                         const void* d_seg_off, const void* d_sigs, void* d_ok, size_t m, void* stream) {
+    return agg_common_batch_dev_api<2>(d_msgs32, d_domain, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
+}

@@ -1034,3 +1034,126 @@ def g1pubs_sign_with_domain_batch_jac(msgs32, domain8, sks):
     buf = _u8(b"".join(bytes(m) for m in msgs32), 32 * n)
     d = _u8(domain8, 8)
     return _sign_jac(_lib().blsmi_g1pubs_sign_with_domain_batch_jac, 288, n, (_p8(buf), _p8(d)), sks)
+
+
+# ---- committees (blsmi 0.9): segmented sums and batches of VerifyAggregateCommon ------------------------------------------------
+def seg_offsets(sizes):
+    """Segment sizes -> the m + 1 offsets (uint64) of the segmented entry points: [0, s0, s0 + s1, ...]"""
+    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
+    if len(sizes):
+        np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
+    return off
+
+
+def _seg_args(idx, seg_off):
+    so = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.uint32)
+    return so, (ix.ctypes.data_as(C.POINTER(C.c_uint32)) if ix is not None and ix.size else None), ix
+
+
+def _sum_segmented(fn, pb, rec, pts, npk, idx, seg_off, in_inf=None):
+    so, pidx, _keep = _seg_args(idx, seg_off)
+    m = so.size - 1
+    if rec == pb:
+        p = _u8(pts, pb * npk) if npk else np.zeros(1, np.uint8)
+        pp = _p8(p)
+    else:
+        p, pp = _j64(pts, rec * npk)
+    f = _u8(in_inf, npk) if in_inf is not None else None
+    out = np.zeros(max(1, pb * m), dtype=np.uint8)
+    oinf = np.zeros(max(1, m), dtype=np.uint8)
+    args = (pp, _p8(f), C.c_size_t(npk)) if rec == pb else (pp, C.c_size_t(npk))
+    _check(fn(*args, pidx, so.ctypes.data_as(_u64p), C.c_size_t(m), _p8(out), _p8(oinf)), "sum_segmented")
+    return out[:pb * m].tobytes(), oinf[:m].copy()
+
+
+def g1_sum_segmented(pts, npk, idx, seg_off, in_inf=None):
+    """m sums of affine G1 points: segment j = pts[idx[k]] for seg_off[j] <= k < seg_off[j + 1] (idx None: k itself).
+    -> (m*96 affine bytes, out_inf: 1 infinity, 0 otherwise)"""
+    return _sum_segmented(_lib().blsmi_g1_sum_segmented, 96, 96, pts, npk, idx, seg_off, in_inf)
+
+
+def g2_sum_segmented(pts, npk, idx, seg_off, in_inf=None):
+    return _sum_segmented(_lib().blsmi_g2_sum_segmented, 192, 192, pts, npk, idx, seg_off, in_inf)
+
+
+def g1_sum_segmented_jac(pts_jac, npk, idx, seg_off):
+    """the same over in-memory G1 points (144 bytes each) -> affine records and flags"""
+    return _sum_segmented(_lib().blsmi_g1_sum_segmented_jac, 96, 144, pts_jac, npk, idx, seg_off)
+
+
+def g2_sum_segmented_jac(pts_jac, npk, idx, seg_off):
+    return _sum_segmented(_lib().blsmi_g2_sum_segmented_jac, 192, 288, pts_jac, npk, idx, seg_off)
+
+
+def sum_segmented_dev(group, d_pts, d_in_inf, npk, d_idx, d_seg_off, m, d_out, d_out_inf, stream=0):
+    """device-pointer form: out_inf bytes 0 / 1 / 2 (2: the segment holds an index >= npk, record zeroed)"""
+    fn = _lib().blsmi_g1_sum_segmented_dev if group == "g1" else _lib().blsmi_g2_sum_segmented_dev
+    _check(fn(C.c_void_p(d_pts or 0), C.c_void_p(d_in_inf or 0), C.c_size_t(npk), C.c_void_p(d_idx or 0), C.c_void_p(d_seg_off or 0), C.c_size_t(m),
+              C.c_void_p(d_out or 0), C.c_void_p(d_out_inf or 0), C.c_void_p(stream)), "sum_segmented_dev")
+
+
+def _agg_common_batch(fn, name, pkb, sgb, jac, head, pks, npk, idx, seg_off, sigs):
+    so, pidx, _keep = _seg_args(idx, seg_off)
+    m = so.size - 1
+    if jac:
+        p, pp = _j64(pks, pkb * npk)
+        s, ps = _j64(sigs, sgb * m)
+    else:
+        p = _u8(pks, pkb * npk) if npk else np.zeros(1, np.uint8)
+        s = _u8(sigs, sgb * m) if m else np.zeros(1, np.uint8)
+        pp, ps = _p8(p), _p8(s)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    bm = np.zeros(max(1, (m + 7) // 8), dtype=np.uint8)
+    _check(fn(*head, pp, C.c_size_t(npk), pidx, so.ctypes.data_as(_u64p), ps, _p8(ok), _p8(bm), C.c_size_t(m)), name)
+    return ok[:m].copy(), bm[:(m + 7) // 8].copy()
+
+
+def _msg_head(msgs):
+    buf, off = _msgs(msgs)
+    return (buf, off), (_p8(buf), off.ctypes.data_as(_u64p))
+
+
+def g2pubs_verify_aggregate_common_batch(msgs, pks, npk, idx, seg_off, sigs):
+    """item j: VerifyAggregateCommon(sigs[j], {pks[idx[k]] : seg_off[j] <= k < seg_off[j + 1]}, msgs[j]) -> (m verdict bytes, bitmap)"""
+    mm, head = _msg_head(msgs)
+    return _agg_common_batch(_lib().blsmi_g2pubs_verify_aggregate_common_batch, "g2pubs_verify_aggregate_common_batch", 192, 96, False, head, pks, npk, idx, seg_off, sigs)
+
+
+def g1pubs_verify_aggregate_common_batch(msgs, pks, npk, idx, seg_off, sigs):
+    mm, head = _msg_head(msgs)
+    return _agg_common_batch(_lib().blsmi_g1pubs_verify_aggregate_common_batch, "g1pubs_verify_aggregate_common_batch", 96, 192, False, head, pks, npk, idx, seg_off, sigs)
+
+
+def g1pubs_verify_aggregate_common_with_domain_batch(msgs32, domain8, pks, npk, idx, seg_off, sigs):
+    m = len(seg_off) - 1
+    buf, d = _u8(msgs32, 32 * m) if m else np.zeros(1, np.uint8), _u8(domain8, 8)
+    return _agg_common_batch(_lib().blsmi_g1pubs_verify_aggregate_common_with_domain_batch, "g1pubs_verify_aggregate_common_with_domain_batch", 96, 192, False,
+                             (_p8(buf), _p8(d)), pks, npk, idx, seg_off, sigs)
+
+
+def g2pubs_verify_aggregate_common_batch_jac(msgs, pks, npk, idx, seg_off, sigs):
+    """the same over in-memory keys (288 bytes) and signatures (144 bytes)"""
+    mm, head = _msg_head(msgs)
+    return _agg_common_batch(_lib().blsmi_g2pubs_verify_aggregate_common_batch_jac, "g2pubs_verify_aggregate_common_batch_jac", 288, 144, True, head, pks, npk, idx, seg_off, sigs)
+
+
+def g1pubs_verify_aggregate_common_batch_jac(msgs, pks, npk, idx, seg_off, sigs):
+    mm, head = _msg_head(msgs)
+    return _agg_common_batch(_lib().blsmi_g1pubs_verify_aggregate_common_batch_jac, "g1pubs_verify_aggregate_common_batch_jac", 144, 288, True, head, pks, npk, idx, seg_off, sigs)
+
+
+def g1pubs_verify_aggregate_common_with_domain_batch_jac(msgs32, domain8, pks, npk, idx, seg_off, sigs):
+    m = len(seg_off) - 1
+    buf, d = _u8(msgs32, 32 * m) if m else np.zeros(1, np.uint8), _u8(domain8, 8)
+    return _agg_common_batch(_lib().blsmi_g1pubs_verify_aggregate_common_with_domain_batch_jac, "g1pubs_verify_aggregate_common_with_domain_batch_jac", 144, 288, True,
+                             (_p8(buf), _p8(d)), pks, npk, idx, seg_off, sigs)
+
+
+def verify_aggregate_common_batch_dev(group, d_msgs, d_off_or_domain, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream=0, domain=False):
+    """device-pointer forms: group "g2pubs" / "g1pubs" (domain=True: d_msgs holds m*32 bytes, d_off_or_domain the 8-byte domain); verdicts in d_ok"""
+    lib = _lib()
+    fn = lib.blsmi_g2pubs_verify_aggregate_common_batch_dev if group == "g2pubs" else \
+        (lib.blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev if domain else lib.blsmi_g1pubs_verify_aggregate_common_batch_dev)
+    _check(fn(C.c_void_p(d_msgs or 0), C.c_void_p(d_off_or_domain or 0), C.c_void_p(d_pks or 0), C.c_size_t(npk), C.c_void_p(d_idx or 0),
+              C.c_void_p(d_seg_off or 0), C.c_void_p(d_sigs or 0), C.c_void_p(d_ok or 0), C.c_size_t(m), C.c_void_p(stream)), "verify_aggregate_common_batch_dev")

@@ -10,7 +10,7 @@ pairing and hash operation runs in the HIP kernels of libblsmi.so (no CPU fallba
 plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks.
 """
 from . import engine
-from ._groups import DeserializeError, Point, all_in_memory, point_sum  # noqa: F401
+from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum  # noqa: F401
 
 SIG_GROUP, PK_GROUP = 2, 1
 
@@ -222,3 +222,36 @@ def SignWithDomainBatch(msgs32, secret_scalars, domain8):
     n = len(msgs32)
     out, inf = engine.g1pubs_sign_with_domain_batch(msgs32, domain8, b"".join(secret_scalars))
     return [Signature(Point(None if inf[i] else out[i].tobytes(), SIG_GROUP)) for i in range(n)]
+
+
+def AggregatePublicKeysBatch(committees):
+    """[AggregatePublicKeys(c) for c in committees] as one segmented sum on the device"""
+    return [PublicKey(p) for p in committee_sums([[k.p for k in c] for c in committees], PK_GROUP)]
+
+
+def VerifyAggregateCommonBatch(sigs, committees, msgs):
+    """[sigs[j].VerifyAggregateCommon(committees[j], msgs[j]) for j] in one call: the committee sums beside the hash, then one verify batch"""
+    m = len(sigs)
+    if not (len(committees) == len(msgs) == m):
+        raise ValueError("length mismatch")
+    if m == 0:
+        return []
+    jac, keys, npk, off, sg = committee_batch_args([[k.p for k in c] for c in committees], [s.s for s in sigs])
+    fn = engine.g1pubs_verify_aggregate_common_batch_jac if jac else engine.g1pubs_verify_aggregate_common_batch
+    ok, _ = fn(msgs, keys, npk, None, off, sg)
+    return [bool(x) for x in ok]
+
+
+def VerifyAggregateCommonWithDomainBatch(sigs, committees, msgs32, domain8):
+    """[VerifyAggregateCommonWithDomain(sigs[j], committees[j], msgs32[j], domain8) for j] in one call"""
+    m = len(sigs)
+    if not (len(committees) == len(msgs32) == m):
+        raise ValueError("length mismatch")
+    if m == 0:
+        return []
+    if any(len(x) != 32 for x in msgs32):
+        raise ValueError("messages must be 32 bytes")
+    jac, keys, npk, off, sg = committee_batch_args([[k.p for k in c] for c in committees], [s.s for s in sigs])
+    fn = engine.g1pubs_verify_aggregate_common_with_domain_batch_jac if jac else engine.g1pubs_verify_aggregate_common_with_domain_batch
+    ok, _ = fn(b"".join(bytes(x) for x in msgs32), domain8, keys, npk, None, off, sg)
+    return [bool(x) for x in ok]

@@ -11,7 +11,7 @@ plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks, and Prepar
 through G2AffineToPrepared (g2.go:639-801) ONCE into tables resident on the device instead of on every Verify (pairing.go:140-147).
 """
 from . import engine
-from ._groups import DeserializeError, Point, all_in_memory, point_sum  # noqa: F401
+from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum  # noqa: F401
 
 SIG_GROUP, PK_GROUP = 1, 2
 
@@ -204,3 +204,21 @@ def SignBatch(msgs, secret_scalars):
     n = len(msgs)
     out, inf = engine.g2pubs_sign_batch(msgs, b"".join(secret_scalars))    # one call: hash, then multiply, on the device
     return [Signature(Point(None if inf[i] else out[i].tobytes(), SIG_GROUP)) for i in range(n)]
+
+
+def AggregatePublicKeysBatch(committees):
+    """[AggregatePublicKeys(c) for c in committees] as one segmented sum on the device"""
+    return [PublicKey(p) for p in committee_sums([[k.p for k in c] for c in committees], PK_GROUP)]
+
+
+def VerifyAggregateCommonBatch(sigs, committees, msgs):
+    """[sigs[j].VerifyAggregateCommon(committees[j], msgs[j]) for j] in one call: the committee sums beside the hash, then one verify batch"""
+    m = len(sigs)
+    if not (len(committees) == len(msgs) == m):
+        raise ValueError("length mismatch")
+    if m == 0:
+        return []
+    jac, keys, npk, off, sg = committee_batch_args([[k.p for k in c] for c in committees], [s.s for s in sigs])
+    fn = engine.g2pubs_verify_aggregate_common_batch_jac if jac else engine.g2pubs_verify_aggregate_common_batch
+    ok, _ = fn(msgs, keys, npk, None, off, sg)
+    return [bool(x) for x in ok]

@@ -73,7 +73,9 @@ void blsmi_shutdown(void);
  * blsmi_prefer_cpu, blsmi_debug_device_leases and the BLSMI_DEVICE_ALIAS test hook; no existing prototype changes.  0.6 adds the *_jac forms
  * (the reference's in-memory Jacobian / Montgomery points at the boundary); no existing prototype changes.  0.7 adds blsmi_set_row_threshold (the lane-row layout for
  * 2 048 .. 8 192 tuples), the "row_side" / "hash_row_min" / "hash_row_max" / "hash_quad_min" / "hash_quad_max" / "hash_oct_min" / "hash_oct_max" / "hash_g1_quad_min" / "hash_g1_quad_max" options and BLSMI_OP_LANE_ROW / BLSMI_OP_ROW_*_STEP / BLSMI_OP_ROW_G2_* / BLSMI_OP_ROW_CLEAR_H2 for blsmi_debug_op; no existing prototype changes.  0.8 adds the randomised batch verification (blsmi_g?pubs_*verify*_batch_rlc[_jac]),
- * the "rlc_min" option, BLSMI_E_RNG and BLSMI_OP_G1_MUL_U64; no existing prototype changes. */
+ * the "rlc_min" option, BLSMI_E_RNG and BLSMI_OP_G1_MUL_U64; no existing prototype changes.  0.9 adds the segmented sums (blsmi_g?_sum_segmented[_jac|_dev]),
+ * the batches of VerifyAggregateCommon over key committees (blsmi_g?pubs_verify_aggregate_common*_batch[_jac|_dev]) and the "segsum_chunk" option;
+ * no existing prototype changes. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -134,6 +136,8 @@ int blsmi_prefer_cpu(int shape, size_t n);
  * so a change applies to the calls that start after it and never to part of a call in flight):
  *   "agg_cofactor_pow" (BLSMI_AGG_COFACTOR_POW, default 1), "msm_sort" (BLSMI_MSM_SORT, default 1), "dup_force_sort" (BLSMI_DUP_FORCE_SORT, 0),
  *   "rlc_min" (BLSMI_RLC_MIN, default 32768): the randomised batch verification (*_verify_batch_rlc) of fewer tuples runs the per-tuple path,
+ *   "segsum_chunk" (BLSMI_SEGSUM_CHUNK, default 0 = automatic: 8, doubled up to 64 while more than 2^16 chunks would remain): positions per lane of
+ *   the segmented sums (blsmi_g?_sum_segmented, the *_verify_aggregate_common*_batch entry points),
  *   "lat_rolled" (BLSMI_LAT_ROLLED, default 1; 0: small Pairing calls run the straight-line copy of their level program instead of the one
  *   whose squaring runs are loops), "row_side" (BLSMI_ROW_SIDE, default 1: a Verify in the row layout runs its signature side beside the hash -- g1pubs, and g2pubs with "row_side_g2pubs"),
  *   "hash_row_min" / "hash_row_max" (defaults 2048 / 4096; no environment name): HashG2 of that many messages clears its cofactor sixteen lanes per message
@@ -500,6 +504,63 @@ int blsmi_debug_hash_tail(int kind, const uint8_t *pts, uint8_t *out, uint8_t *g
  * back to the cleared one. */
 int blsmi_debug_hash_g1_finish(const uint8_t *pts /* n*192 */, int clear /* 2: the four-lanes-per-message tail + its redo pass; *special = messages redone */, uint8_t *out /* n*96 */, int *special, size_t n);
 int blsmi_debug_hash_redo(int kind, const uint8_t *msgs, const uint64_t *off_or_domain, const uint8_t *good, uint8_t *out /* in/out */, size_t n);
+
+/* ---- committees (blsmi 0.9) ----------------------------------------------------------------------------------------------------------
+ * Segmented sums: m sums over ragged, index-addressed subsets of one table of npk points.  Segment j is
+ * {pts[idx[k]] : seg_off[j] <= k < seg_off[j + 1]} (idx NULL: the positions k themselves); seg_off has m + 1 entries, seg_off[0] = 0,
+ * non-decreasing.  out: m affine records (the all-zero record for infinity), out_inf[j] = 1 for infinity (the empty segment included),
+ * else 0.  Each record is the bytes blsmi_g?_sum gives for the gathered points, whatever "segsum_chunk" is.  The host forms check
+ * the offsets and every index (< npk) and return BLSMI_E_ARG before any device work; the _dev forms read seg_off back to the host
+ * (offsets that do not start at 0 or decrease: BLSMI_E_ARG) and mark a segment holding an index >= npk with out_inf = 2 and the
+ * all-zero record, reading nothing past the table.  _jac: the points as the Go values hold them (144 / 288 bytes each, z == 0 is
+ * infinity, no in_inf).  m = 0 returns BLSMI_OK. */
+int blsmi_g1_sum_segmented(const uint8_t *pts /* npk*96 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk,
+                           const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
+                           uint8_t *out /* m*96 */, uint8_t *out_inf /* m */);
+int blsmi_g2_sum_segmented(const uint8_t *pts /* npk*192 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk,
+                           const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
+                           uint8_t *out /* m*192 */, uint8_t *out_inf /* m */);
+int blsmi_g1_sum_segmented_jac(const uint64_t *pts_jac /* npk*18 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off, size_t m,
+                               uint8_t *out /* m*96 */, uint8_t *out_inf /* m */);
+int blsmi_g2_sum_segmented_jac(const uint64_t *pts_jac /* npk*36 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off, size_t m,
+                               uint8_t *out /* m*192 */, uint8_t *out_inf /* m */);
+int blsmi_g1_sum_segmented_dev(const void *d_pts, const void *d_in_inf, size_t npk, const void *d_idx, const void *d_seg_off, size_t m,
+                               void *d_out, void *d_out_inf, void *stream);
+int blsmi_g2_sum_segmented_dev(const void *d_pts, const void *d_in_inf, size_t npk, const void *d_idx, const void *d_seg_off, size_t m,
+                               void *d_out, void *d_out_inf, void *stream);
+/* Batches of VerifyAggregateCommon (g2pubs/bls.go:275-278, g1pubs/bls.go:287-297).  Item j:
+ *   VerifyAggregateCommon(sig_j, {pks[idx[k]] : seg_off[j] <= k < seg_off[j + 1]}, msg_j)
+ * with msg_j = msgs[msg_off[j] .. msg_off[j + 1]) (with_domain: the 32 bytes msgs32 + 32 j under the common 8-byte domain).  Each verdict
+ * is exactly what the single-call entry point returns for that committee, message and signature: 0 for an empty committee, for one that
+ * sums to infinity and for the all-zero signature record.  The committee sums run beside the hash of the m messages, then the m checks
+ * run as one verify batch of m tuples, on one device.  ok: m verdict bytes, ok_bitmap: (m + 7) / 8 bytes, LSB first; either may be NULL,
+ * not both.  The host forms check offsets and indices as the segmented sums do (BLSMI_E_ARG); the _dev forms take every buffer on one of
+ * the library's devices (d_ok: m bytes; d_msg_off / d_domain as blsmi_g?pubs_verify_batch_dev) and give verdict 0 to an item whose
+ * committee holds an index >= npk.  _jac: keys and signatures as the Go values hold them.  m = 0 returns BLSMI_OK. */
+int blsmi_g2pubs_verify_aggregate_common_batch(const uint8_t *msgs, const uint64_t *msg_off /* m+1 */, const uint8_t *pks /* npk*192 */, size_t npk,
+                                               const uint32_t *idx, const uint64_t *seg_off /* m+1 */, const uint8_t *sigs /* m*96 */,
+                                               uint8_t *ok /* m, may be NULL */, uint8_t *ok_bitmap /* may be NULL */, size_t m);
+int blsmi_g1pubs_verify_aggregate_common_batch(const uint8_t *msgs, const uint64_t *msg_off /* m+1 */, const uint8_t *pks /* npk*96 */, size_t npk,
+                                               const uint32_t *idx, const uint64_t *seg_off /* m+1 */, const uint8_t *sigs /* m*192 */,
+                                               uint8_t *ok, uint8_t *ok_bitmap, size_t m);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch(const uint8_t *msgs32 /* m*32 */, const uint8_t domain[8], const uint8_t *pks /* npk*96 */, size_t npk,
+                                                           const uint32_t *idx, const uint64_t *seg_off /* m+1 */, const uint8_t *sigs /* m*192 */,
+                                                           uint8_t *ok, uint8_t *ok_bitmap, size_t m);
+int blsmi_g2pubs_verify_aggregate_common_batch_jac(const uint8_t *msgs, const uint64_t *msg_off, const uint64_t *pks /* npk*36 */, size_t npk,
+                                                   const uint32_t *idx, const uint64_t *seg_off, const uint64_t *sigs /* m*18 */,
+                                                   uint8_t *ok, uint8_t *ok_bitmap, size_t m);
+int blsmi_g1pubs_verify_aggregate_common_batch_jac(const uint8_t *msgs, const uint64_t *msg_off, const uint64_t *pks /* npk*18 */, size_t npk,
+                                                   const uint32_t *idx, const uint64_t *seg_off, const uint64_t *sigs /* m*36 */,
+                                                   uint8_t *ok, uint8_t *ok_bitmap, size_t m);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* npk*18 */, size_t npk,
+                                                               const uint32_t *idx, const uint64_t *seg_off, const uint64_t *sigs /* m*36 */,
+                                                               uint8_t *ok, uint8_t *ok_bitmap, size_t m);
+int blsmi_g2pubs_verify_aggregate_common_batch_dev(const void *d_msgs, const void *d_msg_off, const void *d_pks, size_t npk, const void *d_idx,
+                                                   const void *d_seg_off, const void *d_sigs, void *d_ok, size_t m, void *stream);
+int blsmi_g1pubs_verify_aggregate_common_batch_dev(const void *d_msgs, const void *d_msg_off, const void *d_pks, size_t npk, const void *d_idx,
+                                                   const void *d_seg_off, const void *d_sigs, void *d_ok, size_t m, void *stream);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const void *d_msgs32, const void *d_domain, const void *d_pks, size_t npk, const void *d_idx,
+                                                               const void *d_seg_off, const void *d_sigs, void *d_ok, size_t m, void *stream);
 
 #ifdef __cplusplus
 }

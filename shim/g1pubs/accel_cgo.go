@@ -338,3 +338,59 @@ func SignWithDomainBatch(msgs [][32]byte, keys []*SecretKey, domain [8]byte) []*
 		u8(secretBytes(keys)), &sg[0], C.size_t(n)), "g1pubs_sign_with_domain_batch_jac")
 	return sigsFromWords(sg, n)
 }
+
+// VerifyAggregateCommonBatch is the batch form of VerifyAggregateCommon (blsmi 0.9): out[j] = sigs[j].VerifyAggregateCommon(committees[j],
+// msgs[j]) in one library call -- the m committee sums run on the device beside the hash of the m messages, then one verify batch.
+func VerifyAggregateCommonBatch(sigs []*Signature, committees [][]*PublicKey, msgs [][]byte) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(committees) != n || len(msgs) != n {
+		panic("blsmi: VerifyAggregateCommonBatch: length mismatch")
+	}
+	seg := make([]C.uint64_t, n+1) // committee j = keys[seg[j]:seg[j+1]]: the idx = NULL form
+	var keys []*PublicKey
+	for j, c := range committees {
+		keys = append(keys, c...)
+		seg[j+1] = seg[j] + C.uint64_t(len(c))
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(keys)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_aggregate_common_batch_jac(u8(m), &off[0], u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), u8(ok), nil, C.size_t(n)),
+		"g1pubs_verify_aggregate_common_batch_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// VerifyAggregateCommonWithDomainBatch: out[j] = sigs[j].VerifyAggregateCommonWithDomain(committees[j], msgs[j], domain) in one call.
+func VerifyAggregateCommonWithDomainBatch(sigs []*Signature, committees [][]*PublicKey, msgs [][32]byte, domain [8]byte) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(committees) != n || len(msgs) != n {
+		panic("blsmi: VerifyAggregateCommonWithDomainBatch: length mismatch")
+	}
+	seg := make([]C.uint64_t, n+1) // committee j = keys[seg[j]:seg[j+1]]: the idx = NULL form
+	var keys []*PublicKey
+	for j, c := range committees {
+		keys = append(keys, c...)
+		seg[j+1] = seg[j] + C.uint64_t(len(c))
+	}
+	pk := packKeys(keys)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_aggregate_common_with_domain_batch_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
+		u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), u8(ok), nil, C.size_t(n)), "g1pubs_verify_aggregate_common_with_domain_batch_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}

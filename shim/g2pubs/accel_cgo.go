@@ -308,3 +308,32 @@ func SignBatch(msgs [][]byte, keys []*SecretKey) []*Signature {
 	}
 	return out
 }
+
+// VerifyAggregateCommonBatch is the batch form of VerifyAggregateCommon (blsmi 0.9): out[j] = sigs[j].VerifyAggregateCommon(committees[j],
+// msgs[j]) in one library call -- the m committee sums run on the device beside the hash of the m messages, then one verify batch.
+func VerifyAggregateCommonBatch(sigs []*Signature, committees [][]*PublicKey, msgs [][]byte) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(committees) != n || len(msgs) != n {
+		panic("blsmi: VerifyAggregateCommonBatch: length mismatch")
+	}
+	seg := make([]C.uint64_t, n+1) // committee j = keys[seg[j]:seg[j+1]]: the idx = NULL form
+	var keys []*PublicKey
+	for j, c := range committees {
+		keys = append(keys, c...)
+		seg[j+1] = seg[j] + C.uint64_t(len(c))
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(keys)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g2pubs_verify_aggregate_common_batch_jac(u8(m), &off[0], u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), u8(ok), nil, C.size_t(n)),
+		"g2pubs_verify_aggregate_common_batch_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
