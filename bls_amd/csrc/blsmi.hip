@@ -65,7 +65,6 @@ std::mutex g_mu;
 // g_coll_mu BEFORE g_mu (blsmi_trim only try_locks it while holding g_mu).
 std::mutex g_coll_mu;
 std::condition_variable g_cv;          // a context was released (lease waiters and shutdown both wait here: notify_all)
-bool g_pair_layout = true;              // lane-pair pairing kernels (two lanes per tuple); BLSMI_LAYOUT=single for one tuple per lane
 bool g_ready = false;
 char g_version[200] = "blsmi 0.9 (uninitialised)";
 
@@ -205,7 +204,6 @@ thread_local Ctx* tl_ctx = nullptr;
 #define g_stream (tl_ctx->stream)
 #define g_ws (tl_ctx->ws)
 #define g_gens (tl_ctx->dev->gens)
-bool g_use_gen_lines = true;           // BLSMI_GEN_LINES=0 recomputes the generator's lines per tuple (A/B switch)
 // optional per-kernel timing (HIP events on the launch stream) for bench.py's roofline object; results are per calling thread
 std::atomic<bool> g_profile{false};
 thread_local float tl_last_ms[2] = {0.f, 0.f};
@@ -294,44 +292,23 @@ int init_device(Device& d) {            // caller holds g_mu
 // per-call opt-out of the endomorphism ladders (the *_ex entry points with BLSMI_MUL_ANY_POINT): set on every thread that works for such a call
 thread_local bool tl_mul_any = false;
 struct MulAny { bool saved; explicit MulAny(bool on) : saved(tl_mul_any) { tl_mul_any = on; } ~MulAny() { tl_mul_any = saved; } };
-std::atomic<bool> g_mul_subgroup{Tuning{}.mul_subgroup}; // scalar multiplication through the endomorphisms (multiplicands in the subgroup); BLSMI_MUL_GENERIC=1 / blsmi_set_mul_assume_subgroup(0): plain ladder
-std::atomic<size_t> g_lat_max{Tuning{}.lat_max};    // BLSMI_LAT_MAX, blsmi_set_latency_threshold (read by every call, written rarely).  The two paths meet at ~10 000 tuples
-                                        // for pairings and verifies alike (tools/crossover.py: 8192 pairings 8.4 ms against 10.7, 16 384: 16.4 against 11.3)
-// Three layouts by batch size (pairings and verifies alike; tools/midsize.py): one tuple per WAVE up to min(g_lat_max, g_quad_min) tuples,
-// one per lane QUAD up to g_quad_max (16 384 tuples = one wave on every SIMD), one per lane PAIR beyond (65 536 fill the chip twice over).
-std::atomic<size_t> g_quad_max{Tuning{}.quad_max};  // BLSMI_QUAD_MAX, blsmi_set_quad_threshold (0: no quad kernels)
-std::atomic<size_t> g_quad_min{Tuning{}.quad_min};   // BLSMI_QUAD_MIN: the quad kernels take over from the latency path here already (pairings: 5.9 ms flat against 1 ms per 1 024 tuples; verifies 8.7 against 1.5)
-// The thresholds above are a LONE caller's: one tuple per wave finishes 4 096 pairings in 4.3 ms where the quad kernels take their flat 6 ms.
-// Callers that arrive together are a different matter (tools/midsize_concurrency.py): the latency path saturates the chip at 1.04 M pairings/s
-// whatever the number of calls in flight (its waves are bounded by LDS, 9 per CU), the quad kernels at 2.8 M/s (two 8 192-tuple calls take
-// the 6 ms of one).  So the choice goes by what the DEVICE carries: a call of at least g_crowd_floor tuples takes the quad kernels when its
-// tuples plus those of the other calls in flight pass the lone crossover (floor 1 536: four callers x 2 048 pairings 7.9 -> 6.1 ms a call; at 1 024
-// the sum never passes the crossover with four contexts).  A call registers its tuples at its first layout question and
-// keeps the answer's input for its whole life (one call never sees two different loads); ~CtxLease takes them off again.
-std::atomic<bool> g_crowd_quad{Tuning{}.crowd_quad};        // BLSMI_CROWD_QUAD / blsmi_set_option("crowd_quad")
-std::atomic<size_t> g_crowd_floor{Tuning{}.crowd_floor};     // BLSMI_CROWD_FLOOR / blsmi_set_option("crowd_floor")
-std::atomic<size_t> g_assume_load{Tuning{}.assume_load};        // blsmi_set_option("assume_load"): test hook, tuples pretended to be in flight from other calls
+// ---- the options ------------------------------------------------------------------------------------------------------------------
+// One Tuning and one bit per row of route.h's table ("set through the API": initialisation leaves the row alone), behind a mutex of their own -- taken AFTER
+// g_mu where both are held, never the other way round.  The setters write it at any time, with or without a device; initialisation applies the environment to it
+// once (load_env); every call copies it once.  ADVICE r05: an option set before the first entry point, or before a re-initialisation after blsmi_shutdown, survives it.
+std::mutex g_opt_mu;
+Tuning g_opt;
+uint64_t g_opt_explicit = 0;
+// The options as they stand now.  CtxLease takes one such snapshot per call; each call's every kernel choice reads it (tune(), route.h), so
+// that an option set while calls are in flight applies to the calls that start after it, and never to half of one.
+Tuning tuning_now() { std::lock_guard<std::mutex> lk(g_opt_mu); return g_opt; }
+template <class M> void set_member(M Tuning::*m, M v) { std::lock_guard<std::mutex> lk(g_opt_mu); g_opt.*m = v; g_opt_explicit |= (uint64_t)1 << row_of(m); }
 inline size_t call_load(size_t n) {
     Ctx* c = tl_ctx;
     if (!c || !c->dev) return 0;
     if (!c->load_set) { c->load_others = c->dev->load.fetch_add(n, std::memory_order_relaxed); c->load_n = n; c->load_set = true; }
     return c->load_others + c->tune.assume_load;
 }
-// A fourth layout between the wave and the quad (round 6, k_pairing_row.hip): one tuple per DPP ROW of sixteen lanes.  g_row_min .. g_row_max
-// tuples (2 048 .. 8 192) of a LONE caller take it: 4 096 tuples are one wave on every SIMD there (a quarter of the SIMDs in the quad layout, four waves of
-// 3.3 x the instructions on the one-tuple-per-wave path).  When other calls are in flight on the device the choice above stands (the quad
-// kernels spend fewer lane-instructions per tuple: 12.6 M against 18 M).  blsmi_set_row_threshold / BLSMI_ROW_MIN / BLSMI_ROW_MAX; max 0: off.
-std::atomic<size_t> g_hash_row_min{Tuning{}.hash_row_min}, g_hash_row_max{Tuning{}.hash_row_max};   // blsmi_set_option("hash_row_min" / "hash_row_max"): HashG2 of this many messages clears its cofactor in the lane-row layout (k_clear_h2_row; max 0: never)
-std::atomic<size_t> g_hash_quad_min{Tuning{}.hash_quad_min}, g_hash_quad_max{Tuning{}.hash_quad_max};   // "hash_quad_min" / "hash_quad_max": ... four lanes per message (k_clear_h2_quad)
-std::atomic<size_t> g_hash_oct_min{Tuning{}.hash_oct_min}, g_hash_oct_max{Tuning{}.hash_oct_max};   // "hash_oct_min" / "hash_oct_max": ... eight lanes per message (k_clear_h2_oct, oct_g2.inc); takes precedence over the row and quad tails
-std::atomic<size_t> g_hash_g1_quad_min{Tuning{}.hash_g1_quad_min}, g_hash_g1_quad_max{Tuning{}.hash_g1_quad_max};   // "hash_g1_quad_min" / "hash_g1_quad_max": HashG1's tail four lanes per message (k_hash_g1_finish_quad)
-std::atomic<size_t> g_swu_row_max{Tuning{}.swu_row_max};   // "swu_row_max": the SWU maps of HashG1 / HashG2 run a ROW of sixteen lanes per map (k_swu_g?_rows) above BLSMI_SWU_WAVE_MAX and up to here; 0: never
-std::atomic<bool> g_row_side_g2pubs{Tuning{}.row_side_g2pubs};   // "row_side_g2pubs": ... for g2pubs too (the signature side over the generator's table as a kernel of its own: 4 096 tuples 3.23 against 3.55 ms, verify_host.inc)
-std::atomic<bool> g_row_side{Tuning{}.row_side};     // BLSMI_ROW_SIDE / blsmi_set_option("row_side"): a Verify in the row layout runs its signature side beside the hash (verify_host.inc)
-std::atomic<size_t> g_row_min{Tuning{}.row_min};   // (tools/midsize4.py: 2 048 pairings 2.08 against 2.21 ms on the wave path, g1pubs verifies 4.45 against 4.72, g2pubs 3.66 against 3.57; 1 024: 2.05 against 1.54)
-std::atomic<size_t> g_row_max{Tuning{}.row_max};   // (8 192 pairings 4.0 ms against the quad kernels' flat 5.7; 12 288: 6+ against 5.7)
-// A Pairing call's row range reaches half again as far (route.h: pairing_layout): with no hash beside its two kernels the row kernels stay ahead of the
-// quad kernels' flat 5.7 ms up to 12 288 tuples (three waves per SIMD: 5.34 ms; verifies cross at ~10 000: 12 288 g2pubs verifies 8.96 against 7.95 ms).
 inline unsigned qblocks(size_t n) { return (unsigned)((n + QT - 1) / QT); }
 inline unsigned rblocks(size_t n) { return (unsigned)((n + RT - 1) / RT); }
 // The options of the call this thread serves: the snapshot CtxLease took (tuning_now)
@@ -342,79 +319,21 @@ inline bool mul_subgroup() { return !tl_mul_any && tune().mul_subgroup; }
 inline u32 lat_lds_bytes(size_t prog_offset) { u32 nslot; memcpy(&nslot, blsmi_lat_blob + prog_offset + 8, 4); return nslot * 80; }   // k_lat.hip: SLOT_WORDS * 4
 // ---- the environment is read ONCE, at initialisation (under g_mu), never from an entry point ---------------------------------------
 // getenv racing a setenv in another thread is undefined (glibc), and a variable read per call silently changes what a concurrent caller
-// gets.  Every BLSMI_* variable is therefore read here and nowhere else; what the A/B tests flip at run time are the three
-// atomics below, through blsmi_set_option.  The variables are listed in include/blsmi.h ("Environment").
+// gets.  load_env reads the options' variables (apply_env, route.h: one reader for every row of the table) and the process's
+// own: the combiner and the RCCL path here, streams, shards and the arena cap in ensure_init_list.  include/blsmi.h lists them ("Environment").
 struct EnvCfg {
-    size_t swu_wave_max = 512;          // BLSMI_SWU_WAVE_MAX: the smallest hashes / decompressions run one WAVE per field exponentiation up to here (measured: 0.68 against 0.96 ms at 512 messages, 1.18 against 0.98 at 1 024)
-    bool hash_g1_split = true;          // BLSMI_HASH_G1_SPLIT
-    bool hash_g2_pair = true;           // BLSMI_HASH_G2_PAIR=0 keeps the one-lane HashG2 kernel
-    unsigned hash_g2_pair_redo_every = 0;   // BLSMI_HASH_G2_PAIR_REDO_EVERY (tests: exercise the redo pass)
-    bool cofac2_pair = true;            // BLSMI_COFAC2_PAIR=0 keeps the fused one-lane HashG2WithDomain kernel
-    long long sig_side_max = -1;        // BLSMI_SIG_SIDE_MAX (-1: the per-package defaults)
-    size_t side_max = 131072;           // BLSMI_SIDE_MAX
-    size_t fixed_wave_max = 2048;       // BLSMI_FIXED_WAVE_MAX
-    size_t msm_bucket_min = (size_t)1 << 17;   // BLSMI_MSM_BUCKET_MIN
     size_t combine_max = 1024; int combine_wait_us = 150, combine_inflight_max = 2; bool combine_debug = false;   // BLSMI_COMBINE_*
     char rccl_path[512] = {0};          // BLSMI_RCCL_PATH: librccl for a process that has none mapped yet (a Go binary has no torch to bring it)
 } g_env;
-std::atomic<bool> g_agg_cofactor_pow{Tuning{}.agg_cofactor_pow};    // BLSMI_AGG_COFACTOR_POW / blsmi_set_option("agg_cofactor_pow")
-std::atomic<bool> g_msm_sort{Tuning{}.msm_sort};            // BLSMI_MSM_SORT / blsmi_set_option("msm_sort")
-std::atomic<bool> g_lat_rolled{Tuning{}.lat_rolled};          // BLSMI_LAT_ROLLED / blsmi_set_option("lat_rolled"): 0 = small Pairing calls take the STRAIGHT-LINE copy of their level program (pairing1s) instead of the one with rolled squaring runs (A/B)
-std::atomic<size_t> g_combine_mid_max{8192};  // BLSMI_COMBINE_MID_MAX / blsmi_set_option("combine_mid_max"): concurrent Verify calls of BLSMI_COMBINE_MAX <= n < this many tuples merge into one launch (verify_host.inc); 0: never
-std::atomic<size_t> g_rlc_min{Tuning{}.rlc_min};     // BLSMI_RLC_MIN / blsmi_set_option("rlc_min"): the randomised batch verification takes the per-tuple path below this many tuples (verify_host.inc)
-std::atomic<size_t> g_segsum_chunk{Tuning{}.segsum_chunk};     // BLSMI_SEGSUM_CHUNK / blsmi_set_option("segsum_chunk"): positions per lane of the segmented sums (0: automatic, verify_host.inc)
-std::atomic<bool> g_dup_force_sort{Tuning{}.dup_force_sort};     // BLSMI_DUP_FORCE_SORT / blsmi_set_option("dup_force_sort"): test hook, the duplicate screen's fallback on every call
-// Options a caller has set through the API (blsmi_set_option, blsmi_set_*_threshold, blsmi_set_mul_assume_subgroup) keep their values when the library
-// (re-)initialises: the environment and the defaults apply only to what was never set explicitly (a set_option before the first entry point,
-// or before a re-initialisation after blsmi_shutdown, was silently overwritten here).
-enum { X_AGG_POW, X_MSM_SORT, X_DUP_SORT, X_LAT_ROLLED, X_CROWD_QUAD, X_COMBINE_MID, X_CROWD_FLOOR, X_ROW_SIDE, X_LAT_MAX, X_QUAD_MAX, X_ROW, X_MUL_SUBGROUP, X_RLC_MIN, X_SEGSUM_CHUNK };
-std::atomic<unsigned> g_explicit{0};
-inline void set_explicit(int bit) { g_explicit.fetch_or(1u << bit, std::memory_order_relaxed); }
-inline bool is_explicit(int bit) { return (g_explicit.load(std::memory_order_relaxed) >> bit) & 1u; }
 void load_env() {                       // caller holds g_mu; runs once per initialisation
     auto num = [](const char* name, size_t dflt) { const char* v = getenv(name); return v ? (size_t)strtoull(v, nullptr, 10) : dflt; };
-    auto flag = [](const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; };
-    g_env.swu_wave_max = num("BLSMI_SWU_WAVE_MAX", 512);
-    g_env.hash_g1_split = flag("BLSMI_HASH_G1_SPLIT", true);
-    g_env.hash_g2_pair = flag("BLSMI_HASH_G2_PAIR", true);
-    g_env.hash_g2_pair_redo_every = (unsigned)num("BLSMI_HASH_G2_PAIR_REDO_EVERY", 0);
-    g_env.cofac2_pair = flag("BLSMI_COFAC2_PAIR", true);
-    { const char* v = getenv("BLSMI_SIG_SIDE_MAX"); g_env.sig_side_max = v ? atoll(v) : -1LL; }
-    g_env.side_max = num("BLSMI_SIDE_MAX", 131072);
-    g_env.fixed_wave_max = num("BLSMI_FIXED_WAVE_MAX", 2048);
-    g_env.msm_bucket_min = num("BLSMI_MSM_BUCKET_MIN", (size_t)1 << 17);
     g_env.combine_max = num("BLSMI_COMBINE_MAX", 1024);
-    if (!is_explicit(X_COMBINE_MID)) g_combine_mid_max = num("BLSMI_COMBINE_MID_MAX", 8192);
     g_env.combine_wait_us = (int)num("BLSMI_COMBINE_WAIT_US", 150);
     g_env.combine_inflight_max = std::max(1, (int)num("BLSMI_COMBINE_INFLIGHT", 2));
     g_env.combine_debug = getenv("BLSMI_COMBINE_DEBUG") != nullptr;
     { const char* v = getenv("BLSMI_RCCL_PATH"); snprintf(g_env.rccl_path, sizeof g_env.rccl_path, "%s", v ? v : ""); }
-    if (!is_explicit(X_AGG_POW)) { const char* v = getenv("BLSMI_AGG_COFACTOR_POW"); g_agg_cofactor_pow = !(v && v[0] == '0'); }
-    if (!is_explicit(X_MSM_SORT)) { const char* v = getenv("BLSMI_MSM_SORT"); g_msm_sort = !(v && v[0] == '0'); }
-    if (!is_explicit(X_DUP_SORT)) g_dup_force_sort = getenv("BLSMI_DUP_FORCE_SORT") != nullptr;
-    if (!is_explicit(X_LAT_ROLLED)) { const char* v = getenv("BLSMI_LAT_ROLLED"); g_lat_rolled = !(v && v[0] == '0'); }
-    if (!is_explicit(X_CROWD_QUAD)) { const char* v = getenv("BLSMI_CROWD_QUAD"); g_crowd_quad = !(v && v[0] == '0'); }
-    if (!is_explicit(X_CROWD_FLOOR)) if (const char* v = getenv("BLSMI_CROWD_FLOOR")) g_crowd_floor = (size_t)strtoull(v, nullptr, 10);
-    if (!is_explicit(X_RLC_MIN)) g_rlc_min = num("BLSMI_RLC_MIN", Tuning{}.rlc_min);
-    if (!is_explicit(X_SEGSUM_CHUNK)) g_segsum_chunk = num("BLSMI_SEGSUM_CHUNK", Tuning{}.segsum_chunk);
-}
-// The options as they stand now, copied out of the atomics above and the settings fixed at initialisation: the only place that reads the
-// atomics for a call.  CtxLease takes one such snapshot per call; each call's every kernel choice reads it (tune(), route.h), so that an
-// option set while calls are in flight applies to the calls that start after it, and never to half of one.
-Tuning tuning_now() {
-    constexpr auto rx = std::memory_order_relaxed;
-    Tuning t;
-    t.lat_max = g_lat_max.load(rx); t.quad_max = g_quad_max.load(rx); t.quad_min = g_quad_min.load(rx); t.row_min = g_row_min.load(rx); t.row_max = g_row_max.load(rx);
-    t.crowd_quad = g_crowd_quad.load(rx); t.crowd_floor = g_crowd_floor.load(rx); t.assume_load = g_assume_load.load(rx);
-    t.hash_row_min = g_hash_row_min.load(rx); t.hash_row_max = g_hash_row_max.load(rx); t.hash_quad_min = g_hash_quad_min.load(rx); t.hash_quad_max = g_hash_quad_max.load(rx);
-    t.hash_oct_min = g_hash_oct_min.load(rx); t.hash_oct_max = g_hash_oct_max.load(rx); t.hash_g1_quad_min = g_hash_g1_quad_min.load(rx); t.hash_g1_quad_max = g_hash_g1_quad_max.load(rx);
-    t.swu_row_max = g_swu_row_max.load(rx); t.row_side = g_row_side.load(rx); t.row_side_g2pubs = g_row_side_g2pubs.load(rx);
-    t.agg_cofactor_pow = g_agg_cofactor_pow.load(rx); t.msm_sort = g_msm_sort.load(rx); t.lat_rolled = g_lat_rolled.load(rx); t.dup_force_sort = g_dup_force_sort.load(rx);
-    t.mul_subgroup = g_mul_subgroup.load(rx); t.pair_layout = g_pair_layout; t.use_gen_lines = g_use_gen_lines; t.hash_g2_pair = g_env.hash_g2_pair; t.hash_g1_split = g_env.hash_g1_split;
-    t.swu_wave_max = g_env.swu_wave_max; t.sig_side_max = g_env.sig_side_max; t.fixed_wave_max = g_env.fixed_wave_max;
-    t.rlc_min = g_rlc_min.load(rx);
-    t.segsum_chunk = g_segsum_chunk.load(rx);
-    return t;
+    std::lock_guard<std::mutex> lk(g_opt_mu);
+    apply_env(g_opt, g_opt_explicit, [](const char* name) { return getenv(name); });
 }
 // devs[0..ndev): HIP ordinals.  Caller holds g_mu.
 int ensure_init_list(const int* devs, int ndev) {
@@ -427,21 +346,8 @@ int ensure_init_list(const int* devs, int ndev) {
         for (int j = 0; j < i; j++) if (devs[j] == devs[i] && !g_alias) return BLSMI_E_ARG;
     }
     load_env();
-    const char* lay = getenv("BLSMI_LAYOUT");
-    g_pair_layout = !(lay && std::string(lay) == "single");      // default: lane-pair kernels; BLSMI_LAYOUT=single selects one tuple per lane
     if (const char* ns = getenv("BLSMI_STREAMS")) { int v = atoi(ns); g_nctx = v < 1 ? 1 : (v > MAX_CTX ? MAX_CTX : v); }
-    const char* gl = getenv("BLSMI_GEN_LINES");
-    g_use_gen_lines = !(gl && std::string(gl) == "0");
-    if (!is_explicit(X_LAT_MAX)) if (const char* v = getenv("BLSMI_LAT_MAX")) g_lat_max = (size_t)strtoull(v, nullptr, 10);
-    if (!is_explicit(X_QUAD_MAX)) if (const char* v = getenv("BLSMI_QUAD_MAX")) g_quad_max = (size_t)strtoull(v, nullptr, 10);
-    if (const char* v = getenv("BLSMI_QUAD_MIN")) g_quad_min = (size_t)strtoull(v, nullptr, 10);
-    if (!is_explicit(X_ROW)) {
-        if (const char* v = getenv("BLSMI_ROW_MIN")) g_row_min = (size_t)strtoull(v, nullptr, 10);
-        if (const char* v = getenv("BLSMI_ROW_MAX")) g_row_max = (size_t)strtoull(v, nullptr, 10);
-    }
-    if (!is_explicit(X_ROW_SIDE)) { const char* v = getenv("BLSMI_ROW_SIDE"); g_row_side = !(v && v[0] == '0'); }
     if (const char* v = getenv("BLSMI_ARENA_KEEP_MB")) g_arena_keep = (size_t)strtoull(v, nullptr, 10) << 20;
-    if (!is_explicit(X_MUL_SUBGROUP)) if (const char* v = getenv("BLSMI_MUL_GENERIC")) g_mul_subgroup = std::string(v) == "0";
     g_force_rccl = getenv("BLSMI_FORCE_RCCL") != nullptr && std::string(getenv("BLSMI_FORCE_RCCL")) != "0";
     for (int i = 0; i < ndev; i++) {
         g_dev[i].id = devs[i]; g_dev[i].index = i; g_dev[i].leases = 0;
@@ -872,11 +778,7 @@ static int pairing_dev(const void* d_g1, const void* d_g2, void* d_out, size_t n
 // Enable/disable per-kernel HIP-event timing of blsmi_pairing_batch[_dev]; read back (by the calling thread, for its own
 // last call) with blsmi_last_kernel_ms.
 // Batches of at most `max_tuples` tuples take the latency path (one tuple per wave, k_lat.hip); 0 switches it off.
-BLSMI_API int blsmi_set_latency_threshold(size_t max_tuples) {
-    set_explicit(X_LAT_MAX);
-    g_lat_max.store(max_tuples);
-    return BLSMI_OK;
-}
+BLSMI_API int blsmi_set_latency_threshold(size_t max_tuples) { set_member(&Tuning::lat_max, max_tuples); return BLSMI_OK; }
 // Latency hint for the host shim: 1 when n operations of `shape` in ONE call are expected to finish sooner on one core of the upstream
 // pure-Go path than on the device.  A lone call costs the depth of one wave walking the whole computation (flat in n up to ~2 000
 // operations), so the break-even is n* = device latency of a lone call / CPU time per operation -- both measured by bench.py's
@@ -897,51 +799,17 @@ BLSMI_API int blsmi_prefer_cpu(int shape, size_t n) {
     if (n == 0) return 1;
     return (double)n * rows[shape].cpu_ms_per_op < rows[shape].gpu_ms_lone_call ? 1 : 0;
 }
-BLSMI_API int blsmi_set_quad_threshold(size_t max_tuples) {
-    set_explicit(X_QUAD_MAX);
-    g_quad_max.store(max_tuples);
-    return BLSMI_OK;
-}
-BLSMI_API int blsmi_set_row_threshold(size_t min_tuples, size_t max_tuples) {
-    set_explicit(X_ROW);
-    g_row_min.store(min_tuples);
-    g_row_max.store(max_tuples);
-    return BLSMI_OK;
-}
-BLSMI_API int blsmi_set_mul_assume_subgroup(int on) {
-    set_explicit(X_MUL_SUBGROUP);
-    g_mul_subgroup.store(on != 0);
-    return BLSMI_OK;
-}
-// Run-time switches of code paths that produce identical results (A/B tests, soaks): name = "agg_cofactor_pow" (large g2pubs aggregates
-// raise their Miller product to 1 - x instead of clearing n hash points), "msm_sort" (device radix sort against the exact histogram passes),
-// "dup_force_sort" (the duplicate screen's host-sort fallback on every call); the layout switches (include/blsmi.h).  Each call reads every option
-// once, when it starts (tuning_now): a change applies to the calls that start after it.  The verdicts do not depend on them.
+BLSMI_API int blsmi_set_quad_threshold(size_t max_tuples) { set_member(&Tuning::quad_max, max_tuples); return BLSMI_OK; }
+BLSMI_API int blsmi_set_row_threshold(size_t min_tuples, size_t max_tuples) { set_member(&Tuning::row_min, min_tuples); set_member(&Tuning::row_max, max_tuples); return BLSMI_OK; }
+BLSMI_API int blsmi_set_mul_assume_subgroup(int on) { set_member(&Tuning::mul_subgroup, on != 0); return BLSMI_OK; }
+// Run-time switches of code paths that produce identical results (A/B tests, soaks) and the layout switches: the Set::option rows of route.h's table, by member
+// name (include/blsmi.h).  Each call reads every option once, when it starts (tuning_now): a change applies to the calls that start after it.  The verdicts do not depend on them.
 BLSMI_API int blsmi_set_option(const char* name, long long value) {
     if (!name) return BLSMI_E_ARG;
-    const std::string n(name);
-    if (n == "agg_cofactor_pow") { set_explicit(X_AGG_POW); g_agg_cofactor_pow.store(value != 0); }
-    else if (n == "msm_sort") { set_explicit(X_MSM_SORT); g_msm_sort.store(value != 0); }
-    else if (n == "dup_force_sort") { set_explicit(X_DUP_SORT); g_dup_force_sort.store(value != 0); }
-    else if (n == "lat_rolled") { set_explicit(X_LAT_ROLLED); g_lat_rolled.store(value != 0); }
-    else if (n == "crowd_quad") { set_explicit(X_CROWD_QUAD); g_crowd_quad.store(value != 0); }
-    else if (n == "row_side") { set_explicit(X_ROW_SIDE); g_row_side.store(value != 0); }
-    else if (n == "row_side_g2pubs") g_row_side_g2pubs.store(value != 0);
-    else if (n == "hash_row_min") g_hash_row_min.store((size_t)std::max(0LL, value));
-    else if (n == "hash_row_max") g_hash_row_max.store((size_t)std::max(0LL, value));
-    else if (n == "swu_row_max") g_swu_row_max.store((size_t)std::max(0LL, value));
-    else if (n == "hash_oct_min") g_hash_oct_min.store((size_t)std::max(0LL, value));
-    else if (n == "hash_oct_max") g_hash_oct_max.store((size_t)std::max(0LL, value));
-    else if (n == "hash_g1_quad_min") g_hash_g1_quad_min.store((size_t)std::max(0LL, value));
-    else if (n == "hash_g1_quad_max") g_hash_g1_quad_max.store((size_t)std::max(0LL, value));
-    else if (n == "hash_quad_min") g_hash_quad_min.store((size_t)std::max(0LL, value));
-    else if (n == "hash_quad_max") g_hash_quad_max.store((size_t)std::max(0LL, value));
-    else if (n == "combine_mid_max") { set_explicit(X_COMBINE_MID); g_combine_mid_max.store((size_t)std::max(0LL, value)); }
-    else if (n == "crowd_floor") { set_explicit(X_CROWD_FLOOR); g_crowd_floor.store((size_t)std::max(0LL, value)); }
-    else if (n == "assume_load") g_assume_load.store((size_t)std::max(0LL, value));
-    else if (n == "rlc_min") { set_explicit(X_RLC_MIN); g_rlc_min.store((size_t)std::max(0LL, value)); }
-    else if (n == "segsum_chunk") { set_explicit(X_SEGSUM_CHUNK); g_segsum_chunk.store((size_t)std::max(0LL, value)); }
-    else return BLSMI_E_ARG;
+    std::lock_guard<std::mutex> lk(g_opt_mu);
+    const int row = set_by_name(g_opt, name, value, true);
+    if (row < 0) return BLSMI_E_ARG;
+    g_opt_explicit |= (uint64_t)1 << row;
     return BLSMI_OK;
 }
 BLSMI_API int blsmi_set_profiling(int on) {
@@ -1140,7 +1008,7 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
         // the generator as the common multiplicand (PrivToPub): the device's fixed-base table -- 32 mixed additions, no doublings.
         // Small calls: one scalar per wave (the 32 table entries meet in a tree of additions across the lanes).
         const i32* table = PB == 96 ? g_gens.fixed1 : g_gens.fixed2;
-        if (m <= g_env.fixed_wave_max && m <= tune().lat_max) {
+        if (m <= tune().fixed_wave_max && m <= tune().lat_max) {
             prof_mark(PB == 96 ? "k_g1_mul_fixed_wave" : "k_g2_mul_fixed_wave");
             if (PB == 96) hipLaunchKernelGGL(k_g1_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
             else hipLaunchKernelGGL(k_g2_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
@@ -1170,16 +1038,16 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
     // of the doublings; arbitrary curve points (blsmi_set_mul_assume_subgroup(0)): the plain fixed-window ladder
     const bool glv = mul_subgroup();
     if (glv) {
-        prof_mark(PB == 192 ? (g_pair_layout ? "k_g2_mul_glv_pair" : "k_g2_mul_glv") : "k_g1_mul_glv");
-        if (PB == 192 && g_pair_layout) hipLaunchKernelGGL(k_g2_mul_glv_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
+        prof_mark(PB == 192 ? (tune().pair_layout ? "k_g2_mul_glv_pair" : "k_g2_mul_glv") : "k_g1_mul_glv");
+        if (PB == 192 && tune().pair_layout) hipLaunchKernelGGL(k_g2_mul_glv_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
         else if (PB == 192) hipLaunchKernelGGL(k_g2_mul_glv, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
         else hipLaunchKernelGGL(k_g1_mul_glv, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
     }
-    prof_mark(PB == 192 ? (g_pair_layout ? "k_g2_mul_pair" : "k_g2_mul") : "k_g1_mul");
-    if (PB == 192 && g_pair_layout)                                        // G2: lane-pair kernel, two waves per SIMD
+    prof_mark(PB == 192 ? (tune().pair_layout ? "k_g2_mul_pair" : "k_g2_mul") : "k_g1_mul");
+    if (PB == 192 && tune().pair_layout)                                   // G2: lane-pair kernel, two waves per SIMD
         hipLaunchKernelGGL(k_g2_mul_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
     else
         hipLaunchKernelGGL(kernel, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
@@ -1428,8 +1296,8 @@ static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scal
     hipLaunchKernelGGL(k_msm_class_hist, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, cls.as<u32>());
     hipLaunchKernelGGL(k_msm_class_scan, dim3(1), dim3(256), 0, s, (const u32*)cls.as<u32>(), cls.as<u32>() + 256, cls.as<u32>() + 512);
     hipLaunchKernelGGL(k_msm_class_scatter, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, (const u32*)(cls.as<u32>() + 256), cls.as<u32>() + 512, perm.as<u32>());
-    prof_mark(W == 6 ? (g_pair_layout ? "k_g2_msm_bucket_pair" : "k_g2_msm_bucket") : "k_g1_msm_bucket");
-    if (W == 6 && g_pair_layout)                                           // G2: a lane pair per bucket, two waves per SIMD
+    prof_mark(W == 6 ? (tune().pair_layout ? "k_g2_msm_bucket_pair" : "k_g2_msm_bucket") : "k_g1_msm_bucket");
+    if (W == 6 && tune().pair_layout)                                      // G2: a lane pair per bucket, two waves per SIMD
         hipLaunchKernelGGL(k_g2_msm_bucket_pair, dim3((unsigned)((nb + PT - 1) / PT)), dim3(WG), 0, s, d_pts, (const u32*)idx.as<u32>(), (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), n, c, nb);
     else
         hipLaunchKernelGGL(k.bucket, dim3(nblocks(nb)), dim3(WG), 0, s, d_pts, (const u32*)idx.as<u32>(), (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), n, c, nb);
@@ -1546,7 +1414,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     else hipLaunchKernelGGL(k_g2_msm_bucket_raw_pair, dim3((unsigned)((nb + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)raw.as<i32>(), items, (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), slice_stride, nb);
     // running sums per chunk WITHOUT the per-lane multiplication, then the fold that carries the odd-element sums along (msm.inc):
     // one addition deep per level; out come, per window, X, L and O_0 .. O_{m-1}
-    const bool pairk = W == 6 && g_pair_layout;                            // G2: a lane pair per chunk / per sum, two waves per SIMD
+    const bool pairk = W == 6 && tune().pair_layout;                       // G2: a lane pair per chunk / per sum, two waves per SIMD
     prof_mark(W == 6 ? (pairk ? "k_g2_msm_chunk2_pair" : "k_g2_msm_chunk2") : "k_g1_msm_chunk2");
     if (pairk) hipLaunchKernelGGL(k_g2_msm_chunk2_pair, dim3((unsigned)((nct + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
     else if (W == 6) hipLaunchKernelGGL(k_g2_msm_chunk2, dim3(nblocks(nct)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
@@ -1590,7 +1458,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
 template <int PB, int W, class KM, class K0, class K1, class K2>
 static int msm_dev_core(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s,
                         const std::function<int()>& points_arrive = {}) {
-    const size_t bucket_min = g_env.msm_bucket_min;
+    const size_t bucket_min = tune().msm_bucket_min;
     int rc = BLSMI_E_SKEW;
     bool arrived = !points_arrive;                                         // the host form hands over its copy of the points: issued at the latest before the first kernel that reads them
     auto arrive_once = [&]() -> int { if (arrived) return BLSMI_OK; arrived = true; return points_arrive(); };

@@ -90,7 +90,7 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     }
     // HashG2 of a large batch: a lane pair per message, two waves per SIMD (k_hash_pair.hip); BLSMI_HASH_G2_PAIR=0 keeps the one-lane kernel
     if (kind == 1 && r.path != HashPath::plain) {
-        const unsigned redo_every = g_env.hash_g2_pair_redo_every;
+        const unsigned redo_every = (unsigned)tune().hash_g2_pair_redo_every;
         DBuf good; HIPCHK(good.alloc(n, s));
         const bool g2_oct_tail = r.path == HashPath::g2_oct, g2_row_tail = r.path == HashPath::g2_row;
         if (r.path != HashPath::g2_pair) {
@@ -118,7 +118,7 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     // HashG2WithDomain of a large batch in two kernels: the search and the root, one message per lane with the wave sharing its
     // messages' candidates (k_tai_g2_wave), then ScaleByCofactor with a lane pair per point at two waves per SIMD (k_cofac2_pair);
     // BLSMI_COFAC2_PAIR=0 keeps the one fused one-lane kernel
-    const bool cofac_pair = g_env.cofac2_pair;
+    const bool cofac_pair = tune().cofac2_pair;
     if (kind == 2 && cofac_pair) {
         DBuf pts; HIPCHK(pts.alloc((size_t)192 * n, s));
         prof_mark("k_tai_g2_wave");
@@ -194,7 +194,7 @@ int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host
     const u8* tp = kind == 0 ? (const u8*)d_sigs : g_gens.g1; const size_t sp = kind == 0 ? 96 : 0;
     const u8* tq = kind == 0 ? g_gens.g2 : (const u8*)d_sigs; const size_t sq = kind == 0 ? 0 : 192;
     if (side == Side::row)
-        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, tp, sp, tq, sq, f, n, (kind == 0 && g_use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
+        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, tp, sp, tq, sq, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
     else
         hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), st, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
                            tp, sp, tq, sq, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
@@ -230,7 +230,7 @@ int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_
     const void* d_inf = flags.p;
     const u8* a0 = kind == 0 ? (const u8*)d_sigs : g_gens.g1; const size_t s0 = kind == 0 ? 96 : 0;
     const u8* b0 = kind == 0 ? g_gens.g2 : (const u8*)d_sigs; const size_t t0 = kind == 0 ? 0 : 192;
-    const i32* pre = (kind == 0 && g_use_gen_lines) ? g_gens.lines : nullptr;   // g2pubs: Q0 = G2 generator, prepared at start-up
+    const i32* pre = (kind == 0 && tune().use_gen_lines) ? g_gens.lines : nullptr;   // g2pubs: Q0 = G2 generator, prepared at start-up
     const i32* pre_pair = pre ? g_gens.lines_pair : nullptr;               // ... in the limbs of the lane-pair / lane-quad kernels
     const u8* a1 = kind == 0 ? d_h : (const u8*)d_pks;
     const u8* b1 = kind == 0 ? (const u8*)d_pks : d_h;
@@ -506,7 +506,7 @@ int verify_batch_host(int kind, const uint8_t* msgs, const uint64_t* off_or_doma
     // the BLSMI_COMBINE_* settings are read below: the environment must have been loaded (ADVICE r05: the first call of a process read the defaults, unsynchronised)
     { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
     const bool mid = n >= g_combine_max;                                   // the mid-size class (only where small calls combine at all)
-    if (n == 0 || (mid && (g_combine_max == 0 || n >= g_combine_mid_max.load(std::memory_order_relaxed))) || !msgs || !off_or_domain || !pks || !sigs || (kind != 2 && off_or_domain[0] != 0) || (fmt != 0 && fmt != FMT_JAC))
+    if (n == 0 || (mid && (g_combine_max == 0 || n >= tuning_now().combine_mid_max)) || !msgs || !off_or_domain || !pks || !sigs || (kind != 2 && off_or_domain[0] != 0) || (fmt != 0 && fmt != FMT_JAC))
         return verify_batch_direct(kind, msgs, off_or_domain, pks, sigs, inf_flags, ok, ok_bitmap, n, fmt);
     // a batch this full does not wait for more company.  With several devices a merged batch stays below the split threshold: it runs on ONE lease
     // (one device), and a direct call of BLSMI_SHARD_MIN tuples would have been cut over all of them (ADVICE r05)
@@ -1277,7 +1277,7 @@ int decompress_dev(int group, const u8* d_in, int check, u8* d_out, u8* d_inf, u
     dim3 g(nblocks(n)), w(WG);
     const bool lat = check == 1 && n <= tune().lat_max;
     const int kcheck = lat ? 0 : check;
-    const size_t wave_max = g_env.swu_wave_max;
+    const size_t wave_max = tune().swu_wave_max;
     const bool waves = kcheck == 0 && n <= wave_max;                       // the smallest calls: one wave per point, its square root with one limb per lane (fp_row.cuh)
     prof_mark(group == 1 ? (waves ? "k_g1_decompress_waves" : "k_g1_decompress") : (waves ? "k_g2_decompress_waves" : "k_g2_decompress"));
     if (waves && group == 1) hipLaunchKernelGGL(k_g1_decompress_waves, dim3((unsigned)n), dim3(64), 0, s, d_in, d_out, d_inf, d_err, n);
@@ -1338,7 +1338,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     // streams (fork after the input copies, join before the pairing stage) -- 8.7 -> ~5 ms for one tuple.  So do batches up to
     // 131 072 tuples: their one-lane kernels put one or two waves on a SIMD and the kernels with 256 registers a lane share it
     // (BLSMI_SIDE_MAX; a larger batch fills the chip by itself and stays on one stream).
-    const size_t side_max = g_env.side_max;
+    const size_t side_max = tune().side_max;
     const bool side = n <= std::max(tune().lat_max, side_max);
     hipStream_t spk = g_stream, ssg = g_stream;
     if (side) {

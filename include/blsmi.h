@@ -126,7 +126,9 @@ enum { BLSMI_SHAPE_PAIRING = 0, BLSMI_SHAPE_MILLER_LOOP = 1, BLSMI_SHAPE_FINAL_E
 int blsmi_prefer_cpu(int shape, size_t n);
 /* Environment.  Every BLSMI_* variable is read ONCE, when the library initialises (the first entry point, blsmi_init or blsmi_init_devices),
  * never from an entry point afterwards: changing the environment of a running process changes nothing (and getenv racing setenv is undefined
- * behaviour in a threaded host).  Deployment: BLSMI_STREAMS (call contexts per device, 4), BLSMI_SHARDS, BLSMI_SHARD_MIN, BLSMI_FORCE_RCCL,
+ * behaviour in a threaded host).  An option set through the API (blsmi_set_option, blsmi_set_*) before or between initialisations keeps its value; every
+ * other takes its variable's value, or its default where the variable is unset.  Each option, its variable and the rule the variable is read by are one
+ * row of the table `options` in bls_amd/csrc/route.h.  Deployment: BLSMI_STREAMS (call contexts per device, 4), BLSMI_SHARDS, BLSMI_SHARD_MIN, BLSMI_FORCE_RCCL,
  * BLSMI_RCCL_PATH (the librccl to dlopen when several devices are driven -- a Go binary has no torch that maps one), BLSMI_ARENA_KEEP_MB,
  * BLSMI_LAT_MAX / BLSMI_QUAD_MAX / BLSMI_QUAD_MIN (layout hand-overs; also blsmi_set_latency_threshold / _quad_threshold), BLSMI_MUL_GENERIC,
  * BLSMI_COMBINE_MAX / _WAIT_US / _INFLIGHT / _DEBUG (merging of concurrent one-tuple Verify calls).  A/B switches between code paths with

@@ -2,10 +2,14 @@
 //   <question> <kind> <n> <others> [option=value ...]
 // (options: Tuning members; unnamed ones keep the library defaults) and prints the answer on one line.  Questions: verify, pairing,
 // miller, final_exp, aggregate (layout + Miller records), side, prepared (does a table serve: verify / pairing / aggregate), hash
-// (the hash of a Verify: path + SWU layout), hash_agg (the uncleared hash of a large g2pubs aggregate).
+// (the hash of a Verify: path + SWU layout), hash_agg (the uncleared hash of a large g2pubs aggregate).  Two questions are about the
+// option table itself (tests/test_options.py):
+//   options                                       one line per row: member, blsmi_set_option name or -, variable or -, run-time / fixed, default
+//   env [explicit=member,...] [VARIABLE=value ...]  every member after apply_env over that environment, the named rows set through the API
 #include "../../bls_amd/csrc/route.h"
 #include <cstdlib>
 #include <iostream>
+#include <map>
 #include <sstream>
 #include <string>
 
@@ -16,13 +20,33 @@ static const char* name(Side x) { const char* s[] = {"none", "wave", "row"}; ret
 static const char* name(HashPath p) { const char* s[] = {"lat", "g1_lane", "g1_quad", "g2_oct", "g2_row", "g2_quad", "g2_pair", "plain"}; return s[(int)p]; }
 static const char* name(Swu w) { const char* s[] = {"waves", "rows", "lanes"}; return s[(int)w]; }
 
-static bool set(Tuning& t, const std::string& k, long long v) {
-#define F(m) if (k == #m) { t.m = (decltype(t.m))v; return true; }
-    F(lat_max) F(quad_max) F(quad_min) F(row_min) F(row_max) F(crowd_quad) F(crowd_floor) F(assume_load)
-    F(hash_row_min) F(hash_row_max) F(hash_quad_min) F(hash_quad_max) F(hash_oct_min) F(hash_oct_max) F(hash_g1_quad_min) F(hash_g1_quad_max)
-    F(swu_row_max) F(row_side) F(row_side_g2pubs) F(pair_layout) F(use_gen_lines) F(hash_g2_pair) F(hash_g1_split) F(swu_wave_max) F(sig_side_max)
-#undef F
-    return false;
+static void print_options() {
+    const Tuning dflt;
+    for (const Option& o : options)
+        std::cout << o.member << " " << (o.set == Set::option ? o.member : "-") << " " << (o.env ? o.env : "-") << " " << (o.set == Set::fixed ? "fixed" : "run-time") << " "
+                  << value_of(dflt, o) << "\n";
+}
+static bool print_env(std::istringstream& in) {
+    std::map<std::string, std::string> vars;
+    uint64_t mask = 0;
+    std::string kv;
+    while (in >> kv) {
+        const size_t eq = kv.find('=');
+        if (eq == std::string::npos) return false;
+        if (kv.compare(0, eq, "explicit") != 0) { vars[kv.substr(0, eq)] = kv.substr(eq + 1); continue; }
+        std::istringstream names(kv.substr(eq + 1));
+        for (std::string m; std::getline(names, m, ',');) {
+            int row = 0;
+            while (row < n_options && m != options[row].member) row++;
+            if (row == n_options) return false;
+            mask |= (uint64_t)1 << row;
+        }
+    }
+    Tuning t;
+    apply_env(t, mask, [&](const char* name) { auto it = vars.find(name); return it == vars.end() ? (const char*)nullptr : it->second.c_str(); });
+    for (const Option& o : options) std::cout << o.member << "=" << value_of(t, o) << " ";
+    std::cout << "\n";
+    return true;
 }
 
 int main() {
@@ -31,11 +55,14 @@ int main() {
         std::istringstream in(line);
         std::string q, kv;
         int kind; size_t n, others;
-        if (!(in >> q >> kind >> n >> others)) return 2;
+        if (!(in >> q)) return 2;
+        if (q == "options") { print_options(); continue; }
+        if (q == "env") { if (!print_env(in)) { std::cerr << "bad line " << line << "\n"; return 2; } continue; }
+        if (!(in >> kind >> n >> others)) return 2;
         Tuning t;
         while (in >> kv) {
             const size_t eq = kv.find('=');
-            if (eq == std::string::npos || !set(t, kv.substr(0, eq), std::atoll(kv.c_str() + eq + 1))) { std::cerr << "bad option " << kv << "\n"; return 2; }
+            if (eq == std::string::npos || set_by_name(t, kv.substr(0, eq).c_str(), std::atoll(kv.c_str() + eq + 1), false) < 0) { std::cerr << "bad option " << kv << "\n"; return 2; }
         }
         // the load a call sees: what other calls carry plus the "assume_load" test hook (blsmi.hip: call_load)
         const size_t load = others + t.assume_load;
