@@ -51,13 +51,17 @@ __global__ void k_miller2_row(const u8* p0, size_t sp0, const u8* q0, size_t sq0
 __global__ void k_miller1s_row(const u8* p, size_t sp, const u8* q, size_t sq, i32* fbuf, size_t n, const i32* pre, size_t first, size_t end);
 __global__ void k_miller1m_row(const u8* p, size_t sp, const u8* q, size_t sq, i32* fbuf, size_t n);
 __global__ void k_final_exp_is_one_row(const i32* fbuf, const u8* inf_flags, u8* ok, size_t n);
-__global__ void k_clear_h2_row(const i32* jbuf, u8* good, u8* out, size_t n);
-__global__ void k_clear_h2_oct(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_debug_row(int op, const u64* a, const u64* b, u64* out, size_t n);
-__global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);            // k_hash_quad.hip
-__global__ void k_debug_quad_g2(int op, const u64* a, u64* out, size_t n);
+__global__ void k_clear_h2_oct(const i32* jbuf, u8* good, u8* out, size_t n);
+__global__ void k_clear_h2_row(const i32* jbuf, u8* good, u8* out, size_t n);
+// k_fq12_seg.hip
+__global__ void k_fq12_seg_prod_row(const i32* src, size_t nsrc, const u8* skip, const u64* lo, const u32* cnt, i32* dst, u64* out_m384, size_t nch);
+__global__ void k_pprod_skip(u8* g1, u8* g2, const u8* in_flags, const u8* gen1, const u8* gen2, u8* skip, size_t n);
+__global__ void k_fq12_is_one_m384(const u64* vals, u8* is_one, size_t n);
+// k_hash_quad.hip
+__global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);
-__global__ void k_hash_g1_finish_redo(const u8* pts, const u8* good, u8* out, size_t n);   // k_hash.hip
+__global__ void k_debug_quad_g2(int op, const u64* a, u64* out, size_t n);
 // k_prepared_pair.hip
 __global__ void k_g2_prepare_pair(const u8* g2, i32* tables, size_t n);
 __global__ void k_prepared_export(const i32* tables, u64* out, size_t n);
@@ -67,14 +71,14 @@ __global__ void k_miller1_prep_pair(const u8* g1, const i32* tables, const u32* 
 __global__ void k_miller2_prep_pair(const u8* sigs, const u8* h, const i32* tables, const u32* key_idx, i32* fbuf, size_t n, const i32* pre_gen);
 __global__ void k_miller1x2_prep_pair(const u8* g1, const i32* tables, const u32* key_idx, i32* fbuf, size_t n, size_t m);
 // k_lat.hip
-__global__ void k_lat(const u8* prog, const u8* b0, size_t s0, const u8* b1, size_t s1, const u8* b2, size_t s2,
-                                                const u8* b3, size_t s3, const u8* flags, u8* ok, u64* out, size_t n);
+__global__ void k_lat(const u8* prog, const u8* b0, size_t s0, const u8* b1, size_t s1, const u8* b2, size_t s2, const u8* b3, size_t s3, const u8* flags, u8* ok, u64* out, size_t n);
 // k_hash.hip
 __global__ void k_hash_g1(const u8* msgs, const u64* off, u8* out, size_t n, int clear, int* special);
 __global__ void k_hash_g2(const u8* msgs, const u64* off, u8* out, size_t n);
 __global__ void k_hash_g2_domain(const u8* msgs32, const u8* domain, u8* out, size_t n);
 __global__ void k_swu_g1_two_lanes(const u8* msgs, const u64* off, u8* pts, size_t n);
 __global__ void k_hash_g1_finish(const u8* pts, u8* out, size_t n, int clear, int* special);
+__global__ void k_hash_g1_finish_redo(const u8* pts, const u8* good, u8* out, size_t n);
 __global__ void k_swu_g2_two_lanes(const u8* msgs, const u64* off, u8* pts, size_t n);
 __global__ void k_swu_g1_waves(const u8* msgs, const u64* off, u8* pts, size_t n);
 __global__ void k_swu_g2_waves(const u8* msgs, const u64* off, u8* pts, size_t n);
@@ -108,8 +112,8 @@ __global__ void k_debug_swu_g1(const u64* a, u64* out, size_t n);
 __global__ void k_debug_swu_g2(const u64* a, u64* out, size_t n);
 // k_hash_pair.hip
 __global__ void k_hash_g2_pair(const u8* msgs, const u64* off, u8* good, u8* out, size_t n, unsigned redo_every);
-__global__ void k_cofac2_pair(const u8* pts, u8* out, size_t n);
 __global__ void k_hash_g2_front(const u8* msgs, const u64* off, u8* good, i32* jbuf, size_t n, unsigned redo_every);
+__global__ void k_cofac2_pair(const u8* pts, u8* out, size_t n);
 // k_curve.hip
 __global__ void k_debug_fq6(int op, const u64* a, const u64* b, u64* out, size_t n);
 __global__ void k_debug_curve(int op, const u64* a, const u64* b, u64* out, size_t n);
@@ -138,9 +142,9 @@ __global__ void k_g1_sum_final(const i32* src, u8* out, i32* out_inf);
 __global__ void k_g2_sum_final(const i32* src, u8* out, i32* out_inf);
 __global__ void k_g1_segsum_chunk(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g1_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g1_segsum_fold(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch);
 __global__ void k_g1_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);
-__global__ void k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g2_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);
 __global__ void k_g2_mul_pair(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul_glv_pair(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);

@@ -2003,7 +2003,8 @@ int segsum_check(size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_
     for (uint64_t k = 0; k < total; k++) if (idx[k] >= npk) return BLSMI_E_ARG;
     return BLSMI_OK;
 }
-void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p) {
+// last_max: the partials a segment may still have when the final pass takes over (the sums: one wave adds up to 64 across its lanes)
+void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t last_max = 64) {
     p.m = m; p.K = K;
     std::vector<uint64_t> lo, part_lo(m);
     std::vector<uint32_t> cnt, seg, part_cnt(m);
@@ -2017,7 +2018,7 @@ void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p) {
     p.ch_lo = p.put(lo); p.ch_cnt = p.put(cnt); p.ch_seg = p.put(seg);
     size_t nsrc = p.nch1;
     const size_t Kf = std::max<size_t>(K, 2);
-    while (m && *std::max_element(part_cnt.begin(), part_cnt.end()) > 64) {
+    while (m && *std::max_element(part_cnt.begin(), part_cnt.end()) > last_max) {
         lo.clear(); cnt.clear();
         for (size_t j = 0; j < m; j++) {
             const uint64_t a = part_lo[j], len = part_cnt[j];
@@ -2242,4 +2243,154 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_dev(const void* d_msgs,
 BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const void* d_msgs32, const void* d_domain, const void* d_pks, size_t npk, const void* d_idx,
                                                                          const void* d_seg_off, const void* d_sigs, void* d_ok, size_t m, void* stream) {
     return agg_common_batch_dev_api<2>(d_msgs32, d_domain, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
+}
+
+// ---- pairing products (blsmi 0.10; include/blsmi.h "pairing products") ------------------------------------------------------------------
+// Item j = FinalExponentiation(MillerLoop({(P_k, Q_k) : seg_off[j] <= k < seg_off[j + 1]})) (pairing.go:16-75, 79-129) in three stages on the
+// call's stream: one Miller value per pair in the layout a Pairing call of np tuples takes (any Miller value serves a product that is
+// final-exponentiated, so the wave layout runs "miller1raw"); the segmented product of those values, a lane row per chunk (k_fq12_seg.hip)
+// over the chunk plan of the segmented sums (segsum_plan; fold passes until a segment has at most max(K, 2) partials, K as the sums choose
+// it); the final exponentiation of the m products in the layout blsmi_final_exponentiation_batch gives m values (beyond lat_max: a Pairing
+// call's quad / pair kernels), then the comparison with one.  A pair with a point at infinity runs its loop on the generators and is left out of the product.  One lease, one device.
+namespace {
+// one Miller value per tuple into the hand-off buffer f, the tuples free of points at infinity
+void launch_miller_tuples(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, Layout l) {
+    prof_mark(l == Layout::wave ? "k_lat:miller1raw" : l == Layout::row ? "k_miller1h_row" : l == Layout::quad ? "k_miller1h_quad" : l == Layout::pair ? "k_miller1h_pair" : "k_miller1h");
+    if (l == Layout::wave)
+        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MILLER1RAW_OFFSET,
+                           d_g1, (size_t)96, d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
+    else if (l == Layout::row) hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+    else if (l == Layout::quad) hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+    else if (l == Layout::pair) hipLaunchKernelGGL(k_miller1h_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+    else hipLaunchKernelGGL(k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+}
+void pprod_plan(const uint64_t* seg_off, size_t m, SegPlan& plan) {
+    const size_t K = segsum_chunk_of(seg_off[m]);
+    segsum_plan(seg_off, m, K, plan, std::max<size_t>(K, 2));
+}
+// d_g1 / d_g2: np affine records the call owns (records of skipped pairs are overwritten); d_flags: np flag bytes or null.  The m values go to
+// d_out (576 bytes each) and / or the m verdict bytes to d_is_one.  Synchronises.
+int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& plan, void* d_out, void* d_is_one, hipStream_t s) {
+    const size_t m = plan.m, words = (size_t)12 * NL;
+    DBuf skip, f, blob, prod, vals;
+    HIPCHK(blob.alloc(plan.blob.size()));
+    HIPCHK(hipMemcpyAsync(blob.p, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, s));
+    auto at64 = [&](size_t off) { return reinterpret_cast<const u64*>(blob.as<u8>() + off); };
+    auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(blob.as<u8>() + off); };
+    // the final exponentiation's layout: what blsmi_final_exponentiation_batch gives m values (wave, row), and beyond those -- where that entry
+    // point has only its one-lane kernel -- the quad / pair kernels a Pairing call of m tuples ends in
+    Layout fe = final_exp_layout(m, tune(), route_load(np));
+    if (fe == Layout::single && tune().pair_layout) fe = m <= tune().quad_max ? Layout::quad : Layout::pair;
+    const i32* src = nullptr;
+    if (np) {
+        HIPCHK(skip.alloc(np)); HIPCHK(f.alloc(sizeof(i32) * words * np));
+        hipLaunchKernelGGL(k_pprod_skip, dim3(nblocks(np)), dim3(WG), 0, s, d_g1, d_g2, d_flags, (const u8*)g_gens.g1, (const u8*)g_gens.g2, skip.as<u8>(), np);
+        launch_miller_tuples(d_g1, d_g2, f.as<i32>(), np, s, pairing_layout(0, np, tune(), route_load(np)));
+        src = f.as<i32>();
+    }
+    // the product: pass 1 over the Miller values, the folds, the final pass (its records: the final exponentiation's input -- the reference's
+    // in-memory form for the wave layout, the hand-off buffer otherwise)
+    prof_mark("k_fq12_seg_prod_row");
+    const u8* sk = skip.as<u8>();
+    size_t nsrc = np;
+    if (plan.nch1) {
+        DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * plan.nch1));
+        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.nch1)), dim3(WG), 0, s, src, nsrc, sk, at64(plan.ch_lo), at32(plan.ch_cnt), d.as<i32>(), (u64*)nullptr, plan.nch1);
+        src = d.as<i32>(); nsrc = plan.nch1;
+    }
+    for (const SegPlan::Fold& fo : plan.folds) {
+        DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * fo.nch));
+        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(fo.nch)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(fo.lo), at32(fo.cnt), d.as<i32>(), (u64*)nullptr, fo.nch);
+        src = d.as<i32>(); nsrc = fo.nch;
+    }
+    HIPCHK(prod.alloc(fe == Layout::wave ? 576 * m : sizeof(i32) * words * m));
+    hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(m)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(plan.seg_lo), at32(plan.seg_cnt),
+                       fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, m);
+    u64* out = (u64*)d_out;
+    if (!out) { HIPCHK(vals.alloc(576 * m)); out = vals.as<u64>(); }
+    prof_mark(fe == Layout::wave ? "k_lat:finalexp1" : fe == Layout::row ? "k_final_exp_row" : fe == Layout::quad ? "k_final_exp_quad" : fe == Layout::pair ? "k_final_exp_pair" : "k_final_exp");
+    if (fe == Layout::wave)
+        hipLaunchKernelGGL(k_lat, dim3((unsigned)m), dim3(64), lat_lds_bytes(LAT_FINALEXP1_OFFSET), s, (const u8*)g_gens.lat + LAT_FINALEXP1_OFFSET,
+                           (const u8*)prod.p, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                           (const u8*)nullptr, (u8*)nullptr, out, m);
+    else if (fe == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
+    else if (fe == Layout::quad) hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
+    else if (fe == Layout::pair) hipLaunchKernelGGL(k_final_exp_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
+    else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
+    if (d_is_one) {
+        prof_mark("k_fq12_is_one_m384");
+        hipLaunchKernelGGL(k_fq12_is_one_m384, dim3(rblocks(m)), dim3(WG), 0, s, (const u64*)out, (u8*)d_is_one, m);
+    }
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+// the offsets of a product: from 0, non-decreasing, ending at np
+int pprod_check(const uint64_t* seg_off, size_t m, size_t np) {
+    if (!seg_off || seg_off[0] != 0) return BLSMI_E_ARG;
+    for (size_t j = 0; j < m; j++) if (seg_off[j + 1] < seg_off[j]) return BLSMI_E_ARG;
+    return seg_off[m] == np ? BLSMI_OK : BLSMI_E_ARG;
+}
+int pprod_host(const uint8_t* g1, const uint8_t* g2, const uint8_t* inf_flags, size_t np, const uint64_t* seg_off, size_t m, uint64_t* out_fq12, uint8_t* is_one, bool jac) {
+    if (m == 0) return BLSMI_OK;
+    if ((!out_fq12 && !is_one) || (np && (!g1 || !g2))) return BLSMI_E_ARG;
+    int rc = pprod_check(seg_off, m, np);
+    if (rc) return rc;
+    LOCK_AND_INIT();
+    SegPlan plan;
+    pprod_plan(seg_off, m, plan);
+    DBuf a, b, fl, o, ok;
+    HIPCHK(a.alloc(96 * np)); HIPCHK(b.alloc(192 * np)); HIPCHK(fl.alloc(np)); HIPCHK(o.alloc(576 * m)); HIPCHK(ok.alloc(m));
+    if (np) {
+        rc = upload_points(96, jac, g1, a.p, np, g_stream);
+        if (!rc) rc = upload_points(192, jac, g2, b.p, np, g_stream);
+        if (rc) return rc;
+        if (inf_flags) HIPCHK(hipMemcpyAsync(fl.p, inf_flags, np, hipMemcpyHostToDevice, g_stream));
+    }
+    rc = pprod_dev(a.as<u8>(), b.as<u8>(), inf_flags ? fl.as<u8>() : nullptr, np, plan, out_fq12 ? o.p : nullptr, is_one ? ok.p : nullptr, g_stream);
+    if (rc) return rc;
+    if (out_fq12) HIPCHK(hipMemcpyAsync(out_fq12, o.p, 576 * m, hipMemcpyDeviceToHost, g_stream));
+    if (is_one) HIPCHK(hipMemcpyAsync(is_one, ok.p, m, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+int pprod_dev_api(const void* d_g1, const void* d_g2, const void* d_inf_flags, size_t np, const void* d_seg_off, size_t m, void* d_out_fq12, void* d_is_one, void* stream, bool jac) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_seg_off || (!d_out_fq12 && !d_is_one) || (np && (!d_g1 || !d_g2))) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_out_fq12 ? d_out_fq12 : d_is_one);
+    UseStream us(stream);
+    std::vector<uint64_t> off;
+    int rc = segsum_fetch_offsets(d_seg_off, m, off);
+    if (rc) return rc;
+    if (off[m] != np) return BLSMI_E_ARG;
+    SegPlan plan;
+    pprod_plan(off.data(), m, plan);
+    DBuf a, b;                                                             // the call's own copies: the records of skipped pairs are overwritten
+    HIPCHK(a.alloc(96 * np)); HIPCHK(b.alloc(192 * np));
+    if (np && jac) {
+        rc = jac_to_wire_dev(96, d_g1, a.p, nullptr, np, g_stream);
+        if (!rc) rc = jac_to_wire_dev(192, d_g2, b.p, nullptr, np, g_stream);
+        if (rc) return rc;
+    } else if (np) {
+        HIPCHK(hipMemcpyAsync(a.p, d_g1, 96 * np, hipMemcpyDeviceToDevice, g_stream));
+        HIPCHK(hipMemcpyAsync(b.p, d_g2, 192 * np, hipMemcpyDeviceToDevice, g_stream));
+    }
+    return pprod_dev(a.as<u8>(), b.as<u8>(), (const u8*)d_inf_flags, np, plan, d_out_fq12, d_is_one, g_stream);
+}
+}  // namespace
+BLSMI_API int blsmi_pairing_product_batch(const uint8_t* g1_aff, const uint8_t* g2_aff, const uint8_t* inf_flags, size_t np, const uint64_t* seg_off, size_t m,
+                                          uint64_t* out_fq12, uint8_t* is_one) {
+    return pprod_host(g1_aff, g2_aff, inf_flags, np, seg_off, m, out_fq12, is_one, false);
+}
+BLSMI_API int blsmi_pairing_product_batch_jac(const uint64_t* g1_jac, const uint64_t* g2_jac, size_t np, const uint64_t* seg_off, size_t m, uint64_t* out_fq12, uint8_t* is_one) {
+    return pprod_host(reinterpret_cast<const uint8_t*>(g1_jac), reinterpret_cast<const uint8_t*>(g2_jac), nullptr, np, seg_off, m, out_fq12, is_one, true);
+}
+BLSMI_API int blsmi_pairing_product_batch_dev(const void* d_g1_aff, const void* d_g2_aff, const void* d_inf_flags, size_t np, const void* d_seg_off, size_t m,
+                                              void* d_out_fq12, void* d_is_one, void* stream) {
+    return pprod_dev_api(d_g1_aff, d_g2_aff, d_inf_flags, np, d_seg_off, m, d_out_fq12, d_is_one, stream, false);
+}
+BLSMI_API int blsmi_pairing_product_batch_jac_dev(const void* d_g1_jac, const void* d_g2_jac, size_t np, const void* d_seg_off, size_t m, void* d_out_fq12, void* d_is_one, void* stream) {
+    return pprod_dev_api(d_g1_jac, d_g2_jac, nullptr, np, d_seg_off, m, d_out_fq12, d_is_one, stream, true);
 }

@@ -1157,3 +1157,60 @@ def verify_aggregate_common_batch_dev(group, d_msgs, d_off_or_domain, d_pks, npk
         (lib.blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev if domain else lib.blsmi_g1pubs_verify_aggregate_common_batch_dev)
     _check(fn(C.c_void_p(d_msgs or 0), C.c_void_p(d_off_or_domain or 0), C.c_void_p(d_pks or 0), C.c_size_t(npk), C.c_void_p(d_idx or 0),
               C.c_void_p(d_seg_off or 0), C.c_void_p(d_sigs or 0), C.c_void_p(d_ok or 0), C.c_size_t(m), C.c_void_p(stream)), "verify_aggregate_common_batch_dev")
+
+
+# ---- pairing products (blsmi 0.10): many MillerLoop(items) + FinalExponentiation checks in one call -----------------------------
+def _pprod_offsets(seg_off, np_):
+    so = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+    if so.size < 1:
+        raise ValueError("seg_off needs m + 1 entries")
+    if so.size > 1 and int(so[-1]) != np_:
+        raise ValueError("seg_off ends at %d, the call has %d pairs" % (int(so[-1]), np_))
+    return so, so.size - 1
+
+
+def _pprod_out(m):
+    return np.zeros((m, 72), dtype=np.uint64), np.zeros(max(1, m), dtype=np.uint8)
+
+
+def pairing_product_batch(g1_aff, g2_aff, seg_off, inf_flags=None):
+    """item j = FinalExponentiation(MillerLoop({(P_k, Q_k) : seg_off[j] <= k < seg_off[j + 1]})) over affine records (96 / 192 bytes a
+    point; inf_flags[k] bit 0 / 1: P_k / Q_k is the point at infinity) -> (values (m, 72) uint64, is_one (m,) uint8)"""
+    a, b = _u8(g1_aff), _u8(g2_aff)
+    if a.size % 96 or b.size != 2 * a.size:
+        raise ValueError("expected np*96 and np*192 bytes, got %d and %d" % (a.size, b.size))
+    n = a.size // 96
+    so, m = _pprod_offsets(seg_off, n)
+    f = _u8(inf_flags, n) if inf_flags is not None else None
+    out, one = _pprod_out(m)
+    _check(_lib().blsmi_pairing_product_batch(_p8(a), _p8(b), _p8(f), C.c_size_t(n), so.ctypes.data_as(_u64p), C.c_size_t(m),
+                                              out.ctypes.data_as(_u64p), _p8(one)), "blsmi_pairing_product_batch")
+    return out, one[:m].copy()
+
+
+def pairing_product_batch_jac(g1_jac, g2_jac, seg_off):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    a, b = _u8(g1_jac), _u8(g2_jac)
+    if a.size % 144 or b.size != 2 * a.size:
+        raise ValueError("expected np*144 and np*288 bytes, got %d and %d" % (a.size, b.size))
+    n = a.size // 144
+    so, m = _pprod_offsets(seg_off, n)
+    out, one = _pprod_out(m)
+    (a, pa), (b, pb) = _j64(a, 144 * n), _j64(b, 288 * n)
+    _check(_lib().blsmi_pairing_product_batch_jac(pa, pb, C.c_size_t(n), so.ctypes.data_as(_u64p), C.c_size_t(m), out.ctypes.data_as(_u64p), _p8(one)),
+           "blsmi_pairing_product_batch_jac")
+    return out, one[:m].copy()
+
+
+def pairing_product_batch_dev(d_g1, d_g2, np_, d_seg_off, m, d_out_fq12, d_is_one, d_inf_flags=0, stream=0, jac=False):
+    """device-pointer forms (ints): jac=False affine records and optional flags, jac=True in-memory points; d_out_fq12 (m*576 bytes) or
+    d_is_one (m bytes) may be 0, not both"""
+    v = C.c_void_p
+    if jac:
+        if d_inf_flags:
+            raise ValueError("the in-memory form takes no flags: z == 0 is infinity")
+        rc = _lib().blsmi_pairing_product_batch_jac_dev(v(d_g1 or 0), v(d_g2 or 0), C.c_size_t(np_), v(d_seg_off or 0), C.c_size_t(m), v(d_out_fq12 or 0), v(d_is_one or 0), v(stream))
+    else:
+        rc = _lib().blsmi_pairing_product_batch_dev(v(d_g1 or 0), v(d_g2 or 0), v(d_inf_flags or 0), C.c_size_t(np_), v(d_seg_off or 0), C.c_size_t(m),
+                                                    v(d_out_fq12 or 0), v(d_is_one or 0), v(stream))
+    _check(rc, "blsmi_pairing_product_batch_jac_dev" if jac else "blsmi_pairing_product_batch_dev")

@@ -75,7 +75,8 @@ void blsmi_shutdown(void);
  * 2 048 .. 8 192 tuples), the "row_side" / "hash_row_min" / "hash_row_max" / "hash_quad_min" / "hash_quad_max" / "hash_oct_min" / "hash_oct_max" / "hash_g1_quad_min" / "hash_g1_quad_max" options and BLSMI_OP_LANE_ROW / BLSMI_OP_ROW_*_STEP / BLSMI_OP_ROW_G2_* / BLSMI_OP_ROW_CLEAR_H2 for blsmi_debug_op; no existing prototype changes.  0.8 adds the randomised batch verification (blsmi_g?pubs_*verify*_batch_rlc[_jac]),
  * the "rlc_min" option, BLSMI_E_RNG and BLSMI_OP_G1_MUL_U64; no existing prototype changes.  0.9 adds the segmented sums (blsmi_g?_sum_segmented[_jac|_dev]),
  * the batches of VerifyAggregateCommon over key committees (blsmi_g?pubs_verify_aggregate_common*_batch[_jac|_dev]) and the "segsum_chunk" option;
- * no existing prototype changes. */
+ * no existing prototype changes.  0.10 adds the pairing products (blsmi_pairing_product_batch[_jac|_dev|_jac_dev]: many MillerLoop(items) + FinalExponentiation
+ * checks in one call); no existing prototype changes, no new option. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -139,7 +140,8 @@ int blsmi_prefer_cpu(int shape, size_t n);
  *   "agg_cofactor_pow" (BLSMI_AGG_COFACTOR_POW, default 1), "msm_sort" (BLSMI_MSM_SORT, default 1), "dup_force_sort" (BLSMI_DUP_FORCE_SORT, 0),
  *   "rlc_min" (BLSMI_RLC_MIN, default 32768): the randomised batch verification (*_verify_batch_rlc) of fewer tuples runs the per-tuple path,
  *   "segsum_chunk" (BLSMI_SEGSUM_CHUNK, default 0 = automatic: 8, doubled up to 64 while more than 2^16 chunks would remain): positions per lane of
- *   the segmented sums (blsmi_g?_sum_segmented, the *_verify_aggregate_common*_batch entry points),
+ *   the segmented sums (blsmi_g?_sum_segmented, the *_verify_aggregate_common*_batch entry points) and values per lane row of the pairing products' segmented
+ *   Fq12 product (blsmi_pairing_product_batch*),
  *   "lat_rolled" (BLSMI_LAT_ROLLED, default 1; 0: small Pairing calls run the straight-line copy of their level program instead of the one
  *   whose squaring runs are loops), "row_side" (BLSMI_ROW_SIDE, default 1: a Verify in the row layout runs its signature side beside the hash -- g1pubs, and g2pubs with "row_side_g2pubs"),
  *   "hash_row_min" / "hash_row_max" (defaults 2048 / 4096; no environment name): HashG2 of that many messages clears its cofactor sixteen lanes per message
@@ -563,6 +565,36 @@ int blsmi_g1pubs_verify_aggregate_common_batch_dev(const void *d_msgs, const voi
                                                    const void *d_seg_off, const void *d_sigs, void *d_ok, size_t m, void *stream);
 int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const void *d_msgs32, const void *d_domain, const void *d_pks, size_t npk, const void *d_idx,
                                                                const void *d_seg_off, const void *d_sigs, void *d_ok, size_t m, void *stream);
+
+/* ---- pairing products (blsmi 0.10) -------------------------------------------------------------------------------------------------
+ * m products of pairings, each final-exponentiated once -- the reference's central primitive, bls.MillerLoop(items []MillerLoopItem)
+ * followed by bls.FinalExponentiation (pairing.go:16-75, 79-129), m times in one call:
+ *   item j = FinalExponentiation(MillerLoop({(P_k, Q_k) : seg_off[j] <= k < seg_off[j + 1]}))
+ * Output: out_fq12[j] (72 u64) is in the output format of blsmi_pairing_batch; is_one[j] = 1 exactly when that value equals FQ12One -- for
+ * a two-pair segment with a negated P this is CompareTwoPairings (pairing.go:140-147).  Either output may be NULL, not both (BLSMI_E_ARG).
+ * Infinity: a pair whose P or Q is at infinity contributes 1 (what the reference intends; the Go code itself would panic).  Infinity is
+ * a flag (inf_flags[k] bit 0: P_k, bit 1: Q_k; the array may be NULL), the all-zero record, or z == 0 in the _jac forms (144 / 288 bytes
+ * a point, as the Go values hold them).  An empty segment, or one whose pairs are all skipped, gives FQ12One and is_one = 1.
+ * Offsets: m + 1 entries, seg_off[0] = 0, non-decreasing, seg_off[m] = np.  The host forms check this, and NULL inputs with np > 0, and
+ * return BLSMI_E_ARG before any device work; the _dev forms read the offsets back to the host as the segmented sums do and return the
+ * same error.  m = 0 returns BLSMI_OK; np = 0 with m > 0 is legal: every item is one.
+ * A single-pair segment gives exactly the bytes of blsmi_pairing_batch for that pair, and every result is bit-identical whatever layouts
+ * the stages take: one Miller value per pair in the layout a Pairing call of np tuples takes, the segmented Fq12 product a row of sixteen
+ * lanes per chunk of K consecutive values (K: the "segsum_chunk" option, chosen from np as the segmented sums choose it from their total),
+ * the final exponentiation of the m products in the layout blsmi_final_exponentiation_batch gives m values (more than the latency
+ * threshold: a Pairing call's four- / two-lane kernels).  The call runs on ONE device: it is not sharded and does not join the request
+ * combiner.  The _dev forms take every buffer on one of the library's devices (d_out_fq12: m*576 bytes, d_is_one: m bytes, d_seg_off:
+ * (m + 1) u64) and leave the caller's point buffers untouched. */
+int blsmi_pairing_product_batch(const uint8_t *g1_aff /* np*96 */, const uint8_t *g2_aff /* np*192 */,
+                                const uint8_t *inf_flags /* np, may be NULL: bit0 = P_k infinity, bit1 = Q_k infinity */, size_t np,
+                                const uint64_t *seg_off /* m+1 */, size_t m,
+                                uint64_t *out_fq12 /* m*72, may be NULL */, uint8_t *is_one /* m, may be NULL */);
+int blsmi_pairing_product_batch_jac(const uint64_t *g1_jac /* np*18 */, const uint64_t *g2_jac /* np*36 */, size_t np,
+                                    const uint64_t *seg_off, size_t m, uint64_t *out_fq12, uint8_t *is_one);
+int blsmi_pairing_product_batch_dev(const void *d_g1_aff, const void *d_g2_aff, const void *d_inf_flags, size_t np,
+                                    const void *d_seg_off, size_t m, void *d_out_fq12, void *d_is_one, void *stream);
+int blsmi_pairing_product_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, size_t np,
+                                        const void *d_seg_off, size_t m, void *d_out_fq12, void *d_is_one, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,8 @@ import os
 import re
 
 D = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bls_amd", "csrc")
-FILES = ["k_pairing_single.hip", "k_fe_single.hip", "k_fq12_single.hip", "k_pairing_pair.hip", "pair_kernels.inc", "k_pairing_quad.hip", "k_prepared_pair.hip", "k_lat.hip", "k_hash.hip", "k_wire.hip", "k_hash_pair.hip", "k_curve.hip", "k_msm_pair.hip", "msm.inc"]
-PAT = re.compile(r"^(KERNEL2|KERNEL_PAIR|KERNEL_QUAD|KERNEL_LAT|KERNEL|__global__ void __launch_bounds__\([^)]*\))\s+(k_\w+)\(([^)]*)\)\s*\{", re.M)
+FILES = ["k_pairing_single.hip", "k_fe_single.hip", "k_fq12_single.hip", "k_pairing_pair.hip", "pair_kernels.inc", "k_fe_pair.hip", "k_pairing_quad.hip", "k_pairing_row.hip", "k_fq12_seg.hip", "k_hash_quad.hip", "k_prepared_pair.hip", "k_lat.hip", "k_hash.hip", "k_wire.hip", "k_hash_pair.hip", "k_curve.hip", "k_msm_pair.hip", "msm.inc"]
+PAT = re.compile(r"^(KERNEL2|KERNEL_PAIR|KERNEL_QUAD|KERNEL_ROW|KERNEL_LAT|KERNEL|__global__ void __launch_bounds__\([^)]*\))\s+(k_\w+)\(([^)]*)\)\s*\{", re.M)
 
 out = """// kernels.h -- declarations of the kernels defined in the k_*.hip translation units, for the host side (blsmi.hip).
 // Generated from the definitions by tools/gen_kernel_decls.py; the launch bounds live with the definitions.
@@ -15,6 +15,7 @@ using namespace blsmi;
 #define WG 64
 constexpr int PT = WG / 2;          // tuples per workgroup of the lane-pair kernels
 constexpr int QT = WG / 4;          // tuples per workgroup of the lane-quad kernels
+constexpr int RT = WG / 16;         // tuples per workgroup of the lane-row kernels
 """
 seen = set()
 for f in FILES:
@@ -25,6 +26,6 @@ for f in FILES:
     for m in PAT.finditer(open(p).read()):
         assert m.group(2) not in seen, m.group(2)
         seen.add(m.group(2))
-        out += "__global__ void %s(%s);\n" % (m.group(2), m.group(3))
+        out += "__global__ void %s(%s);\n" % (m.group(2), " ".join(m.group(3).split()))
 open(os.path.join(D, "kernels.h"), "w").write(out)
 print("%d kernels" % len(seen))
