@@ -7,6 +7,7 @@
 #include "util_dev.h"
 #include "prepared.h"
 #include "route.h"
+#include "group_plan.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

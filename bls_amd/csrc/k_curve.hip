@@ -380,6 +380,46 @@ KERNEL2 k_g1_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const 
 KERNEL k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
     segsum_chunk_jac_body<Fp2S>(pts, npk, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
 }
+// Weighted pass 1 (blsmi 0.11: the grouped randomised verification's sum_i r_i pk_i per message, and blsmi_g?_sum_segmented_u64): chunk c
+// adds r[i] * pts[i] over its positions, the scalar addressed by the same index as the point.  The ladder of k_g?_mul_u64 (mul_u64_jac, its
+// 16-entry table) WITHOUT the inversion per lane that makes k_g?_mul_u64's product affine: the products are only going to be added, so the
+// partial leaves as the folds read it.  The host plans this pass with chunks of ONE position (segsum_plan's K1): a chunk of K would chain
+// K ladders on one lane.  So cnt is 1 for every caller today and the jac_add below only ever adds a product to infinity; a chunk of several
+// positions (jac_add's general and doubling cases inside this kernel) is written as the plan's arguments allow it but is UNUSED and
+// UNTESTED -- equal points with equal scalars meet the doubling case in the fold and final kernels instead.  The inlined jac_add is the
+// 336 B of scratch a lane this kernel has over k_g?_mul_u64.  An index >= npk marks its segment; in_inf and a zero scalar contribute
+// nothing (the ladder of either gives infinity).
+template <class F, int PB>
+__device__ void segsum_chunk_u64_body(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt,
+                                      const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    const size_t c = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (c >= nch) return;
+    const u64 lo = ch_lo[c];
+    const u32 cnt = ch_cnt[c];
+    Jac<F> acc = jac_zero<F>();
+    for (u32 k = 0; k < cnt; k++) {
+        const u64 i = idx ? (u64)idx[lo + k] : lo + k;
+        if (i >= npk) { bad[ch_seg[c]] = 1; continue; }
+        Aff<F> a = load_aff<F>(pts + (size_t)PB * i);
+        if (in_inf && in_inf[i]) a.inf = -1;
+        acc = jac_add(acc, mul_u64_jac<F>(a, scalars[i]));
+    }
+    jac_soa_store(part, nch, c, acc);
+}
+KERNEL2 k_g1_segsum_chunk_u64(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    segsum_chunk_u64_body<FpS, 96>(pts, in_inf, npk, scalars, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
+}
+KERNEL k_g2_segsum_chunk_u64(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    segsum_chunk_u64_body<Fp2S, 192>(pts, in_inf, npk, scalars, idx, ch_lo, ch_cnt, ch_seg, bad, part, nch);
+}
+// dst record r = src record idx[r], `words` 32-bit words each, a lane per word (the grouped verification's per-tuple path: the hash point of
+// every tuple from its message's); the host has checked the indices
+KERNEL2 k_gather_records(const u32* src, const u32* idx, u32* dst, u32 words, size_t n) {
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (t >= (size_t)words * n) return;
+    const size_t r = t / words;
+    dst[t] = src[(size_t)idx[r] * words + (t - r * words)];
+}
 // fold: chunk c adds the ch_cnt[c] >= 1 consecutive partials of src from ch_lo[c] on
 KERNEL2 k_g1_segsum_fold(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch) {
     const size_t c = (size_t)blockIdx.x * WG + threadIdx.x;

@@ -143,6 +143,9 @@ __global__ void k_g2_sum_final(const i32* src, u8* out, i32* out_inf);
 __global__ void k_g1_segsum_chunk(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g1_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g2_segsum_chunk_jac(const u64* pts, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g1_segsum_chunk_u64(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g2_segsum_chunk_u64(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_gather_records(const u32* src, const u32* idx, u32* dst, u32 words, size_t n);
 __global__ void k_g1_segsum_fold(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch);
 __global__ void k_g1_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);
 __global__ void k_g2_segsum_final(const i32* src, size_t nsrc, const u64* seg_lo, const u32* seg_cnt, const u8* bad, u8 bad_code, u8* out, u8* out_inf);

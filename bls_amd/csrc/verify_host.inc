@@ -2004,14 +2004,16 @@ int segsum_check(size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_
     return BLSMI_OK;
 }
 // last_max: the partials a segment may still have when the final pass takes over (the sums: one wave adds up to 64 across its lanes)
-void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t last_max = 64) {
+// K1: the chunk size of pass 1 alone (0: K, as the folds; the weighted sums take 1 -- one 64-bit ladder per lane, segsum_dev)
+void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t last_max = 64, size_t K1 = 0) {
     p.m = m; p.K = K;
+    if (K1 == 0) K1 = K;
     std::vector<uint64_t> lo, part_lo(m);
     std::vector<uint32_t> cnt, seg, part_cnt(m);
     for (size_t j = 0; j < m; j++) {
         const uint64_t a = seg_off[j], len = seg_off[j + 1] - a;
         part_lo[j] = lo.size();
-        for (uint64_t c = 0; c < len; c += K) { lo.push_back(a + c); cnt.push_back((uint32_t)std::min<uint64_t>(K, len - c)); seg.push_back((uint32_t)j); }
+        for (uint64_t c = 0; c < len; c += K1) { lo.push_back(a + c); cnt.push_back((uint32_t)std::min<uint64_t>(K1, len - c)); seg.push_back((uint32_t)j); }
         part_cnt[j] = (uint32_t)(lo.size() - part_lo[j]);
     }
     p.nch1 = lo.size();
@@ -2035,8 +2037,10 @@ void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t
 // The segmented sum on the device, everything on stream s, not synchronised (the temporaries come from the call's arena, `p.blob` is read
 // by the copy: both stay alive until the caller synchronises).  group 1 / 2; jac: d_pts are in-memory Jacobian records (no d_in_inf).
 // d_out: m affine records, d_out_inf: m bytes (1 infinity, bad_code for a segment with an index >= npk, 0 otherwise).
+// d_scalars (may be null; affine points only): npk 64-bit weights -- segment j is then sum scalars[i] * pts[i] over its indices i, pass 1
+// running the ladder (k_g?_segsum_chunk_u64) over a plan whose first pass has chunks of one position.
 int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_t npk, const u32* d_idx, const SegPlan& p, u8* d_out, u8* d_out_inf,
-               u8 bad_code, hipStream_t s) {
+               u8 bad_code, hipStream_t s, const u64* d_scalars = nullptr) {
     const size_t m = p.m;
     if (m == 0) return BLSMI_OK;
     const size_t words = (size_t)(group == 1 ? 3 : 6) * NL + 1;
@@ -2048,7 +2052,14 @@ int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_
     auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(plan.as<u8>() + off); };
     HIPCHK(a.alloc(sizeof(i32) * words * p.nch1));
     const size_t n1 = p.nch1;
-    if (n1) {
+    if (n1 && d_scalars) {
+        if (jac) return BLSMI_E_ARG;
+        const bool mark = tl_ctx && s == tl_ctx->stream;                   // (profile marks are events on the context's main stream)
+        if (mark) prof_mark(group == 1 ? "k_g1_segsum_chunk_u64" : "k_g2_segsum_chunk_u64");
+        if (group == 1) hipLaunchKernelGGL(k_g1_segsum_chunk_u64, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        else hipLaunchKernelGGL(k_g2_segsum_chunk_u64, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        if (mark) prof_mark(nullptr);
+    } else if (n1) {
         if (group == 1 && jac) hipLaunchKernelGGL(k_g1_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
         else if (group == 1) hipLaunchKernelGGL(k_g1_segsum_chunk, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
         else if (jac) hipLaunchKernelGGL(k_g2_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
@@ -2068,22 +2079,25 @@ int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_
 }
 size_t segsum_chunk_of(size_t total) { const size_t K = tune().segsum_chunk; return K ? K : segsum_auto_chunk(total); }
 // host forms: everything checked here first, then one lease
+// weighted (not with jac): the _u64 forms, scalars are npk 64-bit weights
 int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m,
-                       uint8_t* out, uint8_t* out_inf) {
+                       uint8_t* out, uint8_t* out_inf, bool weighted = false, const uint64_t* scalars = nullptr) {
     if (m == 0) return BLSMI_OK;
-    if (!out || !out_inf || (npk && !pts)) return BLSMI_E_ARG;
+    if (!out || !out_inf || (npk && !pts) || (weighted && npk && !scalars)) return BLSMI_E_ARG;
     int rc = segsum_check(npk, idx, seg_off, m);
     if (rc) return rc;
     const size_t pb = group == 1 ? 96 : 192, pin = rec_bytes(pb, jac), total = seg_off[m];
     LOCK_AND_INIT();
     SegPlan plan;
-    segsum_plan(seg_off, m, segsum_chunk_of(total), plan);
-    DBuf dp, di, dx, dout, dinf;
+    segsum_plan(seg_off, m, segsum_chunk_of(total), plan, 64, weighted ? 1 : 0);
+    DBuf dp, di, dx, dout, dinf, dsc;
+    if (weighted) { HIPCHK(dsc.alloc(sizeof(uint64_t) * npk)); if (npk) HIPCHK(hipMemcpyAsync(dsc.p, scalars, sizeof(uint64_t) * npk, hipMemcpyHostToDevice, g_stream)); }
     HIPCHK(dp.alloc(pin * npk)); HIPCHK(di.alloc(npk)); HIPCHK(dx.alloc(sizeof(uint32_t) * total)); HIPCHK(dout.alloc(pb * m)); HIPCHK(dinf.alloc(m));
     if (npk) HIPCHK(hipMemcpyAsync(dp.p, pts, pin * npk, hipMemcpyHostToDevice, g_stream));
     if (in_inf && !jac && npk) HIPCHK(hipMemcpyAsync(di.p, in_inf, npk, hipMemcpyHostToDevice, g_stream));
     if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
-    rc = segsum_dev(group, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream);
+    rc = segsum_dev(group, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream,
+                    weighted ? dsc.as<u64>() : nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, pb * m, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(out_inf, dinf.p, m, hipMemcpyDeviceToHost, g_stream));
@@ -2121,6 +2135,12 @@ BLSMI_API int blsmi_g1_sum_segmented(const uint8_t* pts, const uint8_t* in_inf, 
 }
 BLSMI_API int blsmi_g2_sum_segmented(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
     return sum_segmented_host(2, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf);
+}
+BLSMI_API int blsmi_g1_sum_segmented_u64(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint64_t* scalars, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(1, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf, true, scalars);
+}
+BLSMI_API int blsmi_g2_sum_segmented_u64(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint64_t* scalars, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(2, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf, true, scalars);
 }
 BLSMI_API int blsmi_g1_sum_segmented_jac(const uint64_t* pts_jac, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
     return sum_segmented_host(1, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, npk, idx, seg_off, m, out, out_inf);
@@ -2243,6 +2263,159 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_dev(const void* d_msgs,
 BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const void* d_msgs32, const void* d_domain, const void* d_pks, size_t npk, const void* d_idx,
                                                                          const void* d_seg_off, const void* d_sigs, void* d_ok, size_t m, void* stream) {
     return agg_common_batch_dev_api<2>(d_msgs32, d_domain, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
+}
+
+// ---- grouped randomised batch verification (blsmi 0.11; include/blsmi.h "grouped") -------------------------------------------------------
+// The combined check of rlc_shard for batches whose n tuples share d messages: tuple i is (msgs[msg_idx[i]], pk_i, sig_i), and bilinearity
+// lets the tuples of one message share one pairing --
+//     g1pubs: e(G1gen, sum_i r_i sig_i) == prod_g e(sum_{i in g} r_i pk_i, H(m_g))      g2pubs: e(sum_i r_i sig_i, G2gen) == prod_g e(H(m_g), sum_{i in g} r_i pk_i)
+// d' hashes and d' Miller loops for the d' messages some tuple refers to, instead of n of each.  The keys' side is the weighted segmented
+// sum (segsum_dev with scalars: k_g?_segsum_chunk_u64, no inversion per tuple) over the host plan of group_plan.h; the signature side is
+// rlc_shard's (rlc_sig_sum on the side stream, sig_side_start_dev, aggregate_tail).  One lease, one device, no request combiner; "rlc_min"
+// is not consulted: calling this form is the caller's choice of the combined path.  When the check fails, or a point at infinity meets it
+// (an input, a group's sum, the signatures' sum), the per-tuple verdicts of verify_batch come from the buffers on the device, the d' hash
+// points gathered per tuple (k_gather_records).
+namespace {
+int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    if (n && (!msgs || !off_or_domain || !msg_idx || !pks || !sigs)) return BLSMI_E_ARG;
+    if (n > 0xffffffffull) return BLSMI_E_ARG;                             // (the permutation is the 32-bit idx of the segmented sum)
+    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    blsmi_route::GroupPlan gp;
+    std::vector<uint64_t> drawn, coff;
+    std::vector<uint8_t> cm, tmp;
+    try {
+        if (!blsmi_route::group_plan(msg_idx, n, d, gp)) return BLSMI_E_ARG;   // some msg_idx[i] >= d (d == 0 included)
+        const size_t dg = gp.msg_of.size();
+        // the messages some tuple refers to, compacted in table order (an entry nobody refers to is never hashed)
+        if (kind == 2) {
+            cm.resize(32 * dg);
+            for (size_t g = 0; g < dg; g++) memcpy(cm.data() + 32 * g, msgs + (size_t)32 * gp.msg_of[g], 32);
+        } else {
+            coff.assign(dg + 1, 0);
+            for (size_t g = 0; g < dg; g++) {
+                const uint64_t a = off_or_domain[gp.msg_of[g]], b = off_or_domain[gp.msg_of[g] + 1];
+                if (b < a) return BLSMI_E_ARG;
+                coff[g + 1] = coff[g] + (b - a);
+            }
+            cm.resize((size_t)coff[dg]);
+            for (size_t g = 0; g < dg; g++) if (coff[g + 1] > coff[g]) memcpy(cm.data() + coff[g], msgs + off_or_domain[gp.msg_of[g]], (size_t)(coff[g + 1] - coff[g]));
+        }
+        if (!scalars) drawn.resize(n);
+        if (!ok && ok_bitmap) { tmp.resize(n); ok = tmp.data(); }
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    if (!scalars) { int rc = rlc_draw_scalars(drawn.data(), n); if (rc) return rc; scalars = drawn.data(); }
+    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const Kind k = kind_of(kind);
+    const Tuning& t = tune();
+    const size_t dg = gp.msg_of.size();
+    const size_t msg_bytes = cm.size();
+    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (dg + 1);
+    const void* off_src = kind == 2 ? (const void*)off_or_domain : (const void*)coff.data();
+    const size_t words = (size_t)12 * NL;
+    const int pk_group = k.pk_bytes == 192 ? 2 : 1;
+    hipStream_t s = g_stream;
+    HIPCHK(tl_ctx->ensure_aux());
+    hipStream_t st = tl_ctx->aux[0];
+    SegPlan plan;
+    segsum_plan(gp.seg_off.data(), dg, segsum_chunk_of(n), plan, 64, 1);
+    DBuf dm, doff, dp, ds, di, dr, dx, dok, h, agg, ainf, flags, gflags, any, sum, sflag, fr0, fr1;
+    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
+    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dx.alloc(sizeof(uint32_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * dg));
+    HIPCHK(agg.alloc((size_t)k.pk_bytes * dg)); HIPCHK(ainf.alloc(dg)); HIPCHK(flags.alloc(n)); HIPCHK(gflags.alloc(dg)); HIPCHK(any.alloc(sizeof(int)));
+    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
+    // the signatures go first, on the side stream, as in rlc_shard; then the scalars, the d' messages and the plan
+    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
+    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
+    HIPCHK(hipMemcpyAsync(dr.p, scalars, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, cm.data(), msg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(doff.p, off_src, off_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
+    const AggregateRoute ar = aggregate_route(kind, dg, false, true, t, route_load(dg));   // the layout an aggregate of d' records takes; always cleared hash points
+    HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
+    HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
+    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), dg, s, ar.hash);
+    if (rc) return rc;
+    rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the keys travel while the messages are hashed
+    if (rc) return rc;
+    if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dx.p, gp.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
+                       (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
+    // sum_{i in g} r_i pk_i for every group; a sum at infinity is flagged like an input.  On s, the context's main stream: segsum_dev names
+    // k_g?_segsum_chunk_u64 in the profile only there (profile marks are events on that stream), and tests/test_gpu_rlc_grouped.py looks
+    // for the name -- a move of the sums to aux[1] must point the context's stream at it for the stretch (OnStream, as the signature side below)
+    rc = segsum_dev(pk_group, false, dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, dr.as<u64>());
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(dg)), dim3(WG), 0, s, (const u8*)agg.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)ainf.as<u8>(), gflags.as<u8>(), any.as<int>(), dg);
+    launch_miller1(kind == 0 ? h.as<u8>() : agg.as<u8>(), kind == 0 ? agg.as<u8>() : h.as<u8>(), fr0.as<i32>(), dg, s, ar, nullptr);
+    size_t cur = ar.records;
+    i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
+    while (cur > 1) { const size_t half = (cur + 1) / 2; launch_prod_level(src, dst, cur, half, s); std::swap(src, dst); cur = half; }
+    HIPCHK(hipGetLastError());
+    int bad = 0, sum_inf = 0, verdict = 0;
+    HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SigSide ss;
+    {                                                                      // sum r_i sig_i and its Miller loop, beside the tuple side
+        HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+        OnStream on(st);
+        rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
+        if (rc) return rc;
+    }
+    rc = aggregate_tail(kind, src, ss, &verdict);                          // waits for the side stream; synchronises s
+    if (rc) return rc;
+    const bool held = verdict == 1 && bad == 0 && sum_inf == 0;
+    if (held) HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
+    else {
+        // the per-tuple verdicts of verify_batch: every tuple's hash point from its group's, then the pair stage of a batch of n
+        DBuf hfull, dgo, f;
+        HIPCHK(hfull.alloc((size_t)k.h_bytes * n)); HIPCHK(dgo.alloc(sizeof(uint32_t) * n)); HIPCHK(f.alloc(sizeof(i32) * words * n));
+        HIPCHK(hipMemcpyAsync(dgo.p, gp.group_of.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        const u32 hw = (u32)(k.h_bytes / 4);
+        hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * n)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dgo.as<u32>(), hfull.as<u32>(), hw, n);
+        const VerifyRoute vr = verify_route(kind, n, false, false, t, route_load(n));
+        rc = verify_pair_stage(kind, hfull.as<u8>(), dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, s, vr);
+        if (rc) return rc;
+    }
+    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, n);
+    if (combined) *combined = held ? 1 : 0;
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                                const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                                    const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars,
+                                         ok, ok_bitmap, n, combined, FMT_JAC);
 }
 
 // ---- pairing products (blsmi 0.10; include/blsmi.h "pairing products") ------------------------------------------------------------------

@@ -1159,6 +1159,117 @@ def verify_aggregate_common_batch_dev(group, d_msgs, d_off_or_domain, d_pks, npk
               C.c_void_p(d_seg_off or 0), C.c_void_p(d_sigs or 0), C.c_void_p(d_ok or 0), C.c_size_t(m), C.c_void_p(stream)), "verify_aggregate_common_batch_dev")
 
 
+# ---- grouped randomised batch verification and the weighted segmented sums (blsmi 0.11) ----------------------------------------------
+_u32p = C.POINTER(C.c_uint32)
+_G_HEAD = [_u8p, _u64p, C.c_size_t, _u32p]                                 # msgs, msg_off, d, msg_idx
+_G_HEAD_DOMAIN = [_u8p, _u8p, C.c_size_t, _u32p]                           # msgs32, domain, d, msg_idx
+_G_TAIL = [_u64p, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_int)]              # scalars, ok, ok_bitmap, n, combined
+_SUM_U64 = [_u8p, _u8p, C.c_size_t, _u64p, _u32p, _u64p, C.c_size_t, _u8p, _u8p]
+# the argument types of the eight entry points of 0.11, as include/blsmi.h declares them (tests/test_rlc_grouped_cpu.py compares)
+ARGTYPES_0_11 = {
+    "blsmi_g2pubs_verify_batch_rlc_grouped": _G_HEAD + [_u8p, _u8p, _u8p] + _G_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_grouped": _G_HEAD + [_u8p, _u8p, _u8p] + _G_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped": _G_HEAD_DOMAIN + [_u8p, _u8p, _u8p] + _G_TAIL,
+    "blsmi_g2pubs_verify_batch_rlc_grouped_jac": _G_HEAD + [_u64p, _u64p] + _G_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_grouped_jac": _G_HEAD + [_u64p, _u64p] + _G_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac": _G_HEAD_DOMAIN + [_u64p, _u64p] + _G_TAIL,
+    "blsmi_g1_sum_segmented_u64": _SUM_U64,
+    "blsmi_g2_sum_segmented_u64": _SUM_U64,
+}
+
+
+def _fn_0_11(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_11[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _msg_idx(msg_idx, n):
+    ix = np.ascontiguousarray(np.asarray(msg_idx, dtype=np.uint32))
+    if ix.shape != (n,):
+        raise ValueError("need one message index per tuple")
+    return ix, (ix.ctypes.data_as(_u32p) if n else None)
+
+
+def _verify_batch_rlc_grouped(name, kind, jac, msgs, msg_idx, pks, sigs, inf_flags, scalars, domain8=None):
+    """-> (ok, bitmap, combined); msgs: the table of d messages, msg_idx: n indices into it"""
+    pkb, sgb = (192, 96) if kind == 0 else (96, 192)
+    d = len(msgs)
+    n = len(msg_idx)
+    ix, pix = _msg_idx(msg_idx, n)
+    if domain8 is None:
+        buf, off = _msgs(msgs)
+        head = (_p8(buf), off.ctypes.data_as(_u64p))
+    else:
+        buf = _u8(b"".join(bytes(m) for m in msgs) or b"\0" * 32, 32 * max(d, 1))
+        dom = _u8(domain8, 8)
+        head = (_p8(buf), _p8(dom))
+    if jac:
+        p, pp = _j64(pks, pkb // 2 * 3 * n)
+        s, ps = _j64(sigs, sgb // 2 * 3 * n)
+        mid = (pp, ps)
+    else:
+        p, s = _u8(pks, pkb * n), _u8(sigs, sgb * n)
+        f = _u8(inf_flags, n) if inf_flags is not None else None
+        mid = (_p8(p), _p8(s), _p8(f))
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(_fn_0_11(name)(*head, d, pix, *mid, pr, _p8(ok), _p8(bitmap), n, C.byref(comb)), name[len("blsmi_"):])
+    return ok.astype(bool), bitmap, comb.value
+
+
+def g2pubs_verify_batch_rlc_grouped(msgs, msg_idx, pks, sigs, inf_flags=None, scalars=None):
+    """blsmi_g2pubs_verify_batch_rlc_grouped -> (ok, bitmap, combined): tuple i is (msgs[msg_idx[i]], pk_i, sig_i); the tuples of one message
+    share one pairing of the combined check.  Verdicts as g2pubs_verify_batch_rlc on the expanded messages."""
+    return _verify_batch_rlc_grouped("blsmi_g2pubs_verify_batch_rlc_grouped", 0, False, msgs, msg_idx, pks, sigs, inf_flags, scalars)
+
+
+def g1pubs_verify_batch_rlc_grouped(msgs, msg_idx, pks, sigs, inf_flags=None, scalars=None):
+    return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_batch_rlc_grouped", 1, False, msgs, msg_idx, pks, sigs, inf_flags, scalars)
+
+
+def g1pubs_verify_with_domain_batch_rlc_grouped(msgs32, domain8, msg_idx, pks, sigs, inf_flags=None, scalars=None):
+    return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped", 2, False, msgs32, msg_idx, pks, sigs, inf_flags, scalars, domain8)
+
+
+def g2pubs_verify_batch_rlc_grouped_jac(msgs, msg_idx, pks, sigs, scalars=None):
+    """the same over in-memory points (288 / 144 bytes each)"""
+    return _verify_batch_rlc_grouped("blsmi_g2pubs_verify_batch_rlc_grouped_jac", 0, True, msgs, msg_idx, pks, sigs, None, scalars)
+
+
+def g1pubs_verify_batch_rlc_grouped_jac(msgs, msg_idx, pks, sigs, scalars=None):
+    return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_batch_rlc_grouped_jac", 1, True, msgs, msg_idx, pks, sigs, None, scalars)
+
+
+def g1pubs_verify_with_domain_batch_rlc_grouped_jac(msgs32, domain8, msg_idx, pks, sigs, scalars=None):
+    return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac", 2, True, msgs32, msg_idx, pks, sigs, None, scalars, domain8)
+
+
+def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf):
+    so, pidx, _keep = _seg_args(idx, seg_off)
+    m = so.size - 1
+    p = _u8(pts, pb * npk) if npk else np.zeros(1, np.uint8)
+    r, pr = _scalars(scalars, npk)
+    f = _u8(in_inf, npk) if in_inf is not None else None
+    out = np.zeros(max(1, pb * m), dtype=np.uint8)
+    oinf = np.zeros(max(1, m), dtype=np.uint8)
+    _check(_fn_0_11(name)(_p8(p), _p8(f), npk, pr if npk else None, pidx, so.ctypes.data_as(_u64p), m, _p8(out), _p8(oinf)), name[len("blsmi_"):])
+    return out[:pb * m].tobytes(), oinf[:m].copy()
+
+
+def g1_sum_segmented_u64(pts, npk, scalars, idx, seg_off, in_inf=None):
+    """m weighted sums of affine G1 points: segment j = sum scalars[idx[k]] * pts[idx[k]] for seg_off[j] <= k < seg_off[j + 1]; scalars: npk
+    64-bit integers (zero allowed).  -> (m*96 affine bytes, out_inf)"""
+    return _sum_segmented_u64("blsmi_g1_sum_segmented_u64", 96, pts, npk, scalars, idx, seg_off, in_inf)
+
+
+def g2_sum_segmented_u64(pts, npk, scalars, idx, seg_off, in_inf=None):
+    return _sum_segmented_u64("blsmi_g2_sum_segmented_u64", 192, pts, npk, scalars, idx, seg_off, in_inf)
+
+
 # ---- pairing products (blsmi 0.10): many MillerLoop(items) + FinalExponentiation checks in one call -----------------------------
 def _pprod_offsets(seg_off, np_):
     so = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)

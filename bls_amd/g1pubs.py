@@ -134,6 +134,23 @@ def VerifyBatchRandomized(msgs, pubs, sigs, scalars=None):
     return [bool(x) for x in ok]
 
 
+def VerifyBatchRandomizedGrouped(msgs, msg_idx, pubs, sigs, scalars=None):
+    """VerifyBatchRandomized for tuples that share messages: msgs is a table of d messages and tuple i is (msgs[msg_idx[i]], pubs[i], sigs[i]).
+    The tuples of one message share one pairing of the combined check (d hashes and Miller loops, not n); the verdicts are those of
+    VerifyBatchRandomized on the expanded messages.  The combined path runs at any n: choosing this form is choosing it."""
+    n = len(msg_idx)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok, _, _ = engine.g1pubs_verify_batch_rlc_grouped_jac(msgs, msg_idx, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars)
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok, _, _ = engine.g1pubs_verify_batch_rlc_grouped(msgs, msg_idx, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars)
+    return [bool(x) for x in ok]
+
+
 def VerifySerializedBatch(msgs, pub_bytes, sig_bytes):
     """DeserializePublicKey + DeserializeSignature + Verify per tuple, in one device pass over the 48-byte keys and
     96-byte signatures of the wire format.  A tuple whose key or signature does not deserialise (the reference returns
@@ -184,6 +201,21 @@ def VerifyWithDomainBatchRandomized(msgs32, pubs, sigs, domain8, scalars=None):
         return [bool(x) for x in ok]
     flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
     ok, _ = engine.g1pubs_verify_with_domain_batch_rlc(msgs32, domain8, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars)
+    return [bool(x) for x in ok]
+
+
+def VerifyWithDomainBatchRandomizedGrouped(msgs32, msg_idx, pubs, sigs, domain8, scalars=None):
+    """VerifyWithDomainBatchRandomized over a table of d 32-byte messages and n indices into it (VerifyBatchRandomizedGrouped)"""
+    n = len(msg_idx)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok, _, _ = engine.g1pubs_verify_with_domain_batch_rlc_grouped_jac(msgs32, domain8, msg_idx, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars)
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok, _, _ = engine.g1pubs_verify_with_domain_batch_rlc_grouped(msgs32, domain8, msg_idx, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars)
     return [bool(x) for x in ok]
 
 

@@ -76,7 +76,10 @@ void blsmi_shutdown(void);
  * the "rlc_min" option, BLSMI_E_RNG and BLSMI_OP_G1_MUL_U64; no existing prototype changes.  0.9 adds the segmented sums (blsmi_g?_sum_segmented[_jac|_dev]),
  * the batches of VerifyAggregateCommon over key committees (blsmi_g?pubs_verify_aggregate_common*_batch[_jac|_dev]) and the "segsum_chunk" option;
  * no existing prototype changes.  0.10 adds the pairing products (blsmi_pairing_product_batch[_jac|_dev|_jac_dev]: many MillerLoop(items) + FinalExponentiation
- * checks in one call); no existing prototype changes, no new option. */
+ * checks in one call); no existing prototype changes, no new option.  0.11 adds the grouped randomised batch verification
+ * (blsmi_g?pubs_*verify*_batch_rlc_grouped[_jac]: the tuples of one message share one pairing) and the weighted segmented sums
+ * (blsmi_g?_sum_segmented_u64); no existing prototype changes, no new option.  The string below still begins "blsmi 0.10": a caller that
+ * binds by hand tells 0.11 by the presence of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -398,6 +401,49 @@ int blsmi_g1pubs_verify_batch_rlc_jac(const uint8_t *msgs, const uint64_t *off, 
                                       const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
 int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
                                                   const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+/* ---- grouped randomised batch verification (blsmi 0.11) ---------------------------------------------------------------------
+ * The combined check above for batches whose tuples share messages (an attestation subnet, a slot, a sync committee: thousands of
+ * signatures over a few dozen messages).  The messages are a table of d entries -- msgs with msg_off[d + 1] (with_domain: msgs32, d * 32
+ * bytes) -- and tuple i is (msgs[msg_idx[i]], pk_i, sig_i).  Bilinearity lets the tuples of one message share one pairing:
+ *     g1pubs: e(G1gen, sum_i r_i sig_i) == prod_g e(sum_{i in g} r_i pk_i, H(m_g))
+ *     g2pubs: e(sum_i r_i sig_i, G2gen) == prod_g e(H(m_g), sum_{i in g} r_i pk_i)
+ * d' hashes and d' Miller loops for the d' table entries some tuple refers to, not n; the signature side is that of *_verify_batch_rlc.
+ * ok, ok_bitmap, inf_flags, scalars and combined mean exactly what they mean there, and the verdicts are those of *_verify_batch_rlc (and
+ * so of *_verify_batch) on the expanded messages.  The weights are per TUPLE also inside a group: with caller scalars r_a == r_b two tuples
+ * of one message may swap signatures unnoticed -- the caller's responsibility, as every caller scalar is.
+ *   - msg_idx[i] >= d (d = 0 with n > 0 included), a zero caller scalar, and a NULL input with n > 0: BLSMI_E_ARG before any device work.
+ *     n = 0: BLSMI_OK, combined = 0.
+ *   - table entries with equal bytes are not merged (the result is correct, the call shares less); entries no tuple refers to are never hashed.
+ *   - the per-tuple path (combined = 0) runs when the check fails and when a point at infinity meets it: an input (inf_flags, the all-zero
+ *     record, z = 0 in the in-memory forms), a group whose weighted sum is infinity, the signatures' sum.
+ * "rlc_min" does NOT apply: calling this form is the caller's choice of the combined path, at any n.  The call runs on one device (it is not
+ * split like *_verify_batch_rlc) and never joins the request combiner, like the pairing products.
+ * When to call it (one MI355X, host buffers, ms; profiles/r08_rlc_grouped.log; rlc / batch = *_verify_batch_rlc at rlc_min = 0 and
+ * *_verify_batch of the build before this form, messages expanded):
+ *     n x d              g2pubs grouped / rlc / batch      g1pubs grouped / rlc / batch
+ *     1 024 x 64              8.0 /  5.9 /  2.7                 8.4 /  8.3 /  3.4
+ *     16 384 x 64            10.1 / 11.0 /  8.7                12.5 / 16.2 / 10.6
+ *     65 536 x 64            13.3 / 17.5 / 27.2                14.6 / 25.0 / 32.1
+ *     65 536 x 8 192         18.5 / 17.5 / 27.2                18.0 / 25.1 / 32.1
+ *     65 536 x 65 536        59.2 / 17.4 / 26.4                43.5 / 25.2 / 32.1
+ * It pays from some tens of thousands of tuples with d up to a few thousand (1.3x / 1.7x the plain randomised form at 65 536 x 64); the call has
+ * a floor of about 8 ms, and with d near n it loses badly (one final pass and one cleared hash per message): call *_verify_batch_rlc there.  One
+ * bad tuple at 65 536 x 64 costs 36.8 / 40.6 ms (the combined check, then the per-tuple path). */
+int blsmi_g2pubs_verify_batch_rlc_grouped(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* n */,
+                                          const uint8_t *pks /* n*192 */, const uint8_t *sigs /* n*96 */, const uint8_t *inf_flags,
+                                          const uint64_t *scalars /* n, may be NULL */, uint8_t *ok /* n, may be NULL */, uint8_t *ok_bitmap /* may be NULL */, size_t n, int *combined);
+int blsmi_g1pubs_verify_batch_rlc_grouped(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* n */,
+                                          const uint8_t *pks /* n*96 */, const uint8_t *sigs /* n*192 */, const uint8_t *inf_flags,
+                                          const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped(const uint8_t *msgs32 /* d*32 */, const uint8_t domain[8], size_t d, const uint32_t *msg_idx /* n */,
+                                                      const uint8_t *pks, const uint8_t *sigs, const uint8_t *inf_flags,
+                                                      const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g2pubs_verify_batch_rlc_grouped_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*36 */, const uint64_t *sigs /* n*18 */,
+                                              const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_batch_rlc_grouped_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
+                                              const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac(const uint8_t *msgs32, const uint8_t domain[8], size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*18 */,
+                                                          const uint64_t *sigs /* n*36 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
 /* device-pointer forms (every buffer on ONE of the library's devices; `stream` as in blsmi_pairing_batch_dev): the points resident in HBM as the
  * Go side holds them.  d_ok: n verdict bytes on the device. */
 int blsmi_pairing_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, void *d_out_fq12, size_t n, void *stream);
@@ -532,6 +578,16 @@ int blsmi_g1_sum_segmented_dev(const void *d_pts, const void *d_in_inf, size_t n
                                void *d_out, void *d_out_inf, void *stream);
 int blsmi_g2_sum_segmented_dev(const void *d_pts, const void *d_in_inf, size_t npk, const void *d_idx, const void *d_seg_off, size_t m,
                                void *d_out, void *d_out_inf, void *stream);
+/* Weighted segmented sums (blsmi 0.11), a 64-bit segmented MSM: segment j is sum scalars[idx[k]] * pts[idx[k]] over seg_off[j] <= k <
+ * seg_off[j + 1] -- the scalar is addressed by the same index as the point.  Arguments, checks and BLSMI_E_ARG rules as
+ * blsmi_g?_sum_segmented, plus scalars (npk words, NULL with npk > 0: BLSMI_E_ARG).  A zero scalar is allowed and contributes nothing, as
+ * a point flagged in in_inf does.  Each record is the bytes blsmi_g?_sum gives for the multiples, whatever "segsum_chunk" is. */
+int blsmi_g1_sum_segmented_u64(const uint8_t *pts /* npk*96 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk, const uint64_t *scalars /* npk */,
+                               const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
+                               uint8_t *out /* m*96 */, uint8_t *out_inf /* m */);
+int blsmi_g2_sum_segmented_u64(const uint8_t *pts /* npk*192 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk, const uint64_t *scalars /* npk */,
+                               const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
+                               uint8_t *out /* m*192 */, uint8_t *out_inf /* m */);
 /* Batches of VerifyAggregateCommon (g2pubs/bls.go:275-278, g1pubs/bls.go:287-297).  Item j:
  *   VerifyAggregateCommon(sig_j, {pks[idx[k]] : seg_off[j] <= k < seg_off[j + 1]}, msg_j)
  * with msg_j = msgs[msg_off[j] .. msg_off[j + 1]) (with_domain: the 32 bytes msgs32 + 32 j under the common 8-byte domain).  Each verdict
