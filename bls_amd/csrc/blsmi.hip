@@ -8,6 +8,7 @@
 #include "prepared.h"
 #include "route.h"
 #include "group_plan.h"
+#include "locate_plan.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

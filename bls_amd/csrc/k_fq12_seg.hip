@@ -52,6 +52,18 @@ KERNEL_ROW k_fq12_seg_prod_row(const i32* src, size_t nsrc, const u8* skip, cons
     if (out_m384) store_m384(out_m384 + 72 * c + 6 * row_fq_index(pr, par), acc.c.c);
 }
 
+// dst[t] = a[t] * b[t] for the n records of two hand-off buffers, a lane row per product (the block checks of blsmi 0.12: a block's product
+// of tuple-side Miller values times its signature side's).  dst / out_m384 as above: the final exponentiation's input in either form.
+KERNEL_ROW k_fq12_mul_pairs_row(const i32* a, const i32* b, i32* dst, u64* out_m384, size_t n) {
+    const int par = threadIdx.x & 1, pr = (threadIdx.x >> 1) & 7;
+    const size_t t = (size_t)blockIdx.x * RT + (threadIdx.x >> 4);
+    const size_t tt = t < n ? t : n - 1;
+    const P2::R12 acc = P2::r12_mul(row_load12(a, n, tt, pr, par), row_load12(b, n, tt, pr, par));
+    if (t >= n || pr >= 6) return;
+    if (dst) soa_store(dst, n, t, row_fq_index(pr, par), fp_relabel<FpS::L, FpS::V>(acc.c.c));
+    if (out_m384) store_m384(out_m384 + 72 * t + 6 * row_fq_index(pr, par), acc.c.c);
+}
+
 // The pairs a product leaves out: skip[k] = the caller's flags (bit 0: P_k, bit 1: Q_k at infinity; null: none) or an all-zero record.  Such a
 // pair's records are replaced by the generators' so that the Miller kernels, which take no point at infinity, run on valid points; its value
 // is then left out by the product.  g1 / g2: the call's own copies.

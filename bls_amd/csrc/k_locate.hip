@@ -1,0 +1,61 @@
+// k_locate.hip -- the housekeeping kernels of the block-locating randomised verification (blsmi 0.12: blsmi_g?pubs_*verify*_batch_rlc_locate,
+// verify_host.inc): the signature-side pairs of the block checks, the verdict byte of every block, and the gathers / the scatter that
+// move the tuples of the failing blocks into dense buffers for the per-tuple stage and their verdicts back.  The product of a block's
+// Miller values with its signature side's is k_fq12_mul_pairs_row (k_fq12_seg.hip).
+#include "tower.cuh"
+#include "device_io.cuh"
+
+// The B pairs whose Miller values stand for the signature side of the block equations: (-S_b, G2gen) for g2pubs (kind 0, S_b 96 bytes),
+// (-G1gen, S_b) otherwise (S_b 192 bytes).  Where S_b is at infinity (s_inf[b], or the all-zero record) the pair is the generators' -- the
+// Miller kernels take no point at infinity -- and bad[b] = 1: the block's equation is not trusted.
+KERNEL2 k_locate_sig_pairs(int kind, const u8* sums, const u8* s_inf, const u8* gen1, const u8* gen2, u8* g1, u8* g2, u8* bad, size_t nb) {
+    const size_t b = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (b >= nb) return;
+    const u32 sw = kind == 0 ? 24 : 48;
+    const u32* s = reinterpret_cast<const u32*>(sums) + (size_t)sw * b;
+    u32 any = 0;
+    for (u32 i = 0; i < sw; i++) any |= s[i];
+    const bool inf = s_inf[b] != 0 || any == 0;
+    bad[b] = inf ? 1 : 0;
+    const u8* p = (kind == 0 && !inf) ? reinterpret_cast<const u8*>(s) : gen1;
+    const u8* q = (kind != 0 && !inf) ? reinterpret_cast<const u8*>(s) : gen2;
+    u32* o1 = reinterpret_cast<u32*>(g1) + (size_t)24 * b;
+    u32* o2 = reinterpret_cast<u32*>(g2) + (size_t)48 * b;
+    const u32* p32 = reinterpret_cast<const u32*>(p);
+    const u32* q32 = reinterpret_cast<const u32*>(q);
+    for (int i = 0; i < 12; i++) o1[i] = p32[i];
+    store_be48(reinterpret_cast<u8*>(o1 + 12), fp_neg(load_be48(p + 48)));  // (a point of odd order has y != 0; store_be48 writes the canonical q - y)
+    for (int i = 0; i < 48; i++) o2[i] = q32[i];
+}
+
+// fail[b] = 1 unless block b's equation held (is_one[b]), its sum was a point (bad[b] == 0) and none of its tuples is flagged in either of
+// the two flag arrays (the inputs', the scaled points'); block b is the tuples [b * block, min(n, (b + 1) * block)).  Sixteen lanes per
+// block: the flag bytes of a block are contiguous, lane l reads bytes l, l + 16, ...
+KERNEL2 k_locate_block_fail(const u8* flags, const u8* flags2, size_t n, size_t block, const u8* bad, const u8* is_one, u8* fail, size_t nb) {
+    const u32 l = threadIdx.x & 15;
+    const size_t b = (size_t)blockIdx.x * (WG / 16) + (threadIdx.x >> 4);
+    const size_t bb = b < nb ? b : nb - 1;
+    const size_t lo = bb * block, hi = n - lo > block ? lo + block : n;
+    u32 f = 0;
+    for (size_t i = lo + l; i < hi; i += 16) f |= (u32)flags[i] | flags2[i];
+    f |= __shfl_xor(f, 1); f |= __shfl_xor(f, 2); f |= __shfl_xor(f, 4); f |= __shfl_xor(f, 8);
+    if (b < nb && l == 0) fail[b] = (f || bad[b] || !is_one[b]) ? 1 : 0;
+}
+
+// dst record r = src record idx[r] for records of q 16-byte pieces (96 bytes: 6, 192 bytes: 12), a lane per piece: the q lanes of a record
+// are neighbours and read it whole.  The host has built the indices (locate_plan.h: locate_positions); buffers are 16-byte aligned.
+KERNEL2 k_gather_records16(const uint4* src, const u32* idx, uint4* dst, u32 q, size_t n) {
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (t >= (size_t)q * n) return;
+    const size_t r = t / q;
+    dst[t] = src[(size_t)idx[r] * q + (t - r * q)];
+}
+// dst[r] = src[idx[r]] (the caller's flag bytes of the gathered tuples) / dst[idx[r]] = src[r] (their verdicts back into the call's)
+KERNEL2 k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n) {
+    const size_t r = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (r < n) dst[r] = src[idx[r]];
+}
+KERNEL2 k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n) {
+    const size_t r = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (r < n) dst[idx[r]] = src[r];
+}

@@ -56,8 +56,15 @@ __global__ void k_clear_h2_oct(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_clear_h2_row(const i32* jbuf, u8* good, u8* out, size_t n);
 // k_fq12_seg.hip
 __global__ void k_fq12_seg_prod_row(const i32* src, size_t nsrc, const u8* skip, const u64* lo, const u32* cnt, i32* dst, u64* out_m384, size_t nch);
+__global__ void k_fq12_mul_pairs_row(const i32* a, const i32* b, i32* dst, u64* out_m384, size_t n);
 __global__ void k_pprod_skip(u8* g1, u8* g2, const u8* in_flags, const u8* gen1, const u8* gen2, u8* skip, size_t n);
 __global__ void k_fq12_is_one_m384(const u64* vals, u8* is_one, size_t n);
+// k_locate.hip
+__global__ void k_locate_sig_pairs(int kind, const u8* sums, const u8* s_inf, const u8* gen1, const u8* gen2, u8* g1, u8* g2, u8* bad, size_t nb);
+__global__ void k_locate_block_fail(const u8* flags, const u8* flags2, size_t n, size_t block, const u8* bad, const u8* is_one, u8* fail, size_t nb);
+__global__ void k_gather_records16(const uint4* src, const u32* idx, uint4* dst, u32 q, size_t n);
+__global__ void k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
+__global__ void k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);

@@ -2442,34 +2442,21 @@ void pprod_plan(const uint64_t* seg_off, size_t m, SegPlan& plan) {
     const size_t K = segsum_chunk_of(seg_off[m]);
     segsum_plan(seg_off, m, K, plan, std::max<size_t>(K, 2));
 }
-// d_g1 / d_g2: np affine records the call owns (records of skipped pairs are overwritten); d_flags: np flag bytes or null.  The m values go to
-// d_out (576 bytes each) and / or the m verdict bytes to d_is_one.  Synchronises.
-int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& plan, void* d_out, void* d_is_one, hipStream_t s) {
-    const size_t m = plan.m, words = (size_t)12 * NL;
-    DBuf skip, f, blob, prod, vals;
-    HIPCHK(blob.alloc(plan.blob.size()));
-    HIPCHK(hipMemcpyAsync(blob.p, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, s));
-    auto at64 = [&](size_t off) { return reinterpret_cast<const u64*>(blob.as<u8>() + off); };
-    auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(blob.as<u8>() + off); };
-    // the final exponentiation's layout: what blsmi_final_exponentiation_batch gives m values (wave, row), and beyond those -- where that entry
-    // point has only its one-lane kernel -- the quad / pair kernels a Pairing call of m tuples ends in
-    Layout fe = final_exp_layout(m, tune(), route_load(np));
-    if (fe == Layout::single && tune().pair_layout) fe = m <= tune().quad_max ? Layout::quad : Layout::pair;
-    const i32* src = nullptr;
-    if (np) {
-        HIPCHK(skip.alloc(np)); HIPCHK(f.alloc(sizeof(i32) * words * np));
-        hipLaunchKernelGGL(k_pprod_skip, dim3(nblocks(np)), dim3(WG), 0, s, d_g1, d_g2, d_flags, (const u8*)g_gens.g1, (const u8*)g_gens.g2, skip.as<u8>(), np);
-        launch_miller_tuples(d_g1, d_g2, f.as<i32>(), np, s, pairing_layout(0, np, tune(), route_load(np)));
-        src = f.as<i32>();
-    }
-    // the product: pass 1 over the Miller values, the folds, the final pass (its records: the final exponentiation's input -- the reference's
-    // in-memory form for the wave layout, the hand-off buffer otherwise)
-    prof_mark("k_fq12_seg_prod_row");
-    const u8* sk = skip.as<u8>();
-    size_t nsrc = np;
+// the final exponentiation's layout for m values: what blsmi_final_exponentiation_batch gives them (wave, row), and beyond those -- where that
+// entry point has only its one-lane kernel -- the quad / pair kernels a Pairing call of m tuples ends in
+Layout pprod_fe_layout(size_t m, size_t load) {
+    const Layout fe = final_exp_layout(m, tune(), load);
+    return fe == Layout::single && tune().pair_layout ? (m <= tune().quad_max ? Layout::quad : Layout::pair) : fe;
+}
+// The segmented product of the nsrc values at src over `plan`, whose arrays are on the device at d_blob: pass 1 (skip: the values it leaves
+// out, or null), the folds, the final pass.  Its m records go to dst (a hand-off buffer) and / or out_m384 (the reference's in-memory form).
+int seg_prod_dev(const i32* src, size_t nsrc, const u8* skip, const SegPlan& plan, const u8* d_blob, i32* dst, u64* out_m384, hipStream_t s) {
+    const size_t words = (size_t)12 * NL;
+    auto at64 = [&](size_t off) { return reinterpret_cast<const u64*>(d_blob + off); };
+    auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(d_blob + off); };
     if (plan.nch1) {
         DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * plan.nch1));
-        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.nch1)), dim3(WG), 0, s, src, nsrc, sk, at64(plan.ch_lo), at32(plan.ch_cnt), d.as<i32>(), (u64*)nullptr, plan.nch1);
+        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.nch1)), dim3(WG), 0, s, src, nsrc, skip, at64(plan.ch_lo), at32(plan.ch_cnt), d.as<i32>(), (u64*)nullptr, plan.nch1);
         src = d.as<i32>(); nsrc = plan.nch1;
     }
     for (const SegPlan::Fold& fo : plan.folds) {
@@ -2477,24 +2464,49 @@ int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& p
         hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(fo.nch)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(fo.lo), at32(fo.cnt), d.as<i32>(), (u64*)nullptr, fo.nch);
         src = d.as<i32>(); nsrc = fo.nch;
     }
-    HIPCHK(prod.alloc(fe == Layout::wave ? 576 * m : sizeof(i32) * words * m));
-    hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(m)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(plan.seg_lo), at32(plan.seg_cnt),
-                       fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, m);
-    u64* out = (u64*)d_out;
-    if (!out) { HIPCHK(vals.alloc(576 * m)); out = vals.as<u64>(); }
+    hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.m)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(plan.seg_lo), at32(plan.seg_cnt), dst, out_m384, plan.m);
+    return BLSMI_OK;
+}
+// The final exponentiation of m values in the layout fe -- prod: 576-byte in-memory records for the wave layout, a hand-off buffer otherwise --
+// into `out` (576 bytes each) and, where d_is_one is given, their comparison with one.  Leaves the profile mark open.
+void final_exp_values(Layout fe, const void* prod, u64* out, void* d_is_one, size_t m, hipStream_t s) {
     prof_mark(fe == Layout::wave ? "k_lat:finalexp1" : fe == Layout::row ? "k_final_exp_row" : fe == Layout::quad ? "k_final_exp_quad" : fe == Layout::pair ? "k_final_exp_pair" : "k_final_exp");
     if (fe == Layout::wave)
         hipLaunchKernelGGL(k_lat, dim3((unsigned)m), dim3(64), lat_lds_bytes(LAT_FINALEXP1_OFFSET), s, (const u8*)g_gens.lat + LAT_FINALEXP1_OFFSET,
-                           (const u8*)prod.p, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                           (const u8*)prod, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
                            (const u8*)nullptr, (u8*)nullptr, out, m);
-    else if (fe == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
-    else if (fe == Layout::quad) hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
-    else if (fe == Layout::pair) hipLaunchKernelGGL(k_final_exp_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
-    else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(m)), dim3(WG), 0, s, (const i32*)prod.as<i32>(), out, m, 0);
+    else if (fe == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
+    else if (fe == Layout::quad) hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
+    else if (fe == Layout::pair) hipLaunchKernelGGL(k_final_exp_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
+    else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
     if (d_is_one) {
         prof_mark("k_fq12_is_one_m384");
         hipLaunchKernelGGL(k_fq12_is_one_m384, dim3(rblocks(m)), dim3(WG), 0, s, (const u64*)out, (u8*)d_is_one, m);
     }
+}
+// d_g1 / d_g2: np affine records the call owns (records of skipped pairs are overwritten); d_flags: np flag bytes or null.  The m values go to
+// d_out (576 bytes each) and / or the m verdict bytes to d_is_one.  Synchronises.
+int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& plan, void* d_out, void* d_is_one, hipStream_t s) {
+    const size_t m = plan.m, words = (size_t)12 * NL;
+    DBuf skip, f, blob, prod, vals;
+    HIPCHK(blob.alloc(plan.blob.size()));
+    HIPCHK(hipMemcpyAsync(blob.p, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, s));
+    const Layout fe = pprod_fe_layout(m, route_load(np));
+    const i32* src = nullptr;
+    if (np) {
+        HIPCHK(skip.alloc(np)); HIPCHK(f.alloc(sizeof(i32) * words * np));
+        hipLaunchKernelGGL(k_pprod_skip, dim3(nblocks(np)), dim3(WG), 0, s, d_g1, d_g2, d_flags, (const u8*)g_gens.g1, (const u8*)g_gens.g2, skip.as<u8>(), np);
+        launch_miller_tuples(d_g1, d_g2, f.as<i32>(), np, s, pairing_layout(0, np, tune(), route_load(np)));
+        src = f.as<i32>();
+    }
+    // the product (its records: the final exponentiation's input -- the reference's in-memory form for the wave layout, the hand-off buffer otherwise)
+    prof_mark("k_fq12_seg_prod_row");
+    HIPCHK(prod.alloc(fe == Layout::wave ? 576 * m : sizeof(i32) * words * m));
+    int rc = seg_prod_dev(src, np, skip.as<u8>(), plan, blob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
+    if (rc) return rc;
+    u64* out = (u64*)d_out;
+    if (!out) { HIPCHK(vals.alloc(576 * m)); out = vals.as<u64>(); }
+    final_exp_values(fe, prod.p, out, d_is_one, m, s);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -2567,3 +2579,204 @@ BLSMI_API int blsmi_pairing_product_batch_dev(const void* d_g1_aff, const void* 
 BLSMI_API int blsmi_pairing_product_batch_jac_dev(const void* d_g1_jac, const void* d_g2_jac, size_t np, const void* d_seg_off, size_t m, void* d_out_fq12, void* d_is_one, void* stream) {
     return pprod_dev_api(d_g1_jac, d_g2_jac, nullptr, np, d_seg_off, m, d_out_fq12, d_is_one, stream, true);
 }
+
+// ---- randomised batch verification that finds the bad tuples by blocks (blsmi 0.12; include/blsmi.h "locate") -----------------------------
+// rlc_shard's combined check with the batch cut into B contiguous blocks of `block` tuples (locate_plan.h).  The tuple side's Miller values
+// are multiplied block by block first (k_fq12_seg_prod_row over the blocks' record borders) and the B block values KEPT; the product tree
+// then runs over those for the total, which is checked as in rlc_shard.  When the total holds and nothing is flagged every verdict is 1.
+// Otherwise one pairing equation per block --
+//     g2pubs: e(S_b, G2gen) == prod_{i in b} e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, S_b) == prod_{i in b} e(r_i pk_i, H(m_i))        S_b = sum_{i in b} r_i sig_i
+// -- decides which blocks hold: the S_b by the weighted segmented sum, B Miller loops for (-S_b, G2gen) / (-G1gen, S_b), each times its block
+// value (k_fq12_mul_pairs_row), B final exponentiations, the comparison with one.  A block whose weights are its own tuples' r_i is wrong
+// with probability at most 2^-64, as the whole batch is.  A block with a flagged tuple, or whose S_b is at infinity, counts as failing
+// whatever its equation says.  The tuples of the failing blocks, and only those, are gathered into dense buffers and get verify_batch's
+// per-tuple verdicts.  One lease, one device, no request combiner, "rlc_min" not consulted.  The hash points are always cleared here, also
+// where rlc_shard raises the product to 1 - x instead (agg_pow_wanted): the block values then need no exponentiation each and the
+// per-tuple stage reads the hash points that are there (DESIGN 3l has what that costs the call that holds).
+namespace {
+int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                 const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked, int fmt = 0) {
+    if (combined) *combined = 0;
+    if (rechecked) *rechecked = 0;
+    if (!blsmi_route::locate_block_valid(block)) return BLSMI_E_ARG;
+    if (n && (!msgs || !off_or_domain || !pks || !sigs)) return BLSMI_E_ARG;
+    if (n > 0xffffffffull) return BLSMI_E_ARG;                             // (the positions of the failing blocks are 32-bit indices)
+    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    std::vector<uint64_t> drawn;
+    std::vector<uint8_t> tmp;
+    try {
+        if (!scalars) drawn.resize(n);
+        if (!ok && ok_bitmap) { tmp.resize(n); ok = tmp.data(); }
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    if (!scalars) { int rc = rlc_draw_scalars(drawn.data(), n); if (rc) return rc; scalars = drawn.data(); }
+    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const Kind k = kind_of(kind);
+    const Tuning& t = tune();
+    const size_t load = route_load(n);
+    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
+    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    HIPCHK(tl_ctx->ensure_aux());
+    hipStream_t st = tl_ctx->aux[0];
+    const AggregateRoute ar = aggregate_route(kind, n, false, true, t, load);
+    const size_t nrec = ar.records;
+    blsmi_route::LocatePlan lp;
+    SegPlan bplan;
+    try {
+        blsmi_route::locate_plan(n, block ? block : blsmi_route::locate_auto_block(n), nrec != n, lp);
+        pprod_plan(lp.rec_off.data(), lp.blocks(), bplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t B = lp.blocks(), half = (B + 1) / 2;
+    DBuf dm, doff, dp, ds, di, dr, dok, h, scaled, sinf, flags, sflags, any, sum, sflag, fr, bval, t0, t1, bblob;
+    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
+    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * n));
+    HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(flags.alloc(n)); HIPCHK(sflags.alloc(n)); HIPCHK(any.alloc(sizeof(int)));
+    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
+    HIPCHK(fr.alloc(sizeof(i32) * words * nrec)); HIPCHK(bval.alloc(sizeof(i32) * words * B)); HIPCHK(t0.alloc(sizeof(i32) * words * half)); HIPCHK(t1.alloc(sizeof(i32) * words * half));
+    HIPCHK(bblob.alloc(bplan.blob.size()));
+    // stage 1, as rlc_shard: the signatures first, on the side stream; the scalars, the messages, the hash, the keys, the flags, r_i H_i / r_i pk_i, the Miller loops
+    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
+    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
+    HIPCHK(hipMemcpyAsync(dr.p, scalars, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
+    HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
+    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, ar.hash);
+    if (rc) return rc;
+    rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the keys travel while the messages are hashed
+    if (rc) return rc;
+    if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
+                       (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
+    prof_mark("k_g1_mul_u64");
+    hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, kind == 0 ? (const u8*)h.as<u8>() : (const u8*)dp.as<u8>(), (const u64*)dr.as<u64>(), scaled.as<u8>(), sinf.as<u8>(), n);
+    prof_mark(nullptr);
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)scaled.as<u8>(), 24, (const u8*)nullptr, 0, (const u8*)sinf.as<u8>(), sflags.as<u8>(), any.as<int>(), n);   // (its own bytes: the inputs' flags stay for the block checks)
+    launch_miller1(scaled.as<u8>(), kind == 0 ? dp.as<u8>() : h.as<u8>(), fr.as<i32>(), n, s, ar, nullptr);
+    // stage 2: the block values, then the tree over them (its levels alternate between t0 and t1; the block values stay)
+    prof_mark("k_fq12_seg_prod_row");
+    rc = seg_prod_dev(fr.as<i32>(), nrec, nullptr, bplan, bblob.as<u8>(), bval.as<i32>(), nullptr, s);
+    if (rc) return rc;
+    prof_mark(nullptr);
+    const i32* src = bval.as<i32>();
+    i32* dst = t0.as<i32>();
+    for (size_t cur = B; cur > 1;) {
+        const size_t hf = (cur + 1) / 2;
+        launch_prod_level(src, dst, cur, hf, s);
+        src = dst; dst = dst == t0.as<i32>() ? t1.as<i32>() : t0.as<i32>();
+        cur = hf;
+    }
+    HIPCHK(hipGetLastError());
+    int bad = 0, sum_inf = 0, verdict = 0;
+    HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    // stage 3: sum r_i sig_i and its Miller loop on the side stream, the tail
+    SigSide ss;
+    {
+        HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+        OnStream on(st);
+        rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
+        if (rc) return rc;
+    }
+    rc = aggregate_tail(kind, src, ss, &verdict);                          // waits for the side stream; synchronises s
+    if (rc) return rc;
+    const bool held = verdict == 1 && bad == 0 && sum_inf == 0;
+    HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
+    size_t nre = 0;
+    std::vector<uint32_t> pos;
+    if (!held) {
+        // stages 4 and 5: S_b for every block, the B signature-side Miller values in the layout a Pairing call of B tuples takes, each times
+        // its block value, the final exponentiations in the layout a pairing product of B items takes, one byte per block
+        const int sig_group = k.sig_bytes == 192 ? 2 : 1;
+        SegPlan splan;
+        std::vector<uint8_t> fail;
+        try { segsum_plan(lp.tup_off.data(), B, segsum_chunk_of(n), splan, 64, 1); fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+        const size_t bload = route_load(B);
+        const Layout fe = pprod_fe_layout(B, bload);
+        DBuf sb, sbinf, g1, g2, bbad, fs, prod, vals, one, dfail;
+        HIPCHK(sb.alloc((size_t)k.sig_bytes * B)); HIPCHK(sbinf.alloc(B)); HIPCHK(g1.alloc((size_t)96 * B)); HIPCHK(g2.alloc((size_t)192 * B)); HIPCHK(bbad.alloc(B));
+        HIPCHK(fs.alloc(sizeof(i32) * words * B)); HIPCHK(prod.alloc(fe == Layout::wave ? 576 * B : sizeof(i32) * words * B)); HIPCHK(vals.alloc(576 * B));
+        HIPCHK(one.alloc(B)); HIPCHK(dfail.alloc(B));
+        rc = segsum_dev(sig_group, false, ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, dr.as<u64>());
+        if (rc) return rc;
+        prof_mark("k_locate_sig_pairs");
+        hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(B)), dim3(WG), 0, s, kind == 0 ? 0 : 1, (const u8*)sb.as<u8>(), (const u8*)sbinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
+                           g1.as<u8>(), g2.as<u8>(), bbad.as<u8>(), B);
+        launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), B, s, pairing_layout(0, B, t, bload));
+        prof_mark("k_fq12_mul_pairs_row");
+        hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(B)), dim3(WG), 0, s, (const i32*)bval.as<i32>(), (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
+                           fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, B);
+        final_exp_values(fe, prod.p, vals.as<u64>(), one.p, B, s);
+        prof_mark("k_locate_block_fail");
+        hipLaunchKernelGGL(k_locate_block_fail, dim3(rblocks(B)), dim3(WG), 0, s, (const u8*)flags.as<u8>(), (const u8*)sflags.as<u8>(), n, lp.block, (const u8*)bbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), B);
+        prof_mark(nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, B, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+        // stage 6: the tuples of the failing blocks, dense; verify_batch's pair stage routed by their count; the verdicts back
+        try { blsmi_route::locate_positions(lp, fail.data(), pos); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+        nre = pos.size();
+    }
+    if (nre) {
+        DBuf dpos, hd, pd, sd, id, okd, f;
+        HIPCHK(dpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hd.alloc((size_t)k.h_bytes * nre)); HIPCHK(pd.alloc((size_t)k.pk_bytes * nre)); HIPCHK(sd.alloc((size_t)k.sig_bytes * nre));
+        HIPCHK(id.alloc(nre)); HIPCHK(okd.alloc(nre)); HIPCHK(f.alloc(sizeof(i32) * words * nre));
+        HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+        auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) {
+            const u32 q = (u32)(bytes / 16);
+            hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)dpos.as<u32>(), to.as<uint4>(), q, nre);
+        };
+        prof_mark("k_gather_records16");
+        gather(h, hd, k.h_bytes); gather(dp, pd, k.pk_bytes); gather(ds, sd, k.sig_bytes);
+        if (inf_flags) hipLaunchKernelGGL(k_gather_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)di.as<u8>(), (const u32*)dpos.as<u32>(), id.as<u8>(), nre);
+        prof_mark(nullptr);
+        const VerifyRoute vr = verify_route(kind, nre, false, false, t, route_load(nre));
+        rc = verify_pair_stage(kind, hd.as<u8>(), pd.p, sd.p, inf_flags ? id.p : nullptr, okd.p, f.as<i32>(), nre, s, vr);
+        if (rc) return rc;
+        prof_mark("k_scatter_bytes");
+        hipLaunchKernelGGL(k_scatter_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)okd.as<u8>(), (const u32*)dpos.as<u32>(), dok.as<u8>(), nre);
+        prof_mark(nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, n);
+    if (combined) *combined = held ? 1 : 0;
+    if (rechecked) *rechecked = nre;
+    return BLSMI_OK;
+}
+#define JACP(p) reinterpret_cast<const uint8_t*>(p)
+}  // namespace
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(0, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(1, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                               const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                                   uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+#undef JACP

@@ -1325,3 +1325,78 @@ def pairing_product_batch_dev(d_g1, d_g2, np_, d_seg_off, m, d_out_fq12, d_is_on
         rc = _lib().blsmi_pairing_product_batch_dev(v(d_g1 or 0), v(d_g2 or 0), v(d_inf_flags or 0), C.c_size_t(np_), v(d_seg_off or 0), C.c_size_t(m),
                                                     v(d_out_fq12 or 0), v(d_is_one or 0), v(stream))
     _check(rc, "blsmi_pairing_product_batch_jac_dev" if jac else "blsmi_pairing_product_batch_dev")
+
+
+# ---- randomised batch verification that finds the bad tuples by blocks (blsmi 0.12) ---------------------------------------------------
+_L_TAIL = [_u64p, C.c_size_t, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]   # scalars, block, ok, ok_bitmap, n, combined, rechecked
+# the argument types of the six entry points of 0.12, as include/blsmi.h declares them (tests/test_rlc_locate_cpu.py compares)
+ARGTYPES_0_12 = {
+    "blsmi_g2pubs_verify_batch_rlc_locate": [_u8p, _u64p, _u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_locate": [_u8p, _u64p, _u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_locate": [_u8p, _u8p, _u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g2pubs_verify_batch_rlc_locate_jac": [_u8p, _u64p, _u64p, _u64p] + _L_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_locate_jac": [_u8p, _u64p, _u64p, _u64p] + _L_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac": [_u8p, _u8p, _u64p, _u64p] + _L_TAIL,
+}
+
+
+def _verify_batch_rlc_locate(name, kind, jac, msgs, pks, sigs, inf_flags, scalars, block, domain8=None):
+    """-> (ok, bitmap, combined, rechecked)"""
+    pkb, sgb = (192, 96) if kind == 0 else (96, 192)
+    n = len(msgs)
+    block = int(block)
+    if block < 0:
+        raise ValueError("block must not be negative")
+    if domain8 is None:
+        buf, off = _msgs(msgs)
+        head = (_p8(buf), off.ctypes.data_as(_u64p))
+    else:
+        buf = _u8(b"".join(bytes(m) for m in msgs) or b"\0" * 32, 32 * max(n, 1))
+        dom = _u8(domain8, 8)
+        head = (_p8(buf), _p8(dom))
+    if jac:
+        p, pp = _j64(pks, pkb // 2 * 3 * n)
+        s, ps = _j64(sigs, sgb // 2 * 3 * n)
+        mid = (pp, ps)
+    else:
+        p, s = _u8(pks, pkb * n), _u8(sigs, sgb * n)
+        f = _u8(inf_flags, n) if inf_flags is not None else None
+        mid = (_p8(p), _p8(s), _p8(f))
+    r, pr = _scalars(scalars, n)
+    ok = np.zeros(n, dtype=np.uint8)
+    bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+    comb = C.c_int(0)
+    rechecked = C.c_size_t(0)
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_12[name]
+    fn.restype = C.c_int
+    _check(fn(*head, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
+    return ok.astype(bool), bitmap, comb.value, rechecked.value
+
+
+def g2pubs_verify_batch_rlc_locate(msgs, pks, sigs, inf_flags=None, scalars=None, block=0):
+    """blsmi_g2pubs_verify_batch_rlc_locate -> (ok, bitmap, combined, rechecked): g2pubs_verify_batch_rlc's total check; when it fails, one
+    pairing equation per block of `block` tuples (0: automatic; else even, >= 2) and verify_batch's verdicts for the tuples of the failing
+    blocks only -- `rechecked` of them."""
+    return _verify_batch_rlc_locate("blsmi_g2pubs_verify_batch_rlc_locate", 0, False, msgs, pks, sigs, inf_flags, scalars, block)
+
+
+def g1pubs_verify_batch_rlc_locate(msgs, pks, sigs, inf_flags=None, scalars=None, block=0):
+    return _verify_batch_rlc_locate("blsmi_g1pubs_verify_batch_rlc_locate", 1, False, msgs, pks, sigs, inf_flags, scalars, block)
+
+
+def g1pubs_verify_with_domain_batch_rlc_locate(msgs32, domain8, pks, sigs, inf_flags=None, scalars=None, block=0):
+    return _verify_batch_rlc_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_locate", 2, False, msgs32, pks, sigs, inf_flags, scalars, block, domain8)
+
+
+def g2pubs_verify_batch_rlc_locate_jac(msgs, pks, sigs, scalars=None, block=0):
+    """the same over in-memory points (288 / 144 bytes each)"""
+    return _verify_batch_rlc_locate("blsmi_g2pubs_verify_batch_rlc_locate_jac", 0, True, msgs, pks, sigs, None, scalars, block)
+
+
+def g1pubs_verify_batch_rlc_locate_jac(msgs, pks, sigs, scalars=None, block=0):
+    return _verify_batch_rlc_locate("blsmi_g1pubs_verify_batch_rlc_locate_jac", 1, True, msgs, pks, sigs, None, scalars, block)
+
+
+def g1pubs_verify_with_domain_batch_rlc_locate_jac(msgs32, domain8, pks, sigs, scalars=None, block=0):
+    return _verify_batch_rlc_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac", 2, True, msgs32, pks, sigs, None, scalars, block, domain8)

@@ -151,6 +151,23 @@ def VerifyBatchRandomizedGrouped(msgs, msg_idx, pubs, sigs, scalars=None):
     return [bool(x) for x in ok]
 
 
+def VerifyBatchRandomizedLocate(msgs, pubs, sigs, scalars=None, block=0):
+    """VerifyBatchRandomized for input an adversary may have touched: when the combined check fails, one pairing equation per block of `block`
+    tuples (0: automatic; else even and at least 2) finds the blocks that hold, and only the tuples of the others go through the per-tuple
+    path -- a failed check costs the good path plus work proportional to the bad tuples' blocks.  Verdicts as VerifyBatch."""
+    n = len(msgs)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok = engine.g1pubs_verify_batch_rlc_locate_jac(msgs, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars, block)[0]
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok = engine.g1pubs_verify_batch_rlc_locate(msgs, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars, block)[0]
+    return [bool(x) for x in ok]
+
+
 def VerifySerializedBatch(msgs, pub_bytes, sig_bytes):
     """DeserializePublicKey + DeserializeSignature + Verify per tuple, in one device pass over the 48-byte keys and
     96-byte signatures of the wire format.  A tuple whose key or signature does not deserialise (the reference returns
@@ -216,6 +233,21 @@ def VerifyWithDomainBatchRandomizedGrouped(msgs32, msg_idx, pubs, sigs, domain8,
         return [bool(x) for x in ok]
     flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
     ok, _, _ = engine.g1pubs_verify_with_domain_batch_rlc_grouped(msgs32, domain8, msg_idx, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars)
+    return [bool(x) for x in ok]
+
+
+def VerifyWithDomainBatchRandomizedLocate(msgs32, pubs, sigs, domain8, scalars=None, block=0):
+    """VerifyWithDomainBatchRandomized that finds the bad tuples by blocks (VerifyBatchRandomizedLocate)"""
+    n = len(msgs32)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok = engine.g1pubs_verify_with_domain_batch_rlc_locate_jac(msgs32, domain8, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars, block)[0]
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok = engine.g1pubs_verify_with_domain_batch_rlc_locate(msgs32, domain8, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars, block)[0]
     return [bool(x) for x in ok]
 
 

@@ -78,8 +78,9 @@ void blsmi_shutdown(void);
  * no existing prototype changes.  0.10 adds the pairing products (blsmi_pairing_product_batch[_jac|_dev|_jac_dev]: many MillerLoop(items) + FinalExponentiation
  * checks in one call); no existing prototype changes, no new option.  0.11 adds the grouped randomised batch verification
  * (blsmi_g?pubs_*verify*_batch_rlc_grouped[_jac]: the tuples of one message share one pairing) and the weighted segmented sums
- * (blsmi_g?_sum_segmented_u64); no existing prototype changes, no new option.  The string below still begins "blsmi 0.10": a caller that
- * binds by hand tells 0.11 by the presence of those symbols. */
+ * (blsmi_g?_sum_segmented_u64); no existing prototype changes, no new option.  0.12 adds the randomised batch verification that
+ * finds the bad tuples by blocks (blsmi_g?pubs_*verify*_batch_rlc_locate[_jac]); no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11 and 0.12 by the presence of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -375,7 +376,7 @@ int blsmi_g1pubs_verify_aggregate_common_with_domain_jac(const uint8_t msg32[32]
  *   - combined check holds: ok[i] = 1 for every tuple, none checked on its own.  Every invalid tuple among them makes it hold with
  *     probability at most 2^-64 over the r_i.
  *   - it fails: the per-tuple verdicts of verify_batch, computed from the inputs already on the device (the failing call costs about a
- *     verify_batch on top of the combined check).  Bisection is not attempted.
+ *     verify_batch on top of the combined check).  Bisection is not attempted.  (blsmi 0.12: *_verify_batch_rlc_locate below rechecks by blocks.)
  *   - a key or signature at infinity (inf_flags, the all-zero record, or z = 0 in the in-memory forms) gets ok[i] = 0 as in verify_batch;
  *     any point at infinity on the combined path (an input, a scaled r_i H_i / r_i pk_i, the sum) sends the call (or its shard) to the
  *     per-tuple path.
@@ -444,6 +445,52 @@ int blsmi_g1pubs_verify_batch_rlc_grouped_jac(const uint8_t *msgs, const uint64_
                                               const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
 int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac(const uint8_t *msgs32, const uint8_t domain[8], size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*18 */,
                                                           const uint64_t *sigs /* n*36 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined);
+/* ---- randomised batch verification that finds the bad tuples by blocks (blsmi 0.12) ------------------------------------------
+ * *_verify_batch_rlc for input an adversary may have touched.  There one invalid tuple sends all n through the per-tuple path; here the
+ * batch is cut into contiguous blocks of `block` tuples (the last one may be shorter) and the call keeps every block's product of
+ * Miller values.  The total check is that of *_verify_batch_rlc.  When it fails, one pairing equation per block --
+ *     g2pubs: e(S_b, G2gen) == prod_{i in b} e(r_i H(m_i), pk_i)      g1pubs: e(G1gen, S_b) == prod_{i in b} e(r_i pk_i, H(m_i))      S_b = sum_{i in b} r_i sig_i
+ * -- decides which blocks hold, and the tuples of the blocks that fail, and only those, get the per-tuple verdicts of *_verify_batch.
+ * ok[i] = 1 for every tuple of a block whose equation held: its weights are its own tuples' r_i, so such a block is wrong with probability
+ * at most 2^-64, as the whole batch is above.  ok, ok_bitmap, inf_flags and scalars mean what they mean there, with the same soundness
+ * statement and precondition (caller scalars r_a == r_c let two tuples OF ONE BLOCK carry sig_a + D and sig_c - D unnoticed).
+ *   - block: 0 = automatic, the next even number >= max(64, ceil(n / 256)).  Any other value must be even and at least 2 (two consecutive
+ *     tuples share one Miller loop in the layouts of large calls, so a block border must be a border there too); block >= n gives one block.
+ *   - an odd block or block = 1, a zero caller scalar, and a NULL input with n > 0: BLSMI_E_ARG before any device work.  n = 0: BLSMI_OK,
+ *     combined = 0, rechecked = 0.
+ *   - combined (may be NULL): 1 exactly when the total check held (every verdict is 1 then); 0 otherwise and for n = 0.
+ *   - rechecked (may be NULL): the number of tuples whose verdict came from the per-tuple path -- 0 when the total check held, the sum of the
+ *     sizes of the failing blocks otherwise.
+ *   - a block fails, whatever its equation says, when one of its tuples is at infinity (inf_flags, the all-zero record, z = 0 in the in-memory
+ *     forms, a scaled r_i H_i / r_i pk_i) or its S_b is; with such a tuple anywhere, or sum r_i sig_i at infinity, the total's verdict is not
+ *     consulted and the block checks run.
+ * "rlc_min" does NOT apply, the call runs on one device and never joins the request combiner, as the grouped form.  The hash points are
+ * always cleared of their cofactor here (from 65 536 messages g2pubs' *_verify_batch_rlc clears the product instead).
+ * When to call it (one MI355X, host buffers, ms, median of 10; profiles/r09_rlc_locate.log; rlc / batch = *_verify_batch_rlc at rlc_min = 0
+ * and *_verify_batch of the build before this form):
+ *     n, bad tuples          g2pubs locate / rlc / batch      g1pubs locate / rlc / batch
+ *     16 384, none               11.0 / 11.0 /  8.7                16.3 / 16.4 / 10.7
+ *     16 384, one                16.2 / 18.3 /  8.4                23.7 / 24.0 / 10.2
+ *     65 536, none               17.6 / 17.3 / 26.9                24.9 / 25.0 / 31.6
+ *     65 536, one                23.8 / 42.7 / 25.2                34.6 / 50.5 / 30.2
+ *     65 536, 16 in 16 blocks    25.0 / 42.6 / 25.2                36.2 / 50.4 / 30.1
+ * The call that holds costs what *_verify_batch_rlc costs (the differences are inside the run-to-run spread of 0.3 .. 0.7 ms, g2pubs at 65 536 with
+ * its cleared hash included).  A failing call costs the block checks on top -- about 6 ms (g2pubs) / 10 ms (g1pubs) at 65 536: the n 64-bit
+ * multiples of the block sums, 256 Miller loops and final exponentiations -- plus the failing blocks' tuples: call it wherever *_verify_batch_rlc pays and the input is not trusted.  Below
+ * some tens of thousands of tuples *_verify_batch is the faster call, as for *_verify_batch_rlc. */
+int blsmi_g2pubs_verify_batch_rlc_locate(const uint8_t *msgs, const uint64_t *off, const uint8_t *pks /* n*192 */, const uint8_t *sigs /* n*96 */, const uint8_t *inf_flags,
+                                         const uint64_t *scalars /* n, may be NULL */, size_t block, uint8_t *ok /* n, may be NULL */, uint8_t *ok_bitmap /* may be NULL */, size_t n,
+                                         int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_batch_rlc_locate(const uint8_t *msgs, const uint64_t *off, const uint8_t *pks /* n*96 */, const uint8_t *sigs /* n*192 */, const uint8_t *inf_flags,
+                                         const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_locate(const uint8_t *msgs32, const uint8_t domain[8], const uint8_t *pks, const uint8_t *sigs, const uint8_t *inf_flags,
+                                                     const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g2pubs_verify_batch_rlc_locate_jac(const uint8_t *msgs, const uint64_t *off, const uint64_t *pks /* n*36 */, const uint64_t *sigs /* n*18 */,
+                                             const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_batch_rlc_locate_jac(const uint8_t *msgs, const uint64_t *off, const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
+                                             const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
+                                                         const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
 /* device-pointer forms (every buffer on ONE of the library's devices; `stream` as in blsmi_pairing_batch_dev): the points resident in HBM as the
  * Go side holds them.  d_ok: n verdict bytes on the device. */
 int blsmi_pairing_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, void *d_out_fq12, size_t n, void *stream);

@@ -142,6 +142,28 @@ func VerifyBatchRandomized(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) 
 	return out
 }
 
+// VerifyBatchRandomizedLocate is VerifyBatchRandomized for input an adversary may have touched (INTEGRATION.md 2j): when the combined
+// check fails, one pairing equation per block of `block` tuples (0: the library chooses; else even and at least 2) finds the blocks that
+// hold, and only the tuples of the others go through the per-tuple path.  Verdicts as VerifyBatch; an odd block panics, as every
+// library error does.
+func VerifyBatchRandomizedLocate(msgs [][]byte, pubs []*PublicKey, sigs []*Signature, block int) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_batch_rlc_locate_jac(u8(m), &off[0], u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil),
+		"g1pubs_verify_batch_rlc_locate_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // VerifyBatchRandomizedGrouped is VerifyBatchRandomized for tuples that share messages (an attestation subnet, a slot, a sync
 // committee): msgs is a table of d messages and tuple i is (msgs[msgIdx[i]], pubs[i], sigs[i]).  The tuples of one message share one
 // pairing of the combined check -- d hashes and Miller loops instead of n (INTEGRATION.md 2g) -- and the verdicts are those of
@@ -204,6 +226,24 @@ func VerifyWithDomainBatchRandomized(msgs [][32]byte, pubs []*PublicKey, sigs []
 	ok := make([]byte, n)
 	must(C.blsmi_g1pubs_verify_with_domain_batch_rlc_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
 		u64(pk), u64(sg), nil, u8(ok), nil, C.size_t(n), nil), "g1pubs_verify_with_domain_batch_rlc_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// VerifyWithDomainBatchRandomizedLocate is VerifyWithDomainBatchRandomized that finds the bad tuples by blocks (VerifyBatchRandomizedLocate).
+func VerifyWithDomainBatchRandomizedLocate(msgs [][32]byte, pubs []*PublicKey, sigs []*Signature, domain [8]byte, block int) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
+		u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil), "g1pubs_verify_with_domain_batch_rlc_locate_jac")
 	for i := range ok {
 		out[i] = ok[i] != 0
 	}
