@@ -431,7 +431,9 @@ BLSMI_DEV FpS fp_pow_const(const Fp<L, V>& a, const u32* ebits, int nbits) {
 // 27 bits of (f, g) with 27 branch-free divsteps, then applies it to (f, g) (exact division by 2^27) and to (d, e)
 // (division mod q).  34 batches of 27 divsteps = 918 cover the bound of 878 divsteps for a 381-bit modulus
 // (floor((45907 * 381 + 26313) / 19929), the half-delta variant started at delta = 1/2); control flow and
-// instruction stream are the same for every lane (~21 k instructions).  inverse(0) = 0, as the power gave.
+// instruction stream are the same for every lane (38 k executed instructions with 14 x 28-bit limbs -- 33 batches of 1 156 as compiled, counted
+// in the unit's assembly and confirmed by SQ_INSTS_VALU; an earlier estimate here said ~21 k).  inverse(0) = 0, as the power gave.
+// (The lane-pair layer splits the iteration over the two lanes of a pair: fp2_pair.inc, fp_inv_pair_core.)
 // Input: any representative; output: the Montgomery form of the inverse of the value the input stands for.
 BLSMI_DEV FpS fp_inv_fermat(const FpS& a) { return fp_pow_const(a, C_QM2, BLSMI_QM2_BITS); }
 __device__ __noinline__ vlimbs fp_inv_core(vlimbs a_canon) {

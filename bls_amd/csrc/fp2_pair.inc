@@ -23,6 +23,7 @@ BLSMI_DEV i32 bfi(i32 mask, i32 a, i32 b) {                                     
 }
 BLSMI_DEV i32 dpp_swap(i32 x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true); }    // quad_perm [1,0,3,2]; every lane has a source lane, so no "old" value is kept (one v_mov_b32_dpp, no copy)
 BLSMI_DEV i32 dpp_even(i32 x) { return __builtin_amdgcn_update_dpp(0, x, 0xA0, 0xf, 0xf, true); }    // quad_perm [0,0,2,2]: the pair's even lane (c0) on both lanes
+BLSMI_DEV i32 dpp_odd(i32 x) { return __builtin_amdgcn_update_dpp(0, x, 0xF5, 0xf, 0xf, true); }     // quad_perm [1,1,3,3]: the pair's odd lane (c1) on both lanes
 template <int L, int V> BLSMI_DEV Fp<L, V> fp_partner(const Fp<L, V>& a) {
     Fp<L, V> r;
 #pragma unroll
@@ -214,11 +215,89 @@ BLSMI_DEV auto fp2_sqr(const Fp2<L, V>& a) {
 }
 template <int La, int Va, int Lb, int Vb>
 BLSMI_DEV auto fp2_mul_fp(const Fp2<La, Va>& a, const Fp<Lb, Vb>& s) { return wrap(fp_mul(a.c, s)); }
-// fq2.go:133-147: 1/(c0^2 + c1^2) is computed by both lanes
+// The Fq inverse of a value BOTH lanes of a pair hold (the norm of fp2_inv): fp_inv_core's safegcd (fp.cuh) with its work split over the two
+// lanes, one instruction stream.  The state of the iteration is two independent halves and its transition matrix two independent columns:
+//   divsteps     both lanes step (fl, gl, zeta) -- the control masks must agree -- but each carries ONE column of the matrix,
+//                the even lane (u, q), the odd lane (v, r); the partner's column arrives by DPP after the batch
+//   application  the even lane owns (f, g), the odd lane (d, e); both run the (d, e) form A' = (m0 A + m1 B + mA q) / 2^LB, with the
+//                multiple of q forced to zero on even lanes, where the division is exact by construction
+// The odd lane reads the low limbs of f and g from the even lane before every batch (LB divsteps look at LB bits: limb 0 holds them all);
+// at the end sign(f) comes from the even lane and d from the odd one.  Every limb is computed by the same expression as in
+// fp_inv_core, so the result is the same limb for limb: inverse(0) = 0 included (f stays q, d stays 0).
+// Per inversion 38.1 k -> 23.4 k executed instructions (33 batches of 1 156 -> 710 as compiled).  -DBLSMI_INV_PAIR_SPLIT=0: both lanes run fp_inv_core
+// on the same number (A/B).  Measured, parent and change interleaved five times on one MI355X, 65 536 pairings (profiles/r10_inv_pair_split.log):
+// k_final_exp_pair 9.782 -> 9.348 ms (-4.4 %; run-to-run s.d. 0.046), SQ_INSTS_VALU 5.294 G -> 4.963 G wave-instructions per launch (-162 k per
+// wave, eleven inversions), k_miller1h_pair 8.31 -> 8.34 ms (unchanged within its spread), the step 18.12 -> 17.72 ms.  DESIGN 3 (v').
+#ifndef BLSMI_INV_PAIR_SPLIT
+#define BLSMI_INV_PAIR_SPLIT 1
+#endif
+__device__ __noinline__ vlimbs fp_inv_pair_core(vlimbs a_canon) {
+    const i32 odd = lane_odd();
+    i32 A[NL], B[NL];                                                      // even lane: (f, g) = (q, a)      odd lane: (d, e) = (0, 1)
+#pragma unroll
+    for (int i = 0; i < NL; i++) { A[i] = C_Q[i] & ~odd; B[i] = a_canon[i] & ~odd; }
+    B[0] |= odd & 1;
+    i32 zeta = -1;
+    for (int it = 0; it < (878 + LB - 1) / LB + 1; it++) {
+        u32 fl = (u32)dpp_even(A[0]), gl = (u32)dpp_even(B[0]);
+        u32 t = (u32)(~odd & 1), b = (u32)(odd & 1);                       // my column of the matrix, (top, bottom): (u, q) = (1, 0) or (v, r) = (0, 1)
+#pragma unroll
+        for (int i = 0; i < LB; i++) {
+            u32 c1 = (u32)(zeta >> 31);
+            const u32 c2 = 0u - (gl & 1u);
+            const u32 x = (fl ^ c1) - c1, y = (t ^ c1) - c1;
+            gl += x & c2; b += y & c2;
+            c1 &= c2;
+            zeta = (i32)((u32)zeta ^ c1) - 1;
+            fl += gl & c1; t += b & c1;
+            gl >>= 1; t <<= 1;
+        }
+        const i32 pt = dpp_swap((i32)t), pb = dpp_swap((i32)b);
+        const i32 mu = bfi(odd, pt, (i32)t), mv = bfi(odd, (i32)t, pt), mq = bfi(odd, pb, (i32)b), mr = bfi(odd, (i32)b, pb);
+        const i32 sa = A[NL - 1] >> 31, sb = B[NL - 1] >> 31;
+        i32 ma = (mu & sa) + (mv & sb), mb = (mq & sa) + (mr & sb);
+        i64 ca = (i64)mu * A[0] + (i64)mv * B[0], cb = (i64)mq * A[0] + (i64)mr * B[0];
+        ma -= (i32)((BLSMI_QINV_POS * (u32)ca + (u32)ma) & (u32)MASK);
+        mb -= (i32)((BLSMI_QINV_POS * (u32)cb + (u32)mb) & (u32)MASK);
+        ma &= odd; mb &= odd;                                              // (f, g): no multiple of q, the low limb cancels by itself
+        ca += (i64)C_Q[0] * ma; cb += (i64)C_Q[0] * mb;
+        ca >>= LB; cb >>= LB;
+#pragma unroll
+        for (int i = 1; i < NL; i++) {
+            ca += (i64)mu * A[i] + (i64)mv * B[i] + (i64)C_Q[i] * ma;
+            cb += (i64)mq * A[i] + (i64)mr * B[i] + (i64)C_Q[i] * mb;
+            A[i - 1] = (i32)ca & MASK; ca >>= LB;
+            B[i - 1] = (i32)cb & MASK; cb >>= LB;
+        }
+        A[NL - 1] = (i32)ca; B[NL - 1] = (i32)cb;
+    }
+    const i32 sf = dpp_even(A[NL - 1] >> 31);                              // sign(f) * d, as fp_inv_core
+    vlimbs out;
+#pragma unroll
+    for (int i = 0; i < NL; i++) out[i] = (dpp_odd(A[i]) ^ sf) - sf;
+    return out;
+}
+template <int L, int V>
+BLSMI_DEV FpS fp_inv_pair(const Fp<L, V>& a) {                             // fp_inv (fp.cuh) around the lane-pair core
+    const FpC c = fp_canon(a);
+    vlimbs x;
+#pragma unroll
+    for (int i = 0; i < NL; i++) x[i] = c.v[i];
+    const vlimbs z = fp_inv_pair_core(x);
+    Fp<2, 3 * VU> r;
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.v[i] = z[i];
+    return fp_store(fp_mul(fp_relabel<1, 3 * VU>(fp_norm(r)), C_R3));
+}
+// fq2.go:133-147: 1/(c0^2 + c1^2), the same number on both lanes
 template <int L, int V>
 BLSMI_DEV auto fp2_inv(const Fp2<L, V>& a) {
     const auto n = fp_sqr(a.c);
+#if BLSMI_INV_PAIR_SPLIT
+    const FpS t = fp_inv_pair(fp_add(n, fp_partner(n)));
+#else
     const FpS t = fp_inv(fp_add(n, fp_partner(n)));
+#endif
     return wrap(fp_cneg(lane_odd(), fp_mul(a.c, t)));
 }
 template <int P, int L, int V>

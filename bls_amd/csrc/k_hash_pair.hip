@@ -18,7 +18,6 @@ namespace P2 = blsmi::pairl;
 
 namespace blsmi {
 namespace pairl {
-BLSMI_DEV i32 dpp_odd(i32 x) { return __builtin_amdgcn_update_dpp(0, x, 0xF5, 0xf, 0xf, true); }     // quad_perm [1,1,3,3]: the pair's odd lane on both lanes
 BLSMI_DEV FpS fp_of_even(const FpS& a) { FpS r; for (int i = 0; i < NL; i++) r.v[i] = dpp_even(a.v[i]); return r; }
 BLSMI_DEV FpS fp_of_odd(const FpS& a) { FpS r; for (int i = 0; i < NL; i++) r.v[i] = dpp_odd(a.v[i]); return r; }
 BLSMI_DEV FpS fp2_norm_fq(const Fp2S& a) {                                  // c0^2 + c1^2 on both lanes
