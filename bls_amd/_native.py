@@ -68,7 +68,7 @@ def _stale():
         return True
     if not os.path.isdir(BUILD_DIR):                      # a shipped .so without its objects (the GPU box): trust mtimes of the sources
         t = os.path.getmtime(SO_PATH)
-        srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cuh", ".inc", ".h"))] + [HEADER]
+        srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cuh", ".inc", ".h", ".hpp"))] + [HEADER]
         return any(os.path.getmtime(x) > t for x in srcs)
     t = os.path.getmtime(SO_PATH)
     return any(_unit_stale(u) or os.path.getmtime(os.path.join(BUILD_DIR, u + ".o")) > t for u in _UNITS)

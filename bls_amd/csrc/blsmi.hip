@@ -1,6 +1,6 @@
 // blsmi.hip -- host side and C ABI (include/blsmi.h) of libblsmi.so.  The kernels live in their own translation units
 // (k_pairing_pair.hip: the default lane-pair pairing kernels; k_pairing_single.hip; k_hash.hip; k_curve.hip), declared in
-// kernels.h; the verify-path host code is in verify_host.inc.
+// kernels.h; the verify-path host code is in verify_host.inc, that of the randomised batch verifications in rlc_host.hpp.
 #include "../../include/blsmi.h"
 #include "kernels.h"
 #include "lat_programs.h"
@@ -1259,7 +1259,7 @@ struct MsmKernels {
     void (*final)(const i32*, int, int, u8*, i32*);
 };
 template <int PB, int W>
-// nbits: the scalars' width -- 256, or 64 for the randomised batch verification's scalars (verify_host.inc: rlc_sig_sum), whose
+// nbits: the scalars' width -- 256, or 64 for the randomised batch verification's scalars (rlc_host.hpp: rlc_sig_sum), whose
 // 32-byte records are zero above bit 64: four windows instead of sixteen, the Horner tail 48 doublings instead of 240
 static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s, int nbits = 256) {
     // 16-bit windows: n / 2^16 points per bucket, and a 255-bit scalar still fills 15 bits of the top window (a window
@@ -1551,5 +1551,6 @@ BLSMI_API int blsmi_g2_msm_dev_ex(const void* d_pts, const void* d_scalars, size
 }
 
 #include "verify_host.inc"
+#include "rlc_host.hpp"
 
 

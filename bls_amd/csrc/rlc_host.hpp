@@ -1,0 +1,602 @@
+// rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped and
+// ..._rlc_locate.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The three
+// forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
+// Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
+// source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
+namespace {
+// ---- randomised batch verification (blsmi 0.8: blsmi_g?pubs_verify_batch_rlc) ------------------------------------------------------
+// Small-exponent batch verification (Bellare, Garay, Rabin 1998): with random nonzero 64-bit r_i, ONE equation stands for the n of a batch --
+//     g2pubs: e(sum r_i sig_i, G2gen) == prod e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, sum r_i sig_i) == prod e(r_i pk_i, H(m_i))
+// It holds when every tuple is valid; with an invalid tuple among them it holds with probability at most 2^-64 over the r_i (keys and
+// signatures in the prime-order subgroups, as Deserialize guarantees).  n Miller loops, the product tree and ONE final exponentiation (the
+// VerifyAggregate machinery), plus a 64-bit multiplication per tuple (k_g1_mul_u64: r_i H_i for g2pubs, r_i pk_i for g1pubs -- both in G1)
+// and a 64-bit MSM over the signatures, which runs on the side stream beside the hash.  When the check fails, or a point at infinity
+// meets it, the shard computes the per-tuple verdicts of verify_batch from the buffers already on the device.
+//
+// The scalars: nonzero 64-bit words from the OS (getrandom, /dev/urandom), fresh for every call; no state is kept between calls.
+int rlc_draw_scalars(uint64_t* r, size_t n) {
+    uint8_t* p = reinterpret_cast<uint8_t*>(r);
+    size_t want = 8 * n, got = 0;
+#ifdef SYS_getrandom
+    while (got < want) {
+        const long k = syscall(SYS_getrandom, p + got, std::min(want - got, (size_t)1 << 20), 0);
+        if (k > 0) got += (size_t)k;
+        else if (k < 0 && errno == EINTR) continue;
+        else break;
+    }
+#endif
+    if (got < want) {
+        const int fd = open("/dev/urandom", O_RDONLY | O_CLOEXEC);
+        if (fd < 0) return BLSMI_E_RNG;
+        while (got < want) {
+            const ssize_t k = read(fd, p + got, want - got);
+            if (k > 0) got += (size_t)k;
+            else if (k < 0 && errno == EINTR) continue;
+            else break;
+        }
+        close(fd);
+        if (got < want) return BLSMI_E_RNG;
+    }
+    for (size_t i = 0; i < n; i++)                                         // a zero word (probability 2^-64 each) is drawn again
+        while (r[i] == 0) { int rc = rlc_draw_scalars(&r[i], 1); if (rc) return rc; }
+    return BLSMI_OK;
+}
+// The signature side's sum, sum_i r_i sig_i over the n signatures on the device (any curve points): affine at d_sum, infinity flag (int32)
+// at d_flag, on g_stream.  From RLC_MSM_BUCKET_MIN signatures the bucket method of msm_bucket_dev over the scalars' 64 bits (four
+// 16-bit windows); below, or when the digits are skewed (a caller's scalars), per-signature 64-bit ladders and the tree sum.
+constexpr size_t RLC_MSM_BUCKET_MIN = 8192;
+int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum, i32* d_flag) {
+    hipStream_t s = g_stream;
+    if (n >= RLC_MSM_BUCKET_MIN) {
+        DBuf sc; HIPCHK(sc.alloc((size_t)32 * n));
+        hipLaunchKernelGGL(k_scalar_u64_to_be32, dim3(nblocks(n)), dim3(WG), 0, s, d_r, sc.as<u8>(), n);
+        const int rc = kind == 0 ? msm_bucket_dev<96, 3>(g_mk1, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64)
+                                 : msm_bucket_dev<192, 6>(g_mk2, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
+        if (rc != BLSMI_E_SKEW) return rc;
+    }
+    const size_t pb = kind == 0 ? 96 : 192;
+    DBuf m, inf; HIPCHK(m.alloc(pb * n)); HIPCHK(inf.alloc(n));
+    prof_mark(kind == 0 ? "k_g1_mul_u64" : "k_g2_mul_u64");
+    if (kind == 0) hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
+    else hipLaunchKernelGGL(k_g2_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
+                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
+}
+// sig_side_start for a signature already on the device (the sum above, read in place): MillerLoop(-sig, G2gen) / MillerLoop(-G1gen, sig)
+// into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
+int sig_side_start_dev(int kind, const u8* d_sig, SigSide& ss) {
+    HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
+    const u8* tp = kind == 0 ? d_sig : g_gens.g1;
+    const u8* tq = kind == 0 ? g_gens.g2 : d_sig;
+    prof_mark("k_lat:miller1rawn");
+    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
+                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
+                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(ss.ml.p), (size_t)1);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(tl_ctx->join[0], g_stream));
+    return BLSMI_OK;
+}
+// the context's stream pointed at another of its streams for a stretch of one call (the kernels and their profile marks go there)
+struct OnStream { hipStream_t saved; explicit OnStream(hipStream_t s) : saved(tl_ctx->stream) { tl_ctx->stream = s; } ~OnStream() { tl_ctx->stream = saved; } };
+
+// ---- the stages the three forms share ---------------------------------------------------------------------------------------------------
+// The arguments every form checks alike; its own checks that end in BLSMI_E_ARG for a call of n > 0 tuples arrive folded into inputs_ok.
+int rlc_check_args(bool inputs_ok, const uint64_t* scalars, size_t n) {
+    if (n && !inputs_ok) return BLSMI_E_ARG;
+    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
+    return BLSMI_OK;
+}
+// The host memory a call may need: the scalars where the caller gave none (drawn here: `scalars` then points at them), and the n verdict
+// bytes of a caller who wants the bitmap alone (want_ok: `ok` then points at them).
+struct RlcHostScratch { std::vector<uint64_t> drawn; std::vector<uint8_t> tmp; };
+int rlc_scalars_and_ok(RlcHostScratch& hs, const uint64_t*& scalars, uint8_t*& ok, bool want_ok, size_t n) {
+    try {
+        if (!scalars) hs.drawn.resize(n);
+        if (want_ok) hs.tmp.resize(n);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    if (want_ok) ok = hs.tmp.data();
+    if (!scalars) { int rc = rlc_draw_scalars(hs.drawn.data(), n); if (rc) return rc; scalars = hs.drawn.data(); }
+    return BLSMI_OK;
+}
+// What one combined check keeps for the length of its call.  On the device: the inputs, the verdict bytes, the inputs' flag bytes, the word
+// `any` that every flagging kernel ORs into, the signatures' sum and its infinity flag.  On the host: the signature side's Miller value and
+// the three words the check ends in -- targets of asynchronous copies, so the struct stays where it is until the call has synchronised.
+// A buffer that a later stage reads belongs here or in the driver's frame, never in a stage's.
+struct RlcCall {
+    int kind = 0;
+    Kind k{};
+    size_t n = 0, msg_bytes = 0, off_bytes = 0;
+    bool has_inf = false;                                                  // the caller passed infinity flags (rlc_upload_keys)
+    DBuf dm, doff, dp, ds, di, dr, dok, flags, any, sum, sflag;
+    SigSide ss;
+    int bad = 0, sum_inf = 0, verdict = 0;
+    const void* inf() const { return has_inf ? di.p : nullptr; }
+    // the equation holds, nothing is flagged, the signatures' sum is a finite point: every verdict is 1
+    bool held() const { return verdict == 1 && bad == 0 && sum_inf == 0; }
+};
+// the context's side streams, and the buffers for n tuples whose messages / offsets take msg_bytes / off_bytes on the device
+int rlc_begin(RlcCall& c, int kind, size_t n, size_t msg_bytes, size_t off_bytes) {
+    c.kind = kind; c.k = kind_of(kind); c.n = n; c.msg_bytes = msg_bytes; c.off_bytes = off_bytes;
+    HIPCHK(tl_ctx->ensure_aux());
+    HIPCHK(c.dm.alloc(msg_bytes)); HIPCHK(c.doff.alloc(off_bytes)); HIPCHK(c.dp.alloc((size_t)c.k.pk_bytes * n)); HIPCHK(c.ds.alloc((size_t)c.k.sig_bytes * n));
+    HIPCHK(c.di.alloc(n)); HIPCHK(c.dr.alloc(sizeof(uint64_t) * n)); HIPCHK(c.dok.alloc(n)); HIPCHK(c.flags.alloc(n)); HIPCHK(c.any.alloc(sizeof(int)));
+    HIPCHK(c.sum.alloc(c.k.sig_bytes)); HIPCHK(c.sflag.alloc(sizeof(i32)));
+    return BLSMI_OK;
+}
+// The uploads a call starts with.  The signatures go first, on the side stream aux[0] (pageable copies block the host: the hash is queued
+// behind the first of them only), and join[1] marks their arrival.  The scalars r, the messages and their offsets (or the domain) follow on the
+// main stream, where `fork` says that the scalars are there: the side stream's sum may start.
+int rlc_upload_start(RlcCall& c, const uint8_t* sigs, const uint64_t* r, const void* msgs, const void* off_or_domain, int fmt) {
+    hipStream_t s = g_stream, st = tl_ctx->aux[0];
+    { int rc = upload_points(c.k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, c.ds.p, c.n, st); if (rc) return rc; }
+    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
+    HIPCHK(hipMemcpyAsync(c.dr.p, r, sizeof(uint64_t) * c.n, hipMemcpyHostToDevice, s));
+    if (c.msg_bytes) HIPCHK(hipMemcpyAsync(c.dm.p, msgs, c.msg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c.doff.p, off_or_domain, c.off_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));
+    return BLSMI_OK;
+}
+// Right after the form's hash_dev: the keys and the infinity flags travel while the messages are hashed; the main stream then waits for the signatures.
+int rlc_upload_keys(RlcCall& c, const uint8_t* pks, const uint8_t* inf_flags, int fmt) {
+    hipStream_t s = g_stream;
+    int rc = upload_points(c.k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, c.dp.p, c.n, s);
+    if (rc) return rc;
+    c.has_inf = inf_flags != nullptr;
+    if (inf_flags) HIPCHK(hipMemcpyAsync(c.di.p, inf_flags, c.n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
+    return BLSMI_OK;
+}
+// a key or a signature that is the all-zero record, or flagged by the caller: a byte per tuple into c.flags, and `any`
+void rlc_flag_inputs(RlcCall& c) {
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(c.n)), dim3(WG), 0, g_stream, (const u8*)c.dp.as<u8>(), c.k.pk_bytes / 4, (const u8*)c.ds.as<u8>(), c.k.sig_bytes / 4,
+                       (const u8*)c.inf(), c.flags.as<u8>(), c.any.as<int>(), c.n);
+}
+// r_i times the G1 point of tuple i -- src: the hash points (g2pubs; they stay for the fallback) or the keys (g1pubs) -- into `scaled`.  A scaled
+// point at infinity is flagged like an input: into flag_bytes (c.flags, or bytes of the form's own where the inputs' flags must stay), and `any`.
+void rlc_scale_g1(RlcCall& c, const u8* src, u8* scaled, u8* sinf, u8* flag_bytes) {
+    hipStream_t s = g_stream;
+    prof_mark("k_g1_mul_u64");
+    hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(c.n)), dim3(WG), 0, s, src, (const u64*)c.dr.as<u64>(), scaled, sinf, c.n);
+    prof_mark(nullptr);
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(c.n)), dim3(WG), 0, s, (const u8*)scaled, 24, (const u8*)nullptr, 0, (const u8*)sinf, flag_bytes, c.any.as<int>(), c.n);
+}
+// sum r_i sig_i and its Miller loop on the side stream, beside the tuple side: the kernels and their profile marks go where the context's
+// stream points (OnStream); join[0] marks the end (sig_side_start_dev)
+int rlc_signature_side(RlcCall& c) {
+    hipStream_t st = tl_ctx->aux[0];
+    HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+    OnStream on(st);
+    int rc = rlc_sig_sum(c.kind, c.ds.as<u8>(), c.dr.as<u64>(), c.n, c.sum.as<u8>(), c.sflag.as<i32>()); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
+}
+// The end of a combined check, d_prod being the tuple side's product: `any` comes back, the signature side starts (sig_side == false: it
+// has, in an earlier attempt of this call), aggregate_tail waits for the side stream and synchronises the main one.  Then c.held() is valid.
+int rlc_check_total(RlcCall& c, const i32* d_prod, bool sig_side = true) {
+    HIPCHK(hipMemcpyAsync(&c.bad, c.any.p, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    if (sig_side) { int rc = rlc_signature_side(c); if (rc) return rc; }
+    return aggregate_tail(c.kind, d_prod, c.ss, &c.verdict);
+}
+// the per-tuple verdicts of verify_batch for all n tuples, from the inputs on the device and their hash points d_h
+int rlc_fallback_all(RlcCall& c, const u8* d_h, const VerifyRoute& vr) {
+    DBuf f; HIPCHK(f.alloc(sizeof(i32) * 12 * NL * c.n));
+    return verify_pair_stage(c.kind, d_h, c.dp.p, c.ds.p, c.inf(), c.dok.p, f.as<i32>(), c.n, g_stream, vr);
+}
+// the verdict bytes back (ok may be null), the end of the call's device work, the bitmap and *combined for the callers that ask
+int rlc_finish(RlcCall& c, uint8_t* ok, uint8_t* ok_bitmap, int* combined) {
+    if (ok) HIPCHK(hipMemcpyAsync(ok, c.dok.p, c.n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, c.n);
+    if (combined) *combined = c.held() ? 1 : 0;
+    return BLSMI_OK;
+}
+
+// One shard on the leased context (tune(): the call's snapshot).  ok: n verdict bytes (host, may be null); d_bitmap_slice as in
+// verify_batch_leased; *held = true when the combined check held and every verdict is 1.  r: n nonzero scalars (host).
+// Its own: from AGG_POW_MIN g2pubs tuples the hash points stay uncleared and the product is raised to 1 - x (agg_pow_wanted); a message
+// that route does not cover sends the tuple side round once more with the cleared points, over the inputs and the signature side that are there.
+int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+              const uint64_t* r, uint8_t* ok, size_t n, int fmt, bool* held, u8* d_bitmap_slice = nullptr) {
+    *held = false;
+    if (n == 0) return BLSMI_OK;
+    const Tuning& t = tune();
+    const size_t load = route_load(n);
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    RlcCall c;
+    int rc = rlc_begin(c, kind, n, kind == 2 ? 32 * n : (size_t)off_or_domain[n], kind == 2 ? 8 : sizeof(uint64_t) * (n + 1)); if (rc) return rc;
+    DBuf h, scaled, sinf, fr0, fr1, pc;
+    HIPCHK(h.alloc((size_t)c.k.h_bytes * n)); HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n));
+    rc = rlc_upload_start(c, sigs, r, msgs, off_or_domain, fmt); if (rc) return rc;
+    bool powc = agg_pow_wanted(kind, n, t);                                // g2pubs from AGG_POW_MIN: uncleared hash points, the product raised to 1 - x
+    bool first = true, cleared = !powc;
+    // the tuple side: hash, scale, Miller loops, product tree (+ the cofactor power); then the signature side on the side stream; then the tail
+    auto combined_check = [&]() -> int {
+        const AggregateRoute ar = aggregate_route(kind, n, false, !powc, t, load);
+        HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
+        HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
+        int rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, ar.hash, !powc, powc ? c.any.as<int>() : nullptr);   // bad bit 1: a hash point the uncleared path does not cover
+        if (rc) return rc;
+        cleared = !powc;
+        if (first) { rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc; }
+        rlc_flag_inputs(c);
+        rlc_scale_g1(c, kind == 0 ? h.as<u8>() : c.dp.as<u8>(), scaled.as<u8>(), sinf.as<u8>(), c.flags.as<u8>());
+        launch_miller1(scaled.as<u8>(), kind == 0 ? c.dp.as<u8>() : h.as<u8>(), fr0.as<i32>(), n, s, ar, nullptr);
+        const i32* prod = prod_tree(fr0.as<i32>(), ar.records, fr1.as<i32>(), fr0.as<i32>(), s);
+        HIPCHK(hipGetLastError());
+        if (powc) { HIPCHK(pc.alloc(sizeof(i32) * words)); rc = aggregate_pow_c(prod, pc.as<i32>()); if (rc) return rc; prod = pc.as<i32>(); }
+        const bool sig_side = first;
+        first = false;
+        return rlc_check_total(c, prod, sig_side);
+    };
+    rc = combined_check();
+    if (rc) return rc;
+    if (!(c.bad & 1) && (c.bad & 2)) { powc = false; rc = combined_check(); if (rc) return rc; }   // an uncovered hash point: once more with the cleared points
+    *held = c.held();
+    if (*held) HIPCHK(hipMemsetAsync(c.dok.p, 1, n, s));
+    else {
+        // the per-tuple verdicts of verify_batch, from the inputs on the device (the hash again where h holds uncleared points)
+        const VerifyRoute vr = verify_route(kind, n, false, false, t, load);
+        if (!cleared) { rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
+        rc = rlc_fallback_all(c, h.as<u8>(), vr); if (rc) return rc;
+    }
+    if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, s, (const u8*)c.dok.as<u8>(), d_bitmap_slice, n);   // (a split call: the bitmap comes together on the devices)
+    return rlc_finish(c, ok, nullptr, nullptr);
+}
+// The host entry points.  scalars (may be null: drawn here) are checked for zeros first; below the call's rlc_min the per-tuple path runs
+// directly.  A split call (plan_shards) runs one combined check per shard, each with its own fallback; the bitmap comes together as in
+// verify_batch_direct.  *combined (may be null) = 1 when every verdict came from a combined check that held.
+int verify_batch_rlc_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                          const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    int rc = rlc_check_args(msgs && off_or_domain && pks && sigs, scalars, n);
+    if (rc || n == 0) return rc;
+    { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
+    const Tuning t = tuning_now();                                         // the call's options, once: every shard routes by this snapshot
+    if (n < t.rlc_min) return verify_batch_direct(kind, msgs, off_or_domain, pks, sigs, inf_flags, ok, ok_bitmap, n, fmt);
+    const Kind k = kind_of(kind);
+    const ShardPlan plan = plan_shards(n, 64);
+    RlcHostScratch hs;
+    rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap && plan.nshards == 1, n);   // (a split call packs its bitmap on the devices)
+    if (rc) return rc;
+    std::unique_ptr<bool[]> held(new bool[plan.nshards]());
+    std::unique_lock<std::mutex> coll_lk(g_coll_mu, std::defer_lock);
+    const size_t bm = (n + 7) / 8;
+    if (plan.nshards > 1 && ok_bitmap) { coll_lk.lock(); int rc = coll_reserve_all(bm, true); if (rc) return rc; }
+    rc = run_shards(plan, [&](int sh, size_t lo, size_t hi) -> int {
+        tl_ctx->tune = t;
+        const size_t m = hi - lo;
+        std::vector<uint64_t> off_sub;
+        const uint8_t* mp; const uint64_t* op;
+        if (kind == 2) { mp = msgs + 32 * lo; op = off_or_domain; }
+        else {
+            off_sub.resize(m + 1);
+            for (size_t i = 0; i <= m; i++) off_sub[i] = off_or_domain[lo + i] - off_or_domain[lo];
+            mp = msgs + off_or_domain[lo]; op = off_sub.data();
+        }
+        u8* slice = (plan.nshards > 1 && ok_bitmap) ? reinterpret_cast<u8*>(tl_ctx->dev->coll.p) + lo / 8 : nullptr;
+        return rlc_shard(kind, mp, op, pks + rec_bytes(k.pk_bytes, fmt & FMT_PK_JAC) * lo, sigs + rec_bytes(k.sig_bytes, fmt & FMT_SIG_JAC) * lo,
+                         inf_flags ? inf_flags + lo : nullptr, scalars + lo, ok ? ok + lo : nullptr, m, fmt, &held[sh], slice);
+    });
+    if (rc) return rc;
+    if (ok_bitmap) {
+        if (plan.nshards == 1) pack_bitmap(ok, ok_bitmap, n);
+        else {
+            rc = allreduce_bitmap(bm);
+            if (rc) return rc;
+            HIPCHK(hipSetDevice(g_dev[0].id));
+            HIPCHK(hipMemcpyAsync(ok_bitmap, g_dev[0].coll.p, bm, hipMemcpyDeviceToHost, g_dev[0].coll_stream));
+            HIPCHK(hipStreamSynchronize(g_dev[0].coll_stream));
+        }
+    }
+    bool all = true;
+    for (int i = 0; i < plan.nshards; i++) all = all && held[i];
+    if (combined) *combined = all ? 1 : 0;
+    return BLSMI_OK;
+}
+}  // namespace
+#define JACP(p) reinterpret_cast<const uint8_t*>(p)
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(0, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(1, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                         const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    if (n && !domain) return BLSMI_E_ARG;
+    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
+                                                             uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    if (n && !domain) return BLSMI_E_ARG;
+    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+
+// ---- grouped randomised batch verification (blsmi 0.11; include/blsmi.h "grouped") -------------------------------------------------------
+// The combined check of rlc_shard for batches whose n tuples share d messages: tuple i is (msgs[msg_idx[i]], pk_i, sig_i), and bilinearity
+// lets the tuples of one message share one pairing --
+//     g1pubs: e(G1gen, sum_i r_i sig_i) == prod_g e(sum_{i in g} r_i pk_i, H(m_g))      g2pubs: e(sum_i r_i sig_i, G2gen) == prod_g e(H(m_g), sum_{i in g} r_i pk_i)
+// d' hashes and d' Miller loops for the d' messages some tuple refers to, instead of n of each.  The keys' side is the weighted segmented
+// sum (segsum_dev with scalars: k_g?_segsum_chunk_u64, no inversion per tuple) over the host plan of group_plan.h; the signature side is
+// rlc_shard's (rlc_sig_sum on the side stream, sig_side_start_dev, aggregate_tail).  One lease, one device, no request combiner; "rlc_min"
+// is not consulted: calling this form is the caller's choice of the combined path.  When the check fails, or a point at infinity meets it
+// (an input, a group's sum, the signatures' sum), the per-tuple verdicts of verify_batch come from the buffers on the device, the d' hash
+// points gathered per tuple (k_gather_records).
+namespace {
+int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    int rc = rlc_check_args(msgs && off_or_domain && msg_idx && pks && sigs && n <= 0xffffffffull, scalars, n);   // (n: the permutation is the 32-bit idx of the segmented sum)
+    if (rc || n == 0) return rc;
+    blsmi_route::GroupPlan gp;
+    std::vector<uint64_t> coff;
+    std::vector<uint8_t> cm;
+    try {
+        if (!blsmi_route::group_plan(msg_idx, n, d, gp)) return BLSMI_E_ARG;   // some msg_idx[i] >= d (d == 0 included)
+        const size_t dg = gp.msg_of.size();
+        // the messages some tuple refers to, compacted in table order (an entry nobody refers to is never hashed)
+        if (kind == 2) {
+            cm.resize(32 * dg);
+            for (size_t g = 0; g < dg; g++) memcpy(cm.data() + 32 * g, msgs + (size_t)32 * gp.msg_of[g], 32);
+        } else {
+            coff.assign(dg + 1, 0);
+            for (size_t g = 0; g < dg; g++) {
+                const uint64_t a = off_or_domain[gp.msg_of[g]], b = off_or_domain[gp.msg_of[g] + 1];
+                if (b < a) return BLSMI_E_ARG;
+                coff[g + 1] = coff[g] + (b - a);
+            }
+            cm.resize((size_t)coff[dg]);
+            for (size_t g = 0; g < dg; g++) if (coff[g + 1] > coff[g]) memcpy(cm.data() + coff[g], msgs + off_or_domain[gp.msg_of[g]], (size_t)(coff[g + 1] - coff[g]));
+        }
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    RlcHostScratch hs;
+    rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap, n); if (rc) return rc;
+    { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const Tuning& t = tune();
+    const size_t dg = gp.msg_of.size();
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    RlcCall c;
+    rc = rlc_begin(c, kind, n, cm.size(), kind == 2 ? 8 : sizeof(uint64_t) * (dg + 1));   // the d' messages some tuple refers to
+    if (rc) return rc;
+    const Kind& k = c.k;
+    SegPlan plan;
+    segsum_plan(gp.seg_off.data(), dg, segsum_chunk_of(n), plan, 64, 1);
+    const AggregateRoute ar = aggregate_route(kind, dg, false, true, t, route_load(dg));   // the layout an aggregate of d' records takes; always cleared hash points
+    DBuf dx, h, agg, ainf, gflags, fr0, fr1;
+    HIPCHK(dx.alloc(sizeof(uint32_t) * n)); HIPCHK(h.alloc((size_t)k.h_bytes * dg)); HIPCHK(agg.alloc((size_t)k.pk_bytes * dg)); HIPCHK(ainf.alloc(dg)); HIPCHK(gflags.alloc(dg));
+    HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
+    rc = rlc_upload_start(c, sigs, scalars, cm.data(), kind == 2 ? (const void*)off_or_domain : (const void*)coff.data(), fmt); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
+    rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), dg, s, ar.hash);
+    if (rc) return rc;
+    rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(dx.p, gp.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));   // the plan's permutation, behind the keys
+    rlc_flag_inputs(c);
+    // sum_{i in g} r_i pk_i for every group; a sum at infinity is flagged like an input.  On s, the context's main stream: segsum_dev names
+    // k_g?_segsum_chunk_u64 in the profile only there (profile marks are events on that stream), and tests/test_gpu_rlc_grouped.py looks
+    // for the name -- a move of the sums to aux[1] must point the context's stream at it for the stretch (OnStream, as rlc_signature_side)
+    rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, c.dr.as<u64>());
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(dg)), dim3(WG), 0, s, (const u8*)agg.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)ainf.as<u8>(), gflags.as<u8>(), c.any.as<int>(), dg);
+    // d' Miller loops, one per message, and their product
+    launch_miller1(kind == 0 ? h.as<u8>() : agg.as<u8>(), kind == 0 ? agg.as<u8>() : h.as<u8>(), fr0.as<i32>(), dg, s, ar, nullptr);
+    const i32* prod = prod_tree(fr0.as<i32>(), ar.records, fr1.as<i32>(), fr0.as<i32>(), s);
+    HIPCHK(hipGetLastError());
+    rc = rlc_check_total(c, prod); if (rc) return rc;
+    if (c.held()) HIPCHK(hipMemsetAsync(c.dok.p, 1, n, s));
+    else {
+        // the per-tuple verdicts of verify_batch: every tuple's hash point from its group's, then the pair stage of a batch of n
+        DBuf hfull, dgo;
+        HIPCHK(hfull.alloc((size_t)k.h_bytes * n)); HIPCHK(dgo.alloc(sizeof(uint32_t) * n));
+        HIPCHK(hipMemcpyAsync(dgo.p, gp.group_of.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        const u32 hw = (u32)(k.h_bytes / 4);
+        hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * n)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dgo.as<u32>(), hfull.as<u32>(), hw, n);
+        rc = rlc_fallback_all(c, hfull.as<u8>(), verify_route(kind, n, false, false, t, route_load(n))); if (rc) return rc;
+    }
+    return rlc_finish(c, ok, ok_bitmap, combined);
+}
+}  // namespace
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                                const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                                    const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
+    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars,
+                                         ok, ok_bitmap, n, combined, FMT_JAC);
+}
+
+// ---- randomised batch verification that finds the bad tuples by blocks (blsmi 0.12; include/blsmi.h "locate") -----------------------------
+// rlc_shard's combined check with the batch cut into B contiguous blocks of `block` tuples (locate_plan.h).  The tuple side's Miller values
+// are multiplied block by block first (k_fq12_seg_prod_row over the blocks' record borders) and the B block values KEPT; the product tree
+// then runs over those for the total, which is checked as in rlc_shard.  When the total holds and nothing is flagged every verdict is 1.
+// Otherwise one pairing equation per block --
+//     g2pubs: e(S_b, G2gen) == prod_{i in b} e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, S_b) == prod_{i in b} e(r_i pk_i, H(m_i))        S_b = sum_{i in b} r_i sig_i
+// -- decides which blocks hold: the S_b by the weighted segmented sum, B Miller loops for (-S_b, G2gen) / (-G1gen, S_b), each times its block
+// value (k_fq12_mul_pairs_row), B final exponentiations, the comparison with one.  A block whose weights are its own tuples' r_i is wrong
+// with probability at most 2^-64, as the whole batch is.  A block with a flagged tuple, or whose S_b is at infinity, counts as failing
+// whatever its equation says.  The tuples of the failing blocks, and only those, are gathered into dense buffers and get verify_batch's
+// per-tuple verdicts.  One lease, one device, no request combiner, "rlc_min" not consulted.  The hash points are always cleared here, also
+// where rlc_shard raises the product to 1 - x instead (agg_pow_wanted): the block values then need no exponentiation each and the
+// per-tuple stage reads the hash points that are there (DESIGN 3l has what that costs the call that holds).
+namespace {
+// Stages 4 and 5, when the total failed: S_b for every block, the B signature-side Miller values in the layout a Pairing call of B tuples
+// takes, each times its block value, the final exponentiations in the layout a pairing product of B items takes, one byte per block; then
+// `pos`, the positions of the failing blocks' tuples.  sflags: the flag bytes of the scaled points.  Synchronises the main stream.
+int locate_failing_positions(RlcCall& c, const blsmi_route::LocatePlan& lp, const i32* bval, const u8* sflags, std::vector<uint32_t>& pos) {
+    const Kind& k = c.k;
+    const size_t n = c.n, B = lp.blocks(), words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    SegPlan splan;
+    std::vector<uint8_t> fail;
+    try { segsum_plan(lp.tup_off.data(), B, segsum_chunk_of(n), splan, 64, 1); fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t bload = route_load(B);
+    const Layout fe = pprod_fe_layout(B, bload);
+    DBuf sb, sbinf, g1, g2, bbad, fs, prod, vals, one, dfail;
+    HIPCHK(sb.alloc((size_t)k.sig_bytes * B)); HIPCHK(sbinf.alloc(B)); HIPCHK(g1.alloc((size_t)96 * B)); HIPCHK(g2.alloc((size_t)192 * B)); HIPCHK(bbad.alloc(B));
+    HIPCHK(fs.alloc(sizeof(i32) * words * B)); HIPCHK(prod.alloc(fe == Layout::wave ? 576 * B : sizeof(i32) * words * B)); HIPCHK(vals.alloc(576 * B));
+    HIPCHK(one.alloc(B)); HIPCHK(dfail.alloc(B));
+    int rc = segsum_dev(k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, c.dr.as<u64>());
+    if (rc) return rc;
+    prof_mark("k_locate_sig_pairs");
+    hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(B)), dim3(WG), 0, s, c.kind == 0 ? 0 : 1, (const u8*)sb.as<u8>(), (const u8*)sbinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
+                       g1.as<u8>(), g2.as<u8>(), bbad.as<u8>(), B);
+    launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), B, s, pairing_layout(0, B, tune(), bload));
+    prof_mark("k_fq12_mul_pairs_row");
+    hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(B)), dim3(WG), 0, s, bval, (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
+                       fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, B);
+    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, B, s);
+    prof_mark("k_locate_block_fail");
+    hipLaunchKernelGGL(k_locate_block_fail, dim3(rblocks(B)), dim3(WG), 0, s, (const u8*)c.flags.as<u8>(), sflags, n, lp.block, (const u8*)bbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), B);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, B, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    try { blsmi_route::locate_positions(lp, fail.data(), pos); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    return BLSMI_OK;
+}
+// Stage 6: the tuples at `pos` (those of the failing blocks), gathered into dense buffers with their hash points h; verify_batch's pair stage
+// routed by their count; the verdicts back into c.dok
+int locate_recheck(RlcCall& c, const DBuf& h, const std::vector<uint32_t>& pos) {
+    const Kind& k = c.k;
+    const size_t nre = pos.size(), words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    DBuf dpos, hd, pd, sd, id, okd, f;
+    HIPCHK(dpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hd.alloc((size_t)k.h_bytes * nre)); HIPCHK(pd.alloc((size_t)k.pk_bytes * nre)); HIPCHK(sd.alloc((size_t)k.sig_bytes * nre));
+    HIPCHK(id.alloc(nre)); HIPCHK(okd.alloc(nre)); HIPCHK(f.alloc(sizeof(i32) * words * nre));
+    HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) {
+        const u32 q = (u32)(bytes / 16);
+        hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)dpos.as<u32>(), to.as<uint4>(), q, nre);
+    };
+    prof_mark("k_gather_records16");
+    gather(h, hd, k.h_bytes); gather(c.dp, pd, k.pk_bytes); gather(c.ds, sd, k.sig_bytes);
+    if (c.has_inf) hipLaunchKernelGGL(k_gather_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)c.di.as<u8>(), (const u32*)dpos.as<u32>(), id.as<u8>(), nre);
+    prof_mark(nullptr);
+    const VerifyRoute vr = verify_route(c.kind, nre, false, false, tune(), route_load(nre));
+    int rc = verify_pair_stage(c.kind, hd.as<u8>(), pd.p, sd.p, c.has_inf ? id.p : nullptr, okd.p, f.as<i32>(), nre, s, vr);
+    if (rc) return rc;
+    prof_mark("k_scatter_bytes");
+    hipLaunchKernelGGL(k_scatter_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)okd.as<u8>(), (const u32*)dpos.as<u32>(), c.dok.as<u8>(), nre);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                 const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked, int fmt = 0) {
+    if (combined) *combined = 0;
+    if (rechecked) *rechecked = 0;
+    if (!blsmi_route::locate_block_valid(block)) return BLSMI_E_ARG;
+    int rc = rlc_check_args(msgs && off_or_domain && pks && sigs && n <= 0xffffffffull, scalars, n);   // (n: the positions of the failing blocks are 32-bit indices)
+    if (rc || n == 0) return rc;
+    RlcHostScratch hs;
+    rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap, n); if (rc) return rc;
+    { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const Tuning& t = tune();
+    const size_t load = route_load(n);
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    const AggregateRoute ar = aggregate_route(kind, n, false, true, t, load);   // always cleared hash points
+    const size_t nrec = ar.records;
+    blsmi_route::LocatePlan lp;
+    SegPlan bplan;
+    try {
+        blsmi_route::locate_plan(n, block ? block : blsmi_route::locate_auto_block(n), nrec != n, lp);
+        pprod_plan(lp.rec_off.data(), lp.blocks(), bplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t B = lp.blocks(), half = (B + 1) / 2;
+    RlcCall c;
+    rc = rlc_begin(c, kind, n, kind == 2 ? 32 * n : (size_t)off_or_domain[n], kind == 2 ? 8 : sizeof(uint64_t) * (n + 1)); if (rc) return rc;
+    const Kind& k = c.k;
+    DBuf h, scaled, sinf, sflags, fr, bval, t0, t1, bblob;
+    HIPCHK(h.alloc((size_t)k.h_bytes * n)); HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(sflags.alloc(n));
+    HIPCHK(fr.alloc(sizeof(i32) * words * nrec)); HIPCHK(bval.alloc(sizeof(i32) * words * B)); HIPCHK(t0.alloc(sizeof(i32) * words * half)); HIPCHK(t1.alloc(sizeof(i32) * words * half));
+    HIPCHK(bblob.alloc(bplan.blob.size()));
+    // stage 1, as rlc_shard: the uploads, the hash, the flags, r_i H_i / r_i pk_i (flagged into bytes of their own: the inputs' flags stay for the block checks), the Miller loops
+    rc = rlc_upload_start(c, sigs, scalars, msgs, off_or_domain, fmt); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
+    rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, ar.hash);
+    if (rc) return rc;
+    rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
+    rlc_flag_inputs(c);
+    rlc_scale_g1(c, kind == 0 ? h.as<u8>() : c.dp.as<u8>(), scaled.as<u8>(), sinf.as<u8>(), sflags.as<u8>());
+    launch_miller1(scaled.as<u8>(), kind == 0 ? c.dp.as<u8>() : h.as<u8>(), fr.as<i32>(), n, s, ar, nullptr);
+    // stage 2: the block values, then the tree over them (its levels alternate between t0 and t1; the block values stay)
+    prof_mark("k_fq12_seg_prod_row");
+    rc = seg_prod_dev(fr.as<i32>(), nrec, nullptr, bplan, bblob.as<u8>(), bval.as<i32>(), nullptr, s);
+    if (rc) return rc;
+    prof_mark(nullptr);
+    const i32* total = prod_tree(bval.as<i32>(), B, t0.as<i32>(), t1.as<i32>(), s);
+    HIPCHK(hipGetLastError());
+    // stage 3: sum r_i sig_i and its Miller loop on the side stream, the tail
+    rc = rlc_check_total(c, total); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c.dok.p, 1, n, s));
+    std::vector<uint32_t> pos;
+    if (!c.held()) { rc = locate_failing_positions(c, lp, bval.as<i32>(), sflags.as<u8>(), pos); if (rc) return rc; }
+    const size_t nre = pos.size();
+    if (nre) { rc = locate_recheck(c, h, pos); if (rc) return rc; }
+    rc = rlc_finish(c, ok, ok_bitmap, combined);
+    if (rechecked && !rc) *rechecked = nre;
+    return rc;
+}
+}  // namespace
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(0, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(1, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
+                                                               const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
+                                                                   uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
+}
+#undef JACP

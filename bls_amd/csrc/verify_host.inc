@@ -151,6 +151,16 @@ void launch_prod_level(const i32* src, i32* dst, size_t cur, size_t half, hipStr
         hipLaunchKernelGGL(k_fq12_prod_level, dim3(nblocks(half)), dim3(WG), 0, s, src, dst, cur, half);
     prof_mark(nullptr);
 }
+// The product tree over the cur values at src: level after level into a, b, a, ... (each with room for half the values it reads; src is never
+// written, so b may be src itself); returns where the one product lies -- src when cur == 1
+const i32* prod_tree(const i32* src, size_t cur, i32* a, i32* b, hipStream_t s) {
+    for (i32* dst = a; cur > 1; dst = dst == a ? b : a) {
+        const size_t half = (cur + 1) / 2;
+        launch_prod_level(src, dst, cur, half, s);
+        src = dst; cur = half;
+    }
+    return src;
+}
 // The Miller loops of an aggregate in the layout of its route (route.h: aggregate_route), which also says how many Fq12 values they leave
 // in f: n, or ceil(n / 2) when two tuples share a loop.  prep: the keys' tables (only where r.tables; d_g2 is unused then).
 void launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, const AggregateRoute& r, const PrepKeys* prep) {
@@ -677,14 +687,7 @@ int aggregate_shard_dev(int kind, const void* d_msgs, const void* d_off_or_domai
     else hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, d_pks, k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)nullptr, flags.as<u8>(), any.as<int>(), n);
     // Pairing(h_i, pk_i) (g2pubs) / Pairing(pk_i, h_i) (g1pubs): Miller loops only, then the product tree
     launch_miller1(kind == 0 ? h.as<u8>() : d_pks, kind == 0 ? d_pks : h.as<u8>(), fr0.as<i32>(), n, s, r, prep);
-    size_t cur = nrec;
-    i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
-    while (cur > 1) {
-        const size_t half = (cur + 1) / 2;
-        launch_prod_level(src, dst, cur, half, s);
-        std::swap(src, dst);
-        cur = half;
-    }
+    const i32* src = prod_tree(fr0.as<i32>(), nrec, fr1.as<i32>(), fr0.as<i32>(), s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(d_out, src, sizeof(i32) * words, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -907,15 +910,8 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
     if (lease.rc) return lease.rc;
     i32* soa = lhs + words; i32* scratch = soa + words * total;
     hipLaunchKernelGGL(k_fq12_aos_to_soa, dim3(nblocks(words * cnt)), dim3(WG), 0, g_stream, gathered, soa, cnt);
-    i32* src = soa; i32* dst = scratch;
-    size_t cur = cnt;
-    while (cur > 1) {
-        const size_t half = (cur + 1) / 2;
-        launch_prod_level(src, dst, cur, half, g_stream);
-        std::swap(src, dst);
-        cur = half;
-    }
-    if (powc) { int rc2 = aggregate_pow_c(src, dst); if (rc2) return rc2; src = dst; }   // (dst: the tree's other buffer, free now)
+    const i32* src = prod_tree(soa, cnt, scratch, soa, g_stream);
+    if (powc) { i32* dst = src == soa ? scratch : soa; int rc2 = aggregate_pow_c(src, dst); if (rc2) return rc2; src = dst; }   // (dst: the tree's other buffer, free now)
     return aggregate_tail(kind, src, sig, ok, fmt);
 }
 int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, int fmt = 0) {
@@ -964,233 +960,6 @@ int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_doma
     }
     if (powc) { DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * words)); int rc = aggregate_pow_c(prod.as<i32>(), pc.as<i32>()); if (rc) return rc; return aggregate_tail(kind, pc.as<i32>(), ss, ok); }
     return aggregate_tail(kind, prod.as<i32>(), ss, ok);
-}
-// ---- randomised batch verification (blsmi 0.8: blsmi_g?pubs_verify_batch_rlc) ------------------------------------------------------
-// Small-exponent batch verification (Bellare, Garay, Rabin 1998): with random nonzero 64-bit r_i, ONE equation stands for the n of a batch --
-//     g2pubs: e(sum r_i sig_i, G2gen) == prod e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, sum r_i sig_i) == prod e(r_i pk_i, H(m_i))
-// It holds when every tuple is valid; with an invalid tuple among them it holds with probability at most 2^-64 over the r_i (keys and
-// signatures in the prime-order subgroups, as Deserialize guarantees).  n Miller loops, the product tree and ONE final exponentiation (the
-// VerifyAggregate machinery), plus a 64-bit multiplication per tuple (k_g1_mul_u64: r_i H_i for g2pubs, r_i pk_i for g1pubs -- both in G1)
-// and a 64-bit MSM over the signatures, which runs on the side stream beside the hash.  When the check fails, or a point at infinity
-// meets it, the shard computes the per-tuple verdicts of verify_batch from the buffers already on the device.
-//
-// The scalars: nonzero 64-bit words from the OS (getrandom, /dev/urandom), fresh for every call; no state is kept between calls.
-int rlc_draw_scalars(uint64_t* r, size_t n) {
-    uint8_t* p = reinterpret_cast<uint8_t*>(r);
-    size_t want = 8 * n, got = 0;
-#ifdef SYS_getrandom
-    while (got < want) {
-        const long k = syscall(SYS_getrandom, p + got, std::min(want - got, (size_t)1 << 20), 0);
-        if (k > 0) got += (size_t)k;
-        else if (k < 0 && errno == EINTR) continue;
-        else break;
-    }
-#endif
-    if (got < want) {
-        const int fd = open("/dev/urandom", O_RDONLY | O_CLOEXEC);
-        if (fd < 0) return BLSMI_E_RNG;
-        while (got < want) {
-            const ssize_t k = read(fd, p + got, want - got);
-            if (k > 0) got += (size_t)k;
-            else if (k < 0 && errno == EINTR) continue;
-            else break;
-        }
-        close(fd);
-        if (got < want) return BLSMI_E_RNG;
-    }
-    for (size_t i = 0; i < n; i++)                                         // a zero word (probability 2^-64 each) is drawn again
-        while (r[i] == 0) { int rc = rlc_draw_scalars(&r[i], 1); if (rc) return rc; }
-    return BLSMI_OK;
-}
-// The signature side's sum, sum_i r_i sig_i over the n signatures on the device (any curve points): affine at d_sum, infinity flag (int32)
-// at d_flag, on g_stream.  From RLC_MSM_BUCKET_MIN signatures the bucket method of msm_bucket_dev over the scalars' 64 bits (four
-// 16-bit windows); below, or when the digits are skewed (a caller's scalars), per-signature 64-bit ladders and the tree sum.
-constexpr size_t RLC_MSM_BUCKET_MIN = 8192;
-int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum, i32* d_flag) {
-    hipStream_t s = g_stream;
-    if (n >= RLC_MSM_BUCKET_MIN) {
-        DBuf sc; HIPCHK(sc.alloc((size_t)32 * n));
-        hipLaunchKernelGGL(k_scalar_u64_to_be32, dim3(nblocks(n)), dim3(WG), 0, s, d_r, sc.as<u8>(), n);
-        const int rc = kind == 0 ? msm_bucket_dev<96, 3>(g_mk1, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64)
-                                 : msm_bucket_dev<192, 6>(g_mk2, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
-        if (rc != BLSMI_E_SKEW) return rc;
-    }
-    const size_t pb = kind == 0 ? 96 : 192;
-    DBuf m, inf; HIPCHK(m.alloc(pb * n)); HIPCHK(inf.alloc(n));
-    prof_mark(kind == 0 ? "k_g1_mul_u64" : "k_g2_mul_u64");
-    if (kind == 0) hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
-    else hipLaunchKernelGGL(k_g2_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    return kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
-                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
-}
-// sig_side_start for a signature already on the device (the sum above, read in place): MillerLoop(-sig, G2gen) / MillerLoop(-G1gen, sig)
-// into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
-int sig_side_start_dev(int kind, const u8* d_sig, SigSide& ss) {
-    HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
-    const u8* tp = kind == 0 ? d_sig : g_gens.g1;
-    const u8* tq = kind == 0 ? g_gens.g2 : d_sig;
-    prof_mark("k_lat:miller1rawn");
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
-                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(ss.ml.p), (size_t)1);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(tl_ctx->join[0], g_stream));
-    return BLSMI_OK;
-}
-// the context's stream pointed at another of its streams for a stretch of one call (the kernels and their profile marks go there)
-struct OnStream { hipStream_t saved; explicit OnStream(hipStream_t s) : saved(tl_ctx->stream) { tl_ctx->stream = s; } ~OnStream() { tl_ctx->stream = saved; } };
-
-// One shard on the leased context (tune(): the call's snapshot).  ok: n verdict bytes (host, may be null); d_bitmap_slice as in
-// verify_batch_leased; *held = true when the combined check held and every verdict is 1.  r: n nonzero scalars (host).
-int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-              const uint64_t* r, uint8_t* ok, size_t n, int fmt, bool* held, u8* d_bitmap_slice = nullptr) {
-    *held = false;
-    if (n == 0) return BLSMI_OK;
-    const Kind k = kind_of(kind);
-    const Tuning& t = tune();
-    const size_t load = route_load(n);
-    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
-    const size_t words = (size_t)12 * NL;
-    hipStream_t s = g_stream;
-    HIPCHK(tl_ctx->ensure_aux());
-    hipStream_t st = tl_ctx->aux[0];
-    DBuf dm, doff, dp, ds, di, dr, dok, h, scaled, sinf, flags, any, sum, sflag, fr0, fr1, pc, dokb;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
-    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * n));
-    HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(flags.alloc(n)); HIPCHK(any.alloc(sizeof(int)));
-    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
-    // the signatures go first, on the side stream (pageable copies block the host: the hash is queued behind the first of them only)
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
-    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
-    HIPCHK(hipMemcpyAsync(dr.p, r, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
-    bool powc = agg_pow_wanted(kind, n, t);                                // g2pubs from AGG_POW_MIN: uncleared hash points, the product raised to 1 - x
-    bool sig_side = false, cleared = !powc;
-    SigSide ss;
-    int bad = 0, sum_inf = 0, verdict = 0;
-    // the tuple side: hash, scale, Miller loops, product tree (+ the cofactor power); then the signature side on the side stream; then the tail
-    auto combined_check = [&]() -> int {
-        const AggregateRoute ar = aggregate_route(kind, n, false, !powc, t, load);
-        const size_t nrec = ar.records;
-        HIPCHK(fr0.alloc(sizeof(i32) * words * nrec)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((nrec + 1) / 2)));
-        HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
-        int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, ar.hash, !powc, powc ? any.as<int>() : nullptr);   // *bad bit 1: a hash point the uncleared path does not cover
-        if (rc) return rc;
-        cleared = !powc;
-        if (!sig_side) {                                                   // (first attempt) the keys travel while the messages are hashed
-            rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);
-            if (rc) return rc;
-            if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
-        }
-        hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
-                           (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
-        // r_i H_i (g2pubs; h itself stays for the fallback) / r_i pk_i (g1pubs); a scaled point at infinity is flagged like an input
-        const u8* src1 = kind == 0 ? h.as<u8>() : dp.as<u8>();
-        prof_mark("k_g1_mul_u64");
-        hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, src1, (const u64*)dr.as<u64>(), scaled.as<u8>(), sinf.as<u8>(), n);
-        prof_mark(nullptr);
-        hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)scaled.as<u8>(), 24, (const u8*)nullptr, 0, (const u8*)sinf.as<u8>(), flags.as<u8>(), any.as<int>(), n);
-        launch_miller1(scaled.as<u8>(), kind == 0 ? dp.as<u8>() : h.as<u8>(), fr0.as<i32>(), n, s, ar, nullptr);
-        size_t cur = nrec;
-        i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
-        while (cur > 1) { const size_t half = (cur + 1) / 2; launch_prod_level(src, dst, cur, half, s); std::swap(src, dst); cur = half; }
-        HIPCHK(hipGetLastError());
-        if (powc) { HIPCHK(pc.alloc(sizeof(i32) * words)); rc = aggregate_pow_c(src, pc.as<i32>()); if (rc) return rc; src = pc.as<i32>(); }
-        HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        if (!sig_side) {                                                   // sum r_i sig_i and its Miller loop, beside the tuple side
-            sig_side = true;
-            HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
-            OnStream on(st);
-            rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
-            if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-            rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
-            if (rc) return rc;
-        }
-        return aggregate_tail(kind, src, ss, &verdict);                    // waits for the side stream; synchronises s
-    };
-    int rc = combined_check();
-    if (rc) return rc;
-    if (!(bad & 1) && (bad & 2)) { powc = false; rc = combined_check(); if (rc) return rc; }   // an uncovered hash point: once more with the cleared points
-    *held = verdict == 1 && bad == 0 && sum_inf == 0;
-    if (*held) HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
-    else {
-        // the per-tuple verdicts of verify_batch, from the inputs on the device (the hash again where h holds uncleared points)
-        const VerifyRoute vr = verify_route(kind, n, false, false, t, load);
-        if (!cleared) { rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
-        DBuf f; HIPCHK(f.alloc(sizeof(i32) * words * n));
-        rc = verify_pair_stage(kind, h.as<u8>(), dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, s, vr);
-        if (rc) return rc;
-    }
-    if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, s, (const u8*)dok.as<u8>(), d_bitmap_slice, n);
-    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return BLSMI_OK;
-}
-// The host entry points.  scalars (may be null: drawn here) are checked for zeros first; below the call's rlc_min the per-tuple path runs
-// directly.  A split call (plan_shards) runs one combined check per shard, each with its own fallback; the bitmap comes together as in
-// verify_batch_direct.  *combined (may be null) = 1 when every verdict came from a combined check that held.
-int verify_batch_rlc_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                          const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
-    if (combined) *combined = 0;
-    if (n && (!msgs || !off_or_domain || !pks || !sigs)) return BLSMI_E_ARG;
-    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
-    if (n == 0) return BLSMI_OK;
-    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
-    const Tuning t = tuning_now();                                         // the call's options, once: every shard routes by this snapshot
-    if (n < t.rlc_min) return verify_batch_direct(kind, msgs, off_or_domain, pks, sigs, inf_flags, ok, ok_bitmap, n, fmt);
-    std::vector<uint64_t> drawn;
-    if (!scalars) {
-        try { drawn.resize(n); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-        int rc = rlc_draw_scalars(drawn.data(), n);
-        if (rc) return rc;
-        scalars = drawn.data();
-    }
-    const Kind k = kind_of(kind);
-    const ShardPlan plan = plan_shards(n, 64);
-    std::vector<uint8_t> tmp;
-    if (!ok && ok_bitmap && plan.nshards == 1) { tmp.resize(n); ok = tmp.data(); }
-    std::unique_ptr<bool[]> held(new bool[plan.nshards]());
-    std::unique_lock<std::mutex> coll_lk(g_coll_mu, std::defer_lock);
-    const size_t bm = (n + 7) / 8;
-    if (plan.nshards > 1 && ok_bitmap) { coll_lk.lock(); int rc = coll_reserve_all(bm, true); if (rc) return rc; }
-    int rc = run_shards(plan, [&](int sh, size_t lo, size_t hi) -> int {
-        tl_ctx->tune = t;
-        const size_t m = hi - lo;
-        std::vector<uint64_t> off_sub;
-        const uint8_t* mp; const uint64_t* op;
-        if (kind == 2) { mp = msgs + 32 * lo; op = off_or_domain; }
-        else {
-            off_sub.resize(m + 1);
-            for (size_t i = 0; i <= m; i++) off_sub[i] = off_or_domain[lo + i] - off_or_domain[lo];
-            mp = msgs + off_or_domain[lo]; op = off_sub.data();
-        }
-        u8* slice = (plan.nshards > 1 && ok_bitmap) ? reinterpret_cast<u8*>(tl_ctx->dev->coll.p) + lo / 8 : nullptr;
-        return rlc_shard(kind, mp, op, pks + rec_bytes(k.pk_bytes, fmt & FMT_PK_JAC) * lo, sigs + rec_bytes(k.sig_bytes, fmt & FMT_SIG_JAC) * lo,
-                         inf_flags ? inf_flags + lo : nullptr, scalars + lo, ok ? ok + lo : nullptr, m, fmt, &held[sh], slice);
-    });
-    if (rc) return rc;
-    if (ok_bitmap) {
-        if (plan.nshards == 1) pack_bitmap(ok, ok_bitmap, n);
-        else {
-            rc = allreduce_bitmap(bm);
-            if (rc) return rc;
-            HIPCHK(hipSetDevice(g_dev[0].id));
-            HIPCHK(hipMemcpyAsync(ok_bitmap, g_dev[0].coll.p, bm, hipMemcpyDeviceToHost, g_dev[0].coll_stream));
-            HIPCHK(hipStreamSynchronize(g_dev[0].coll_stream));
-        }
-    }
-    bool all = true;
-    for (int i = 0; i < plan.nshards; i++) all = all && held[i];
-    if (combined) *combined = all ? 1 : 0;
-    return BLSMI_OK;
 }
 
 // VerifyAggregateCommon: AggregatePublicKeys (sum) then one Verify (g2pubs/bls.go:275-278)
@@ -1427,14 +1196,7 @@ BLSMI_API int blsmi_fq12_product(const uint64_t* in, size_t n, uint64_t* out72) 
     HIPCHK(di.alloc(576 * n)); HIPCHK(fr0.alloc(sizeof(i32) * words * n)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((n + 1) / 2))); HIPCHK(dout.alloc(576));
     HIPCHK(hipMemcpyAsync(di.p, in, 576 * n, hipMemcpyHostToDevice, g_stream));
     hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, di.as<u64>(), fr0.as<i32>(), n);
-    i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
-    size_t cur = n;
-    while (cur > 1) {
-        const size_t half = (cur + 1) / 2;
-        launch_prod_level(src, dst, cur, half, g_stream);
-        std::swap(src, dst);
-        cur = half;
-    }
+    const i32* src = prod_tree(fr0.as<i32>(), n, fr1.as<i32>(), fr0.as<i32>(), g_stream);
     hipLaunchKernelGGL(k_final_exp, dim3(1), dim3(WG), 0, g_stream, (const i32*)src, dout.as<u64>(), (size_t)1, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out72, dout.p, 576, hipMemcpyDeviceToHost, g_stream));
@@ -1603,19 +1365,6 @@ BLSMI_API int blsmi_g1pubs_verify_batch(const uint8_t* msgs, const uint64_t* off
 BLSMI_API int blsmi_g1pubs_verify_with_domain_batch(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags, uint8_t* ok, uint8_t* ok_bitmap, size_t n) {
     if (!domain) return BLSMI_E_ARG;
     return verify_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, ok, ok_bitmap, n);
-}
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_host(0, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                             const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_host(1, msgs, off, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                                         const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    if (n && !domain) return BLSMI_E_ARG;
-    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
 }
 BLSMI_API int blsmi_g2pubs_verify_batch_dev(const void* d_msgs, const void* d_off, const void* d_pks, const void* d_sigs, const void* d_inf, void* d_ok, size_t n, void* stream) {
     if (n == 0) return BLSMI_OK;
@@ -1867,19 +1616,6 @@ BLSMI_API int blsmi_g1pubs_verify_batch_jac(const uint8_t* msgs, const uint64_t*
 BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, uint8_t* ok, uint8_t* ok_bitmap, size_t n) {
     if (!domain) return BLSMI_E_ARG;
     return verify_batch_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, ok, ok_bitmap, n, FMT_JAC);
-}
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
-                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
-                                                 uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars,
-                                                             uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    if (n && !domain) return BLSMI_E_ARG;
-    return verify_batch_rlc_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
 }
 BLSMI_API int blsmi_g2pubs_verify_aggregate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t sig[18], size_t n, int* ok) {
     return verify_aggregate_host(0, msgs, off, JACP(pks), JACP(sig), n, ok, true, FMT_JAC);
@@ -2265,159 +2001,6 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const v
     return agg_common_batch_dev_api<2>(d_msgs32, d_domain, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, stream);
 }
 
-// ---- grouped randomised batch verification (blsmi 0.11; include/blsmi.h "grouped") -------------------------------------------------------
-// The combined check of rlc_shard for batches whose n tuples share d messages: tuple i is (msgs[msg_idx[i]], pk_i, sig_i), and bilinearity
-// lets the tuples of one message share one pairing --
-//     g1pubs: e(G1gen, sum_i r_i sig_i) == prod_g e(sum_{i in g} r_i pk_i, H(m_g))      g2pubs: e(sum_i r_i sig_i, G2gen) == prod_g e(H(m_g), sum_{i in g} r_i pk_i)
-// d' hashes and d' Miller loops for the d' messages some tuple refers to, instead of n of each.  The keys' side is the weighted segmented
-// sum (segsum_dev with scalars: k_g?_segsum_chunk_u64, no inversion per tuple) over the host plan of group_plan.h; the signature side is
-// rlc_shard's (rlc_sig_sum on the side stream, sig_side_start_dev, aggregate_tail).  One lease, one device, no request combiner; "rlc_min"
-// is not consulted: calling this form is the caller's choice of the combined path.  When the check fails, or a point at infinity meets it
-// (an input, a group's sum, the signatures' sum), the per-tuple verdicts of verify_batch come from the buffers on the device, the d' hash
-// points gathered per tuple (k_gather_records).
-namespace {
-int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
-                                  const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
-    if (combined) *combined = 0;
-    if (n && (!msgs || !off_or_domain || !msg_idx || !pks || !sigs)) return BLSMI_E_ARG;
-    if (n > 0xffffffffull) return BLSMI_E_ARG;                             // (the permutation is the 32-bit idx of the segmented sum)
-    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
-    if (n == 0) return BLSMI_OK;
-    blsmi_route::GroupPlan gp;
-    std::vector<uint64_t> drawn, coff;
-    std::vector<uint8_t> cm, tmp;
-    try {
-        if (!blsmi_route::group_plan(msg_idx, n, d, gp)) return BLSMI_E_ARG;   // some msg_idx[i] >= d (d == 0 included)
-        const size_t dg = gp.msg_of.size();
-        // the messages some tuple refers to, compacted in table order (an entry nobody refers to is never hashed)
-        if (kind == 2) {
-            cm.resize(32 * dg);
-            for (size_t g = 0; g < dg; g++) memcpy(cm.data() + 32 * g, msgs + (size_t)32 * gp.msg_of[g], 32);
-        } else {
-            coff.assign(dg + 1, 0);
-            for (size_t g = 0; g < dg; g++) {
-                const uint64_t a = off_or_domain[gp.msg_of[g]], b = off_or_domain[gp.msg_of[g] + 1];
-                if (b < a) return BLSMI_E_ARG;
-                coff[g + 1] = coff[g] + (b - a);
-            }
-            cm.resize((size_t)coff[dg]);
-            for (size_t g = 0; g < dg; g++) if (coff[g + 1] > coff[g]) memcpy(cm.data() + coff[g], msgs + off_or_domain[gp.msg_of[g]], (size_t)(coff[g + 1] - coff[g]));
-        }
-        if (!scalars) drawn.resize(n);
-        if (!ok && ok_bitmap) { tmp.resize(n); ok = tmp.data(); }
-    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    if (!scalars) { int rc = rlc_draw_scalars(drawn.data(), n); if (rc) return rc; scalars = drawn.data(); }
-    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
-    CtxLease lease;
-    if (lease.rc) return lease.rc;
-    const Kind k = kind_of(kind);
-    const Tuning& t = tune();
-    const size_t dg = gp.msg_of.size();
-    const size_t msg_bytes = cm.size();
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (dg + 1);
-    const void* off_src = kind == 2 ? (const void*)off_or_domain : (const void*)coff.data();
-    const size_t words = (size_t)12 * NL;
-    const int pk_group = k.pk_bytes == 192 ? 2 : 1;
-    hipStream_t s = g_stream;
-    HIPCHK(tl_ctx->ensure_aux());
-    hipStream_t st = tl_ctx->aux[0];
-    SegPlan plan;
-    segsum_plan(gp.seg_off.data(), dg, segsum_chunk_of(n), plan, 64, 1);
-    DBuf dm, doff, dp, ds, di, dr, dx, dok, h, agg, ainf, flags, gflags, any, sum, sflag, fr0, fr1;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
-    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dx.alloc(sizeof(uint32_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * dg));
-    HIPCHK(agg.alloc((size_t)k.pk_bytes * dg)); HIPCHK(ainf.alloc(dg)); HIPCHK(flags.alloc(n)); HIPCHK(gflags.alloc(dg)); HIPCHK(any.alloc(sizeof(int)));
-    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
-    // the signatures go first, on the side stream, as in rlc_shard; then the scalars, the d' messages and the plan
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
-    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
-    HIPCHK(hipMemcpyAsync(dr.p, scalars, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, cm.data(), msg_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, off_src, off_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
-    const AggregateRoute ar = aggregate_route(kind, dg, false, true, t, route_load(dg));   // the layout an aggregate of d' records takes; always cleared hash points
-    HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
-    HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), dg, s, ar.hash);
-    if (rc) return rc;
-    rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the keys travel while the messages are hashed
-    if (rc) return rc;
-    if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dx.p, gp.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
-                       (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
-    // sum_{i in g} r_i pk_i for every group; a sum at infinity is flagged like an input.  On s, the context's main stream: segsum_dev names
-    // k_g?_segsum_chunk_u64 in the profile only there (profile marks are events on that stream), and tests/test_gpu_rlc_grouped.py looks
-    // for the name -- a move of the sums to aux[1] must point the context's stream at it for the stretch (OnStream, as the signature side below)
-    rc = segsum_dev(pk_group, false, dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, dr.as<u64>());
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(dg)), dim3(WG), 0, s, (const u8*)agg.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)ainf.as<u8>(), gflags.as<u8>(), any.as<int>(), dg);
-    launch_miller1(kind == 0 ? h.as<u8>() : agg.as<u8>(), kind == 0 ? agg.as<u8>() : h.as<u8>(), fr0.as<i32>(), dg, s, ar, nullptr);
-    size_t cur = ar.records;
-    i32* src = fr0.as<i32>(); i32* dst = fr1.as<i32>();
-    while (cur > 1) { const size_t half = (cur + 1) / 2; launch_prod_level(src, dst, cur, half, s); std::swap(src, dst); cur = half; }
-    HIPCHK(hipGetLastError());
-    int bad = 0, sum_inf = 0, verdict = 0;
-    HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    SigSide ss;
-    {                                                                      // sum r_i sig_i and its Miller loop, beside the tuple side
-        HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
-        OnStream on(st);
-        rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
-        if (rc) return rc;
-    }
-    rc = aggregate_tail(kind, src, ss, &verdict);                          // waits for the side stream; synchronises s
-    if (rc) return rc;
-    const bool held = verdict == 1 && bad == 0 && sum_inf == 0;
-    if (held) HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
-    else {
-        // the per-tuple verdicts of verify_batch: every tuple's hash point from its group's, then the pair stage of a batch of n
-        DBuf hfull, dgo, f;
-        HIPCHK(hfull.alloc((size_t)k.h_bytes * n)); HIPCHK(dgo.alloc(sizeof(uint32_t) * n)); HIPCHK(f.alloc(sizeof(i32) * words * n));
-        HIPCHK(hipMemcpyAsync(dgo.p, gp.group_of.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        const u32 hw = (u32)(k.h_bytes / 4);
-        hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * n)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dgo.as<u32>(), hfull.as<u32>(), hw, n);
-        const VerifyRoute vr = verify_route(kind, n, false, false, t, route_load(n));
-        rc = verify_pair_stage(kind, hfull.as<u8>(), dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, s, vr);
-        if (rc) return rc;
-    }
-    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, n);
-    if (combined) *combined = held ? 1 : 0;
-    return BLSMI_OK;
-}
-}  // namespace
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
-                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
-                                                    const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
-                                                                const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, pks, sigs, inf_flags, scalars, ok, ok_bitmap, n, combined);
-}
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
-                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(0, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
-                                                        const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(1, msgs, msg_off, d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars, ok, ok_bitmap, n, combined, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
-                                                                    const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined) {
-    return verify_batch_rlc_grouped_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), d, msg_idx, reinterpret_cast<const uint8_t*>(pks), reinterpret_cast<const uint8_t*>(sigs), nullptr, scalars,
-                                         ok, ok_bitmap, n, combined, FMT_JAC);
-}
-
 // ---- pairing products (blsmi 0.10; include/blsmi.h "pairing products") ------------------------------------------------------------------
 // Item j = FinalExponentiation(MillerLoop({(P_k, Q_k) : seg_off[j] <= k < seg_off[j + 1]})) (pairing.go:16-75, 79-129) in three stages on the
 // call's stream: one Miller value per pair in the layout a Pairing call of np tuples takes (any Miller value serves a product that is
@@ -2579,204 +2162,3 @@ BLSMI_API int blsmi_pairing_product_batch_dev(const void* d_g1_aff, const void* 
 BLSMI_API int blsmi_pairing_product_batch_jac_dev(const void* d_g1_jac, const void* d_g2_jac, size_t np, const void* d_seg_off, size_t m, void* d_out_fq12, void* d_is_one, void* stream) {
     return pprod_dev_api(d_g1_jac, d_g2_jac, nullptr, np, d_seg_off, m, d_out_fq12, d_is_one, stream, true);
 }
-
-// ---- randomised batch verification that finds the bad tuples by blocks (blsmi 0.12; include/blsmi.h "locate") -----------------------------
-// rlc_shard's combined check with the batch cut into B contiguous blocks of `block` tuples (locate_plan.h).  The tuple side's Miller values
-// are multiplied block by block first (k_fq12_seg_prod_row over the blocks' record borders) and the B block values KEPT; the product tree
-// then runs over those for the total, which is checked as in rlc_shard.  When the total holds and nothing is flagged every verdict is 1.
-// Otherwise one pairing equation per block --
-//     g2pubs: e(S_b, G2gen) == prod_{i in b} e(r_i H(m_i), pk_i)        g1pubs: e(G1gen, S_b) == prod_{i in b} e(r_i pk_i, H(m_i))        S_b = sum_{i in b} r_i sig_i
-// -- decides which blocks hold: the S_b by the weighted segmented sum, B Miller loops for (-S_b, G2gen) / (-G1gen, S_b), each times its block
-// value (k_fq12_mul_pairs_row), B final exponentiations, the comparison with one.  A block whose weights are its own tuples' r_i is wrong
-// with probability at most 2^-64, as the whole batch is.  A block with a flagged tuple, or whose S_b is at infinity, counts as failing
-// whatever its equation says.  The tuples of the failing blocks, and only those, are gathered into dense buffers and get verify_batch's
-// per-tuple verdicts.  One lease, one device, no request combiner, "rlc_min" not consulted.  The hash points are always cleared here, also
-// where rlc_shard raises the product to 1 - x instead (agg_pow_wanted): the block values then need no exponentiation each and the
-// per-tuple stage reads the hash points that are there (DESIGN 3l has what that costs the call that holds).
-namespace {
-int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                 const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked, int fmt = 0) {
-    if (combined) *combined = 0;
-    if (rechecked) *rechecked = 0;
-    if (!blsmi_route::locate_block_valid(block)) return BLSMI_E_ARG;
-    if (n && (!msgs || !off_or_domain || !pks || !sigs)) return BLSMI_E_ARG;
-    if (n > 0xffffffffull) return BLSMI_E_ARG;                             // (the positions of the failing blocks are 32-bit indices)
-    if (scalars) for (size_t i = 0; i < n; i++) if (scalars[i] == 0) return BLSMI_E_ARG;
-    if (n == 0) return BLSMI_OK;
-    std::vector<uint64_t> drawn;
-    std::vector<uint8_t> tmp;
-    try {
-        if (!scalars) drawn.resize(n);
-        if (!ok && ok_bitmap) { tmp.resize(n); ok = tmp.data(); }
-    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    if (!scalars) { int rc = rlc_draw_scalars(drawn.data(), n); if (rc) return rc; scalars = drawn.data(); }
-    { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
-    CtxLease lease;
-    if (lease.rc) return lease.rc;
-    const Kind k = kind_of(kind);
-    const Tuning& t = tune();
-    const size_t load = route_load(n);
-    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
-    const size_t words = (size_t)12 * NL;
-    hipStream_t s = g_stream;
-    HIPCHK(tl_ctx->ensure_aux());
-    hipStream_t st = tl_ctx->aux[0];
-    const AggregateRoute ar = aggregate_route(kind, n, false, true, t, load);
-    const size_t nrec = ar.records;
-    blsmi_route::LocatePlan lp;
-    SegPlan bplan;
-    try {
-        blsmi_route::locate_plan(n, block ? block : blsmi_route::locate_auto_block(n), nrec != n, lp);
-        pprod_plan(lp.rec_off.data(), lp.blocks(), bplan);
-    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    const size_t B = lp.blocks(), half = (B + 1) / 2;
-    DBuf dm, doff, dp, ds, di, dr, dok, h, scaled, sinf, flags, sflags, any, sum, sflag, fr, bval, t0, t1, bblob;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
-    HIPCHK(di.alloc(n)); HIPCHK(dr.alloc(sizeof(uint64_t) * n)); HIPCHK(dok.alloc(n)); HIPCHK(h.alloc((size_t)k.h_bytes * n));
-    HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(flags.alloc(n)); HIPCHK(sflags.alloc(n)); HIPCHK(any.alloc(sizeof(int)));
-    HIPCHK(sum.alloc(k.sig_bytes)); HIPCHK(sflag.alloc(sizeof(i32)));
-    HIPCHK(fr.alloc(sizeof(i32) * words * nrec)); HIPCHK(bval.alloc(sizeof(i32) * words * B)); HIPCHK(t0.alloc(sizeof(i32) * words * half)); HIPCHK(t1.alloc(sizeof(i32) * words * half));
-    HIPCHK(bblob.alloc(bplan.blob.size()));
-    // stage 1, as rlc_shard: the signatures first, on the side stream; the scalars, the messages, the hash, the keys, the flags, r_i H_i / r_i pk_i, the Miller loops
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, st); if (rc) return rc; }
-    HIPCHK(hipEventRecord(tl_ctx->join[1], st));
-    HIPCHK(hipMemcpyAsync(dr.p, scalars, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(tl_ctx->fork, s));                              // the scalars are there: the side stream's sum may start
-    HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(any.p, 0, sizeof(int), s));
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, s, ar.hash);
-    if (rc) return rc;
-    rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the keys travel while the messages are hashed
-    if (rc) return rc;
-    if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)dp.as<u8>(), k.pk_bytes / 4, (const u8*)ds.as<u8>(), k.sig_bytes / 4,
-                       (const u8*)(inf_flags ? di.as<u8>() : nullptr), flags.as<u8>(), any.as<int>(), n);
-    prof_mark("k_g1_mul_u64");
-    hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, kind == 0 ? (const u8*)h.as<u8>() : (const u8*)dp.as<u8>(), (const u64*)dr.as<u64>(), scaled.as<u8>(), sinf.as<u8>(), n);
-    prof_mark(nullptr);
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)scaled.as<u8>(), 24, (const u8*)nullptr, 0, (const u8*)sinf.as<u8>(), sflags.as<u8>(), any.as<int>(), n);   // (its own bytes: the inputs' flags stay for the block checks)
-    launch_miller1(scaled.as<u8>(), kind == 0 ? dp.as<u8>() : h.as<u8>(), fr.as<i32>(), n, s, ar, nullptr);
-    // stage 2: the block values, then the tree over them (its levels alternate between t0 and t1; the block values stay)
-    prof_mark("k_fq12_seg_prod_row");
-    rc = seg_prod_dev(fr.as<i32>(), nrec, nullptr, bplan, bblob.as<u8>(), bval.as<i32>(), nullptr, s);
-    if (rc) return rc;
-    prof_mark(nullptr);
-    const i32* src = bval.as<i32>();
-    i32* dst = t0.as<i32>();
-    for (size_t cur = B; cur > 1;) {
-        const size_t hf = (cur + 1) / 2;
-        launch_prod_level(src, dst, cur, hf, s);
-        src = dst; dst = dst == t0.as<i32>() ? t1.as<i32>() : t0.as<i32>();
-        cur = hf;
-    }
-    HIPCHK(hipGetLastError());
-    int bad = 0, sum_inf = 0, verdict = 0;
-    HIPCHK(hipMemcpyAsync(&bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    // stage 3: sum r_i sig_i and its Miller loop on the side stream, the tail
-    SigSide ss;
-    {
-        HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
-        OnStream on(st);
-        rc = rlc_sig_sum(kind, ds.as<u8>(), dr.as<u64>(), n, sum.as<u8>(), sflag.as<i32>());
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(&sum_inf, sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        rc = sig_side_start_dev(kind, sum.as<u8>(), ss);
-        if (rc) return rc;
-    }
-    rc = aggregate_tail(kind, src, ss, &verdict);                          // waits for the side stream; synchronises s
-    if (rc) return rc;
-    const bool held = verdict == 1 && bad == 0 && sum_inf == 0;
-    HIPCHK(hipMemsetAsync(dok.p, 1, n, s));
-    size_t nre = 0;
-    std::vector<uint32_t> pos;
-    if (!held) {
-        // stages 4 and 5: S_b for every block, the B signature-side Miller values in the layout a Pairing call of B tuples takes, each times
-        // its block value, the final exponentiations in the layout a pairing product of B items takes, one byte per block
-        const int sig_group = k.sig_bytes == 192 ? 2 : 1;
-        SegPlan splan;
-        std::vector<uint8_t> fail;
-        try { segsum_plan(lp.tup_off.data(), B, segsum_chunk_of(n), splan, 64, 1); fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-        const size_t bload = route_load(B);
-        const Layout fe = pprod_fe_layout(B, bload);
-        DBuf sb, sbinf, g1, g2, bbad, fs, prod, vals, one, dfail;
-        HIPCHK(sb.alloc((size_t)k.sig_bytes * B)); HIPCHK(sbinf.alloc(B)); HIPCHK(g1.alloc((size_t)96 * B)); HIPCHK(g2.alloc((size_t)192 * B)); HIPCHK(bbad.alloc(B));
-        HIPCHK(fs.alloc(sizeof(i32) * words * B)); HIPCHK(prod.alloc(fe == Layout::wave ? 576 * B : sizeof(i32) * words * B)); HIPCHK(vals.alloc(576 * B));
-        HIPCHK(one.alloc(B)); HIPCHK(dfail.alloc(B));
-        rc = segsum_dev(sig_group, false, ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, dr.as<u64>());
-        if (rc) return rc;
-        prof_mark("k_locate_sig_pairs");
-        hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(B)), dim3(WG), 0, s, kind == 0 ? 0 : 1, (const u8*)sb.as<u8>(), (const u8*)sbinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
-                           g1.as<u8>(), g2.as<u8>(), bbad.as<u8>(), B);
-        launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), B, s, pairing_layout(0, B, t, bload));
-        prof_mark("k_fq12_mul_pairs_row");
-        hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(B)), dim3(WG), 0, s, (const i32*)bval.as<i32>(), (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
-                           fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, B);
-        final_exp_values(fe, prod.p, vals.as<u64>(), one.p, B, s);
-        prof_mark("k_locate_block_fail");
-        hipLaunchKernelGGL(k_locate_block_fail, dim3(rblocks(B)), dim3(WG), 0, s, (const u8*)flags.as<u8>(), (const u8*)sflags.as<u8>(), n, lp.block, (const u8*)bbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), B);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, B, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-        // stage 6: the tuples of the failing blocks, dense; verify_batch's pair stage routed by their count; the verdicts back
-        try { blsmi_route::locate_positions(lp, fail.data(), pos); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-        nre = pos.size();
-    }
-    if (nre) {
-        DBuf dpos, hd, pd, sd, id, okd, f;
-        HIPCHK(dpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hd.alloc((size_t)k.h_bytes * nre)); HIPCHK(pd.alloc((size_t)k.pk_bytes * nre)); HIPCHK(sd.alloc((size_t)k.sig_bytes * nre));
-        HIPCHK(id.alloc(nre)); HIPCHK(okd.alloc(nre)); HIPCHK(f.alloc(sizeof(i32) * words * nre));
-        HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
-        auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) {
-            const u32 q = (u32)(bytes / 16);
-            hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)dpos.as<u32>(), to.as<uint4>(), q, nre);
-        };
-        prof_mark("k_gather_records16");
-        gather(h, hd, k.h_bytes); gather(dp, pd, k.pk_bytes); gather(ds, sd, k.sig_bytes);
-        if (inf_flags) hipLaunchKernelGGL(k_gather_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)di.as<u8>(), (const u32*)dpos.as<u32>(), id.as<u8>(), nre);
-        prof_mark(nullptr);
-        const VerifyRoute vr = verify_route(kind, nre, false, false, t, route_load(nre));
-        rc = verify_pair_stage(kind, hd.as<u8>(), pd.p, sd.p, inf_flags ? id.p : nullptr, okd.p, f.as<i32>(), nre, s, vr);
-        if (rc) return rc;
-        prof_mark("k_scatter_bytes");
-        hipLaunchKernelGGL(k_scatter_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)okd.as<u8>(), (const u32*)dpos.as<u32>(), dok.as<u8>(), nre);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    if (ok) HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, n);
-    if (combined) *combined = held ? 1 : 0;
-    if (rechecked) *rechecked = nre;
-    return BLSMI_OK;
-}
-#define JACP(p) reinterpret_cast<const uint8_t*>(p)
-}  // namespace
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(0, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                                   const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(1, msgs, off, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags,
-                                                               const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked);
-}
-BLSMI_API int blsmi_g2pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
-                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(0, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_batch_rlc_locate_jac(const uint8_t* msgs, const uint64_t* off, const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
-                                                       uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(1, msgs, off, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
-}
-BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint64_t* pks, const uint64_t* sigs, const uint64_t* scalars, size_t block,
-                                                                   uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
-    return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
-}
-#undef JACP

@@ -1192,22 +1192,22 @@ def _msg_idx(msg_idx, n):
     return ix, (ix.ctypes.data_as(_u32p) if n else None)
 
 
-def _verify_batch_rlc_grouped(name, kind, jac, msgs, msg_idx, pks, sigs, inf_flags, scalars, domain8=None):
-    """-> (ok, bitmap, combined); msgs: the table of d messages, msg_idx: n indices into it"""
+def _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8):
+    """The arguments the grouped and the block-locating forms pass alike, for n tuples over the messages `msgs` -> (head, mid, pr, ok, bitmap,
+    comb, keep): head = the messages and their offsets (or the domain), mid = keys, signatures (and infinity flags), pr = the scalars; ok, bitmap
+    and comb receive the results; keep holds the arrays the pointers refer to."""
     pkb, sgb = (192, 96) if kind == 0 else (96, 192)
-    d = len(msgs)
-    n = len(msg_idx)
-    ix, pix = _msg_idx(msg_idx, n)
     if domain8 is None:
         buf, off = _msgs(msgs)
         head = (_p8(buf), off.ctypes.data_as(_u64p))
     else:
-        buf = _u8(b"".join(bytes(m) for m in msgs) or b"\0" * 32, 32 * max(d, 1))
-        dom = _u8(domain8, 8)
-        head = (_p8(buf), _p8(dom))
+        buf = _u8(b"".join(bytes(m) for m in msgs) or b"\0" * 32, 32 * max(len(msgs), 1))
+        off = _u8(domain8, 8)
+        head = (_p8(buf), _p8(off))
     if jac:
         p, pp = _j64(pks, pkb // 2 * 3 * n)
         s, ps = _j64(sigs, sgb // 2 * 3 * n)
+        f = None
         mid = (pp, ps)
     else:
         p, s = _u8(pks, pkb * n), _u8(sigs, sgb * n)
@@ -1216,8 +1216,15 @@ def _verify_batch_rlc_grouped(name, kind, jac, msgs, msg_idx, pks, sigs, inf_fla
     r, pr = _scalars(scalars, n)
     ok = np.zeros(n, dtype=np.uint8)
     bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
-    comb = C.c_int(0)
-    _check(_fn_0_11(name)(*head, d, pix, *mid, pr, _p8(ok), _p8(bitmap), n, C.byref(comb)), name[len("blsmi_"):])
+    return head, mid, pr, ok, bitmap, C.c_int(0), (buf, off, p, s, f, r)
+
+
+def _verify_batch_rlc_grouped(name, kind, jac, msgs, msg_idx, pks, sigs, inf_flags, scalars, domain8=None):
+    """-> (ok, bitmap, combined); msgs: the table of d messages, msg_idx: n indices into it"""
+    n = len(msg_idx)
+    ix, pix = _msg_idx(msg_idx, n)
+    head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
+    _check(_fn_0_11(name)(*head, len(msgs), pix, *mid, pr, _p8(ok), _p8(bitmap), n, C.byref(comb)), name[len("blsmi_"):])
     return ok.astype(bool), bitmap, comb.value
 
 
@@ -1342,30 +1349,11 @@ ARGTYPES_0_12 = {
 
 def _verify_batch_rlc_locate(name, kind, jac, msgs, pks, sigs, inf_flags, scalars, block, domain8=None):
     """-> (ok, bitmap, combined, rechecked)"""
-    pkb, sgb = (192, 96) if kind == 0 else (96, 192)
     n = len(msgs)
     block = int(block)
     if block < 0:
         raise ValueError("block must not be negative")
-    if domain8 is None:
-        buf, off = _msgs(msgs)
-        head = (_p8(buf), off.ctypes.data_as(_u64p))
-    else:
-        buf = _u8(b"".join(bytes(m) for m in msgs) or b"\0" * 32, 32 * max(n, 1))
-        dom = _u8(domain8, 8)
-        head = (_p8(buf), _p8(dom))
-    if jac:
-        p, pp = _j64(pks, pkb // 2 * 3 * n)
-        s, ps = _j64(sigs, sgb // 2 * 3 * n)
-        mid = (pp, ps)
-    else:
-        p, s = _u8(pks, pkb * n), _u8(sigs, sgb * n)
-        f = _u8(inf_flags, n) if inf_flags is not None else None
-        mid = (_p8(p), _p8(s), _p8(f))
-    r, pr = _scalars(scalars, n)
-    ok = np.zeros(n, dtype=np.uint8)
-    bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
-    comb = C.c_int(0)
+    head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
     rechecked = C.c_size_t(0)
     fn = getattr(_lib(), name)
     fn.argtypes = ARGTYPES_0_12[name]

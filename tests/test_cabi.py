@@ -42,7 +42,7 @@ def test_product_never_touches_the_oracle():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for dirpath, _, files in os.walk(os.path.join(root, "bls_amd")):
         for f in files:
-            if f.endswith((".py", ".hip", ".cuh", ".inc", ".h")):
+            if f.endswith((".py", ".hip", ".cuh", ".inc", ".h", ".hpp")):
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "refcpu" not in txt and "pyref" not in txt and "from oracle" not in txt and "import oracle" not in txt, f
 

@@ -170,7 +170,7 @@ def test_only_the_table_reads_an_option_s_variable():
                "BLSMI_SHARDS", "BLSMI_SHARD_MIN", "BLSMI_ARENA_KEEP_MB", "BLSMI_FORCE_RCCL", "BLSMI_DEVICE_ALIAS"}
     csrc = os.path.join(ROOT, "bls_amd", "csrc")
     for f in sorted(os.listdir(csrc)):
-        if not f.endswith((".hip", ".inc", ".h", ".cuh")):
+        if not f.endswith((".hip", ".inc", ".h", ".hpp", ".cuh")):
             continue
         text = "\n".join(l.split("//")[0] for l in open(os.path.join(csrc, f), errors="ignore").read().splitlines())
         for arg in re.findall(r"\bgetenv\(([^)]*)\)", text):
