@@ -137,7 +137,7 @@ int blsmi_prefer_cpu(int shape, size_t n);
  * BLSMI_RCCL_PATH (the librccl to dlopen when several devices are driven -- a Go binary has no torch that maps one), BLSMI_ARENA_KEEP_MB,
  * BLSMI_LAT_MAX / BLSMI_QUAD_MAX / BLSMI_QUAD_MIN (layout hand-overs; also blsmi_set_latency_threshold / _quad_threshold), BLSMI_MUL_GENERIC,
  * BLSMI_COMBINE_MAX / _WAIT_US / _INFLIGHT / _DEBUG (merging of concurrent one-tuple Verify calls).  A/B switches between code paths with
- * identical results: BLSMI_LAYOUT, BLSMI_GEN_LINES, BLSMI_HASH_G1_SPLIT, BLSMI_HASH_G2_PAIR, BLSMI_HASH_G2_PAIR_REDO_EVERY, BLSMI_COFAC2_PAIR,
+ * identical results (held to the oracle by tests/test_gpu_startup_switches.py): BLSMI_LAYOUT, BLSMI_GEN_LINES, BLSMI_HASH_G1_SPLIT, BLSMI_HASH_G2_PAIR, BLSMI_HASH_G2_PAIR_REDO_EVERY, BLSMI_COFAC2_PAIR,
  * BLSMI_SWU_WAVE_MAX, BLSMI_SIG_SIDE_MAX, BLSMI_SIDE_MAX, BLSMI_FIXED_WAVE_MAX, BLSMI_MSM_BUCKET_MIN, and the ones that can ALSO be
  * switched while running through blsmi_set_option(name, value) (as the thresholds above: every call reads every option ONCE, when it starts,
  * so a change applies to the calls that start after it and never to part of a call in flight):
