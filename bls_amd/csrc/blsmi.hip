@@ -319,6 +319,16 @@ inline const Tuning& tune() { return tl_ctx->tune; }
 inline size_t route_load(size_t n) { return crowded(n, tune()) ? call_load(n) : 0; }
 inline bool mul_subgroup() { return !tl_mul_any && tune().mul_subgroup; }
 inline u32 lat_lds_bytes(size_t prog_offset) { u32 nslot; memcpy(&nslot, blsmi_lat_blob + prog_offset + 8, 4); return nslot * 80; }   // k_lat.hip: SLOT_WORDS * 4
+// One launch of a level program (k_lat.hip): n waves, wave t on item t.  The operands by the names the programs know them by (gen_lat.py);
+// what a program does not read stays empty.  A few programs read a COUNT where the others read a stride: lat_count says so at the call site.
+struct LatBuf { const void* p = nullptr; size_t stride = 0; };
+struct LatArgs { LatBuf b0, b1, b2, b3; const void* flags = nullptr; void* ok = nullptr; void* out = nullptr; };
+inline LatBuf lat_count(size_t count, const void* p = nullptr) { return {p, count}; }
+inline void launch_lat(size_t prog_offset, hipStream_t s, const LatArgs& a, size_t n) {
+    hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog_offset), s, (const u8*)g_gens.lat + prog_offset,
+                       (const u8*)a.b0.p, a.b0.stride, (const u8*)a.b1.p, a.b1.stride, (const u8*)a.b2.p, a.b2.stride, (const u8*)a.b3.p, a.b3.stride,
+                       (const u8*)a.flags, (u8*)a.ok, (u64*)a.out, n);
+}
 // ---- the environment is read ONCE, at initialisation (under g_mu), never from an entry point ---------------------------------------
 // getenv racing a setenv in another thread is undefined (glibc), and a variable read per call silently changes what a concurrent caller
 // gets.  load_env reads the options' variables (apply_env, route.h: one reader for every row of the table) and the process's
@@ -745,9 +755,7 @@ static int pairing_dev(const void* d_g1, const void* d_g2, void* d_out, size_t n
     if (lay == Layout::wave) {   // small call: one pairing per wave (k_lat.hip; pairing1s: its squaring runs unrolled, A/B partner), MillerLoop: the reference's steps
         const size_t prog = mode ? (size_t)LAT_MILLER1X_OFFSET : tune().lat_rolled ? (size_t)LAT_PAIRING1_OFFSET : (size_t)LAT_PAIRING1S_OFFSET;
         prof_mark(mode ? "k_lat:miller1x" : prog == LAT_PAIRING1_OFFSET ? "k_lat:pairing1" : "k_lat:pairing1s");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog,
-                           (const u8*)d_g1, (size_t)96, (const u8*)d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, (u64*)d_out, n);
+        launch_lat(prog, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = d_out}, n);
     } else {
         HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
         i32* f = reinterpret_cast<i32*>(g_ws.p);
@@ -916,9 +924,7 @@ BLSMI_API int blsmi_final_exponentiation_batch(const uint64_t* in, uint64_t* out
     HIPCHK(hipMemcpyAsync(i.p, in, 576 * n, hipMemcpyHostToDevice, g_stream));
     const Layout lay = final_exp_layout(n, tune(), route_load(n));
     if (lay == Layout::wave)                                               // small call: one final exponentiation per wave (k_lat.hip)
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_FINALEXP1_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_FINALEXP1_OFFSET,
-                           (const u8*)i.p, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, o.as<u64>(), n);
+        launch_lat(LAT_FINALEXP1_OFFSET, g_stream, {.b0 = {i.p, 576}, .out = o.p}, n);
     else {                                                                 // a few thousand values: sixteen lanes per value (k_pairing_row.hip), 1.2 ms up to 4 096
         hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, i.as<u64>(), f.as<i32>(), n);
         if (lay == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), o.as<u64>(), n, 0);
@@ -1028,9 +1034,7 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
         DBuf good, rec; HIPCHK(good.alloc(m, s)); HIPCHK(rec.alloc(64 * m, s));
         hipLaunchKernelGGL(k_glv_recode, dim3(nblocks(m)), dim3(WG), 0, s, d_scalars, PB == 96 ? 1 : 2, rec.as<u8>(), m);
         prof_mark(PB == 96 ? "k_lat:mul1" : "k_lat:mul2");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)m), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog, base, stride,
-                           (const u8*)rec.as<u8>(), (size_t)64, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, good.as<u8>(), reinterpret_cast<u64*>(d_out), m);
+        launch_lat(prog, s, {.b0 = {base, stride}, .b1 = {rec.p, 64}, .ok = good.p, .out = d_out}, m);
         prof_mark(nullptr);
         hipLaunchKernelGGL(k_mul_finish, dim3(nblocks(m)), dim3(WG), 0, s, (const u8*)good.as<u8>(), base, stride, PB / 4, d_out, d_inf, m);
         HIPCHK(hipGetLastError());
@@ -1149,22 +1153,18 @@ static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, si
         // few points: every addition of the tree as a level program, one per wave (k_lat.hip: sum0 / sum1 / sumfin; complete
         // projective formulas, two product levels per addition) -- ~10 us a level instead of ~70-140
         const size_t p0 = W == 3 ? LAT_SUM0_1_OFFSET : LAT_SUM0_2_OFFSET, p1 = W == 3 ? LAT_SUM1_1_OFFSET : LAT_SUM1_2_OFFSET, pf = W == 3 ? LAT_SUMFIN_1_OFFSET : LAT_SUMFIN_2_OFFSET;
-        const u8* L = (const u8*)g_gens.lat;
         prof_mark("k_lat:sum");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)half), dim3(64), lat_lds_bytes(p0), s, L + p0, d_pts, (size_t)PB, d_inf, (size_t)0, (const u8*)nullptr, half,
-                           (const u8*)nullptr, n, (const u8*)nullptr, (u8*)nullptr, b0.as<u64>(), half);
+        launch_lat(p0, s, {.b0 = {d_pts, PB}, .b1 = {d_inf, 0}, .b2 = lat_count(half), .b3 = lat_count(n), .out = b0.p}, half);   // sum0: pairs of the n points
         i32* src = b0.as<i32>(); i32* dst = b1.as<i32>();
         size_t cur = half;
         while (cur > 1) {
             const size_t h = (cur + 1) / 2;
-            hipLaunchKernelGGL(k_lat, dim3((unsigned)h), dim3(64), lat_lds_bytes(p1), s, L + p1, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                               (const u8*)nullptr, h, reinterpret_cast<const u8*>(src), cur, (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(dst), h);
+            launch_lat(p1, s, {.b2 = lat_count(h), .b3 = lat_count(cur, src), .out = dst}, h);   // sum1: pairs of the cur partial sums at src
             std::swap(src, dst);
             cur = h;
         }
         DBuf good; HIPCHK(good.alloc(1, s));
-        hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(pf), s, L + pf, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (size_t)0, reinterpret_cast<const u8*>(src), (size_t)1, (const u8*)nullptr, good.as<u8>(), reinterpret_cast<u64*>(d_out), (size_t)1);
+        launch_lat(pf, s, {.b3 = lat_count(1, src), .ok = good.p, .out = d_out}, 1);
         hipLaunchKernelGGL(k_good_to_flag, dim3(1), dim3(WG), 0, s, (const u8*)good.as<u8>(), d_out_inf);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
@@ -1438,9 +1438,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
         const size_t prog = W == 3 ? LAT_MSMFIN1_OFFSET : LAT_MSMFIN2_OFFSET;
         DBuf good; HIPCHK(good.alloc(1, s));
         prof_mark(W == 3 ? "k_lat:msmfin1" : "k_lat:msmfin2");
-        hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, reinterpret_cast<const u8*>(src), nrec,
-                           (const u8*)nullptr, good.as<u8>(), reinterpret_cast<u64*>(d_out), (size_t)1);
+        launch_lat(prog, s, {.b3 = lat_count(nrec, src), .ok = good.p, .out = d_out}, 1);
         hipLaunchKernelGGL(k_good_to_flag, dim3(1), dim3(WG), 0, s, (const u8*)good.as<u8>(), d_flag);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());

@@ -68,12 +68,8 @@ int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum,
 // into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
 int sig_side_start_dev(int kind, const u8* d_sig, SigSide& ss) {
     HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
-    const u8* tp = kind == 0 ? d_sig : g_gens.g1;
-    const u8* tq = kind == 0 ? g_gens.g2 : d_sig;
     prof_mark("k_lat:miller1rawn");
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
-                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(ss.ml.p), (size_t)1);
+    launch_sig_miller(sig_pair(kind, d_sig, 0), ss.ml.p, 1, g_stream);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(tl_ctx->join[0], g_stream));
@@ -108,20 +104,22 @@ int rlc_scalars_and_ok(RlcHostScratch& hs, const uint64_t*& scalars, uint8_t*& o
 struct RlcCall {
     int kind = 0;
     Kind k{};
-    size_t n = 0, msg_bytes = 0, off_bytes = 0;
+    size_t n = 0;
     bool has_inf = false;                                                  // the caller passed infinity flags (rlc_upload_keys)
-    DBuf dm, doff, dp, ds, di, dr, dok, flags, any, sum, sflag;
+    DevMsgs msgs;                                                          // (of the messages that are hashed: n, or a grouped call's d')
+    DBuf dp, ds, di, dr, dok, flags, any, sum, sflag;
     SigSide ss;
     int bad = 0, sum_inf = 0, verdict = 0;
     const void* inf() const { return has_inf ? di.p : nullptr; }
     // the equation holds, nothing is flagged, the signatures' sum is a finite point: every verdict is 1
     bool held() const { return verdict == 1 && bad == 0 && sum_inf == 0; }
 };
-// the context's side streams, and the buffers for n tuples whose messages / offsets take msg_bytes / off_bytes on the device
-int rlc_begin(RlcCall& c, int kind, size_t n, size_t msg_bytes, size_t off_bytes) {
-    c.kind = kind; c.k = kind_of(kind); c.n = n; c.msg_bytes = msg_bytes; c.off_bytes = off_bytes;
+// the context's side streams, and the buffers for n tuples over nmsg messages with the host offsets off_or_domain
+int rlc_begin(RlcCall& c, int kind, size_t n, const void* off_or_domain, size_t nmsg) {
+    c.kind = kind; c.k = kind_of(kind); c.n = n; c.msgs = DevMsgs(kind, off_or_domain, nmsg);
     HIPCHK(tl_ctx->ensure_aux());
-    HIPCHK(c.dm.alloc(msg_bytes)); HIPCHK(c.doff.alloc(off_bytes)); HIPCHK(c.dp.alloc((size_t)c.k.pk_bytes * n)); HIPCHK(c.ds.alloc((size_t)c.k.sig_bytes * n));
+    { int rc = c.msgs.alloc(); if (rc) return rc; }
+    HIPCHK(c.dp.alloc((size_t)c.k.pk_bytes * n)); HIPCHK(c.ds.alloc((size_t)c.k.sig_bytes * n));
     HIPCHK(c.di.alloc(n)); HIPCHK(c.dr.alloc(sizeof(uint64_t) * n)); HIPCHK(c.dok.alloc(n)); HIPCHK(c.flags.alloc(n)); HIPCHK(c.any.alloc(sizeof(int)));
     HIPCHK(c.sum.alloc(c.k.sig_bytes)); HIPCHK(c.sflag.alloc(sizeof(i32)));
     return BLSMI_OK;
@@ -134,8 +132,7 @@ int rlc_upload_start(RlcCall& c, const uint8_t* sigs, const uint64_t* r, const v
     { int rc = upload_points(c.k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, c.ds.p, c.n, st); if (rc) return rc; }
     HIPCHK(hipEventRecord(tl_ctx->join[1], st));
     HIPCHK(hipMemcpyAsync(c.dr.p, r, sizeof(uint64_t) * c.n, hipMemcpyHostToDevice, s));
-    if (c.msg_bytes) HIPCHK(hipMemcpyAsync(c.dm.p, msgs, c.msg_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c.doff.p, off_or_domain, c.off_bytes, hipMemcpyHostToDevice, s));
+    { int rc = c.msgs.copy(msgs, off_or_domain, s); if (rc) return rc; }
     HIPCHK(hipEventRecord(tl_ctx->fork, s));
     return BLSMI_OK;
 }
@@ -178,7 +175,7 @@ int rlc_signature_side(RlcCall& c) {
 int rlc_check_total(RlcCall& c, const i32* d_prod, bool sig_side = true) {
     HIPCHK(hipMemcpyAsync(&c.bad, c.any.p, sizeof(int), hipMemcpyDeviceToHost, g_stream));
     if (sig_side) { int rc = rlc_signature_side(c); if (rc) return rc; }
-    return aggregate_tail(c.kind, d_prod, c.ss, &c.verdict);
+    return aggregate_tail(d_prod, c.ss, &c.verdict);
 }
 // the per-tuple verdicts of verify_batch for all n tuples, from the inputs on the device and their hash points d_h
 int rlc_fallback_all(RlcCall& c, const u8* d_h, const VerifyRoute& vr) {
@@ -207,7 +204,7 @@ int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, cons
     const size_t words = (size_t)12 * NL;
     hipStream_t s = g_stream;
     RlcCall c;
-    int rc = rlc_begin(c, kind, n, kind == 2 ? 32 * n : (size_t)off_or_domain[n], kind == 2 ? 8 : sizeof(uint64_t) * (n + 1)); if (rc) return rc;
+    int rc = rlc_begin(c, kind, n, off_or_domain, n); if (rc) return rc;
     DBuf h, scaled, sinf, fr0, fr1, pc;
     HIPCHK(h.alloc((size_t)c.k.h_bytes * n)); HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n));
     rc = rlc_upload_start(c, sigs, r, msgs, off_or_domain, fmt); if (rc) return rc;
@@ -218,7 +215,7 @@ int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, cons
         const AggregateRoute ar = aggregate_route(kind, n, false, !powc, t, load);
         HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
         HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
-        int rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, ar.hash, !powc, powc ? c.any.as<int>() : nullptr);   // bad bit 1: a hash point the uncleared path does not cover
+        int rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), n, s, ar.hash, !powc, powc ? c.any.as<int>() : nullptr);   // bad bit 1: a hash point the uncleared path does not cover
         if (rc) return rc;
         cleared = !powc;
         if (first) { rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc; }
@@ -240,7 +237,7 @@ int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, cons
     else {
         // the per-tuple verdicts of verify_batch, from the inputs on the device (the hash again where h holds uncleared points)
         const VerifyRoute vr = verify_route(kind, n, false, false, t, load);
-        if (!cleared) { rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
+        if (!cleared) { rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
         rc = rlc_fallback_all(c, h.as<u8>(), vr); if (rc) return rc;
     }
     if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, s, (const u8*)c.dok.as<u8>(), d_bitmap_slice, n);   // (a split call: the bitmap comes together on the devices)
@@ -373,7 +370,7 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
     const size_t words = (size_t)12 * NL;
     hipStream_t s = g_stream;
     RlcCall c;
-    rc = rlc_begin(c, kind, n, cm.size(), kind == 2 ? 8 : sizeof(uint64_t) * (dg + 1));   // the d' messages some tuple refers to
+    rc = rlc_begin(c, kind, n, kind == 2 ? (const void*)off_or_domain : (const void*)coff.data(), dg);   // the d' messages some tuple refers to
     if (rc) return rc;
     const Kind& k = c.k;
     SegPlan plan;
@@ -384,7 +381,7 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
     HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
     rc = rlc_upload_start(c, sigs, scalars, cm.data(), kind == 2 ? (const void*)off_or_domain : (const void*)coff.data(), fmt); if (rc) return rc;
     HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
-    rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), dg, s, ar.hash);
+    rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), dg, s, ar.hash);
     if (rc) return rc;
     rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(dx.p, gp.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));   // the plan's permutation, behind the keys
@@ -540,7 +537,7 @@ int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* 
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     const size_t B = lp.blocks(), half = (B + 1) / 2;
     RlcCall c;
-    rc = rlc_begin(c, kind, n, kind == 2 ? 32 * n : (size_t)off_or_domain[n], kind == 2 ? 8 : sizeof(uint64_t) * (n + 1)); if (rc) return rc;
+    rc = rlc_begin(c, kind, n, off_or_domain, n); if (rc) return rc;
     const Kind& k = c.k;
     DBuf h, scaled, sinf, sflags, fr, bval, t0, t1, bblob;
     HIPCHK(h.alloc((size_t)k.h_bytes * n)); HIPCHK(scaled.alloc((size_t)96 * n)); HIPCHK(sinf.alloc(n)); HIPCHK(sflags.alloc(n));
@@ -550,7 +547,7 @@ int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* 
     rc = rlc_upload_start(c, sigs, scalars, msgs, off_or_domain, fmt); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
-    rc = hash_dev(kind, c.dm.p, c.doff.p, h.as<u8>(), n, s, ar.hash);
+    rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), n, s, ar.hash);
     if (rc) return rc;
     rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
     rlc_flag_inputs(c);

@@ -54,9 +54,7 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
         else if (waves) hipLaunchKernelGGL(k_tai_g2_waves8, dim3((unsigned)n), dim3(512), 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, pts.as<u8>(), n);
         else hipLaunchKernelGGL(k_tai_g2_lanes8, dim3(nblocks(8 * n)), w, 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, pts.as<u8>(), n);
         prof_mark(kind == 0 ? "k_lat:hashfin1" : kind == 1 ? "k_lat:hashfin2" : "k_lat:cofac2");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog, (const u8*)pts.as<u8>(), rec,
-                           (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, good.as<u8>(), reinterpret_cast<u64*>(d_h), n);
+        launch_lat(prog, s, {.b0 = {pts.p, rec}, .ok = good.p, .out = d_h}, n);
         prof_mark("k_hash_redo");
         if (kind == 0) hipLaunchKernelGGL(k_hash_g1_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
         else if (kind == 1) hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
@@ -144,9 +142,7 @@ void launch_prod_level(const i32* src, i32* dst, size_t cur, size_t half, hipStr
     const bool lat = half <= tune().lat_max;
     prof_mark(lat ? "k_lat:mul12raw" : "k_fq12_prod_level");
     if (lat)                                                               // few products: one per wave (k_lat.hip, "mul12raw"), ~5 us instead of ~80
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)half), dim3(64), lat_lds_bytes(LAT_MUL12RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MUL12RAW_OFFSET,
-                           (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, half, reinterpret_cast<const u8*>(src), cur,
-                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(dst), half);
+        launch_lat(LAT_MUL12RAW_OFFSET, s, {.b2 = lat_count(half), .b3 = lat_count(cur, src), .out = dst}, half);
     else
         hipLaunchKernelGGL(k_fq12_prod_level, dim3(nblocks(half)), dim3(WG), 0, s, src, dst, cur, half);
     prof_mark(nullptr);
@@ -175,9 +171,7 @@ void launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_
     if (l == Layout::row)                                                  // a few thousand signers: one Miller loop per lane ROW (k_pairing_row.hip), n values as on the wave path
         hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, (size_t)96, d_g2, (size_t)192, f, n, (const i32*)nullptr, (size_t)0, n);
     else if (l == Layout::wave)                                            // small aggregate: one Miller loop per wave (any Miller value serves a product that is final-exponentiated)
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MILLER1RAW_OFFSET,
-                           d_g1, (size_t)96, d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
+        launch_lat(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
     else if (l == Layout::quad)                                            // mid-size aggregate: two consecutive tuples per lane QUAD (k_pairing_quad.hip)
         hipLaunchKernelGGL(k_miller1x2_quad, dim3(qblocks(m)), dim3(WG), 0, s, d_g1, d_g2, f, n, m);
     else if (l == Layout::pair)                                            // two consecutive tuples per lane pair, one 2-pair loop
@@ -195,20 +189,23 @@ void launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_
 // after: a stream whose enqueued work produces d_sigs (null: d_sigs is complete, or host_sigs is given and copied here, on the side stream)
 // sigs_jac: host_sigs are in-memory Jacobian records (converted into d_sigs on the side stream, blsmi.hip: upload_points)
 // side: the call's signature side (route.h: sig_side), wave or row
+// (P, Q) of the signature side's Miller loop: (sig_t, G2One) for g2pubs, (G1One, sig_t) for g1pubs, the signatures `stride` bytes apart (one
+// signature: 0); the generator is the same record for every t.  launch_sig_miller: MillerLoop(-P, Q) of n such pairs into f, one wave each
+// (program "miller1rawn"); the caller places its profile mark, or none on a side stream.
+struct SigPair { LatBuf P, Q; };
+inline SigPair sig_pair(int kind, const void* d_sigs, size_t stride) { return kind == 0 ? SigPair{{d_sigs, stride}, {g_gens.g2, 0}} : SigPair{{g_gens.g1, 0}, {d_sigs, stride}}; }
+inline void launch_sig_miller(const SigPair& sp, void* f, size_t n, hipStream_t st) { launch_lat(LAT_MILLER1RAWN_OFFSET, st, {.b0 = sp.P, .b1 = sp.Q, .out = f}, n); }
 int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host_sigs, i32* f, size_t n, hipStream_t after, bool sigs_jac = false) {
     const Kind k = kind_of(kind);
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t st = tl_ctx->aux[0];
     if (after) { HIPCHK(hipEventRecord(tl_ctx->fork, after)); HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0)); }
     if (host_sigs) { int rc = upload_points(k.sig_bytes, sigs_jac, host_sigs, d_sigs, n, st); if (rc) return rc; }
-    const u8* tp = kind == 0 ? (const u8*)d_sigs : g_gens.g1; const size_t sp = kind == 0 ? 96 : 0;
-    const u8* tq = kind == 0 ? g_gens.g2 : (const u8*)d_sigs; const size_t sq = kind == 0 ? 0 : 192;
+    const SigPair sp = sig_pair(kind, d_sigs, k.sig_bytes);
     if (side == Side::row)
-        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, tp, sp, tq, sq, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
+        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, (const u8*)sp.P.p, sp.P.stride, (const u8*)sp.Q.p, sp.Q.stride, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
     else
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), st, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
-                           tp, sp, tq, sq, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
+        launch_sig_miller(sp, f, n, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(tl_ctx->join[0], st));
     return BLSMI_OK;
@@ -251,12 +248,10 @@ int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_
         hipLaunchKernelGGL(k_final_exp_is_one_row, dim3(rblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
     } else if (r.side == Side::wave) {                                     // small call, the signature side already under way: one Miller loop, the product, the final exponentiation
         prof_mark("k_lat:verify1s");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_VERIFY1S_OFFSET), s, (const u8*)g_gens.lat + LAT_VERIFY1S_OFFSET,
-                           a1, (size_t)96, b1, (size_t)192, (const u8*)nullptr, (size_t)0, reinterpret_cast<const u8*>(f), n, (const u8*)d_inf, (u8*)d_ok, (u64*)nullptr, n);
+        launch_lat(LAT_VERIFY1S_OFFSET, s, {.b0 = {a1, 96}, .b1 = {b1, 192}, .b3 = lat_count(n, f), .flags = d_inf, .ok = d_ok}, n);   // b3: the n Miller values of the side stream
     } else if (r.layout == Layout::wave) {                                 // small call: one Verify per wave (k_lat.hip)
         prof_mark("k_lat:verify2");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_VERIFY2_OFFSET), s, (const u8*)g_gens.lat + LAT_VERIFY2_OFFSET,
-                           a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, (const u8*)d_inf, (u8*)d_ok, (u64*)nullptr, n);
+        launch_lat(LAT_VERIFY2_OFFSET, s, {.b0 = {a0, s0}, .b1 = {b0, t0}, .b2 = {a1, 96}, .b3 = {b1, 192}, .flags = d_inf, .ok = d_ok}, n);
     } else if (r.layout == Layout::row) {                                  // a few thousand tuples: sixteen lanes per tuple (k_pairing_row.hip)
         prof_mark("k_miller2_row");
         hipLaunchKernelGGL(k_miller2_row, dim3(rblocks(n)), w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
@@ -303,6 +298,30 @@ void pack_bitmap(const uint8_t* ok, uint8_t* bitmap, size_t n) {
     memset(bitmap, 0, (n + 7) / 8);
     for (size_t i = 0; i < n; i++) if (ok[i]) bitmap[i >> 3] |= (uint8_t)(1u << (i & 7));
 }
+// the n verdict bytes at d_ok back on the host -- in ok, or in a temporary for a caller who wants the bitmap alone --, s synchronised, the bitmap packed
+int fetch_verdicts(const void* d_ok, uint8_t* ok, uint8_t* ok_bitmap, size_t n, hipStream_t s) {
+    std::vector<uint8_t> tmp;
+    if (!ok) { tmp.resize(n); ok = tmp.data(); }
+    HIPCHK(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    if (ok_bitmap) pack_bitmap(ok, ok_bitmap, n);
+    return BLSMI_OK;
+}
+// The messages of n > 0 tuples and their offsets on the leased context's device (kind 2: n x 32 bytes and the 8-byte domain), sized from
+// the host's offsets: alloc takes the two buffers from the call's arena, copy enqueues the two uploads on s, upload does both
+struct DevMsgs {
+    DBuf m, off;
+    size_t msg_bytes = 0, off_bytes = 0;
+    DevMsgs() {}
+    DevMsgs(int kind, const void* off_or_domain, size_t n)
+        : msg_bytes(kind == 2 ? 32 * n : (size_t)static_cast<const uint64_t*>(off_or_domain)[n]), off_bytes(kind == 2 ? 8 : sizeof(uint64_t) * (n + 1)) {}
+    int alloc() { HIPCHK(m.alloc(msg_bytes)); HIPCHK(off.alloc(off_bytes)); return BLSMI_OK; }
+    int upload(const void* msgs, const void* off_or_domain, hipStream_t s) { int rc = alloc(); return rc ? rc : copy(msgs, off_or_domain, s); }
+    int copy(const void* msgs, const void* off_or_domain, hipStream_t s) const {
+        if (msg_bytes) HIPCHK(hipMemcpyAsync(m.p, msgs, msg_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(off.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, s));
+        return BLSMI_OK;
+    }
+};
 // body of a host-buffer batch verify; the caller holds a context lease (tl_ctx)
 // d_bitmap_slice (may be null): where this batch's packed verdict bits go on the lease's device (a shard of a split batch)
 int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sigs,
@@ -310,11 +329,10 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
                         const i32* prep_tables = nullptr, const uint32_t* prep_idx = nullptr, int fmt = 0) {
     if (n == 0) return BLSMI_OK;
     const Kind k = kind_of(kind);
-    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
-    DBuf dm, doff, dp, ds, di, dok;
+    DevMsgs dm(kind, off_or_domain, n); DBuf dp, ds, di, dok;
+    { int rc = dm.alloc(); if (rc) return rc; }
     // prepared keys (resident tables): `pks` is unused, the per-tuple table indices travel in its place
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc(prep_tables ? sizeof(uint32_t) * n : (size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
+    HIPCHK(dp.alloc(prep_tables ? sizeof(uint32_t) * n : (size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
     HIPCHK(di.alloc(n)); HIPCHK(dok.alloc(n));
     // messages first, so that the hash-to-curve kernel runs while the (pageable, host-blocking) copies of the keys
     // and signatures are still on their way
@@ -324,9 +342,9 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
     const VerifyRoute r = verify_route(kind, n, prep_tables != nullptr, true, tune(), route_load(n));
     const bool side = r.side != Side::none;
     if (side) { int rc = verify_sig_side_start(kind, r.side, ds.p, sigs, f.as<i32>(), n, nullptr, (fmt & FMT_SIG_JAC) != 0); if (rc) return rc; }
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream, r.hash);
+    int rc = dm.copy(msgs, off_or_domain, g_stream);
+    if (rc) return rc;
+    rc = hash_dev(kind, dm.m.p, dm.off.p, h.as<u8>(), n, g_stream, r.hash);
     if (rc) return rc;
     if (prep_tables) { if (prep_idx) HIPCHK(hipMemcpyAsync(dp.p, prep_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, g_stream)); }
     else { rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); if (rc) return rc; }   // (in-memory points: ToAffine on the device, after the hash)
@@ -336,12 +354,7 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
     rc = verify_pair_stage(kind, h.as<u8>(), prep_tables ? nullptr : dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, g_stream, r, prep_tables ? &prep : nullptr);
     if (rc) return rc;
     if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, g_stream, (const u8*)dok.as<u8>(), d_bitmap_slice, n);
-    std::vector<uint8_t> tmp;
-    uint8_t* dst = ok;
-    if (!dst) { tmp.resize(n); dst = tmp.data(); }
-    HIPCHK(hipMemcpyAsync(dst, dok.p, n, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-    if (ok_bitmap) pack_bitmap(dst, ok_bitmap, n);
-    return BLSMI_OK;
+    return fetch_verdicts(dok.p, ok, ok_bitmap, n, g_stream);
 }
 
 // ---- collectives of a split batch -------------------------------------------------------------------------------
@@ -693,20 +706,14 @@ int aggregate_shard_dev(int kind, const void* d_msgs, const void* d_off_or_domai
     HIPCHK(hipMemcpyAsync(bad, any.p, sizeof(int), hipMemcpyDeviceToHost, s));
     return BLSMI_OK;                                                      // temporaries are released in stream order
 }
-// Host-buffer form of one shard on the leased context: copies in, runs the shard, synchronises.  d_dup (may be null): a
-// device int that receives the duplicate-message verdict of this shard's messages (k_util.hip), checked on the device
-// while the messages are there anyway.
-int aggregate_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, size_t n, i32* d_out, int* bad, int* d_dup = nullptr, bool g1_clear = true, int fmt = 0) {
+// Host-buffer form of one shard on the leased context: copies in, runs the shard, synchronises.
+int aggregate_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, size_t n, i32* d_out, int* bad, bool g1_clear = true, int fmt = 0) {
     const Kind k = kind_of(kind);
-    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n];
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
-    DBuf dm, doff, dp;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
-    if (d_dup && kind != 2) { if (blsmi_util::dup_check_async(dm.p, doff.p, n, dup_key()[0], dup_key()[1], d_dup, g_stream, [](size_t b) { return tl_ctx->arena.alloc(b); }) != 0) return BLSMI_E_HIP; }
+    DevMsgs dm(kind, off_or_domain, n); DBuf dp;
+    HIPCHK(dp.alloc((size_t)k.pk_bytes * n));
+    { int rc = dm.upload(msgs, off_or_domain, g_stream); if (rc) return rc; }
     hipStream_t s = g_stream;
-    int rc = aggregate_shard_dev(kind, dm.p, doff.p, dp.as<u8>(), n, d_out, bad, s, [&]() -> int {
+    int rc = aggregate_shard_dev(kind, dm.m.p, dm.off.p, dp.as<u8>(), n, d_out, bad, s, [&]() -> int {
         return upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
     }, nullptr, g1_clear);
     if (rc) return rc;
@@ -725,11 +732,44 @@ inline bool agg_pow_wanted(int kind, size_t n, const Tuning& t) { return kind ==
 // d_prod (180 words, device representation) -> d_out = d_prod^(1 - x), on g_stream
 int aggregate_pow_c(const i32* d_prod, i32* d_out) {
     prof_mark("k_lat:powc12raw");
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_POWC12RAW_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_POWC12RAW_OFFSET,
-                       (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)d_prod, (size_t)0,
-                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(d_out), (size_t)1);
+    launch_lat(LAT_POWC12RAW_OFFSET, g_stream, {.b3 = {d_prod, 0}, .out = d_out}, 1);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+// The tuple side of an aggregate with its uncleared-hash route decided in ONE place.  run(g1_clear, &bad) enqueues the shard(s), synchronises
+// and leaves the bits of aggregate_shard_dev in bad.  powc (agg_pow_wanted): the shards pair the hash points before their cofactor clearing;
+// where they met a message that route does not cover (bit 1; hash.cuh: swu_finish_g1) and no key at infinity has settled the verdict anyway,
+// they run once more over the cleared points and powc comes back false.  powc still true: the product wants aggregate_pow_c.
+template <class Run>
+int run_tuple_side(bool& powc, int* bad, const Run& run) {
+    *bad = 0;
+    int rc = run(!powc, bad);
+    if (rc == BLSMI_OK && (*bad & 3) == 2) { powc = false; *bad = 0; rc = run(true, bad); }
+    return rc;
+}
+// ... for a product that lies on the leased context: prod ends as the value the tail takes, raised to 1 - x where the route asks for it
+// (nothing more is enqueued once *bad & 1 says that the verdict is 0)
+template <class Run>
+int tuple_side_product(bool powc, DBuf& prod, int* bad, const Run& run) {
+    int rc = run_tuple_side(powc, bad, run);
+    if (rc || (*bad & 1) || !powc) return rc;
+    DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * 12 * NL));
+    rc = aggregate_pow_c(prod.as<i32>(), pc.as<i32>());
+    prod = pc;
+    return rc;
+}
+// one wave of a tail program ("aggtail", "aggtail2") on g_stream and its verdict byte fetched into *ok; synchronises.  a: all operands but ok
+int tail_verdict(size_t prog, const char* mark, LatArgs a, int* ok) {
+    DBuf dokb; HIPCHK(dokb.alloc(1));
+    a.ok = dokb.p;
+    prof_mark(mark);
+    launch_lat(prog, g_stream, a, 1);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    uint8_t flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, dokb.p, 1, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
+    *ok = flag;
     return BLSMI_OK;
 }
 // The end of every VerifyAggregate, on the leased context: e(sig-side) == FE(prod) <=> FE(MillerLoop(-P, Q) * prod) == 1 with
@@ -738,21 +778,10 @@ int aggregate_pow_c(const i32* d_prod, i32* d_out) {
 // exponentiations (~30 ms).  d_prod: the product of the tuple-side Miller loops (180 words on this device).
 int aggregate_tail(int kind, const i32* d_prod, const uint8_t* sig, int* ok, int fmt = 0) {
     const Kind k = kind_of(kind);
-    DBuf dsig, dokb;
-    HIPCHK(dsig.alloc(k.sig_bytes)); HIPCHK(dokb.alloc(1));
+    DBuf dsig; HIPCHK(dsig.alloc(k.sig_bytes));
     { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
-    const u8* tp = kind == 0 ? dsig.as<u8>() : g_gens.g1;
-    const u8* tq = kind == 0 ? g_gens.g2 : dsig.as<u8>();
-    prof_mark("k_lat:aggtail");
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_AGGTAIL_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_AGGTAIL_OFFSET,
-                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)d_prod, (size_t)0,
-                       (const u8*)nullptr, dokb.as<u8>(), (u64*)nullptr, (size_t)1);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    uint8_t flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, dokb.p, 1, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-    *ok = flag;
-    return BLSMI_OK;
+    const SigPair sp = sig_pair(kind, dsig.p, 0);
+    return tail_verdict(LAT_AGGTAIL_OFFSET, "k_lat:aggtail", {.b0 = sp.P, .b1 = sp.Q, .b3 = {d_prod, 0}}, ok);
 }
 // The same tail in two pieces for calls that run on ONE context: the signature side's Miller loop does not depend on the tuple side, so it
 // starts on a side stream BEFORE the messages are hashed (sig_side_start: program "miller1rawn", one wave, ~0.7 ms, hidden behind the
@@ -765,33 +794,79 @@ int sig_side_start(int kind, const uint8_t* sig, SigSide& ss, int fmt = 0) {
     hipStream_t st = tl_ctx->aux[0];
     HIPCHK(ss.sig.alloc(k.sig_bytes)); HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
     { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, ss.sig.p, 1, st); if (rc) return rc; }
-    const u8* tp = kind == 0 ? ss.sig.as<u8>() : g_gens.g1;
-    const u8* tq = kind == 0 ? g_gens.g2 : ss.sig.as<u8>();
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_MILLER1RAWN_OFFSET), st, (const u8*)g_gens.lat + LAT_MILLER1RAWN_OFFSET,
-                       tp, (size_t)0, tq, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                       (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(ss.ml.p), (size_t)1);
+    launch_sig_miller(sig_pair(kind, ss.sig.p, 0), ss.ml.p, 1, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(tl_ctx->join[0], st));
     return BLSMI_OK;
 }
-int aggregate_tail(int kind, const i32* d_prod, const SigSide& ss, int* ok) {
-    (void)kind;
-    DBuf dokb;
-    HIPCHK(dokb.alloc(1));
+int aggregate_tail(const i32* d_prod, const SigSide& ss, int* ok) {
     HIPCHK(hipStreamWaitEvent(g_stream, tl_ctx->join[0], 0));
-    prof_mark("k_lat:aggtail2");
-    hipLaunchKernelGGL(k_lat, dim3(1), dim3(64), lat_lds_bytes(LAT_AGGTAIL2_OFFSET), g_stream, (const u8*)g_gens.lat + LAT_AGGTAIL2_OFFSET,
-                       (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)ss.ml.p, (size_t)0, (const u8*)d_prod, (size_t)0,
-                       (const u8*)nullptr, dokb.as<u8>(), (u64*)nullptr, (size_t)1);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    uint8_t flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, dokb.p, 1, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-    *ok = flag;
-    return BLSMI_OK;
+    return tail_verdict(LAT_AGGTAIL2_OFFSET, "k_lat:aggtail2", {.b2 = {ss.ml.p, 0}, .b3 = {d_prod, 0}}, ok);
+}
+inline bool sig_is_infinity(int kind, const uint8_t* sig, int fmt) {       // the reference panics in MillerLoop: verdict 0
+    const Kind k = kind_of(kind);
+    return (fmt & FMT_SIG_JAC) ? jac_host_is_infinity(sig, k.sig_bytes) : all_zero(sig, k.sig_bytes);
 }
 // below this many messages the duplicate screen runs inline on the calling thread (a few microseconds) before any GPU work
 constexpr size_t DUP_INLINE_MAX = 4096;
+// The tuple side of an unsplit VerifyAggregate as the leased context's device sees it: messages, offsets (kind 2: the domain) and keys (or
+// prep: their tables) at device addresses.  The device-pointer forms have them there.  The host form stages them through its two hooks:
+// stage_msgs, before the duplicate screen and the hash, takes the buffers, fills in the three addresses and enqueues the copy of the
+// messages and offsets; after_hash (the keys) runs once the hash is enqueued, as aggregate_shard_dev's.  msgs / off: the host's own copy of
+// the messages where the caller passed one (the duplicate screen's sort fallback reads it; otherwise it fetches them from the device).
+struct AggInputs {
+    const void* d_msgs = nullptr; const void* d_off_or_domain = nullptr; const u8* d_pks = nullptr; const PrepKeys* prep = nullptr;
+    const uint8_t* msgs = nullptr; const uint64_t* off = nullptr;
+    std::function<int(AggInputs&)> stage_msgs;
+    std::function<int()> after_hash;
+};
+// the duplicate verdict of the reference's sort (has_duplicates_sorted) where the device table gave up (k_util.hip), or "dup_force_sort" asks
+int dup_sort_fallback(const AggInputs& in, size_t n, bool* dup) {
+    try {
+        if (in.msgs) { *dup = has_duplicates_sorted(in.msgs, in.off, n); return BLSMI_OK; }
+        std::vector<uint64_t> off(n + 1);                                  // resident messages: fetched
+        HIPCHK(hipMemcpyAsync(off.data(), in.d_off_or_domain, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
+        std::vector<uint8_t> m((size_t)off[n] ? (size_t)off[n] : 1);
+        HIPCHK(hipMemcpyAsync(m.data(), in.d_msgs, (size_t)off[n], hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
+        *dup = has_duplicates_sorted(m.data(), off.data(), n);
+        return BLSMI_OK;
+    } catch (...) { return BLSMI_E_NOMEM; }
+}
+// An unsplit VerifyAggregate on the leased context -- the host form's one-shard case and every device-pointer form.  in: by value, the
+// host form's stage_msgs completes it.  sig: host memory,
+// not the point at infinity; *ok is 0 on entry.  screen: the duplicate-message rule of g2pubs/bls.go:245-261 is still to be applied, on the
+// device (k_util.hip).  Enqueue order: the signature side on aux[0]; the message copy; the duplicate screen; the hash; the key upload or the
+// prepared gather; the infinity flags; the Miller loops; the product tree; then the flag fetches.  A repeated or empty message ends the
+// call as a key at infinity does (bad bit 0: verdict 0; the lease drains the side stream).
+int verify_aggregate_on_ctx(int kind, AggInputs in, const uint8_t* sig, size_t n, int* ok, bool screen, int fmt) {
+    screen = screen && kind != 2 && n > 0;
+    DBuf prod, ddup; HIPCHK(prod.alloc(sizeof(i32) * 12 * NL)); HIPCHK(ddup.alloc(sizeof(int)));
+    SigSide ss;
+    { int rc = sig_side_start(kind, sig, ss, fmt); if (rc) return rc; }
+    if (n == 0) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_stream, prod.as<i32>());
+    else {
+        bool first = true;
+        int bad = 0;
+        int rc = tuple_side_product(agg_pow_wanted(kind, n, tune()), prod, &bad, [&](bool g1_clear, int* b) -> int {
+            const bool fresh = first;                                      // (the second run: messages, keys and the screen's verdict are where the first left them)
+            first = false;
+            if (fresh && in.stage_msgs) { int rc = in.stage_msgs(in); if (rc) return rc; }
+            if (fresh && screen && blsmi_util::dup_check_async(in.d_msgs, in.d_off_or_domain, n, dup_key()[0], dup_key()[1], ddup.as<int>(), g_stream, [](size_t b) { return tl_ctx->arena.alloc(b); }) != 0) return BLSMI_E_HIP;
+            int rc = aggregate_shard_dev(kind, in.d_msgs, in.d_off_or_domain, in.d_pks, n, prod.as<i32>(), b, g_stream, fresh ? in.after_hash : std::function<int()>{}, in.prep, g1_clear);
+            if (rc) return rc;
+            HIPCHK(hipStreamSynchronize(g_stream));
+            if (!fresh || !screen) return BLSMI_OK;
+            int dupflag = 0;
+            HIPCHK(hipMemcpyAsync(&dupflag, ddup.p, sizeof dupflag, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
+            if (tune().dup_force_sort) dupflag |= 2;                       // test hook: take the fallback on every call
+            if (dupflag & 2) { bool d = false; rc = dup_sort_fallback(in, n, &d); if (rc) return rc; dupflag = d ? 1 : 0; }
+            if (dupflag) *b |= 1;
+            return BLSMI_OK;
+        });
+        if (rc || bad) return rc;                                          // a key at infinity / a repeated or empty message: verdict 0
+    }
+    return aggregate_tail(prod.as<i32>(), ss, ok);
+}
 // e(sig-side) == prod_i e(h_i, pk_i): n Miller loops, an Fq12 product tree, ONE final exponentiation
 // (FinalExponentiation is a homomorphism, so the verdict equals the reference's product of n full pairings).
 // A call that is not split (one shard; the common case of a small aggregate and of a single-device deployment) runs on
@@ -799,19 +874,16 @@ constexpr size_t DUP_INLINE_MAX = 4096;
 // calls from several goroutines run side by side on the library's streams.  A call that IS split occupies every
 // device anyway: it takes g_coll_mu, each shard leaves its partial product in its device's exchange buffer, one
 // all-gather (720 bytes per slot) brings them together, device 0 multiplies them and compares.
-// *redo (never null): set when the call took the uncleared-hash path (agg_pow_wanted) and met a message it does not cover (*bad bit 1, hash.cuh:
-// swu_finish_g1): the wrapper below runs the call again with the cleared hash points.
-int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, int fmt, bool no_powc, bool* redo) {
+int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, int fmt = 0) {
     if (!ok || !sig || (n && (!msgs || !off_or_domain || !pks))) return BLSMI_E_ARG;
     *ok = 0;
     { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
     const Kind k = kind_of(kind);
-    if ((fmt & FMT_SIG_JAC) ? jac_host_is_infinity(sig, k.sig_bytes) : all_zero(sig, k.sig_bytes)) return BLSMI_OK;   // signature at infinity: the reference panics, verdict 0
+    if (sig_is_infinity(kind, sig, fmt)) return BLSMI_OK;
     const size_t pk_in = rec_bytes(k.pk_bytes, fmt & FMT_PK_JAC);
     const size_t words = (size_t)12 * NL;
     const ShardPlan plan = plan_shards(n, 64);
     const Tuning t = tuning_now();                                         // what holds across the shards' threads is decided here, once
-    const bool powc = !no_powc && agg_pow_wanted(kind, n, t);              // hash points without their cofactor clearing, the product raised to 1 - x instead
     check_dups = check_dups && n > 0;
     bool dup = false;
     if (check_dups && n <= DUP_INLINE_MAX) {                               // small: screened here, no thread, no device work
@@ -823,26 +895,18 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
     if (plan.nshards == 1 && !g_force_rccl) {
         CtxLease lease;                                                    // any device, any free context
         if (lease.rc) return lease.rc;
-        DBuf prod, ddup; HIPCHK(prod.alloc(sizeof(i32) * words)); HIPCHK(ddup.alloc(sizeof(int)));
-        SigSide ss;
-        { int rc = sig_side_start(kind, sig, ss, fmt); if (rc) return rc; }
-        int bad = 0, dupflag = 0;
-        if (n == 0) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_stream, prod.as<i32>());
-        else {
-            int rc = aggregate_shard(kind, msgs, off_or_domain, pks, n, prod.as<i32>(), &bad, check_dups ? ddup.as<int>() : nullptr, !powc, fmt);   // synchronises
-            if (rc) return rc;
-            if (check_dups) { HIPCHK(hipMemcpyAsync(&dupflag, ddup.p, sizeof dupflag, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); }
-        }
-        if (check_dups && t.dup_force_sort) dupflag |= 2;     // test hook: take the fallback on every call
-        if (dupflag & 2) {                                                 // the device table gave up (k_util.hip): the reference's sort, on the host
-            bool d = false;
-            try { d = has_duplicates_sorted(msgs, off_or_domain, n); } catch (...) { return BLSMI_E_NOMEM; }
-            dupflag = d ? 1 : 0;
-        }
-        if ((bad & 1) || dupflag) return BLSMI_OK;                         // a key at infinity / a repeated or empty message: verdict 0 (the lease drains the side stream)
-        if (bad & 2) { *redo = true; return BLSMI_OK; }
-        if (powc) { DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * words)); int rc = aggregate_pow_c(prod.as<i32>(), pc.as<i32>()); if (rc) return rc; return aggregate_tail(kind, pc.as<i32>(), ss, ok); }
-        return aggregate_tail(kind, prod.as<i32>(), ss, ok);
+        if (n == 0) return verify_aggregate_on_ctx(kind, AggInputs{}, sig, 0, ok, false, fmt);
+        DevMsgs dm(kind, off_or_domain, n); DBuf dp;
+        AggInputs in;
+        in.msgs = msgs; in.off = off_or_domain;
+        in.stage_msgs = [&](AggInputs& a) -> int {
+            int rc = dm.alloc(); if (rc) return rc;
+            HIPCHK(dp.alloc((size_t)k.pk_bytes * n));
+            a.d_msgs = dm.m.p; a.d_off_or_domain = dm.off.p; a.d_pks = dp.as<u8>();
+            return dm.copy(msgs, off_or_domain, g_stream);
+        };
+        in.after_hash = [&]() -> int { return upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); };   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
+        return verify_aggregate_on_ctx(kind, in, sig, n, ok, check_dups, fmt);
     }
     const int S = (plan.nshards + g_ndev - 1) / g_ndev;                    // partial-product slots per device
     const size_t total = (size_t)g_ndev * S;
@@ -866,29 +930,34 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
         try { dup_thread = std::thread([&] { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup, t.dup_force_sort); }); }
         catch (...) { dup_rc = has_duplicates_rc(msgs, off_or_domain, n, &dup, t.dup_force_sort); }   // no thread to be had: screen here
     }
-    std::vector<int> bad(plan.nshards, 0);
+    bool powc = agg_pow_wanted(kind, n, t);                                // hash points without their cofactor clearing, the product raised to 1 - x instead
+    int bad = 0;
     rc = BLSMI_OK;
-    auto shard_body = [&](int sh, size_t lo, size_t hi) -> int {
-        const size_t m = hi - lo;
-        std::vector<uint64_t> off_sub;
-        const uint8_t* mp; const uint64_t* op;
-        if (kind == 2) { mp = msgs + 32 * lo; op = off_or_domain; }
-        else {
-            off_sub.resize(m + 1);
-            for (size_t i = 0; i <= m; i++) off_sub[i] = off_or_domain[lo + i] - off_or_domain[lo];
-            mp = msgs + off_or_domain[lo]; op = off_sub.data();
-        }
-        i32* slot = reinterpret_cast<i32*>(tl_ctx->dev->coll.p) + words * (sh / g_ndev);
-        return aggregate_shard(kind, mp, op, pks + pk_in * lo, m, slot, &bad[sh], nullptr, !powc, fmt);
-    };
-    if (n && plan.nshards == 1) { CtxLease lease(0); rc = lease.rc ? lease.rc : shard_body(0, 0, n); }   // (forced RCCL with one shard: test hook)
-    else if (n) rc = run_shards(plan, shard_body);
+    if (n) rc = run_tuple_side(powc, &bad, [&](bool g1_clear, int* any_bad) -> int {
+        std::vector<int> shard_bad(plan.nshards, 0);
+        auto shard_body = [&](int sh, size_t lo, size_t hi) -> int {
+            const size_t m = hi - lo;
+            std::vector<uint64_t> off_sub;
+            const uint8_t* mp; const uint64_t* op;
+            if (kind == 2) { mp = msgs + 32 * lo; op = off_or_domain; }
+            else {
+                off_sub.resize(m + 1);
+                for (size_t i = 0; i <= m; i++) off_sub[i] = off_or_domain[lo + i] - off_or_domain[lo];
+                mp = msgs + off_or_domain[lo]; op = off_sub.data();
+            }
+            i32* slot = reinterpret_cast<i32*>(tl_ctx->dev->coll.p) + words * (sh / g_ndev);
+            return aggregate_shard(kind, mp, op, pks + pk_in * lo, m, slot, &shard_bad[sh], g1_clear, fmt);
+        };
+        int rc;
+        if (plan.nshards == 1) { CtxLease lease(0); rc = lease.rc ? lease.rc : shard_body(0, 0, n); }   // (forced RCCL with one shard: test hook)
+        else rc = run_shards(plan, shard_body);
+        for (int b : shard_bad) *any_bad |= b;
+        return rc;
+    });
     if (dup_thread.joinable()) dup_thread.join();
     if (rc) return rc;
     if (dup_rc) return dup_rc;
-    for (int b : bad) if (b & 1) return BLSMI_OK;                          // a key at infinity: verdict 0
-    if (dup) return BLSMI_OK;                                              // *ok stays 0
-    for (int b : bad) if (b & 2) { *redo = true; return BLSMI_OK; }
+    if ((bad & 1) || dup) return BLSMI_OK;                                 // a key at infinity / a repeated or empty message: *ok stays 0
     // the one exchange step of VerifyAggregate: all-gather of the per-device partial products
     const i32* gathered = c0; size_t cnt = S;
     if (g_have_comm && g_alias) {
@@ -914,52 +983,13 @@ int verify_aggregate_host_impl(int kind, const uint8_t* msgs, const uint64_t* of
     if (powc) { i32* dst = src == soa ? scratch : soa; int rc2 = aggregate_pow_c(src, dst); if (rc2) return rc2; src = dst; }   // (dst: the tree's other buffer, free now)
     return aggregate_tail(kind, src, sig, ok, fmt);
 }
-int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, const uint8_t* pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, int fmt = 0) {
-    bool redo = false;
-    int rc = verify_aggregate_host_impl(kind, msgs, off_or_domain, pks, sig, n, ok, check_dups, fmt, false, &redo);
-    if (rc == BLSMI_OK && redo) { redo = false; rc = verify_aggregate_host_impl(kind, msgs, off_or_domain, pks, sig, n, ok, check_dups, fmt, true, &redo); }
-    return rc;
-}
-// Device-pointer form: messages, offsets and keys resident on ONE of the library's devices (the one that owns d_pks); the
-// aggregate signature is 96 / 192 bytes of HOST memory.  Duplicate rejection runs on the device (k_util.hip).  Not split over
-// devices: the caller's buffers live on one.
-int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_domain, const void* d_pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, const PrepKeys* prep = nullptr, int fmt = 0, bool no_powc = false) {
-    const Kind k = kind_of(kind);
+// Device-pointer forms: messages, offsets and keys (or their prepared tables) resident on ONE of the library's devices, whose lease the
+// caller holds; the aggregate signature is 96 / 192 bytes of HOST memory.  Duplicate rejection runs on the device (k_util.hip).  Not split
+// over devices: the caller's buffers live on one.
+int verify_aggregate_dev(int kind, const void* d_msgs, const void* d_off_or_domain, const void* d_pks, const uint8_t* sig, size_t n, int* ok, bool check_dups, const PrepKeys* prep = nullptr, int fmt = 0) {
     *ok = 0;
-    if ((fmt & FMT_SIG_JAC) ? jac_host_is_infinity(sig, k.sig_bytes) : all_zero(sig, k.sig_bytes)) return BLSMI_OK;
-    const size_t words = (size_t)12 * NL;
-    const bool powc = !no_powc && agg_pow_wanted(kind, n, tune());
-    DBuf prod, ddup; HIPCHK(prod.alloc(sizeof(i32) * words)); HIPCHK(ddup.alloc(sizeof(int)));
-    SigSide ss;
-    { int rc = sig_side_start(kind, sig, ss, fmt); if (rc) return rc; }
-    int bad = 0, dupflag = 0;
-    if (n == 0) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_stream, prod.as<i32>());
-    else {
-        if (check_dups && kind != 2) {
-            if (blsmi_util::dup_check_async(d_msgs, d_off_or_domain, n, dup_key()[0], dup_key()[1], ddup.as<int>(), g_stream, [](size_t b) { return tl_ctx->arena.alloc(b); }) != 0) return BLSMI_E_HIP;
-            HIPCHK(hipMemcpyAsync(&dupflag, ddup.p, sizeof dupflag, hipMemcpyDeviceToHost, g_stream));
-        }
-        int rc = aggregate_shard_dev(kind, d_msgs, d_off_or_domain, (const u8*)d_pks, n, prod.as<i32>(), &bad, g_stream, {}, prep, !powc);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(g_stream));
-    }
-    if (check_dups && kind != 2 && n && tune().dup_force_sort) dupflag |= 2;   // test hook: take the fallback on every call
-    if (dupflag & 2) {                                                     // the device table gave up (k_util.hip): fetch the messages, the reference's sort on the host
-        try {
-            std::vector<uint64_t> off(n + 1);
-            HIPCHK(hipMemcpyAsync(off.data(), d_off_or_domain, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-            std::vector<uint8_t> m((size_t)off[n] ? (size_t)off[n] : 1);
-            HIPCHK(hipMemcpyAsync(m.data(), d_msgs, (size_t)off[n], hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-            dupflag = has_duplicates_sorted(m.data(), off.data(), n) ? 1 : 0;
-        } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    }
-    if ((bad & 1) || dupflag) return BLSMI_OK;
-    if (bad & 2) {                                                         // the uncleared-hash path met a message it does not cover: once more with the cleared hash points
-        HIPCHK(hipStreamSynchronize(tl_ctx->aux[0]));                      // (the signature side's Miller loop of this attempt)
-        return verify_aggregate_dev(kind, d_msgs, d_off_or_domain, d_pks, sig, n, ok, check_dups, prep, fmt, true);
-    }
-    if (powc) { DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * words)); int rc = aggregate_pow_c(prod.as<i32>(), pc.as<i32>()); if (rc) return rc; return aggregate_tail(kind, pc.as<i32>(), ss, ok); }
-    return aggregate_tail(kind, prod.as<i32>(), ss, ok);
+    if (sig_is_infinity(kind, sig, fmt)) return BLSMI_OK;
+    return verify_aggregate_on_ctx(kind, AggInputs{d_msgs, d_off_or_domain, (const u8*)d_pks, prep}, sig, n, ok, check_dups, fmt);
 }
 
 // VerifyAggregateCommon: AggregatePublicKeys (sum) then one Verify (g2pubs/bls.go:275-278)
@@ -1026,15 +1056,15 @@ int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uin
     return BLSMI_OK;
 }
 template <int IB, int OB, class K>
-int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, size_t off_bytes, size_t msg_bytes, uint8_t* out, size_t n) {
+int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, uint8_t* out, size_t n) {
     if (n && (!msgs || !off_or_domain || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
-    DBuf dm, doff, dout;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dout.alloc((size_t)OB * n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
-    int rc = hash_dev(kernel_kind, dm.p, doff.p, dout.as<u8>(), n, g_stream, hash_route_alone(kernel_kind, n));
+    DevMsgs dm(kernel_kind, off_or_domain, n); DBuf dout;
+    HIPCHK(dout.alloc((size_t)OB * n));
+    int rc = dm.upload(msgs, off_or_domain, g_stream);
+    if (rc) return rc;
+    rc = hash_dev(kernel_kind, dm.m.p, dm.off.p, dout.as<u8>(), n, g_stream, hash_route_alone(kernel_kind, n));
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1058,9 +1088,7 @@ int decompress_dev(int group, const u8* d_in, int check, u8* d_out, u8* d_inf, u
         const size_t prog = group == 1 ? LAT_SUBGRP1_OFFSET : LAT_SUBGRP2_OFFSET;
         DBuf sub; HIPCHK(sub.alloc(n, s));
         prof_mark(group == 1 ? "k_lat:subgrp1" : "k_lat:subgrp2");
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog), s, (const u8*)g_gens.lat + prog, (const u8*)d_out, rec,
-                           (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, sub.as<u8>(), (u64*)nullptr, n);
+        launch_lat(prog, s, {.b0 = {d_out, rec}, .ok = sub.p}, n);
         hipLaunchKernelGGL(k_apply_subgroup, g, w, 0, s, (const u8*)sub.as<u8>(), d_out, (int)(rec / 4), (const u8*)d_inf, d_err, n);
     }
     prof_mark(nullptr);
@@ -1093,13 +1121,11 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
     const Kind k = kind_of(kind);
-    const size_t pkc = k.pk_bytes / 2, sgc = k.sig_bytes / 2, msg_bytes = (size_t)off[n];
-    DBuf dm, doff, dpc, dsc, dp, ds, ipk, epk, isg, esg, dfl, dok;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(sizeof(uint64_t) * (n + 1)));
+    const size_t pkc = k.pk_bytes / 2, sgc = k.sig_bytes / 2;
+    DevMsgs dm(kind, off, n); DBuf dpc, dsc, dp, ds, ipk, epk, isg, esg, dfl, dok;
     HIPCHK(dpc.alloc(pkc * n)); HIPCHK(dsc.alloc(sgc * n)); HIPCHK(dp.alloc((size_t)k.pk_bytes * n)); HIPCHK(ds.alloc((size_t)k.sig_bytes * n));
     HIPCHK(ipk.alloc(n)); HIPCHK(epk.alloc(n)); HIPCHK(isg.alloc(n)); HIPCHK(esg.alloc(n)); HIPCHK(dfl.alloc(n)); HIPCHK(dok.alloc(n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, g_stream));
+    { int rc = dm.upload(msgs, off, g_stream); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(dpc.p, pks, pkc * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dsc.p, sigs, sgc * n, hipMemcpyHostToDevice, g_stream));
     dim3 g(nblocks(n)), w(WG);
@@ -1126,7 +1152,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     DBuf h, f;
     HIPCHK(h.alloc((size_t)kk.h_bytes * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
     const VerifyRoute r = verify_route(kind, n, false, false, tune(), route_load(n));   // (no signature side: the signatures are still being decompressed)
-    int rc = hash_dev(kind, dm.p, doff.p, h.as<u8>(), n, g_stream, r.hash);  // on the main stream, beside the decompressions
+    int rc = hash_dev(kind, dm.m.p, dm.off.p, h.as<u8>(), n, g_stream, r.hash);  // on the main stream, beside the decompressions
     if (rc) return rc;
     if (side) {
         HIPCHK(hipEventRecord(tl_ctx->join[0], spk)); HIPCHK(hipEventRecord(tl_ctx->join[1], ssg));
@@ -1172,11 +1198,8 @@ static int aggregate_partial_host(int kind, const uint8_t* msgs, const uint64_t*
     else {
         // a large g2pubs shard pairs the hash points before their cofactor clearing and raises ITS product to 1 - x (agg_pow_wanted): the
         // value differs from prod ML(H(m_i), pk_i) only by what the final exponentiation removes, which is all a partial product is used for
-        bool powc = agg_pow_wanted(kind, n, tune());
-        int rc = aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), &b, nullptr, !powc);
+        int rc = tuple_side_product(agg_pow_wanted(kind, n, tune()), f, &b, [&](bool g1_clear, int* bad) { return aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), bad, g1_clear); });
         if (rc) return rc;
-        if (b & 2) { powc = false; b = 0; rc = aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), &b, nullptr, true); if (rc) return rc; }   // a message the uncleared path does not cover: cleared hash points
-        if (powc) { DBuf pc; HIPCHK(pc.alloc(sizeof(i32) * words)); rc = aggregate_pow_c(f.as<i32>(), pc.as<i32>()); if (rc) return rc; f = pc; }
     }
     hipLaunchKernelGGL(k_final_exp, dim3(1), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), dout.as<u64>(), (size_t)1, 1);   // mode 1: format conversion only
     HIPCHK(hipGetLastError());
@@ -1217,9 +1240,7 @@ BLSMI_API int blsmi_debug_hash_tail(int kind, const uint8_t* pts, uint8_t* out, 
     DBuf dp, dout, dg;
     HIPCHK(dp.alloc(rec * n)); HIPCHK(dout.alloc(hb * n)); HIPCHK(dg.alloc(n));
     HIPCHK(hipMemcpyAsync(dp.p, pts, rec * n, hipMemcpyHostToDevice, g_stream));
-    hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(prog), g_stream, (const u8*)g_gens.lat + prog, (const u8*)dp.as<u8>(), rec,
-                       (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                       (const u8*)nullptr, dg.as<u8>(), dout.as<u64>(), n);
+    launch_lat(prog, g_stream, {.b0 = {dp.p, rec}, .ok = dg.p, .out = dout.p}, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, hb * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(good, dg.p, n, hipMemcpyDeviceToHost, g_stream));
@@ -1261,17 +1282,15 @@ BLSMI_API int blsmi_debug_hash_redo(int kind, const uint8_t* msgs, const uint64_
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
     const size_t hb = kind == 0 ? 96 : 192;
-    const size_t msg_bytes = kind == 2 ? 32 * n : (size_t)off_or_domain[n], off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (n + 1);
-    DBuf dm, doff, dout, dg;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes)); HIPCHK(dout.alloc(hb * n)); HIPCHK(dg.alloc(n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
+    DevMsgs dm(kind, off_or_domain, n); DBuf dout, dg;
+    HIPCHK(dout.alloc(hb * n)); HIPCHK(dg.alloc(n));
+    { int rc = dm.upload(msgs, off_or_domain, g_stream); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(dout.p, out, hb * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dg.p, good, n, hipMemcpyHostToDevice, g_stream));
     dim3 g(nblocks(n)), w(WG);
-    if (kind == 0) hipLaunchKernelGGL(k_hash_g1_redo, g, w, 0, g_stream, dm.as<u8>(), doff.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
-    else if (kind == 1) hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, g_stream, dm.as<u8>(), doff.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
-    else hipLaunchKernelGGL(k_hash_g2_domain_redo, g, w, 0, g_stream, dm.as<u8>(), doff.as<u8>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
+    if (kind == 0) hipLaunchKernelGGL(k_hash_g1_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
+    else if (kind == 1) hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
+    else hipLaunchKernelGGL(k_hash_g2_domain_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u8>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, hb * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1279,13 +1298,13 @@ BLSMI_API int blsmi_debug_hash_redo(int kind, const uint8_t* msgs, const uint64_
 }
 
 BLSMI_API int blsmi_hash_g1_batch(const uint8_t* msgs, const uint64_t* off, uint8_t* out, size_t n) {
-    return hash_host<0, 96>(0, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, out, n);
+    return hash_host<0, 96>(0, msgs, off, out, n);
 }
 BLSMI_API int blsmi_hash_g2_batch(const uint8_t* msgs, const uint64_t* off, uint8_t* out, size_t n) {
-    return hash_host<0, 192>(1, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, out, n);
+    return hash_host<0, 192>(1, msgs, off, out, n);
 }
 BLSMI_API int blsmi_hash_g2_with_domain_batch(const uint8_t* msgs32, const uint8_t domain[8], uint8_t* out, size_t n) {
-    return hash_host<0, 192>(2, msgs32, domain, 8, 32 * n, out, n);
+    return hash_host<0, 192>(2, msgs32, domain, out, n);
 }
 
 // Sign for n (message, secret key) pairs in one call: sig_i = sk_i * H(m_i) (g2pubs/bls.go:132-135, g1pubs/bls.go:132-135, 138-141) -- the hash
@@ -1467,26 +1486,30 @@ BLSMI_API int blsmi_g2_prepare_batch(const uint8_t* g2_aff, size_t n, uint64_t* 
 }
 // For callers without a HIP runtime of their own (the cgo shim): the library allocates the tables on the calling thread's device
 // (device 0 unless blsmi_init chose another), prepares n host keys into them and hands back the device pointer as the handle.
-BLSMI_API int blsmi_g2_prepared_create(const uint8_t* g2_aff, size_t n, void** handle) {
-    if (!handle || !n || !g2_aff) return BLSMI_E_ARG;
+// jac: the keys are in-memory Jacobian records (blsmi 0.6), brought to affine on the device (upload_points)
+static int g2_prepared_create(const uint8_t* g2, bool jac, size_t n, void** handle) {
+    if (!handle || !n || !g2) return BLSMI_E_ARG;
     *handle = nullptr;
     LOCK_AND_INIT();
     void* tab = nullptr;
     HIPCHK(hipMalloc(&tab, (size_t)BLSMI_G2_PREPARED_BYTES * n));
+    auto code = [](hipError_t e) { return e == hipSuccess ? BLSMI_OK : e == hipErrorOutOfMemory ? BLSMI_E_NOMEM : BLSMI_E_HIP; };
     DBuf q;
-    hipError_t e = q.alloc(192 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(q.p, g2_aff, 192 * n, hipMemcpyHostToDevice, g_stream);
-    if (e == hipSuccess) {
+    int rc = code(q.alloc(192 * n));
+    if (!rc) rc = jac ? upload_points(192, true, g2, q.p, n, g_stream) : code(hipMemcpyAsync(q.p, g2, 192 * n, hipMemcpyHostToDevice, g_stream));
+    if (!rc) {
         prof_mark("k_g2_prepare_pair");
         hipLaunchKernelGGL(k_g2_prepare_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, g_stream, q.as<u8>(), (i32*)tab, n);
         prof_mark(nullptr);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
+        rc = (jac && e != hipSuccess) ? BLSMI_E_HIP : code(e);             // (the in-memory form reports every failure of the kernel as HIP)
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
-    if (e != hipSuccess) { (void)hipFree(tab); return e == hipErrorOutOfMemory ? BLSMI_E_NOMEM : BLSMI_E_HIP; }
+    if (rc) { (void)hipStreamSynchronize(g_stream); (void)hipFree(tab); return rc; }   // (nothing queued may still write the tables)
     *handle = tab;
     return BLSMI_OK;
 }
+BLSMI_API int blsmi_g2_prepared_create(const uint8_t* g2_aff, size_t n, void** handle) { return g2_prepared_create(g2_aff, false, n, handle); }
 BLSMI_API int blsmi_g2_prepared_destroy(void* handle) {
     if (!handle) return BLSMI_OK;
     const int idx = device_index_of_pointer(handle);
@@ -1546,19 +1569,21 @@ BLSMI_API int blsmi_g2pubs_verify_aggregate_prepared_dev(const void* d_msgs, con
     return verify_aggregate_dev(0, d_msgs, d_off, nullptr, sig, n, ok, true, &prep);
 }
 // Signature.VerifyAggregate with messages, key indices and the signature in HOST memory and the keys prepared (the cgo shim's form)
-BLSMI_API int blsmi_g2pubs_verify_aggregate_prepared(const uint8_t* msgs, const uint64_t* off, const void* d_prepared, const uint32_t* key_idx, const uint8_t sig[96], size_t n, int* ok) {
+// fmt: FMT_SIG_JAC -- the signature is an in-memory Jacobian record
+static int verify_aggregate_prepared_host(const uint8_t* msgs, const uint64_t* off, const void* d_prepared, const uint32_t* key_idx, const uint8_t* sig, size_t n, int* ok, int fmt) {
     if (!ok || !sig || (n && (!msgs || !off || !d_prepared))) return BLSMI_E_ARG;
     *ok = 0;
-    if (n == 0) return verify_aggregate_host(0, msgs, off, nullptr, sig, 0, ok, true);
+    if (n == 0) return verify_aggregate_host(0, msgs, off, nullptr, sig, 0, ok, true, fmt);
     LOCK_AND_INIT_AT(d_prepared);
-    const size_t msg_bytes = (size_t)off[n];
-    DBuf dm, doff, didx;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(sizeof(uint64_t) * (n + 1))); HIPCHK(didx.alloc(sizeof(uint32_t) * n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, g_stream));
+    DevMsgs dm(0, off, n); DBuf didx;
+    HIPCHK(didx.alloc(sizeof(uint32_t) * n));
+    { int rc = dm.upload(msgs, off, g_stream); if (rc) return rc; }
     if (key_idx) HIPCHK(hipMemcpyAsync(didx.p, key_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, g_stream));
     const PrepKeys prep{(const i32*)d_prepared, key_idx ? didx.as<u32>() : nullptr};
-    return verify_aggregate_dev(0, dm.p, doff.p, nullptr, sig, n, ok, true, &prep);
+    return verify_aggregate_dev(0, dm.m.p, dm.off.p, nullptr, sig, n, ok, true, &prep, fmt);
+}
+BLSMI_API int blsmi_g2pubs_verify_aggregate_prepared(const uint8_t* msgs, const uint64_t* off, const void* d_prepared, const uint32_t* key_idx, const uint8_t sig[96], size_t n, int* ok) {
+    return verify_aggregate_prepared_host(msgs, off, d_prepared, key_idx, sig, n, ok, 0);
 }
 BLSMI_API int blsmi_g2pubs_verify_aggregate_common(const uint8_t* msg, size_t msg_len, const uint8_t* pks, const uint8_t sig[96], size_t n, int* ok) {
     return verify_aggregate_common_host(0, msg, msg_len, nullptr, pks, sig, n, ok);
@@ -1662,25 +1687,7 @@ BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_jac_dev(const void* d_msgs32
     return verify_batch_jac_dev_api<2>(d_msgs32, d_domain, d_pks, d_sigs, d_ok, n, stream);
 }
 // prepared keys (g2pubs) from, and verified against, in-memory points
-BLSMI_API int blsmi_g2_prepared_create_jac(const uint64_t* g2_jac, size_t n, void** handle) {
-    if (!handle || !n || !g2_jac) return BLSMI_E_ARG;
-    *handle = nullptr;
-    LOCK_AND_INIT();
-    void* tab = nullptr;
-    HIPCHK(hipMalloc(&tab, (size_t)BLSMI_G2_PREPARED_BYTES * n));
-    DBuf q;
-    hipError_t e = q.alloc(192 * n);
-    int rc = e == hipSuccess ? upload_points(192, true, JACP(g2_jac), q.p, n, g_stream) : BLSMI_E_NOMEM;
-    if (rc == BLSMI_OK) {
-        prof_mark("k_g2_prepare_pair");
-        hipLaunchKernelGGL(k_g2_prepare_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, g_stream, q.as<u8>(), (i32*)tab, n);
-        prof_mark(nullptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(g_stream) != hipSuccess) rc = BLSMI_E_HIP;
-    }
-    if (rc) { (void)hipStreamSynchronize(g_stream); (void)hipFree(tab); return rc; }
-    *handle = tab;
-    return BLSMI_OK;
-}
+BLSMI_API int blsmi_g2_prepared_create_jac(const uint64_t* g2_jac, size_t n, void** handle) { return g2_prepared_create(JACP(g2_jac), true, n, handle); }
 BLSMI_API int blsmi_g2pubs_verify_batch_prepared_jac(const uint8_t* msgs, const uint64_t* off, const void* d_prepared, const uint32_t* key_idx, const uint64_t* sigs,
                                                      uint8_t* ok, uint8_t* ok_bitmap, size_t n) {
     if (n == 0) return BLSMI_OK;
@@ -1689,18 +1696,7 @@ BLSMI_API int blsmi_g2pubs_verify_batch_prepared_jac(const uint8_t* msgs, const 
     return verify_batch_leased(0, msgs, off, nullptr, JACP(sigs), nullptr, ok, ok_bitmap, n, nullptr, (const i32*)d_prepared, key_idx, FMT_SIG_JAC);
 }
 BLSMI_API int blsmi_g2pubs_verify_aggregate_prepared_jac(const uint8_t* msgs, const uint64_t* off, const void* d_prepared, const uint32_t* key_idx, const uint64_t sig[18], size_t n, int* ok) {
-    if (!ok || !sig || (n && (!msgs || !off || !d_prepared))) return BLSMI_E_ARG;
-    *ok = 0;
-    if (n == 0) return verify_aggregate_host(0, msgs, off, nullptr, JACP(sig), 0, ok, true, FMT_SIG_JAC);
-    LOCK_AND_INIT_AT(d_prepared);
-    const size_t msg_bytes = (size_t)off[n];
-    DBuf dm, doff, didx;
-    HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(sizeof(uint64_t) * (n + 1))); HIPCHK(didx.alloc(sizeof(uint32_t) * n));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, g_stream));
-    if (key_idx) HIPCHK(hipMemcpyAsync(didx.p, key_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, g_stream));
-    const PrepKeys prep{(const i32*)d_prepared, key_idx ? didx.as<u32>() : nullptr};
-    return verify_aggregate_dev(0, dm.p, doff.p, nullptr, JACP(sig), n, ok, true, &prep, FMT_SIG_JAC);
+    return verify_aggregate_prepared_host(msgs, off, d_prepared, key_idx, JACP(sig), n, ok, FMT_SIG_JAC);
 }
 #undef JACP
 
@@ -1917,9 +1913,8 @@ int agg_common_batch_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
         if (off_or_domain[0] != 0) return BLSMI_E_ARG;
         for (size_t j = 0; j < m; j++) if (off_or_domain[j + 1] < off_or_domain[j]) return BLSMI_E_ARG;
     }
-    const size_t msg_bytes = kind == 2 ? 32 * m : (size_t)off_or_domain[m];
-    const size_t off_bytes = kind == 2 ? 8 : sizeof(uint64_t) * (m + 1);
-    if (msg_bytes && !msgs) return BLSMI_E_ARG;
+    DevMsgs dm(kind, off_or_domain, m);
+    if (dm.msg_bytes && !msgs) return BLSMI_E_ARG;
     int rc = segsum_check(npk, idx, seg_off, m);
     if (rc) return rc;
     const Kind k = kind_of(kind);
@@ -1930,23 +1925,18 @@ int agg_common_batch_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
     if (lease.rc) return lease.rc;
     SegPlan plan;
     segsum_plan(seg_off, m, segsum_chunk_of(total), plan);
-    DBuf dp, dx, dm, doff, ds, dok;
-    HIPCHK(dp.alloc(pin * npk)); HIPCHK(dx.alloc(sizeof(uint32_t) * total)); HIPCHK(dm.alloc(msg_bytes)); HIPCHK(doff.alloc(off_bytes));
+    DBuf dp, dx, ds, dok;
+    HIPCHK(dp.alloc(pin * npk)); HIPCHK(dx.alloc(sizeof(uint32_t) * total));
     HIPCHK(ds.alloc((size_t)k.sig_bytes * m)); HIPCHK(dok.alloc(m));
     if (npk) HIPCHK(hipMemcpyAsync(dp.p, pks, pin * npk, hipMemcpyHostToDevice, g_stream));
     if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
-    if (msg_bytes) HIPCHK(hipMemcpyAsync(dm.p, msgs, msg_bytes, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, off_bytes, hipMemcpyHostToDevice, g_stream));
+    rc = dm.upload(msgs, off_or_domain, g_stream);
+    if (rc) return rc;
     rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, m, g_stream);
     if (rc) return rc;
-    rc = agg_common_batch_dev(kind, dm.p, doff.p, dp.p, npk, idx ? dx.as<u32>() : nullptr, plan, ds.p, dok.p, pj);
+    rc = agg_common_batch_dev(kind, dm.m.p, dm.off.p, dp.p, npk, idx ? dx.as<u32>() : nullptr, plan, ds.p, dok.p, pj);
     if (rc) return rc;
-    std::vector<uint8_t> tmp;
-    uint8_t* dst = ok;
-    if (!dst) { tmp.resize(m); dst = tmp.data(); }
-    HIPCHK(hipMemcpyAsync(dst, dok.p, m, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
-    if (ok_bitmap) pack_bitmap(dst, ok_bitmap, m);
-    return BLSMI_OK;
+    return fetch_verdicts(dok.p, ok, ok_bitmap, m, g_stream);
 }
 template <int KIND>
 static int agg_common_batch_dev_api(const void* d_msgs, const void* d_off_or_domain, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off,
@@ -2013,9 +2003,7 @@ namespace {
 void launch_miller_tuples(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, Layout l) {
     prof_mark(l == Layout::wave ? "k_lat:miller1raw" : l == Layout::row ? "k_miller1h_row" : l == Layout::quad ? "k_miller1h_quad" : l == Layout::pair ? "k_miller1h_pair" : "k_miller1h");
     if (l == Layout::wave)
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)n), dim3(64), lat_lds_bytes(LAT_MILLER1RAW_OFFSET), s, (const u8*)g_gens.lat + LAT_MILLER1RAW_OFFSET,
-                           d_g1, (size_t)96, d_g2, (size_t)192, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, reinterpret_cast<u64*>(f), n);
+        launch_lat(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
     else if (l == Layout::row) hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
     else if (l == Layout::quad) hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
     else if (l == Layout::pair) hipLaunchKernelGGL(k_miller1h_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, s, d_g1, d_g2, f, n);
@@ -2055,9 +2043,7 @@ int seg_prod_dev(const i32* src, size_t nsrc, const u8* skip, const SegPlan& pla
 void final_exp_values(Layout fe, const void* prod, u64* out, void* d_is_one, size_t m, hipStream_t s) {
     prof_mark(fe == Layout::wave ? "k_lat:finalexp1" : fe == Layout::row ? "k_final_exp_row" : fe == Layout::quad ? "k_final_exp_quad" : fe == Layout::pair ? "k_final_exp_pair" : "k_final_exp");
     if (fe == Layout::wave)
-        hipLaunchKernelGGL(k_lat, dim3((unsigned)m), dim3(64), lat_lds_bytes(LAT_FINALEXP1_OFFSET), s, (const u8*)g_gens.lat + LAT_FINALEXP1_OFFSET,
-                           (const u8*)prod, (size_t)576, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0, (const u8*)nullptr, (size_t)0,
-                           (const u8*)nullptr, (u8*)nullptr, out, m);
+        launch_lat(LAT_FINALEXP1_OFFSET, s, {.b0 = {prod, 576}, .out = out}, m);
     else if (fe == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
     else if (fe == Layout::quad) hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
     else if (fe == Layout::pair) hipLaunchKernelGGL(k_final_exp_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
