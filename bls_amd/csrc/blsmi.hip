@@ -9,6 +9,7 @@
 #include "route.h"
 #include "group_plan.h"
 #include "locate_plan.h"
+#include "cell_plan.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

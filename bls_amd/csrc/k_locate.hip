@@ -1,7 +1,8 @@
 // k_locate.hip -- the housekeeping kernels of the block-locating randomised verification (blsmi 0.12: blsmi_g?pubs_*verify*_batch_rlc_locate,
-// verify_host.inc): the signature-side pairs of the block checks, the verdict byte of every block, and the gathers / the scatter that
-// move the tuples of the failing blocks into dense buffers for the per-tuple stage and their verdicts back.  The product of a block's
-// Miller values with its signature side's is k_fq12_mul_pairs_row (k_fq12_seg.hip).
+// rlc_host.hpp) and of its grouped form (blsmi 0.13: ..._rlc_grouped_locate, whose blocks are the cells of cell_plan.h): the signature-side
+// pairs of the block checks, the verdict byte of every block / cell, and the gathers / the scatter that move the tuples of the failing
+// ones into dense buffers for the per-tuple stage and their verdicts back.  The product of a block's Miller values with its signature
+// side's is k_fq12_mul_pairs_row (k_fq12_seg.hip).
 #include "tower.cuh"
 #include "device_io.cuh"
 
@@ -40,6 +41,26 @@ KERNEL2 k_locate_block_fail(const u8* flags, const u8* flags2, size_t n, size_t 
     for (size_t i = lo + l; i < hi; i += 16) f |= (u32)flags[i] | flags2[i];
     f |= __shfl_xor(f, 1); f |= __shfl_xor(f, 2); f |= __shfl_xor(f, 4); f |= __shfl_xor(f, 8);
     if (b < nb && l == 0) fail[b] = (f || bad[b] || !is_one[b]) ? 1 : 0;
+}
+
+// The same for the cells of a grouped call: cell c is the tuples perm[cell_off[c] .. cell_off[c + 1]) -- ragged, and scattered over the call's
+// flag bytes, so every lane goes through perm (the uniform stride above does not serve).  cell_bad: the flag byte of the cell's key sum;
+// flags2 may be null (this form scales no point per tuple).  Sixteen lanes per cell, lane l takes positions l, l + 16, ... of its cell; the
+// OR across the sixteen stays inside their DPP row.  n: the tuples of the call, every perm entry below it.
+KERNEL2 k_locate_cell_fail(const u8* flags, const u8* flags2, const u32* perm, const u64* cell_off, const u8* cell_bad, const u8* bad, const u8* is_one, u8* fail, size_t n, size_t nc) {
+    const u32 l = threadIdx.x & 15;
+    const size_t c = (size_t)blockIdx.x * (WG / 16) + (threadIdx.x >> 4);
+    const size_t cc = c < nc ? c : nc - 1;
+    const u64 lo = cell_off[cc], hi = cell_off[cc + 1];
+    u32 f = 0;
+    for (u64 k = lo + l; k < hi; k += 16) {
+        const u32 i = perm[k];
+        if (i >= n) { f = 1; continue; }                                   // (the host's plan never has one: such a cell would fail, nothing is read)
+        f |= flags[i];
+        if (flags2) f |= flags2[i];
+    }
+    f |= __shfl_xor(f, 1); f |= __shfl_xor(f, 2); f |= __shfl_xor(f, 4); f |= __shfl_xor(f, 8);
+    if (c < nc && l == 0) fail[c] = (f || cell_bad[c] || bad[c] || !is_one[c]) ? 1 : 0;
 }
 
 // dst record r = src record idx[r] for records of q 16-byte pieces (96 bytes: 6, 192 bytes: 12), a lane per piece: the q lanes of a record

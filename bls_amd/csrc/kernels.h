@@ -62,6 +62,7 @@ __global__ void k_fq12_is_one_m384(const u64* vals, u8* is_one, size_t n);
 // k_locate.hip
 __global__ void k_locate_sig_pairs(int kind, const u8* sums, const u8* s_inf, const u8* gen1, const u8* gen2, u8* g1, u8* g2, u8* bad, size_t nb);
 __global__ void k_locate_block_fail(const u8* flags, const u8* flags2, size_t n, size_t block, const u8* bad, const u8* is_one, u8* fail, size_t nb);
+__global__ void k_locate_cell_fail(const u8* flags, const u8* flags2, const u32* perm, const u64* cell_off, const u8* cell_bad, const u8* bad, const u8* is_one, u8* fail, size_t n, size_t nc);
 __global__ void k_gather_records16(const uint4* src, const u32* idx, uint4* dst, u32 q, size_t n);
 __global__ void k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n);

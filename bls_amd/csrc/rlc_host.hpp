@@ -1,5 +1,5 @@
-// rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped and
-// ..._rlc_locate.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The three
+// rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
+// ..._rlc_locate and ..._rlc_grouped_locate.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -334,18 +334,14 @@ BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_jac(const uint8_t* msgs3
 // (an input, a group's sum, the signatures' sum), the per-tuple verdicts of verify_batch come from the buffers on the device, the d' hash
 // points gathered per tuple (k_gather_records).
 namespace {
-int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
-                                  const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
-    if (combined) *combined = 0;
-    int rc = rlc_check_args(msgs && off_or_domain && msg_idx && pks && sigs && n <= 0xffffffffull, scalars, n);   // (n: the permutation is the 32-bit idx of the segmented sum)
-    if (rc || n == 0) return rc;
-    blsmi_route::GroupPlan gp;
-    std::vector<uint64_t> coff;
-    std::vector<uint8_t> cm;
+// The host plan of a grouped call (group_plan.h) and the messages some tuple refers to, compacted in table order into cm with the offsets
+// coff (kind 2: 32 bytes each, no offsets) -- an entry nobody refers to is never hashed.  BLSMI_E_ARG: some msg_idx[i] >= d (d == 0
+// included), or offsets that decrease.
+int grouped_plan_and_messages(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, size_t n, blsmi_route::GroupPlan& gp,
+                              std::vector<uint64_t>& coff, std::vector<uint8_t>& cm) {
     try {
-        if (!blsmi_route::group_plan(msg_idx, n, d, gp)) return BLSMI_E_ARG;   // some msg_idx[i] >= d (d == 0 included)
+        if (!blsmi_route::group_plan(msg_idx, n, d, gp)) return BLSMI_E_ARG;
         const size_t dg = gp.msg_of.size();
-        // the messages some tuple refers to, compacted in table order (an entry nobody refers to is never hashed)
         if (kind == 2) {
             cm.resize(32 * dg);
             for (size_t g = 0; g < dg; g++) memcpy(cm.data() + 32 * g, msgs + (size_t)32 * gp.msg_of[g], 32);
@@ -360,6 +356,17 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
             for (size_t g = 0; g < dg; g++) if (coff[g + 1] > coff[g]) memcpy(cm.data() + coff[g], msgs + off_or_domain[gp.msg_of[g]], (size_t)(coff[g + 1] - coff[g]));
         }
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    return BLSMI_OK;
+}
+int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* inf_flags, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    int rc = rlc_check_args(msgs && off_or_domain && msg_idx && pks && sigs && n <= 0xffffffffull, scalars, n);   // (n: the permutation is the 32-bit idx of the segmented sum)
+    if (rc || n == 0) return rc;
+    blsmi_route::GroupPlan gp;
+    std::vector<uint64_t> coff;
+    std::vector<uint8_t> cm;
+    rc = grouped_plan_and_messages(kind, msgs, off_or_domain, d, msg_idx, n, gp, coff, cm); if (rc) return rc;
     RlcHostScratch hs;
     rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap, n); if (rc) return rc;
     { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
@@ -485,21 +492,24 @@ int locate_failing_positions(RlcCall& c, const blsmi_route::LocatePlan& lp, cons
     return BLSMI_OK;
 }
 // Stage 6: the tuples at `pos` (those of the failing blocks), gathered into dense buffers with their hash points h; verify_batch's pair stage
-// routed by their count; the verdicts back into c.dok
-int locate_recheck(RlcCall& c, const DBuf& h, const std::vector<uint32_t>& pos) {
+// routed by their count; the verdicts back into c.dok.  hpos (null: pos): a second index list, as long as pos, where the hash point of
+// pos[r] is h[hpos[r]] -- a grouped call keeps one hash point per message.
+int locate_recheck(RlcCall& c, const DBuf& h, const std::vector<uint32_t>& pos, const std::vector<uint32_t>* hpos = nullptr) {
     const Kind& k = c.k;
     const size_t nre = pos.size(), words = (size_t)12 * NL;
     hipStream_t s = g_stream;
-    DBuf dpos, hd, pd, sd, id, okd, f;
+    DBuf dpos, dhpos, hd, pd, sd, id, okd, f;
     HIPCHK(dpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hd.alloc((size_t)k.h_bytes * nre)); HIPCHK(pd.alloc((size_t)k.pk_bytes * nre)); HIPCHK(sd.alloc((size_t)k.sig_bytes * nre));
     HIPCHK(id.alloc(nre)); HIPCHK(okd.alloc(nre)); HIPCHK(f.alloc(sizeof(i32) * words * nre));
     HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
-    auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) {
+    if (hpos) { HIPCHK(dhpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hipMemcpyAsync(dhpos.p, hpos->data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s)); }
+    auto gather_by = [&](const DBuf& from, DBuf& to, size_t bytes, const DBuf& by) {
         const u32 q = (u32)(bytes / 16);
-        hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)dpos.as<u32>(), to.as<uint4>(), q, nre);
+        hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)by.as<u32>(), to.as<uint4>(), q, nre);
     };
+    auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) { gather_by(from, to, bytes, dpos); };
     prof_mark("k_gather_records16");
-    gather(h, hd, k.h_bytes); gather(c.dp, pd, k.pk_bytes); gather(c.ds, sd, k.sig_bytes);
+    gather_by(h, hd, k.h_bytes, hpos ? dhpos : dpos); gather(c.dp, pd, k.pk_bytes); gather(c.ds, sd, k.sig_bytes);
     if (c.has_inf) hipLaunchKernelGGL(k_gather_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)c.di.as<u8>(), (const u32*)dpos.as<u32>(), id.as<u8>(), nre);
     prof_mark(nullptr);
     const VerifyRoute vr = verify_route(c.kind, nre, false, false, tune(), route_load(nre));
@@ -596,4 +606,162 @@ BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t
                                                                    uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
     return verify_batch_rlc_locate_host(2, msgs32, reinterpret_cast<const uint64_t*>(domain), JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC);
 }
+// ---- grouped randomised batch verification that finds the bad tuples by cells (blsmi 0.13; include/blsmi.h "grouped_locate") -------------
+// The grouped form's combined check with every group cut into cells of at most `block` tuples (cell_plan.h), and BOTH sides summed per
+// cell from the start: K_c = sum_{i in c} r_i pk_i and S_c = sum_{i in c} r_i sig_i, two weighted segmented sums over one plan (idx = the
+// group plan's permutation, the cells as segments), the keys on the main stream, the signatures on the side stream in place of
+// rlc_sig_sum's MSM.  sum_i r_i sig_i is then the plain sum of the C values S_c, and the tuple side's total the product of the C Miller
+// values of (H_g(c), K_c) / (K_c, H_g(c)), which are KEPT.  When the total fails, or something is flagged, one equation per cell decides --
+//     g2pubs: e(S_c, G2gen) == e(H_g(c), K_c)        g1pubs: e(G1gen, S_c) == e(K_c, H_g(c))
+// -- from what is on the device: C Miller loops for the signature side, each times its kept cell value, C final exponentiations.  Nothing
+// is scaled again.  The tuples of the failing cells go through locate_recheck.  One value per cell in every layout: the cells' Miller loops
+// take the route of a Pairing call of C tuples (launch_miller_tuples), not an aggregate's, whose quad and pair layouts leave one value per
+// two consecutive records and would merge neighbouring cells.  One lease, one device, no request combiner, "rlc_min" not consulted.
+namespace {
+// what the driver keeps per cell on the device: the two sums with their flags, and the Miller values of the tuple side
+struct CellBufs { DBuf dx, kc, kinf, kflag, sc, scinf, cval; };
+// S_c for every cell, their sum into c.sum / c.sflag and its Miller loop, on the side stream (as rlc_signature_side; dx, the permutation,
+// is on the device by the time `fork` says so)
+int cells_signature_side(RlcCall& c, const SegPlan& plan, CellBufs& b) {
+    hipStream_t st = tl_ctx->aux[0];
+    const size_t C = plan.m;
+    HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+    OnStream on(st);
+    int rc = segsum_dev(c.k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, c.n, b.dx.as<u32>(), plan, b.sc.as<u8>(), b.scinf.as<u8>(), 1, st, c.dr.as<u64>());
+    if (rc) return rc;
+    rc = c.kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false)
+                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
+}
+// When the total failed: the C signature-side Miller values of (-S_c, G2gen) / (-G1gen, S_c), each times its cell value, the final
+// exponentiations, one byte per cell (k_locate_cell_fail); then the tuples of the failing cells.  Synchronises the main stream.
+int cells_failing_positions(RlcCall& c, const blsmi_route::GroupPlan& gp, const blsmi_route::CellPlan& cp, CellBufs& b, std::vector<uint32_t>& pos, std::vector<uint32_t>& grp) {
+    const size_t C = cp.cells(), words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    std::vector<uint8_t> fail;
+    try { fail.resize(C); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t cload = route_load(C);
+    const Layout fe = pprod_fe_layout(C, cload);
+    DBuf g1, g2, sbad, fs, prod, vals, one, dfail, doff;
+    HIPCHK(g1.alloc((size_t)96 * C)); HIPCHK(g2.alloc((size_t)192 * C)); HIPCHK(sbad.alloc(C)); HIPCHK(fs.alloc(sizeof(i32) * words * C));
+    HIPCHK(prod.alloc(fe == Layout::wave ? 576 * C : sizeof(i32) * words * C)); HIPCHK(vals.alloc(576 * C)); HIPCHK(one.alloc(C)); HIPCHK(dfail.alloc(C));
+    HIPCHK(doff.alloc(sizeof(uint64_t) * (C + 1)));
+    HIPCHK(hipMemcpyAsync(doff.p, cp.cell_off.data(), sizeof(uint64_t) * (C + 1), hipMemcpyHostToDevice, s));
+    prof_mark("k_locate_sig_pairs");
+    hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(C)), dim3(WG), 0, s, c.kind == 0 ? 0 : 1, (const u8*)b.sc.as<u8>(), (const u8*)b.scinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
+                       g1.as<u8>(), g2.as<u8>(), sbad.as<u8>(), C);
+    launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), C, s, pairing_layout(0, C, tune(), cload));
+    prof_mark("k_fq12_mul_pairs_row");
+    hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(C)), dim3(WG), 0, s, (const i32*)b.cval.as<i32>(), (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
+                       fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, C);
+    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, C, s);
+    prof_mark("k_locate_cell_fail");
+    hipLaunchKernelGGL(k_locate_cell_fail, dim3(rblocks(C)), dim3(WG), 0, s, (const u8*)c.flags.as<u8>(), (const u8*)nullptr, (const u32*)b.dx.as<u32>(), (const u64*)doff.as<u64>(),
+                       (const u8*)b.kflag.as<u8>(), (const u8*)sbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), c.n, C);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, C, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    try { blsmi_route::cell_positions(gp, cp, fail.data(), pos, grp); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    return BLSMI_OK;
+}
+int verify_batch_rlc_grouped_locate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                         const uint8_t* inf_flags, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked, int fmt = 0) {
+    if (combined) *combined = 0;
+    if (rechecked) *rechecked = 0;
+    int rc = rlc_check_args(msgs && off_or_domain && msg_idx && pks && sigs && n <= 0xffffffffull, scalars, n);   // (n: the permutation and the positions are 32-bit indices)
+    if (rc || n == 0) return rc;
+    blsmi_route::GroupPlan gp;
+    blsmi_route::CellPlan cp;
+    std::vector<uint64_t> coff;
+    std::vector<uint8_t> cm;
+    rc = grouped_plan_and_messages(kind, msgs, off_or_domain, d, msg_idx, n, gp, coff, cm); if (rc) return rc;
+    RlcHostScratch hs;
+    rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap, n); if (rc) return rc;
+    { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const Tuning& t = tune();
+    SegPlan plan;
+    try {
+        blsmi_route::cell_plan(gp, block ? block : blsmi_route::locate_auto_block(n), cp);
+        segsum_plan(cp.cell_off.data(), cp.cells(), segsum_chunk_of(n), plan, 64, 1);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t dg = gp.msg_of.size(), C = cp.cells(), half = (C + 1) / 2;
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    RlcCall c;
+    rc = rlc_begin(c, kind, n, kind == 2 ? (const void*)off_or_domain : (const void*)coff.data(), dg);   // the d' messages some tuple refers to
+    if (rc) return rc;
+    const Kind& k = c.k;
+    const HashRoute hr = aggregate_route(kind, dg, false, true, t, route_load(dg)).hash;   // the hash of the grouped form; always cleared hash points
+    CellBufs b;
+    DBuf h, hc, dcg, t0, t1;
+    HIPCHK(b.dx.alloc(sizeof(uint32_t) * n)); HIPCHK(b.kc.alloc((size_t)k.pk_bytes * C)); HIPCHK(b.kinf.alloc(C)); HIPCHK(b.kflag.alloc(C));
+    HIPCHK(b.sc.alloc((size_t)k.sig_bytes * C)); HIPCHK(b.scinf.alloc(C)); HIPCHK(b.cval.alloc(sizeof(i32) * words * C));
+    HIPCHK(h.alloc((size_t)k.h_bytes * dg)); HIPCHK(hc.alloc((size_t)k.h_bytes * C)); HIPCHK(dcg.alloc(sizeof(uint32_t) * C));
+    HIPCHK(t0.alloc(sizeof(i32) * words * half)); HIPCHK(t1.alloc(sizeof(i32) * words * half));
+    // the uploads, the hash and the flags as in the grouped form; the permutation goes ahead of the keys and `fork` is recorded again behind it,
+    // since the side stream's sums read it
+    rc = rlc_upload_start(c, sigs, scalars, cm.data(), kind == 2 ? (const void*)off_or_domain : (const void*)coff.data(), fmt); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(b.dx.p, gp.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dcg.p, cp.group_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));
+    HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
+    rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), dg, s, hr);
+    if (rc) return rc;
+    rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
+    rlc_flag_inputs(c);
+    // K_c for every cell (on the main stream: the profile names k_g?_segsum_chunk_u64 there); a sum at infinity is flagged per cell
+    rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, b.dx.as<u32>(), plan, b.kc.as<u8>(), b.kinf.as<u8>(), 1, s, c.dr.as<u64>());
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(C)), dim3(WG), 0, s, (const u8*)b.kc.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)b.kinf.as<u8>(), b.kflag.as<u8>(), c.any.as<int>(), C);
+    // every cell its group's hash point, C Miller loops with one value each, the values kept; the tree over them gives the total
+    const u32 hw = (u32)(k.h_bytes / 4);
+    hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * C)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dcg.as<u32>(), hc.as<u32>(), hw, C);
+    launch_miller_tuples(kind == 0 ? hc.as<u8>() : b.kc.as<u8>(), kind == 0 ? b.kc.as<u8>() : hc.as<u8>(), b.cval.as<i32>(), C, s, pairing_layout(0, C, t, route_load(C)));
+    prof_mark(nullptr);
+    const i32* total = prod_tree(b.cval.as<i32>(), C, t0.as<i32>(), t1.as<i32>(), s);
+    HIPCHK(hipGetLastError());
+    rc = cells_signature_side(c, plan, b); if (rc) return rc;
+    rc = rlc_check_total(c, total, false); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c.dok.p, 1, n, s));
+    std::vector<uint32_t> pos, grp;
+    if (!c.held()) { rc = cells_failing_positions(c, gp, cp, b, pos, grp); if (rc) return rc; }
+    const size_t nre = pos.size();
+    if (nre) { rc = locate_recheck(c, h, pos, &grp); if (rc) return rc; }
+    rc = rlc_finish(c, ok, ok_bitmap, combined);
+    if (rechecked && !rc) *rechecked = nre;
+    return rc;
+}
+}  // namespace
+#define GLOC(kind, m, o) return verify_batch_rlc_grouped_locate_host(kind, m, o, d, msg_idx, pks, sigs, inf_flags, scalars, block, ok, ok_bitmap, n, combined, rechecked)
+#define GLOCJ(kind, m, o) return verify_batch_rlc_grouped_locate_host(kind, m, o, d, msg_idx, JACP(pks), JACP(sigs), nullptr, scalars, block, ok, ok_bitmap, n, combined, rechecked, FMT_JAC)
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped_locate(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                           const uint8_t* inf_flags, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOC(0, msgs, msg_off);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped_locate(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                           const uint8_t* inf_flags, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOC(1, msgs, msg_off);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint8_t* pks, const uint8_t* sigs,
+                                                                       const uint8_t* inf_flags, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOC(2, msgs32, reinterpret_cast<const uint64_t*>(domain));
+}
+BLSMI_API int blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                               const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOCJ(0, msgs, msg_off);
+}
+BLSMI_API int blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac(const uint8_t* msgs, const uint64_t* msg_off, size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                               const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOCJ(1, msgs, msg_off);
+}
+BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac(const uint8_t* msgs32, const uint8_t domain[8], size_t d, const uint32_t* msg_idx, const uint64_t* pks, const uint64_t* sigs,
+                                                                           const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* ok_bitmap, size_t n, int* combined, size_t* rechecked) {
+    GLOCJ(2, msgs32, reinterpret_cast<const uint64_t*>(domain));
+}
+#undef GLOC
+#undef GLOCJ
 #undef JACP

@@ -1388,3 +1388,59 @@ def g1pubs_verify_batch_rlc_locate_jac(msgs, pks, sigs, scalars=None, block=0):
 
 def g1pubs_verify_with_domain_batch_rlc_locate_jac(msgs32, domain8, pks, sigs, scalars=None, block=0):
     return _verify_batch_rlc_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac", 2, True, msgs32, pks, sigs, None, scalars, block, domain8)
+
+
+# ---- grouped randomised batch verification that finds the bad tuples by cells (blsmi 0.13) ---------------------------------------------
+# the argument types of the six entry points of 0.13, as include/blsmi.h declares them (tests/test_rlc_grouped_locate_cpu.py compares)
+ARGTYPES_0_13 = {
+    "blsmi_g2pubs_verify_batch_rlc_grouped_locate": _G_HEAD + [_u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_grouped_locate": _G_HEAD + [_u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate": _G_HEAD_DOMAIN + [_u8p, _u8p, _u8p] + _L_TAIL,
+    "blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac": _G_HEAD + [_u64p, _u64p] + _L_TAIL,
+    "blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac": _G_HEAD + [_u64p, _u64p] + _L_TAIL,
+    "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac": _G_HEAD_DOMAIN + [_u64p, _u64p] + _L_TAIL,
+}
+
+
+def _verify_batch_rlc_grouped_locate(name, kind, jac, msgs, msg_idx, pks, sigs, inf_flags, scalars, block, domain8=None):
+    """-> (ok, bitmap, combined, rechecked); msgs: the table of d messages, msg_idx: n indices into it"""
+    n = len(msg_idx)
+    block = int(block)
+    if block < 0:
+        raise ValueError("block must not be negative")
+    ix, pix = _msg_idx(msg_idx, n)
+    head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
+    rechecked = C.c_size_t(0)
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_13[name]
+    fn.restype = C.c_int
+    _check(fn(*head, len(msgs), pix, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
+    return ok.astype(bool), bitmap, comb.value, rechecked.value
+
+
+def g2pubs_verify_batch_rlc_grouped_locate(msgs, msg_idx, pks, sigs, inf_flags=None, scalars=None, block=0):
+    """blsmi_g2pubs_verify_batch_rlc_grouped_locate -> (ok, bitmap, combined, rechecked): g2pubs_verify_batch_rlc_grouped's total check over
+    cells of at most `block` tuples of one message (0: automatic; else any value >= 1); when it fails, one pairing equation per cell and
+    verify_batch's verdicts for the tuples of the failing cells only -- `rechecked` of them."""
+    return _verify_batch_rlc_grouped_locate("blsmi_g2pubs_verify_batch_rlc_grouped_locate", 0, False, msgs, msg_idx, pks, sigs, inf_flags, scalars, block)
+
+
+def g1pubs_verify_batch_rlc_grouped_locate(msgs, msg_idx, pks, sigs, inf_flags=None, scalars=None, block=0):
+    return _verify_batch_rlc_grouped_locate("blsmi_g1pubs_verify_batch_rlc_grouped_locate", 1, False, msgs, msg_idx, pks, sigs, inf_flags, scalars, block)
+
+
+def g1pubs_verify_with_domain_batch_rlc_grouped_locate(msgs32, domain8, msg_idx, pks, sigs, inf_flags=None, scalars=None, block=0):
+    return _verify_batch_rlc_grouped_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate", 2, False, msgs32, msg_idx, pks, sigs, inf_flags, scalars, block, domain8)
+
+
+def g2pubs_verify_batch_rlc_grouped_locate_jac(msgs, msg_idx, pks, sigs, scalars=None, block=0):
+    """the same over in-memory points (288 / 144 bytes each)"""
+    return _verify_batch_rlc_grouped_locate("blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac", 0, True, msgs, msg_idx, pks, sigs, None, scalars, block)
+
+
+def g1pubs_verify_batch_rlc_grouped_locate_jac(msgs, msg_idx, pks, sigs, scalars=None, block=0):
+    return _verify_batch_rlc_grouped_locate("blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac", 1, True, msgs, msg_idx, pks, sigs, None, scalars, block)
+
+
+def g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac(msgs32, domain8, msg_idx, pks, sigs, scalars=None, block=0):
+    return _verify_batch_rlc_grouped_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac", 2, True, msgs32, msg_idx, pks, sigs, None, scalars, block, domain8)

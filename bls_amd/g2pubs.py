@@ -186,6 +186,24 @@ def VerifyBatchRandomizedGrouped(msgs, msg_idx, pubs, sigs, scalars=None):
     return [bool(x) for x in ok]
 
 
+def VerifyBatchRandomizedGroupedLocate(msgs, msg_idx, pubs, sigs, scalars=None, block=0):
+    """VerifyBatchRandomizedGrouped for input an adversary may have touched: every message's tuples are cut into cells of at most `block`
+    tuples (0: automatic; else any value >= 1), the combined check runs over the cells' sums, and when it fails one pairing equation per
+    cell finds the cells that hold -- only the tuples of the others go through the per-tuple path.  Verdicts as VerifyBatch on the
+    expanded messages."""
+    n = len(msg_idx)
+    if not (len(pubs) == len(sigs) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return []
+    if all_in_memory([p.p for p in pubs] + [s.s for s in sigs]):
+        ok = engine.g2pubs_verify_batch_rlc_grouped_locate_jac(msgs, msg_idx, b"".join(p.p.jac for p in pubs), b"".join(s.s.jac for s in sigs), scalars, block)[0]
+        return [bool(x) for x in ok]
+    flags = [(1 if p.p.infinity else 0) | (2 if s.s.infinity else 0) for p, s in zip(pubs, sigs)]
+    ok = engine.g2pubs_verify_batch_rlc_grouped_locate(msgs, msg_idx, b"".join(p.p.bytes_or_zero() for p in pubs), b"".join(s.s.bytes_or_zero() for s in sigs), flags, scalars, block)[0]
+    return [bool(x) for x in ok]
+
+
 def VerifyBatchRandomizedLocate(msgs, pubs, sigs, scalars=None, block=0):
     """VerifyBatchRandomized for input an adversary may have touched: when the combined check fails, one pairing equation per block of `block`
     tuples (0: automatic; else even and at least 2) finds the blocks that hold, and only the tuples of the others go through the per-tuple

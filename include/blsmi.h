@@ -79,8 +79,10 @@ void blsmi_shutdown(void);
  * checks in one call); no existing prototype changes, no new option.  0.11 adds the grouped randomised batch verification
  * (blsmi_g?pubs_*verify*_batch_rlc_grouped[_jac]: the tuples of one message share one pairing) and the weighted segmented sums
  * (blsmi_g?_sum_segmented_u64); no existing prototype changes, no new option.  0.12 adds the randomised batch verification that
- * finds the bad tuples by blocks (blsmi_g?pubs_*verify*_batch_rlc_locate[_jac]); no existing prototype changes, no new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11 and 0.12 by the presence of those symbols. */
+ * finds the bad tuples by blocks (blsmi_g?pubs_*verify*_batch_rlc_locate[_jac]); no existing prototype changes, no new option.  0.13 adds the grouped
+ * randomised batch verification that finds the bad tuples by cells (blsmi_g?pubs_*verify*_batch_rlc_grouped_locate[_jac]); no existing prototype
+ * changes, no new option.  The string below still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12 and 0.13 by the presence of
+ * those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -491,6 +493,70 @@ int blsmi_g1pubs_verify_batch_rlc_locate_jac(const uint8_t *msgs, const uint64_t
                                              const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
 int blsmi_g1pubs_verify_with_domain_batch_rlc_locate_jac(const uint8_t *msgs32, const uint8_t domain[8], const uint64_t *pks /* n*18 */, const uint64_t *sigs /* n*36 */,
                                                          const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+/* ---- grouped randomised batch verification that finds the bad tuples by cells (blsmi 0.13) -----------------------------------
+ * *_verify_batch_rlc_grouped for input an adversary may have touched: the batches that share messages (a subnet, a slot, a sync
+ * committee) are the ones anybody can put a bad signature into, and there one invalid tuple sends all n through the per-tuple path.  The
+ * arguments are those of *_verify_batch_rlc_grouped with `block` after `scalars` and `rechecked` at the end, as in *_verify_batch_rlc_locate;
+ * ok, ok_bitmap, inf_flags, scalars and combined mean what they mean in the grouped form, rechecked what it means in the block-locating
+ * form, and the verdicts are those of *_verify_batch on the expanded messages.
+ * The tuples are sorted by message (stable: the tuples of one message keep their input order), and every message's tuples are cut, in that
+ * order, into CELLS of at most `block` consecutive tuples: in each group every cell but the last is full, and no cell crosses a group
+ * border.  The call sums keys AND signatures per cell -- K_c = sum_{i in c} r_i pk_i, S_c = sum_{i in c} r_i sig_i -- runs one Miller loop
+ * per cell and keeps its value; the total check is the grouped form's, its two sides being the product of the cell values and the sum of
+ * the S_c.  When it fails, one pairing equation per cell decides, from what is already on the device (nothing is scaled again) --
+ *     g2pubs: e(S_c, G2gen) == e(H(m_g(c)), K_c)        g1pubs: e(G1gen, S_c) == e(K_c, H(m_g(c)))
+ * -- and the tuples of the cells that fail, and only those, get the per-tuple verdicts of *_verify_batch.  A cell's weights are its own
+ * tuples' r_i, so a cell whose equation holds is wrong with probability at most 2^-64, as the whole batch is.  With caller scalars
+ * r_a == r_c two tuples OF ONE CELL may carry sig_a + D and sig_c - D unnoticed, and two tuples of one group may swap signatures (the
+ * grouped form's caveat) -- the caller's responsibility, as every caller scalar is.  The subgroup precondition of *_verify_batch_rlc applies.
+ *   - block: 0 = automatic, the rule of *_verify_batch_rlc_locate (the next even number >= max(64, ceil(n / 256))).  Any other value >= 1 is
+ *     accepted; there is no evenness rule here, each cell has a Miller loop of its own.  block >= the largest group makes cells equal to
+ *     groups: the call then locates by message.
+ *   - msg_idx[i] >= d (d = 0 with n > 0 included), a zero caller scalar, a NULL input with n > 0, and n > 2^32 - 1: BLSMI_E_ARG before any
+ *     device work.  n = 0: BLSMI_OK, combined = 0, rechecked = 0.
+ *   - combined (may be NULL): 1 exactly when the total check held (every verdict is 1 then); 0 otherwise and for n = 0.
+ *   - rechecked (may be NULL): the number of tuples whose verdict came from the per-tuple path -- 0 when the total check held, the sum of the
+ *     sizes of the failing cells otherwise.
+ *   - a cell fails, whatever its equation says, when one of its tuples is at infinity (inf_flags, the all-zero record, z = 0 in the
+ *     in-memory forms), its K_c is, or its S_c is; with such a tuple or K_c anywhere, or sum r_i sig_i at infinity, the total's verdict is
+ *     not consulted and the cell checks run.
+ * "rlc_min" does NOT apply, the call runs on one device and never joins the request combiner, as the grouped form.  The hash points are
+ * always cleared of their cofactor.
+ * When to call it (one MI355X, host buffers, ms, median of 10; profiles/r10_rlc_grouped_locate.log; grouped / batch =
+ * *_verify_batch_rlc_grouped and *_verify_batch, messages expanded, of the build before this form, on the same tuples):
+ *     n x d, bad tuples          g2pubs cells / grouped / batch      g1pubs cells / grouped / batch
+ *     16 384 x 64, none                6.8 / 10.1 /  8.5                  7.7 / 12.4 / 10.4
+ *     16 384 x 64, one                10.3 / 17.3 /  8.2                 11.2 / 20.1 /  9.9
+ *     65 536 x 64, none               11.9 / 13.3 / 25.3                 12.6 / 14.6 / 31.1
+ *     65 536 x 64, one                15.5 / 36.0 / 24.4                 16.2 / 39.7 / 29.7
+ *     65 536 x 64, 16 in 16 cells     16.6 / 36.1 / 24.6                 17.8 / 39.8 / 29.7
+ *     65 536 x 8 192, none            18.5 / 18.7 / 25.4                 20.6 / 18.1 / 31.0
+ * (spreads, max - min of the ten, 0.05 .. 0.8 ms.)  With one bad tuple at 65 536 x 64 the call costs 0.43x / 0.41x the grouped form's failing call and
+ * stays below *_verify_batch; a failing call pays about 3.6 ms over the call that holds -- 256 Miller loops and final exponentiations and
+ * the 256 rechecked tuples, no sum is taken again.  The call that holds is not slower than the grouped form where messages are shared widely
+ * (-1.4 / -2.1 ms at 65 536 x 64, -3.2 / -4.8 ms at 16 384 x 64: the signatures' segmented sum is enqueued whole, the MSM it replaces waits on
+ * the host between its passes); with few tuples per message it is level (g2pubs) or slower (g1pubs +2.5 ms at 65 536 x 8 192: 8 192 cells, a
+ * Miller loop and a final pass of the G2 sums each): call *_verify_batch_rlc_locate or *_verify_batch_rlc_grouped there.  At 16 384 x 64 one
+ * bad tuple still leaves *_verify_batch the faster call (8.2 / 9.9 ms). */
+int blsmi_g2pubs_verify_batch_rlc_grouped_locate(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* n */,
+                                                 const uint8_t *pks /* n*192 */, const uint8_t *sigs /* n*96 */, const uint8_t *inf_flags,
+                                                 const uint64_t *scalars /* n, may be NULL */, size_t block, uint8_t *ok /* n, may be NULL */, uint8_t *ok_bitmap /* may be NULL */,
+                                                 size_t n, int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_batch_rlc_grouped_locate(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* n */,
+                                                 const uint8_t *pks /* n*96 */, const uint8_t *sigs /* n*192 */, const uint8_t *inf_flags,
+                                                 const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate(const uint8_t *msgs32 /* d*32 */, const uint8_t domain[8], size_t d, const uint32_t *msg_idx /* n */,
+                                                             const uint8_t *pks, const uint8_t *sigs, const uint8_t *inf_flags,
+                                                             const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n, int *combined, size_t *rechecked);
+int blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*36 */,
+                                                     const uint64_t *sigs /* n*18 */, const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n,
+                                                     int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*18 */,
+                                                     const uint64_t *sigs /* n*36 */, const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n,
+                                                     int *combined, size_t *rechecked);
+int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac(const uint8_t *msgs32, const uint8_t domain[8], size_t d, const uint32_t *msg_idx, const uint64_t *pks /* n*18 */,
+                                                                 const uint64_t *sigs /* n*36 */, const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *ok_bitmap, size_t n,
+                                                                 int *combined, size_t *rechecked);
 /* device-pointer forms (every buffer on ONE of the library's devices; `stream` as in blsmi_pairing_batch_dev): the points resident in HBM as the
  * Go side holds them.  d_ok: n verdict bytes on the device. */
 int blsmi_pairing_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, void *d_out_fq12, size_t n, void *stream);

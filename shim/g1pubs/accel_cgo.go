@@ -186,6 +186,28 @@ func VerifyBatchRandomizedGrouped(msgs [][]byte, msgIdx []uint32, pubs []*Public
 	return out
 }
 
+// VerifyBatchRandomizedGroupedLocate is VerifyBatchRandomizedGrouped for input an adversary may have touched (INTEGRATION.md 2k): the
+// tuples of every message are cut into cells of at most `block` tuples (0: the library chooses; any other value >= 1 is taken), the
+// combined check runs over the cells' sums, and when it fails one pairing equation per cell finds the cells that hold -- only the
+// tuples of the others go through the per-tuple path.  Verdicts as VerifyBatch on the expanded messages.
+func VerifyBatchRandomizedGroupedLocate(msgs [][]byte, msgIdx []uint32, pubs []*PublicKey, sigs []*Signature, block int) []bool {
+	n := len(msgIdx)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac(u8(m), &off[0], C.size_t(len(msgs)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])),
+		u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil), "g1pubs_verify_batch_rlc_grouped_locate_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // Verify keeps the upstream signature (g1pubs/bls.go:165).
 func Verify(m []byte, pub *PublicKey, sig *Signature) bool {
 	return VerifyBatch([][]byte{m}, []*PublicKey{pub}, []*Signature{sig})[0]
@@ -267,6 +289,29 @@ func VerifyWithDomainBatchRandomizedGrouped(msgs [][32]byte, msgIdx []uint32, pu
 	must(C.blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
 		C.size_t(len(msgs)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])), u64(pk), u64(sg), nil, u8(ok), nil, C.size_t(n), nil),
 		"g1pubs_verify_with_domain_batch_rlc_grouped_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// VerifyWithDomainBatchRandomizedGroupedLocate is VerifyWithDomainBatchRandomizedGrouped that finds the bad tuples by cells
+// (VerifyBatchRandomizedGroupedLocate).
+func VerifyWithDomainBatchRandomizedGroupedLocate(msgs [][32]byte, msgIdx []uint32, pubs []*PublicKey, sigs []*Signature, domain [8]byte, block int) []bool {
+	n := len(msgIdx)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(msgs) == 0 {
+		panic("blsmi: VerifyWithDomainBatchRandomizedGroupedLocate: empty message table")
+	}
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
+		C.size_t(len(msgs)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])), u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil),
+		"g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac")
 	for i := range ok {
 		out[i] = ok[i] != 0
 	}

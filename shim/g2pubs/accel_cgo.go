@@ -189,6 +189,28 @@ func VerifyBatchRandomizedGrouped(msgs [][]byte, msgIdx []uint32, pubs []*Public
 	return out
 }
 
+// VerifyBatchRandomizedGroupedLocate is VerifyBatchRandomizedGrouped for input an adversary may have touched (INTEGRATION.md 2k): the
+// tuples of every message are cut into cells of at most `block` tuples (0: the library chooses; any other value >= 1 is taken), the
+// combined check runs over the cells' sums, and when it fails one pairing equation per cell finds the cells that hold -- only the
+// tuples of the others go through the per-tuple path.  Verdicts as VerifyBatch on the expanded messages.
+func VerifyBatchRandomizedGroupedLocate(msgs [][]byte, msgIdx []uint32, pubs []*PublicKey, sigs []*Signature, block int) []bool {
+	n := len(msgIdx)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := packKeys(pubs)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac(u8(m), &off[0], C.size_t(len(msgs)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])),
+		u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil), "g2pubs_verify_batch_rlc_grouped_locate_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // Verify keeps the upstream signature (g2pubs/bls.go:159).  A lone Verify is faster on the device than on
 // one CPU core (2.0 ms against 3.7 ms): blsmi_prefer_cpu(BLSMI_SHAPE_VERIFY, 1) is 0, so there is no CPU branch.
 func Verify(m []byte, pub *PublicKey, sig *Signature) bool {
