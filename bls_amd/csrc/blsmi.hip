@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -247,7 +248,62 @@ struct AliasRange { const char* lo; const char* hi; int dev; };
 std::vector<AliasRange> g_alias_own;   // device-pointer ranges assigned to a logical device (g_mu)
 #define NCCLCHK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) { fprintf(stderr, "blsmi: %s failed: %s\n", #x, g_rccl.GetErrorString(r_)); return BLSMI_E_RCCL; } } while (0)
 
-inline unsigned nblocks(size_t n) { return (unsigned)((n + WG - 1) / WG); }
+// prof_mark(name): called right before the launch of a major kernel (name = nullptr: after the last one).  Segment i runs from
+// mark i to mark i + 1 on the launch stream and carries the name of mark i; the marks of a call are turned into
+// (name, ms) pairs when its context lease ends (every entry point is blocking, so the stream is idle by then).
+inline void prof_mark(const char* name) {
+    if (!g_profile.load(std::memory_order_relaxed) || !tl_ctx) return;
+    Ctx& c = *tl_ctx;
+    if (c.pused == c.pev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; c.pev.push_back(e); c.pname.push_back(nullptr); }
+    if (hipEventRecord(c.pev[c.pused], tl_ctx->stream) != hipSuccess) return;
+    c.pname[c.pused++] = name;
+}
+
+// ---- launches -------------------------------------------------------------------------------------------------------------------------
+// A kernel and the name its profile segment carries.  KERNEL_OF(k): the name is the symbol; kernel_named(k, "..."): the few kernels whose
+// segment has always been called something else (tests, the launch-trace tools and bench.py's per-kernel breakdown key on these strings).
+template <class... P> struct Kernel { void (*fn)(P...); const char* name; };
+template <class... P> constexpr Kernel<P...> kernel_named(void (*fn)(P...), const char* name) { return {fn, name}; }
+#define KERNEL_OF(k) kernel_named(k, #k)
+// An argument as the kernel's parameter type: any object pointer (const void*, u8*, DBuf::p ...) as the typed pointer, never dropping a
+// const; any integer as the parameter's integer type.
+template <class To, class From> inline To launch_arg(From v) {
+    if constexpr (std::is_null_pointer_v<From>) { static_assert(std::is_pointer_v<To>, "nullptr for a parameter that is no pointer"); return nullptr; }
+    else if constexpr (std::is_pointer_v<To>) { static_assert(std::is_pointer_v<From>, "a pointer parameter takes a pointer"); return reinterpret_cast<To>(v); }
+    else { static_assert(!std::is_pointer_v<From>, "a pointer for a parameter that is none"); return static_cast<To>(v); }
+}
+// launch_quiet: `blocks` workgroups of WG lanes on s, one argument per kernel parameter.  launch: the same after a profile mark of the
+// kernel's name.  A mark opens a timing segment on the call's MAIN stream whatever stream the kernel goes to (prof_mark), so the small
+// helper kernels inside a segment and everything on a side stream go out quiet.  The *_sized forms: kernels that do not run WG lanes
+// per block (a wave per item, the 256-lane scans of the MSM).
+template <class... P, class... A> inline void launch_quiet_sized(const Kernel<P...>& k, size_t blocks, unsigned lanes, hipStream_t s, A... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)blocks), dim3(lanes), 0, s, launch_arg<P>(args)...);
+}
+template <class... P, class... A> inline void launch_sized(const Kernel<P...>& k, size_t blocks, unsigned lanes, hipStream_t s, A... args) { prof_mark(k.name); launch_quiet_sized(k, blocks, lanes, s, args...); }
+template <class... P, class... A> inline void launch_quiet(const Kernel<P...>& k, size_t blocks, hipStream_t s, A... args) { launch_quiet_sized(k, blocks, WG, s, args...); }
+template <class... P, class... A> inline void launch(const Kernel<P...>& k, size_t blocks, hipStream_t s, A... args) { launch_sized(k, blocks, WG, s, args...); }
+static_assert(tuples_per_block(Layout::single) == WG && tuples_per_block(Layout::pair) == PT && tuples_per_block(Layout::quad) == QT && tuples_per_block(Layout::row) == RT, "route.h and kernels.h agree on the tuples of a workgroup");
+inline unsigned nblocks(size_t n) { return tuple_blocks(Layout::single, n); }   // one lane per item: the helper kernels
+// The pairing kernels every lane layout has under one signature (the wave layout is level programs: launch_lat)
+struct LayoutKernels {
+    Kernel<const u8*, const u8*, i32*, size_t> miller1h;
+    Kernel<const u8*, size_t, const u8*, size_t, const u8*, size_t, const u8*, size_t, i32*, size_t, const i32*> miller2;
+    Kernel<const i32*, u64*, size_t, int> final_exp;
+    Kernel<const i32*, const u8*, u8*, size_t> final_exp_is_one;
+};
+inline LayoutKernels kernels_of(Layout l) {
+#define BLSMI_LAYOUT_KERNELS(sfx) {KERNEL_OF(k_miller1h##sfx), KERNEL_OF(k_miller2##sfx), KERNEL_OF(k_final_exp##sfx), KERNEL_OF(k_final_exp_is_one##sfx)}
+    switch (l) {
+        case Layout::row: return BLSMI_LAYOUT_KERNELS(_row);
+        case Layout::quad: return BLSMI_LAYOUT_KERNELS(_quad);
+        case Layout::pair: return BLSMI_LAYOUT_KERNELS(_pair);
+        default: return BLSMI_LAYOUT_KERNELS();
+    }
+#undef BLSMI_LAYOUT_KERNELS
+}
+// the exact-step Miller loop (MillerLoop: the reference's steps), which only the pair and the one-lane layout have
+inline Kernel<const u8*, const u8*, i32*, size_t> miller1_of(Layout l) { return l == Layout::pair ? KERNEL_OF(k_miller1_pair) : KERNEL_OF(k_miller1); }
 int init_device(Device& d) {            // caller holds g_mu
     HIPCHK(hipSetDevice(d.id));
     hipMemPool_t pool;
@@ -261,11 +317,11 @@ int init_device(Device& d) {            // caller holds g_mu
     for (int i = 0; i < g_nctx; i++) if (!d.ctx[i].stream) HIPCHK(hipStreamCreateWithFlags(&d.ctx[i].stream, hipStreamNonBlocking));
     if (!d.gens.g1) {
         HIPCHK(hipMalloc((void**)&d.gens.g1, 96)); HIPCHK(hipMalloc((void**)&d.gens.g2, 192));
-        hipLaunchKernelGGL(k_write_generators, dim3(1), dim3(WG), 0, nullptr, d.gens.g1, d.gens.g2);
+        launch_quiet(KERNEL_OF(k_write_generators), 1, nullptr, d.gens.g1, d.gens.g2);
         HIPCHK(hipMalloc((void**)&d.gens.lines, sizeof(i32) * 68 * 3 * 2 * NL));
-        hipLaunchKernelGGL(k_prepare_generator_lines, dim3(1), dim3(WG), 0, nullptr, (const u8*)d.gens.g2, d.gens.lines);
+        launch_quiet(KERNEL_OF(k_prepare_generator_lines), 1, nullptr, d.gens.g2, d.gens.lines);
         HIPCHK(hipMalloc((void**)&d.gens.lines_pair, sizeof(i32) * 68 * 3 * 2 * NL));
-        hipLaunchKernelGGL(k_prepare_generator_lines_pair, dim3(1), dim3(WG), 0, nullptr, (const u8*)d.gens.g2, d.gens.lines_pair);
+        launch_quiet(KERNEL_OF(k_prepare_generator_lines_pair), 1, nullptr, d.gens.g2, d.gens.lines_pair);
         HIPCHK(hipGetLastError());
         if (inflate_programs()) { fprintf(stderr, "blsmi: the embedded level programs do not inflate\n"); return BLSMI_E_ARG; }
         HIPCHK(hipMalloc((void**)&d.gens.lat, LAT_TOTAL_BYTES));
@@ -280,10 +336,10 @@ int init_device(Device& d) {            // caller holds g_mu
             HIPCHK(hipMalloc((void**)&dsc, NE * 32)); HIPCHK(hipMalloc((void**)&wire, NE * 192)); HIPCHK(hipMalloc((void**)&inf, NE));
             HIPCHK(hipMemcpy(dsc, sc.data(), NE * 32, hipMemcpyHostToDevice));
             HIPCHK(hipMalloc((void**)&d.gens.fixed1, sizeof(i32) * NE * 2 * NL)); HIPCHK(hipMalloc((void**)&d.gens.fixed2, sizeof(i32) * NE * 4 * NL));
-            hipLaunchKernelGGL(k_g1_mul_glv, dim3(nblocks(NE)), dim3(WG), 0, nullptr, (const u8*)d.gens.g1, (size_t)0, (const u8*)dsc, wire, inf, NE);
-            hipLaunchKernelGGL(k_fixed_table_from_wire, dim3(nblocks(NE * 2)), dim3(WG), 0, nullptr, (const u8*)wire, 2, d.gens.fixed1, NE);
-            hipLaunchKernelGGL(k_g2_mul_glv_pair, dim3((unsigned)((NE + PT - 1) / PT)), dim3(WG), 0, nullptr, (const u8*)d.gens.g2, (size_t)0, (const u8*)dsc, wire, inf, NE);
-            hipLaunchKernelGGL(k_fixed_table_from_wire, dim3(nblocks(NE * 4)), dim3(WG), 0, nullptr, (const u8*)wire, 4, d.gens.fixed2, NE);
+            launch_quiet(KERNEL_OF(k_g1_mul_glv), nblocks(NE), nullptr, d.gens.g1, 0, dsc, wire, inf, NE);
+            launch_quiet(KERNEL_OF(k_fixed_table_from_wire), nblocks(NE * 2), nullptr, wire, 2, d.gens.fixed1, NE);
+            launch_quiet(KERNEL_OF(k_g2_mul_glv_pair), tuple_blocks(Layout::pair, NE), nullptr, d.gens.g2, 0, dsc, wire, inf, NE);
+            launch_quiet(KERNEL_OF(k_fixed_table_from_wire), nblocks(NE * 4), nullptr, wire, 4, d.gens.fixed2, NE);
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
             (void)hipFree(dsc); (void)hipFree(wire); (void)hipFree(inf);
@@ -312,8 +368,6 @@ inline size_t call_load(size_t n) {
     if (!c->load_set) { c->load_others = c->dev->load.fetch_add(n, std::memory_order_relaxed); c->load_n = n; c->load_set = true; }
     return c->load_others + c->tune.assume_load;
 }
-inline unsigned qblocks(size_t n) { return (unsigned)((n + QT - 1) / QT); }
-inline unsigned rblocks(size_t n) { return (unsigned)((n + RT - 1) / RT); }
 // The options of the call this thread serves: the snapshot CtxLease took (tuning_now)
 inline const Tuning& tune() { return tl_ctx->tune; }
 // what the layout questions of a call of n tuples see of the other calls on its device (a crowded call registers its own tuples: call_load)
@@ -330,6 +384,36 @@ inline void launch_lat(size_t prog_offset, hipStream_t s, const LatArgs& a, size
                        (const u8*)a.b0.p, a.b0.stride, (const u8*)a.b1.p, a.b1.stride, (const u8*)a.b2.p, a.b2.stride, (const u8*)a.b3.p, a.b3.stride,
                        (const u8*)a.flags, (u8*)a.ok, (u64*)a.out, n);
 }
+// The profile name of a level program where its launch opens a segment (launch_lat_marked).  sum0 opens the segment of a whole tree of sums.
+inline const char* lat_mark(size_t prog_offset) {
+    switch (prog_offset) {
+        case LAT_PAIRING1_OFFSET: return "k_lat:pairing1";
+        case LAT_PAIRING1S_OFFSET: return "k_lat:pairing1s";
+        case LAT_MILLER1X_OFFSET: return "k_lat:miller1x";
+        case LAT_MILLER1RAW_OFFSET: return "k_lat:miller1raw";
+        case LAT_MILLER1RAWN_OFFSET: return "k_lat:miller1rawn";
+        case LAT_FINALEXP1_OFFSET: return "k_lat:finalexp1";
+        case LAT_VERIFY1S_OFFSET: return "k_lat:verify1s";
+        case LAT_VERIFY2_OFFSET: return "k_lat:verify2";
+        case LAT_AGGTAIL_OFFSET: return "k_lat:aggtail";
+        case LAT_AGGTAIL2_OFFSET: return "k_lat:aggtail2";
+        case LAT_MUL12RAW_OFFSET: return "k_lat:mul12raw";
+        case LAT_POWC12RAW_OFFSET: return "k_lat:powc12raw";
+        case LAT_MUL1_OFFSET: return "k_lat:mul1";
+        case LAT_MUL2_OFFSET: return "k_lat:mul2";
+        case LAT_SUM0_1_OFFSET: case LAT_SUM0_2_OFFSET: return "k_lat:sum";
+        case LAT_MSMFIN1_OFFSET: return "k_lat:msmfin1";
+        case LAT_MSMFIN2_OFFSET: return "k_lat:msmfin2";
+        case LAT_HASHFIN1_OFFSET: return "k_lat:hashfin1";
+        case LAT_HASHFIN2_OFFSET: return "k_lat:hashfin2";
+        case LAT_COFAC2_OFFSET: return "k_lat:cofac2";
+        case LAT_SUBGRP1_OFFSET: return "k_lat:subgrp1";
+        case LAT_SUBGRP2_OFFSET: return "k_lat:subgrp2";
+    }
+    return "k_lat";
+}
+// launch_lat is unmarked, as the side streams need it; this is the form for a program that opens a profile segment on the main stream
+inline void launch_lat_marked(size_t prog_offset, hipStream_t s, const LatArgs& a, size_t n) { prof_mark(lat_mark(prog_offset)); launch_lat(prog_offset, s, a, n); }
 // ---- the environment is read ONCE, at initialisation (under g_mu), never from an entry point ---------------------------------------
 // getenv racing a setenv in another thread is undefined (glibc), and a variable read per call silently changes what a concurrent caller
 // gets.  load_env reads the options' variables (apply_env, route.h: one reader for every row of the table) and the process's
@@ -398,17 +482,6 @@ int ensure_init_default() {             // lazy initialisation by the first entr
 }
 int device_index_of_ordinal(int ordinal) { for (int i = 0; i < g_ndev; i++) if (g_dev[i].id == ordinal) return i; return -1; }
 
-// prof_mark(name): called right before the launch of a major kernel (name = nullptr: after the last one).  Segment i runs from
-// mark i to mark i + 1 on the launch stream and carries the name of mark i; the marks of a call are turned into
-// (name, ms) pairs when its context lease ends (every entry point is blocking, so the stream is idle by then).
-#define g_stream_ (tl_ctx->stream)
-inline void prof_mark(const char* name) {
-    if (!g_profile.load(std::memory_order_relaxed) || !tl_ctx) return;
-    Ctx& c = *tl_ctx;
-    if (c.pused == c.pev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; c.pev.push_back(e); c.pname.push_back(nullptr); }
-    if (hipEventRecord(c.pev[c.pused], g_stream_) != hipSuccess) return;
-    c.pname[c.pused++] = name;
-}
 inline void prof_collect(Ctx& c) {
     if (c.pused < 2) { c.pused = 0; return; }
     (void)hipEventSynchronize(c.pev[c.pused - 1]);
@@ -717,9 +790,9 @@ inline size_t rec_bytes(size_t wire_bytes, bool jac) { return jac ? wire_bytes /
 int jac_to_wire_dev(size_t wire_bytes, const void* d_jac, void* d_out, void* d_inf, size_t n, hipStream_t s) {
     if (n == 0) return BLSMI_OK;
     const bool mark = tl_ctx && s == tl_ctx->stream;                       // (profile marks are events on the context's main stream)
-    if (mark) prof_mark(wire_bytes == 96 ? "k_g1_jac_to_affine" : "k_g2_jac_to_affine");
-    if (wire_bytes == 96) hipLaunchKernelGGL(k_g1_jac_to_affine, dim3(nblocks(n)), dim3(WG), 0, s, (const u64*)d_jac, (u8*)d_out, (u8*)d_inf, n);
-    else hipLaunchKernelGGL(k_g2_jac_to_affine, dim3(nblocks(n)), dim3(WG), 0, s, (const u64*)d_jac, (u8*)d_out, (u8*)d_inf, n);
+    const auto k = wire_bytes == 96 ? KERNEL_OF(k_g1_jac_to_affine) : KERNEL_OF(k_g2_jac_to_affine);
+    if (mark) prof_mark(k.name);
+    launch_quiet(k, nblocks(n), s, d_jac, d_out, d_inf, n);
     if (mark) prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
@@ -755,31 +828,13 @@ static int pairing_dev(const void* d_g1, const void* d_g2, void* d_out, size_t n
     if (n == 0) return BLSMI_OK;
     if (lay == Layout::wave) {   // small call: one pairing per wave (k_lat.hip; pairing1s: its squaring runs unrolled, A/B partner), MillerLoop: the reference's steps
         const size_t prog = mode ? (size_t)LAT_MILLER1X_OFFSET : tune().lat_rolled ? (size_t)LAT_PAIRING1_OFFSET : (size_t)LAT_PAIRING1S_OFFSET;
-        prof_mark(mode ? "k_lat:miller1x" : prog == LAT_PAIRING1_OFFSET ? "k_lat:pairing1" : "k_lat:pairing1s");
-        launch_lat(prog, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = d_out}, n);
-    } else {
+        launch_lat_marked(prog, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = d_out}, n);
+    } else {   // row: a few thousand tuples, one wave per SIMD at 4 096; quad: a mid-size batch, one wave per SIMD at 16 384; pair and single beyond
         HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
         i32* f = reinterpret_cast<i32*>(g_ws.p);
-        const unsigned pblocks = (unsigned)((n + PT - 1) / PT);
-        const bool pairl = lay == Layout::pair;
-        if (lay == Layout::row) {                                          // a few thousand tuples: sixteen lanes per tuple, one wave per SIMD at 4 096 tuples
-            prof_mark("k_miller1h_row");
-            hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-            prof_mark("k_final_exp_row");
-            hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
-        } else if (lay == Layout::quad) {                                  // mid-size batch: four lanes per tuple, one wave per SIMD at 16 384 tuples
-            prof_mark("k_miller1h_quad");
-            hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-            prof_mark("k_final_exp_quad");
-            hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, 0);
-        } else {                                                           // mode 1 (MillerLoop): the reference's steps; mode 0 (Pairing): the homogeneous steps
-            prof_mark(pairl ? (mode ? "k_miller1_pair" : "k_miller1h_pair") : (mode ? "k_miller1" : "k_miller1h"));
-            if (pairl) hipLaunchKernelGGL(mode ? k_miller1_pair : k_miller1h_pair, dim3(pblocks), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-            else hipLaunchKernelGGL(mode ? k_miller1 : k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)d_g1, (const u8*)d_g2, f, n);
-            prof_mark(pairl ? "k_final_exp_pair" : "k_final_exp");
-            if (pairl) hipLaunchKernelGGL(k_final_exp_pair, dim3(pblocks), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
-            else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, s, (const i32*)f, (u64*)d_out, n, mode);
-        }
+        const bool exact = mode && (lay == Layout::pair || lay == Layout::single);   // MillerLoop: the reference's steps; Pairing: the homogeneous steps
+        launch(exact ? miller1_of(lay) : kernels_of(lay).miller1h, tuple_blocks(lay, n), s, d_g1, d_g2, f, n);
+        launch(kernels_of(lay).final_exp, tuple_blocks(lay, n), s, f, d_out, n, exact ? mode : 0);
     }
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
@@ -927,9 +982,8 @@ BLSMI_API int blsmi_final_exponentiation_batch(const uint64_t* in, uint64_t* out
     if (lay == Layout::wave)                                               // small call: one final exponentiation per wave (k_lat.hip)
         launch_lat(LAT_FINALEXP1_OFFSET, g_stream, {.b0 = {i.p, 576}, .out = o.p}, n);
     else {                                                                 // a few thousand values: sixteen lanes per value (k_pairing_row.hip), 1.2 ms up to 4 096
-        hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, i.as<u64>(), f.as<i32>(), n);
-        if (lay == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(n)), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), o.as<u64>(), n, 0);
-        else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(n)), dim3(WG), 0, g_stream, f.as<i32>(), o.as<u64>(), n, 0);
+        launch_quiet(KERNEL_OF(k_fq12_from_m384), nblocks(n), g_stream, i.p, f.p, n);
+        launch_quiet(kernels_of(lay).final_exp, tuple_blocks(lay, n), g_stream, f.p, o.p, n, 0);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, o.p, 576 * n, hipMemcpyDeviceToHost, g_stream));
@@ -964,19 +1018,19 @@ BLSMI_API int blsmi_debug_op(int op_in, const uint64_t* a, const uint64_t* b, ui
     HIPCHK(hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, g_stream));
     if (b) HIPCHK(hipMemcpyAsync(db.p, b, bytes, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemsetAsync(dflag.p, 1, n, g_stream));
-    dim3 g(nblocks(n)), w(WG);
-    if (rowl) hipLaunchKernelGGL(k_debug_row, dim3(rblocks(n)), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
-    else if (quadg2) hipLaunchKernelGGL(k_debug_quad_g2, dim3(qblocks(n)), w, 0, g_stream, op, da.as<u64>(), dout.as<u64>(), n);
-    else if (quadl) hipLaunchKernelGGL(k_debug_quad, dim3(qblocks(n)), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
-    else if (pairl && fexp) hipLaunchKernelGGL(k_debug_final_exp_pair, dim3((unsigned)((n + PT - 1) / PT)), w, 0, g_stream, da.as<u64>(), dout.as<u64>(), n);
-    else if (pairl) hipLaunchKernelGGL(k_debug_pairl, dim3((unsigned)((n + WG / 2 - 1) / (WG / 2))), w, 0, g_stream, op, da.as<u64>(), b ? db.as<u64>() : (const u64*)nullptr, dout.as<u64>(), n);
-    else if (op < 16) hipLaunchKernelGGL(k_debug_fq, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), dflag.as<u8>(), n);
-    else if (op < 32) hipLaunchKernelGGL(k_debug_fq2, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), dflag.as<u8>(), n);
-    else if (op < 48) hipLaunchKernelGGL(k_debug_fq6, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), n);
-    else if (op < 64) hipLaunchKernelGGL(k_debug_fq12, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), n);
-    else if (op == BLSMI_OP_SWU_G1) hipLaunchKernelGGL(k_debug_swu_g1, g, w, 0, g_stream, da.as<u64>(), dout.as<u64>(), n);
-    else if (op == BLSMI_OP_SWU_G2) hipLaunchKernelGGL(k_debug_swu_g2, g, w, 0, g_stream, da.as<u64>(), dout.as<u64>(), n);
-    else hipLaunchKernelGGL(k_debug_curve, g, w, 0, g_stream, op, da.as<u64>(), db.as<u64>(), dout.as<u64>(), n);
+    const unsigned g = nblocks(n);
+    if (rowl) launch_quiet(KERNEL_OF(k_debug_row), tuple_blocks(Layout::row, n), g_stream, op, da.p, b ? db.as<u64>() : (const u64*)nullptr, dout.p, n);
+    else if (quadg2) launch_quiet(KERNEL_OF(k_debug_quad_g2), tuple_blocks(Layout::quad, n), g_stream, op, da.p, dout.p, n);
+    else if (quadl) launch_quiet(KERNEL_OF(k_debug_quad), tuple_blocks(Layout::quad, n), g_stream, op, da.p, b ? db.as<u64>() : (const u64*)nullptr, dout.p, n);
+    else if (pairl && fexp) launch_quiet(KERNEL_OF(k_debug_final_exp_pair), tuple_blocks(Layout::pair, n), g_stream, da.p, dout.p, n);
+    else if (pairl) launch_quiet(KERNEL_OF(k_debug_pairl), tuple_blocks(Layout::pair, n), g_stream, op, da.p, b ? db.as<u64>() : (const u64*)nullptr, dout.p, n);
+    else if (op < 16) launch_quiet(KERNEL_OF(k_debug_fq), g, g_stream, op, da.p, db.p, dout.p, dflag.p, n);
+    else if (op < 32) launch_quiet(KERNEL_OF(k_debug_fq2), g, g_stream, op, da.p, db.p, dout.p, dflag.p, n);
+    else if (op < 48) launch_quiet(KERNEL_OF(k_debug_fq6), g, g_stream, op, da.p, db.p, dout.p, n);
+    else if (op < 64) launch_quiet(KERNEL_OF(k_debug_fq12), g, g_stream, op, da.p, db.p, dout.p, n);
+    else if (op == BLSMI_OP_SWU_G1) launch_quiet(KERNEL_OF(k_debug_swu_g1), g, g_stream, da.p, dout.p, n);
+    else if (op == BLSMI_OP_SWU_G2) launch_quiet(KERNEL_OF(k_debug_swu_g2), g, g_stream, da.p, dout.p, n);
+    else launch_quiet(KERNEL_OF(k_debug_curve), g, g_stream, op, da.p, db.p, dout.p, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, g_stream));
     if (flag) HIPCHK(hipMemcpyAsync(flag, dflag.p, n, hipMemcpyDeviceToHost, g_stream));
@@ -994,11 +1048,11 @@ BLSMI_API int blsmi_debug_g2_prepare(const uint8_t* g2_aff, int mode, uint64_t* 
     const i32* src = g_gens.lines;
     if (mode != 2) {
         HIPCHK(hipMemcpyAsync(dq.p, g2_aff, 192, hipMemcpyHostToDevice, g_stream));
-        if (mode == 0) hipLaunchKernelGGL(k_debug_prepare_single, dim3(1), dim3(WG), 0, g_stream, dq.as<u8>(), tab.as<i32>());
-        else hipLaunchKernelGGL(k_debug_prepare_pair, dim3(1), dim3(WG), 0, g_stream, dq.as<u8>(), tab.as<i32>());
+        if (mode == 0) launch_quiet(KERNEL_OF(k_debug_prepare_single), 1, g_stream, dq.p, tab.p);
+        else launch_quiet(KERNEL_OF(k_debug_prepare_pair), 1, g_stream, dq.p, tab.p);
         src = tab.as<i32>();
     }
-    hipLaunchKernelGGL(k_debug_lines_to_m384, dim3((68 * 3 * 2 + WG - 1) / WG), dim3(WG), 0, g_stream, src, dout.as<u64>());
+    launch_quiet(KERNEL_OF(k_debug_lines_to_m384), (68 * 3 * 2 + WG - 1) / WG, g_stream, src, dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(u64) * 68 * 3 * 12, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1018,13 +1072,11 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
         // Small calls: one scalar per wave (the 32 table entries meet in a tree of additions across the lanes).
         const i32* table = PB == 96 ? g_gens.fixed1 : g_gens.fixed2;
         if (m <= tune().fixed_wave_max && m <= tune().lat_max) {
-            prof_mark(PB == 96 ? "k_g1_mul_fixed_wave" : "k_g2_mul_fixed_wave");
-            if (PB == 96) hipLaunchKernelGGL(k_g1_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
-            else hipLaunchKernelGGL(k_g2_mul_fixed_wave, dim3((unsigned)m), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
+            if (PB == 96) launch(KERNEL_OF(k_g1_mul_fixed_wave), m, s, table, d_scalars, d_out, d_inf, m);
+            else launch(KERNEL_OF(k_g2_mul_fixed_wave), m, s, table, d_scalars, d_out, d_inf, m);
         } else {
-            prof_mark(PB == 96 ? "k_g1_mul_fixed" : "k_g2_mul_fixed");
-            if (PB == 96) hipLaunchKernelGGL(k_g1_mul_fixed, dim3(nblocks(m)), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
-            else hipLaunchKernelGGL(k_g2_mul_fixed, dim3(nblocks(m)), dim3(WG), 0, s, table, d_scalars, d_out, d_inf, m);
+            if (PB == 96) launch(KERNEL_OF(k_g1_mul_fixed), nblocks(m), s, table, d_scalars, d_out, d_inf, m);
+            else launch(KERNEL_OF(k_g2_mul_fixed), nblocks(m), s, table, d_scalars, d_out, d_inf, m);
         }
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
@@ -1033,11 +1085,10 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
     if (m <= tune().lat_max && mul_subgroup()) { // small call: one multiplication per wave (k_lat.hip, SEL levels over the decomposed scalar)
         const size_t prog = PB == 96 ? LAT_MUL1_OFFSET : LAT_MUL2_OFFSET;
         DBuf good, rec; HIPCHK(good.alloc(m, s)); HIPCHK(rec.alloc(64 * m, s));
-        hipLaunchKernelGGL(k_glv_recode, dim3(nblocks(m)), dim3(WG), 0, s, d_scalars, PB == 96 ? 1 : 2, rec.as<u8>(), m);
-        prof_mark(PB == 96 ? "k_lat:mul1" : "k_lat:mul2");
-        launch_lat(prog, s, {.b0 = {base, stride}, .b1 = {rec.p, 64}, .ok = good.p, .out = d_out}, m);
+        launch_quiet(KERNEL_OF(k_glv_recode), nblocks(m), s, d_scalars, PB == 96 ? 1 : 2, rec.p, m);
+        launch_lat_marked(prog, s, {.b0 = {base, stride}, .b1 = {rec.p, 64}, .ok = good.p, .out = d_out}, m);
         prof_mark(nullptr);
-        hipLaunchKernelGGL(k_mul_finish, dim3(nblocks(m)), dim3(WG), 0, s, (const u8*)good.as<u8>(), base, stride, PB / 4, d_out, d_inf, m);
+        launch_quiet(KERNEL_OF(k_mul_finish), nblocks(m), s, good.p, base, stride, PB / 4, d_out, d_inf, m);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;                                                   // `good` is released in stream order
     }
@@ -1045,19 +1096,17 @@ static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_sc
     // of the doublings; arbitrary curve points (blsmi_set_mul_assume_subgroup(0)): the plain fixed-window ladder
     const bool glv = mul_subgroup();
     if (glv) {
-        prof_mark(PB == 192 ? (tune().pair_layout ? "k_g2_mul_glv_pair" : "k_g2_mul_glv") : "k_g1_mul_glv");
-        if (PB == 192 && tune().pair_layout) hipLaunchKernelGGL(k_g2_mul_glv_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
-        else if (PB == 192) hipLaunchKernelGGL(k_g2_mul_glv, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
-        else hipLaunchKernelGGL(k_g1_mul_glv, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
+        if (PB == 192 && tune().pair_layout) launch(KERNEL_OF(k_g2_mul_glv_pair), tuple_blocks(Layout::pair, m), s, base, stride, d_scalars, d_out, d_inf, m);
+        else if (PB == 192) launch(KERNEL_OF(k_g2_mul_glv), nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
+        else launch(KERNEL_OF(k_g1_mul_glv), nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
     }
-    prof_mark(PB == 192 ? (tune().pair_layout ? "k_g2_mul_pair" : "k_g2_mul") : "k_g1_mul");
     if (PB == 192 && tune().pair_layout)                                   // G2: lane-pair kernel, two waves per SIMD
-        hipLaunchKernelGGL(k_g2_mul_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
+        launch(KERNEL_OF(k_g2_mul_pair), tuple_blocks(Layout::pair, m), s, base, stride, d_scalars, d_out, d_inf, m);
     else
-        hipLaunchKernelGGL(kernel, dim3(nblocks(m)), dim3(WG), 0, s, base, stride, d_scalars, d_out, d_inf, m);
+        launch(kernel, nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
@@ -1082,7 +1131,7 @@ static int mul_batch(K kernel, const uint8_t* pts, int gen_group, const uint8_t*
         if (out_jac) {
             const size_t jb = rec_bytes(PB, true);
             DBuf dj; HIPCHK(dj.alloc(jb * m));
-            hipLaunchKernelGGL(k_affine_to_jac, dim3(nblocks(m)), dim3(WG), 0, g_stream, (const u8*)dout.as<u8>(), (const void*)dinf.p, 1, PB == 96 ? 1 : 2, dj.as<u64>(), m);
+            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, PB == 96 ? 1 : 2, dj.p, m);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(out_jac) + jb * lo, dj.p, jb * m, hipMemcpyDeviceToHost, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));
@@ -1094,13 +1143,13 @@ static int mul_batch(K kernel, const uint8_t* pts, int gen_group, const uint8_t*
         return BLSMI_OK;
     });
 }
-BLSMI_API int blsmi_g1_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<96>(k_g1_mul, pts, 0, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g2_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<192>(k_g2_mul, pts, 0, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g1_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<96>(k_g1_mul, nullptr, 1, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g2_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<192>(k_g2_mul, nullptr, 2, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g1_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<96>(KERNEL_OF(k_g1_mul), pts, 0, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g2_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<192>(KERNEL_OF(k_g2_mul), pts, 0, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g1_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<96>(KERNEL_OF(k_g1_mul), nullptr, 1, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g2_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<192>(KERNEL_OF(k_g2_mul), nullptr, 2, scalars, out, out_inf, n); }
 // PrivToPub for n keys with the results as the Go types hold them (bls.G?Projective with z = 1): PublicKey{p} is the record, no FQReprToFQ on the host
-BLSMI_API int blsmi_g1_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<96>(k_g1_mul, nullptr, 1, scalars, nullptr, nullptr, n, false, out_jac); }
-BLSMI_API int blsmi_g2_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<192>(k_g2_mul, nullptr, 2, scalars, nullptr, nullptr, n, false, out_jac); }
+BLSMI_API int blsmi_g1_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<96>(KERNEL_OF(k_g1_mul), nullptr, 1, scalars, nullptr, nullptr, n, false, out_jac); }
+BLSMI_API int blsmi_g2_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<192>(KERNEL_OF(k_g2_mul), nullptr, 2, scalars, nullptr, nullptr, n, false, out_jac); }
 // device-pointer forms: points (NULL = the group generator), scalars, results and infinity bytes resident on one device
 template <int PB, class K>
 static int mul_batch_dev(K kernel, int gen_group, const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, bool any_point = false) {
@@ -1114,24 +1163,24 @@ static int mul_batch_dev(K kernel, int gen_group, const void* d_pts, const void*
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<96>(k_g1_mul, 1, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
-BLSMI_API int blsmi_g2_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<192>(k_g2_mul, 2, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
+BLSMI_API int blsmi_g1_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<96>(KERNEL_OF(k_g1_mul), 1, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
+BLSMI_API int blsmi_g2_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<192>(KERNEL_OF(k_g2_mul), 2, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
 // per-call choice of the ladder (flags & BLSMI_MUL_ANY_POINT: the plain windowed ladder, which serves every curve point like MulFR, g1.go:80-90)
 BLSMI_API int blsmi_g1_mul_batch_ex(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, unsigned flags) {
     if ((n && !pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch<96>(k_g1_mul, pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch<96>(KERNEL_OF(k_g1_mul), pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_mul_batch_ex(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, unsigned flags) {
     if ((n && !pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch<192>(k_g2_mul, pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch<192>(KERNEL_OF(k_g2_mul), pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g1_mul_batch_dev_ex(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, unsigned flags) {
     if ((n && !d_pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch_dev<96>(k_g1_mul, 1, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch_dev<96>(KERNEL_OF(k_g1_mul), 1, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_mul_batch_dev_ex(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, unsigned flags) {
     if ((n && !d_pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch_dev<192>(k_g2_mul, 2, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch_dev<192>(KERNEL_OF(k_g2_mul), 2, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 
 // tree reduction of n affine points already on the device; result (affine bytes + inf flag) on the device
@@ -1154,8 +1203,7 @@ static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, si
         // few points: every addition of the tree as a level program, one per wave (k_lat.hip: sum0 / sum1 / sumfin; complete
         // projective formulas, two product levels per addition) -- ~10 us a level instead of ~70-140
         const size_t p0 = W == 3 ? LAT_SUM0_1_OFFSET : LAT_SUM0_2_OFFSET, p1 = W == 3 ? LAT_SUM1_1_OFFSET : LAT_SUM1_2_OFFSET, pf = W == 3 ? LAT_SUMFIN_1_OFFSET : LAT_SUMFIN_2_OFFSET;
-        prof_mark("k_lat:sum");
-        launch_lat(p0, s, {.b0 = {d_pts, PB}, .b1 = {d_inf, 0}, .b2 = lat_count(half), .b3 = lat_count(n), .out = b0.p}, half);   // sum0: pairs of the n points
+        launch_lat_marked(p0, s, {.b0 = {d_pts, PB}, .b1 = {d_inf, 0}, .b2 = lat_count(half), .b3 = lat_count(n), .out = b0.p}, half);   // sum0: pairs of the n points
         i32* src = b0.as<i32>(); i32* dst = b1.as<i32>();
         size_t cur = half;
         while (cur > 1) {
@@ -1166,27 +1214,25 @@ static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, si
         }
         DBuf good; HIPCHK(good.alloc(1, s));
         launch_lat(pf, s, {.b3 = lat_count(1, src), .ok = good.p, .out = d_out}, 1);
-        hipLaunchKernelGGL(k_good_to_flag, dim3(1), dim3(WG), 0, s, (const u8*)good.as<u8>(), d_out_inf);
+        launch_quiet(KERNEL_OF(k_good_to_flag), 1, s, good.p, d_out_inf);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         if (sync) HIPCHK(hipStreamSynchronize(s));                        // (the temporaries live in the call's arena: an unsynchronised caller orders its own readers)
         return BLSMI_OK;
     }
-    prof_mark(W == 3 ? "k_g1_sum0" : "k_g2_sum0");
-    if (jac && W == 3) hipLaunchKernelGGL(k_g1_sum0_jac, dim3(nblocks(half)), dim3(WG), 0, s, (const u64*)d_pts, b0.as<i32>(), n, half);
-    else if (jac) hipLaunchKernelGGL(k_g2_sum0_jac, dim3(nblocks(half)), dim3(WG), 0, s, (const u64*)d_pts, b0.as<i32>(), n, half);
-    else hipLaunchKernelGGL(k0, dim3(nblocks(half)), dim3(WG), 0, s, d_pts, d_inf, b0.as<i32>(), n, half);
-    prof_mark(W == 3 ? "k_g1_sum" : "k_g2_sum");
+    if (jac && W == 3) launch(kernel_named(k_g1_sum0_jac, "k_g1_sum0"), nblocks(half), s, d_pts, b0.p, n, half);
+    else if (jac) launch(kernel_named(k_g2_sum0_jac, "k_g2_sum0"), nblocks(half), s, d_pts, b0.p, n, half);
+    else launch(k0, nblocks(half), s, d_pts, d_inf, b0.p, n, half);
+    prof_mark(k1.name);                                                    // one segment: the levels of the tree
     i32* src = b0.as<i32>(); i32* dst = b1.as<i32>();
     size_t cur = half;
     while (cur > 1) {
         const size_t h = (cur + 1) / 2;
-        hipLaunchKernelGGL(k1, dim3(nblocks(h)), dim3(WG), 0, s, (const i32*)src, dst, cur, h);
+        launch_quiet(k1, nblocks(h), s, src, dst, cur, h);
         std::swap(src, dst);
         cur = h;
     }
-    prof_mark(W == 3 ? "k_g1_sum_final" : "k_g2_sum_final");
-    hipLaunchKernelGGL(kfinal, dim3(1), dim3(WG), 0, s, (const i32*)src, d_out, d_out_inf);
+    launch(kfinal, 1, s, src, d_out, d_out_inf);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     if (sync) HIPCHK(hipStreamSynchronize(s));
@@ -1212,7 +1258,7 @@ static int sum_host(K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* 
     if (rc) return rc;
     i32 flag = 0;
     if (out_jac) {
-        hipLaunchKernelGGL(k_affine_to_jac, dim3(1), dim3(WG), 0, g_stream, (const u8*)dout.as<u8>(), (const void*)dflag.p, 0, W == 3 ? 1 : 2, dj.as<u64>(), (size_t)1);
+        launch_quiet(KERNEL_OF(k_affine_to_jac), 1, g_stream, dout.p, dflag.p, 0, W == 3 ? 1 : 2, dj.p, 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out_jac, dj.p, jb, hipMemcpyDeviceToHost, g_stream));
     }
@@ -1222,15 +1268,15 @@ static int sum_host(K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* 
     *out_inf = flag;
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[96], int* out_inf) { return sum_host<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, pts, in_inf, n, out, out_inf); }
-BLSMI_API int blsmi_g2_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[192], int* out_inf) { return sum_host<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, pts, in_inf, n, out, out_inf); }
+BLSMI_API int blsmi_g1_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[96], int* out_inf) { return sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, in_inf, n, out, out_inf); }
+BLSMI_API int blsmi_g2_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[192], int* out_inf) { return sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, in_inf, n, out, out_inf); }
 // AggregateSignatures / AggregatePublicKeys (g2pubs/bls.go:165-192, g1pubs/bls.go:177-204) over the points as the Go values hold them, the sum
 // handed back the same way (z = 1): no ToAffine, no SerializeBytes, no FQReprToFQ in the shim
 BLSMI_API int blsmi_g1_sum_jac(const uint64_t* pts_jac, size_t n, uint64_t out_jac[18], int* out_inf) {
-    return sum_host<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
+    return sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
 }
 BLSMI_API int blsmi_g2_sum_jac(const uint64_t* pts_jac, size_t n, uint64_t out_jac[36], int* out_inf) {
-    return sum_host<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
+    return sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
 }
 template <int PB, int W, class K0, class K1, class K2>
 static int sum_dev_api(K0 k0, K1 k1, K2 kfinal, const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) {
@@ -1246,18 +1292,18 @@ static int sum_dev_api(K0 k0, K1 k1, K2 kfinal, const void* d_pts, const void* d
     *out_inf = flag;
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, d_pts, d_in_inf, n, d_out, out_inf, stream); }
-BLSMI_API int blsmi_g2_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, d_pts, d_in_inf, n, d_out, out_inf, stream); }
+BLSMI_API int blsmi_g1_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_in_inf, n, d_out, out_inf, stream); }
+BLSMI_API int blsmi_g2_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_in_inf, n, d_out, out_inf, stream); }
 
 // multi-scalar multiplication sum_i k_i * P_i.  Small batches: per-point windowed multiples feed the tree sum on the
 // device (one launch of latency, ~6 ms up to 64k points).  From BLSMI_MSM_BUCKET_MIN points (default 2^17, where the
 // two cross over) on: the bucket method of msm.inc, whose fixed tail (chunk reduction + 240 serial doublings) is ~6 ms.
 constexpr int BLSMI_E_SKEW = -1000;    // internal: bucket method declined (unbalanced digits)
 struct MsmKernels {
-    void (*bucket)(const u8*, const u32*, const u32*, const u32*, const u32*, i32*, size_t, int, size_t);
-    void (*chunk)(const i32*, i32*, int, int, size_t, size_t);
-    void (*fold)(const i32*, i32*, size_t, size_t, int);
-    void (*final)(const i32*, int, int, u8*, i32*);
+    Kernel<const u8*, const u32*, const u32*, const u32*, const u32*, i32*, size_t, int, size_t> bucket;
+    Kernel<const i32*, i32*, int, int, size_t, size_t> chunk;
+    Kernel<const i32*, i32*, size_t, size_t, int> fold;
+    Kernel<const i32*, int, int, u8*, i32*> final;
 };
 template <int PB, int W>
 // nbits: the scalars' width -- 256, or 64 for the randomised batch verification's scalars (rlc_host.hpp: rlc_sig_sum), whose
@@ -1276,50 +1322,42 @@ static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scal
     HIPCHK(ch0.alloc(sizeof(i32) * jw * nct)); HIPCHK(ch1.alloc(sizeof(i32) * jw * ((per_win + 1) / 2) * nwin));
     HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(u32) * nb, s));
     HIPCHK(hipMemsetAsync(dmax.p, 0, sizeof(u32), s));
-    prof_mark("k_msm_hist");
-    hipLaunchKernelGGL(k_msm_hist, dim3(nblocks(n)), dim3(WG), 0, s, d_scalars, n, c, nwin, hist.as<u32>());
-    prof_mark("k_msm_max");
+    launch(KERNEL_OF(k_msm_hist), nblocks(n), s, d_scalars, n, c, nwin, hist.p);
     // Skewed scalars (many equal digits) would leave one lane adding a whole bucket by itself: beyond 2048 points in
     // any bucket the caller falls back to the per-point multiples, whose cost does not depend on the scalars.
-    hipLaunchKernelGGL(k_msm_max, dim3(nblocks(nb)), dim3(WG), 0, s, (const u32*)hist.as<u32>(), nb, dmax.as<u32>());
+    launch(KERNEL_OF(k_msm_max), nblocks(nb), s, hist.p, nb, dmax.p);
     u32 biggest = 0;
     HIPCHK(hipMemcpyAsync(&biggest, dmax.p, sizeof biggest, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (biggest > 2048) return BLSMI_E_SKEW;
-    prof_mark("k_msm_scan");
-    hipLaunchKernelGGL(k_msm_scan, dim3(nwin), dim3(256), 0, s, (const u32*)hist.as<u32>(), offs.as<u32>(), cursor.as<u32>(), c);
-    prof_mark("k_msm_scatter");
-    hipLaunchKernelGGL(k_msm_scatter, dim3(nblocks(n)), dim3(WG), 0, s, d_scalars, n, c, nwin, cursor.as<u32>(), idx.as<u32>());
+    launch_sized(KERNEL_OF(k_msm_scan), nwin, 256, s, hist.p, offs.p, cursor.p, c);
+    launch(KERNEL_OF(k_msm_scatter), nblocks(n), s, d_scalars, n, c, nwin, cursor.p, idx.p);
     // buckets ranked by population, so that the 64 lanes of a wave add about the same number of points (msm.inc)
     DBuf cls, perm;
     HIPCHK(cls.alloc(sizeof(u32) * 768, s)); HIPCHK(perm.alloc(sizeof(u32) * nb, s));
     HIPCHK(hipMemsetAsync(cls.p, 0, sizeof(u32) * 256, s));
     const unsigned cb = (unsigned)((nb + 255) / 256);
-    prof_mark("k_msm_class_*");
-    hipLaunchKernelGGL(k_msm_class_hist, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, cls.as<u32>());
-    hipLaunchKernelGGL(k_msm_class_scan, dim3(1), dim3(256), 0, s, (const u32*)cls.as<u32>(), cls.as<u32>() + 256, cls.as<u32>() + 512);
-    hipLaunchKernelGGL(k_msm_class_scatter, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, (const u32*)(cls.as<u32>() + 256), cls.as<u32>() + 512, perm.as<u32>());
-    prof_mark(W == 6 ? (tune().pair_layout ? "k_g2_msm_bucket_pair" : "k_g2_msm_bucket") : "k_g1_msm_bucket");
+    launch_sized(kernel_named(k_msm_class_hist, "k_msm_class_*"), cb, 256, s, hist.p, nb, cls.p);
+    launch_quiet_sized(KERNEL_OF(k_msm_class_scan), 1, 256, s, cls.p, cls.as<u32>() + 256, cls.as<u32>() + 512);
+    launch_quiet_sized(KERNEL_OF(k_msm_class_scatter), cb, 256, s, hist.p, nb, cls.as<u32>() + 256, cls.as<u32>() + 512, perm.p);
     if (W == 6 && tune().pair_layout)                                      // G2: a lane pair per bucket, two waves per SIMD
-        hipLaunchKernelGGL(k_g2_msm_bucket_pair, dim3((unsigned)((nb + PT - 1) / PT)), dim3(WG), 0, s, d_pts, (const u32*)idx.as<u32>(), (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), n, c, nb);
+        launch(KERNEL_OF(k_g2_msm_bucket_pair), tuple_blocks(Layout::pair, nb), s, d_pts, idx.p, offs.p, hist.p, perm.p, buckets.p, n, c, nb);
     else
-        hipLaunchKernelGGL(k.bucket, dim3(nblocks(nb)), dim3(WG), 0, s, d_pts, (const u32*)idx.as<u32>(), (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), n, c, nb);
-    prof_mark(W == 6 ? "k_g2_msm_chunk" : "k_g1_msm_chunk");
-    hipLaunchKernelGGL(k.chunk, dim3(nblocks(nct)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
-    prof_mark(W == 6 ? "k_g2_msm_fold" : "k_g1_msm_fold");
+        launch(k.bucket, nblocks(nb), s, d_pts, idx.p, offs.p, hist.p, perm.p, buckets.p, n, c, nb);
+    launch(k.chunk, nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
+    prof_mark(k.fold.name);                                                // one segment: the levels of the fold
     i32* src = ch0.as<i32>(); i32* dst = ch1.as<i32>();
     size_t seg = per_win;
     while (seg > 1) {
         const size_t half = (seg + 1) / 2;
-        hipLaunchKernelGGL(k.fold, dim3(nblocks(half * nwin)), dim3(WG), 0, s, (const i32*)src, dst, seg, half, nwin);
+        launch_quiet(k.fold, nblocks(half * nwin), s, src, dst, seg, half, nwin);
         std::swap(src, dst);
         seg = half;
     }
     // Horner over the 16 windows (240 dependent doublings) and ToAffine on one lane: this is the path for ARBITRARY curve points
     // (blsmi_set_mul_assume_subgroup(0)); the default path (msm_bucket_glv_dev) has a level program for its shorter tail
     static_assert(W == 3 || W == 6, "G1 / G2");
-    prof_mark(W == 6 ? "k_g2_msm_final" : "k_g1_msm_final");
-    hipLaunchKernelGGL(k.final, dim3(1), dim3(WG), 0, s, (const i32*)src, nwin, c, d_out, d_flag);
+    launch(k.final, 1, s, src, nwin, c, d_out, d_flag);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));                                       // temporaries die with this scope
     return BLSMI_OK;
@@ -1359,96 +1397,84 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(u32) * nb, s));
     HIPCHK(hipMemsetAsync(dmax.p, 0, sizeof(u32), s));
     HIPCHK(hipMemsetAsync(cls.p, 0, sizeof(u32) * 256, s));
-    prof_mark(W == 3 ? "k_msm_recode_g1" : "k_msm_recode_g2");
-    if (W == 3) hipLaunchKernelGGL(k_msm_recode_g1, dim3(nblocks(n)), dim3(WG), 0, s, d_scalars, rec.as<u8>(), n);
-    else hipLaunchKernelGGL(k_msm_recode_g2, dim3(nblocks(n)), dim3(WG), 0, s, d_scalars, rec.as<u8>(), n);
+    if (W == 3) launch(KERNEL_OF(k_msm_recode_g1), nblocks(n), s, d_scalars, rec.p, n);
+    else launch(KERNEL_OF(k_msm_recode_g2), nblocks(n), s, d_scalars, rec.p, n);
     u32 biggest = 0;
     size_t slice_stride = per_win_items;                                   // a bucket's items: idx + (bucket >> 16) * slice_stride + offs[bucket]
     auto exact_passes = [&]() -> int {
         {
-            prof_mark("k_msm_hist_glv");
-            hipLaunchKernelGGL(k_msm_hist_glv, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)rec.as<u8>(), n, nbw, hist.as<u32>());
-            prof_mark("k_msm_max");
-            hipLaunchKernelGGL(k_msm_max, dim3(nblocks(nb)), dim3(WG), 0, s, (const u32*)hist.as<u32>(), nb, dmax.as<u32>());
+            launch(KERNEL_OF(k_msm_hist_glv), nblocks(n), s, rec.p, n, nbw, hist.p);
+            launch(KERNEL_OF(k_msm_max), nblocks(nb), s, hist.p, nb, dmax.p);
             HIPCHK(hipMemcpyAsync(&biggest, dmax.p, sizeof biggest, hipMemcpyDeviceToHost, s));
         }
-        prof_mark("k_msm_scan");
-        hipLaunchKernelGGL(k_msm_scan, dim3(nbw), dim3(256), 0, s, (const u32*)hist.as<u32>(), offs.as<u32>(), cursor.as<u32>(), c);
-        prof_mark("k_msm_scatter_glv");
-        hipLaunchKernelGGL(k_msm_scatter_glv, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)rec.as<u8>(), n, nbw, sh, cursor.as<u32>(), idx.as<u32>());
+        launch_sized(KERNEL_OF(k_msm_scan), nbw, 256, s, hist.p, offs.p, cursor.p, c);
+        launch(KERNEL_OF(k_msm_scatter_glv), nblocks(n), s, rec.p, n, nbw, sh, cursor.p, idx.p);
         slice_stride = per_win_items;
         return BLSMI_OK;
     };
     const u32* items = nullptr;                                            // the bucket pass reads items + (bucket >> 16) * slice_stride + offs[bucket]
     if (sort_mode) {
-        prof_mark("k_msm_items");
-        hipLaunchKernelGGL(k_msm_items, dim3(nblocks(n)), dim3(WG), 0, s, (const u8*)rec.as<u8>(), n, nbw, sh, skey[0].as<u32>(), sval[0].as<u32>());
+        launch(KERNEL_OF(k_msm_items), nblocks(n), s, rec.p, n, nbw, sh, skey[0].p, sval[0].p);
         prof_mark("rocprim:radix_sort");
         u32* kk[2] = {skey[0].as<u32>(), skey[1].as<u32>()}; u32* vv[2] = {sval[0].as<u32>(), sval[1].as<u32>()};
         u32 *ks = nullptr, *vs = nullptr;
         int bits = 17; while (((size_t)1 << bits) <= nb) bits++;            // buckets 0 .. nb - 1 and the sentinel nb
         if (const int e = blsmi_util::sort_pairs_async(kk, vv, nitems, bits, s, [](size_t b) { return tl_ctx->arena.alloc(b); }, &ks, &vs)) { (void)hipGetLastError(); return e == (int)hipErrorOutOfMemory ? BLSMI_E_NOMEM : BLSMI_E_HIP; }
-        prof_mark("k_msm_runs");
+        prof_mark(KERNEL_OF(k_msm_runs).name);                             // (the segment begins with the two clears)
         HIPCHK(hipMemsetAsync(offs.p, 0, sizeof(u32) * nb, s)); HIPCHK(hipMemsetAsync(cursor.p, 0, sizeof(u32) * nb, s));
-        hipLaunchKernelGGL(k_msm_runs, dim3(nblocks(nitems)), dim3(WG), 0, s, (const u32*)ks, nitems, (u32)nb, offs.as<u32>(), cursor.as<u32>());
-        hipLaunchKernelGGL(k_msm_run_lengths, dim3(nblocks(nb)), dim3(WG), 0, s, (const u32*)offs.as<u32>(), (const u32*)cursor.as<u32>(), nb, hist.as<u32>(), dmax.as<u32>());
+        launch_quiet(KERNEL_OF(k_msm_runs), nblocks(nitems), s, ks, nitems, (u32)nb, offs.p, cursor.p);
+        launch_quiet(KERNEL_OF(k_msm_run_lengths), nblocks(nb), s, offs.p, cursor.p, nb, hist.p, dmax.p);
         HIPCHK(hipMemcpyAsync(&biggest, dmax.p, sizeof biggest, hipMemcpyDeviceToHost, s));
         items = vs; slice_stride = 0;
     } else { const int rc = exact_passes(); if (rc) return rc; }
-    prof_mark("k_msm_class_*");
     const unsigned cb = (unsigned)((nb + 255) / 256);
-    hipLaunchKernelGGL(k_msm_class_hist, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, cls.as<u32>());
-    hipLaunchKernelGGL(k_msm_class_scan, dim3(1), dim3(256), 0, s, (const u32*)cls.as<u32>(), cls.as<u32>() + 256, cls.as<u32>() + 512);
-    hipLaunchKernelGGL(k_msm_class_scatter, dim3(cb), dim3(256), 0, s, (const u32*)hist.as<u32>(), nb, (const u32*)(cls.as<u32>() + 256), cls.as<u32>() + 512, perm.as<u32>());
+    launch_sized(kernel_named(k_msm_class_hist, "k_msm_class_*"), cb, 256, s, hist.p, nb, cls.p);
+    launch_quiet_sized(KERNEL_OF(k_msm_class_scan), 1, 256, s, cls.p, cls.as<u32>() + 256, cls.as<u32>() + 512);
+    launch_quiet_sized(KERNEL_OF(k_msm_class_scatter), cb, 256, s, hist.p, nb, cls.as<u32>() + 256, cls.as<u32>() + 512, perm.p);
     prof_mark(nullptr);
     // The digit passes above need the scalars only: the host form copies the POINTS now, beside them (points_arrive), and only
     // then are the points converted to raw limbs.  Skewed scalars (a bucket beyond 2048 items would be one lane's serial work)
     // fall back to the per-point multiples, whose cost does not depend on the scalars.
     if (points_arrive) { const int rc = points_arrive(); if (rc) return rc; }
-    prof_mark(W == 3 ? "k_msm_rawpts_g1" : "k_msm_rawpts_g2");
-    if (W == 3) hipLaunchKernelGGL(k_msm_rawpts_g1, dim3(nblocks(n)), dim3(WG), 0, s, d_pts, raw.as<i32>(), n);
-    else hipLaunchKernelGGL(k_msm_rawpts_g2, dim3(nblocks(n)), dim3(WG), 0, s, d_pts, raw.as<i32>(), n);
+    if (W == 3) launch(KERNEL_OF(k_msm_rawpts_g1), nblocks(n), s, d_pts, raw.p, n);
+    else launch(KERNEL_OF(k_msm_rawpts_g2), nblocks(n), s, d_pts, raw.p, n);
     prof_mark(nullptr);
     HIPCHK(hipStreamSynchronize(s));
     if (biggest > 2048) return BLSMI_E_SKEW;
     if (!sort_mode) items = idx.as<u32>();
-    prof_mark(W == 3 ? "k_g1_msm_bucket_raw" : "k_g2_msm_bucket_raw_pair");
-    if (W == 3) hipLaunchKernelGGL(k_g1_msm_bucket_raw, dim3(nblocks(nb)), dim3(WG), 0, s, (const i32*)raw.as<i32>(), items, (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), slice_stride, nb);
-    else hipLaunchKernelGGL(k_g2_msm_bucket_raw_pair, dim3((unsigned)((nb + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)raw.as<i32>(), items, (const u32*)offs.as<u32>(), (const u32*)hist.as<u32>(), (const u32*)perm.as<u32>(), buckets.as<i32>(), slice_stride, nb);
+    if (W == 3) launch(KERNEL_OF(k_g1_msm_bucket_raw), nblocks(nb), s, raw.p, items, offs.p, hist.p, perm.p, buckets.p, slice_stride, nb);
+    else launch(KERNEL_OF(k_g2_msm_bucket_raw_pair), tuple_blocks(Layout::pair, nb), s, raw.p, items, offs.p, hist.p, perm.p, buckets.p, slice_stride, nb);
     // running sums per chunk WITHOUT the per-lane multiplication, then the fold that carries the odd-element sums along (msm.inc):
     // one addition deep per level; out come, per window, X, L and O_0 .. O_{m-1}
     const bool pairk = W == 6 && tune().pair_layout;                       // G2: a lane pair per chunk / per sum, two waves per SIMD
-    prof_mark(W == 6 ? (pairk ? "k_g2_msm_chunk2_pair" : "k_g2_msm_chunk2") : "k_g1_msm_chunk2");
-    if (pairk) hipLaunchKernelGGL(k_g2_msm_chunk2_pair, dim3((unsigned)((nct + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
-    else if (W == 6) hipLaunchKernelGGL(k_g2_msm_chunk2, dim3(nblocks(nct)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
-    else hipLaunchKernelGGL(k_g1_msm_chunk2, dim3(nblocks(nct)), dim3(WG), 0, s, (const i32*)buckets.as<i32>(), ch0.as<i32>(), c, K, nb, nct);
-    prof_mark(W == 6 ? (pairk ? "k_g2_msm_fold2_pair" : "k_g2_msm_fold2") : "k_g1_msm_fold2");
+    if (pairk) launch(KERNEL_OF(k_g2_msm_chunk2_pair), tuple_blocks(Layout::pair, nct), s, buckets.p, ch0.p, c, K, nb, nct);
+    else if (W == 6) launch(KERNEL_OF(k_g2_msm_chunk2), nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
+    else launch(KERNEL_OF(k_g1_msm_chunk2), nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
+    prof_mark(W == 6 ? (pairk ? KERNEL_OF(k_g2_msm_fold2_pair) : KERNEL_OF(k_g2_msm_fold2)).name : KERNEL_OF(k_g1_msm_fold2).name);   // one segment: the levels of the fold
     i32* src = ch0.as<i32>(); i32* dst = ch1.as<i32>();
     int narr = 2, m = 0;
     const bool lat_tail = tune().lat_max > 0 && per_win_chunks == ((size_t)1 << 13) && K == 8;   // the tail runs as a latency program (k_lat.hip), which reads the inter-kernel record form
     for (size_t len = per_win_chunks; len > 1; len /= 2, narr++, m++) {
         const size_t lanes = (size_t)(narr + 1) * nbw * (len / 2);
         const int io = (lat_tail && len == 2) ? 1 : 0;                     // the last level writes what the tail program reads
-        if (pairk) hipLaunchKernelGGL(k_g2_msm_fold2_pair, dim3((unsigned)((lanes + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)src, dst, narr, nbw, len, io);
-        else if (W == 6) hipLaunchKernelGGL(k_g2_msm_fold2, dim3(nblocks(lanes)), dim3(WG), 0, s, (const i32*)src, dst, narr, nbw, len, io);
-        else hipLaunchKernelGGL(k_g1_msm_fold2, dim3(nblocks(lanes)), dim3(WG), 0, s, (const i32*)src, dst, narr, nbw, len, io);
+        if (pairk) launch_quiet(KERNEL_OF(k_g2_msm_fold2_pair), tuple_blocks(Layout::pair, lanes), s, src, dst, narr, nbw, len, io);
+        else if (W == 6) launch_quiet(KERNEL_OF(k_g2_msm_fold2), nblocks(lanes), s, src, dst, narr, nbw, len, io);
+        else launch_quiet(KERNEL_OF(k_g1_msm_fold2), nblocks(lanes), s, src, dst, narr, nbw, len, io);
         std::swap(src, dst);
     }
     const size_t nrec = (size_t)(m + 2) * nbw;                             // X, L, O_0 .. O_{m-1} per window
     if (lat_tail) {                              // Horner over the O's and over the 8 / 4 windows + ToAffine: one wave (k_lat.hip: msmfin1 / msmfin2)
         const size_t prog = W == 3 ? LAT_MSMFIN1_OFFSET : LAT_MSMFIN2_OFFSET;
         DBuf good; HIPCHK(good.alloc(1, s));
-        prof_mark(W == 3 ? "k_lat:msmfin1" : "k_lat:msmfin2");
-        launch_lat(prog, s, {.b3 = lat_count(nrec, src), .ok = good.p, .out = d_out}, 1);
-        hipLaunchKernelGGL(k_good_to_flag, dim3(1), dim3(WG), 0, s, (const u8*)good.as<u8>(), d_flag);
+        launch_lat_marked(prog, s, {.b3 = lat_count(nrec, src), .ok = good.p, .out = d_out}, 1);
+        launch_quiet(KERNEL_OF(k_good_to_flag), 1, s, good.p, d_flag);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         return BLSMI_OK;
     }
-    prof_mark(W == 6 ? "k_g2_msm_final2" : "k_g1_msm_final2");
-    if (W == 6) hipLaunchKernelGGL(k_g2_msm_final2, dim3(1), dim3(WG), 0, s, (const i32*)src, nbw, m, 3, c, d_out, d_flag);
-    else hipLaunchKernelGGL(k_g1_msm_final2, dim3(1), dim3(WG), 0, s, (const i32*)src, nbw, m, 3, c, d_out, d_flag);
+    if (W == 6) launch(KERNEL_OF(k_g2_msm_final2), 1, s, src, nbw, m, 3, c, d_out, d_flag);
+    else launch(KERNEL_OF(k_g1_msm_final2), 1, s, src, nbw, m, 3, c, d_out, d_flag);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -1517,36 +1543,36 @@ static int msm_dev_api(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, c
     *out_inf = flag;
     return BLSMI_OK;
 }
-static const MsmKernels g_mk1{k_g1_msm_bucket, k_g1_msm_chunk, k_g1_msm_fold, k_g1_msm_final};
-static const MsmKernels g_mk2{k_g2_msm_bucket, k_g2_msm_chunk, k_g2_msm_fold, k_g2_msm_final};
+static const MsmKernels g_mk1{KERNEL_OF(k_g1_msm_bucket), KERNEL_OF(k_g1_msm_chunk), KERNEL_OF(k_g1_msm_fold), KERNEL_OF(k_g1_msm_final)};
+static const MsmKernels g_mk2{KERNEL_OF(k_g2_msm_bucket), KERNEL_OF(k_g2_msm_chunk), KERNEL_OF(k_g2_msm_fold), KERNEL_OF(k_g2_msm_final)};
 BLSMI_API int blsmi_g1_msm(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[96], int* out_inf) {
-    return msm_host<96, 3>(g_mk1, k_g1_mul, k_g1_sum0, k_g1_sum, k_g1_sum_final, pts, scalars, n, out, out_inf);
+    return msm_host<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, scalars, n, out, out_inf);
 }
 BLSMI_API int blsmi_g2_msm(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[192], int* out_inf) {
-    return msm_host<192, 6>(g_mk2, k_g2_mul, k_g2_sum0, k_g2_sum, k_g2_sum_final, pts, scalars, n, out, out_inf);
+    return msm_host<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, scalars, n, out, out_inf);
 }
 BLSMI_API int blsmi_g1_msm_dev(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream) {
-    return msm_dev_api<96, 3>(g_mk1, k_g1_mul, k_g1_sum0, k_g1_sum, k_g1_sum_final, d_pts, d_scalars, n, d_out, out_inf, stream);
+    return msm_dev_api<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream);
 }
 BLSMI_API int blsmi_g2_msm_dev(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream) {
-    return msm_dev_api<192, 6>(g_mk2, k_g2_mul, k_g2_sum0, k_g2_sum, k_g2_sum_final, d_pts, d_scalars, n, d_out, out_inf, stream);
+    return msm_dev_api<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream);
 }
 #define BLSMI_FLAGS_OK(f) (((f) & ~(unsigned)BLSMI_MUL_ANY_POINT) == 0)
 BLSMI_API int blsmi_g1_msm_ex(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[96], int* out_inf, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_host<96, 3>(g_mk1, k_g1_mul, k_g1_sum0, k_g1_sum, k_g1_sum_final, pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_host<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_msm_ex(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[192], int* out_inf, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_host<192, 6>(g_mk2, k_g2_mul, k_g2_sum0, k_g2_sum, k_g2_sum_final, pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_host<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g1_msm_dev_ex(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_dev_api<96, 3>(g_mk1, k_g1_mul, k_g1_sum0, k_g1_sum, k_g1_sum_final, d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_dev_api<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_msm_dev_ex(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_dev_api<192, 6>(g_mk2, k_g2_mul, k_g2_sum0, k_g2_sum, k_g2_sum_final, d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_dev_api<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 
 #include "verify_host.inc"

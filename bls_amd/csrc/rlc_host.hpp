@@ -49,26 +49,25 @@ int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum,
     hipStream_t s = g_stream;
     if (n >= RLC_MSM_BUCKET_MIN) {
         DBuf sc; HIPCHK(sc.alloc((size_t)32 * n));
-        hipLaunchKernelGGL(k_scalar_u64_to_be32, dim3(nblocks(n)), dim3(WG), 0, s, d_r, sc.as<u8>(), n);
+        launch_quiet(KERNEL_OF(k_scalar_u64_to_be32), nblocks(n), s, d_r, sc.p, n);
         const int rc = kind == 0 ? msm_bucket_dev<96, 3>(g_mk1, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64)
                                  : msm_bucket_dev<192, 6>(g_mk2, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
         if (rc != BLSMI_E_SKEW) return rc;
     }
     const size_t pb = kind == 0 ? 96 : 192;
     DBuf m, inf; HIPCHK(m.alloc(pb * n)); HIPCHK(inf.alloc(n));
-    prof_mark(kind == 0 ? "k_g1_mul_u64" : "k_g2_mul_u64");
-    if (kind == 0) hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
-    else hipLaunchKernelGGL(k_g2_mul_u64, dim3(nblocks(n)), dim3(WG), 0, s, d_sigs, d_r, m.as<u8>(), inf.as<u8>(), n);
+    if (kind == 0) launch(KERNEL_OF(k_g1_mul_u64), nblocks(n), s, d_sigs, d_r, m.p, inf.p, n);
+    else launch(KERNEL_OF(k_g2_mul_u64), nblocks(n), s, d_sigs, d_r, m.p, inf.p, n);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
-    return kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
-                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
+    return kind == 0 ? sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
+                     : sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
 }
 // sig_side_start for a signature already on the device (the sum above, read in place): MillerLoop(-sig, G2gen) / MillerLoop(-G1gen, sig)
 // into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
 int sig_side_start_dev(int kind, const u8* d_sig, SigSide& ss) {
     HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
-    prof_mark("k_lat:miller1rawn");
+    prof_mark(lat_mark(LAT_MILLER1RAWN_OFFSET));
     launch_sig_miller(sig_pair(kind, d_sig, 0), ss.ml.p, 1, g_stream);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
@@ -148,17 +147,15 @@ int rlc_upload_keys(RlcCall& c, const uint8_t* pks, const uint8_t* inf_flags, in
 }
 // a key or a signature that is the all-zero record, or flagged by the caller: a byte per tuple into c.flags, and `any`
 void rlc_flag_inputs(RlcCall& c) {
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(c.n)), dim3(WG), 0, g_stream, (const u8*)c.dp.as<u8>(), c.k.pk_bytes / 4, (const u8*)c.ds.as<u8>(), c.k.sig_bytes / 4,
-                       (const u8*)c.inf(), c.flags.as<u8>(), c.any.as<int>(), c.n);
+    launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(c.n), g_stream, c.dp.p, c.k.pk_bytes / 4, c.ds.p, c.k.sig_bytes / 4, c.inf(), c.flags.p, c.any.p, c.n);
 }
 // r_i times the G1 point of tuple i -- src: the hash points (g2pubs; they stay for the fallback) or the keys (g1pubs) -- into `scaled`.  A scaled
 // point at infinity is flagged like an input: into flag_bytes (c.flags, or bytes of the form's own where the inputs' flags must stay), and `any`.
 void rlc_scale_g1(RlcCall& c, const u8* src, u8* scaled, u8* sinf, u8* flag_bytes) {
     hipStream_t s = g_stream;
-    prof_mark("k_g1_mul_u64");
-    hipLaunchKernelGGL(k_g1_mul_u64, dim3(nblocks(c.n)), dim3(WG), 0, s, src, (const u64*)c.dr.as<u64>(), scaled, sinf, c.n);
+    launch(KERNEL_OF(k_g1_mul_u64), nblocks(c.n), s, src, c.dr.p, scaled, sinf, c.n);
     prof_mark(nullptr);
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(c.n)), dim3(WG), 0, s, (const u8*)scaled, 24, (const u8*)nullptr, 0, (const u8*)sinf, flag_bytes, c.any.as<int>(), c.n);
+    launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(c.n), s, scaled, 24, nullptr, 0, sinf, flag_bytes, c.any.p, c.n);
 }
 // sum r_i sig_i and its Miller loop on the side stream, beside the tuple side: the kernels and their profile marks go where the context's
 // stream points (OnStream); join[0] marks the end (sig_side_start_dev)
@@ -240,7 +237,7 @@ int rlc_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, cons
         if (!cleared) { rc = hash_dev(kind, c.msgs.m.p, c.msgs.off.p, h.as<u8>(), n, s, vr.hash); if (rc) return rc; }
         rc = rlc_fallback_all(c, h.as<u8>(), vr); if (rc) return rc;
     }
-    if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, s, (const u8*)c.dok.as<u8>(), d_bitmap_slice, n);   // (a split call: the bitmap comes together on the devices)
+    if (d_bitmap_slice) launch_quiet(KERNEL_OF(k_pack_bitmap), nblocks((n + 7) / 8), s, c.dok.p, d_bitmap_slice, n);   // (a split call: the bitmap comes together on the devices)
     return rlc_finish(c, ok, nullptr, nullptr);
 }
 // The host entry points.  scalars (may be null: drawn here) are checked for zeros first; below the call's rlc_min the per-tuple path runs
@@ -398,7 +395,7 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
     // for the name -- a move of the sums to aux[1] must point the context's stream at it for the stretch (OnStream, as rlc_signature_side)
     rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(dg)), dim3(WG), 0, s, (const u8*)agg.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)ainf.as<u8>(), gflags.as<u8>(), c.any.as<int>(), dg);
+    launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(dg), s, agg.p, k.pk_bytes / 4, nullptr, 0, ainf.p, gflags.p, c.any.p, dg);
     // d' Miller loops, one per message, and their product
     launch_miller1(kind == 0 ? h.as<u8>() : agg.as<u8>(), kind == 0 ? agg.as<u8>() : h.as<u8>(), fr0.as<i32>(), dg, s, ar, nullptr);
     const i32* prod = prod_tree(fr0.as<i32>(), ar.records, fr1.as<i32>(), fr0.as<i32>(), s);
@@ -411,7 +408,7 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
         HIPCHK(hfull.alloc((size_t)k.h_bytes * n)); HIPCHK(dgo.alloc(sizeof(uint32_t) * n));
         HIPCHK(hipMemcpyAsync(dgo.p, gp.group_of.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
         const u32 hw = (u32)(k.h_bytes / 4);
-        hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * n)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dgo.as<u32>(), hfull.as<u32>(), hw, n);
+        launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)hw * n), s, h.p, dgo.p, hfull.p, hw, n);
         rc = rlc_fallback_all(c, hfull.as<u8>(), verify_route(kind, n, false, false, t, route_load(n))); if (rc) return rc;
     }
     return rlc_finish(c, ok, ok_bitmap, combined);
@@ -475,16 +472,11 @@ int locate_failing_positions(RlcCall& c, const blsmi_route::LocatePlan& lp, cons
     HIPCHK(one.alloc(B)); HIPCHK(dfail.alloc(B));
     int rc = segsum_dev(k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
-    prof_mark("k_locate_sig_pairs");
-    hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(B)), dim3(WG), 0, s, c.kind == 0 ? 0 : 1, (const u8*)sb.as<u8>(), (const u8*)sbinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
-                       g1.as<u8>(), g2.as<u8>(), bbad.as<u8>(), B);
+    launch(KERNEL_OF(k_locate_sig_pairs), nblocks(B), s, c.kind == 0 ? 0 : 1, sb.p, sbinf.p, g_gens.g1, g_gens.g2, g1.p, g2.p, bbad.p, B);
     launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), B, s, pairing_layout(0, B, tune(), bload));
-    prof_mark("k_fq12_mul_pairs_row");
-    hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(B)), dim3(WG), 0, s, bval, (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
-                       fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, B);
+    launch(KERNEL_OF(k_fq12_mul_pairs_row), tuple_blocks(Layout::row, B), s, bval, fs.p, fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, B);
     final_exp_values(fe, prod.p, vals.as<u64>(), one.p, B, s);
-    prof_mark("k_locate_block_fail");
-    hipLaunchKernelGGL(k_locate_block_fail, dim3(rblocks(B)), dim3(WG), 0, s, (const u8*)c.flags.as<u8>(), sflags, n, lp.block, (const u8*)bbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), B);
+    launch(KERNEL_OF(k_locate_block_fail), tuple_blocks(Layout::row, B), s, c.flags.p, sflags, n, lp.block, bbad.p, one.p, dfail.p, B);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, B, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
@@ -505,18 +497,17 @@ int locate_recheck(RlcCall& c, const DBuf& h, const std::vector<uint32_t>& pos, 
     if (hpos) { HIPCHK(dhpos.alloc(sizeof(uint32_t) * nre)); HIPCHK(hipMemcpyAsync(dhpos.p, hpos->data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s)); }
     auto gather_by = [&](const DBuf& from, DBuf& to, size_t bytes, const DBuf& by) {
         const u32 q = (u32)(bytes / 16);
-        hipLaunchKernelGGL(k_gather_records16, dim3(nblocks((size_t)q * nre)), dim3(WG), 0, s, (const uint4*)from.as<uint4>(), (const u32*)by.as<u32>(), to.as<uint4>(), q, nre);
+        launch_quiet(KERNEL_OF(k_gather_records16), nblocks((size_t)q * nre), s, from.p, by.p, to.p, q, nre);
     };
     auto gather = [&](const DBuf& from, DBuf& to, size_t bytes) { gather_by(from, to, bytes, dpos); };
-    prof_mark("k_gather_records16");
+    prof_mark(KERNEL_OF(k_gather_records16).name);                     // one segment: the gathers
     gather_by(h, hd, k.h_bytes, hpos ? dhpos : dpos); gather(c.dp, pd, k.pk_bytes); gather(c.ds, sd, k.sig_bytes);
-    if (c.has_inf) hipLaunchKernelGGL(k_gather_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)c.di.as<u8>(), (const u32*)dpos.as<u32>(), id.as<u8>(), nre);
+    if (c.has_inf) launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(nre), s, c.di.p, dpos.p, id.p, nre);
     prof_mark(nullptr);
     const VerifyRoute vr = verify_route(c.kind, nre, false, false, tune(), route_load(nre));
     int rc = verify_pair_stage(c.kind, hd.as<u8>(), pd.p, sd.p, c.has_inf ? id.p : nullptr, okd.p, f.as<i32>(), nre, s, vr);
     if (rc) return rc;
-    prof_mark("k_scatter_bytes");
-    hipLaunchKernelGGL(k_scatter_bytes, dim3(nblocks(nre)), dim3(WG), 0, s, (const u8*)okd.as<u8>(), (const u32*)dpos.as<u32>(), c.dok.as<u8>(), nre);
+    launch(KERNEL_OF(k_scatter_bytes), nblocks(nre), s, okd.p, dpos.p, c.dok.p, nre);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
@@ -564,7 +555,7 @@ int verify_batch_rlc_locate_host(int kind, const uint8_t* msgs, const uint64_t* 
     rlc_scale_g1(c, kind == 0 ? h.as<u8>() : c.dp.as<u8>(), scaled.as<u8>(), sinf.as<u8>(), sflags.as<u8>());
     launch_miller1(scaled.as<u8>(), kind == 0 ? c.dp.as<u8>() : h.as<u8>(), fr.as<i32>(), n, s, ar, nullptr);
     // stage 2: the block values, then the tree over them (its levels alternate between t0 and t1; the block values stay)
-    prof_mark("k_fq12_seg_prod_row");
+    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of seg_prod_dev
     rc = seg_prod_dev(fr.as<i32>(), nrec, nullptr, bplan, bblob.as<u8>(), bval.as<i32>(), nullptr, s);
     if (rc) return rc;
     prof_mark(nullptr);
@@ -629,8 +620,8 @@ int cells_signature_side(RlcCall& c, const SegPlan& plan, CellBufs& b) {
     OnStream on(st);
     int rc = segsum_dev(c.k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, c.n, b.dx.as<u32>(), plan, b.sc.as<u8>(), b.scinf.as<u8>(), 1, st, c.dr.as<u64>());
     if (rc) return rc;
-    rc = c.kind == 0 ? sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false)
-                     : sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false);
+    rc = c.kind == 0 ? sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false)
+                     : sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
@@ -649,17 +640,11 @@ int cells_failing_positions(RlcCall& c, const blsmi_route::GroupPlan& gp, const 
     HIPCHK(prod.alloc(fe == Layout::wave ? 576 * C : sizeof(i32) * words * C)); HIPCHK(vals.alloc(576 * C)); HIPCHK(one.alloc(C)); HIPCHK(dfail.alloc(C));
     HIPCHK(doff.alloc(sizeof(uint64_t) * (C + 1)));
     HIPCHK(hipMemcpyAsync(doff.p, cp.cell_off.data(), sizeof(uint64_t) * (C + 1), hipMemcpyHostToDevice, s));
-    prof_mark("k_locate_sig_pairs");
-    hipLaunchKernelGGL(k_locate_sig_pairs, dim3(nblocks(C)), dim3(WG), 0, s, c.kind == 0 ? 0 : 1, (const u8*)b.sc.as<u8>(), (const u8*)b.scinf.as<u8>(), (const u8*)g_gens.g1, (const u8*)g_gens.g2,
-                       g1.as<u8>(), g2.as<u8>(), sbad.as<u8>(), C);
+    launch(KERNEL_OF(k_locate_sig_pairs), nblocks(C), s, c.kind == 0 ? 0 : 1, b.sc.p, b.scinf.p, g_gens.g1, g_gens.g2, g1.p, g2.p, sbad.p, C);
     launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), C, s, pairing_layout(0, C, tune(), cload));
-    prof_mark("k_fq12_mul_pairs_row");
-    hipLaunchKernelGGL(k_fq12_mul_pairs_row, dim3(rblocks(C)), dim3(WG), 0, s, (const i32*)b.cval.as<i32>(), (const i32*)fs.as<i32>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(),
-                       fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, C);
+    launch(KERNEL_OF(k_fq12_mul_pairs_row), tuple_blocks(Layout::row, C), s, b.cval.p, fs.p, fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, C);
     final_exp_values(fe, prod.p, vals.as<u64>(), one.p, C, s);
-    prof_mark("k_locate_cell_fail");
-    hipLaunchKernelGGL(k_locate_cell_fail, dim3(rblocks(C)), dim3(WG), 0, s, (const u8*)c.flags.as<u8>(), (const u8*)nullptr, (const u32*)b.dx.as<u32>(), (const u64*)doff.as<u64>(),
-                       (const u8*)b.kflag.as<u8>(), (const u8*)sbad.as<u8>(), (const u8*)one.as<u8>(), dfail.as<u8>(), c.n, C);
+    launch(KERNEL_OF(k_locate_cell_fail), tuple_blocks(Layout::row, C), s, c.flags.p, nullptr, b.dx.p, doff.p, b.kflag.p, sbad.p, one.p, dfail.p, c.n, C);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(fail.data(), dfail.p, C, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
@@ -716,10 +701,10 @@ int verify_batch_rlc_grouped_locate_host(int kind, const uint8_t* msgs, const ui
     // K_c for every cell (on the main stream: the profile names k_g?_segsum_chunk_u64 there); a sum at infinity is flagged per cell
     rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, b.dx.as<u32>(), plan, b.kc.as<u8>(), b.kinf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
-    hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(C)), dim3(WG), 0, s, (const u8*)b.kc.as<u8>(), k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)b.kinf.as<u8>(), b.kflag.as<u8>(), c.any.as<int>(), C);
+    launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(C), s, b.kc.p, k.pk_bytes / 4, nullptr, 0, b.kinf.p, b.kflag.p, c.any.p, C);
     // every cell its group's hash point, C Miller loops with one value each, the values kept; the tree over them gives the total
     const u32 hw = (u32)(k.h_bytes / 4);
-    hipLaunchKernelGGL(k_gather_records, dim3(nblocks((size_t)hw * C)), dim3(WG), 0, s, (const u32*)h.as<u32>(), (const u32*)dcg.as<u32>(), hc.as<u32>(), hw, C);
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)hw * C), s, h.p, dcg.p, hc.p, hw, C);
     launch_miller_tuples(kind == 0 ? hc.as<u8>() : b.kc.as<u8>(), kind == 0 ? b.kc.as<u8>() : hc.as<u8>(), b.cval.as<i32>(), C, s, pairing_layout(0, C, t, route_load(C)));
     prof_mark(nullptr);
     const i32* total = prod_tree(b.cval.as<i32>(), C, t0.as<i32>(), t1.as<i32>(), s);

@@ -153,6 +153,9 @@ inline void apply_env(Tuning& t, uint64_t explicit_mask, Getenv&& env) {
 // one-lane kernels of what has no other layout)
 enum class Layout : uint8_t { wave, row, quad, pair, single };
 enum class Call : uint8_t { pairing, verify, aggregate };
+// Tuples a workgroup of 64 lanes serves in a lane layout, and the workgroups n tuples take (a wave-layout call launches a wave per tuple)
+constexpr size_t tuples_per_block(Layout l) { return l == Layout::single ? 64 : l == Layout::pair ? 32 : l == Layout::quad ? 16 : l == Layout::row ? 4 : 1; }
+constexpr unsigned tuple_blocks(Layout l, size_t n) { return (unsigned)((n + tuples_per_block(l) - 1) / tuples_per_block(l)); }
 
 // The hand-overs are a lone caller's; a call of at least crowd_floor tuples also counts the `others` in flight on its device.
 inline bool crowded(size_t n, const Tuning& t) { return t.crowd_quad && n >= t.crowd_floor; }

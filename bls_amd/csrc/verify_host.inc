@@ -18,8 +18,7 @@ struct PrepKeys { const i32* tables; const u32* idx; };
 // lane-pair kernels reading them: 16 384 verifies 8.3 against ~12 ms)
 int prep_gather_keys(const PrepKeys& prep, DBuf& pk, size_t n, hipStream_t s) {
     HIPCHK(pk.alloc((size_t)192 * n, s));
-    prof_mark("k_prepared_gather_keys");
-    hipLaunchKernelGGL(k_prepared_gather_keys, dim3(nblocks(48 * n)), dim3(WG), 0, s, prep.tables, prep.idx, pk.as<u32>(), n);
+    launch(KERNEL_OF(k_prepared_gather_keys), nblocks(48 * n), s, prep.tables, prep.idx, pk.p, n);
     prof_mark(nullptr);
     return BLSMI_OK;
 }
@@ -29,7 +28,7 @@ int prep_gather_keys(const PrepKeys& prep, DBuf& pk, size_t n, hipStream_t s) {
 // d_special (may be null; with g1_clear == false): a device int that gets bit 1 when some message's mapped points cancel (hash.cuh: swu_finish_g1)
 // r: the route of the hash (route.h: hash_route; hash_route_alone below for a hash that is the whole call)
 int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h, size_t n, hipStream_t s, const HashRoute& r, bool g1_clear = true, int* d_special = nullptr) {
-    dim3 g(nblocks(n)), w(WG), g2(nblocks(2 * n));
+    const unsigned g = nblocks(n), g2 = nblocks(2 * n);
     // a call in the lane-row layout (2 048 .. 8 192 tuples) hashes on the latency programs while they beat the mid-size kernels'
     // flat times (tools/midsize4.py: HashG1 two lanes + finish 1.5 ms, k_hash_g2_pair 2.9 ms; the programs take 0.27 / 0.53 ms per 1 024 messages on top of the maps)
     // HashG2 of 2 048 .. 4 096 messages (round 6): the maps and the isogeny a lane pair per message (k_hash_g2_front, an eighth of the SIMDs), then the cofactor
@@ -44,21 +43,18 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
         const size_t prog = kind == 0 ? LAT_HASHFIN1_OFFSET : kind == 1 ? LAT_HASHFIN2_OFFSET : LAT_COFAC2_OFFSET;
         DBuf pts, good; HIPCHK(pts.alloc(rec * n, s)); HIPCHK(good.alloc(n, s));
         // the smallest calls: one WAVE per SWU map, its exponentiation with one limb per lane (fp_row.cuh); then a row of sixteen lanes per map (k_hash.hip)
-        prof_mark(kind == 0 ? (waves ? "k_swu_g1_waves" : rows ? "k_swu_g1_rows" : "k_swu_g1_two_lanes") : kind == 1 ? (waves ? "k_swu_g2_waves" : rows ? "k_swu_g2_rows" : "k_swu_g2_two_lanes") : (waves ? "k_tai_g2_waves8" : "k_tai_g2_lanes8"));
-        if (rows && kind == 0) hipLaunchKernelGGL(k_swu_g1_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (rows) hipLaunchKernelGGL(k_swu_g2_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (kind == 0 && waves) hipLaunchKernelGGL(k_swu_g1_waves, dim3((unsigned)(2 * n)), dim3(64), 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (kind == 1 && waves) hipLaunchKernelGGL(k_swu_g2_waves, dim3((unsigned)(2 * n)), dim3(64), 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (kind == 0) hipLaunchKernelGGL(k_swu_g1_two_lanes, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (kind == 1) hipLaunchKernelGGL(k_swu_g2_two_lanes, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else if (waves) hipLaunchKernelGGL(k_tai_g2_waves8, dim3((unsigned)n), dim3(512), 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, pts.as<u8>(), n);
-        else hipLaunchKernelGGL(k_tai_g2_lanes8, dim3(nblocks(8 * n)), w, 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, pts.as<u8>(), n);
-        prof_mark(kind == 0 ? "k_lat:hashfin1" : kind == 1 ? "k_lat:hashfin2" : "k_lat:cofac2");
-        launch_lat(prog, s, {.b0 = {pts.p, rec}, .ok = good.p, .out = d_h}, n);
-        prof_mark("k_hash_redo");
-        if (kind == 0) hipLaunchKernelGGL(k_hash_g1_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
-        else if (kind == 1) hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
-        else hipLaunchKernelGGL(k_hash_g2_domain_redo, g, w, 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
+        if (rows && kind == 0) launch(KERNEL_OF(k_swu_g1_rows), nblocks(32 * n), s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (rows) launch(KERNEL_OF(k_swu_g2_rows), nblocks(32 * n), s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (kind == 0 && waves) launch_sized(KERNEL_OF(k_swu_g1_waves), 2 * n, 64, s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (kind == 1 && waves) launch_sized(KERNEL_OF(k_swu_g2_waves), 2 * n, 64, s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (kind == 0) launch(KERNEL_OF(k_swu_g1_two_lanes), g2, s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (kind == 1) launch(KERNEL_OF(k_swu_g2_two_lanes), g2, s, d_msgs, d_off_or_domain, pts.p, n);
+        else if (waves) launch_sized(KERNEL_OF(k_tai_g2_waves8), n, 512, s, d_msgs, d_off_or_domain, pts.p, n);
+        else launch(KERNEL_OF(k_tai_g2_lanes8), nblocks(8 * n), s, d_msgs, d_off_or_domain, pts.p, n);
+        launch_lat_marked(prog, s, {.b0 = {pts.p, rec}, .ok = good.p, .out = d_h}, n);
+        if (kind == 0) launch(kernel_named(k_hash_g1_redo, "k_hash_redo"), g, s, d_msgs, d_off_or_domain, good.p, d_h, n);
+        else if (kind == 1) launch(kernel_named(k_hash_g2_redo, "k_hash_redo"), g, s, d_msgs, d_off_or_domain, good.p, d_h, n);
+        else launch(kernel_named(k_hash_g2_domain_redo, "k_hash_redo"), g, s, d_msgs, d_off_or_domain, good.p, d_h, n);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
@@ -67,21 +63,17 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     // SWU maps of a message on two lanes, then the tail one message per lane -- k_hash_g1 alone leaves most SIMDs without a wave there
     if (r.path == HashPath::g1_lane || r.path == HashPath::g1_quad) {
         DBuf pts; HIPCHK(pts.alloc((size_t)192 * n, s));
-        prof_mark(rows ? "k_swu_g1_rows" : "k_swu_g1_two_lanes");
-        if (rows) hipLaunchKernelGGL(k_swu_g1_rows, dim3(nblocks(32 * n)), w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
-        else hipLaunchKernelGGL(k_swu_g1_two_lanes, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, pts.as<u8>(), n);
+        if (rows) launch(KERNEL_OF(k_swu_g1_rows), nblocks(32 * n), s, d_msgs, d_off_or_domain, pts.p, n);
+        else launch(KERNEL_OF(k_swu_g1_two_lanes), g2, s, d_msgs, d_off_or_domain, pts.p, n);
         if (r.path == HashPath::g1_quad) {                                 // four lanes per message (k_hash_quad.hip, quad_g1.inc); exceptions redone a message per lane
             DBuf good; HIPCHK(good.alloc(n, s));
-            prof_mark("k_hash_g1_finish_quad");
-            hipLaunchKernelGGL(k_hash_g1_finish_quad, dim3(qblocks(n)), w, 0, s, (const u8*)pts.as<u8>(), good.as<u8>(), d_h, n);
-            prof_mark("k_hash_redo");
-            hipLaunchKernelGGL(k_hash_g1_finish_redo, g, w, 0, s, (const u8*)pts.as<u8>(), (const u8*)good.as<u8>(), d_h, n);
+            launch(KERNEL_OF(k_hash_g1_finish_quad), tuple_blocks(Layout::quad, n), s, pts.p, good.p, d_h, n);
+            launch(kernel_named(k_hash_g1_finish_redo, "k_hash_redo"), g, s, pts.p, good.p, d_h, n);
             prof_mark(nullptr);
             HIPCHK(hipGetLastError());
             return BLSMI_OK;
         }
-        prof_mark("k_hash_g1_finish");
-        hipLaunchKernelGGL(k_hash_g1_finish, g, w, 0, s, (const u8*)pts.as<u8>(), d_h, n, g1_clear ? 1 : 0, d_special);
+        launch(KERNEL_OF(k_hash_g1_finish), g, s, pts.p, d_h, n, g1_clear ? 1 : 0, d_special);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
@@ -93,22 +85,17 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
         const bool g2_oct_tail = r.path == HashPath::g2_oct, g2_row_tail = r.path == HashPath::g2_row;
         if (r.path != HashPath::g2_pair) {
             DBuf jb; HIPCHK(jb.alloc(sizeof(i32) * 6 * NL_IO * n, s));
-            prof_mark("k_hash_g2_front");
-            hipLaunchKernelGGL(k_hash_g2_front, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, good.as<u8>(), jb.as<i32>(), n, redo_every);
-            prof_mark(g2_oct_tail ? "k_clear_h2_oct" : g2_row_tail ? "k_clear_h2_row" : "k_clear_h2_quad");
-            if (g2_oct_tail) hipLaunchKernelGGL(k_clear_h2_oct, dim3((unsigned)((n + 7) / 8)), w, 0, s, (const i32*)jb.as<i32>(), good.as<u8>(), d_h, n);
-            else if (g2_row_tail) hipLaunchKernelGGL(k_clear_h2_row, dim3(rblocks(n)), w, 0, s, (const i32*)jb.as<i32>(), good.as<u8>(), d_h, n);
-            else hipLaunchKernelGGL(k_clear_h2_quad, dim3(qblocks(n)), w, 0, s, (const i32*)jb.as<i32>(), good.as<u8>(), d_h, n);
-            prof_mark("k_hash_redo");
-            hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
+            launch(KERNEL_OF(k_hash_g2_front), g2, s, d_msgs, d_off_or_domain, good.p, jb.p, n, redo_every);
+            if (g2_oct_tail) launch(KERNEL_OF(k_clear_h2_oct), (n + 7) / 8, s, jb.p, good.p, d_h, n);
+            else if (g2_row_tail) launch(KERNEL_OF(k_clear_h2_row), tuple_blocks(Layout::row, n), s, jb.p, good.p, d_h, n);
+            else launch(KERNEL_OF(k_clear_h2_quad), tuple_blocks(Layout::quad, n), s, jb.p, good.p, d_h, n);
+            launch(kernel_named(k_hash_g2_redo, "k_hash_redo"), g, s, d_msgs, d_off_or_domain, good.p, d_h, n);
             prof_mark(nullptr);
             HIPCHK(hipGetLastError());
             return BLSMI_OK;
         }
-        prof_mark("k_hash_g2_pair");
-        hipLaunchKernelGGL(k_hash_g2_pair, g2, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, good.as<u8>(), d_h, n, redo_every);
-        prof_mark("k_hash_redo");
-        hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, (const u8*)good.as<u8>(), d_h, n);
+        launch(KERNEL_OF(k_hash_g2_pair), g2, s, d_msgs, d_off_or_domain, good.p, d_h, n, redo_every);
+        launch(kernel_named(k_hash_g2_redo, "k_hash_redo"), g, s, d_msgs, d_off_or_domain, good.p, d_h, n);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
@@ -119,18 +106,15 @@ int hash_dev(int kind, const void* d_msgs, const void* d_off_or_domain, u8* d_h,
     const bool cofac_pair = tune().cofac2_pair;
     if (kind == 2 && cofac_pair) {
         DBuf pts; HIPCHK(pts.alloc((size_t)192 * n, s));
-        prof_mark("k_tai_g2_wave");
-        hipLaunchKernelGGL(k_tai_g2_wave, g, w, 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, pts.as<u8>(), n);
-        prof_mark("k_cofac2_pair");
-        hipLaunchKernelGGL(k_cofac2_pair, g2, w, 0, s, (const u8*)pts.as<u8>(), d_h, n);
+        launch(KERNEL_OF(k_tai_g2_wave), g, s, d_msgs, d_off_or_domain, pts.p, n);
+        launch(KERNEL_OF(k_cofac2_pair), g2, s, pts.p, d_h, n);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
     }
-    prof_mark(kind == 0 ? "k_hash_g1" : kind == 1 ? "k_hash_g2" : "k_hash_g2_domain");
-    if (kind == 0) hipLaunchKernelGGL(k_hash_g1, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, d_h, n, g1_clear ? 1 : 0, d_special);
-    else if (kind == 1) hipLaunchKernelGGL(k_hash_g2, g, w, 0, s, (const u8*)d_msgs, (const u64*)d_off_or_domain, d_h, n);
-    else hipLaunchKernelGGL(k_hash_g2_domain, g, w, 0, s, (const u8*)d_msgs, (const u8*)d_off_or_domain, d_h, n);
+    if (kind == 0) launch(KERNEL_OF(k_hash_g1), g, s, d_msgs, d_off_or_domain, d_h, n, g1_clear ? 1 : 0, d_special);
+    else if (kind == 1) launch(KERNEL_OF(k_hash_g2), g, s, d_msgs, d_off_or_domain, d_h, n);
+    else launch(KERNEL_OF(k_hash_g2_domain), g, s, d_msgs, d_off_or_domain, d_h, n);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
@@ -140,11 +124,10 @@ inline HashRoute hash_route_alone(int kind, size_t n) { return hash_route(kind, 
 // one level of the Fq12 product tree: dst[t] = src[t] * src[t + half] (a missing partner counts as 1), SoA buffers of cur / half records
 void launch_prod_level(const i32* src, i32* dst, size_t cur, size_t half, hipStream_t s) {
     const bool lat = half <= tune().lat_max;
-    prof_mark(lat ? "k_lat:mul12raw" : "k_fq12_prod_level");
     if (lat)                                                               // few products: one per wave (k_lat.hip, "mul12raw"), ~5 us instead of ~80
-        launch_lat(LAT_MUL12RAW_OFFSET, s, {.b2 = lat_count(half), .b3 = lat_count(cur, src), .out = dst}, half);
+        launch_lat_marked(LAT_MUL12RAW_OFFSET, s, {.b2 = lat_count(half), .b3 = lat_count(cur, src), .out = dst}, half);
     else
-        hipLaunchKernelGGL(k_fq12_prod_level, dim3(nblocks(half)), dim3(WG), 0, s, src, dst, cur, half);
+        launch(KERNEL_OF(k_fq12_prod_level), nblocks(half), s, src, dst, cur, half);
     prof_mark(nullptr);
 }
 // The product tree over the cur values at src: level after level into a, b, a, ... (each with room for half the values it reads; src is never
@@ -162,22 +145,20 @@ const i32* prod_tree(const i32* src, size_t cur, i32* a, i32* b, hipStream_t s) 
 void launch_miller1(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, const AggregateRoute& r, const PrepKeys* prep) {
     const size_t m = r.records;
     if (r.tables) {
-        prof_mark("k_miller1x2_prep_pair");
-        hipLaunchKernelGGL(k_miller1x2_prep_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, d_g1, prep->tables, prep->idx, f, n, m);
+        launch(KERNEL_OF(k_miller1x2_prep_pair), tuple_blocks(Layout::pair, m), s, d_g1, prep->tables, prep->idx, f, n, m);
         return;
     }
     const Layout l = r.layout;
-    prof_mark(l == Layout::row ? "k_miller1s_row" : l == Layout::wave ? "k_lat:miller1raw" : l == Layout::quad ? "k_miller1x2_quad" : l == Layout::pair ? "k_miller1x2_pair" : "k_miller1h");
     if (l == Layout::row)                                                  // a few thousand signers: one Miller loop per lane ROW (k_pairing_row.hip), n values as on the wave path
-        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, (size_t)96, d_g2, (size_t)192, f, n, (const i32*)nullptr, (size_t)0, n);
+        launch(KERNEL_OF(k_miller1s_row), tuple_blocks(l, n), s, d_g1, 96, d_g2, 192, f, n, nullptr, 0, n);
     else if (l == Layout::wave)                                            // small aggregate: one Miller loop per wave (any Miller value serves a product that is final-exponentiated)
-        launch_lat(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
+        launch_lat_marked(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
     else if (l == Layout::quad)                                            // mid-size aggregate: two consecutive tuples per lane QUAD (k_pairing_quad.hip)
-        hipLaunchKernelGGL(k_miller1x2_quad, dim3(qblocks(m)), dim3(WG), 0, s, d_g1, d_g2, f, n, m);
+        launch(KERNEL_OF(k_miller1x2_quad), tuple_blocks(l, m), s, d_g1, d_g2, f, n, m);
     else if (l == Layout::pair)                                            // two consecutive tuples per lane pair, one 2-pair loop
-        hipLaunchKernelGGL(k_miller1x2_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, d_g1, d_g2, f, n, m);
+        launch(KERNEL_OF(k_miller1x2_pair), tuple_blocks(l, m), s, d_g1, d_g2, f, n, m);
     else
-        hipLaunchKernelGGL(k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+        launch(kernels_of(l).miller1h, tuple_blocks(l, n), s, d_g1, d_g2, f, n);
 }
 // The signature side's Miller loop -- MillerLoop(-sig, G2One) for g2pubs, MillerLoop(-G1One, sig) for g1pubs -- needs nothing of the message,
 // so it runs on a side stream WHILE the message is hashed (route.h: sig_side), its values left in f.  Small calls: program "miller1rawn", one
@@ -203,7 +184,7 @@ int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host
     if (host_sigs) { int rc = upload_points(k.sig_bytes, sigs_jac, host_sigs, d_sigs, n, st); if (rc) return rc; }
     const SigPair sp = sig_pair(kind, d_sigs, k.sig_bytes);
     if (side == Side::row)
-        hipLaunchKernelGGL(k_miller1s_row, dim3(rblocks(n)), dim3(WG), 0, st, (const u8*)sp.P.p, sp.P.stride, (const u8*)sp.Q.p, sp.Q.stride, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, (size_t)0, n);
+        launch_quiet(KERNEL_OF(k_miller1s_row), tuple_blocks(Layout::row, n), st, sp.P.p, sp.P.stride, sp.Q.p, sp.Q.stride, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, 0, n);
     else
         launch_sig_miller(sp, f, n, st);
     HIPCHK(hipGetLastError());
@@ -214,16 +195,14 @@ int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host
 // CompareTwoPairings(sig, G2One, h, pub) (g2pubs/bls.go:161)  /  CompareTwoPairings(G1One, sig, pub, h) (g1pubs/bls.go:167, 173)
 // r: the call's route (route.h: verify_route); r.side != none: the signature side's Miller values are on their way into f (verify_sig_side_start)
 int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_sigs, const void* d_inf_in, void* d_ok, i32* f, size_t n, hipStream_t s, const VerifyRoute& r, const PrepKeys* prep = nullptr) {
-    dim3 g(nblocks(n)), w(WG), gp((unsigned)((n + PT - 1) / PT));
+    const unsigned g = nblocks(n), gp = tuple_blocks(Layout::pair, n);
     if (r.side != Side::none) HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[0], 0));       // (also orders the side stream's copy of the signatures before the flag kernel below)
     DBuf gathered;
     if (prep && r.tables) {                       // both pairs read their lines: the generator's table and the key's
         DBuf fl; HIPCHK(fl.alloc(n, s));
-        hipLaunchKernelGGL(k_flag_prepared, g, w, 0, s, prep->tables, prep->idx, (const u8*)d_sigs, 24, (const u8*)d_inf_in, fl.as<u8>(), (int*)nullptr, n);
-        prof_mark("k_miller2_prep_pair");
-        hipLaunchKernelGGL(k_miller2_prep_pair, gp, w, 0, s, (const u8*)d_sigs, d_h, prep->tables, prep->idx, f, n, (const i32*)g_gens.lines_pair);
-        prof_mark("k_final_exp_is_one_pair");
-        hipLaunchKernelGGL(k_final_exp_is_one_pair, gp, w, 0, s, (const i32*)f, (const u8*)fl.as<u8>(), (u8*)d_ok, n);
+        launch_quiet(KERNEL_OF(k_flag_prepared), g, s, prep->tables, prep->idx, d_sigs, 24, d_inf_in, fl.p, nullptr, n);
+        launch(KERNEL_OF(k_miller2_prep_pair), gp, s, d_sigs, d_h, prep->tables, prep->idx, f, n, g_gens.lines_pair);
+        launch(KERNEL_OF(k_final_exp_is_one_pair), gp, s, f, fl.p, d_ok, n);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
@@ -233,7 +212,7 @@ int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_
     // MillerLoop (pairing.go:17-26 vs :54); here the tuple gets verdict 0
     const Kind kk = kind_of(kind);
     DBuf flags; HIPCHK(flags.alloc(n, s));
-    hipLaunchKernelGGL(k_flag_zero_records, g, w, 0, s, (const u8*)d_pks, kk.pk_bytes / 4, (const u8*)d_sigs, kk.sig_bytes / 4, (const u8*)d_inf_in, flags.as<u8>(), (int*)nullptr, n);
+    launch_quiet(KERNEL_OF(k_flag_zero_records), g, s, d_pks, kk.pk_bytes / 4, d_sigs, kk.sig_bytes / 4, d_inf_in, flags.p, nullptr, n);
     const void* d_inf = flags.p;
     const u8* a0 = kind == 0 ? (const u8*)d_sigs : g_gens.g1; const size_t s0 = kind == 0 ? 96 : 0;
     const u8* b0 = kind == 0 ? g_gens.g2 : (const u8*)d_sigs; const size_t t0 = kind == 0 ? 0 : 192;
@@ -242,36 +221,16 @@ int verify_pair_stage(int kind, const u8* d_h, const void* d_pks, const void* d_
     const u8* a1 = kind == 0 ? d_h : (const u8*)d_pks;
     const u8* b1 = kind == 0 ? (const u8*)d_pks : d_h;
     if (r.side == Side::row) {                                             // lane-row layout, the signature side's Miller value already in f: the other pair's loop times it
-        prof_mark("k_miller1m_row");
-        hipLaunchKernelGGL(k_miller1m_row, dim3(rblocks(n)), w, 0, s, a1, (size_t)96, b1, (size_t)192, f, n);
-        prof_mark("k_final_exp_is_one_row");
-        hipLaunchKernelGGL(k_final_exp_is_one_row, dim3(rblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
+        launch(KERNEL_OF(k_miller1m_row), tuple_blocks(Layout::row, n), s, a1, 96, b1, 192, f, n);
+        launch(KERNEL_OF(k_final_exp_is_one_row), tuple_blocks(Layout::row, n), s, f, d_inf, d_ok, n);
     } else if (r.side == Side::wave) {                                     // small call, the signature side already under way: one Miller loop, the product, the final exponentiation
-        prof_mark("k_lat:verify1s");
-        launch_lat(LAT_VERIFY1S_OFFSET, s, {.b0 = {a1, 96}, .b1 = {b1, 192}, .b3 = lat_count(n, f), .flags = d_inf, .ok = d_ok}, n);   // b3: the n Miller values of the side stream
+        launch_lat_marked(LAT_VERIFY1S_OFFSET, s, {.b0 = {a1, 96}, .b1 = {b1, 192}, .b3 = lat_count(n, f), .flags = d_inf, .ok = d_ok}, n);   // b3: the n Miller values of the side stream
     } else if (r.layout == Layout::wave) {                                 // small call: one Verify per wave (k_lat.hip)
-        prof_mark("k_lat:verify2");
-        launch_lat(LAT_VERIFY2_OFFSET, s, {.b0 = {a0, s0}, .b1 = {b0, t0}, .b2 = {a1, 96}, .b3 = {b1, 192}, .flags = d_inf, .ok = d_ok}, n);
-    } else if (r.layout == Layout::row) {                                  // a few thousand tuples: sixteen lanes per tuple (k_pairing_row.hip)
-        prof_mark("k_miller2_row");
-        hipLaunchKernelGGL(k_miller2_row, dim3(rblocks(n)), w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
-        prof_mark("k_final_exp_is_one_row");
-        hipLaunchKernelGGL(k_final_exp_is_one_row, dim3(rblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else if (r.layout == Layout::quad) {                                 // mid-size batch: four lanes per tuple (k_pairing_quad.hip)
-        prof_mark("k_miller2_quad");
-        hipLaunchKernelGGL(k_miller2_quad, dim3(qblocks(n)), w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
-        prof_mark("k_final_exp_is_one_quad");
-        hipLaunchKernelGGL(k_final_exp_is_one_quad, dim3(qblocks(n)), w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else if (r.layout == Layout::pair) {
-        prof_mark("k_miller2_pair");
-        hipLaunchKernelGGL(k_miller2_pair, gp, w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre_pair);
-        prof_mark("k_final_exp_is_one_pair");
-        hipLaunchKernelGGL(k_final_exp_is_one_pair, gp, w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
-    } else {
-        prof_mark("k_miller2");
-        hipLaunchKernelGGL(k_miller2, g, w, 0, s, a0, s0, b0, t0, a1, (size_t)96, b1, (size_t)192, f, n, pre);
-        prof_mark("k_final_exp_is_one");
-        hipLaunchKernelGGL(k_final_exp_is_one, g, w, 0, s, (const i32*)f, (const u8*)d_inf, (u8*)d_ok, n);
+        launch_lat_marked(LAT_VERIFY2_OFFSET, s, {.b0 = {a0, s0}, .b1 = {b0, t0}, .b2 = {a1, 96}, .b3 = {b1, 192}, .flags = d_inf, .ok = d_ok}, n);
+    } else {   // row: a few thousand tuples, sixteen lanes each (k_pairing_row.hip); quad: a mid-size batch, four lanes each (k_pairing_quad.hip); pair, single
+        const Layout l = r.layout;
+        launch(kernels_of(l).miller2, tuple_blocks(l, n), s, a0, s0, b0, t0, a1, 96, b1, 192, f, n, l == Layout::single ? pre : pre_pair);
+        launch(kernels_of(l).final_exp_is_one, tuple_blocks(l, n), s, f, d_inf, d_ok, n);
     }
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
@@ -353,7 +312,7 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
     const PrepKeys prep{prep_tables, prep_idx ? dp.as<u32>() : nullptr};
     rc = verify_pair_stage(kind, h.as<u8>(), prep_tables ? nullptr : dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, g_stream, r, prep_tables ? &prep : nullptr);
     if (rc) return rc;
-    if (d_bitmap_slice) hipLaunchKernelGGL(k_pack_bitmap, dim3(nblocks((n + 7) / 8)), dim3(WG), 0, g_stream, (const u8*)dok.as<u8>(), d_bitmap_slice, n);
+    if (d_bitmap_slice) launch_quiet(KERNEL_OF(k_pack_bitmap), nblocks((n + 7) / 8), g_stream, dok.p, d_bitmap_slice, n);
     return fetch_verdicts(dok.p, ok, ok_bitmap, n, g_stream);
 }
 
@@ -696,8 +655,8 @@ int aggregate_shard_dev(int kind, const void* d_msgs, const void* d_off_or_domai
     int rc = hash_dev(kind, d_msgs, d_off_or_domain, h.as<u8>(), n, s, r.hash, g1_clear, g1_clear ? nullptr : any.as<int>());   // *bad bit 1: a hash point the uncleared path does not cover
     if (rc) return rc;
     if (after_hash) { rc = after_hash(); if (rc) return rc; }
-    if (prep) hipLaunchKernelGGL(k_flag_prepared, dim3(nblocks(n)), dim3(WG), 0, s, prep->tables, prep->idx, (const u8*)nullptr, 0, (const u8*)nullptr, flags.as<u8>(), any.as<int>(), n);
-    else hipLaunchKernelGGL(k_flag_zero_records, dim3(nblocks(n)), dim3(WG), 0, s, d_pks, k.pk_bytes / 4, (const u8*)nullptr, 0, (const u8*)nullptr, flags.as<u8>(), any.as<int>(), n);
+    if (prep) launch_quiet(KERNEL_OF(k_flag_prepared), nblocks(n), s, prep->tables, prep->idx, nullptr, 0, nullptr, flags.p, any.p, n);
+    else launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(n), s, d_pks, k.pk_bytes / 4, nullptr, 0, nullptr, flags.p, any.p, n);
     // Pairing(h_i, pk_i) (g2pubs) / Pairing(pk_i, h_i) (g1pubs): Miller loops only, then the product tree
     launch_miller1(kind == 0 ? h.as<u8>() : d_pks, kind == 0 ? d_pks : h.as<u8>(), fr0.as<i32>(), n, s, r, prep);
     const i32* src = prod_tree(fr0.as<i32>(), nrec, fr1.as<i32>(), fr0.as<i32>(), s);
@@ -731,8 +690,7 @@ constexpr size_t AGG_POW_MIN = 65536;
 inline bool agg_pow_wanted(int kind, size_t n, const Tuning& t) { return kind == 0 && n >= AGG_POW_MIN && t.lat_max != 0 && t.agg_cofactor_pow; }
 // d_prod (180 words, device representation) -> d_out = d_prod^(1 - x), on g_stream
 int aggregate_pow_c(const i32* d_prod, i32* d_out) {
-    prof_mark("k_lat:powc12raw");
-    launch_lat(LAT_POWC12RAW_OFFSET, g_stream, {.b3 = {d_prod, 0}, .out = d_out}, 1);
+    launch_lat_marked(LAT_POWC12RAW_OFFSET, g_stream, {.b3 = {d_prod, 0}, .out = d_out}, 1);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
@@ -760,11 +718,10 @@ int tuple_side_product(bool powc, DBuf& prod, int* bad, const Run& run) {
     return rc;
 }
 // one wave of a tail program ("aggtail", "aggtail2") on g_stream and its verdict byte fetched into *ok; synchronises.  a: all operands but ok
-int tail_verdict(size_t prog, const char* mark, LatArgs a, int* ok) {
+int tail_verdict(size_t prog, LatArgs a, int* ok) {
     DBuf dokb; HIPCHK(dokb.alloc(1));
     a.ok = dokb.p;
-    prof_mark(mark);
-    launch_lat(prog, g_stream, a, 1);
+    launch_lat_marked(prog, g_stream, a, 1);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     uint8_t flag = 0;
@@ -781,7 +738,7 @@ int aggregate_tail(int kind, const i32* d_prod, const uint8_t* sig, int* ok, int
     DBuf dsig; HIPCHK(dsig.alloc(k.sig_bytes));
     { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
     const SigPair sp = sig_pair(kind, dsig.p, 0);
-    return tail_verdict(LAT_AGGTAIL_OFFSET, "k_lat:aggtail", {.b0 = sp.P, .b1 = sp.Q, .b3 = {d_prod, 0}}, ok);
+    return tail_verdict(LAT_AGGTAIL_OFFSET, {.b0 = sp.P, .b1 = sp.Q, .b3 = {d_prod, 0}}, ok);
 }
 // The same tail in two pieces for calls that run on ONE context: the signature side's Miller loop does not depend on the tuple side, so it
 // starts on a side stream BEFORE the messages are hashed (sig_side_start: program "miller1rawn", one wave, ~0.7 ms, hidden behind the
@@ -801,7 +758,7 @@ int sig_side_start(int kind, const uint8_t* sig, SigSide& ss, int fmt = 0) {
 }
 int aggregate_tail(const i32* d_prod, const SigSide& ss, int* ok) {
     HIPCHK(hipStreamWaitEvent(g_stream, tl_ctx->join[0], 0));
-    return tail_verdict(LAT_AGGTAIL2_OFFSET, "k_lat:aggtail2", {.b2 = {ss.ml.p, 0}, .b3 = {d_prod, 0}}, ok);
+    return tail_verdict(LAT_AGGTAIL2_OFFSET, {.b2 = {ss.ml.p, 0}, .b3 = {d_prod, 0}}, ok);
 }
 inline bool sig_is_infinity(int kind, const uint8_t* sig, int fmt) {       // the reference panics in MillerLoop: verdict 0
     const Kind k = kind_of(kind);
@@ -843,7 +800,7 @@ int verify_aggregate_on_ctx(int kind, AggInputs in, const uint8_t* sig, size_t n
     DBuf prod, ddup; HIPCHK(prod.alloc(sizeof(i32) * 12 * NL)); HIPCHK(ddup.alloc(sizeof(int)));
     SigSide ss;
     { int rc = sig_side_start(kind, sig, ss, fmt); if (rc) return rc; }
-    if (n == 0) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_stream, prod.as<i32>());
+    if (n == 0) launch_quiet(KERNEL_OF(k_fq12_one), 1, g_stream, prod.p);
     else {
         bool first = true;
         int bad = 0;
@@ -917,7 +874,7 @@ int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
     if (rc) return rc;
     for (int d = 0; d < g_ndev; d++) {                                       // slots start as 1 (a shard with no tuples contributes nothing)
         HIPCHK(hipSetDevice(g_dev[d].id));
-        for (int sl = 0; sl < S; sl++) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_dev[d].coll_stream, reinterpret_cast<i32*>(g_dev[d].coll.p) + words * sl);
+        for (int sl = 0; sl < S; sl++) launch_quiet(KERNEL_OF(k_fq12_one), 1, g_dev[d].coll_stream, reinterpret_cast<i32*>(g_dev[d].coll.p) + words * sl);
     }
     rc = coll_sync_all();
     if (rc) return rc;
@@ -978,7 +935,7 @@ int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
     CtxLease lease(0);
     if (lease.rc) return lease.rc;
     i32* soa = lhs + words; i32* scratch = soa + words * total;
-    hipLaunchKernelGGL(k_fq12_aos_to_soa, dim3(nblocks(words * cnt)), dim3(WG), 0, g_stream, gathered, soa, cnt);
+    launch_quiet(KERNEL_OF(k_fq12_aos_to_soa), nblocks(words * cnt), g_stream, gathered, soa, cnt);
     const i32* src = prod_tree(soa, cnt, scratch, soa, g_stream);
     if (powc) { i32* dst = src == soa ? scratch : soa; int rc2 = aggregate_pow_c(src, dst); if (rc2) return rc2; src = dst; }   // (dst: the tree's other buffer, free now)
     return aggregate_tail(kind, src, sig, ok, fmt);
@@ -1010,8 +967,8 @@ int verify_aggregate_common_host(int kind, const uint8_t* msg, size_t msg_len, c
     }
     uint8_t agg[192]; int agg_inf = 0;
     int rc;
-    if (fmt & FMT_PK_JAC) rc = (k.pk_bytes == 192) ? sum_host<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, pks, nullptr, n, agg, &agg_inf, true)
-                                                   : sum_host<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, pks, nullptr, n, agg, &agg_inf, true);
+    if (fmt & FMT_PK_JAC) rc = (k.pk_bytes == 192) ? sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pks, nullptr, n, agg, &agg_inf, true)
+                                                   : sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pks, nullptr, n, agg, &agg_inf, true);
     else rc = (k.pk_bytes == 192) ? blsmi_g2_sum(pks, nullptr, n, agg, &agg_inf) : blsmi_g1_sum(pks, nullptr, n, agg, &agg_inf);
     if (rc) return rc;
     uint8_t flags = agg_inf ? 1 : 0, res = 0;
@@ -1037,10 +994,10 @@ int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uin
     if (n == 0) {                                                          // the empty sum is the point at infinity (g2pubs/bls.go:181)
         HIPCHK(hipMemsetAsync(dagg.p, 0, k.pk_bytes, side)); HIPCHK(hipMemsetAsync(dinf.p, 1, 1, side));
     } else {
-        int rc = k.pk_bytes == 192 ? sum_dev<192, 6>(k_g2_sum0, k_g2_sum, k_g2_sum_final, (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj)
-                                   : sum_dev<96, 3>(k_g1_sum0, k_g1_sum, k_g1_sum_final, (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj);
+        int rc = k.pk_bytes == 192 ? sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj)
+                                   : sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_flag_to_byte, dim3(1), dim3(WG), 0, side, (const i32*)dflag.as<i32>(), dinf.as<u8>());
+        launch_quiet(KERNEL_OF(k_flag_to_byte), 1, side, dflag.p, dinf.p);
     }
     HIPCHK(hipEventRecord(tl_ctx->join[1], side));
     uint64_t off[2] = {0, (uint64_t)msg_len};
@@ -1073,23 +1030,21 @@ int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, uin
 // n compressed points -> affine records, infinity flags, error codes (g1.go:185-249, g2.go:219-295), on stream s.
 // group 1 / 2 = G1 / G2.  Small batches take the subgroup test (check == 1) as a level program of the latency path.
 int decompress_dev(int group, const u8* d_in, int check, u8* d_out, u8* d_inf, u8* d_err, size_t n, hipStream_t s) {
-    dim3 g(nblocks(n)), w(WG);
+    const unsigned g = nblocks(n);
     const bool lat = check == 1 && n <= tune().lat_max;
     const int kcheck = lat ? 0 : check;
     const size_t wave_max = tune().swu_wave_max;
     const bool waves = kcheck == 0 && n <= wave_max;                       // the smallest calls: one wave per point, its square root with one limb per lane (fp_row.cuh)
-    prof_mark(group == 1 ? (waves ? "k_g1_decompress_waves" : "k_g1_decompress") : (waves ? "k_g2_decompress_waves" : "k_g2_decompress"));
-    if (waves && group == 1) hipLaunchKernelGGL(k_g1_decompress_waves, dim3((unsigned)n), dim3(64), 0, s, d_in, d_out, d_inf, d_err, n);
-    else if (waves) hipLaunchKernelGGL(k_g2_decompress_waves, dim3((unsigned)n), dim3(64), 0, s, d_in, d_out, d_inf, d_err, n);
-    else if (group == 1) hipLaunchKernelGGL(k_g1_decompress, g, w, 0, s, d_in, kcheck, d_out, d_inf, d_err, n);
-    else hipLaunchKernelGGL(k_g2_decompress, g, w, 0, s, d_in, kcheck, d_out, d_inf, d_err, n);
+    if (waves && group == 1) launch_sized(KERNEL_OF(k_g1_decompress_waves), n, 64, s, d_in, d_out, d_inf, d_err, n);
+    else if (waves) launch_sized(KERNEL_OF(k_g2_decompress_waves), n, 64, s, d_in, d_out, d_inf, d_err, n);
+    else if (group == 1) launch(KERNEL_OF(k_g1_decompress), g, s, d_in, kcheck, d_out, d_inf, d_err, n);
+    else launch(KERNEL_OF(k_g2_decompress), g, s, d_in, kcheck, d_out, d_inf, d_err, n);
     if (lat) {
         const size_t rec = group == 1 ? 96 : 192;
         const size_t prog = group == 1 ? LAT_SUBGRP1_OFFSET : LAT_SUBGRP2_OFFSET;
         DBuf sub; HIPCHK(sub.alloc(n, s));
-        prof_mark(group == 1 ? "k_lat:subgrp1" : "k_lat:subgrp2");
-        launch_lat(prog, s, {.b0 = {d_out, rec}, .ok = sub.p}, n);
-        hipLaunchKernelGGL(k_apply_subgroup, g, w, 0, s, (const u8*)sub.as<u8>(), d_out, (int)(rec / 4), (const u8*)d_inf, d_err, n);
+        launch_lat_marked(prog, s, {.b0 = {d_out, rec}, .ok = sub.p}, n);
+        launch_quiet(KERNEL_OF(k_apply_subgroup), g, s, sub.p, d_out, (int)(rec / 4), d_inf, d_err, n);
     }
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
@@ -1128,7 +1083,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     { int rc = dm.upload(msgs, off, g_stream); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(dpc.p, pks, pkc * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dsc.p, sigs, sgc * n, hipMemcpyHostToDevice, g_stream));
-    dim3 g(nblocks(n)), w(WG);
+    const unsigned g = nblocks(n);
     // The two decompressions and the hash are independent, each a serial chain per lane: for a small call they go to three
     // streams (fork after the input copies, join before the pairing stage) -- 8.7 -> ~5 ms for one tuple.  So do batches up to
     // 131 072 tuples: their one-lane kernels put one or two waves on a SIMD and the kernels with 256 registers a lane share it
@@ -1158,7 +1113,7 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
         HIPCHK(hipEventRecord(tl_ctx->join[0], spk)); HIPCHK(hipEventRecord(tl_ctx->join[1], ssg));
         HIPCHK(hipStreamWaitEvent(g_stream, tl_ctx->join[0], 0)); HIPCHK(hipStreamWaitEvent(g_stream, tl_ctx->join[1], 0));
     }
-    hipLaunchKernelGGL(k_merge_flags, g, w, 0, g_stream, ipk.as<u8>(), epk.as<u8>(), isg.as<u8>(), esg.as<u8>(), dfl.as<u8>(), n);
+    launch_quiet(KERNEL_OF(k_merge_flags), g, g_stream, ipk.p, epk.p, isg.p, esg.p, dfl.p, n);
     HIPCHK(hipGetLastError());
     rc = verify_pair_stage(kind, h.as<u8>(), dp.p, ds.p, dfl.p, dok.p, f.as<i32>(), n, g_stream, r);
     if (rc) return rc;
@@ -1177,7 +1132,7 @@ int compress_host(K kernel, const uint8_t* pts, const uint8_t* in_inf, uint8_t* 
     HIPCHK(di.alloc((size_t)IB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(dout.alloc((size_t)OB * n));
     HIPCHK(hipMemcpyAsync(di.p, pts, (size_t)IB * n, hipMemcpyHostToDevice, g_stream));
     if (in_inf) HIPCHK(hipMemcpyAsync(dinf.p, in_inf, n, hipMemcpyHostToDevice, g_stream));
-    hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(WG), 0, g_stream, di.as<u8>(), in_inf ? dinf.as<u8>() : (const u8*)nullptr, dout.as<u8>(), n);
+    launch_quiet(kernel, nblocks(n), g_stream, di.p, in_inf ? dinf.p : nullptr, dout.p, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1194,14 +1149,14 @@ static int aggregate_partial_host(int kind, const uint8_t* msgs, const uint64_t*
     const size_t words = (size_t)12 * NL;
     DBuf dout, f; HIPCHK(dout.alloc(576)); HIPCHK(f.alloc(sizeof(i32) * words));
     int b = 0;
-    if (n == 0) hipLaunchKernelGGL(k_fq12_one, dim3(1), dim3(WG), 0, g_stream, f.as<i32>());
+    if (n == 0) launch_quiet(KERNEL_OF(k_fq12_one), 1, g_stream, f.p);
     else {
         // a large g2pubs shard pairs the hash points before their cofactor clearing and raises ITS product to 1 - x (agg_pow_wanted): the
         // value differs from prod ML(H(m_i), pk_i) only by what the final exponentiation removes, which is all a partial product is used for
         int rc = tuple_side_product(agg_pow_wanted(kind, n, tune()), f, &b, [&](bool g1_clear, int* bad) { return aggregate_shard(kind, msgs, off_or_domain, pks, n, f.as<i32>(), bad, g1_clear); });
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_final_exp, dim3(1), dim3(WG), 0, g_stream, (const i32*)f.as<i32>(), dout.as<u64>(), (size_t)1, 1);   // mode 1: format conversion only
+    launch_quiet(KERNEL_OF(k_final_exp), 1, g_stream, f.p, dout.p, 1, 1);   // mode 1: format conversion only
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out72, dout.p, 576, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1218,9 +1173,9 @@ BLSMI_API int blsmi_fq12_product(const uint64_t* in, size_t n, uint64_t* out72) 
     DBuf di, fr0, fr1, dout;
     HIPCHK(di.alloc(576 * n)); HIPCHK(fr0.alloc(sizeof(i32) * words * n)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((n + 1) / 2))); HIPCHK(dout.alloc(576));
     HIPCHK(hipMemcpyAsync(di.p, in, 576 * n, hipMemcpyHostToDevice, g_stream));
-    hipLaunchKernelGGL(k_fq12_from_m384, dim3(nblocks(n)), dim3(WG), 0, g_stream, di.as<u64>(), fr0.as<i32>(), n);
+    launch_quiet(KERNEL_OF(k_fq12_from_m384), nblocks(n), g_stream, di.p, fr0.p, n);
     const i32* src = prod_tree(fr0.as<i32>(), n, fr1.as<i32>(), fr0.as<i32>(), g_stream);
-    hipLaunchKernelGGL(k_final_exp, dim3(1), dim3(WG), 0, g_stream, (const i32*)src, dout.as<u64>(), (size_t)1, 1);
+    launch_quiet(KERNEL_OF(k_final_exp), 1, g_stream, src, dout.p, 1, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out72, dout.p, 576, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1259,8 +1214,8 @@ BLSMI_API int blsmi_debug_hash_g1_finish(const uint8_t* pts, int clear, uint8_t*
     HIPCHK(hipMemsetAsync(dsp.p, 0, sizeof(int), g_stream));
     if (clear == 2) {                                                       // the four-lanes-per-message tail and its redo pass (k_hash_quad.hip)
         DBuf dg; HIPCHK(dg.alloc(n));
-        hipLaunchKernelGGL(k_hash_g1_finish_quad, dim3(qblocks(n)), dim3(WG), 0, g_stream, (const u8*)dp.as<u8>(), dg.as<u8>(), dout.as<u8>(), n);
-        hipLaunchKernelGGL(k_hash_g1_finish_redo, dim3(nblocks(n)), dim3(WG), 0, g_stream, (const u8*)dp.as<u8>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
+        launch_quiet(KERNEL_OF(k_hash_g1_finish_quad), tuple_blocks(Layout::quad, n), g_stream, dp.p, dg.p, dout.p, n);
+        launch_quiet(KERNEL_OF(k_hash_g1_finish_redo), nblocks(n), g_stream, dp.p, dg.p, dout.p, n);
         HIPCHK(hipGetLastError());
         std::vector<u8> hg(n);
         HIPCHK(hipMemcpyAsync(hg.data(), dg.p, n, hipMemcpyDeviceToHost, g_stream));
@@ -1269,7 +1224,7 @@ BLSMI_API int blsmi_debug_hash_g1_finish(const uint8_t* pts, int clear, uint8_t*
         *special = (int)std::count(hg.begin(), hg.end(), (u8)0);             // clear == 2: how many messages the quad kernel handed to the redo pass
         return BLSMI_OK;
     }
-    hipLaunchKernelGGL(k_hash_g1_finish, dim3(nblocks(n)), dim3(WG), 0, g_stream, (const u8*)dp.as<u8>(), dout.as<u8>(), n, clear, dsp.as<int>());
+    launch_quiet(KERNEL_OF(k_hash_g1_finish), nblocks(n), g_stream, dp.p, dout.p, n, clear, dsp.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, 96 * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(special, dsp.p, sizeof(int), hipMemcpyDeviceToHost, g_stream));
@@ -1287,10 +1242,10 @@ BLSMI_API int blsmi_debug_hash_redo(int kind, const uint8_t* msgs, const uint64_
     { int rc = dm.upload(msgs, off_or_domain, g_stream); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(dout.p, out, hb * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dg.p, good, n, hipMemcpyHostToDevice, g_stream));
-    dim3 g(nblocks(n)), w(WG);
-    if (kind == 0) hipLaunchKernelGGL(k_hash_g1_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
-    else if (kind == 1) hipLaunchKernelGGL(k_hash_g2_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u64>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
-    else hipLaunchKernelGGL(k_hash_g2_domain_redo, g, w, 0, g_stream, dm.m.as<u8>(), dm.off.as<u8>(), (const u8*)dg.as<u8>(), dout.as<u8>(), n);
+    const unsigned g = nblocks(n);
+    if (kind == 0) launch_quiet(KERNEL_OF(k_hash_g1_redo), g, g_stream, dm.m.p, dm.off.p, dg.p, dout.p, n);
+    else if (kind == 1) launch_quiet(KERNEL_OF(k_hash_g2_redo), g, g_stream, dm.m.p, dm.off.p, dg.p, dout.p, n);
+    else launch_quiet(KERNEL_OF(k_hash_g2_domain_redo), g, g_stream, dm.m.p, dm.off.p, dg.p, dout.p, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, hb * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1337,13 +1292,13 @@ int sign_host(int kind, const uint8_t* msgs, const void* off_or_domain, size_t o
         int rc = hash_dev(kind, dm.p, doff.p, dh.as<u8>(), m, g_stream, hash_route_alone(kind, m));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(dk.p, sks + 32 * lo, 32 * m, hipMemcpyHostToDevice, g_stream));   // the keys travel while the hash runs
-        if (OB == 96) rc = mul_dev_core<96>(k_g1_mul, dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
-        else rc = mul_dev_core<192>(k_g2_mul, dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
+        if (OB == 96) rc = mul_dev_core<96>(KERNEL_OF(k_g1_mul), dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
+        else rc = mul_dev_core<192>(KERNEL_OF(k_g2_mul), dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
         if (rc) return rc;
         if (out_jac) {
             const size_t jb = rec_bytes(OB, true);
             DBuf dj; HIPCHK(dj.alloc(jb * m));
-            hipLaunchKernelGGL(k_affine_to_jac, dim3(nblocks(m)), dim3(WG), 0, g_stream, (const u8*)dout.as<u8>(), (const void*)dinf.p, 1, OB == 96 ? 1 : 2, dj.as<u64>(), m);
+            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, OB == 96 ? 1 : 2, dj.p, m);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(out_jac) + jb * lo, dj.p, jb * m, hipMemcpyDeviceToHost, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));
@@ -1445,8 +1400,7 @@ BLSMI_API int blsmi_g2_prepare_batch_dev(const void* d_g2_aff, size_t n, void* d
     if (!d_g2_aff || !d_prepared) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_prepared);
     UseStream us(stream);
-    prof_mark("k_g2_prepare_pair");
-    hipLaunchKernelGGL(k_g2_prepare_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, g_stream, (const u8*)d_g2_aff, (i32*)d_prepared, n);
+    launch(KERNEL_OF(k_g2_prepare_pair), tuple_blocks(Layout::pair, n), g_stream, d_g2_aff, d_prepared, n);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1457,7 +1411,7 @@ BLSMI_API int blsmi_g2_prepared_export_dev(const void* d_prepared, size_t n, voi
     if (!d_prepared || !d_out) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
-    hipLaunchKernelGGL(k_prepared_export, dim3(nblocks(408 * n)), dim3(WG), 0, g_stream, (const i32*)d_prepared, (u64*)d_out, n);
+    launch_quiet(KERNEL_OF(k_prepared_export), nblocks(408 * n), g_stream, d_prepared, d_out, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
@@ -1473,10 +1427,9 @@ BLSMI_API int blsmi_g2_prepare_batch(const uint8_t* g2_aff, size_t n, uint64_t* 
         DBuf q, tab, o;
         HIPCHK(q.alloc(192 * m)); HIPCHK(tab.alloc(sizeof(i32) * blsmi_prep::WORDS * m)); HIPCHK(o.alloc(sizeof(u64) * 68 * 3 * 12 * m));
         HIPCHK(hipMemcpyAsync(q.p, g2_aff + 192 * lo, 192 * m, hipMemcpyHostToDevice, g_stream));
-        prof_mark("k_g2_prepare_pair");
-        hipLaunchKernelGGL(k_g2_prepare_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, g_stream, q.as<u8>(), tab.as<i32>(), m);
+        launch(KERNEL_OF(k_g2_prepare_pair), tuple_blocks(Layout::pair, m), g_stream, q.p, tab.p, m);
         prof_mark(nullptr);
-        hipLaunchKernelGGL(k_prepared_export, dim3(nblocks(408 * m)), dim3(WG), 0, g_stream, (const i32*)tab.as<i32>(), o.as<u64>(), m);
+        launch_quiet(KERNEL_OF(k_prepared_export), nblocks(408 * m), g_stream, tab.p, o.p, m);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out_coeffs + (size_t)68 * 3 * 12 * lo, o.p, sizeof(u64) * 68 * 3 * 12 * m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
@@ -1498,8 +1451,7 @@ static int g2_prepared_create(const uint8_t* g2, bool jac, size_t n, void** hand
     int rc = code(q.alloc(192 * n));
     if (!rc) rc = jac ? upload_points(192, true, g2, q.p, n, g_stream) : code(hipMemcpyAsync(q.p, g2, 192 * n, hipMemcpyHostToDevice, g_stream));
     if (!rc) {
-        prof_mark("k_g2_prepare_pair");
-        hipLaunchKernelGGL(k_g2_prepare_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, g_stream, q.as<u8>(), (i32*)tab, n);
+        launch(KERNEL_OF(k_g2_prepare_pair), tuple_blocks(Layout::pair, n), g_stream, q.p, tab, n);
         prof_mark(nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
@@ -1542,10 +1494,8 @@ BLSMI_API int blsmi_pairing_batch_prepared_dev(const void* d_g1, const void* d_p
     HIPCHK(g_ws.reserve(sizeof(i32) * 12 * NL * n));
     i32* f = reinterpret_cast<i32*>(g_ws.p);
     const unsigned pblocks = (unsigned)((n + PT - 1) / PT);
-    prof_mark("k_miller1_prep_pair");
-    hipLaunchKernelGGL(k_miller1_prep_pair, dim3(pblocks), dim3(WG), 0, g_stream, (const u8*)d_g1, prep.tables, prep.idx, f, n);
-    prof_mark("k_final_exp_pair");
-    hipLaunchKernelGGL(k_final_exp_pair, dim3(pblocks), dim3(WG), 0, g_stream, (const i32*)f, (u64*)d_out, n, 0);
+    launch(KERNEL_OF(k_miller1_prep_pair), pblocks, g_stream, d_g1, prep.tables, prep.idx, f, n);
+    launch(KERNEL_OF(k_final_exp_pair), pblocks, g_stream, f, d_out, n, 0);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1625,8 +1575,8 @@ BLSMI_API int blsmi_g1pubs_verify_serialized_batch(const uint8_t* msgs, const ui
 }
 BLSMI_API int blsmi_g1_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host<48, 96>(1, in, check, out, out_inf, err, n); }
 BLSMI_API int blsmi_g2_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host<96, 192>(2, in, check, out, out_inf, err, n); }
-BLSMI_API int blsmi_g1_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<96, 48>(k_g1_compress, pts, in_inf, out, n); }
-BLSMI_API int blsmi_g2_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<192, 96>(k_g2_compress, pts, in_inf, out, n); }
+BLSMI_API int blsmi_g1_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<96, 48>(KERNEL_OF(k_g1_compress), pts, in_inf, out, n); }
+BLSMI_API int blsmi_g2_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<192, 96>(KERNEL_OF(k_g2_compress), pts, in_inf, out, n); }
 
 // ---- the verify surface over the reference's in-memory points (blsmi 0.6; include/blsmi.h "in-memory points") ---------------------------
 // Keys and signatures as the Go values hold them: bls.G2Projective = 36 x u64, bls.G1Projective = 18 x u64 (x, y, z; FQ = 6 LE u64 Montgomery
@@ -1787,25 +1737,25 @@ int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_
     if (n1 && d_scalars) {
         if (jac) return BLSMI_E_ARG;
         const bool mark = tl_ctx && s == tl_ctx->stream;                   // (profile marks are events on the context's main stream)
-        if (mark) prof_mark(group == 1 ? "k_g1_segsum_chunk_u64" : "k_g2_segsum_chunk_u64");
-        if (group == 1) hipLaunchKernelGGL(k_g1_segsum_chunk_u64, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
-        else hipLaunchKernelGGL(k_g2_segsum_chunk_u64, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        const auto k = group == 1 ? KERNEL_OF(k_g1_segsum_chunk_u64) : KERNEL_OF(k_g2_segsum_chunk_u64);
+        if (mark) prof_mark(k.name);
+        launch_quiet(k, nblocks(n1), s, d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
         if (mark) prof_mark(nullptr);
     } else if (n1) {
-        if (group == 1 && jac) hipLaunchKernelGGL(k_g1_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
-        else if (group == 1) hipLaunchKernelGGL(k_g1_segsum_chunk, dim3(nblocks(n1)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
-        else if (jac) hipLaunchKernelGGL(k_g2_segsum_chunk_jac, dim3(nblocks(n1)), dim3(WG), 0, s, (const u64*)d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
-        else hipLaunchKernelGGL(k_g2_segsum_chunk_pair, dim3((unsigned)((n1 + PT - 1) / PT)), dim3(WG), 0, s, (const u8*)d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.as<u8>(), a.as<i32>(), n1);
+        if (group == 1 && jac) launch_quiet(KERNEL_OF(k_g1_segsum_chunk_jac), nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        else if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_chunk), nblocks(n1), s, d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        else if (jac) launch_quiet(KERNEL_OF(k_g2_segsum_chunk_jac), nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        else launch_quiet(KERNEL_OF(k_g2_segsum_chunk_pair), tuple_blocks(Layout::pair, n1), s, d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
     }
     i32* src = a.as<i32>();
     for (const SegPlan::Fold& f : p.folds) {
         DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * f.nch));
-        if (group == 1) hipLaunchKernelGGL(k_g1_segsum_fold, dim3(nblocks(f.nch)), dim3(WG), 0, s, (const i32*)src, f.nsrc, at64(f.lo), at32(f.cnt), d.as<i32>(), f.nch);
-        else hipLaunchKernelGGL(k_g2_segsum_fold_pair, dim3((unsigned)((f.nch + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)src, f.nsrc, at64(f.lo), at32(f.cnt), d.as<i32>(), f.nch);
+        if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_fold), nblocks(f.nch), s, src, f.nsrc, at64(f.lo), at32(f.cnt), d.p, f.nch);
+        else launch_quiet(KERNEL_OF(k_g2_segsum_fold_pair), tuple_blocks(Layout::pair, f.nch), s, src, f.nsrc, at64(f.lo), at32(f.cnt), d.p, f.nch);
         src = d.as<i32>();
     }
-    if (group == 1) hipLaunchKernelGGL(k_g1_segsum_final, dim3((unsigned)m), dim3(WG), 0, s, (const i32*)src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), (const u8*)bad.as<u8>(), bad_code, d_out, d_out_inf);
-    else hipLaunchKernelGGL(k_g2_segsum_final, dim3((unsigned)m), dim3(WG), 0, s, (const i32*)src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), (const u8*)bad.as<u8>(), bad_code, d_out, d_out_inf);
+    if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_final), m, s, src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), bad.p, bad_code, d_out, d_out_inf);
+    else launch_quiet(KERNEL_OF(k_g2_segsum_final), m, s, src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), bad.p, bad_code, d_out, d_out_inf);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
@@ -2001,13 +1951,8 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_dev(const v
 namespace {
 // one Miller value per tuple into the hand-off buffer f, the tuples free of points at infinity
 void launch_miller_tuples(const u8* d_g1, const u8* d_g2, i32* f, size_t n, hipStream_t s, Layout l) {
-    prof_mark(l == Layout::wave ? "k_lat:miller1raw" : l == Layout::row ? "k_miller1h_row" : l == Layout::quad ? "k_miller1h_quad" : l == Layout::pair ? "k_miller1h_pair" : "k_miller1h");
-    if (l == Layout::wave)
-        launch_lat(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
-    else if (l == Layout::row) hipLaunchKernelGGL(k_miller1h_row, dim3(rblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
-    else if (l == Layout::quad) hipLaunchKernelGGL(k_miller1h_quad, dim3(qblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
-    else if (l == Layout::pair) hipLaunchKernelGGL(k_miller1h_pair, dim3((unsigned)((n + PT - 1) / PT)), dim3(WG), 0, s, d_g1, d_g2, f, n);
-    else hipLaunchKernelGGL(k_miller1h, dim3(nblocks(n)), dim3(WG), 0, s, d_g1, d_g2, f, n);
+    if (l == Layout::wave) launch_lat_marked(LAT_MILLER1RAW_OFFSET, s, {.b0 = {d_g1, 96}, .b1 = {d_g2, 192}, .out = f}, n);
+    else launch(kernels_of(l).miller1h, tuple_blocks(l, n), s, d_g1, d_g2, f, n);
 }
 void pprod_plan(const uint64_t* seg_off, size_t m, SegPlan& plan) {
     const size_t K = segsum_chunk_of(seg_off[m]);
@@ -2027,30 +1972,24 @@ int seg_prod_dev(const i32* src, size_t nsrc, const u8* skip, const SegPlan& pla
     auto at32 = [&](size_t off) { return reinterpret_cast<const u32*>(d_blob + off); };
     if (plan.nch1) {
         DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * plan.nch1));
-        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.nch1)), dim3(WG), 0, s, src, nsrc, skip, at64(plan.ch_lo), at32(plan.ch_cnt), d.as<i32>(), (u64*)nullptr, plan.nch1);
+        launch_quiet(KERNEL_OF(k_fq12_seg_prod_row), tuple_blocks(Layout::row, plan.nch1), s, src, nsrc, skip, at64(plan.ch_lo), at32(plan.ch_cnt), d.p, nullptr, plan.nch1);
         src = d.as<i32>(); nsrc = plan.nch1;
     }
     for (const SegPlan::Fold& fo : plan.folds) {
         DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * fo.nch));
-        hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(fo.nch)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(fo.lo), at32(fo.cnt), d.as<i32>(), (u64*)nullptr, fo.nch);
+        launch_quiet(KERNEL_OF(k_fq12_seg_prod_row), tuple_blocks(Layout::row, fo.nch), s, src, nsrc, nullptr, at64(fo.lo), at32(fo.cnt), d.p, nullptr, fo.nch);
         src = d.as<i32>(); nsrc = fo.nch;
     }
-    hipLaunchKernelGGL(k_fq12_seg_prod_row, dim3(rblocks(plan.m)), dim3(WG), 0, s, src, nsrc, (const u8*)nullptr, at64(plan.seg_lo), at32(plan.seg_cnt), dst, out_m384, plan.m);
+    launch_quiet(KERNEL_OF(k_fq12_seg_prod_row), tuple_blocks(Layout::row, plan.m), s, src, nsrc, nullptr, at64(plan.seg_lo), at32(plan.seg_cnt), dst, out_m384, plan.m);
     return BLSMI_OK;
 }
 // The final exponentiation of m values in the layout fe -- prod: 576-byte in-memory records for the wave layout, a hand-off buffer otherwise --
 // into `out` (576 bytes each) and, where d_is_one is given, their comparison with one.  Leaves the profile mark open.
 void final_exp_values(Layout fe, const void* prod, u64* out, void* d_is_one, size_t m, hipStream_t s) {
-    prof_mark(fe == Layout::wave ? "k_lat:finalexp1" : fe == Layout::row ? "k_final_exp_row" : fe == Layout::quad ? "k_final_exp_quad" : fe == Layout::pair ? "k_final_exp_pair" : "k_final_exp");
-    if (fe == Layout::wave)
-        launch_lat(LAT_FINALEXP1_OFFSET, s, {.b0 = {prod, 576}, .out = out}, m);
-    else if (fe == Layout::row) hipLaunchKernelGGL(k_final_exp_row, dim3(rblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
-    else if (fe == Layout::quad) hipLaunchKernelGGL(k_final_exp_quad, dim3(qblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
-    else if (fe == Layout::pair) hipLaunchKernelGGL(k_final_exp_pair, dim3((unsigned)((m + PT - 1) / PT)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
-    else hipLaunchKernelGGL(k_final_exp, dim3(nblocks(m)), dim3(WG), 0, s, (const i32*)prod, out, m, 0);
+    if (fe == Layout::wave) launch_lat_marked(LAT_FINALEXP1_OFFSET, s, {.b0 = {prod, 576}, .out = out}, m);
+    else launch(kernels_of(fe).final_exp, tuple_blocks(fe, m), s, prod, out, m, 0);
     if (d_is_one) {
-        prof_mark("k_fq12_is_one_m384");
-        hipLaunchKernelGGL(k_fq12_is_one_m384, dim3(rblocks(m)), dim3(WG), 0, s, (const u64*)out, (u8*)d_is_one, m);
+        launch(KERNEL_OF(k_fq12_is_one_m384), tuple_blocks(Layout::row, m), s, out, d_is_one, m);
     }
 }
 // d_g1 / d_g2: np affine records the call owns (records of skipped pairs are overwritten); d_flags: np flag bytes or null.  The m values go to
@@ -2064,12 +2003,12 @@ int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& p
     const i32* src = nullptr;
     if (np) {
         HIPCHK(skip.alloc(np)); HIPCHK(f.alloc(sizeof(i32) * words * np));
-        hipLaunchKernelGGL(k_pprod_skip, dim3(nblocks(np)), dim3(WG), 0, s, d_g1, d_g2, d_flags, (const u8*)g_gens.g1, (const u8*)g_gens.g2, skip.as<u8>(), np);
+        launch_quiet(KERNEL_OF(k_pprod_skip), nblocks(np), s, d_g1, d_g2, d_flags, g_gens.g1, g_gens.g2, skip.p, np);
         launch_miller_tuples(d_g1, d_g2, f.as<i32>(), np, s, pairing_layout(0, np, tune(), route_load(np)));
         src = f.as<i32>();
     }
     // the product (its records: the final exponentiation's input -- the reference's in-memory form for the wave layout, the hand-off buffer otherwise)
-    prof_mark("k_fq12_seg_prod_row");
+    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                         // one segment: the passes of seg_prod_dev
     HIPCHK(prod.alloc(fe == Layout::wave ? 576 * m : sizeof(i32) * words * m));
     int rc = seg_prod_dev(src, np, skip.as<u8>(), plan, blob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
     if (rc) return rc;

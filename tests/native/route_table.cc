@@ -2,7 +2,8 @@
 //   <question> <kind> <n> <others> [option=value ...]
 // (options: Tuning members; unnamed ones keep the library defaults) and prints the answer on one line.  Questions: verify, pairing,
 // miller, final_exp, aggregate (layout + Miller records), side, prepared (does a table serve: verify / pairing / aggregate), hash
-// (the hash of a Verify: path + SWU layout), hash_agg (the uncleared hash of a large g2pubs aggregate).  Two questions are about the
+// (the hash of a Verify: path + SWU layout), hash_agg (the uncleared hash of a large g2pubs aggregate), blocks (the workgroups n tuples
+// take in the single, pair, quad and row layouts).  Two questions are about the
 // option table itself (tests/test_options.py):
 //   options                                       one line per row: member, blsmi_set_option name or -, variable or -, run-time / fixed, default
 //   env [explicit=member,...] [VARIABLE=value ...]  every member after apply_env over that environment, the named rows set through the API
@@ -77,6 +78,8 @@ int main() {
                       << aggregate_route(0, n, true, true, t, load).tables;
         else if (q == "hash") { const HashRoute h = verify_route(kind, n, false, true, t, load).hash; std::cout << name(h.path) << " " << name(h.swu); }
         else if (q == "hash_agg") { const HashRoute h = aggregate_route(kind, n, false, false, t, load).hash; std::cout << name(h.path) << " " << name(h.swu); }
+        else if (q == "blocks")
+            std::cout << tuple_blocks(Layout::single, n) << " " << tuple_blocks(Layout::pair, n) << " " << tuple_blocks(Layout::quad, n) << " " << tuple_blocks(Layout::row, n);
         else { std::cerr << "bad question " << q << "\n"; return 2; }
         std::cout << "\n";
     }

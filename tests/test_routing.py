@@ -115,3 +115,10 @@ def test_hash_tails_at_their_edges(ask):
     assert ask("hash", [128, 129, 3072, 3073], kind=2) == {128: "lat waves", 129: "lat lanes", 3072: "lat lanes", 3073: "plain lanes"}
     # a g2pubs aggregate that raises its product to 1 - x hashes without clearing the cofactor: never the level programs or the four-lane tail
     assert ask("hash_agg", [100, 32768, 32769], kind=0) == {100: "g1_lane lanes", 32768: "g1_lane lanes", 32769: "plain lanes"}
+
+
+def test_tuple_blocks(ask):
+    """the workgroups of n tuples: 64, 32, 16 and 4 tuples to a workgroup of 64 lanes in the single, pair, quad and row layouts"""
+    sizes = sorted({n for per in (64, 32, 16, 4) for n in (0, 1, per - 1, per, per + 1, 2 ** 20 + 1)})
+    want = {n: "%d %d %d %d" % ((n + 63) // 64, (n + 31) // 32, (n + 15) // 16, (n + 3) // 4) for n in sizes}
+    assert ask("blocks", sizes) == want

@@ -1,6 +1,7 @@
 """VerifyAggregate from the host's point of view: ms per call at the sizes where the host code shows -- a 1-signer and a 128-signer aggregate of
 both packages from host buffers; 2 304 and 8 192 signers from host buffers and resident; the 65 536- and 2^20-signer g2pubs aggregate
-resident and from host buffers; one verify_batch_rlc call per package at 32 768.  One process is one run: it prints `leg median_ms` for
+resident and from host buffers; one verify_batch_rlc call per package at 32 768; and the smallest calls, where the host's cost per launch shows
+most: a lone Pairing, g2pubs Verify and g1pubs Verify at 1 and 2 304 tuples from host buffers.  One process is one run: it prints `leg median_ms` for
 every leg.  To compare two builds, start it alternately with and without BLSMI_LIB (bls_amd/_native.py), several runs each.  The points
 are well-formed but no signatures (tools/options_launch_trace.py's workload): the verdict is 0 at the end of the same work.  GPU box only."""
 import hashlib, os, sys, time
@@ -55,4 +56,9 @@ pm = packed(n)
 one = np.ones(n, dtype=np.uint64)
 leg("g2pubs.VerifyBatchRlc/host/%d" % n, lambda: E.g2pubs_verify_batch_rlc(pm, g2[:n], g1[:n], scalars=None), 7)
 leg("g1pubs.VerifyBatchRlc/host/%d" % n, lambda: E.g1pubs_verify_batch_rlc(pm, g1[:n], g2[:n], scalars=None), 7)
+for n, reps in ((1, 200), (2304, 60)):
+    pm = packed(n)
+    leg("Pairing/host/%d" % n, lambda: E.pairing_batch(g1[:n], g2[:n], n), reps)
+    leg("g2pubs.Verify/host/%d" % n, lambda: E.g2pubs_verify_batch(pm, g2[:n], g1[:n]), reps)
+    leg("g1pubs.Verify/host/%d" % n, lambda: E.g1pubs_verify_batch(pm, g1[:n], g2[:n]), reps)
 E.shutdown()
