@@ -7,14 +7,10 @@
 #define BLSMI_QUAD_WAVES 1
 #endif
 // measured at 16 384 pairings (same box, tools/ab_bench.py): the Fq12-level routines expanded in line 7.11 -> 6.87 ms (the accumulator
-// stays in registers: 512 of them at one wave per SIMD); the 16-squaring run of |x| NOT compressed 4.05 -> 3.95 ms for the final
-// exponentiation (a decompression -- one inversion, which does not split over the pairs -- outweighs 16 x (3 - 2) products here);
-// assembly-blob cores 7.5 ms and two waves per SIMD (256 registers) 7.6 ms: both off
+// stays in registers: 512 of them at one wave per SIMD); assembly-blob cores 7.5 ms and two waves per SIMD (256 registers) 7.6 ms: both off.
+// (The 16-squaring run of |x| is not compressed here either: quad_body.inc, QuadOps::MIN_RUN.)
 #ifndef BLSMI_QUAD_NO_INLINE
 #define BLSMI_QUAD_INLINE
-#endif
-#ifndef BLSMI_QUAD_MIN_RUN
-#define BLSMI_QUAD_MIN_RUN 27
 #endif
 #include "pairing.cuh"
 #include "device_io.cuh"

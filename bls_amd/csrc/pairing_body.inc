@@ -102,12 +102,8 @@ BLSMI_NOINLINE void addition_step_h(G2Proj& r, const Fp2S& qx, const Fp2S& qy, F
 template <bool EXACT> BLSMI_DEV void dbl_step(G2Proj& r, Fp2S& o0, Fp2S& o1, Fp2S& o2) {
     // Inlining the homogeneous step into the loops (the running point would stay in registers instead of crossing a call boundary
     // 63 times) was measured and is NOT a gain here -- k_miller1h_pair 9.65 ms against 9.5 ms per 65 536 -- unlike in the G1 / G2
-    // ladders of k_curve.hip: the accumulator f does not fit beside it.  -DBLSMI_DBL_INLINE is the A/B switch.
-#ifdef BLSMI_DBL_INLINE
-    if constexpr (EXACT) doubling_step(r, o0, o1, o2); else doubling_step_h_i(r, o0, o1, o2);
-#else
+    // ladders of k_curve.hip: the accumulator f does not fit beside it.
     if constexpr (EXACT) doubling_step(r, o0, o1, o2); else doubling_step_h(r, o0, o1, o2);
-#endif
 }
 template <bool EXACT> BLSMI_DEV void add_step(G2Proj& r, const Fp2S& qx, const Fp2S& qy, Fp2S& o0, Fp2S& o1, Fp2S& o2) {
     if constexpr (EXACT) addition_step(r, qx, qy, o0, o1, o2); else addition_step_h(r, qx, qy, o0, o1, o2);
@@ -119,14 +115,15 @@ BLSMI_NOINLINE void ell(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2
     f = fp12_store(fp12_mul_by_014(f, o2, c1, c0));
 }
 
-// f = (f * line(P))^2 in one call: the 180-word accumulator crosses the call boundary once per iteration
-BLSMI_DEV void ell_sqr_i(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
+// f = (f * line(P))^2 in one call: the 180-word accumulator crosses the call boundary once per iteration.  (Expanded in line at the loop's
+// one call site, so that f would be a local of the kernel, it was measured slower: k_miller1h_pair 9.83 against 9.31 ms -- the kernel
+// then spills 3 072 instead of 1 664 bytes a lane.)
+BLSMI_NOINLINE void ell_sqr(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
     const auto c0 = fp2_mul_fp(o0, py);
     const auto c1 = fp2_mul_fp(o1, px);
     const Fp12S g = fp12_store(fp12_mul_by_014(f, o2, c1, c0));
     f = fp12_store(fp12_sqr(g));
 }
-BLSMI_NOINLINE void ell_sqr(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) { ell_sqr_i(f, o0, o1, o2, px, py); }
 
 // two lines (one per pair of a 2-pair loop) multiplied into f as one 5-coefficient element; SQR: followed by f^2
 template <bool SQR>
@@ -138,12 +135,31 @@ BLSMI_NOINLINE void ell2(Fp12S& f, const Fp2S& a0, const Fp2S& a1, const Fp2S& a
     if (SQR) f = fp12_store(fp12_sqr(g)); else f = g;
 }
 
-// pairing.go:16-75 for NP pairs sharing the squarings; bits of |x|>>1 below its leading one.
+// The walk over the bits of |x| >> 1 below its leading one (pairing.go:41-70; g2.go:650-801 runs the same walk to prepare a point),
+// written ONCE for the single-lane, lane-pair and lane-quad loops: a doubling per bit; where the bit is set the line(s) go into f and an
+// addition follows; multiply-and-square; after the last bit one more doubling, whose line(s) go in unsquared.  The caller sets f to one
+// before and conjugates after (blsIsNegative, pairing.go:71-73).  (The lane-row loops keep a shape of their own, written out: row_body.inc.)
+template <class Dbl, class Add, class Mul, class MulSqr>
+BLSMI_DEV void x_bit_walk(Dbl dbl, Add add, Mul mul, MulSqr mul_sqr) {
+    const u64 xr = BLSMI_X_ABS >> 1;
+    for (int i = 61; i >= 0; i--) {
+        dbl();
+        if ((xr >> i) & 1) { mul(); add(); }
+        mul_sqr();
+    }
+    dbl();
+    mul();
+}
+
+// pairing.go:16-75 for one pair, or for two pairs sharing the squarings.
 // PRE0: the G2 point of pair 0 is the fixed generator, whose 68 line-coefficient triples (the reference's
 // G2Prepared, g2.go:639-801) were computed once at start-up by the same doubling/addition steps and are read
 // from `pre` ([line][coefficient][c0|c1][limb]) instead of being recomputed per tuple.
 BLSMI_DEV void load_line(const i32* pre, int line, Fp2S& o0, Fp2S& o1, Fp2S& o2) {
     o0 = fp2_table_load(pre, 3 * line); o1 = fp2_table_load(pre, 3 * line + 1); o2 = fp2_table_load(pre, 3 * line + 2);
+}
+BLSMI_DEV void store_line(i32* table, int line, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2) {
+    fp2_table_store(table, 3 * line, o0); fp2_table_store(table, 3 * line + 1, o1); fp2_table_store(table, 3 * line + 2, o2);
 }
 // EXACT: the reference's doubling / addition steps -- f is then the reference's Miller value itself; otherwise the
 // homogeneous steps, f differs by a factor the final exponentiation removes.
@@ -172,126 +188,117 @@ BLSMI_DEV G2Proj lds_get_proj(const i32* l) {
 }
 template <int NP, bool PRE0 = false, bool EXACT = true, bool PRE1 = false, class G1P, class G2P>
 BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], const i32* pre = nullptr, const i32* pre1 = nullptr, i32* lds_r = nullptr) {
+    static_assert(NP == 1 || NP == 2, "one pair, or two pairs sharing the squarings");
+    constexpr int LAST = NP - 1;
+    constexpr bool PRE_LAST = NP == 1 ? PRE0 : PRE1;                       // the last pair's lines come from a table: it has no running point
     G2Proj r[NP];
 #pragma unroll
     for (int k = 0; k < NP; k++) { r[k].x = q[k].x; r[k].y = q[k].y; r[k].z = fp2_one(); }
     f = fp12_one();
-    const u64 xr = BLSMI_X_ABS >> 1;
+    const bool in_lds = !EXACT && !PRE_LAST && lds_r != nullptr;           // the last pair's running point in LDS, its doubling step in line (see lds_put_proj)
+    if (in_lds) lds_put_proj(lds_r, r[LAST]);
+    auto dbl_last = [&](Fp2S& a0, Fp2S& a1, Fp2S& a2) {
+        if (in_lds) { G2Proj t = lds_get_proj(lds_r); doubling_step_h_i(t, a0, a1, a2); lds_put_proj(lds_r, t); }
+        else dbl_step<EXACT>(r[LAST], a0, a1, a2);
+    };
+    auto add_last = [&](Fp2S& a0, Fp2S& a1, Fp2S& a2) {
+        if (in_lds) { G2Proj t = lds_get_proj(lds_r); add_step<EXACT>(t, q[LAST].x, q[LAST].y, a0, a1, a2); lds_put_proj(lds_r, t); }
+        else add_step<EXACT>(r[LAST], q[LAST].x, q[LAST].y, a0, a1, a2);
+    };
     Fp2S o0, o1, o2;
     int line = 0;
-    if constexpr (NP == 2) {
+    if constexpr (NP == 1) {
+        x_bit_walk([&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else dbl_last(o0, o1, o2); },
+                   [&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else add_last(o0, o1, o2); },
+                   [&] { ell(f, o0, o1, o2, p[0].x, p[0].y); },
+                   [&] { ell_sqr(f, o0, o1, o2, p[0].x, p[0].y); });
+    } else {
         // both pairs' lines of a step are multiplied together first (ell2): 23 instead of 26 Fq2 products per step
         Fp2S n0, n1, n2;
         int line1 = 0;
-        const bool r1_lds = !EXACT && !PRE1 && lds_r != nullptr;          // pair 1's running point in LDS, its doubling step in line (see lds_put_proj)
-        if (r1_lds) lds_put_proj(lds_r, r[1]);
-        auto dbl1 = [&]() {
-            if (PRE1) load_line(pre1, line1++, n0, n1, n2);
-            else if (r1_lds) { G2Proj t = lds_get_proj(lds_r); doubling_step_h_i(t, n0, n1, n2); lds_put_proj(lds_r, t); }
-            else dbl_step<EXACT>(r[1], n0, n1, n2);
-        };
-        auto add1 = [&]() {
-            if (PRE1) load_line(pre1, line1++, n0, n1, n2);
-            else if (r1_lds) { G2Proj t = lds_get_proj(lds_r); add_step<EXACT>(t, q[1].x, q[1].y, n0, n1, n2); lds_put_proj(lds_r, t); }
-            else add_step<EXACT>(r[1], q[1].x, q[1].y, n0, n1, n2);
-        };
-        for (int i = 61; i >= 0; i--) {
-            const bool add = (xr >> i) & 1;
-            if (PRE0) load_line(pre, line++, o0, o1, o2); else dbl_step<EXACT>(r[0], o0, o1, o2);
-            dbl1();
-            if (add) {
-                ell2<false>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y);
-                if (PRE0) load_line(pre, line++, o0, o1, o2); else add_step<EXACT>(r[0], q[0].x, q[0].y, o0, o1, o2);
-                add1();
-            }
-            ell2<true>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y);
-        }
-        if (PRE0) load_line(pre, line++, o0, o1, o2); else dbl_step<EXACT>(r[0], o0, o1, o2);
-        dbl1();
-        ell2<false>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y);
-        fp12_conj_inplace(f);
-        return;
-    }
-    const bool in_lds = !EXACT && lds_r != nullptr && !(PRE0 && NP == 1);
-    if (in_lds) lds_put_proj(lds_r, r[NP - 1]);
-    auto dbl_last = [&](Fp2S& a0, Fp2S& a1, Fp2S& a2) {                   // the doubling step of pair NP - 1
-        if (in_lds) { G2Proj t = lds_get_proj(lds_r); doubling_step_h_i(t, a0, a1, a2); lds_put_proj(lds_r, t); }
-        else dbl_step<EXACT>(r[NP - 1], a0, a1, a2);
-    };
-    auto add_last = [&](Fp2S& a0, Fp2S& a1, Fp2S& a2) {
-        if (in_lds) { G2Proj t = lds_get_proj(lds_r); add_step<EXACT>(t, q[NP - 1].x, q[NP - 1].y, a0, a1, a2); lds_put_proj(lds_r, t); }
-        else add_step<EXACT>(r[NP - 1], q[NP - 1].x, q[NP - 1].y, a0, a1, a2);
-    };
-#ifdef BLSMI_ELL_INLINE
-    if constexpr (NP == 1 && !PRE0) {
-        // A/B (-DBLSMI_ELL_INLINE): one call site for the multiply-and-square step, expanded in line -- the accumulator f then is a local
-        // of the kernel.  Measured: k_miller1h_pair 9.83 against 9.31 ms (the kernel spills 3 072 instead of 1 664 bytes a lane).  Off.
-        if (in_lds) {
-            for (int i = 61; i >= 0; i--) {
-                dbl_last(o0, o1, o2);
-                if ((xr >> i) & 1) { ell(f, o0, o1, o2, p[0].x, p[0].y); add_last(o0, o1, o2); }
-                ell_sqr_i(f, o0, o1, o2, p[0].x, p[0].y);
-            }
-            dbl_last(o0, o1, o2);
-            ell(f, o0, o1, o2, p[0].x, p[0].y);
-            fp12_conj_inplace(f);
-            return;
-        }
-    }
-#endif
-    for (int i = 61; i >= 0; i--) {
-        const bool add = (xr >> i) & 1;
-#pragma unroll
-        for (int k = 0; k < NP; k++) {
-            if (PRE0 && k == 0) load_line(pre, line++, o0, o1, o2);
-            else if (k == NP - 1) dbl_last(o0, o1, o2);
-            else dbl_step<EXACT>(r[k], o0, o1, o2);
-            if (!add && k == NP - 1) ell_sqr(f, o0, o1, o2, p[k].x, p[k].y);       // common case: multiply by the last line and square
-            else ell(f, o0, o1, o2, p[k].x, p[k].y);
-        }
-        if (add) {
-#pragma unroll
-            for (int k = 0; k < NP; k++) {
-                if (PRE0 && k == 0) load_line(pre, line++, o0, o1, o2);
-                else if (k == NP - 1) add_last(o0, o1, o2);
-                else add_step<EXACT>(r[k], q[k].x, q[k].y, o0, o1, o2);
-                if (k == NP - 1) ell_sqr(f, o0, o1, o2, p[k].x, p[k].y);
-                else ell(f, o0, o1, o2, p[k].x, p[k].y);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NP; k++) {
-        if (PRE0 && k == 0) load_line(pre, line++, o0, o1, o2);
-        else if (k == NP - 1) dbl_last(o0, o1, o2);
-        else dbl_step<EXACT>(r[k], o0, o1, o2);
-        ell(f, o0, o1, o2, p[k].x, p[k].y);
+        x_bit_walk([&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else dbl_step<EXACT>(r[0], o0, o1, o2);
+                         if (PRE1) load_line(pre1, line1++, n0, n1, n2); else dbl_last(n0, n1, n2); },
+                   [&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else add_step<EXACT>(r[0], q[0].x, q[0].y, o0, o1, o2);
+                         if (PRE1) load_line(pre1, line1++, n0, n1, n2); else add_last(n0, n1, n2); },
+                   [&] { ell2<false>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); },
+                   [&] { ell2<true>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); });
     }
     fp12_conj_inplace(f);                                              // blsIsNegative (pairing.go:71-73)
 }
 // the 68 triples of one G2 point, in loop order, written by every lane that calls it (identical values)
 BLSMI_DEV void prepare_lines(const Fp2S& qx, const Fp2S& qy, i32* table) {
     G2Proj r; r.x = qx; r.y = qy; r.z = fp2_one();
-    const u64 xr = BLSMI_X_ABS >> 1;
     Fp2S o0, o1, o2;
     int line = 0;
-    for (int i = 61; i >= 0; i--) {
-        doubling_step(r, o0, o1, o2);
-        fp2_table_store(table, 3 * line, o0); fp2_table_store(table, 3 * line + 1, o1); fp2_table_store(table, 3 * line + 2, o2); line++;
-        if ((xr >> i) & 1) {
-            addition_step(r, qx, qy, o0, o1, o2);
-            fp2_table_store(table, 3 * line, o0); fp2_table_store(table, 3 * line + 1, o1); fp2_table_store(table, 3 * line + 2, o2); line++;
-        }
-    }
-    doubling_step(r, o0, o1, o2);
-    fp2_table_store(table, 3 * line, o0); fp2_table_store(table, 3 * line + 1, o1); fp2_table_store(table, 3 * line + 2, o2);
+    x_bit_walk([&] { doubling_step(r, o0, o1, o2); store_line(table, line++, o0, o1, o2); },
+               [&] { addition_step(r, qx, qy, o0, o1, o2); store_line(table, line++, o0, o1, o2); },
+               [] {}, [] {});                                             // no accumulator: the lines are the result
 }
 
+// ---- final exponentiation, written ONCE for every lane layout over a struct O of static operations on the layout's Fq12 type O::T
+// (Fp12Ops below; QuadOps in quad_body.inc, RowOps in row_body.inc).  Every operation is one call into the layout's own routine and writes
+// its first argument, which may be one of its operands.
+//
 // pairing.go:92-98 (ExpByX): f^|e| then conjugate.  f must lie in the cyclotomic subgroup.
-// Square-and-multiply from the top bit, as the reference does.  A run of >= EXPX_MIN_RUN squarings with no
+// Square-and-multiply from the top bit, as the reference does.  A run of >= O::MIN_RUN squarings with no
 // multiplication in between (|x| has runs of 32 and 16) is walked in Karabina's compressed form -- four coefficients, two
 // Fq4 squarings per step instead of three -- and decompressed once at its end (one safegcd inversion): same element.
-constexpr int EXPX_MIN_RUN = 12;
+// O::x_sqr is one plain squaring inside this loop, O::x_sqr_run a compressed run; MIN_RUN = 0: the layout never compresses (and has no
+// x_sqr_run).  (x_sqr, x_sqr_run and exp_x are named apart from the layouts' routines cyc_sqr_run / exp_by_x, which a member would hide.)
+template <class O>
+BLSMI_DEV void exp_by_x_loop(typename O::T& out, const typename O::T& f, u64 e) {
+    typename O::T res = f;
+    int i = 62 - __builtin_clzll(e);                                       // next bit to process
+    while (i >= 0) {
+        // squarings up to and including the next set bit (or down to bit 0)
+        const u64 below = e & ((2ull << i) - 1);                           // bits i..0
+        const int next = below ? 63 - __builtin_clzll(below) : -1;         // position of the next set bit at or below i
+        const int run = next < 0 ? i + 1 : i - next + 1;                   // squarings up to and including that bit
+        bool plain = true;
+        if constexpr (O::MIN_RUN > 0)
+            if (run >= O::MIN_RUN) { O::x_sqr_run(res, res, run); plain = false; }
+        if (plain) for (int j = 0; j < run; j++) O::x_sqr(res, res);
+        if (next >= 0) { typename O::T t = res; O::mul(t, t, f); res = t; }
+        i = next - 1;
+        if (next < 0) break;
+    }
+    O::conj(res);
+    out = res;
+}
+// pairing.go:79-129.  Computes r^(3(q^12-1)/r_order) in place; a non-invertible input (only 0)
+// maps to 0 where the reference returns nil.
+template <class O>
+BLSMI_DEV void final_exp_chain(typename O::T& r) {
+    typename O::T f2, y0, y1, y2, y3;
+    O::inv(f2, r);
+    O::conj(r);
+    O::mul(r, r, f2);
+    O::frob2(f2, r);
+    O::mul(r, f2, r);
+    const u64 x = BLSMI_X_ABS;
+    O::cyc_sqr(y0, r);
+    O::exp_x(y1, y0, x);
+    O::exp_x(y2, y1, x >> 1);
+    y3 = r; O::conj(y3);
+    O::mul(y1, y1, y3);
+    O::conj(y1);
+    O::mul(y1, y1, y2);
+    O::exp_x(y2, y1, x);
+    O::exp_x(y3, y2, x);
+    O::conj(y1);
+    O::mul(y3, y3, y1);
+    O::conj(y1);
+    O::frob3(y1, y1);
+    O::frob2(y2, y2);
+    O::mul(y1, y1, y2);
+    O::exp_x(y2, y3, x);
+    O::mul(y2, y2, y0);
+    O::mul(y2, y2, r);
+    O::mul(y1, y1, y2);
+    O::frob1(y3, y3);
+    O::mul(r, y1, y3);
+}
+
 BLSMI_DEV Fp12S cyc_sqr_run(const Fp12S& g, int m) {
     CycCompressed c = cyc_compress(g);
     for (int j = 0; j < m; j++) c = cyc_compressed_sqr(c);
@@ -299,53 +306,22 @@ BLSMI_DEV Fp12S cyc_sqr_run(const Fp12S& g, int m) {
     cyc_z1_fraction(c, num, den);
     return cyc_decompress(c, fp2_store(fp2_mul(num, fp2_store(fp2_inv(den)))));
 }
-BLSMI_NOINLINE void exp_by_x(Fp12S& out, const Fp12S& f, u64 e) {
-    Fp12S res = f;
-    int i = 62 - __builtin_clzll(e);                                       // next bit to process
-    while (i >= 0) {
-        // squarings up to and including the next set bit (or down to bit 0)
-        const u64 below = e & ((2ull << i) - 1);                           // bits i..0
-        const int next = below ? 63 - __builtin_clzll(below) : -1;         // position of the next set bit at or below i
-        const int run = next < 0 ? i + 1 : i - next + 1;                   // squarings up to and including that bit
-        if (run >= EXPX_MIN_RUN) res = cyc_sqr_run(res, run);
-        else for (int j = 0; j < run; j++) res = fp12_cyclotomic_sqr(res);
-        if (next >= 0) { Fp12S t = res; nf_fp12_mul(t, t, f); res = t; }
-        i = next - 1;
-        if (next < 0) break;
-    }
-    fp12_conj_inplace(res);
-    out = res;
-}
-// pairing.go:79-129.  Computes r^(3(q^12-1)/r_order) in place; a non-invertible input (only 0)
-// maps to 0 where the reference returns nil.
-BLSMI_DEV void final_exponentiation(Fp12S& r) {
-    Fp12S f2, y0, y1, y2, y3;
-    nf_fp12_inv(f2, r);
-    fp12_conj_inplace(r);
-    nf_fp12_mul(r, r, f2);
-    nf_fp12_frob2(f2, r);
-    nf_fp12_mul(r, f2, r);
-    const u64 x = BLSMI_X_ABS;
-    nf_fp12_cyc_sqr(y0, r);
-    exp_by_x(y1, y0, x);
-    exp_by_x(y2, y1, x >> 1);
-    y3 = r; fp12_conj_inplace(y3);
-    nf_fp12_mul(y1, y1, y3);
-    fp12_conj_inplace(y1);
-    nf_fp12_mul(y1, y1, y2);
-    exp_by_x(y2, y1, x);
-    exp_by_x(y3, y2, x);
-    fp12_conj_inplace(y1);
-    nf_fp12_mul(y3, y3, y1);
-    fp12_conj_inplace(y1);
-    nf_fp12_frob3(y1, y1);
-    nf_fp12_frob2(y2, y2);
-    nf_fp12_mul(y1, y1, y2);
-    exp_by_x(y2, y3, x);
-    nf_fp12_mul(y2, y2, y0);
-    nf_fp12_mul(y2, y2, r);
-    nf_fp12_mul(y1, y1, y2);
-    nf_fp12_frob1(y3, y3);
-    nf_fp12_mul(r, y1, y3);
-}
+BLSMI_NOINLINE void exp_by_x(Fp12S& out, const Fp12S& f, u64 e);
+// one tuple per lane / per lane pair: the out-of-line routines above; inside exp_by_x the squarings are expanded in line
+struct Fp12Ops {
+    using T = Fp12S;
+    static constexpr int MIN_RUN = 12;
+    static BLSMI_DEV void inv(T& r, const T& a) { nf_fp12_inv(r, a); }
+    static BLSMI_DEV void mul(T& r, const T& a, const T& b) { nf_fp12_mul(r, a, b); }
+    static BLSMI_DEV void cyc_sqr(T& r, const T& a) { nf_fp12_cyc_sqr(r, a); }
+    static BLSMI_DEV void x_sqr(T& r, const T& a) { r = fp12_cyclotomic_sqr(a); }
+    static BLSMI_DEV void x_sqr_run(T& r, const T& a, int m) { r = cyc_sqr_run(a, m); }
+    static BLSMI_DEV void frob1(T& r, const T& a) { nf_fp12_frob1(r, a); }
+    static BLSMI_DEV void frob2(T& r, const T& a) { nf_fp12_frob2(r, a); }
+    static BLSMI_DEV void frob3(T& r, const T& a) { nf_fp12_frob3(r, a); }
+    static BLSMI_DEV void conj(T& a) { fp12_conj_inplace(a); }
+    static BLSMI_DEV void exp_x(T& r, const T& a, u64 e) { exp_by_x(r, a, e); }
+};
+BLSMI_NOINLINE void exp_by_x(Fp12S& out, const Fp12S& f, u64 e) { exp_by_x_loop<Fp12Ops>(out, f, e); }
+BLSMI_DEV void final_exponentiation(Fp12S& r) { final_exp_chain<Fp12Ops>(r); }
 

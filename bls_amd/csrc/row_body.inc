@@ -345,6 +345,13 @@ BLSMI_DEV void r_addition_step(G2Proj& r, const QSRC& q, const RPoint& P, RLine&
     if constexpr (TAB) { lt->c0 = t->o2; lt->c1 = bcast<4>(P4); lt->c4 = bcast<5>(P4); }
     r.x = r_stored(bcast<0>(P4)); r.y = fp2_store(fp2_sub(bcast<1>(P4), bcast<2>(P4))); r.z = r_stored(bcast<3>(P4));
 }
+// The three loops below each write out their walk over the bits of |x| >> 1, in one shape: a bit is a loop over its steps -- the doubling, then the
+// addition where |x|'s bit is set -- that ends in ONE expansion site of the fused line product (it is expanded in line; code size: -DBLSMI_ROW_INLINE
+// above shows what 235 KB of code cost), then the squaring.  That shape is not pairing_body.inc's x_bit_walk, which has two sites a bit.  A walker of
+// this shape shared by the three loops (a template over the step, the steps a closure or a step object) was built and measured: the same
+// multiply-adds, but the compiler lays the blocks out otherwise and copies a line (41 moves) at the loop head -- k_miller1h_row 0.976 -> 1.003 ms per
+// 4 096 (the parent's worst of five runs: 0.989), the 2 304-signer aggregates 2.863 -> 2.908 and 3.995 -> 4.036 ms (profiles/r14_pairing_bodies.log).
+// These kernels are instruction-count bound at the edge of their register budget, so the loops stay written out.
 // one (P, Q) pair: the value k_miller1h_pair computes
 BLSMI_DEV void miller_loop_r(R12& f, const FpS& px, const FpS& py, const RQ& q) {
     G2Proj r; q.load(r.x, r.y); r.z = fp2_one();
@@ -454,42 +461,20 @@ BLSMI_DEV R12 r12_frob(const R12& a) {
 BLSMI_NOINLINE R12 r12_frob1(const R12 a) { return r12_frob<1>(a); }
 BLSMI_NOINLINE R12 r12_frob2(const R12 a) { return r12_frob<2>(a); }
 BLSMI_NOINLINE R12 r12_frob3(const R12 a) { return r12_frob<3>(a); }
-// pairing.go:92-98 (ExpByX): f^|e| then conjugate; square-and-multiply from the top bit
-BLSMI_NOINLINE R12 exp_by_x_r(const R12 f, u64 e) {
-    R12 res = f;
-    for (int i = 62 - __builtin_clzll(e); i >= 0; i--) {
-        res = r12_cyc_sqr(res);
-        if ((e >> i) & 1) res = r12_mul(res, f);
-    }
-    r12_conj_inplace(res);
-    return res;
-}
-BLSMI_DEV void final_exponentiation_r(R12& r) {
-    R12 f2 = r12_inv(r);
-    r12_conj_inplace(r);
-    r = r12_mul(r, f2);
-    f2 = r12_frob2(r);
-    r = r12_mul(f2, r);
-    const u64 x = BLSMI_X_ABS;
-    const R12 y0 = r12_cyc_sqr(r);
-    R12 y1 = exp_by_x_r(y0, x);
-    R12 y2 = exp_by_x_r(y1, x >> 1);
-    R12 y3 = r; r12_conj_inplace(y3);
-    y1 = r12_mul(y1, y3);
-    r12_conj_inplace(y1);
-    y1 = r12_mul(y1, y2);
-    y2 = exp_by_x_r(y1, x);
-    y3 = exp_by_x_r(y2, x);
-    r12_conj_inplace(y1);
-    y3 = r12_mul(y3, y1);
-    r12_conj_inplace(y1);
-    y1 = r12_frob3(y1);
-    y2 = r12_frob2(y2);
-    y1 = r12_mul(y1, y2);
-    y2 = exp_by_x_r(y3, x);
-    y2 = r12_mul(y2, y0);
-    y2 = r12_mul(y2, r);
-    y1 = r12_mul(y1, y2);
-    y3 = r12_frob1(y3);
-    r = r12_mul(y1, y3);
-}
+// the chain and the ExpByX loop of pairing_body.inc over R12: plain Granger-Scott squarings throughout (MIN_RUN = 0; see the head of this file)
+BLSMI_NOINLINE R12 exp_by_x_r(const R12 f, u64 e);
+struct RowOps {
+    using T = R12;
+    static constexpr int MIN_RUN = 0;
+    static BLSMI_DEV void inv(T& r, const T& a) { r = r12_inv(a); }
+    static BLSMI_DEV void mul(T& r, const T& a, const T& b) { r = r12_mul(a, b); }
+    static BLSMI_DEV void cyc_sqr(T& r, const T& a) { r = r12_cyc_sqr(a); }
+    static BLSMI_DEV void x_sqr(T& r, const T& a) { r = r12_cyc_sqr(a); }
+    static BLSMI_DEV void frob1(T& r, const T& a) { r = r12_frob1(a); }
+    static BLSMI_DEV void frob2(T& r, const T& a) { r = r12_frob2(a); }
+    static BLSMI_DEV void frob3(T& r, const T& a) { r = r12_frob3(a); }
+    static BLSMI_DEV void conj(T& a) { r12_conj_inplace(a); }
+    static BLSMI_DEV void exp_x(T& r, const T& a, u64 e) { r = exp_by_x_r(a, e); }
+};
+BLSMI_NOINLINE R12 exp_by_x_r(const R12 f, u64 e) { R12 r; exp_by_x_loop<RowOps>(r, f, e); return r; }
+BLSMI_DEV void final_exponentiation_r(R12& r) { final_exp_chain<RowOps>(r); }

@@ -57,7 +57,7 @@ SETTINGS = {
     "nosort":     (8192, 16384, (2048, 8192), 1, 0),                       # the MSM's exact digit passes instead of the sort
 }
 
-PAIRING = ["pairing", "pprod"]
+PAIRING = ["pairing", "pprod", "miller"]
 VERIFY = ["g2v", "g1v", "g1vd"]
 G2AGG = ["g2agg_ok", "g2agg_bad", "g2common_ok", "g2common_bad"]
 G1AGG = ["g1agg_ok", "g1agg_bad"]
@@ -85,13 +85,13 @@ def _no(*banned):
 # configuration -> (environment, [(settings, calls)], [(settings, call, kernel names that must appear)], [(settings, calls, names -> offenders)])
 CONFIGS = {
     "defaults": ({}, [("pair", EVERYTHING), ("default", ["gen1", "gen2"] + VERIFY)],          # the control: same worker, same expectations
-                 [("pair", "pairing", ["k_miller1h_pair", "k_final_exp_pair"]), ("pair", "g2v", ["k_miller2_pair", "k_final_exp_is_one_pair"]),
+                 [("pair", "pairing", ["k_miller1h_pair", "k_final_exp_pair"]), ("pair", "miller", ["k_miller1_pair"]), ("pair", "g2v", ["k_miller2_pair", "k_final_exp_is_one_pair"]),
                   ("pair", "g2mul", ["k_g2_mul_glv_pair"]), ("pair", "msm_g1_n67", ["k_g1_mul_glv"]), ("pair", "msm_g2_n67", ["k_g2_mul_glv_pair"]),
                   ("default", "gen1", ["k_g1_mul_fixed_wave"]), ("default", "gen2", ["k_g2_mul_fixed_wave"]),
                   ("default", "g2v", ["k_swu_g1_waves", "k_lat:verify2"]), ("default", "g1v", ["k_swu_g2_waves", "k_lat:verify1s"]), ("default", "g1vd", ["k_lat:verify1s"])], []),
     "single": ({"BLSMI_LAYOUT": "single"}, [("pair", EVERYTHING)],
                [("pair", c, ["k_miller2", "k_final_exp_is_one"]) for c in VERIFY + ["ser_g2"]]
-               + [("pair", "pairing", ["k_miller1h", "k_final_exp"]), ("pair", "pprod", ["k_miller1h", "k_final_exp"]),
+               + [("pair", "pairing", ["k_miller1h", "k_final_exp"]), ("pair", "pprod", ["k_miller1h", "k_final_exp"]), ("pair", "miller", ["k_miller1"]),
                   ("pair", "g2agg_ok", ["k_miller1h"]), ("pair", "g1agg_ok", ["k_miller1h"]),
                   ("pair", "g2mul", ["k_g2_mul_glv"]), ("pair", "g2mul_any", ["k_g2_mul"]), ("pair", "msm_g2_n67", ["k_g2_mul_glv"])],
                [("pair", PAIRING + VERIFY + G2AGG + G1AGG + ["ser_g2"], _only_one_lane), ("pair", ["g2mul", "g2mul_any"] + MSM_G2, _no("k_g2_mul_glv_pair", "k_g2_mul_pair"))]),
@@ -197,6 +197,7 @@ def _calls(E, W):
     c = {
         "pairing": lambda: {"values": _tokens(E.pairing_batch(g1, g2, N), N)},
         "pprod": pprod,
+        "miller": lambda: {"values": _tokens(E.miller_loop_batch(g1, g2, N), N)},
         "g2v": lambda: verdicts(*E.g2pubs_verify_batch(msgs, W["g2v_pks"].tobytes(), W["g2v_sigs"].tobytes(), W["g2v_flags"])),
         "g1v": lambda: verdicts(*E.g1pubs_verify_batch(msgs, W["g1v_pks"].tobytes(), W["g1v_sigs"].tobytes(), W["g1v_flags"])),
         "g1vd": lambda: verdicts(E.g1pubs_verify_with_domain_batch(msgs32, DOMAIN, W["g1vd_pks"].tobytes(), W["g1vd_sigs"].tobytes(), W["g1vd_flags"])),
@@ -288,6 +289,7 @@ def _build():
     g1s, g2s = [rand_g1(xs) for _ in range(N)], [rand_g2(xs) for _ in range(N)]
     W["g1"], W["g2"] = arr(g1s), arr(g2s)
     X["pairing"] = {"values": _tokens(RC.pairing_batch(b"".join(g1s), b"".join(g2s), N), N)}
+    X["miller"] = {"values": _tokens(np.stack([RC.miller_loop(a, b, 1) for a, b in zip(g1s, g2s)]), N)}     # MillerLoop: the reference's exact steps
     one = np.zeros(72, dtype=np.uint64); one[:6] = np.array(P.limbs64(P.to_mont(1)), dtype=np.uint64)
     vals = [one]
     for lo, hi in ((0, 1), (1, N)):
