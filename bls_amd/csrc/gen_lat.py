@@ -51,6 +51,8 @@ LMAX = 15             # fp.cuh: L*(2^27+64) < 2^31
 VPROD_MAX = 1 << 23
 V_REDUCE_AT = 512     # a LIN result whose value bound would exceed this is value-reduced (fp_reduce -> V = 3)
 CMAX = 15             # |coefficient| of a gathered term
+SQR_LMAX = 2          # lat_sqr3 (gen_lat_mul.py) multiplies the operand's limbs by 6 in int32: 6 L (2^27 + 64) < 2^31
+LIN_VMAX = 1 << 12    # fp.cuh VMAX: k_lat.hip labels the gather of a LIN (and INV) job Fp<LMAX, VMAX>
 
 
 class Node:
@@ -128,7 +130,7 @@ class Builder:
             assert len(coords) == ncoord
             for j, v in enumerate(coords):
                 v = self.flatten(Lin(v))
-                assert len(v) <= TLIN and v.L() <= LMAX and v.cmax() <= CMAX
+                assert len(v) <= TLIN and v.L() <= LMAX and v.cmax() <= CMAX and v.V() <= LIN_VMAX
                 n = self._node("lin", x=Lin(v), V=max(1, v.V()))
                 n.pin = (tid, d * ncoord + j)
                 nodes.append(n)
@@ -173,19 +175,22 @@ class Builder:
             (k, c), = x.items()
             if c == 1:
                 return Lin(x)
-        while len(x) > TLIN or x.L() > LMAX or x.cmax() > CMAX:
-            # too long / too large for one gather: materialise a chunk that satisfies the limits, keep the rest
-            chunk, rest, l = Lin(), Lin(), 0
+        while len(x) > TLIN or x.L() > LMAX or x.cmax() > CMAX or x.V() > LIN_VMAX:
+            # too long / too large (limbs or value) for one gather: materialise a chunk that satisfies the limits, keep the rest
+            chunk, rest, l, v = Lin(), Lin(), 0, 0
             for k, c in sorted(x.items(), key=lambda kc: -abs(kc[1])):
                 take = max(-CMAX, min(CMAX, c))
-                if len(chunk) < TLIN and l + abs(take) <= LMAX:
-                    chunk[k] = take; l += abs(take)
+                if abs(take) * k.V > LIN_VMAX - v:                     # the value bound of the chunk's gather: as much of this term as still fits
+                    take = (LIN_VMAX - v) // k.V * (1 if c > 0 else -1)
+                if take and len(chunk) < TLIN and l + abs(take) <= LMAX:
+                    chunk[k] = take; l += abs(take); v += abs(take) * k.V
                     if c != take:
                         rest[k] = c - take
                 else:
                     rest[k] = c
             assert chunk
             x = rest + self.lin(chunk)
+        assert x.V() <= LIN_VMAX
         red = force_reduce or x.V() > V_REDUCE_AT
         n = self._node("lin", x=Lin(x), V=3 if red else x.V())
         n.reduce = red
@@ -212,12 +217,12 @@ class Builder:
     def sqr3(self, x):
         """3 x^2 as a job of a SQR level: every lane of such a level runs the squaring core (120 + 240 multiply-adds instead of
         225 + 240, one operand gather); the factor 3 rides on the doubled operand (cross terms against 6x, diagonal against 3x),
-        which bounds the operand to L <= 3.  Only worth using where a whole level consists of squarings (the cyclotomic
-        squaring chains of the final exponentiation)."""
+        and 6x is formed in int32: 6 L (2^27 + 64) < 2^31 bounds the operand to L <= 2, |limb| <= 2 (2^27 + 64).  Only worth using
+        where a whole level consists of squarings (the cyclotomic squaring chains of the final exponentiation)."""
         if not x:
             return Lin()
         x = self.fit(x, TMAX)
-        while x.L() > 3 or 3 * x.V() * x.V() > VPROD_MAX:
+        while x.L() > SQR_LMAX or 3 * x.V() * x.V() > VPROD_MAX:
             x = self.lin(x, force_reduce=x.V() > 1600)
         return Lin({self._node("sqr3", x=x, V=2): 1})
 
@@ -1213,6 +1218,139 @@ def build_hash_program(b, T, kind):
     return b
 
 
+# ---- unit programs (tests only) ---------------------------------------------------------------------------------------------
+# One job kind each, at the bounds the Builder admits -- the shipped programs stay well inside them, and real curve data never puts every
+# limb at its bound (tests/test_lat_units_cpu.py, tests/test_gpu_lat_units.py).  Inputs: raw device-representation elements (BUF_RAW3: 15 int32 limbs each, taken as they are; the contract of an
+# `in` node: |limb| <= 2^27 + 64, |value| <= q).  Outputs: 'outraw12' -- the limbs as the kernel left them -- or a verdict.  They are
+# appended to the image AFTER the shipped programs (main), so no shipped program moves; blsmi_debug_lat_unit runs them.
+UNIT_PROGRAMS = ("unit_mul0", "unit_mul1", "unit_mul2", "unit_mulv", "unit_sqr", "unit_lin4", "unit_lin4r", "unit_linv", "unit_linmix", "unit_lin2", "unit_lin1",
+                 "unit_inv", "unit_check1", "unit_iszero")
+
+
+def _comb(nodes, coefs, first=0):
+    """sum_i coefs[i] * nodes[(first + i) % len(nodes)]"""
+    r = Lin()
+    for i, c in enumerate(coefs):
+        r = r + nodes[(first + i) % len(nodes)].scale(c)
+    return r
+
+
+def _split15(c):
+    """c and what is left of L = 15 with the other sign: (c,) for |c| = 15, else (c, -+(15 - |c|))"""
+    return (c,) if abs(c) == 15 else (c, (abs(c) - 15) if c > 0 else (15 - abs(c)))
+
+
+def unit_mul_jobs():
+    """(x coefficients, y coefficients) of the MUL unit jobs: every (La, Lb) the tests name -- La * Lb = 33 included --, 7-term gathers on
+    either side (7 terms on BOTH sides of one job would need La * Lb >= 49), every coefficient -15 .. 15, mixed signs inside a gather"""
+    alt = lambda n: [1 if i % 2 == 0 else -1 for i in range(n)]
+    jobs = [([1], [1]), ([-1], [1]), ([1], [3, -2, 2, -2, 2, -2, 2])]
+    ysmall = ([1, -1], [2], [-2], [-1, -1])
+    for i, c in enumerate((15, -14, 13, -12, 11, -10, 9, -8)):                   # (15, 2): the big coefficients on the x side
+        jobs.append((list(_split15(c)), ysmall[i % 4]))
+    for i, c in enumerate((-15, 14, -13, 12, -11, 10, -9, 8)):                   # (2, 15): ... on the y side
+        jobs.append((ysmall[(i + 1) % 4], list(_split15(c))))
+    jobs += [([1, -1, 1], [2, -2, 2, -2, 1, -1, 1]), ([5, -6], [3]), ([3, -3, 2, -2, 1], [-1, 1, -1]),       # (3, 11), (11, 3) twice
+             ([1, 1, 1, 1], [2, -1, 1, -1, 1, -1, 1]), ([-8], [2, -2]), ([-2, 1, -1, 1, -1, 1, -1], [-1, -1, -1, -1]),   # (4, 8), (8, 4) twice
+             ([1, -1, 1, -1, 1], [1, 1, 1, 1, 1, 1]),                                                         # (5, 6)
+             (alt(7), alt(4)), ([-c for c in alt(4)], alt(7)), ([3, 2, 2, 2, 2, 2, 2], [1, 1])]               # 7 x 4, 4 x 7 terms, 7 terms of L = 15
+    return jobs
+
+
+def _chain(b, a, v=512, s=1):
+    """un-reduced LIN jobs on top of each other, from the input a to a node of value bound v: 15 a, 15 (15 a), 2 (225 a) + ..."""
+    n1 = b.lin(a.scale(15 * s)); n2 = b.lin(n1.scale(15))
+    rest = {512: (4, 2), 496: (3, 1)}[v]
+    return b.lin(n2.scale(2) + n1.scale(rest[0]) + a.scale(rest[1] * s)), n2, n1
+
+
+def _spread15(nt, j):
+    """nt coefficients with sum |c| = 15, signs alternating from (-1)^j"""
+    mag = [15 // nt + (1 if i < 15 % nt else 0) for i in range(nt)]
+    return [m if (i + j) % 2 == 0 else -m for i, m in enumerate(mag)]
+
+
+def build_unit_program(name):
+    b = Builder()
+    b.noflatten = True                                                         # a chain of LIN jobs stays a chain
+    raw = lambda n: [b.inp(BUF_RAW3, e) for e in range(n)]
+    if name in ("unit_mul0", "unit_mul1", "unit_mul2"):
+        # x operands over inputs 0..7, y operands over inputs 8..15; one MUL level per program, every product leaves
+        inp = raw(16)
+        jobs = unit_mul_jobs()
+        k = int(name[-1])
+        outs = [b.mul(_comb(inp[:8], cx, j), _comb(inp[8:], cy, 3 * j)) for j, (cx, cy) in enumerate(jobs) if j % 3 == k]
+    elif name == "unit_mulv":
+        # products at the value bound: operands are sums of un-reduced LIN results of value bound 512 / 496 (chains from the inputs)
+        inp = raw(16)
+        X = [_chain(b, a, 512, -1 if i == 5 else 1)[0] for i, a in enumerate(inp[:8])]
+        Y = [_chain(b, a, 512, -1 if i == 6 else 1)[0] for i, a in enumerate(inp[8:])]
+        Xs = [_chain(b, a, 496)[0] for a in inp[:7]]
+        Ys = [_chain(b, a, 496)[0] for a in inp[8:15]]
+        s11 = [2, 2, 2, 2, 1, 1, 1]
+        outs = [b.mul(_comb(X, [1, 1, 1, 1]), _comb(Y, [1] * 5 + [3])),                                    # (4, 8): Vx Vy = 2048 * 4096 = VPROD_MAX
+                b.mul(_comb(X, [2, -2], 4), _comb(Y, [2, -2, 2, -2])),
+                b.mul(_comb(X, [1, -1, 1, -1, 1, -1, 2]), _comb(Y, [-1, -1, -1, -1], 4)),                  # (8, 4)
+                b.mul(_comb(X, [-4, -4], 2), _comb(Y, [4], 7)),
+                b.mul(_comb(X, [1, 1, 1], 5), _comb(Ys, s11)),                                              # (3, 11): 1536 * 5456 = 0.999 VPROD_MAX, La * Lb = 33
+                b.mul(_comb(X, [-1, 1, -1]), _comb(Ys, [-c if i % 2 else c for i, c in enumerate(s11)], 3)),
+                b.mul(_comb(Xs, s11, 2), _comb(Y, [1, 1, 1], 1)),                                           # (11, 3)
+                b.mul(_comb(Xs, [-c for c in s11]), _comb(Y, [3], 2))]
+    elif name == "unit_sqr":
+        inp = raw(8)
+        N = [_chain(b, a, 512, -1 if i == 3 else 1)[0] for i, a in enumerate(inp[:7])]
+        outs = [b.sqr3(_comb(inp, c, j)) for j, c in enumerate(([1], [-1], [2], [-2], [1, 1], [1, -1], [-1, -1], [-1, 1]))]
+        outs += [b.sqr3(N[0].scale(2)), b.sqr3(N[1] + N[2]), b.sqr3(-N[3] - N[4]), b.sqr3(N[5] - N[6])]      # V = 1024: the most L <= 2 admits
+    elif name == "unit_lin4":
+        # un-reduced, at most 16 jobs a level (four lanes per job): every result leaves
+        inp = raw(16)
+        outs = [b.lin(_comb(inp, [2] + [1] * 13)), b.lin(_comb(inp, [-1 if i % 2 else 1 for i in range(13)] + [-2], 1)), b.lin(_comb(inp, [-1] * 13 + [-2], 2)),
+                b.lin(_comb(inp, [-15], 15)), b.lin(_comb(inp, [8, -7], 3)), b.lin(_comb(inp, [1, 1], 5)), b.lin(_comb(inp, _spread15(5, 0), 7)),
+                b.lin(_comb(inp, _spread15(7, 1), 9)), b.lin(_comb(inp, _spread15(8, 0), 11))]
+        n3, n2, n1 = _chain(b, inp[0], 512)
+        m3, _, _ = _chain(b, inp[1], 512, -1)
+        outs += [n2, n3, m3]                                                     # value bounds 225, V_REDUCE_AT, V_REDUCE_AT
+    elif name == "unit_lin4r":
+        # value-reduced, at most 16 jobs a level
+        inp = raw(16)
+        red = lambda x: b.lin(x, True)
+        outs = [red(_comb(inp, [2] + [1] * 13)), red(_comb(inp, [1 if i % 2 else -1 for i in range(13)] + [2], 1)), red(_comb(inp, [-1] * 13 + [-2], 2)),
+                red(_comb(inp, [-15], 15)), red(_comb(inp, [1], 14)), red(_comb(inp, [15], 13)), red(_comb(inp, [-1], 12))]
+        outs += [red(_comb(inp, _spread15(nt, nt), 2 * nt)) for nt in (2, 4, 6, 9, 12)]
+    elif name == "unit_linv":
+        # value-reduced gathers at the value bound LIN_VMAX, over un-reduced chains (whose levels hold no reduced job: the flag is level-wide)
+        inp = raw(8)
+        ch = [_chain(b, a, 512, -1 if i == 2 else 1) for i, a in enumerate(inp)]
+        N = [c[0] for c in ch]
+        red = lambda x: b.lin(x, True)
+        outs = [red(_comb(N, [1] * 8)), red(_comb(N, [1, -1] * 4)), red(N[0].scale(8)), red(N[1].scale(-8)),
+                red(_comb(N, [1] * 7, 1) + ch[0][1].scale(2) + ch[0][2].scale(4) + inp[0].scale(2)),          # 10 terms, L = 15, V = 4096
+                red(_comb(N, [-1] * 8))]
+    elif name == "unit_linmix":
+        # one level whose jobs ask for the value reduction and do not, in turn: the flag is level-wide
+        inp = raw(16)
+        outs = [b.lin(_comb(inp, _spread15(1 + (5 * j) % 14, j), j), force_reduce=j % 2 == 0) for j in range(12)]
+    elif name in ("unit_lin2", "unit_lin1"):
+        # a wide un-reduced level (17..32 jobs: two lanes per job; more than 32: one), a reduced level as wide on top of it, then the sums that leave
+        inp = raw(16)
+        w, per = (24, 2) if name == "unit_lin2" else (40, 4)
+        sweep = [c for m in range(15, 0, -1) for c in ((m, -m) if m % 2 else (-m, m))]                       # every coefficient once
+        l1 = [b.lin(_comb(inp, list(_split15(sweep[j])) if j < len(sweep) and name == "unit_lin1" else _spread15(1 + (3 * j) % 14, j), j)) for j in range(w)]
+        l2 = [b.lin(_comb(l1, [1, -2, 3, -4, 5] if j % 2 else [-5, 4, -3, 2, -1], j), True) for j in range(w)]
+        outs = [b.lin(_comb(l2, list(range(1, per + 1)), per * k), True) for k in range(12)]
+    elif name == "unit_inv":
+        inp = raw(5)
+        outs = [b.inv(b.lin(inp[0], True)), b.inv(inp[1] + inp[2]), b.inv(b.lin(-inp[3], True)), b.inv(b.lin(inp[4].scale(15), True))]
+    elif name in ("unit_check1", "unit_iszero"):
+        outs = [b.lin(a, True) for a in raw(12)]
+        b.out = ("check1", outs) if name == "unit_check1" else ("iszero", outs, len(outs))
+        return b
+    else:
+        raise KeyError(name)
+    b.out = ("outraw12", outs)
+    return b
+
+
 # ---- levelling, slot allocation ---------------------------------------------------------------------------------------
 class Program:
     pass
@@ -1361,6 +1499,7 @@ def schedule(b):
     p.nout = b.out[2] if len(b.out) > 2 else len(out_nodes)
     p.table_base = table_base
     p.table_ncoord = {tid: nc for tid, (nc, _) in enumerate(getattr(b, "tables", []))}
+    p.inputs = [n for n in b.inputs if n.id in live]
     return p
 
 
@@ -1521,16 +1660,24 @@ def stats(p):
         len(p.levels), c[K_MUL], c[K_SQR], c[K_LIN], c[K_INV], c[K_LOAD], jobs[K_MUL], jobs[K_LIN], p.nslot, len(p.consts))
 
 
+SHIPPED_PROGRAMS = ("verify2", "verify1s", "pairing1", "pairing1s", "aggtail", "aggtail2", "finalexp1", "miller1raw", "miller1rawn", "miller1x", "hashfin1", "hashfin2", "cofac2",
+                    "subgrp1", "subgrp2", "msmfin1", "msmfin2", "mul1", "mul2", "mul12raw", "powc12raw", "sum0_1", "sum0_2", "sum1_1", "sum1_2", "sumfin_1", "sumfin_2")
+
+
 def main():
     import pathlib
     here = pathlib.Path(__file__).resolve().parent
     sys.setrecursionlimit(100000)
     out = bytearray()
     index = []
-    for name in ("verify2", "verify1s", "pairing1", "pairing1s", "aggtail", "aggtail2", "finalexp1", "miller1raw", "miller1rawn", "miller1x", "hashfin1", "hashfin2", "cofac2", "subgrp1", "subgrp2", "msmfin1", "msmfin2", "mul1", "mul2", "mul12raw", "powc12raw", "sum0_1", "sum0_2", "sum1_1", "sum1_2", "sumfin_1", "sumfin_2"):
-        p = schedule(build_program(name))
+    units = []
+    for name in SHIPPED_PROGRAMS + UNIT_PROGRAMS:                           # the unit programs LAST: every shipped program keeps its offset and bytes
+        unit = name in UNIT_PROGRAMS
+        p = schedule(build_unit_program(name) if unit else build_program(name))
         blob = encode(p)
         index.append((name, len(out), len(blob)))
+        if unit:
+            units.append((len(out), len(p.inputs), p.nout if p.out == "outraw12" else 0))
         out += blob
         while len(out) % 256:
             out += b"\0"
@@ -1543,6 +1690,8 @@ def main():
         for name, off, ln in index:
             f.write("#define LAT_%s_OFFSET %d\n#define LAT_%s_BYTES %d\n" % (name.upper(), off, name.upper(), ln))
         f.write("#define LAT_TOTAL_BYTES %d\n" % len(out))
+        # blsmi_debug_lat_unit: {offset, input elements, output elements (0: the program leaves a verdict byte)} of unit program `which`
+        f.write("#define LAT_UNIT_COUNT %d\n#define LAT_UNIT_TABLE { %s }\n" % (len(units), ", ".join("{ %d, %d, %d }" % u for u in units)))
 
 
 if __name__ == "__main__":

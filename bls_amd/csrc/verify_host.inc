@@ -1202,6 +1202,25 @@ BLSMI_API int blsmi_debug_hash_tail(int kind, const uint8_t* pts, uint8_t* out, 
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
+// One launch of a unit program of the latency path (gen_lat.py: UNIT_PROGRAMS, appended to the image after the shipped programs): raw
+// device-representation elements in, the limbs as the kernel left them (or a verdict byte) out.  n tuples of nin elements, one wave each.
+BLSMI_API int blsmi_debug_lat_unit(int which, const int32_t* in_raw, size_t nin, size_t n, int32_t* out_raw, uint8_t* ok) {
+    static const struct { size_t offset, nin, nout; } units[LAT_UNIT_COUNT] = LAT_UNIT_TABLE;      // nout 0: a verdict program (check1 / iszero)
+    if (which < 0 || which >= LAT_UNIT_COUNT || nin != units[which].nin || n == 0 || n > 4096 || !in_raw) return BLSMI_E_ARG;
+    const size_t prog = units[which].offset, nout = units[which].nout;
+    if (nout ? !out_raw : !ok) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    DBuf din, dout, dok;
+    HIPCHK(din.alloc(n * nin * 60)); HIPCHK(dout.alloc(std::max<size_t>(nout, 1) * 60 * n)); HIPCHK(dok.alloc(n));
+    HIPCHK(hipMemcpyAsync(din.p, in_raw, n * nin * 60, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dok.p, 0, n, g_stream));
+    launch_lat(prog, g_stream, {.b3 = {din.p, nin * 60}, .ok = dok.p, .out = dout.p}, n);
+    HIPCHK(hipGetLastError());
+    if (nout) { HIPCHK(hipMemcpyAsync(out_raw, dout.p, nout * 60 * n, hipMemcpyDeviceToHost, g_stream)); }
+    if (ok) { HIPCHK(hipMemcpyAsync(ok, dok.p, n, hipMemcpyDeviceToHost, g_stream)); }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
 // the throughput tail of HashG1 (k_hash_g1_finish: sum of the two mapped points, 11-isogeny, cofactor clearing when clear != 0) on caller-chosen
 // mapped points, and the flag a large aggregate's uncleared path raises when a message's two points cancel (*special bit 1; hash.cuh: swu_finish_g1)
 BLSMI_API int blsmi_debug_hash_g1_finish(const uint8_t* pts, int clear, uint8_t* out, int* special, size_t n) {

@@ -756,6 +756,19 @@ def debug_hash_redo(kind, msgs, good, out, domain8=None):
     return o
 
 
+def debug_lat_unit(which, in_raw, nout):
+    """one launch of unit program `which` of the latency path (gen_lat.py: UNIT_PROGRAMS) on (n, nin, 15) int32 raw limbs ->
+    (the nout results as the kernel left them, (n, nout, 15) int32; the verdict bytes (n,) uint8).  nout = 0: a verdict program"""
+    a = np.ascontiguousarray(in_raw, dtype=np.int32)
+    n, nin, nl = a.shape
+    assert nl == 15
+    out = np.zeros((nout, 15, n), dtype=np.int32)                    # as K_OUTRAW12 writes them: structure of arrays over the tuples
+    ok = np.zeros(n, dtype=np.uint8)
+    i32p = C.POINTER(C.c_int32)
+    _check(_lib().blsmi_debug_lat_unit(C.c_int(which), a.ctypes.data_as(i32p), C.c_size_t(nin), C.c_size_t(n), out.ctypes.data_as(i32p) if nout else None, _p8(ok)), "blsmi_debug_lat_unit")
+    return np.ascontiguousarray(out.transpose(2, 0, 1)), ok
+
+
 LANE_QUAD = 0x200          # BLSMI_OP_LANE_QUAD
 LANE_ROW = 0x400           # BLSMI_OP_LANE_ROW
 

@@ -667,6 +667,13 @@ int blsmi_debug_hash_tail(int kind, const uint8_t *pts, uint8_t *out, uint8_t *g
  * back to the cleared one. */
 int blsmi_debug_hash_g1_finish(const uint8_t *pts /* n*192 */, int clear /* 2: the four-lanes-per-message tail + its redo pass; *special = messages redone */, uint8_t *out /* n*96 */, int *special, size_t n);
 int blsmi_debug_hash_redo(int kind, const uint8_t *msgs, const uint64_t *off_or_domain, const uint8_t *good, uint8_t *out /* in/out */, size_t n);
+/* One launch of unit program `which` of the latency path (bls_amd/csrc/gen_lat.py: UNIT_PROGRAMS, in that order): single job kinds at the
+ * bounds the program generator admits, for the parity tests.  in_raw: n tuples of nin field elements in the device representation, 15 int32
+ * limbs each, taken as they are (|limb| <= 2^27 + 64, |value| <= q), array of structures; one wave per tuple.  out_raw: the program's nout
+ * results as the kernel left them, limb j of result e of tuple t at ((e * 15) + j) * n + t; ok: the n verdict bytes of the two verdict
+ * programs (which write no out_raw; either pointer may be NULL where the program does not write it).  BLSMI_E_ARG for an unknown `which`,
+ * an nin that is not the program's, n == 0 or n > 4096. */
+int blsmi_debug_lat_unit(int which, const int32_t *in_raw /* n*nin*15 */, size_t nin, size_t n, int32_t *out_raw /* nout*15*n */, uint8_t *ok /* n */);
 
 /* ---- committees (blsmi 0.9) ----------------------------------------------------------------------------------------------------------
  * Segmented sums: m sums over ragged, index-addressed subsets of one table of npk points.  Segment j is

@@ -52,6 +52,10 @@ def test_duplicate_argument_checks(lib):
     assert lib.blsmi_pairing_batch(None, None, None, ctypes.c_size_t(1)) == -3
     ok = ctypes.c_int(7)
     assert lib.blsmi_g2pubs_verify_aggregate(None, None, None, None, ctypes.c_size_t(0), ctypes.byref(ok)) == -3
+    # blsmi_debug_lat_unit: an unknown program, an input count that is not the program's, n == 0
+    buf = (ctypes.c_int32 * (16 * 15))()
+    for which, nin, n in ((-1, 16, 1), (1000, 16, 1), (0, 15, 1), (0, 16, 0)):
+        assert lib.blsmi_debug_lat_unit(which, buf, ctypes.c_size_t(nin), ctypes.c_size_t(n), buf, None) == -3
 
 
 def test_header_is_plain_c():

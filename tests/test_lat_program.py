@@ -259,8 +259,21 @@ def test_scalar_multiplication_programs():
                 assert out[:2] == [want[0], want[1]] and out[2]
 
 
-def test_program_bounds_and_shape(progs):
-    for name, p in progs.items():
+@pytest.fixture(scope="module")
+def all_progs(progs):
+    """every shipped program and every unit program (tests/test_lat_units_cpu.py), scheduled"""
+    out = dict(progs)
+    for k in G.SHIPPED_PROGRAMS:
+        if k not in out:
+            out[k] = G.schedule(G.build_program(k))
+    for k in G.UNIT_PROGRAMS:
+        out[k] = G.schedule(G.build_unit_program(k))
+    return out
+
+
+def test_program_bounds_and_shape(all_progs):
+    assert len(all_progs) == len(G.SHIPPED_PROGRAMS) + len(G.UNIT_PROGRAMS)
+    for name, p in all_progs.items():
         assert p.nslot < 1024
         for kind, jobs in p.levels:
             assert len(jobs) <= (1 if kind == G.K_INV else G.LANES)
@@ -271,6 +284,14 @@ def test_program_bounds_and_shape(progs):
                     assert n.x.cmax() <= G.CMAX and n.y.cmax() <= G.CMAX
                 elif n.kind == "lin":
                     assert len(n.x) <= G.TLIN and n.x.L() <= G.LMAX and n.x.cmax() <= G.CMAX
+                    assert n.x.V() <= G.LIN_VMAX == 4096                                   # k_lat.hip labels the gather Fp<LMAX, VMAX> (fp.cuh: VMAX = 2^12)
+                    assert n.reduce or n.pin or n.x.V() <= G.V_REDUCE_AT                            # an un-reduced result keeps the gather's value bound
+                elif n.kind == "sqr3":
+                    # lat_sqr3 forms 6x in int32: 6 L (2^27 + 64) < 2^31 only for L <= 2 (tests/lat_limb_model.py)
+                    assert len(n.x) <= G.TMAX and n.x.cmax() <= G.CMAX and n.x.L() <= G.SQR_LMAX == 2 and 3 * n.x.V() * n.x.V() <= G.VPROD_MAX
+                elif n.kind == "inv":
+                    (d, c), = n.x.items()                                                  # fp_inv of ONE stored value
+                    assert c == 1 and n.x.L() == 1 and n.x.V() <= G.LIN_VMAX
                 for lin in (n.x, n.y):
                     if lin:
                         assert all(d.level < n.level for d in lin)                  # operands come from earlier levels
