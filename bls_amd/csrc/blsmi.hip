@@ -304,6 +304,62 @@ inline LayoutKernels kernels_of(Layout l) {
 }
 // the exact-step Miller loop (MillerLoop: the reference's steps), which only the pair and the one-lane layout have
 inline Kernel<const u8*, const u8*, i32*, size_t> miller1_of(Layout l) { return l == Layout::pair ? KERNEL_OF(k_miller1_pair) : KERNEL_OF(k_miller1); }
+// The second table: what the host routines of the group operations need to know of G1 or G2.  Every kernel family below has a twin with the
+// same parameter list in either group (kernels.h); a routine takes a row and never asks which group it serves.
+// Laid: a kernel that has a lane-pair form, with the layout its grid is counted in -- the launch is tuple_blocks(e.layout, items).
+template <class K> struct Laid { K k; Layout layout; };
+struct GroupKernels {
+    int id;                             // 1 / 2: the `group` argument of k_affine_to_jac and k_glv_recode
+    size_t wire_bytes; int fq;          // the affine wire record (96 / 192 bytes; in memory: rec_bytes) and its Fq per Jacobian point (3 / 6)
+    size_t lat_sum0, lat_sum1, lat_sumfin, lat_mul, lat_subgrp, lat_msmfin;   // the group's level programs (k_lat.hip)
+    u8* Gens::*gen; i32* Gens::*fixed;  // the leased device's generator and its fixed-base table
+    int msm_shift; size_t msm_raw_words; // the bucket method over the endomorphisms (msm.inc): 2^3 / 2^2 bucket-windows, a point's words in raw limbs
+#define BLSMI_K(k) decltype(KERNEL_OF(k))
+    Laid<BLSMI_K(k_g1_mul)> mul, mul_glv; BLSMI_K(k_g1_mul_u64) mul_u64; BLSMI_K(k_g1_mul_fixed) mul_fixed, mul_fixed_wave;
+    BLSMI_K(k_g1_sum0) sum0; BLSMI_K(k_g1_sum0_jac) sum0_jac; BLSMI_K(k_g1_sum) sum; BLSMI_K(k_g1_sum_final) sum_final;
+    Laid<BLSMI_K(k_g1_segsum_chunk)> segsum_chunk; BLSMI_K(k_g1_segsum_chunk_jac) segsum_chunk_jac; BLSMI_K(k_g1_segsum_chunk_u64) segsum_chunk_u64;
+    Laid<BLSMI_K(k_g1_segsum_fold)> segsum_fold; BLSMI_K(k_g1_segsum_final) segsum_final;
+    BLSMI_K(k_g1_compress) compress; BLSMI_K(k_g1_decompress) decompress; BLSMI_K(k_g1_decompress_waves) decompress_waves; BLSMI_K(k_g1_jac_to_affine) jac_to_affine;
+    BLSMI_K(k_msm_recode_g1) msm_recode; BLSMI_K(k_msm_rawpts_g1) msm_rawpts; Laid<BLSMI_K(k_g1_msm_bucket)> msm_bucket; BLSMI_K(k_g1_msm_chunk) msm_chunk; BLSMI_K(k_g1_msm_fold) msm_fold; BLSMI_K(k_g1_msm_final) msm_final;
+    Laid<BLSMI_K(k_g1_msm_bucket_raw)> msm_bucket_raw; Laid<BLSMI_K(k_g1_msm_chunk2)> msm_chunk2; Laid<BLSMI_K(k_g1_msm_fold2)> msm_fold2; BLSMI_K(k_g1_msm_final2) msm_final2;
+#undef BLSMI_K
+};
+// The one place that decides which form of a kernel serves.  G1 has one lane per item throughout.  G2: `opt` families take the lane-pair
+// form when the options say so (pair_layout; BLSMI_LAYOUT=single: the one-lane kernel); `always` families exist in the lane-pair form
+// only and take it whatever the options say; every other family has one lane per item in both groups.  sum0_jac carries the name of sum0:
+// one profile name for level 0 of a sum, whatever form its points arrive in.
+inline GroupKernels group_row(int group, bool pair_forms) {
+    const auto one = [](auto k) { return Laid<decltype(k)>{k, Layout::single}; };
+    const auto always = [](auto k) { return Laid<decltype(k)>{k, Layout::pair}; };
+    const auto opt = [&](auto k, decltype(k) kpair) { return pair_forms ? always(kpair) : one(k); };
+    if (group == 1) return {
+        .id = 1, .wire_bytes = 96, .fq = 3, .lat_sum0 = LAT_SUM0_1_OFFSET, .lat_sum1 = LAT_SUM1_1_OFFSET, .lat_sumfin = LAT_SUMFIN_1_OFFSET, .lat_mul = LAT_MUL1_OFFSET, .lat_subgrp = LAT_SUBGRP1_OFFSET, .lat_msmfin = LAT_MSMFIN1_OFFSET,
+        .gen = &Gens::g1, .fixed = &Gens::fixed1, .msm_shift = 3, .msm_raw_words = 48,
+        .mul = one(KERNEL_OF(k_g1_mul)), .mul_glv = one(KERNEL_OF(k_g1_mul_glv)), .mul_u64 = KERNEL_OF(k_g1_mul_u64), .mul_fixed = KERNEL_OF(k_g1_mul_fixed), .mul_fixed_wave = KERNEL_OF(k_g1_mul_fixed_wave),
+        .sum0 = KERNEL_OF(k_g1_sum0), .sum0_jac = kernel_named(k_g1_sum0_jac, "k_g1_sum0"), .sum = KERNEL_OF(k_g1_sum), .sum_final = KERNEL_OF(k_g1_sum_final),
+        .segsum_chunk = one(KERNEL_OF(k_g1_segsum_chunk)), .segsum_chunk_jac = KERNEL_OF(k_g1_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g1_segsum_chunk_u64), .segsum_fold = one(KERNEL_OF(k_g1_segsum_fold)), .segsum_final = KERNEL_OF(k_g1_segsum_final),
+        .compress = KERNEL_OF(k_g1_compress), .decompress = KERNEL_OF(k_g1_decompress), .decompress_waves = KERNEL_OF(k_g1_decompress_waves), .jac_to_affine = KERNEL_OF(k_g1_jac_to_affine),
+        .msm_recode = KERNEL_OF(k_msm_recode_g1), .msm_rawpts = KERNEL_OF(k_msm_rawpts_g1), .msm_bucket = one(KERNEL_OF(k_g1_msm_bucket)), .msm_chunk = KERNEL_OF(k_g1_msm_chunk), .msm_fold = KERNEL_OF(k_g1_msm_fold), .msm_final = KERNEL_OF(k_g1_msm_final),
+        .msm_bucket_raw = one(KERNEL_OF(k_g1_msm_bucket_raw)), .msm_chunk2 = one(KERNEL_OF(k_g1_msm_chunk2)), .msm_fold2 = one(KERNEL_OF(k_g1_msm_fold2)), .msm_final2 = KERNEL_OF(k_g1_msm_final2)};
+    return {
+        .id = 2, .wire_bytes = 192, .fq = 6, .lat_sum0 = LAT_SUM0_2_OFFSET, .lat_sum1 = LAT_SUM1_2_OFFSET, .lat_sumfin = LAT_SUMFIN_2_OFFSET, .lat_mul = LAT_MUL2_OFFSET, .lat_subgrp = LAT_SUBGRP2_OFFSET, .lat_msmfin = LAT_MSMFIN2_OFFSET,
+        .gen = &Gens::g2, .fixed = &Gens::fixed2, .msm_shift = 2, .msm_raw_words = 244,
+        .mul = opt(KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_mul_pair)), .mul_glv = opt(KERNEL_OF(k_g2_mul_glv), KERNEL_OF(k_g2_mul_glv_pair)), .mul_u64 = KERNEL_OF(k_g2_mul_u64), .mul_fixed = KERNEL_OF(k_g2_mul_fixed), .mul_fixed_wave = KERNEL_OF(k_g2_mul_fixed_wave),
+        .sum0 = KERNEL_OF(k_g2_sum0), .sum0_jac = kernel_named(k_g2_sum0_jac, "k_g2_sum0"), .sum = KERNEL_OF(k_g2_sum), .sum_final = KERNEL_OF(k_g2_sum_final),
+        .segsum_chunk = always(KERNEL_OF(k_g2_segsum_chunk_pair)), .segsum_chunk_jac = KERNEL_OF(k_g2_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g2_segsum_chunk_u64), .segsum_fold = always(KERNEL_OF(k_g2_segsum_fold_pair)), .segsum_final = KERNEL_OF(k_g2_segsum_final),
+        .compress = KERNEL_OF(k_g2_compress), .decompress = KERNEL_OF(k_g2_decompress), .decompress_waves = KERNEL_OF(k_g2_decompress_waves), .jac_to_affine = KERNEL_OF(k_g2_jac_to_affine),
+        .msm_recode = KERNEL_OF(k_msm_recode_g2), .msm_rawpts = KERNEL_OF(k_msm_rawpts_g2), .msm_bucket = opt(KERNEL_OF(k_g2_msm_bucket), KERNEL_OF(k_g2_msm_bucket_pair)), .msm_chunk = KERNEL_OF(k_g2_msm_chunk), .msm_fold = KERNEL_OF(k_g2_msm_fold), .msm_final = KERNEL_OF(k_g2_msm_final),
+        .msm_bucket_raw = always(KERNEL_OF(k_g2_msm_bucket_raw_pair)), .msm_chunk2 = opt(KERNEL_OF(k_g2_msm_chunk2), KERNEL_OF(k_g2_msm_chunk2_pair)), .msm_fold2 = opt(KERNEL_OF(k_g2_msm_fold2), KERNEL_OF(k_g2_msm_fold2_pair)), .msm_final2 = KERNEL_OF(k_g2_msm_final2)};
+}
+// group: 1 / 2.  The rows are built once; the sizes, offsets and accessors of a group do not depend on pair_forms.
+inline const GroupKernels& group_kernels(int group, bool pair_forms) {
+    static const GroupKernels rows[2][2] = {{group_row(1, false), group_row(1, true)}, {group_row(2, false), group_row(2, true)}};
+    return rows[group - 1][pair_forms];
+}
+inline size_t wire_bytes_of(int group) { return group_kernels(group, false).wire_bytes; }   // for what an entry point does before its call has options
+// such a kernel on n items: as many workgroups as its layout needs for them
+template <class K, class... A> inline void launch_items(const Laid<K>& e, size_t n, hipStream_t s, A... args) { launch(e.k, tuple_blocks(e.layout, n), s, args...); }
+template <class K, class... A> inline void launch_items_quiet(const Laid<K>& e, size_t n, hipStream_t s, A... args) { launch_quiet(e.k, tuple_blocks(e.layout, n), s, args...); }
 int init_device(Device& d) {            // caller holds g_mu
     HIPCHK(hipSetDevice(d.id));
     hipMemPool_t pool;
@@ -336,10 +392,11 @@ int init_device(Device& d) {            // caller holds g_mu
             HIPCHK(hipMalloc((void**)&dsc, NE * 32)); HIPCHK(hipMalloc((void**)&wire, NE * 192)); HIPCHK(hipMalloc((void**)&inf, NE));
             HIPCHK(hipMemcpy(dsc, sc.data(), NE * 32, hipMemcpyHostToDevice));
             HIPCHK(hipMalloc((void**)&d.gens.fixed1, sizeof(i32) * NE * 2 * NL)); HIPCHK(hipMalloc((void**)&d.gens.fixed2, sizeof(i32) * NE * 4 * NL));
-            launch_quiet(KERNEL_OF(k_g1_mul_glv), nblocks(NE), nullptr, d.gens.g1, 0, dsc, wire, inf, NE);
-            launch_quiet(KERNEL_OF(k_fixed_table_from_wire), nblocks(NE * 2), nullptr, wire, 2, d.gens.fixed1, NE);
-            launch_quiet(KERNEL_OF(k_g2_mul_glv_pair), tuple_blocks(Layout::pair, NE), nullptr, d.gens.g2, 0, dsc, wire, inf, NE);
-            launch_quiet(KERNEL_OF(k_fixed_table_from_wire), nblocks(NE * 4), nullptr, wire, 4, d.gens.fixed2, NE);
+            for (int group = 1; group <= 2; group++) {                      // (G2: the lane-pair ladder, whatever BLSMI_LAYOUT says)
+                const GroupKernels& g = group_kernels(group, true);
+                launch_items_quiet(g.mul_glv, NE, nullptr, d.gens.*g.gen, 0, dsc, wire, inf, NE);
+                launch_quiet(KERNEL_OF(k_fixed_table_from_wire), nblocks(NE * (g.wire_bytes / 48)), nullptr, wire, g.wire_bytes / 48, d.gens.*g.fixed, NE);   // (/ 48: Fq of an affine point)
+            }
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
             (void)hipFree(dsc); (void)hipFree(wire); (void)hipFree(inf);
@@ -370,6 +427,7 @@ inline size_t call_load(size_t n) {
 }
 // The options of the call this thread serves: the snapshot CtxLease took (tuning_now)
 inline const Tuning& tune() { return tl_ctx->tune; }
+inline const GroupKernels& group_kernels(int group) { return group_kernels(group, tune().pair_layout); }   // ... and its row of a group
 // what the layout questions of a call of n tuples see of the other calls on its device (a crowded call registers its own tuples: call_load)
 inline size_t route_load(size_t n) { return crowded(n, tune()) ? call_load(n) : 0; }
 inline bool mul_subgroup() { return !tl_mul_any && tune().mul_subgroup; }
@@ -787,23 +845,22 @@ namespace {
 constexpr int FMT_PK_JAC = 1, FMT_SIG_JAC = 2, FMT_JAC = 3;
 inline size_t rec_bytes(size_t wire_bytes, bool jac) { return jac ? wire_bytes / 2 * 3 : wire_bytes; }
 // n in-memory records on the device -> n wire records (the all-zero record for z == 0) and, if asked, their infinity flags
-int jac_to_wire_dev(size_t wire_bytes, const void* d_jac, void* d_out, void* d_inf, size_t n, hipStream_t s) {
+int jac_to_wire_dev(const GroupKernels& g, const void* d_jac, void* d_out, void* d_inf, size_t n, hipStream_t s) {
     if (n == 0) return BLSMI_OK;
     const bool mark = tl_ctx && s == tl_ctx->stream;                       // (profile marks are events on the context's main stream)
-    const auto k = wire_bytes == 96 ? KERNEL_OF(k_g1_jac_to_affine) : KERNEL_OF(k_g2_jac_to_affine);
-    if (mark) prof_mark(k.name);
-    launch_quiet(k, nblocks(n), s, d_jac, d_out, d_inf, n);
+    if (mark) prof_mark(g.jac_to_affine.name);
+    launch_quiet(g.jac_to_affine, nblocks(n), s, d_jac, d_out, d_inf, n);
     if (mark) prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
 // host copy + conversion of n records of one group: `host` holds wire records (jac == false: plain copy into d_wire) or in-memory
 // records (copied into a temporary of the call, converted into d_wire); everything on s
-int upload_points(size_t wire_bytes, bool jac, const uint8_t* host, void* d_wire, size_t n, hipStream_t s) {
-    if (!jac) { HIPCHK(hipMemcpyAsync(d_wire, host, wire_bytes * n, hipMemcpyHostToDevice, s)); return BLSMI_OK; }
-    DBuf raw; HIPCHK(raw.alloc(rec_bytes(wire_bytes, true) * n));
-    HIPCHK(hipMemcpyAsync(raw.p, host, rec_bytes(wire_bytes, true) * n, hipMemcpyHostToDevice, s));
-    return jac_to_wire_dev(wire_bytes, raw.p, d_wire, nullptr, n, s);
+int upload_points(const GroupKernels& g, bool jac, const uint8_t* host, void* d_wire, size_t n, hipStream_t s) {
+    if (!jac) { HIPCHK(hipMemcpyAsync(d_wire, host, g.wire_bytes * n, hipMemcpyHostToDevice, s)); return BLSMI_OK; }
+    DBuf raw; HIPCHK(raw.alloc(rec_bytes(g.wire_bytes, true) * n));
+    HIPCHK(hipMemcpyAsync(raw.p, host, rec_bytes(g.wire_bytes, true) * n, hipMemcpyHostToDevice, s));
+    return jac_to_wire_dev(g, raw.p, d_wire, nullptr, n, s);
 }
 // Is ONE host-side in-memory record the point at infinity?  z.IsZero() (g1.go:287-289, g2.go:325-327), where a coordinate that is not
 // below q counts as 0 exactly as on the device (device_io.cuh: load_m384_checked).  No field arithmetic: a compare.
@@ -919,9 +976,9 @@ static int pairing_host(const uint8_t* g1, const uint8_t* g2, uint64_t* out, siz
         const size_t m = hi - lo;
         DBuf a, b, o;
         HIPCHK(a.alloc(96 * m)); HIPCHK(b.alloc(192 * m)); HIPCHK(o.alloc(576 * m));
-        int rc = upload_points(96, jac, g1 + rec_bytes(96, jac) * lo, a.p, m, g_stream);
+        int rc = upload_points(group_kernels(1), jac, g1 + rec_bytes(96, jac) * lo, a.p, m, g_stream);
         if (rc) return rc;
-        rc = upload_points(192, jac, g2 + rec_bytes(192, jac) * lo, b.p, m, g_stream);
+        rc = upload_points(group_kernels(2), jac, g2 + rec_bytes(192, jac) * lo, b.p, m, g_stream);
         if (rc) return rc;
         rc = pairing_dev(a.p, b.p, o.p, m, g_stream, mode, pairing_layout(mode, m, tune(), route_load(m)));
         if (rc) return rc;
@@ -944,33 +1001,33 @@ BLSMI_API int blsmi_pairing_batch_jac_dev(const void* d_g1_jac, const void* d_g2
     UseStream us(stream);
     DBuf a, b;
     HIPCHK(a.alloc(96 * n)); HIPCHK(b.alloc(192 * n));
-    int rc = jac_to_wire_dev(96, d_g1_jac, a.p, nullptr, n, g_stream);
-    if (!rc) rc = jac_to_wire_dev(192, d_g2_jac, b.p, nullptr, n, g_stream);
+    int rc = jac_to_wire_dev(group_kernels(1), d_g1_jac, a.p, nullptr, n, g_stream);
+    if (!rc) rc = jac_to_wire_dev(group_kernels(2), d_g2_jac, b.p, nullptr, n, g_stream);
     if (rc) return rc;
     return pairing_dev(a.p, b.p, d_out, n, g_stream, 0, pairing_layout(0, n, tune(), route_load(n)));
 }
 // G?Projective.ToAffine().SerializeBytes() (g1.go:322-340 + 157-167, g2.go:365-386 + 172-186) for n points: wire records (all zero for
 // the point at infinity) and the infinity flags
-template <int PB>
-static int jac_to_affine_host(const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) {
+static int jac_to_affine_host(int group, const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) {
     if (n && (!jac || !out)) return BLSMI_E_ARG;
     if (n == 0) return BLSMI_OK;
     { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
     return run_shards(plan_shards(n, 64), [&](int, size_t lo, size_t hi) -> int {
-        const size_t m = hi - lo, in = rec_bytes(PB, true);
+        const GroupKernels& g = group_kernels(group);
+        const size_t m = hi - lo, PB = g.wire_bytes, in = rec_bytes(PB, true);
         DBuf raw, o, fl;
-        HIPCHK(raw.alloc(in * m)); HIPCHK(o.alloc((size_t)PB * m)); HIPCHK(fl.alloc(m));
+        HIPCHK(raw.alloc(in * m)); HIPCHK(o.alloc(PB * m)); HIPCHK(fl.alloc(m));
         HIPCHK(hipMemcpyAsync(raw.p, reinterpret_cast<const uint8_t*>(jac) + in * lo, in * m, hipMemcpyHostToDevice, g_stream));
-        int rc = jac_to_wire_dev(PB, raw.p, o.p, fl.p, m, g_stream);
+        int rc = jac_to_wire_dev(g, raw.p, o.p, fl.p, m, g_stream);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(out + (size_t)PB * lo, o.p, (size_t)PB * m, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(out + PB * lo, o.p, PB * m, hipMemcpyDeviceToHost, g_stream));
         if (out_inf) HIPCHK(hipMemcpyAsync(out_inf + lo, fl.p, m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
         return BLSMI_OK;
     });
 }
-BLSMI_API int blsmi_g1_jac_to_affine_batch(const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) { return jac_to_affine_host<96>(jac, out, out_inf, n); }
-BLSMI_API int blsmi_g2_jac_to_affine_batch(const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) { return jac_to_affine_host<192>(jac, out, out_inf, n); }
+BLSMI_API int blsmi_g1_jac_to_affine_batch(const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) { return jac_to_affine_host(1, jac, out, out_inf, n); }
+BLSMI_API int blsmi_g2_jac_to_affine_batch(const uint64_t* jac, uint8_t* out, uint8_t* out_inf, size_t n) { return jac_to_affine_host(2, jac, out, out_inf, n); }
 BLSMI_API int blsmi_final_exponentiation_batch(const uint64_t* in, uint64_t* out, size_t n) {
     if (n && (!in || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
@@ -1062,131 +1119,109 @@ BLSMI_API int blsmi_debug_g2_prepare(const uint8_t* g2_aff, int mode, uint64_t* 
 // ---- scalar multiplication / sums ----------------------------------------------------------------
 // d_pts == nullptr: every scalar multiplies the group generator (PrivToPub, g2pubs/bls.go:138-140, g1pubs/bls.go:144-146).
 // Everything on the device of the leased context; enqueues on s, no synchronisation.
-template <int PB, class K>
-static int mul_dev_core(K kernel, const u8* d_pts, int gen_group, const u8* d_scalars, u8* d_out, u8* d_inf, size_t m, hipStream_t s) {
-    const u8* d_gen = gen_group == 1 ? g_gens.g1 : g_gens.g2;            // the leased device's copy of the generator
-    const u8* base = d_pts ? d_pts : d_gen;
-    const size_t stride = d_pts ? (size_t)PB : 0;
+static int mul_dev_core(const GroupKernels& g, const u8* d_pts, const u8* d_scalars, u8* d_out, u8* d_inf, size_t m, hipStream_t s) {
     if (!d_pts) {
         // the generator as the common multiplicand (PrivToPub): the device's fixed-base table -- 32 mixed additions, no doublings.
         // Small calls: one scalar per wave (the 32 table entries meet in a tree of additions across the lanes).
-        const i32* table = PB == 96 ? g_gens.fixed1 : g_gens.fixed2;
-        if (m <= tune().fixed_wave_max && m <= tune().lat_max) {
-            if (PB == 96) launch(KERNEL_OF(k_g1_mul_fixed_wave), m, s, table, d_scalars, d_out, d_inf, m);
-            else launch(KERNEL_OF(k_g2_mul_fixed_wave), m, s, table, d_scalars, d_out, d_inf, m);
-        } else {
-            if (PB == 96) launch(KERNEL_OF(k_g1_mul_fixed), nblocks(m), s, table, d_scalars, d_out, d_inf, m);
-            else launch(KERNEL_OF(k_g2_mul_fixed), nblocks(m), s, table, d_scalars, d_out, d_inf, m);
-        }
+        const i32* table = g_gens.*g.fixed;
+        if (m <= tune().fixed_wave_max && m <= tune().lat_max) launch(g.mul_fixed_wave, m, s, table, d_scalars, d_out, d_inf, m);
+        else launch(g.mul_fixed, nblocks(m), s, table, d_scalars, d_out, d_inf, m);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;
     }
+    const size_t stride = g.wire_bytes;
     if (m <= tune().lat_max && mul_subgroup()) { // small call: one multiplication per wave (k_lat.hip, SEL levels over the decomposed scalar)
-        const size_t prog = PB == 96 ? LAT_MUL1_OFFSET : LAT_MUL2_OFFSET;
         DBuf good, rec; HIPCHK(good.alloc(m, s)); HIPCHK(rec.alloc(64 * m, s));
-        launch_quiet(KERNEL_OF(k_glv_recode), nblocks(m), s, d_scalars, PB == 96 ? 1 : 2, rec.p, m);
-        launch_lat_marked(prog, s, {.b0 = {base, stride}, .b1 = {rec.p, 64}, .ok = good.p, .out = d_out}, m);
+        launch_quiet(KERNEL_OF(k_glv_recode), nblocks(m), s, d_scalars, g.id, rec.p, m);
+        launch_lat_marked(g.lat_mul, s, {.b0 = {d_pts, stride}, .b1 = {rec.p, 64}, .ok = good.p, .out = d_out}, m);
         prof_mark(nullptr);
-        launch_quiet(KERNEL_OF(k_mul_finish), nblocks(m), s, good.p, base, stride, PB / 4, d_out, d_inf, m);
+        launch_quiet(KERNEL_OF(k_mul_finish), nblocks(m), s, good.p, d_pts, stride, g.wire_bytes / 4, d_out, d_inf, m);
         HIPCHK(hipGetLastError());
         return BLSMI_OK;                                                   // `good` is released in stream order
     }
     // points of the prime-order subgroup (the default): the ladder through the curve endomorphisms (glv.cuh) -- half / a quarter
     // of the doublings; arbitrary curve points (blsmi_set_mul_assume_subgroup(0)): the plain fixed-window ladder
-    const bool glv = mul_subgroup();
-    if (glv) {
-        if (PB == 192 && tune().pair_layout) launch(KERNEL_OF(k_g2_mul_glv_pair), tuple_blocks(Layout::pair, m), s, base, stride, d_scalars, d_out, d_inf, m);
-        else if (PB == 192) launch(KERNEL_OF(k_g2_mul_glv), nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
-        else launch(KERNEL_OF(k_g1_mul_glv), nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
-        prof_mark(nullptr);
-        HIPCHK(hipGetLastError());
-        return BLSMI_OK;
-    }
-    if (PB == 192 && tune().pair_layout)                                   // G2: lane-pair kernel, two waves per SIMD
-        launch(KERNEL_OF(k_g2_mul_pair), tuple_blocks(Layout::pair, m), s, base, stride, d_scalars, d_out, d_inf, m);
-    else
-        launch(kernel, nblocks(m), s, base, stride, d_scalars, d_out, d_inf, m);
+    launch_items(mul_subgroup() ? g.mul_glv : g.mul, m, s, d_pts, stride, d_scalars, d_out, d_inf, m);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
-template <int PB, class K>
-static int mul_batch(K kernel, const uint8_t* pts, int gen_group, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, bool any_point = false, uint64_t* out_jac = nullptr) {
+// gen: the group generator is the multiplicand (pts == nullptr)
+static int mul_batch(int group, const uint8_t* pts, bool gen, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, bool any_point = false, uint64_t* out_jac = nullptr) {
     // out_jac (replaces out / out_inf): the results as in-memory Jacobian records with z = 1, (0, 1, 0) for the point at infinity
-    if (n && ((!pts && !gen_group) || !scalars || (out_jac ? false : (!out || !out_inf)))) return BLSMI_E_ARG;
+    if (n && ((!pts && !gen) || !scalars || (out_jac ? false : (!out || !out_inf)))) return BLSMI_E_ARG;
     if (n == 0) return BLSMI_OK;
     { std::lock_guard<std::mutex> lk(g_mu); int rc = ensure_init_default(); if (rc) return rc; }
     // independent multiplications: large host-buffer batches are split by contiguous block like a verify batch (devices,
     // logical shards): each block has its own host thread and stream, so one block's copies run beside another's kernel
     return run_shards(plan_shards(n, 64), [&](int, size_t lo, size_t hi) -> int {
-        const size_t m = hi - lo;
+        const GroupKernels& g = group_kernels(group);
+        const size_t m = hi - lo, PB = g.wire_bytes;
         MulAny any_guard(any_point);                                       // shards run on their own threads
         DBuf dp, ds, dout, dinf;
-        HIPCHK(ds.alloc(32 * m)); HIPCHK(dout.alloc((size_t)PB * m)); HIPCHK(dinf.alloc(m));
-        if (pts) { HIPCHK(dp.alloc((size_t)PB * m)); HIPCHK(hipMemcpyAsync(dp.p, pts + (size_t)PB * lo, (size_t)PB * m, hipMemcpyHostToDevice, g_stream)); }
+        HIPCHK(ds.alloc(32 * m)); HIPCHK(dout.alloc(PB * m)); HIPCHK(dinf.alloc(m));
+        if (pts) { HIPCHK(dp.alloc(PB * m)); HIPCHK(hipMemcpyAsync(dp.p, pts + PB * lo, PB * m, hipMemcpyHostToDevice, g_stream)); }
         HIPCHK(hipMemcpyAsync(ds.p, scalars + 32 * lo, 32 * m, hipMemcpyHostToDevice, g_stream));
-        int rc = mul_dev_core<PB>(kernel, pts ? dp.as<u8>() : nullptr, gen_group, ds.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
+        int rc = mul_dev_core(g, pts ? dp.as<u8>() : nullptr, ds.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
         if (rc) return rc;
         if (out_jac) {
             const size_t jb = rec_bytes(PB, true);
             DBuf dj; HIPCHK(dj.alloc(jb * m));
-            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, PB == 96 ? 1 : 2, dj.p, m);
+            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, g.id, dj.p, m);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(out_jac) + jb * lo, dj.p, jb * m, hipMemcpyDeviceToHost, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));
             return BLSMI_OK;
         }
-        HIPCHK(hipMemcpyAsync(out + (size_t)PB * lo, dout.p, (size_t)PB * m, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(out + PB * lo, dout.p, PB * m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipMemcpyAsync(out_inf + lo, dinf.p, m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
         return BLSMI_OK;
     });
 }
-BLSMI_API int blsmi_g1_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<96>(KERNEL_OF(k_g1_mul), pts, 0, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g2_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch<192>(KERNEL_OF(k_g2_mul), pts, 0, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g1_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<96>(KERNEL_OF(k_g1_mul), nullptr, 1, scalars, out, out_inf, n); }
-BLSMI_API int blsmi_g2_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch<192>(KERNEL_OF(k_g2_mul), nullptr, 2, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g1_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch(1, pts, false, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g2_mul_batch(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { if (n && !pts) return BLSMI_E_ARG; return mul_batch(2, pts, false, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g1_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch(1, nullptr, true, scalars, out, out_inf, n); }
+BLSMI_API int blsmi_g2_mul_generator_batch(const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) { return mul_batch(2, nullptr, true, scalars, out, out_inf, n); }
 // PrivToPub for n keys with the results as the Go types hold them (bls.G?Projective with z = 1): PublicKey{p} is the record, no FQReprToFQ on the host
-BLSMI_API int blsmi_g1_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<96>(KERNEL_OF(k_g1_mul), nullptr, 1, scalars, nullptr, nullptr, n, false, out_jac); }
-BLSMI_API int blsmi_g2_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch<192>(KERNEL_OF(k_g2_mul), nullptr, 2, scalars, nullptr, nullptr, n, false, out_jac); }
+BLSMI_API int blsmi_g1_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch(1, nullptr, true, scalars, nullptr, nullptr, n, false, out_jac); }
+BLSMI_API int blsmi_g2_mul_generator_batch_jac(const uint8_t* scalars, uint64_t* out_jac, size_t n) { return mul_batch(2, nullptr, true, scalars, nullptr, nullptr, n, false, out_jac); }
 // device-pointer forms: points (NULL = the group generator), scalars, results and infinity bytes resident on one device
-template <int PB, class K>
-static int mul_batch_dev(K kernel, int gen_group, const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, bool any_point = false) {
+static int mul_batch_dev(int group, const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, bool any_point = false) {
     if (n == 0) return BLSMI_OK;
     if (!d_scalars || !d_out || !d_out_inf) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
     MulAny any_guard(any_point);
-    int rc = mul_dev_core<PB>(kernel, (const u8*)d_pts, gen_group, (const u8*)d_scalars, (u8*)d_out, (u8*)d_out_inf, n, g_stream);
+    int rc = mul_dev_core(group_kernels(group), (const u8*)d_pts, (const u8*)d_scalars, (u8*)d_out, (u8*)d_out_inf, n, g_stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<96>(KERNEL_OF(k_g1_mul), 1, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
-BLSMI_API int blsmi_g2_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev<192>(KERNEL_OF(k_g2_mul), 2, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
+BLSMI_API int blsmi_g1_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev(1, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
+BLSMI_API int blsmi_g2_mul_batch_dev(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) { return mul_batch_dev(2, d_pts, d_scalars, d_out, d_out_inf, n, stream); }
 // per-call choice of the ladder (flags & BLSMI_MUL_ANY_POINT: the plain windowed ladder, which serves every curve point like MulFR, g1.go:80-90)
 BLSMI_API int blsmi_g1_mul_batch_ex(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, unsigned flags) {
     if ((n && !pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch<96>(KERNEL_OF(k_g1_mul), pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch(1, pts, false, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_mul_batch_ex(const uint8_t* pts, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n, unsigned flags) {
     if ((n && !pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch<192>(KERNEL_OF(k_g2_mul), pts, 0, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch(2, pts, false, scalars, out, out_inf, n, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g1_mul_batch_dev_ex(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, unsigned flags) {
     if ((n && !d_pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch_dev<96>(KERNEL_OF(k_g1_mul), 1, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch_dev(1, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_mul_batch_dev_ex(const void* d_pts, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream, unsigned flags) {
     if ((n && !d_pts) || (flags & ~(unsigned)BLSMI_MUL_ANY_POINT)) return BLSMI_E_ARG;
-    return mul_batch_dev<192>(KERNEL_OF(k_g2_mul), 2, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return mul_batch_dev(2, d_pts, d_scalars, d_out, d_out_inf, n, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 
 // tree reduction of n affine points already on the device; result (affine bytes + inf flag) on the device
-template <int PB, int W, class K0, class K1, class K2>
-static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, size_t n, u8* d_out, i32* d_out_inf, hipStream_t s, bool sync = true, bool jac = false) {
-    const size_t words = (size_t)W * NL + 1;
+static int sum_dev(const GroupKernels& g, const u8* d_pts, const u8* d_inf, size_t n, u8* d_out, i32* d_out_inf, hipStream_t s, bool sync = true, bool jac = false) {
+    const size_t words = (size_t)g.fq * NL + 1;
     size_t half = (n + 1) / 2;
     DBuf b0, b1, wire;
     HIPCHK(b0.alloc(sizeof(i32) * words * half)); HIPCHK(b1.alloc(sizeof(i32) * words * ((half + 1) / 2)));
@@ -1194,55 +1229,52 @@ static int sum_dev(K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_inf, si
     // them as they are (k_g?_sum0_jac: no inversion anywhere before the one at the end); few: they become wire records for the level programs
     const bool lat = half <= tune().lat_max;
     if (jac && lat) {
-        HIPCHK(wire.alloc((size_t)PB * n));
-        int rc = jac_to_wire_dev(PB, d_pts, wire.p, nullptr, n, s);
+        HIPCHK(wire.alloc(g.wire_bytes * n));
+        int rc = jac_to_wire_dev(g, d_pts, wire.p, nullptr, n, s);
         if (rc) return rc;
         d_pts = wire.as<u8>(); d_inf = nullptr; jac = false;
     }
     if (lat) {
         // few points: every addition of the tree as a level program, one per wave (k_lat.hip: sum0 / sum1 / sumfin; complete
         // projective formulas, two product levels per addition) -- ~10 us a level instead of ~70-140
-        const size_t p0 = W == 3 ? LAT_SUM0_1_OFFSET : LAT_SUM0_2_OFFSET, p1 = W == 3 ? LAT_SUM1_1_OFFSET : LAT_SUM1_2_OFFSET, pf = W == 3 ? LAT_SUMFIN_1_OFFSET : LAT_SUMFIN_2_OFFSET;
-        launch_lat_marked(p0, s, {.b0 = {d_pts, PB}, .b1 = {d_inf, 0}, .b2 = lat_count(half), .b3 = lat_count(n), .out = b0.p}, half);   // sum0: pairs of the n points
+        launch_lat_marked(g.lat_sum0, s, {.b0 = {d_pts, g.wire_bytes}, .b1 = {d_inf, 0}, .b2 = lat_count(half), .b3 = lat_count(n), .out = b0.p}, half);   // sum0: pairs of the n points
         i32* src = b0.as<i32>(); i32* dst = b1.as<i32>();
         size_t cur = half;
         while (cur > 1) {
             const size_t h = (cur + 1) / 2;
-            launch_lat(p1, s, {.b2 = lat_count(h), .b3 = lat_count(cur, src), .out = dst}, h);   // sum1: pairs of the cur partial sums at src
+            launch_lat(g.lat_sum1, s, {.b2 = lat_count(h), .b3 = lat_count(cur, src), .out = dst}, h);   // sum1: pairs of the cur partial sums at src
             std::swap(src, dst);
             cur = h;
         }
         DBuf good; HIPCHK(good.alloc(1, s));
-        launch_lat(pf, s, {.b3 = lat_count(1, src), .ok = good.p, .out = d_out}, 1);
+        launch_lat(g.lat_sumfin, s, {.b3 = lat_count(1, src), .ok = good.p, .out = d_out}, 1);
         launch_quiet(KERNEL_OF(k_good_to_flag), 1, s, good.p, d_out_inf);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         if (sync) HIPCHK(hipStreamSynchronize(s));                        // (the temporaries live in the call's arena: an unsynchronised caller orders its own readers)
         return BLSMI_OK;
     }
-    if (jac && W == 3) launch(kernel_named(k_g1_sum0_jac, "k_g1_sum0"), nblocks(half), s, d_pts, b0.p, n, half);
-    else if (jac) launch(kernel_named(k_g2_sum0_jac, "k_g2_sum0"), nblocks(half), s, d_pts, b0.p, n, half);
-    else launch(k0, nblocks(half), s, d_pts, d_inf, b0.p, n, half);
-    prof_mark(k1.name);                                                    // one segment: the levels of the tree
+    if (jac) launch(g.sum0_jac, nblocks(half), s, d_pts, b0.p, n, half);
+    else launch(g.sum0, nblocks(half), s, d_pts, d_inf, b0.p, n, half);
+    prof_mark(g.sum.name);                                                    // one segment: the levels of the tree
     i32* src = b0.as<i32>(); i32* dst = b1.as<i32>();
     size_t cur = half;
     while (cur > 1) {
         const size_t h = (cur + 1) / 2;
-        launch_quiet(k1, nblocks(h), s, src, dst, cur, h);
+        launch_quiet(g.sum, nblocks(h), s, src, dst, cur, h);
         std::swap(src, dst);
         cur = h;
     }
-    launch(kfinal, 1, s, src, d_out, d_out_inf);
+    launch(g.sum_final, 1, s, src, d_out, d_out_inf);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     if (sync) HIPCHK(hipStreamSynchronize(s));
     return BLSMI_OK;
 }
-template <int PB, int W, class K0, class K1, class K2>
-static int sum_host(K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t* out, int* out_inf, bool jac = false, uint64_t* out_jac = nullptr) {
+static int sum_host(int group, const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t* out, int* out_inf, bool jac = false, uint64_t* out_jac = nullptr) {
     // jac: pts are in-memory Jacobian records (no in_inf); out_jac (may be null): the sum as such a record with z = 1, (0, 1, 0) for infinity
     if (!out_inf || (!out && !out_jac) || (n && !pts)) return BLSMI_E_ARG;
-    const size_t jb = rec_bytes(PB, true);
+    const size_t PB = wire_bytes_of(group), jb = rec_bytes(PB, true);
     if (n == 0) {                                                          // empty sum = infinity (g2pubs/bls.go:166, 181)
         if (out) memset(out, 0, PB);
         if (out_jac) { static const uint64_t one[6] = {0x760900000002fffdull, 0xebf4000bc40c0002ull, 0x5f48985753c758baull, 0x77ce585370525745ull, 0x5c071a97a256ec6dull, 0x15f65ec3fa80e493ull};
@@ -1250,15 +1282,16 @@ static int sum_host(K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* 
         *out_inf = 1; return BLSMI_OK;
     }
     LOCK_AND_INIT();
+    const GroupKernels& g = group_kernels(group);
     DBuf dp, di, dout, dflag, dj;
-    HIPCHK(dp.alloc((jac ? jb : (size_t)PB) * n)); HIPCHK(di.alloc(n)); HIPCHK(dout.alloc(PB)); HIPCHK(dflag.alloc(sizeof(i32))); HIPCHK(dj.alloc(jb));
-    HIPCHK(hipMemcpyAsync(dp.p, pts, (jac ? jb : (size_t)PB) * n, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(dp.alloc((jac ? jb : PB) * n)); HIPCHK(di.alloc(n)); HIPCHK(dout.alloc(PB)); HIPCHK(dflag.alloc(sizeof(i32))); HIPCHK(dj.alloc(jb));
+    HIPCHK(hipMemcpyAsync(dp.p, pts, (jac ? jb : PB) * n, hipMemcpyHostToDevice, g_stream));
     if (in_inf && !jac) HIPCHK(hipMemcpyAsync(di.p, in_inf, n, hipMemcpyHostToDevice, g_stream));
-    int rc = sum_dev<PB, W>(k0, k1, kfinal, dp.as<u8>(), (in_inf && !jac) ? di.as<u8>() : nullptr, n, dout.as<u8>(), dflag.as<i32>(), g_stream, true, jac);
+    int rc = sum_dev(g, dp.as<u8>(), (in_inf && !jac) ? di.as<u8>() : nullptr, n, dout.as<u8>(), dflag.as<i32>(), g_stream, true, jac);
     if (rc) return rc;
     i32 flag = 0;
     if (out_jac) {
-        launch_quiet(KERNEL_OF(k_affine_to_jac), 1, g_stream, dout.p, dflag.p, 0, W == 3 ? 1 : 2, dj.p, 1);
+        launch_quiet(KERNEL_OF(k_affine_to_jac), 1, g_stream, dout.p, dflag.p, 0, g.id, dj.p, 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out_jac, dj.p, jb, hipMemcpyDeviceToHost, g_stream));
     }
@@ -1268,54 +1301,47 @@ static int sum_host(K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* 
     *out_inf = flag;
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[96], int* out_inf) { return sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, in_inf, n, out, out_inf); }
-BLSMI_API int blsmi_g2_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[192], int* out_inf) { return sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, in_inf, n, out, out_inf); }
+BLSMI_API int blsmi_g1_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[96], int* out_inf) { return sum_host(1, pts, in_inf, n, out, out_inf); }
+BLSMI_API int blsmi_g2_sum(const uint8_t* pts, const uint8_t* in_inf, size_t n, uint8_t out[192], int* out_inf) { return sum_host(2, pts, in_inf, n, out, out_inf); }
 // AggregateSignatures / AggregatePublicKeys (g2pubs/bls.go:165-192, g1pubs/bls.go:177-204) over the points as the Go values hold them, the sum
 // handed back the same way (z = 1): no ToAffine, no SerializeBytes, no FQReprToFQ in the shim
 BLSMI_API int blsmi_g1_sum_jac(const uint64_t* pts_jac, size_t n, uint64_t out_jac[18], int* out_inf) {
-    return sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
+    return sum_host(1, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
 }
 BLSMI_API int blsmi_g2_sum_jac(const uint64_t* pts_jac, size_t n, uint64_t out_jac[36], int* out_inf) {
-    return sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
+    return sum_host(2, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, n, nullptr, out_inf, true, out_jac);
 }
-template <int PB, int W, class K0, class K1, class K2>
-static int sum_dev_api(K0 k0, K1 k1, K2 kfinal, const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) {
+static int sum_dev_api(int group, const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) {
     if (!d_out || !out_inf || (n && !d_pts)) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
-    if (n == 0) { HIPCHK(hipMemsetAsync(d_out, 0, PB, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); *out_inf = 1; return BLSMI_OK; }
+    const GroupKernels& g = group_kernels(group);
+    if (n == 0) { HIPCHK(hipMemsetAsync(d_out, 0, g.wire_bytes, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); *out_inf = 1; return BLSMI_OK; }
     DBuf dflag; HIPCHK(dflag.alloc(sizeof(i32)));
-    int rc = sum_dev<PB, W>(k0, k1, kfinal, (const u8*)d_pts, (const u8*)d_in_inf, n, (u8*)d_out, dflag.as<i32>(), g_stream);
+    int rc = sum_dev(g, (const u8*)d_pts, (const u8*)d_in_inf, n, (u8*)d_out, dflag.as<i32>(), g_stream);
     if (rc) return rc;
     i32 flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, dflag.p, sizeof flag, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
     *out_inf = flag;
     return BLSMI_OK;
 }
-BLSMI_API int blsmi_g1_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_in_inf, n, d_out, out_inf, stream); }
-BLSMI_API int blsmi_g2_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_in_inf, n, d_out, out_inf, stream); }
+BLSMI_API int blsmi_g1_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api(1, d_pts, d_in_inf, n, d_out, out_inf, stream); }
+BLSMI_API int blsmi_g2_sum_dev(const void* d_pts, const void* d_in_inf, size_t n, void* d_out, int* out_inf, void* stream) { return sum_dev_api(2, d_pts, d_in_inf, n, d_out, out_inf, stream); }
 
 // multi-scalar multiplication sum_i k_i * P_i.  Small batches: per-point windowed multiples feed the tree sum on the
 // device (one launch of latency, ~6 ms up to 64k points).  From BLSMI_MSM_BUCKET_MIN points (default 2^17, where the
 // two cross over) on: the bucket method of msm.inc, whose fixed tail (chunk reduction + 240 serial doublings) is ~6 ms.
 constexpr int BLSMI_E_SKEW = -1000;    // internal: bucket method declined (unbalanced digits)
-struct MsmKernels {
-    Kernel<const u8*, const u32*, const u32*, const u32*, const u32*, i32*, size_t, int, size_t> bucket;
-    Kernel<const i32*, i32*, int, int, size_t, size_t> chunk;
-    Kernel<const i32*, i32*, size_t, size_t, int> fold;
-    Kernel<const i32*, int, int, u8*, i32*> final;
-};
-template <int PB, int W>
 // nbits: the scalars' width -- 256, or 64 for the randomised batch verification's scalars (rlc_host.hpp: rlc_sig_sum), whose
 // 32-byte records are zero above bit 64: four windows instead of sixteen, the Horner tail 48 doublings instead of 240
-static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s, int nbits = 256) {
+static int msm_bucket_dev(const GroupKernels& g, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s, int nbits = 256) {
     // 16-bit windows: n / 2^16 points per bucket, and a 255-bit scalar still fills 15 bits of the top window (a window
     // size that leaves the top window a few bits wide would pile every point into a handful of buckets there)
     const int c = 16;
     const int K = 16;                                                      // buckets per chunk lane: 2^12 chunk lanes per window keep every SIMD busy
     const int nwin = (nbits + c - 1) / c;
     const size_t B1 = (size_t)1 << c, nb = B1 * nwin, per_win = B1 / K, nct = per_win * nwin;
-    const size_t jw = (size_t)W * NL + 1;                                  // words of one Jacobian SoA record
+    const size_t jw = (size_t)g.fq * NL + 1;                               // words of one Jacobian SoA record
     DBuf hist, offs, cursor, idx, buckets, ch0, ch1, dmax;
     HIPCHK(hist.alloc(sizeof(u32) * nb)); HIPCHK(offs.alloc(sizeof(u32) * nb)); HIPCHK(cursor.alloc(sizeof(u32) * nb)); HIPCHK(dmax.alloc(sizeof(u32)));
     HIPCHK(idx.alloc(sizeof(u32) * n * nwin)); HIPCHK(buckets.alloc(sizeof(i32) * jw * nb));
@@ -1340,38 +1366,33 @@ static int msm_bucket_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scal
     launch_sized(kernel_named(k_msm_class_hist, "k_msm_class_*"), cb, 256, s, hist.p, nb, cls.p);
     launch_quiet_sized(KERNEL_OF(k_msm_class_scan), 1, 256, s, cls.p, cls.as<u32>() + 256, cls.as<u32>() + 512);
     launch_quiet_sized(KERNEL_OF(k_msm_class_scatter), cb, 256, s, hist.p, nb, cls.as<u32>() + 256, cls.as<u32>() + 512, perm.p);
-    if (W == 6 && tune().pair_layout)                                      // G2: a lane pair per bucket, two waves per SIMD
-        launch(KERNEL_OF(k_g2_msm_bucket_pair), tuple_blocks(Layout::pair, nb), s, d_pts, idx.p, offs.p, hist.p, perm.p, buckets.p, n, c, nb);
-    else
-        launch(k.bucket, nblocks(nb), s, d_pts, idx.p, offs.p, hist.p, perm.p, buckets.p, n, c, nb);
-    launch(k.chunk, nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
-    prof_mark(k.fold.name);                                                // one segment: the levels of the fold
+    launch_items(g.msm_bucket, nb, s, d_pts, idx.p, offs.p, hist.p, perm.p, buckets.p, n, c, nb);   // (G2: a lane pair per bucket, two waves per SIMD)
+    launch(g.msm_chunk, nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
+    prof_mark(g.msm_fold.name);                                              // one segment: the levels of the fold
     i32* src = ch0.as<i32>(); i32* dst = ch1.as<i32>();
     size_t seg = per_win;
     while (seg > 1) {
         const size_t half = (seg + 1) / 2;
-        launch_quiet(k.fold, nblocks(half * nwin), s, src, dst, seg, half, nwin);
+        launch_quiet(g.msm_fold, nblocks(half * nwin), s, src, dst, seg, half, nwin);
         std::swap(src, dst);
         seg = half;
     }
     // Horner over the 16 windows (240 dependent doublings) and ToAffine on one lane: this is the path for ARBITRARY curve points
     // (blsmi_set_mul_assume_subgroup(0)); the default path (msm_bucket_glv_dev) has a level program for its shorter tail
-    static_assert(W == 3 || W == 6, "G1 / G2");
-    launch(k.final, 1, s, src, nwin, c, d_out, d_flag);
+    launch(g.msm_final, 1, s, src, nwin, c, d_out, d_flag);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));                                       // temporaries die with this scope
     return BLSMI_OK;
 }
 // The bucket method for points of the prime-order subgroup (msm.inc, second half): scalars decomposed through the endomorphisms
 // (G1: 8 bucket-windows fed by 2 n items, G2: 4 fed by 4 n), points converted to raw limbs once.  Same result as msm_bucket_dev.
-template <int PB, int W>
-static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s,
+static int msm_bucket_glv_dev(const GroupKernels& g, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s,
                               const std::function<int()>& points_arrive = {}) {
     constexpr int c = 16, K = 8;                                           // 8 buckets per chunk lane: 2^13 chunks per window, 13 fold levels (the tail programs are generated for that)
-    constexpr int nbw = W == 3 ? 8 : 4, sh = W == 3 ? 3 : 2, NS = 16 / nbw;
-    constexpr size_t RAWW = W == 3 ? 48 : 244;
+    const int sh = g.msm_shift, nbw = 1 << sh, NS = 16 / nbw;
+    const size_t RAWW = g.msm_raw_words;
     const size_t B1 = (size_t)1 << c, nb = B1 * nbw, per_win_chunks = B1 / K, nct = per_win_chunks * nbw, per_win_items = (size_t)NS * n;
-    const size_t jw = (size_t)W * NL + 1;
+    const size_t jw = (size_t)g.fq * NL + 1;
     if (n >= ((size_t)1 << 30)) return BLSMI_E_ARG;                         // the item word keeps the stream in bits 30-31
     DBuf raw, rec, hist, offs, cursor, idx, buckets, ch0, ch1, dmax, cls, perm;
     HIPCHK(raw.alloc(sizeof(i32) * RAWW * n, s)); HIPCHK(rec.alloc(32 * n, s));
@@ -1397,8 +1418,7 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(u32) * nb, s));
     HIPCHK(hipMemsetAsync(dmax.p, 0, sizeof(u32), s));
     HIPCHK(hipMemsetAsync(cls.p, 0, sizeof(u32) * 256, s));
-    if (W == 3) launch(KERNEL_OF(k_msm_recode_g1), nblocks(n), s, d_scalars, rec.p, n);
-    else launch(KERNEL_OF(k_msm_recode_g2), nblocks(n), s, d_scalars, rec.p, n);
+    launch(g.msm_recode, nblocks(n), s, d_scalars, rec.p, n);
     u32 biggest = 0;
     size_t slice_stride = per_win_items;                                   // a bucket's items: idx + (bucket >> 16) * slice_stride + offs[bucket]
     auto exact_passes = [&]() -> int {
@@ -1436,45 +1456,36 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
     // then are the points converted to raw limbs.  Skewed scalars (a bucket beyond 2048 items would be one lane's serial work)
     // fall back to the per-point multiples, whose cost does not depend on the scalars.
     if (points_arrive) { const int rc = points_arrive(); if (rc) return rc; }
-    if (W == 3) launch(KERNEL_OF(k_msm_rawpts_g1), nblocks(n), s, d_pts, raw.p, n);
-    else launch(KERNEL_OF(k_msm_rawpts_g2), nblocks(n), s, d_pts, raw.p, n);
+    launch(g.msm_rawpts, nblocks(n), s, d_pts, raw.p, n);
     prof_mark(nullptr);
     HIPCHK(hipStreamSynchronize(s));
     if (biggest > 2048) return BLSMI_E_SKEW;
     if (!sort_mode) items = idx.as<u32>();
-    if (W == 3) launch(KERNEL_OF(k_g1_msm_bucket_raw), nblocks(nb), s, raw.p, items, offs.p, hist.p, perm.p, buckets.p, slice_stride, nb);
-    else launch(KERNEL_OF(k_g2_msm_bucket_raw_pair), tuple_blocks(Layout::pair, nb), s, raw.p, items, offs.p, hist.p, perm.p, buckets.p, slice_stride, nb);
+    launch_items(g.msm_bucket_raw, nb, s, raw.p, items, offs.p, hist.p, perm.p, buckets.p, slice_stride, nb);
     // running sums per chunk WITHOUT the per-lane multiplication, then the fold that carries the odd-element sums along (msm.inc):
     // one addition deep per level; out come, per window, X, L and O_0 .. O_{m-1}
-    const bool pairk = W == 6 && tune().pair_layout;                       // G2: a lane pair per chunk / per sum, two waves per SIMD
-    if (pairk) launch(KERNEL_OF(k_g2_msm_chunk2_pair), tuple_blocks(Layout::pair, nct), s, buckets.p, ch0.p, c, K, nb, nct);
-    else if (W == 6) launch(KERNEL_OF(k_g2_msm_chunk2), nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
-    else launch(KERNEL_OF(k_g1_msm_chunk2), nblocks(nct), s, buckets.p, ch0.p, c, K, nb, nct);
-    prof_mark(W == 6 ? (pairk ? KERNEL_OF(k_g2_msm_fold2_pair) : KERNEL_OF(k_g2_msm_fold2)).name : KERNEL_OF(k_g1_msm_fold2).name);   // one segment: the levels of the fold
+    launch_items(g.msm_chunk2, nct, s, buckets.p, ch0.p, c, K, nb, nct);   // (G2: a lane pair per chunk / per sum, two waves per SIMD)
+    prof_mark(g.msm_fold2.k.name);                                         // one segment: the levels of the fold
     i32* src = ch0.as<i32>(); i32* dst = ch1.as<i32>();
     int narr = 2, m = 0;
     const bool lat_tail = tune().lat_max > 0 && per_win_chunks == ((size_t)1 << 13) && K == 8;   // the tail runs as a latency program (k_lat.hip), which reads the inter-kernel record form
     for (size_t len = per_win_chunks; len > 1; len /= 2, narr++, m++) {
         const size_t lanes = (size_t)(narr + 1) * nbw * (len / 2);
         const int io = (lat_tail && len == 2) ? 1 : 0;                     // the last level writes what the tail program reads
-        if (pairk) launch_quiet(KERNEL_OF(k_g2_msm_fold2_pair), tuple_blocks(Layout::pair, lanes), s, src, dst, narr, nbw, len, io);
-        else if (W == 6) launch_quiet(KERNEL_OF(k_g2_msm_fold2), nblocks(lanes), s, src, dst, narr, nbw, len, io);
-        else launch_quiet(KERNEL_OF(k_g1_msm_fold2), nblocks(lanes), s, src, dst, narr, nbw, len, io);
+        launch_items_quiet(g.msm_fold2, lanes, s, src, dst, narr, nbw, len, io);
         std::swap(src, dst);
     }
     const size_t nrec = (size_t)(m + 2) * nbw;                             // X, L, O_0 .. O_{m-1} per window
     if (lat_tail) {                              // Horner over the O's and over the 8 / 4 windows + ToAffine: one wave (k_lat.hip: msmfin1 / msmfin2)
-        const size_t prog = W == 3 ? LAT_MSMFIN1_OFFSET : LAT_MSMFIN2_OFFSET;
         DBuf good; HIPCHK(good.alloc(1, s));
-        launch_lat_marked(prog, s, {.b3 = lat_count(nrec, src), .ok = good.p, .out = d_out}, 1);
+        launch_lat_marked(g.lat_msmfin, s, {.b3 = lat_count(nrec, src), .ok = good.p, .out = d_out}, 1);
         launch_quiet(KERNEL_OF(k_good_to_flag), 1, s, good.p, d_flag);
         prof_mark(nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         return BLSMI_OK;
     }
-    if (W == 6) launch(KERNEL_OF(k_g2_msm_final2), 1, s, src, nbw, m, 3, c, d_out, d_flag);
-    else launch(KERNEL_OF(k_g1_msm_final2), 1, s, src, nbw, m, 3, c, d_out, d_flag);
+    launch(g.msm_final2, 1, s, src, nbw, m, 3, c, d_out, d_flag);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -1482,40 +1493,40 @@ static int msm_bucket_glv_dev(const MsmKernels& k, const u8* d_pts, const u8* d_
 }
 // sum_i k_i P_i with everything resident on the leased device: bucket method from bucket_min points on (unless the digits
 // are skewed), per-point multiples + tree sum below.  Result: affine bytes at d_out, infinity flag (i32) at d_flag.  Synchronises s.
-template <int PB, int W, class KM, class K0, class K1, class K2>
-static int msm_dev_core(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s,
+static int msm_dev_core(const GroupKernels& g, const u8* d_pts, const u8* d_scalars, size_t n, u8* d_out, i32* d_flag, hipStream_t s,
                         const std::function<int()>& points_arrive = {}) {
     const size_t bucket_min = tune().msm_bucket_min;
     int rc = BLSMI_E_SKEW;
     bool arrived = !points_arrive;                                         // the host form hands over its copy of the points: issued at the latest before the first kernel that reads them
     auto arrive_once = [&]() -> int { if (arrived) return BLSMI_OK; arrived = true; return points_arrive(); };
-    if (n >= bucket_min && mul_subgroup()) rc = msm_bucket_glv_dev<PB, W>(mk, d_pts, d_scalars, n, d_out, d_flag, s, arrive_once);
-    else if (n >= bucket_min) { rc = arrive_once(); if (!rc) rc = msm_bucket_dev<PB, W>(mk, d_pts, d_scalars, n, d_out, d_flag, s); }
+    if (n >= bucket_min && mul_subgroup()) rc = msm_bucket_glv_dev(g, d_pts, d_scalars, n, d_out, d_flag, s, arrive_once);
+    else if (n >= bucket_min) { rc = arrive_once(); if (!rc) rc = msm_bucket_dev(g, d_pts, d_scalars, n, d_out, d_flag, s); }
     if (rc != BLSMI_E_SKEW) return rc;
     rc = arrive_once();
     if (rc) return rc;
     DBuf dm, dinf;
-    HIPCHK(dm.alloc((size_t)PB * n, s)); HIPCHK(dinf.alloc(n, s));
-    rc = mul_dev_core<PB>(kmul, d_pts, 0, d_scalars, dm.as<u8>(), dinf.as<u8>(), n, s);
+    HIPCHK(dm.alloc(g.wire_bytes * n, s)); HIPCHK(dinf.alloc(n, s));
+    rc = mul_dev_core(g, d_pts, d_scalars, dm.as<u8>(), dinf.as<u8>(), n, s);
     if (rc) return rc;
-    return sum_dev<PB, W>(k0, k1, kfinal, dm.as<u8>(), dinf.as<u8>(), n, d_out, d_flag, s);   // synchronises: the temporaries may go
+    return sum_dev(g, dm.as<u8>(), dinf.as<u8>(), n, d_out, d_flag, s);   // synchronises: the temporaries may go
 }
-template <int PB, int W, class KM, class K0, class K1, class K2>
-static int msm_host(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* out, int* out_inf, bool any_point = false) {
+static int msm_host(int group, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* out, int* out_inf, bool any_point = false) {
     if (!out || !out_inf || (n && (!pts || !scalars))) return BLSMI_E_ARG;
-    if (n == 0) { memset(out, 0, PB); *out_inf = 1; return BLSMI_OK; }
+    if (n == 0) { memset(out, 0, wire_bytes_of(group)); *out_inf = 1; return BLSMI_OK; }
     LOCK_AND_INIT();
+    const GroupKernels& g = group_kernels(group);
+    const size_t PB = g.wire_bytes;
     MulAny any_guard(any_point);
     DBuf dp, ds, dout, dflag;
-    HIPCHK(dp.alloc((size_t)PB * n)); HIPCHK(ds.alloc(32 * n)); HIPCHK(dout.alloc(PB)); HIPCHK(dflag.alloc(sizeof(i32)));
+    HIPCHK(dp.alloc(PB * n)); HIPCHK(ds.alloc(32 * n)); HIPCHK(dout.alloc(PB)); HIPCHK(dflag.alloc(sizeof(i32)));
     // scalars first; the points follow while the digit passes (which need the scalars only) run
     HIPCHK(hipMemcpyAsync(ds.p, scalars, 32 * n, hipMemcpyHostToDevice, g_stream));
     // (on a side stream: a copy from pageable memory issued on the compute stream would wait for the kernels queued there)
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t st = g_stream, side = tl_ctx->aux[0];
     hipEvent_t arrived = tl_ctx->join[0];
-    int rc = msm_dev_core<PB, W>(mk, kmul, k0, k1, kfinal, dp.as<u8>(), ds.as<u8>(), n, dout.as<u8>(), dflag.as<i32>(), g_stream, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(dp.p, pts, (size_t)PB * n, hipMemcpyHostToDevice, side));
+    int rc = msm_dev_core(g, dp.as<u8>(), ds.as<u8>(), n, dout.as<u8>(), dflag.as<i32>(), g_stream, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(dp.p, pts, PB * n, hipMemcpyHostToDevice, side));
         HIPCHK(hipEventRecord(arrived, side));
         HIPCHK(hipStreamWaitEvent(st, arrived, 0));
         return BLSMI_OK;
@@ -1528,51 +1539,49 @@ static int msm_host(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, cons
     *out_inf = flag;
     return BLSMI_OK;
 }
-template <int PB, int W, class KM, class K0, class K1, class K2>
-static int msm_dev_api(const MsmKernels& mk, KM kmul, K0 k0, K1 k1, K2 kfinal, const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, bool any_point = false) {
+static int msm_dev_api(int group, const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, bool any_point = false) {
     if (!d_out || !out_inf || (n && (!d_pts || !d_scalars))) return BLSMI_E_ARG;
     LOCK_AND_INIT_AT(d_out);
     UseStream us(stream);
     MulAny any_guard(any_point);
-    if (n == 0) { HIPCHK(hipMemsetAsync(d_out, 0, PB, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); *out_inf = 1; return BLSMI_OK; }
+    const GroupKernels& g = group_kernels(group);
+    if (n == 0) { HIPCHK(hipMemsetAsync(d_out, 0, g.wire_bytes, g_stream)); HIPCHK(hipStreamSynchronize(g_stream)); *out_inf = 1; return BLSMI_OK; }
     DBuf dflag; HIPCHK(dflag.alloc(sizeof(i32)));
-    int rc = msm_dev_core<PB, W>(mk, kmul, k0, k1, kfinal, (const u8*)d_pts, (const u8*)d_scalars, n, (u8*)d_out, dflag.as<i32>(), g_stream);
+    int rc = msm_dev_core(g, (const u8*)d_pts, (const u8*)d_scalars, n, (u8*)d_out, dflag.as<i32>(), g_stream);
     if (rc) return rc;
     i32 flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, dflag.p, sizeof flag, hipMemcpyDeviceToHost, g_stream)); HIPCHK(hipStreamSynchronize(g_stream));
     *out_inf = flag;
     return BLSMI_OK;
 }
-static const MsmKernels g_mk1{KERNEL_OF(k_g1_msm_bucket), KERNEL_OF(k_g1_msm_chunk), KERNEL_OF(k_g1_msm_fold), KERNEL_OF(k_g1_msm_final)};
-static const MsmKernels g_mk2{KERNEL_OF(k_g2_msm_bucket), KERNEL_OF(k_g2_msm_chunk), KERNEL_OF(k_g2_msm_fold), KERNEL_OF(k_g2_msm_final)};
 BLSMI_API int blsmi_g1_msm(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[96], int* out_inf) {
-    return msm_host<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, scalars, n, out, out_inf);
+    return msm_host(1, pts, scalars, n, out, out_inf);
 }
 BLSMI_API int blsmi_g2_msm(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[192], int* out_inf) {
-    return msm_host<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, scalars, n, out, out_inf);
+    return msm_host(2, pts, scalars, n, out, out_inf);
 }
 BLSMI_API int blsmi_g1_msm_dev(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream) {
-    return msm_dev_api<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream);
+    return msm_dev_api(1, d_pts, d_scalars, n, d_out, out_inf, stream);
 }
 BLSMI_API int blsmi_g2_msm_dev(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream) {
-    return msm_dev_api<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream);
+    return msm_dev_api(2, d_pts, d_scalars, n, d_out, out_inf, stream);
 }
 #define BLSMI_FLAGS_OK(f) (((f) & ~(unsigned)BLSMI_MUL_ANY_POINT) == 0)
 BLSMI_API int blsmi_g1_msm_ex(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[96], int* out_inf, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_host<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_host(1, pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_msm_ex(const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t out[192], int* out_inf, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_host<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_host(2, pts, scalars, n, out, out_inf, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g1_msm_dev_ex(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_dev_api<96, 3>(g_mk1, KERNEL_OF(k_g1_mul), KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_dev_api(1, d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 BLSMI_API int blsmi_g2_msm_dev_ex(const void* d_pts, const void* d_scalars, size_t n, void* d_out, int* out_inf, void* stream, unsigned flags) {
     if (!BLSMI_FLAGS_OK(flags)) return BLSMI_E_ARG;
-    return msm_dev_api<192, 6>(g_mk2, KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
+    return msm_dev_api(2, d_pts, d_scalars, n, d_out, out_inf, stream, (flags & BLSMI_MUL_ANY_POINT) != 0);
 }
 
 #include "verify_host.inc"

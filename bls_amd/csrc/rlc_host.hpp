@@ -45,23 +45,19 @@ int rlc_draw_scalars(uint64_t* r, size_t n) {
 // at d_flag, on g_stream.  From RLC_MSM_BUCKET_MIN signatures the bucket method of msm_bucket_dev over the scalars' 64 bits (four
 // 16-bit windows); below, or when the digits are skewed (a caller's scalars), per-signature 64-bit ladders and the tree sum.
 constexpr size_t RLC_MSM_BUCKET_MIN = 8192;
-int rlc_sig_sum(int kind, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum, i32* d_flag) {
+int rlc_sig_sum(const GroupKernels& g, const u8* d_sigs, const u64* d_r, size_t n, u8* d_sum, i32* d_flag) {
     hipStream_t s = g_stream;
     if (n >= RLC_MSM_BUCKET_MIN) {
         DBuf sc; HIPCHK(sc.alloc((size_t)32 * n));
         launch_quiet(KERNEL_OF(k_scalar_u64_to_be32), nblocks(n), s, d_r, sc.p, n);
-        const int rc = kind == 0 ? msm_bucket_dev<96, 3>(g_mk1, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64)
-                                 : msm_bucket_dev<192, 6>(g_mk2, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
+        const int rc = msm_bucket_dev(g, d_sigs, sc.as<u8>(), n, d_sum, d_flag, s, 64);
         if (rc != BLSMI_E_SKEW) return rc;
     }
-    const size_t pb = kind == 0 ? 96 : 192;
-    DBuf m, inf; HIPCHK(m.alloc(pb * n)); HIPCHK(inf.alloc(n));
-    if (kind == 0) launch(KERNEL_OF(k_g1_mul_u64), nblocks(n), s, d_sigs, d_r, m.p, inf.p, n);
-    else launch(KERNEL_OF(k_g2_mul_u64), nblocks(n), s, d_sigs, d_r, m.p, inf.p, n);
+    DBuf m, inf; HIPCHK(m.alloc(g.wire_bytes * n)); HIPCHK(inf.alloc(n));
+    launch(g.mul_u64, nblocks(n), s, d_sigs, d_r, m.p, inf.p, n);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
-    return kind == 0 ? sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false)
-                     : sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
+    return sum_dev(g, m.as<u8>(), inf.as<u8>(), n, d_sum, d_flag, s, false);
 }
 // sig_side_start for a signature already on the device (the sum above, read in place): MillerLoop(-sig, G2gen) / MillerLoop(-G1gen, sig)
 // into ss.ml, on g_stream, which the caller has pointed at the side stream; join[0] marks its end for aggregate_tail
@@ -128,7 +124,7 @@ int rlc_begin(RlcCall& c, int kind, size_t n, const void* off_or_domain, size_t 
 // main stream, where `fork` says that the scalars are there: the side stream's sum may start.
 int rlc_upload_start(RlcCall& c, const uint8_t* sigs, const uint64_t* r, const void* msgs, const void* off_or_domain, int fmt) {
     hipStream_t s = g_stream, st = tl_ctx->aux[0];
-    { int rc = upload_points(c.k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, c.ds.p, c.n, st); if (rc) return rc; }
+    { int rc = upload_points(c.k.sig(), (fmt & FMT_SIG_JAC) != 0, sigs, c.ds.p, c.n, st); if (rc) return rc; }
     HIPCHK(hipEventRecord(tl_ctx->join[1], st));
     HIPCHK(hipMemcpyAsync(c.dr.p, r, sizeof(uint64_t) * c.n, hipMemcpyHostToDevice, s));
     { int rc = c.msgs.copy(msgs, off_or_domain, s); if (rc) return rc; }
@@ -138,7 +134,7 @@ int rlc_upload_start(RlcCall& c, const uint8_t* sigs, const uint64_t* r, const v
 // Right after the form's hash_dev: the keys and the infinity flags travel while the messages are hashed; the main stream then waits for the signatures.
 int rlc_upload_keys(RlcCall& c, const uint8_t* pks, const uint8_t* inf_flags, int fmt) {
     hipStream_t s = g_stream;
-    int rc = upload_points(c.k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, c.dp.p, c.n, s);
+    int rc = upload_points(c.k.pk(), (fmt & FMT_PK_JAC) != 0, pks, c.dp.p, c.n, s);
     if (rc) return rc;
     c.has_inf = inf_flags != nullptr;
     if (inf_flags) HIPCHK(hipMemcpyAsync(c.di.p, inf_flags, c.n, hipMemcpyHostToDevice, s));
@@ -153,7 +149,7 @@ void rlc_flag_inputs(RlcCall& c) {
 // point at infinity is flagged like an input: into flag_bytes (c.flags, or bytes of the form's own where the inputs' flags must stay), and `any`.
 void rlc_scale_g1(RlcCall& c, const u8* src, u8* scaled, u8* sinf, u8* flag_bytes) {
     hipStream_t s = g_stream;
-    launch(KERNEL_OF(k_g1_mul_u64), nblocks(c.n), s, src, c.dr.p, scaled, sinf, c.n);
+    launch(group_kernels(1).mul_u64, nblocks(c.n), s, src, c.dr.p, scaled, sinf, c.n);
     prof_mark(nullptr);
     launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(c.n), s, scaled, 24, nullptr, 0, sinf, flag_bytes, c.any.p, c.n);
 }
@@ -163,7 +159,7 @@ int rlc_signature_side(RlcCall& c) {
     hipStream_t st = tl_ctx->aux[0];
     HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
     OnStream on(st);
-    int rc = rlc_sig_sum(c.kind, c.ds.as<u8>(), c.dr.as<u64>(), c.n, c.sum.as<u8>(), c.sflag.as<i32>()); if (rc) return rc;
+    int rc = rlc_sig_sum(c.k.sig(), c.ds.as<u8>(), c.dr.as<u64>(), c.n, c.sum.as<u8>(), c.sflag.as<i32>()); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
 }
@@ -393,7 +389,7 @@ int verify_batch_rlc_grouped_host(int kind, const uint8_t* msgs, const uint64_t*
     // sum_{i in g} r_i pk_i for every group; a sum at infinity is flagged like an input.  On s, the context's main stream: segsum_dev names
     // k_g?_segsum_chunk_u64 in the profile only there (profile marks are events on that stream), and tests/test_gpu_rlc_grouped.py looks
     // for the name -- a move of the sums to aux[1] must point the context's stream at it for the stretch (OnStream, as rlc_signature_side)
-    rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, c.dr.as<u64>());
+    rc = segsum_dev(k.pk(), false, c.dp.p, nullptr, n, dx.as<u32>(), plan, agg.as<u8>(), ainf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
     launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(dg), s, agg.p, k.pk_bytes / 4, nullptr, 0, ainf.p, gflags.p, c.any.p, dg);
     // d' Miller loops, one per message, and their product
@@ -470,7 +466,7 @@ int locate_failing_positions(RlcCall& c, const blsmi_route::LocatePlan& lp, cons
     HIPCHK(sb.alloc((size_t)k.sig_bytes * B)); HIPCHK(sbinf.alloc(B)); HIPCHK(g1.alloc((size_t)96 * B)); HIPCHK(g2.alloc((size_t)192 * B)); HIPCHK(bbad.alloc(B));
     HIPCHK(fs.alloc(sizeof(i32) * words * B)); HIPCHK(prod.alloc(fe == Layout::wave ? 576 * B : sizeof(i32) * words * B)); HIPCHK(vals.alloc(576 * B));
     HIPCHK(one.alloc(B)); HIPCHK(dfail.alloc(B));
-    int rc = segsum_dev(k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, c.dr.as<u64>());
+    int rc = segsum_dev(k.sig(), false, c.ds.p, nullptr, n, nullptr, splan, sb.as<u8>(), sbinf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
     launch(KERNEL_OF(k_locate_sig_pairs), nblocks(B), s, c.kind == 0 ? 0 : 1, sb.p, sbinf.p, g_gens.g1, g_gens.g2, g1.p, g2.p, bbad.p, B);
     launch_miller_tuples(g1.as<u8>(), g2.as<u8>(), fs.as<i32>(), B, s, pairing_layout(0, B, tune(), bload));
@@ -618,10 +614,9 @@ int cells_signature_side(RlcCall& c, const SegPlan& plan, CellBufs& b) {
     const size_t C = plan.m;
     HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
     OnStream on(st);
-    int rc = segsum_dev(c.k.sig_bytes == 192 ? 2 : 1, false, c.ds.p, nullptr, c.n, b.dx.as<u32>(), plan, b.sc.as<u8>(), b.scinf.as<u8>(), 1, st, c.dr.as<u64>());
+    int rc = segsum_dev(c.k.sig(), false, c.ds.p, nullptr, c.n, b.dx.as<u32>(), plan, b.sc.as<u8>(), b.scinf.as<u8>(), 1, st, c.dr.as<u64>());
     if (rc) return rc;
-    rc = c.kind == 0 ? sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false)
-                     : sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false);
+    rc = sum_dev(c.k.sig(), b.sc.as<u8>(), b.scinf.as<u8>(), C, c.sum.as<u8>(), c.sflag.as<i32>(), st, false);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
@@ -699,7 +694,7 @@ int verify_batch_rlc_grouped_locate_host(int kind, const uint8_t* msgs, const ui
     rc = rlc_upload_keys(c, pks, inf_flags, fmt); if (rc) return rc;
     rlc_flag_inputs(c);
     // K_c for every cell (on the main stream: the profile names k_g?_segsum_chunk_u64 there); a sum at infinity is flagged per cell
-    rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, false, c.dp.p, nullptr, n, b.dx.as<u32>(), plan, b.kc.as<u8>(), b.kinf.as<u8>(), 1, s, c.dr.as<u64>());
+    rc = segsum_dev(k.pk(), false, c.dp.p, nullptr, n, b.dx.as<u32>(), plan, b.kc.as<u8>(), b.kinf.as<u8>(), 1, s, c.dr.as<u64>());
     if (rc) return rc;
     launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(C), s, b.kc.p, k.pk_bytes / 4, nullptr, 0, b.kinf.p, b.kflag.p, c.any.p, C);
     // every cell its group's hash point, C Miller loops with one value each, the values kept; the tree over them gives the total

@@ -7,8 +7,12 @@ namespace {
 
 // kind 0 = g2pubs (pk in G2 192 B, sig in G1 96 B, H -> G1); 1 = g1pubs (pk in G1 96 B, sig in G2 192 B, H -> G2);
 // 2 = g1pubs *WithDomain (msgs are n x 32 bytes, d_off = the 8-byte domain)
-struct Kind { int pk_bytes, sig_bytes, h_bytes; };
-inline Kind kind_of(int kind) { return kind == 0 ? Kind{192, 96, 96} : Kind{96, 192, 192}; }
+// pk_group / sig_group: the curve group (1 / 2) of the keys and of the signatures; pk() / sig(): its row for the call this thread serves
+struct Kind {
+    int pk_group, sig_group, pk_bytes, sig_bytes, h_bytes;
+    const GroupKernels& pk() const { return group_kernels(pk_group); } const GroupKernels& sig() const { return group_kernels(sig_group); }
+};
+inline Kind kind_of(int kind) { return kind == 0 ? Kind{2, 1, 192, 96, 96} : Kind{1, 2, 96, 192, 192}; }
 
 // Prepared public keys (k_prepared_pair.hip, g2pubs only): tables of blsmi_prep::WORDS i32 each on the device, and per tuple
 // the index of its key's table (null: tuple t uses table t).
@@ -181,7 +185,7 @@ int verify_sig_side_start(int kind, Side side, void* d_sigs, const uint8_t* host
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t st = tl_ctx->aux[0];
     if (after) { HIPCHK(hipEventRecord(tl_ctx->fork, after)); HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0)); }
-    if (host_sigs) { int rc = upload_points(k.sig_bytes, sigs_jac, host_sigs, d_sigs, n, st); if (rc) return rc; }
+    if (host_sigs) { int rc = upload_points(k.sig(), sigs_jac, host_sigs, d_sigs, n, st); if (rc) return rc; }
     const SigPair sp = sig_pair(kind, d_sigs, k.sig_bytes);
     if (side == Side::row)
         launch_quiet(KERNEL_OF(k_miller1s_row), tuple_blocks(Layout::row, n), st, sp.P.p, sp.P.stride, sp.Q.p, sp.Q.stride, f, n, (kind == 0 && tune().use_gen_lines) ? (const i32*)g_gens.lines_pair : (const i32*)nullptr, 0, n);
@@ -306,8 +310,8 @@ int verify_batch_leased(int kind, const uint8_t* msgs, const uint64_t* off_or_do
     rc = hash_dev(kind, dm.m.p, dm.off.p, h.as<u8>(), n, g_stream, r.hash);
     if (rc) return rc;
     if (prep_tables) { if (prep_idx) HIPCHK(hipMemcpyAsync(dp.p, prep_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, g_stream)); }
-    else { rc = upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); if (rc) return rc; }   // (in-memory points: ToAffine on the device, after the hash)
-    if (!side) { rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, g_stream); if (rc) return rc; }
+    else { rc = upload_points(k.pk(), (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); if (rc) return rc; }   // (in-memory points: ToAffine on the device, after the hash)
+    if (!side) { rc = upload_points(k.sig(), (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, n, g_stream); if (rc) return rc; }
     if (inf_flags) HIPCHK(hipMemcpyAsync(di.p, inf_flags, n, hipMemcpyHostToDevice, g_stream));
     const PrepKeys prep{prep_tables, prep_idx ? dp.as<u32>() : nullptr};
     rc = verify_pair_stage(kind, h.as<u8>(), prep_tables ? nullptr : dp.p, ds.p, inf_flags ? di.p : nullptr, dok.p, f.as<i32>(), n, g_stream, r, prep_tables ? &prep : nullptr);
@@ -673,7 +677,7 @@ int aggregate_shard(int kind, const uint8_t* msgs, const uint64_t* off_or_domain
     { int rc = dm.upload(msgs, off_or_domain, g_stream); if (rc) return rc; }
     hipStream_t s = g_stream;
     int rc = aggregate_shard_dev(kind, dm.m.p, dm.off.p, dp.as<u8>(), n, d_out, bad, s, [&]() -> int {
-        return upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
+        return upload_points(k.pk(), (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, s);   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
     }, nullptr, g1_clear);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
@@ -736,7 +740,7 @@ int tail_verdict(size_t prog, LatArgs a, int* ok) {
 int aggregate_tail(int kind, const i32* d_prod, const uint8_t* sig, int* ok, int fmt = 0) {
     const Kind k = kind_of(kind);
     DBuf dsig; HIPCHK(dsig.alloc(k.sig_bytes));
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
+    { int rc = upload_points(k.sig(), (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
     const SigPair sp = sig_pair(kind, dsig.p, 0);
     return tail_verdict(LAT_AGGTAIL_OFFSET, {.b0 = sp.P, .b1 = sp.Q, .b3 = {d_prod, 0}}, ok);
 }
@@ -750,7 +754,7 @@ int sig_side_start(int kind, const uint8_t* sig, SigSide& ss, int fmt = 0) {
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t st = tl_ctx->aux[0];
     HIPCHK(ss.sig.alloc(k.sig_bytes)); HIPCHK(ss.ml.alloc(sizeof(i32) * 12 * NL));
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, ss.sig.p, 1, st); if (rc) return rc; }
+    { int rc = upload_points(k.sig(), (fmt & FMT_SIG_JAC) != 0, sig, ss.sig.p, 1, st); if (rc) return rc; }
     launch_sig_miller(sig_pair(kind, ss.sig.p, 0), ss.ml.p, 1, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(tl_ctx->join[0], st));
@@ -862,7 +866,7 @@ int verify_aggregate_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
             a.d_msgs = dm.m.p; a.d_off_or_domain = dm.off.p; a.d_pks = dp.as<u8>();
             return dm.copy(msgs, off_or_domain, g_stream);
         };
-        in.after_hash = [&]() -> int { return upload_points(k.pk_bytes, (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); };   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
+        in.after_hash = [&]() -> int { return upload_points(k.pk(), (fmt & FMT_PK_JAC) != 0, pks, dp.p, n, g_stream); };   // the hash runs while the keys are on their way (in-memory points: + ToAffine on the device)
         return verify_aggregate_on_ctx(kind, in, sig, n, ok, check_dups, fmt);
     }
     const int S = (plan.nshards + g_ndev - 1) / g_ndev;                    // partial-product slots per device
@@ -966,10 +970,7 @@ int verify_aggregate_common_host(int kind, const uint8_t* msg, size_t msg_len, c
         return verify_aggregate_common_dev(kind, dp.p, n, msg, msg_len, domain, sig, ok, fmt);
     }
     uint8_t agg[192]; int agg_inf = 0;
-    int rc;
-    if (fmt & FMT_PK_JAC) rc = (k.pk_bytes == 192) ? sum_host<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), pks, nullptr, n, agg, &agg_inf, true)
-                                                   : sum_host<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), pks, nullptr, n, agg, &agg_inf, true);
-    else rc = (k.pk_bytes == 192) ? blsmi_g2_sum(pks, nullptr, n, agg, &agg_inf) : blsmi_g1_sum(pks, nullptr, n, agg, &agg_inf);
+    int rc = sum_host(k.pk_group, pks, nullptr, n, agg, &agg_inf, (fmt & FMT_PK_JAC) != 0);
     if (rc) return rc;
     uint8_t flags = agg_inf ? 1 : 0, res = 0;
     if (kind == 2) rc = verify_batch_host(2, msg, reinterpret_cast<const uint64_t*>(domain), agg, sig, &flags, &res, nullptr, 1, fmt & FMT_SIG_JAC);
@@ -994,8 +995,7 @@ int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uin
     if (n == 0) {                                                          // the empty sum is the point at infinity (g2pubs/bls.go:181)
         HIPCHK(hipMemsetAsync(dagg.p, 0, k.pk_bytes, side)); HIPCHK(hipMemsetAsync(dinf.p, 1, 1, side));
     } else {
-        int rc = k.pk_bytes == 192 ? sum_dev<192, 6>(KERNEL_OF(k_g2_sum0), KERNEL_OF(k_g2_sum), KERNEL_OF(k_g2_sum_final), (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj)
-                                   : sum_dev<96, 3>(KERNEL_OF(k_g1_sum0), KERNEL_OF(k_g1_sum), KERNEL_OF(k_g1_sum_final), (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj);
+        int rc = sum_dev(k.pk(), (const u8*)d_pks, (const u8*)nullptr, n, dagg.as<u8>(), dflag.as<i32>(), side, false, pj);
         if (rc) return rc;
         launch_quiet(KERNEL_OF(k_flag_to_byte), 1, side, dflag.p, dinf.p);
     }
@@ -1004,7 +1004,7 @@ int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uin
     if (msg_len) HIPCHK(hipMemcpyAsync(dm.p, msg, msg_len, hipMemcpyHostToDevice, g_stream));
     if (kind == 2) HIPCHK(hipMemcpyAsync(doff.p, domain, 8, hipMemcpyHostToDevice, g_stream));
     else HIPCHK(hipMemcpyAsync(doff.p, off, sizeof off, hipMemcpyHostToDevice, g_stream));
-    { int rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
+    { int rc = upload_points(k.sig(), (fmt & FMT_SIG_JAC) != 0, sig, dsig.p, 1, g_stream); if (rc) return rc; }
     int rc = verify_batch_dev(kind, dm.p, doff.p, dagg.p, dsig.p, dinf.p, dok.p, 1, g_stream, nullptr, tl_ctx->join[1]);   // synchronises
     if (rc) return rc;
     uint8_t res = 0;
@@ -1012,54 +1012,51 @@ int verify_aggregate_common_dev(int kind, const void* d_pks, size_t n, const uin
     *ok = res;
     return BLSMI_OK;
 }
-template <int IB, int OB, class K>
-int hash_host(K kernel_kind, const uint8_t* msgs, const void* off_or_domain, uint8_t* out, size_t n) {
+int hash_host(int kernel_kind, const uint8_t* msgs, const void* off_or_domain, uint8_t* out, size_t n) {
     if (n && (!msgs || !off_or_domain || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
+    const size_t OB = kind_of(kernel_kind).h_bytes;
     DevMsgs dm(kernel_kind, off_or_domain, n); DBuf dout;
-    HIPCHK(dout.alloc((size_t)OB * n));
+    HIPCHK(dout.alloc(OB * n));
     int rc = dm.upload(msgs, off_or_domain, g_stream);
     if (rc) return rc;
     rc = hash_dev(kernel_kind, dm.m.p, dm.off.p, dout.as<u8>(), n, g_stream, hash_route_alone(kernel_kind, n));
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(out, dout.p, OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
 // n compressed points -> affine records, infinity flags, error codes (g1.go:185-249, g2.go:219-295), on stream s.
-// group 1 / 2 = G1 / G2.  Small batches take the subgroup test (check == 1) as a level program of the latency path.
-int decompress_dev(int group, const u8* d_in, int check, u8* d_out, u8* d_inf, u8* d_err, size_t n, hipStream_t s) {
+// Small batches take the subgroup test (check == 1) as a level program of the latency path.
+int decompress_dev(const GroupKernels& gk, const u8* d_in, int check, u8* d_out, u8* d_inf, u8* d_err, size_t n, hipStream_t s) {
     const unsigned g = nblocks(n);
     const bool lat = check == 1 && n <= tune().lat_max;
     const int kcheck = lat ? 0 : check;
     const size_t wave_max = tune().swu_wave_max;
     const bool waves = kcheck == 0 && n <= wave_max;                       // the smallest calls: one wave per point, its square root with one limb per lane (fp_row.cuh)
-    if (waves && group == 1) launch_sized(KERNEL_OF(k_g1_decompress_waves), n, 64, s, d_in, d_out, d_inf, d_err, n);
-    else if (waves) launch_sized(KERNEL_OF(k_g2_decompress_waves), n, 64, s, d_in, d_out, d_inf, d_err, n);
-    else if (group == 1) launch(KERNEL_OF(k_g1_decompress), g, s, d_in, kcheck, d_out, d_inf, d_err, n);
-    else launch(KERNEL_OF(k_g2_decompress), g, s, d_in, kcheck, d_out, d_inf, d_err, n);
+    if (waves) launch_sized(gk.decompress_waves, n, 64, s, d_in, d_out, d_inf, d_err, n);
+    else launch(gk.decompress, g, s, d_in, kcheck, d_out, d_inf, d_err, n);
     if (lat) {
-        const size_t rec = group == 1 ? 96 : 192;
-        const size_t prog = group == 1 ? LAT_SUBGRP1_OFFSET : LAT_SUBGRP2_OFFSET;
         DBuf sub; HIPCHK(sub.alloc(n, s));
-        launch_lat_marked(prog, s, {.b0 = {d_out, rec}, .ok = sub.p}, n);
-        launch_quiet(KERNEL_OF(k_apply_subgroup), g, s, sub.p, d_out, (int)(rec / 4), d_inf, d_err, n);
+        launch_lat_marked(gk.lat_subgrp, s, {.b0 = {d_out, gk.wire_bytes}, .ok = sub.p}, n);
+        launch_quiet(KERNEL_OF(k_apply_subgroup), g, s, sub.p, d_out, (int)(gk.wire_bytes / 4), d_inf, d_err, n);
     }
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
-template <int IB, int OB>
 int decompress_host(int group, const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) {
     if (n && (!in || !out || !out_inf || !err)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
+    const GroupKernels& gk = group_kernels(group);
+    const size_t OB = gk.wire_bytes, IB = OB / 2;
     DBuf di, dout, dinf, derr;
-    HIPCHK(di.alloc((size_t)IB * n)); HIPCHK(dout.alloc((size_t)OB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(derr.alloc(n));
-    HIPCHK(hipMemcpyAsync(di.p, in, (size_t)IB * n, hipMemcpyHostToDevice, g_stream));
-    { const int rc = decompress_dev(group, di.as<u8>(), check, dout.as<u8>(), dinf.as<u8>(), derr.as<u8>(), n, g_stream); if (rc) return rc; }
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(di.alloc(IB * n)); HIPCHK(dout.alloc(OB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(derr.alloc(n));
+    HIPCHK(hipMemcpyAsync(di.p, in, IB * n, hipMemcpyHostToDevice, g_stream));
+    { const int rc = decompress_dev(gk, di.as<u8>(), check, dout.as<u8>(), dinf.as<u8>(), derr.as<u8>(), n, g_stream); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(out, dout.p, OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(out_inf, dinf.p, n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(err, derr.p, n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -1098,14 +1095,13 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
         HIPCHK(hipStreamWaitEvent(spk, tl_ctx->fork, 0)); HIPCHK(hipStreamWaitEvent(ssg, tl_ctx->fork, 0));
     }
     {
-        int rc = decompress_dev(kind == 0 ? 2 : 1, dpc.as<u8>(), check, dp.as<u8>(), ipk.as<u8>(), epk.as<u8>(), n, spk);
+        int rc = decompress_dev(k.pk(), dpc.as<u8>(), check, dp.as<u8>(), ipk.as<u8>(), epk.as<u8>(), n, spk);
         if (rc) return rc;
-        rc = decompress_dev(kind == 0 ? 1 : 2, dsc.as<u8>(), check, ds.as<u8>(), isg.as<u8>(), esg.as<u8>(), n, ssg);
+        rc = decompress_dev(k.sig(), dsc.as<u8>(), check, ds.as<u8>(), isg.as<u8>(), esg.as<u8>(), n, ssg);
         if (rc) return rc;
     }
-    const Kind kk = kind_of(kind);
     DBuf h, f;
-    HIPCHK(h.alloc((size_t)kk.h_bytes * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
+    HIPCHK(h.alloc((size_t)k.h_bytes * n)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * n));
     const VerifyRoute r = verify_route(kind, n, false, false, tune(), route_load(n));   // (no signature side: the signatures are still being decompressed)
     int rc = hash_dev(kind, dm.m.p, dm.off.p, h.as<u8>(), n, g_stream, r.hash);  // on the main stream, beside the decompressions
     if (rc) return rc;
@@ -1123,18 +1119,19 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
-template <int IB, int OB, class K>
-int compress_host(K kernel, const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) {
+int compress_host(int group, const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) {
     if (n && (!pts || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
     if (n == 0) return BLSMI_OK;
+    const GroupKernels& gk = group_kernels(group);
+    const size_t IB = gk.wire_bytes, OB = IB / 2;
     DBuf di, dinf, dout;
-    HIPCHK(di.alloc((size_t)IB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(dout.alloc((size_t)OB * n));
-    HIPCHK(hipMemcpyAsync(di.p, pts, (size_t)IB * n, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(di.alloc(IB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(dout.alloc(OB * n));
+    HIPCHK(hipMemcpyAsync(di.p, pts, IB * n, hipMemcpyHostToDevice, g_stream));
     if (in_inf) HIPCHK(hipMemcpyAsync(dinf.p, in_inf, n, hipMemcpyHostToDevice, g_stream));
-    launch_quiet(kernel, nblocks(n), g_stream, di.p, in_inf ? dinf.p : nullptr, dout.p, n);
+    launch_quiet(gk.compress, nblocks(n), g_stream, di.p, in_inf ? dinf.p : nullptr, dout.p, n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)OB * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(out, dout.p, OB * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
@@ -1272,20 +1269,19 @@ BLSMI_API int blsmi_debug_hash_redo(int kind, const uint8_t* msgs, const uint64_
 }
 
 BLSMI_API int blsmi_hash_g1_batch(const uint8_t* msgs, const uint64_t* off, uint8_t* out, size_t n) {
-    return hash_host<0, 96>(0, msgs, off, out, n);
+    return hash_host(0, msgs, off, out, n);
 }
 BLSMI_API int blsmi_hash_g2_batch(const uint8_t* msgs, const uint64_t* off, uint8_t* out, size_t n) {
-    return hash_host<0, 192>(1, msgs, off, out, n);
+    return hash_host(1, msgs, off, out, n);
 }
 BLSMI_API int blsmi_hash_g2_with_domain_batch(const uint8_t* msgs32, const uint8_t domain[8], uint8_t* out, size_t n) {
-    return hash_host<0, 192>(2, msgs32, domain, out, n);
+    return hash_host(2, msgs32, domain, out, n);
 }
 
 // Sign for n (message, secret key) pairs in one call: sig_i = sk_i * H(m_i) (g2pubs/bls.go:132-135, g1pubs/bls.go:132-135, 138-141) -- the hash
 // points never leave the device between the two steps.  kind: 0 g2pubs (HashG1, 96-byte signatures), 1 g1pubs (HashG2, 192), 2 g1pubs
 // WithDomain (HashG2WithDomain of 32-byte messages).  sks: n x 32 bytes big-endian.  out_inf[i] = 1 when the signature is the point at
 // infinity (sk_i = 0 mod r: the reference returns the zero point).
-template <int OB>
 int sign_host(int kind, const uint8_t* msgs, const void* off_or_domain, size_t off_bytes, size_t msg_bytes, const uint8_t* sks, uint8_t* out, uint8_t* out_inf, size_t n, uint64_t* out_jac = nullptr) {
     // out_jac (replaces out / out_inf): the signatures as in-memory Jacobian records, z = 1 ((0, 1, 0) for sk = 0 mod r)
     if (n && (!msgs || !off_or_domain || !sks || (out_jac ? false : (!out || !out_inf)))) return BLSMI_E_ARG;
@@ -1294,11 +1290,12 @@ int sign_host(int kind, const uint8_t* msgs, const void* off_or_domain, size_t o
     const bool domain = kind == 2;
     const uint64_t* off = domain ? nullptr : static_cast<const uint64_t*>(off_or_domain);
     return run_shards(plan_shards(n, 64), [&](int, size_t lo, size_t hi) -> int {
-        const size_t m = hi - lo;
+        const GroupKernels& g = kind_of(kind).sig();
+        const size_t m = hi - lo, OB = g.wire_bytes;
         const size_t mb = domain ? 32 * m : (size_t)(off[hi] - off[lo]);
         DBuf dm, doff, dh, dk, dout, dinf;
-        HIPCHK(dm.alloc(mb)); HIPCHK(doff.alloc(domain ? 8 : sizeof(uint64_t) * (m + 1))); HIPCHK(dh.alloc((size_t)OB * m));
-        HIPCHK(dk.alloc(32 * m)); HIPCHK(dout.alloc((size_t)OB * m)); HIPCHK(dinf.alloc(m));
+        HIPCHK(dm.alloc(mb)); HIPCHK(doff.alloc(domain ? 8 : sizeof(uint64_t) * (m + 1))); HIPCHK(dh.alloc(OB * m));
+        HIPCHK(dk.alloc(32 * m)); HIPCHK(dout.alloc(OB * m)); HIPCHK(dinf.alloc(m));
         if (mb) HIPCHK(hipMemcpyAsync(dm.p, msgs + (domain ? 32 * lo : (size_t)off[lo]), mb, hipMemcpyHostToDevice, g_stream));
         if (domain) HIPCHK(hipMemcpyAsync(doff.p, off_or_domain, 8, hipMemcpyHostToDevice, g_stream));
         else if (lo == 0) HIPCHK(hipMemcpyAsync(doff.p, off, sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, g_stream));
@@ -1311,43 +1308,42 @@ int sign_host(int kind, const uint8_t* msgs, const void* off_or_domain, size_t o
         int rc = hash_dev(kind, dm.p, doff.p, dh.as<u8>(), m, g_stream, hash_route_alone(kind, m));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(dk.p, sks + 32 * lo, 32 * m, hipMemcpyHostToDevice, g_stream));   // the keys travel while the hash runs
-        if (OB == 96) rc = mul_dev_core<96>(KERNEL_OF(k_g1_mul), dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
-        else rc = mul_dev_core<192>(KERNEL_OF(k_g2_mul), dh.as<u8>(), 0, dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
+        rc = mul_dev_core(g, dh.as<u8>(), dk.as<u8>(), dout.as<u8>(), dinf.as<u8>(), m, g_stream);
         if (rc) return rc;
         if (out_jac) {
             const size_t jb = rec_bytes(OB, true);
             DBuf dj; HIPCHK(dj.alloc(jb * m));
-            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, OB == 96 ? 1 : 2, dj.p, m);
+            launch_quiet(KERNEL_OF(k_affine_to_jac), nblocks(m), g_stream, dout.p, dinf.p, 1, g.id, dj.p, m);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(out_jac) + jb * lo, dj.p, jb * m, hipMemcpyDeviceToHost, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));
             return BLSMI_OK;
         }
-        HIPCHK(hipMemcpyAsync(out + (size_t)OB * lo, dout.p, (size_t)OB * m, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(out + OB * lo, dout.p, OB * m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipMemcpyAsync(out_inf + lo, dinf.p, m, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
         return BLSMI_OK;
     });
 }
 BLSMI_API int blsmi_g2pubs_sign_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* sks, uint8_t* out_sigs, uint8_t* out_inf, size_t n) {
-    return sign_host<96>(0, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, out_sigs, out_inf, n);
+    return sign_host(0, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, out_sigs, out_inf, n);
 }
 BLSMI_API int blsmi_g1pubs_sign_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* sks, uint8_t* out_sigs, uint8_t* out_inf, size_t n) {
-    return sign_host<192>(1, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, out_sigs, out_inf, n);
+    return sign_host(1, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, out_sigs, out_inf, n);
 }
 BLSMI_API int blsmi_g1pubs_sign_with_domain_batch(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* sks, uint8_t* out_sigs, uint8_t* out_inf, size_t n) {
-    return sign_host<192>(2, msgs32, domain, 8, 32 * n, sks, out_sigs, out_inf, n);
+    return sign_host(2, msgs32, domain, 8, 32 * n, sks, out_sigs, out_inf, n);
 }
 
 // ... with the signatures handed back as the Go types hold them (Signature{s *bls.G?Projective}, z = 1)
 BLSMI_API int blsmi_g2pubs_sign_batch_jac(const uint8_t* msgs, const uint64_t* off, const uint8_t* sks, uint64_t* out_sigs_jac, size_t n) {
-    return sign_host<96>(0, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, nullptr, nullptr, n, out_sigs_jac);
+    return sign_host(0, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, nullptr, nullptr, n, out_sigs_jac);
 }
 BLSMI_API int blsmi_g1pubs_sign_batch_jac(const uint8_t* msgs, const uint64_t* off, const uint8_t* sks, uint64_t* out_sigs_jac, size_t n) {
-    return sign_host<192>(1, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, nullptr, nullptr, n, out_sigs_jac);
+    return sign_host(1, msgs, off, sizeof(uint64_t) * (n + 1), (n && off) ? (size_t)off[n] : 0, sks, nullptr, nullptr, n, out_sigs_jac);
 }
 BLSMI_API int blsmi_g1pubs_sign_with_domain_batch_jac(const uint8_t* msgs32, const uint8_t domain[8], const uint8_t* sks, uint64_t* out_sigs_jac, size_t n) {
-    return sign_host<192>(2, msgs32, domain, 8, 32 * n, sks, nullptr, nullptr, n, out_sigs_jac);
+    return sign_host(2, msgs32, domain, 8, 32 * n, sks, nullptr, nullptr, n, out_sigs_jac);
 }
 BLSMI_API int blsmi_g2pubs_verify_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, const uint8_t* inf_flags, uint8_t* ok, uint8_t* ok_bitmap, size_t n) {
     return verify_batch_host(0, msgs, off, pks, sigs, inf_flags, ok, ok_bitmap, n);
@@ -1468,7 +1464,7 @@ static int g2_prepared_create(const uint8_t* g2, bool jac, size_t n, void** hand
     auto code = [](hipError_t e) { return e == hipSuccess ? BLSMI_OK : e == hipErrorOutOfMemory ? BLSMI_E_NOMEM : BLSMI_E_HIP; };
     DBuf q;
     int rc = code(q.alloc(192 * n));
-    if (!rc) rc = jac ? upload_points(192, true, g2, q.p, n, g_stream) : code(hipMemcpyAsync(q.p, g2, 192 * n, hipMemcpyHostToDevice, g_stream));
+    if (!rc) rc = jac ? upload_points(group_kernels(2), true, g2, q.p, n, g_stream) : code(hipMemcpyAsync(q.p, g2, 192 * n, hipMemcpyHostToDevice, g_stream));
     if (!rc) {
         launch(KERNEL_OF(k_g2_prepare_pair), tuple_blocks(Layout::pair, n), g_stream, q.p, tab, n);
         prof_mark(nullptr);
@@ -1592,10 +1588,10 @@ BLSMI_API int blsmi_g2pubs_verify_serialized_batch(const uint8_t* msgs, const ui
 BLSMI_API int blsmi_g1pubs_verify_serialized_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* pks, const uint8_t* sigs, int check_subgroup, uint8_t* ok, uint8_t* err_pk, uint8_t* err_sig, size_t n) {
     return verify_serialized_host(1, msgs, off, pks, sigs, check_subgroup, ok, err_pk, err_sig, n);
 }
-BLSMI_API int blsmi_g1_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host<48, 96>(1, in, check, out, out_inf, err, n); }
-BLSMI_API int blsmi_g2_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host<96, 192>(2, in, check, out, out_inf, err, n); }
-BLSMI_API int blsmi_g1_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<96, 48>(KERNEL_OF(k_g1_compress), pts, in_inf, out, n); }
-BLSMI_API int blsmi_g2_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host<192, 96>(KERNEL_OF(k_g2_compress), pts, in_inf, out, n); }
+BLSMI_API int blsmi_g1_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host(1, in, check, out, out_inf, err, n); }
+BLSMI_API int blsmi_g2_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host(2, in, check, out, out_inf, err, n); }
+BLSMI_API int blsmi_g1_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host(1, pts, in_inf, out, n); }
+BLSMI_API int blsmi_g2_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host(2, pts, in_inf, out, n); }
 
 // ---- the verify surface over the reference's in-memory points (blsmi 0.6; include/blsmi.h "in-memory points") ---------------------------
 // Keys and signatures as the Go values hold them: bls.G2Projective = 36 x u64, bls.G1Projective = 18 x u64 (x, y, z; FQ = 6 LE u64 Montgomery
@@ -1641,8 +1637,8 @@ static int verify_batch_jac_dev_api(const void* d_msgs, const void* d_off, const
     const Kind k = kind_of(KIND);
     DBuf p, sg;
     HIPCHK(p.alloc((size_t)k.pk_bytes * n)); HIPCHK(sg.alloc((size_t)k.sig_bytes * n));
-    int rc = jac_to_wire_dev(k.pk_bytes, d_pks, p.p, nullptr, n, g_stream);
-    if (!rc) rc = jac_to_wire_dev(k.sig_bytes, d_sigs, sg.p, nullptr, n, g_stream);
+    int rc = jac_to_wire_dev(k.pk(), d_pks, p.p, nullptr, n, g_stream);
+    if (!rc) rc = jac_to_wire_dev(k.sig(), d_sigs, sg.p, nullptr, n, g_stream);
     if (rc) return rc;
     return verify_batch_dev(KIND, d_msgs, d_off, p.p, sg.p, nullptr, d_ok, n, g_stream);
 }
@@ -1736,15 +1732,15 @@ void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t
     p.seg_lo = p.put(part_lo); p.seg_cnt = p.put(part_cnt);
 }
 // The segmented sum on the device, everything on stream s, not synchronised (the temporaries come from the call's arena, `p.blob` is read
-// by the copy: both stay alive until the caller synchronises).  group 1 / 2; jac: d_pts are in-memory Jacobian records (no d_in_inf).
+// by the copy: both stay alive until the caller synchronises).  jac: d_pts are in-memory Jacobian records (no d_in_inf).
 // d_out: m affine records, d_out_inf: m bytes (1 infinity, bad_code for a segment with an index >= npk, 0 otherwise).
 // d_scalars (may be null; affine points only): npk 64-bit weights -- segment j is then sum scalars[i] * pts[i] over its indices i, pass 1
 // running the ladder (k_g?_segsum_chunk_u64) over a plan whose first pass has chunks of one position.
-int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_t npk, const u32* d_idx, const SegPlan& p, u8* d_out, u8* d_out_inf,
+int segsum_dev(const GroupKernels& g, bool jac, const void* d_pts, const u8* d_in_inf, size_t npk, const u32* d_idx, const SegPlan& p, u8* d_out, u8* d_out_inf,
                u8 bad_code, hipStream_t s, const u64* d_scalars = nullptr) {
     const size_t m = p.m;
     if (m == 0) return BLSMI_OK;
-    const size_t words = (size_t)(group == 1 ? 3 : 6) * NL + 1;
+    const size_t words = (size_t)g.fq * NL + 1;
     DBuf plan, bad, a, b;
     HIPCHK(plan.alloc(p.blob.size())); HIPCHK(bad.alloc(m));
     HIPCHK(hipMemcpyAsync(plan.p, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, s));
@@ -1756,25 +1752,20 @@ int segsum_dev(int group, bool jac, const void* d_pts, const u8* d_in_inf, size_
     if (n1 && d_scalars) {
         if (jac) return BLSMI_E_ARG;
         const bool mark = tl_ctx && s == tl_ctx->stream;                   // (profile marks are events on the context's main stream)
-        const auto k = group == 1 ? KERNEL_OF(k_g1_segsum_chunk_u64) : KERNEL_OF(k_g2_segsum_chunk_u64);
-        if (mark) prof_mark(k.name);
-        launch_quiet(k, nblocks(n1), s, d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        if (mark) prof_mark(g.segsum_chunk_u64.name);
+        launch_quiet(g.segsum_chunk_u64, nblocks(n1), s, d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
         if (mark) prof_mark(nullptr);
     } else if (n1) {
-        if (group == 1 && jac) launch_quiet(KERNEL_OF(k_g1_segsum_chunk_jac), nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
-        else if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_chunk), nblocks(n1), s, d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
-        else if (jac) launch_quiet(KERNEL_OF(k_g2_segsum_chunk_jac), nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
-        else launch_quiet(KERNEL_OF(k_g2_segsum_chunk_pair), tuple_blocks(Layout::pair, n1), s, d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        if (jac) launch_quiet(g.segsum_chunk_jac, nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        else launch_items_quiet(g.segsum_chunk, n1, s, d_pts, d_in_inf, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
     }
     i32* src = a.as<i32>();
     for (const SegPlan::Fold& f : p.folds) {
         DBuf d; HIPCHK(d.alloc(sizeof(i32) * words * f.nch));
-        if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_fold), nblocks(f.nch), s, src, f.nsrc, at64(f.lo), at32(f.cnt), d.p, f.nch);
-        else launch_quiet(KERNEL_OF(k_g2_segsum_fold_pair), tuple_blocks(Layout::pair, f.nch), s, src, f.nsrc, at64(f.lo), at32(f.cnt), d.p, f.nch);
+        launch_items_quiet(g.segsum_fold, f.nch, s, src, f.nsrc, at64(f.lo), at32(f.cnt), d.p, f.nch);
         src = d.as<i32>();
     }
-    if (group == 1) launch_quiet(KERNEL_OF(k_g1_segsum_final), m, s, src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), bad.p, bad_code, d_out, d_out_inf);
-    else launch_quiet(KERNEL_OF(k_g2_segsum_final), m, s, src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), bad.p, bad_code, d_out, d_out_inf);
+    launch_quiet(g.segsum_final, m, s, src, p.nlast, at64(p.seg_lo), at32(p.seg_cnt), bad.p, bad_code, d_out, d_out_inf);
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
@@ -1787,8 +1778,9 @@ int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* i
     if (!out || !out_inf || (npk && !pts) || (weighted && npk && !scalars)) return BLSMI_E_ARG;
     int rc = segsum_check(npk, idx, seg_off, m);
     if (rc) return rc;
-    const size_t pb = group == 1 ? 96 : 192, pin = rec_bytes(pb, jac), total = seg_off[m];
     LOCK_AND_INIT();
+    const GroupKernels& g = group_kernels(group);
+    const size_t pb = g.wire_bytes, pin = rec_bytes(pb, jac), total = seg_off[m];
     SegPlan plan;
     segsum_plan(seg_off, m, segsum_chunk_of(total), plan, 64, weighted ? 1 : 0);
     DBuf dp, di, dx, dout, dinf, dsc;
@@ -1797,7 +1789,7 @@ int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* i
     if (npk) HIPCHK(hipMemcpyAsync(dp.p, pts, pin * npk, hipMemcpyHostToDevice, g_stream));
     if (in_inf && !jac && npk) HIPCHK(hipMemcpyAsync(di.p, in_inf, npk, hipMemcpyHostToDevice, g_stream));
     if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
-    rc = segsum_dev(group, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream,
+    rc = segsum_dev(g, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream,
                     weighted ? dsc.as<u64>() : nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, pb * m, hipMemcpyDeviceToHost, g_stream));
@@ -1825,7 +1817,7 @@ int sum_segmented_dev_api(int group, const void* d_pts, const void* d_in_inf, si
     if (rc) return rc;
     SegPlan plan;
     segsum_plan(off.data(), m, segsum_chunk_of(off[m]), plan);
-    rc = segsum_dev(group, false, d_pts, (const u8*)d_in_inf, npk, (const u32*)d_idx, plan, (u8*)d_out, (u8*)d_out_inf, 2, g_stream);
+    rc = segsum_dev(group_kernels(group), false, d_pts, (const u8*)d_in_inf, npk, (const u32*)d_idx, plan, (u8*)d_out, (u8*)d_out_inf, 2, g_stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
@@ -1869,7 +1861,7 @@ int agg_common_batch_dev(int kind, const void* d_msgs, const void* d_off_or_doma
     HIPCHK(tl_ctx->ensure_aux());
     hipStream_t side = tl_ctx->aux[1];
     HIPCHK(hipEventRecord(tl_ctx->fork, g_stream)); HIPCHK(hipStreamWaitEvent(side, tl_ctx->fork, 0));   // (the keys and indices may still be arriving on g_stream)
-    int rc = segsum_dev(k.pk_bytes == 192 ? 2 : 1, pks_jac, d_pks, nullptr, npk, d_idx, plan, dagg.as<u8>(), dinf.as<u8>(), 1, side);
+    int rc = segsum_dev(k.pk(), pks_jac, d_pks, nullptr, npk, d_idx, plan, dagg.as<u8>(), dinf.as<u8>(), 1, side);
     if (rc) return rc;
     HIPCHK(hipEventRecord(tl_ctx->join[1], side));
     return verify_batch_dev(kind, d_msgs, d_off_or_domain, dagg.p, d_sigs, dinf.p, d_ok, m, g_stream, nullptr, tl_ctx->join[1]);   // synchronises
@@ -1901,7 +1893,7 @@ int agg_common_batch_host(int kind, const uint8_t* msgs, const uint64_t* off_or_
     if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
     rc = dm.upload(msgs, off_or_domain, g_stream);
     if (rc) return rc;
-    rc = upload_points(k.sig_bytes, (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, m, g_stream);
+    rc = upload_points(k.sig(), (fmt & FMT_SIG_JAC) != 0, sigs, ds.p, m, g_stream);
     if (rc) return rc;
     rc = agg_common_batch_dev(kind, dm.m.p, dm.off.p, dp.p, npk, idx ? dx.as<u32>() : nullptr, plan, ds.p, dok.p, pj);
     if (rc) return rc;
@@ -2056,8 +2048,8 @@ int pprod_host(const uint8_t* g1, const uint8_t* g2, const uint8_t* inf_flags, s
     DBuf a, b, fl, o, ok;
     HIPCHK(a.alloc(96 * np)); HIPCHK(b.alloc(192 * np)); HIPCHK(fl.alloc(np)); HIPCHK(o.alloc(576 * m)); HIPCHK(ok.alloc(m));
     if (np) {
-        rc = upload_points(96, jac, g1, a.p, np, g_stream);
-        if (!rc) rc = upload_points(192, jac, g2, b.p, np, g_stream);
+        rc = upload_points(group_kernels(1), jac, g1, a.p, np, g_stream);
+        if (!rc) rc = upload_points(group_kernels(2), jac, g2, b.p, np, g_stream);
         if (rc) return rc;
         if (inf_flags) HIPCHK(hipMemcpyAsync(fl.p, inf_flags, np, hipMemcpyHostToDevice, g_stream));
     }
@@ -2082,8 +2074,8 @@ int pprod_dev_api(const void* d_g1, const void* d_g2, const void* d_inf_flags, s
     DBuf a, b;                                                             // the call's own copies: the records of skipped pairs are overwritten
     HIPCHK(a.alloc(96 * np)); HIPCHK(b.alloc(192 * np));
     if (np && jac) {
-        rc = jac_to_wire_dev(96, d_g1, a.p, nullptr, np, g_stream);
-        if (!rc) rc = jac_to_wire_dev(192, d_g2, b.p, nullptr, np, g_stream);
+        rc = jac_to_wire_dev(group_kernels(1), d_g1, a.p, nullptr, np, g_stream);
+        if (!rc) rc = jac_to_wire_dev(group_kernels(2), d_g2, b.p, nullptr, np, g_stream);
         if (rc) return rc;
     } else if (np) {
         HIPCHK(hipMemcpyAsync(a.p, d_g1, 96 * np, hipMemcpyDeviceToDevice, g_stream));
