@@ -95,6 +95,36 @@ def all_in_memory(points):
     return len(points) > 0 and all(p.jac is not None for p in points)
 
 
+def _wire_as_jac(p):
+    """the in-memory record of a point held in wire form, read as the library reads the wire record: z = 1 (G?Affine.ToProjective), the
+    all-zero record and None as z = 0, a coordinate not below q as 0.  Host big integers: a multiplication by 2^384 per coordinate."""
+    nfq = 2 if p.group == 1 else 4
+    raw = p._raw
+    if raw is None or not any(raw):
+        return bytes(48 * nfq * 3 // 2)
+    vals = [int.from_bytes(raw[48 * e:48 * e + 48], "big") for e in range(nfq)]
+    mont = [((v if v < _Q else 0) << 384) % _Q for v in vals] + [(1 << 384) % _Q] + [0] * (nfq // 2 - 1)
+    return b"".join(v.to_bytes(48, "little") for v in mont)
+
+
+def point_statuses(points, group, check=1):
+    """blsmi_g?_check_batch of a list of Points in ONE engine call: the affine form when every point is held in wire form, else the
+    in-memory form (the wire-form points of a mixed list become z = 1 records on the host) -> (n,) uint8 of engine.POINT_*"""
+    n = len(points)
+    if n == 0:
+        return []
+    if any(p.jac is not None for p in points):
+        fn = engine.g1_check_batch_jac if group == 1 else engine.g2_check_batch_jac
+        return fn(b"".join(p.jac if p.jac is not None else _wire_as_jac(p) for p in points), n, check)
+    fn = engine.g1_check_batch if group == 1 else engine.g2_check_batch
+    return fn(b"".join(p.bytes_or_zero() for p in points), n, [1 if p.infinity else 0 for p in points], check)
+
+
+def points_valid(points, group):
+    """[IsOnCurve() && IsInCorrectSubgroupAssumingOnCurve()] (g1.go:93-105, 137-141; g2.go:118-130, 293-295; both true for infinity)"""
+    return [int(st) in (engine.POINT_OK, engine.POINT_INFINITY) for st in point_statuses(points, group)]
+
+
 def flatten_committees(committees):
     """committees (lists of Points) -> (every point in order, the m + 1 segment offsets): the idx = NULL form of the committee entry points
     (blsmi_g?_sum_segmented, *_verify_aggregate_common*_batch)"""

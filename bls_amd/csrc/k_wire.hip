@@ -2,35 +2,10 @@
 // unit ops of the parity tests (split from k_hash.hip: the two halves compile in parallel).
 #include "hash.cuh"
 #include "device_io.cuh"
+#include "subgroup.cuh"
 
 // ---- compressed wire format (g1.go:185-249, g2.go:219-295) ----------------------------------------
-// IsInCorrectSubgroupAssumingOnCurve (g1.go:137-141, g2.go:293-295) tests r * P == infinity with a 255-bit
-// double-and-add.  The same predicate, for a point ON the curve, through the curve's endomorphisms:
-//   G1: phi(x, y) = (beta x, y) satisfies phi^2 + phi + 1 = 0; phi(P) = [-x^2] P implies (x^4 - x^2 + 1) P = r P = 0,
-//       and on G1 phi acts as that eigenvalue: two 64-bit multiplications instead of one 255-bit one.
-//   G2: psi (untwist-Frobenius-twist) satisfies psi^2 - t psi + q = 0 with t = x + 1; psi(P) = [x] P implies
-//       (q - x) P = (h1 r) P = 0, so the order of P divides r gcd(h1, h2) = r (the cofactors are coprime), and on
-//       G2 psi acts as x: one 64-bit multiplication.
-// The slow form is kept (in_subgroup_by_order) and the two are compared on curve points inside and outside
-// the subgroup by tests/test_gpu_verify.py::test_wire_format.
-template <class F> BLSMI_DEV bool in_subgroup_by_order(const Aff<F>& p) {
-    Jac<F> res = to_jac(p);
-    for (int i = BLSMI_R_ORDER_BITS - 2; i >= 0; i--) {
-        res = jac_double(res);
-        if ((C_R_ORDER[i >> 5] >> (i & 31)) & 1) res = jac_add_affine(res, p);
-    }
-    return res.inf != 0;
-}
-BLSMI_DEV bool in_subgroup(const G1Aff& p) {                             // [x^2] P + phi(P) == infinity
-    const G1Jac j = jac_mul_u64_public(aff_mul_u64_public(p, BLSMI_X_ABS), BLSMI_X_ABS);
-    G1Aff ph; ph.x = fp_store(fp_mul(p.x, C_BETA)); ph.y = p.y; ph.inf = 0;
-    return jac_add_affine(j, ph).inf != 0;
-}
-BLSMI_DEV bool in_subgroup(const G2Aff& p) {                             // [|x|] P + psi(P) == infinity  (x < 0)
-    const G2Jac j = aff_mul_u64_public(p, BLSMI_X_ABS);
-    G2Aff ps; psi(ps, p);
-    return jac_add_affine(j, ps).inf != 0;
-}
+// the subgroup predicates in_subgroup / in_subgroup_by_order: subgroup.cuh (shared with k_check.hip)
 BLSMI_DEV FpS load_be48_masked(const u8* p) {                            // clears the three flag bits of the first byte
     const u32* w32 = reinterpret_cast<const u32*>(p);
     u32 w[12];

@@ -118,6 +118,13 @@ __global__ void k_debug_fq(int op, const u64* a, const u64* b, u64* out, u8* fla
 __global__ void k_debug_fq2(int op, const u64* a, const u64* b, u64* out, u8* flag, size_t n);
 __global__ void k_debug_swu_g1(const u64* a, u64* out, size_t n);
 __global__ void k_debug_swu_g2(const u64* a, u64* out, size_t n);
+// k_check.hip
+__global__ void k_g1_check(const u8* pts, const u8* in_inf, int check, u8* status, size_t n);
+__global__ void k_g1_check_jac(const u64* pts, int check, u8* status, size_t n);
+__global__ void k_g2_check(const u8* pts, const u8* in_inf, int check, u8* status, size_t n);
+__global__ void k_g2_check_jac(const u64* pts, int check, u8* status, size_t n);
+__global__ void k_g2_check_pair(const u8* pts, const u8* in_inf, int check, u8* status, size_t n);
+__global__ void k_g2_check_jac_pair(const u64* pts, int check, u8* status, size_t n);
 // k_hash_pair.hip
 __global__ void k_hash_g2_pair(const u8* msgs, const u64* off, u8* good, u8* out, size_t n, unsigned redo_every);
 __global__ void k_hash_g2_front(const u8* msgs, const u64* off, u8* good, i32* jbuf, size_t n, unsigned redo_every);

@@ -1119,6 +1119,46 @@ int verify_serialized_host(int kind, const uint8_t* msgs, const uint64_t* off, c
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
+// Point validation (blsmi 0.14): the status byte of n points as they arrive -- affine wire records (+ optional infinity flags) or, jac, the
+// reference's in-memory Jacobian records -- in ONE launch for every n (k_check.hip).  check: 0 / 1 / 2 as decompress_dev.  Reads only.
+int check_dev(const GroupKernels& gk, bool jac, const void* d_pts, const void* d_in_inf, int check, void* d_status, size_t n, hipStream_t s) {
+    if (jac) launch_items(gk.check_jac, n, s, d_pts, check, d_status, n);
+    else launch_items(gk.check, n, s, d_pts, d_in_inf, check, d_status, n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+inline int check_args(const void* pts, const void* status, int check, size_t n) {   // what both forms refuse before any device work
+    if (check < 0 || check > 2) return BLSMI_E_ARG;
+    if (n && (!pts || !status)) return BLSMI_E_ARG;
+    return BLSMI_OK;
+}
+int check_host(int group, bool jac, const uint8_t* pts, const uint8_t* in_inf, int check, uint8_t* status, size_t n) {
+    { const int rc = check_args(pts, status, check, n); if (rc) return rc; }
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT();
+    const GroupKernels& gk = group_kernels(group);
+    const size_t IB = rec_bytes(gk.wire_bytes, jac);
+    const bool flags = in_inf && !jac;
+    DBuf di, dinf, dst;
+    HIPCHK(di.alloc(IB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(dst.alloc(n));
+    HIPCHK(hipMemcpyAsync(di.p, pts, IB * n, hipMemcpyHostToDevice, g_stream));
+    if (flags) HIPCHK(hipMemcpyAsync(dinf.p, in_inf, n, hipMemcpyHostToDevice, g_stream));
+    { const int rc = check_dev(gk, jac, di.p, flags ? dinf.p : nullptr, check, dst.p, n, g_stream); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(status, dst.p, n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+int check_dev_api(int group, const void* d_pts, const void* d_in_inf, int jac, int check, void* d_status, size_t n, void* stream) {
+    { const int rc = check_args(d_pts, d_status, check, n); if (rc) return rc; }
+    if (jac && d_in_inf) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT_AT(d_status);
+    UseStream us(stream);
+    { const int rc = check_dev(group_kernels(group), jac != 0, d_pts, d_in_inf, check, d_status, n, g_stream); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
 int compress_host(int group, const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) {
     if (n && (!pts || !out)) return BLSMI_E_ARG;
     LOCK_AND_INIT();
@@ -1592,6 +1632,12 @@ BLSMI_API int blsmi_g1_decompress_batch(const uint8_t* in, int check, uint8_t* o
 BLSMI_API int blsmi_g2_decompress_batch(const uint8_t* in, int check, uint8_t* out, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_host(2, in, check, out, out_inf, err, n); }
 BLSMI_API int blsmi_g1_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host(1, pts, in_inf, out, n); }
 BLSMI_API int blsmi_g2_compress_batch(const uint8_t* pts, const uint8_t* in_inf, uint8_t* out, size_t n) { return compress_host(2, pts, in_inf, out, n); }
+BLSMI_API int blsmi_g1_check_batch(const uint8_t* pts, const uint8_t* in_inf, int check, uint8_t* status, size_t n) { return check_host(1, false, pts, in_inf, check, status, n); }
+BLSMI_API int blsmi_g2_check_batch(const uint8_t* pts, const uint8_t* in_inf, int check, uint8_t* status, size_t n) { return check_host(2, false, pts, in_inf, check, status, n); }
+BLSMI_API int blsmi_g1_check_batch_jac(const uint64_t* pts_jac, int check, uint8_t* status, size_t n) { return check_host(1, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, check, status, n); }
+BLSMI_API int blsmi_g2_check_batch_jac(const uint64_t* pts_jac, int check, uint8_t* status, size_t n) { return check_host(2, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, check, status, n); }
+BLSMI_API int blsmi_g1_check_batch_dev(const void* d_pts, const void* d_in_inf, int jac, int check, void* d_status, size_t n, void* stream) { return check_dev_api(1, d_pts, d_in_inf, jac, check, d_status, n, stream); }
+BLSMI_API int blsmi_g2_check_batch_dev(const void* d_pts, const void* d_in_inf, int jac, int check, void* d_status, size_t n, void* stream) { return check_dev_api(2, d_pts, d_in_inf, jac, check, d_status, n, stream); }
 
 // ---- the verify surface over the reference's in-memory points (blsmi 0.6; include/blsmi.h "in-memory points") ---------------------------
 // Keys and signatures as the Go values hold them: bls.G2Projective = 36 x u64, bls.G1Projective = 18 x u64 (x, y, z; FQ = 6 LE u64 Montgomery

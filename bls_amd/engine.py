@@ -1457,3 +1457,67 @@ def g1pubs_verify_batch_rlc_grouped_locate_jac(msgs, msg_idx, pks, sigs, scalars
 
 def g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac(msgs32, domain8, msg_idx, pks, sigs, scalars=None, block=0):
     return _verify_batch_rlc_grouped_locate("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac", 2, True, msgs32, msg_idx, pks, sigs, None, scalars, block, domain8)
+
+
+# ---- point validation (blsmi 0.14): on-curve and subgroup status of points in either form ----------------------------------------------
+POINT_OK, POINT_INFINITY, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = 0, 1, 3, 4   # BLSMI_POINT_* (3, 4: the decompression error codes)
+_V = C.c_void_p
+# the argument types of the six entry points of 0.14, as include/blsmi.h declares them (tests/test_point_check_cpu.py compares)
+ARGTYPES_0_14 = {
+    "blsmi_g1_check_batch": [_u8p, _u8p, C.c_int, _u8p, C.c_size_t],
+    "blsmi_g2_check_batch": [_u8p, _u8p, C.c_int, _u8p, C.c_size_t],
+    "blsmi_g1_check_batch_jac": [_u64p, C.c_int, _u8p, C.c_size_t],
+    "blsmi_g2_check_batch_jac": [_u64p, C.c_int, _u8p, C.c_size_t],
+    "blsmi_g1_check_batch_dev": [_V, _V, C.c_int, C.c_int, _V, C.c_size_t, _V],
+    "blsmi_g2_check_batch_dev": [_V, _V, C.c_int, C.c_int, _V, C.c_size_t, _V],
+}
+
+
+def _fn_0_14(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_14[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _check_batch(name, pb, pts, n, in_inf, check):
+    a = _u8(pts, pb * n) if n else np.zeros(1, np.uint8)
+    f = _u8(in_inf, n) if in_inf is not None else None
+    status = np.zeros(max(1, n), dtype=np.uint8)
+    _check(_fn_0_14(name)(_p8(a), _p8(f), int(check), _p8(status), n), name[len("blsmi_"):])
+    return status[:n].copy()
+
+
+def g1_check_batch(pts, n, in_inf=None, check=1):
+    """IsOnCurve / IsInCorrectSubgroupAssumingOnCurve of n affine G1 records (96 bytes each; in_inf: optional infinity flags) -> (n,) uint8:
+    0 good, 1 infinity, 3 not on the curve, 4 outside the subgroup.  check: 0 the curve equation only, 1 the endomorphism test, 2 r * P."""
+    return _check_batch("blsmi_g1_check_batch", 96, pts, n, in_inf, check)
+
+
+def g2_check_batch(pts, n, in_inf=None, check=1):
+    return _check_batch("blsmi_g2_check_batch", 192, pts, n, in_inf, check)
+
+
+def _check_batch_jac(name, jb, jac, n, check):
+    a, pa = _j64(jac, jb * n)
+    status = np.zeros(max(1, n), dtype=np.uint8)
+    _check(_fn_0_14(name)(pa, int(check), _p8(status), n), name[len("blsmi_"):])
+    return status[:n].copy()
+
+
+def g1_check_batch_jac(jac, n, check=1):
+    """the same over in-memory G1 points (144 bytes each, z == 0: infinity): no conversion to affine, no inversion"""
+    return _check_batch_jac("blsmi_g1_check_batch_jac", 144, jac, n, check)
+
+
+def g2_check_batch_jac(jac, n, check=1):
+    return _check_batch_jac("blsmi_g2_check_batch_jac", 288, jac, n, check)
+
+
+def check_batch_dev(group, d_pts, d_in_inf, n, d_status, jac=False, check=1, stream=0):
+    """device-pointer form (ints): d_pts affine records, or in-memory points with jac=True (then d_in_inf must be 0).  The n status bytes are
+    in d_status when the call returns (it synchronises); the caller's point buffers are only read."""
+    if jac and d_in_inf:
+        raise ValueError("the in-memory form takes no flags: z == 0 is infinity")
+    name = "blsmi_g1_check_batch_dev" if group == "g1" else "blsmi_g2_check_batch_dev"
+    _check(_fn_0_14(name)(d_pts or 0, d_in_inf or 0, int(bool(jac)), int(check), d_status or 0, n, stream or 0), name[len("blsmi_"):])

@@ -10,7 +10,7 @@ pairing and hash operation runs in the HIP kernels of libblsmi.so (no CPU fallba
 plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks.
 """
 from . import engine
-from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum  # noqa: F401
+from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum, points_valid  # noqa: F401
 
 SIG_GROUP, PK_GROUP = 2, 1
 
@@ -352,3 +352,14 @@ def VerifyAggregateCommonWithDomainBatch(sigs, committees, msgs32, domain8):
     fn = engine.g1pubs_verify_aggregate_common_with_domain_batch_jac if jac else engine.g1pubs_verify_aggregate_common_with_domain_batch
     ok, _ = fn(b"".join(bytes(x) for x in msgs32), domain8, keys, npk, None, off, sg)
     return [bool(x) for x in ok]
+
+
+def ValidatePublicKeys(pubs):
+    """[pub is on the curve and in the prime-order subgroup] -- what the randomised batch verifications and the default multiplications
+    presuppose and Deserialize* guarantees -- for keys built any other way, held in either form, in one call; infinity counts as valid,
+    as in the reference's IsOnCurve / IsInCorrectSubgroupAssumingOnCurve"""
+    return points_valid([p.p for p in pubs], PK_GROUP)
+
+
+def ValidateSignatures(sigs):
+    return points_valid([s.s for s in sigs], SIG_GROUP)

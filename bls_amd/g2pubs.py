@@ -11,7 +11,7 @@ plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks, and Prepar
 through G2AffineToPrepared (g2.go:639-801) ONCE into tables resident on the device instead of on every Verify (pairing.go:140-147).
 """
 from . import engine
-from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum  # noqa: F401
+from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum, points_valid  # noqa: F401
 
 SIG_GROUP, PK_GROUP = 1, 2
 
@@ -274,3 +274,14 @@ def VerifyAggregateCommonBatch(sigs, committees, msgs):
     fn = engine.g2pubs_verify_aggregate_common_batch_jac if jac else engine.g2pubs_verify_aggregate_common_batch
     ok, _ = fn(msgs, keys, npk, None, off, sg)
     return [bool(x) for x in ok]
+
+
+def ValidatePublicKeys(pubs):
+    """[pub is on the curve and in the prime-order subgroup] -- what the randomised batch verifications and the default multiplications
+    presuppose and Deserialize* guarantees -- for keys built any other way, held in either form, in one call; infinity counts as valid,
+    as in the reference's IsOnCurve / IsInCorrectSubgroupAssumingOnCurve"""
+    return points_valid([p.p for p in pubs], PK_GROUP)
+
+
+def ValidateSignatures(sigs):
+    return points_valid([s.s for s in sigs], SIG_GROUP)

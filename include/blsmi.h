@@ -81,7 +81,9 @@ void blsmi_shutdown(void);
  * (blsmi_g?_sum_segmented_u64); no existing prototype changes, no new option.  0.12 adds the randomised batch verification that
  * finds the bad tuples by blocks (blsmi_g?pubs_*verify*_batch_rlc_locate[_jac]); no existing prototype changes, no new option.  0.13 adds the grouped
  * randomised batch verification that finds the bad tuples by cells (blsmi_g?pubs_*verify*_batch_rlc_grouped_locate[_jac]); no existing prototype
- * changes, no new option.  The string below still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12 and 0.13 by the presence of
+ * changes, no new option.  0.14 adds the batch point validation (blsmi_g?_check_batch[_jac|_dev]: on-curve and subgroup status of points in either
+ * form, no inversion, no square root) and the BLSMI_POINT_* status names; no existing prototype changes, no new option.  The string below still begins
+ * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13 and 0.14 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -771,6 +773,38 @@ int blsmi_pairing_product_batch_dev(const void *d_g1_aff, const void *d_g2_aff, 
                                     const void *d_seg_off, size_t m, void *d_out_fq12, void *d_is_one, void *stream);
 int blsmi_pairing_product_batch_jac_dev(const void *d_g1_jac, const void *d_g2_jac, size_t np,
                                         const void *d_seg_off, size_t m, void *d_out_fq12, void *d_is_one, void *stream);
+
+/* ---- point validation (blsmi 0.14) ---------------------------------------------------------------------------------------------------
+ * The tool behind every "PRECONDITION: ... in the prime-order subgroups" above: G?Affine.IsOnCurve (g1.go:93-105, g2.go:118-130) and
+ * IsInCorrectSubgroupAssumingOnCurve (g1.go:137-141, g2.go:293-295) of n points in the form the caller holds them, without the detour
+ * through compress + decompress(check).  status[i] is one of the BLSMI_POINT_* values below; NOT_ON_CURVE and NOT_IN_SUBGROUP are
+ * deliberately the error codes 3 and 4 of blsmi_g?_decompress_batch.  A point is usable where the reference's
+ * IsOnCurve() && IsInCorrectSubgroupAssumingOnCurve() holds: status OK or INFINITY (the reference returns true for infinity in both).
+ *   check   as in the decompression calls: 0 the curve equation only (NOT_IN_SUBGROUP never appears), 1 the subgroup test through the
+ *           curve's endomorphisms ([x^2] P + phi(P) on G1, [|x|] P + psi(P) on G2), 2 the reference's r * P == infinity walk (same
+ *           verdicts, ~4x / ~2x the work).  Any other value: BLSMI_E_ARG.
+ *   order   infinity gives INFINITY; otherwise a failed curve equation gives NOT_ON_CURVE and the subgroup test, which assumes a curve
+ *           point, is not consulted; otherwise a failed subgroup test gives NOT_IN_SUBGROUP.
+ *   records are read exactly as every other entry point reads them.  Infinity is the all-zero affine record, a set in_inf byte, or
+ *           z == 0 in a Jacobian record (whatever x and y hold).  A coordinate whose big-endian value (affine) or limb image (Jacobian)
+ *           is not below q is read as 0, as everywhere in this library, and the point is judged AS THAT POINT: an affine record with
+ *           x >= q is the point (0, y).
+ *   cost    the curve equation is tested on the coordinates as they arrive (Jacobian: Y^2 == X^3 + b Z^6) and the subgroup verdict is
+ *           the infinity flag of a sum: no field inversion and no square root, one kernel launch for every n.
+ * n == 0 returns BLSMI_OK; NULL pts or status with n > 0 is BLSMI_E_ARG before any device work.  The call runs on ONE device: it is not
+ * sharded and does not join the request combiner.  The _dev forms take every buffer on one of the library's devices (d_status: n bytes;
+ * jac != 0: d_pts holds Jacobian records and d_in_inf must be NULL, else BLSMI_E_ARG) and leave the caller's point buffers untouched.
+ * G2 runs a lane pair per point by default and one lane per point under BLSMI_LAYOUT=single; the statuses are the same. */
+#define BLSMI_POINT_OK 0              /* a finite point of the prime-order subgroup (check 0: of the curve) */
+#define BLSMI_POINT_INFINITY 1        /* the point at infinity */
+#define BLSMI_POINT_NOT_ON_CURVE 3    /* = the decompression error "x is not on the curve" */
+#define BLSMI_POINT_NOT_IN_SUBGROUP 4 /* on the curve, outside the prime-order subgroup (= the decompression error 4) */
+int blsmi_g1_check_batch(const uint8_t *pts /* n*96 */, const uint8_t *in_inf /* n, may be NULL */, int check, uint8_t *status /* n */, size_t n);
+int blsmi_g2_check_batch(const uint8_t *pts /* n*192 */, const uint8_t *in_inf /* n, may be NULL */, int check, uint8_t *status /* n */, size_t n);
+int blsmi_g1_check_batch_jac(const uint64_t *pts_jac /* n*18 */, int check, uint8_t *status /* n */, size_t n);
+int blsmi_g2_check_batch_jac(const uint64_t *pts_jac /* n*36 */, int check, uint8_t *status /* n */, size_t n);
+int blsmi_g1_check_batch_dev(const void *d_pts, const void *d_in_inf, int jac, int check, void *d_status, size_t n, void *stream);
+int blsmi_g2_check_batch_dev(const void *d_pts, const void *d_in_inf, int jac, int check, void *d_status, size_t n, void *stream);
 
 #ifdef __cplusplus
 }

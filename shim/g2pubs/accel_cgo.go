@@ -124,6 +124,40 @@ func VerifyBatch(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) []bool {
 	return out
 }
 
+// ValidatePublicKeys: out[i] = pubs[i] is on the curve and in the prime-order subgroup (IsOnCurve && IsInCorrectSubgroupAssumingOnCurve,
+// true for infinity as upstream) -- what the randomised batch verifications and the default multiplications presuppose and Deserialize*
+// guarantees.  For keys built any other way; the points go over as they lie, nothing is inverted (INTEGRATION.md 2l).
+func ValidatePublicKeys(pubs []*PublicKey) []bool {
+	n := len(pubs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	pk := packKeys(pubs)
+	st := make([]byte, n)
+	must(C.blsmi_g2_check_batch_jac(u64(pk), 1, u8(st), C.size_t(n)), "g2_check_batch_jac")
+	for i := range st {
+		out[i] = st[i] == C.BLSMI_POINT_OK || st[i] == C.BLSMI_POINT_INFINITY
+	}
+	return out
+}
+
+// ValidateSignatures: the same for signatures.
+func ValidateSignatures(sigs []*Signature) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	sg := packSigs(sigs)
+	st := make([]byte, n)
+	must(C.blsmi_g1_check_batch_jac(u64(sg), 1, u8(st), C.size_t(n)), "g1_check_batch_jac")
+	for i := range st {
+		out[i] = st[i] == C.BLSMI_POINT_OK || st[i] == C.BLSMI_POINT_INFINITY
+	}
+	return out
+}
+
 // VerifyBatchRandomized gives VerifyBatch's verdicts from ONE pairing check over the whole batch (small-exponent batch
 // verification: the library draws fresh random 64-bit weights per call; INTEGRATION.md 2g).  When the check holds every tuple is
 // true; when it fails the library computes the per-tuple verdicts.  Keys and signatures must lie in the prime-order subgroups,
@@ -145,7 +179,7 @@ func VerifyBatchRandomized(msgs [][]byte, pubs []*PublicKey, sigs []*Signature) 
 	return out
 }
 
-// VerifyBatchRandomizedLocate is VerifyBatchRandomized for input an adversary may have touched (INTEGRATION.md 2j): when the combined
+// VerifyBatchRandomizedLocate is VerifyBatchRandomized for input an adversary may have touched (INTEGRATION.md 2l): when the combined
 // check fails, one pairing equation per block of `block` tuples (0: the library chooses; else even and at least 2) finds the blocks that
 // hold, and only the tuples of the others go through the per-tuple path.  Verdicts as VerifyBatch; an odd block panics, as every
 // library error does.
