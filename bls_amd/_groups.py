@@ -62,6 +62,9 @@ class Point:
 
     def serialize(self):
         """CompressG1 / CompressG2 (g1.go:230-249, g2.go:269-289)."""
+        if self.jac is not None:                                              # an in-memory point: ToAffine + Compress in one library call
+            fn = engine.g1_compress_batch_jac if self.group == 1 else engine.g2_compress_batch_jac
+            return fn(self.jac, 1)[0].tobytes()
         fn = engine.g1_compress_batch if self.group == 1 else engine.g2_compress_batch
         return fn(self.bytes_or_zero(), 1, [1 if self.infinity else 0])[0].tobytes()
 
@@ -73,6 +76,17 @@ class Point:
         if err[0]:
             raise DeserializeError(_DECODE_ERRORS.get(int(err[0]), "decode error"))
         return Point(None if inf[0] else out[0].tobytes(), group)
+
+    @staticmethod
+    def deserialize_many(blobs, group):
+        """DecompressG? with the subgroup check + ToProjective of every blob in ONE library call -> (in-memory Points, error codes).  The
+        point of a blob with an error code is the reference's zero point, as the library hands it back."""
+        n = len(blobs)
+        if n == 0:
+            return [], []
+        fn = engine.g1_decompress_batch_jac if group == 1 else engine.g2_decompress_batch_jac
+        jac, _, err = fn(b"".join(bytes(b) for b in blobs), n, True)
+        return [Point(None, group, jac=jac[i].tobytes()) for i in range(n)], [int(e) for e in err]
 
 
 def point_sum(points, group):
@@ -88,6 +102,39 @@ def point_sum(points, group):
     inf = [1 if p.infinity else 0 for p in points]
     fn = engine.g1_sum if group == 1 else engine.g2_sum
     return Point(fn(buf, n, inf), group)
+
+
+def deserialize_objects(blobs, group, wrap):
+    """the batch Deserialize* of the packages: (objects, errors) from one library call; objects[i] is None where errors[i] != 0"""
+    pts, err = Point.deserialize_many(blobs, group)
+    return [None if e else wrap(p) for p, e in zip(pts, err)], err
+
+
+def serialize_points(points, group):
+    """[p.serialize() for p in points] in one library call where every point is held in memory form (else one call too: the wire-form
+    points become z = 1 records on the host, as in point_statuses)"""
+    n = len(points)
+    if n == 0:
+        return []
+    fn = engine.g1_compress_batch_jac if group == 1 else engine.g2_compress_batch_jac
+    out = fn(b"".join(p.jac if p.jac is not None else _wire_as_jac(p) for p in points), n)
+    return [out[i].tobytes() for i in range(n)]
+
+
+def verify_serialized_randomized(pkg, pk_group, sig_group, msgs, pub_bytes, sig_bytes, block):
+    """VerifySerializedBatchRandomized of both packages: two decompressions with the subgroup check into flat in-memory buffers, then the
+    package's *_verify_batch_rlc_locate_jac, whose (ok, bitmap, combined, rechecked) comes back.  An undecodable element is the zero point
+    there (z == 0): its tuple gets False."""
+    n = len(msgs)
+    if not (len(pub_bytes) == len(sig_bytes) == n):
+        raise ValueError("length mismatch")
+    if n == 0:
+        return [], b"", 1, 0
+    dec = {1: engine.g1_decompress_batch_jac, 2: engine.g2_decompress_batch_jac}
+    pk, _, _ = dec[pk_group](b"".join(bytes(b) for b in pub_bytes), n, True)
+    sg, _, _ = dec[sig_group](b"".join(bytes(b) for b in sig_bytes), n, True)
+    fn = getattr(engine, pkg + "_verify_batch_rlc_locate_jac")
+    return fn(msgs, pk.reshape(-1), sg.reshape(-1), None, block)
 
 
 def all_in_memory(points):

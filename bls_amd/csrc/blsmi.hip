@@ -321,6 +321,7 @@ struct GroupKernels {
     Laid<BLSMI_K(k_g1_segsum_fold)> segsum_fold; BLSMI_K(k_g1_segsum_final) segsum_final;
     BLSMI_K(k_g1_compress) compress; BLSMI_K(k_g1_decompress) decompress; BLSMI_K(k_g1_decompress_waves) decompress_waves; BLSMI_K(k_g1_jac_to_affine) jac_to_affine;
     Laid<BLSMI_K(k_g1_check)> check; Laid<BLSMI_K(k_g1_check_jac)> check_jac;   // point validation (k_check.hip): affine records, in-memory Jacobian records
+    BLSMI_K(k_g1_decompress_jac) decompress_jac; BLSMI_K(k_g1_compress_jac) compress_jac;   // the wire format <-> in-memory records (blsmi 0.15)
     BLSMI_K(k_msm_recode_g1) msm_recode; BLSMI_K(k_msm_rawpts_g1) msm_rawpts; Laid<BLSMI_K(k_g1_msm_bucket)> msm_bucket; BLSMI_K(k_g1_msm_chunk) msm_chunk; BLSMI_K(k_g1_msm_fold) msm_fold; BLSMI_K(k_g1_msm_final) msm_final;
     Laid<BLSMI_K(k_g1_msm_bucket_raw)> msm_bucket_raw; Laid<BLSMI_K(k_g1_msm_chunk2)> msm_chunk2; Laid<BLSMI_K(k_g1_msm_fold2)> msm_fold2; BLSMI_K(k_g1_msm_final2) msm_final2;
 #undef BLSMI_K
@@ -341,6 +342,7 @@ inline GroupKernels group_row(int group, bool pair_forms) {
         .segsum_chunk = one(KERNEL_OF(k_g1_segsum_chunk)), .segsum_chunk_jac = KERNEL_OF(k_g1_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g1_segsum_chunk_u64), .segsum_fold = one(KERNEL_OF(k_g1_segsum_fold)), .segsum_final = KERNEL_OF(k_g1_segsum_final),
         .compress = KERNEL_OF(k_g1_compress), .decompress = KERNEL_OF(k_g1_decompress), .decompress_waves = KERNEL_OF(k_g1_decompress_waves), .jac_to_affine = KERNEL_OF(k_g1_jac_to_affine),
         .check = one(KERNEL_OF(k_g1_check)), .check_jac = one(KERNEL_OF(k_g1_check_jac)),
+        .decompress_jac = KERNEL_OF(k_g1_decompress_jac), .compress_jac = KERNEL_OF(k_g1_compress_jac),
         .msm_recode = KERNEL_OF(k_msm_recode_g1), .msm_rawpts = KERNEL_OF(k_msm_rawpts_g1), .msm_bucket = one(KERNEL_OF(k_g1_msm_bucket)), .msm_chunk = KERNEL_OF(k_g1_msm_chunk), .msm_fold = KERNEL_OF(k_g1_msm_fold), .msm_final = KERNEL_OF(k_g1_msm_final),
         .msm_bucket_raw = one(KERNEL_OF(k_g1_msm_bucket_raw)), .msm_chunk2 = one(KERNEL_OF(k_g1_msm_chunk2)), .msm_fold2 = one(KERNEL_OF(k_g1_msm_fold2)), .msm_final2 = KERNEL_OF(k_g1_msm_final2)};
     return {
@@ -351,6 +353,7 @@ inline GroupKernels group_row(int group, bool pair_forms) {
         .segsum_chunk = always(KERNEL_OF(k_g2_segsum_chunk_pair)), .segsum_chunk_jac = KERNEL_OF(k_g2_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g2_segsum_chunk_u64), .segsum_fold = always(KERNEL_OF(k_g2_segsum_fold_pair)), .segsum_final = KERNEL_OF(k_g2_segsum_final),
         .compress = KERNEL_OF(k_g2_compress), .decompress = KERNEL_OF(k_g2_decompress), .decompress_waves = KERNEL_OF(k_g2_decompress_waves), .jac_to_affine = KERNEL_OF(k_g2_jac_to_affine),
         .check = opt(KERNEL_OF(k_g2_check), KERNEL_OF(k_g2_check_pair)), .check_jac = opt(KERNEL_OF(k_g2_check_jac), KERNEL_OF(k_g2_check_jac_pair)),
+        .decompress_jac = KERNEL_OF(k_g2_decompress_jac), .compress_jac = KERNEL_OF(k_g2_compress_jac),
         .msm_recode = KERNEL_OF(k_msm_recode_g2), .msm_rawpts = KERNEL_OF(k_msm_rawpts_g2), .msm_bucket = opt(KERNEL_OF(k_g2_msm_bucket), KERNEL_OF(k_g2_msm_bucket_pair)), .msm_chunk = KERNEL_OF(k_g2_msm_chunk), .msm_fold = KERNEL_OF(k_g2_msm_fold), .msm_final = KERNEL_OF(k_g2_msm_final),
         .msm_bucket_raw = always(KERNEL_OF(k_g2_msm_bucket_raw_pair)), .msm_chunk2 = opt(KERNEL_OF(k_g2_msm_chunk2), KERNEL_OF(k_g2_msm_chunk2_pair)), .msm_fold2 = opt(KERNEL_OF(k_g2_msm_fold2), KERNEL_OF(k_g2_msm_fold2_pair)), .msm_final2 = KERNEL_OF(k_g2_msm_final2)};
 }

@@ -84,6 +84,15 @@ BLSMI_DEV void store_be48(u8* p, const Fp<L, V>& x) {
 #pragma unroll
     for (int j = 0; j < 12; j++) w32[11 - j] = __builtin_bswap32(w[j]);
 }
+// one 48-byte half of a COMPRESSED record (g1.go:230-249, g2.go:269-289): x big-endian (zeros for infinity), `flags` OR-ed into the first byte
+template <int L, int V>
+BLSMI_DEV void store_wire48(u8* p, const Fp<L, V>& x, i32 inf, u32 flags) {
+    u32 w[12];
+    fp_to_words(x, w);
+    u32* w32 = reinterpret_cast<u32*>(p);
+#pragma unroll
+    for (int j = 0; j < 12; j++) w32[11 - j] = __builtin_bswap32((inf ? 0u : w[j]) | (j == 11 ? flags << 24 : 0u));
+}
 BLSMI_DEV FpS load_m384(const u64* p) {
     const u32* w32 = reinterpret_cast<const u32*>(p);
     u32 w[12];

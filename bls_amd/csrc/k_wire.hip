@@ -14,10 +14,22 @@ BLSMI_DEV FpS load_be48_masked(const u8* p) {                            // clea
     w[11] &= 0x1fffffffu;
     return fp_from_words(w);
 }
+// The record writers of the decompression bodies: the affine wire record (store_g1 / store_g2: all zero for an unusable point) or the
+// reference's in-memory record (blsmi 0.15, store_jac_m384: (x, y, 1), and (0, 1, 0) for an unusable point), whose infinity flags may stay home.
+struct WireRecord {
+    using out_t = u8; static constexpr bool inf_optional = false;
+    static BLSMI_DEV void put(u8* out, size_t t, const G1Aff& a) { store_g1(out + 96 * t, a); }
+    static BLSMI_DEV void put(u8* out, size_t t, const G2Aff& a) { store_g2(out + 192 * t, a); }
+};
+struct JacRecord {
+    using out_t = u64; static constexpr bool inf_optional = true;
+    static BLSMI_DEV void put(u64* out, size_t t, const G1Aff& a) { store_jac_m384(out + 18 * t, a); }
+    static BLSMI_DEV void put(u64* out, size_t t, const G2Aff& a) { store_jac_m384(out + 36 * t, a); }
+};
 // WAVE: one point per 64-lane workgroup (t = blockIdx.x, every lane the same values, lane 0 stores), the square root's exponentiation
 // with one limb per lane (fp_row.cuh) -- the smallest calls; no subgroup test in that form (the caller runs it as a level program)
-template <bool WAVE>
-BLSMI_DEV void g1_decompress_body(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n) {
+template <bool WAVE, class W = WireRecord>
+BLSMI_DEV void g1_decompress_body(const u8* in, int check, typename W::out_t* out, u8* out_inf, u8* err, size_t n) {
     const size_t t = WAVE ? (size_t)blockIdx.x : (size_t)blockIdx.x * WG + threadIdx.x;
     const size_t tt = t < n ? t : n - 1;
     const u8* c = in + 48 * tt;
@@ -38,14 +50,16 @@ BLSMI_DEV void g1_decompress_body(const u8* in, int check, u8* out, u8* out_inf,
     else if (!sub) e = 4;
     if (t < n && (!WAVE || threadIdx.x == 0)) {
         a.inf = (inf || e) ? -1 : 0;
-        store_g1(out + 96 * t, a);
-        out_inf[t] = inf; err[t] = e;
+        W::put(out, t, a);
+        if (!W::inf_optional || out_inf) out_inf[t] = inf;
+        err[t] = e;
     }
 }
 KERNEL2 k_g1_decompress(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n) { g1_decompress_body<false>(in, check, out, out_inf, err, n); }
+KERNEL2 k_g1_decompress_jac(const u8* in, int check, u64* out, u8* out_inf, u8* err, size_t n) { g1_decompress_body<false, JacRecord>(in, check, out, out_inf, err, n); }   // DecompressG1(b).ToProjective()
 __global__ void __launch_bounds__(64, 2) k_g1_decompress_waves(const u8* in, u8* out, u8* out_inf, u8* err, size_t n) { g1_decompress_body<true>(in, 0, out, out_inf, err, n); }
-template <bool WAVE>
-BLSMI_DEV void g2_decompress_body(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n) {
+template <bool WAVE, class W = WireRecord>
+BLSMI_DEV void g2_decompress_body(const u8* in, int check, typename W::out_t* out, u8* out_inf, u8* err, size_t n) {
     const size_t t = WAVE ? (size_t)blockIdx.x : (size_t)blockIdx.x * WG + threadIdx.x;
     const size_t tt = t < n ? t : n - 1;
     const u8* c = in + 96 * tt;
@@ -66,11 +80,13 @@ BLSMI_DEV void g2_decompress_body(const u8* in, int check, u8* out, u8* out_inf,
     else if (!sub) e = 4;
     if (t < n && (!WAVE || threadIdx.x == 0)) {
         a.inf = (inf || e) ? -1 : 0;
-        store_g2(out + 192 * t, a);
-        out_inf[t] = inf; err[t] = e;
+        W::put(out, t, a);
+        if (!W::inf_optional || out_inf) out_inf[t] = inf;
+        err[t] = e;
     }
 }
 KERNEL k_g2_decompress(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n) { g2_decompress_body<false>(in, check, out, out_inf, err, n); }
+KERNEL k_g2_decompress_jac(const u8* in, int check, u64* out, u8* out_inf, u8* err, size_t n) { g2_decompress_body<false, JacRecord>(in, check, out, out_inf, err, n); }
 __global__ void __launch_bounds__(64) k_g2_decompress_waves(const u8* in, u8* out, u8* out_inf, u8* err, size_t n) { g2_decompress_body<true>(in, 0, out, out_inf, err, n); }
 // Small batches: the decompression kernels run without their subgroup test, the test runs as a level program of the latency
 // path (k_lat.hip: subgrp1 / subgrp2, one point per wave) and this kernel applies its verdict -- what the kernels above do
@@ -160,6 +176,29 @@ BLSMI_DEV void jac_to_affine_body(const u64* in, u8* out, u8* out_inf, size_t n)
 }
 KERNEL2 k_g1_jac_to_affine(const u64* in, u8* out, u8* out_inf, size_t n) { jac_to_affine_body<FpS, 96>(in, out, out_inf, n); }
 KERNEL k_g2_jac_to_affine(const u64* in, u8* out, u8* out_inf, size_t n) { jac_to_affine_body<Fp2S, 192>(in, out, out_inf, n); }
+// Serialize() of n in-memory points in one pass (blsmi 0.15): the ToAffine above, then CompressG1 / CompressG2 (g1.go:230-249, g2.go:269-289)
+// on the affine point while it is still in registers -- the bytes k_g?_compress writes for the record and flag k_g?_jac_to_affine writes.
+// z == 0 gives 0xc0 and zeros whatever x and y hold; there is no curve test.
+template <class F>
+BLSMI_DEV void compress_jac_body(const u64* in, u8* out, size_t n) {
+    constexpr int NC = sizeof(F) / sizeof(FpS);
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    const size_t tt = t < n ? t : n - 1;
+    bool z_one;
+    const Jac<F> j = load_jac_m384<F>(in + (size_t)18 * NC * tt, &z_one);
+    Aff<F> a;
+    if (__all(z_one || j.inf)) { a.x = j.x; a.y = j.y; a.inf = j.inf; }
+    else a = jac_to_affine(j);
+    if (t >= n) return;
+    u8* o = out + (size_t)48 * NC * t;
+    if constexpr (NC == 1) store_wire48(o, a.x, a.inf, a.inf ? 0xc0u : 0x80u | (fp_gt_half(a.y) ? 0x20u : 0u));
+    else {
+        store_wire48(o, a.x.c1, a.inf, a.inf ? 0xc0u : 0x80u | (fp2_sign_is_neg(a.y) ? 0x20u : 0u));    // x.c1 || x.c0 on the wire
+        store_wire48(o + 48, a.x.c0, a.inf, 0u);
+    }
+}
+KERNEL2 k_g1_compress_jac(const u64* in, u8* out, size_t n) { compress_jac_body<FpS>(in, out, n); }
+KERNEL k_g2_compress_jac(const u64* in, u8* out, size_t n) { compress_jac_body<Fp2S>(in, out, n); }
 // the other direction, for results that go back into a Go value (AggregatePublicKeys / AggregateSignatures: one point): wire record
 // + infinity flag -> the in-memory record with z = 1
 // (in_inf: n flags, int32 -- the sums' -- or, inf_u8 != 0, bytes -- the multiplication kernels')

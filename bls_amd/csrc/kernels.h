@@ -101,8 +101,10 @@ __global__ void k_hash_g2_domain_redo(const u8* msgs32, const u8* domain, const 
 __global__ void k_write_generators(u8* g1, u8* g2);
 // k_wire.hip
 __global__ void k_g1_decompress(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n);
+__global__ void k_g1_decompress_jac(const u8* in, int check, u64* out, u8* out_inf, u8* err, size_t n);
 __global__ void k_g1_decompress_waves(const u8* in, u8* out, u8* out_inf, u8* err, size_t n);
 __global__ void k_g2_decompress(const u8* in, int check, u8* out, u8* out_inf, u8* err, size_t n);
+__global__ void k_g2_decompress_jac(const u8* in, int check, u64* out, u8* out_inf, u8* err, size_t n);
 __global__ void k_g2_decompress_waves(const u8* in, u8* out, u8* out_inf, u8* err, size_t n);
 __global__ void k_apply_subgroup(const u8* in_subgroup, u8* out, int rec_words, const u8* out_inf, u8* err, size_t n);
 __global__ void k_merge_flags(const u8* inf_pk, const u8* err_pk, const u8* inf_sig, const u8* err_sig, u8* flags, size_t n);
@@ -113,6 +115,8 @@ __global__ void k_g1_compress(const u8* pts, const u8* in_inf, u8* out, size_t n
 __global__ void k_g2_compress(const u8* pts, const u8* in_inf, u8* out, size_t n);
 __global__ void k_g1_jac_to_affine(const u64* in, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_jac_to_affine(const u64* in, u8* out, u8* out_inf, size_t n);
+__global__ void k_g1_compress_jac(const u64* in, u8* out, size_t n);
+__global__ void k_g2_compress_jac(const u64* in, u8* out, size_t n);
 __global__ void k_affine_to_jac(const u8* in, const void* in_inf, int inf_u8, int group, u64* out, size_t n);
 __global__ void k_debug_fq(int op, const u64* a, const u64* b, u64* out, u8* flag, size_t n);
 __global__ void k_debug_fq2(int op, const u64* a, const u64* b, u64* out, u8* flag, size_t n);

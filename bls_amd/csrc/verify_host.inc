@@ -1175,6 +1175,90 @@ int compress_host(int group, const uint8_t* pts, const uint8_t* in_inf, uint8_t*
     HIPCHK(hipStreamSynchronize(g_stream));
     return BLSMI_OK;
 }
+// The wire format <-> the reference's in-memory points (blsmi 0.15).  Decompression: what decompress_dev gives for the same bytes and check,
+// its records as store_jac_m384 writes them -- (x, y, 1), and (0, 1, 0) wherever the affine record is the all-zero one (a well-formed infinity,
+// every err != 0).  The calls decompress_dev serves with the one-lane kernel take its twin that writes the in-memory record itself; the small
+// calls it serves otherwise (a wave per point, the subgroup test as a level program) run unchanged into a temporary and k_affine_to_jac
+// finishes, reading the all-zero record as every kernel does.  d_inf may be null.  The bytes are the same on every route.
+int decompress_jac_dev(const GroupKernels& gk, const u8* d_in, int check, u64* d_out, u8* d_inf, u8* d_err, size_t n, hipStream_t s) {
+    const bool lat = check == 1 && n <= tune().lat_max;
+    const bool waves = (lat ? 0 : check) == 0 && n <= tune().swu_wave_max;
+    if (!lat && !waves) {
+        launch(gk.decompress_jac, nblocks(n), s, d_in, check, d_out, d_inf, d_err, n);
+        prof_mark(nullptr);
+        HIPCHK(hipGetLastError());
+        return BLSMI_OK;
+    }
+    DBuf aff, inf;
+    HIPCHK(aff.alloc(gk.wire_bytes * n, s)); HIPCHK(inf.alloc(n, s));
+    u8* flags = d_inf ? d_inf : inf.as<u8>();
+    { const int rc = decompress_dev(gk, d_in, check, aff.as<u8>(), flags, d_err, n, s); if (rc) return rc; }
+    launch(KERNEL_OF(k_affine_to_jac), nblocks(n), s, aff.p, nullptr, 1, gk.id, d_out, n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+inline int decompress_jac_args(const void* in, const void* out, const void* err, int check, size_t n) {   // what both forms refuse before any device work
+    if (check < 0 || check > 2) return BLSMI_E_ARG;
+    if (n && (!in || !out || !err)) return BLSMI_E_ARG;
+    return BLSMI_OK;
+}
+int decompress_jac_host(int group, const uint8_t* in, int check, uint64_t* out, uint8_t* out_inf, uint8_t* err, size_t n) {
+    { const int rc = decompress_jac_args(in, out, err, check, n); if (rc) return rc; }
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT();
+    const GroupKernels& gk = group_kernels(group);
+    const size_t IB = gk.wire_bytes / 2, OB = rec_bytes(gk.wire_bytes, true);
+    DBuf di, dout, dinf, derr;
+    HIPCHK(di.alloc(IB * n)); HIPCHK(dout.alloc(OB * n)); HIPCHK(dinf.alloc(n)); HIPCHK(derr.alloc(n));
+    HIPCHK(hipMemcpyAsync(di.p, in, IB * n, hipMemcpyHostToDevice, g_stream));
+    { const int rc = decompress_jac_dev(gk, di.as<u8>(), check, dout.as<u64>(), out_inf ? dinf.as<u8>() : nullptr, derr.as<u8>(), n, g_stream); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(out, dout.p, OB * n, hipMemcpyDeviceToHost, g_stream));
+    if (out_inf) HIPCHK(hipMemcpyAsync(out_inf, dinf.p, n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(err, derr.p, n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+int decompress_jac_dev_api(int group, const void* d_in, int check, void* d_out, void* d_inf, void* d_err, size_t n, void* stream) {
+    { const int rc = decompress_jac_args(d_in, d_out, d_err, check, n); if (rc) return rc; }
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    { const int rc = decompress_jac_dev(group_kernels(group), static_cast<const u8*>(d_in), check, static_cast<u64*>(d_out), static_cast<u8*>(d_inf), static_cast<u8*>(d_err), n, g_stream); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+// Compression: the bytes compress_host gives for the record and flag jac_to_wire_dev gives, in ONE launch for every n and without the affine
+// records in between (k_g?_compress_jac, one lane per point).  Reads only.
+int compress_jac_dev(const GroupKernels& gk, const void* d_jac, void* d_out, size_t n, hipStream_t s) {
+    launch(gk.compress_jac, nblocks(n), s, d_jac, d_out, n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int compress_jac_host(int group, const uint64_t* jac, uint8_t* out, size_t n) {
+    if (n && (!jac || !out)) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT();
+    const GroupKernels& gk = group_kernels(group);
+    const size_t IB = rec_bytes(gk.wire_bytes, true), OB = gk.wire_bytes / 2;
+    DBuf di, dout;
+    HIPCHK(di.alloc(IB * n)); HIPCHK(dout.alloc(OB * n));
+    HIPCHK(hipMemcpyAsync(di.p, jac, IB * n, hipMemcpyHostToDevice, g_stream));
+    { const int rc = compress_jac_dev(gk, di.p, dout.p, n, g_stream); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(out, dout.p, OB * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+int compress_jac_dev_api(int group, const void* d_jac, void* d_out, size_t n, void* stream) {
+    if (n && (!d_jac || !d_out)) return BLSMI_E_ARG;
+    if (n == 0) return BLSMI_OK;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    { const int rc = compress_jac_dev(group_kernels(group), d_jac, d_out, n, g_stream); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
 }  // namespace
 
 // Shard-level half of VerifyAggregate for callers that shard ACROSS PROCESSES (one rank per GPU under torchrun, bls_amd/dist.py):
@@ -1638,6 +1722,14 @@ BLSMI_API int blsmi_g1_check_batch_jac(const uint64_t* pts_jac, int check, uint8
 BLSMI_API int blsmi_g2_check_batch_jac(const uint64_t* pts_jac, int check, uint8_t* status, size_t n) { return check_host(2, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, check, status, n); }
 BLSMI_API int blsmi_g1_check_batch_dev(const void* d_pts, const void* d_in_inf, int jac, int check, void* d_status, size_t n, void* stream) { return check_dev_api(1, d_pts, d_in_inf, jac, check, d_status, n, stream); }
 BLSMI_API int blsmi_g2_check_batch_dev(const void* d_pts, const void* d_in_inf, int jac, int check, void* d_status, size_t n, void* stream) { return check_dev_api(2, d_pts, d_in_inf, jac, check, d_status, n, stream); }
+BLSMI_API int blsmi_g1_decompress_batch_jac(const uint8_t* in, int check, uint64_t* out_jac, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_jac_host(1, in, check, out_jac, out_inf, err, n); }
+BLSMI_API int blsmi_g2_decompress_batch_jac(const uint8_t* in, int check, uint64_t* out_jac, uint8_t* out_inf, uint8_t* err, size_t n) { return decompress_jac_host(2, in, check, out_jac, out_inf, err, n); }
+BLSMI_API int blsmi_g1_compress_batch_jac(const uint64_t* pts_jac, uint8_t* out, size_t n) { return compress_jac_host(1, pts_jac, out, n); }
+BLSMI_API int blsmi_g2_compress_batch_jac(const uint64_t* pts_jac, uint8_t* out, size_t n) { return compress_jac_host(2, pts_jac, out, n); }
+BLSMI_API int blsmi_g1_decompress_batch_jac_dev(const void* d_in, int check, void* d_out_jac, void* d_out_inf, void* d_err, size_t n, void* stream) { return decompress_jac_dev_api(1, d_in, check, d_out_jac, d_out_inf, d_err, n, stream); }
+BLSMI_API int blsmi_g2_decompress_batch_jac_dev(const void* d_in, int check, void* d_out_jac, void* d_out_inf, void* d_err, size_t n, void* stream) { return decompress_jac_dev_api(2, d_in, check, d_out_jac, d_out_inf, d_err, n, stream); }
+BLSMI_API int blsmi_g1_compress_batch_jac_dev(const void* d_pts_jac, void* d_out, size_t n, void* stream) { return compress_jac_dev_api(1, d_pts_jac, d_out, n, stream); }
+BLSMI_API int blsmi_g2_compress_batch_jac_dev(const void* d_pts_jac, void* d_out, size_t n, void* stream) { return compress_jac_dev_api(2, d_pts_jac, d_out, n, stream); }
 
 // ---- the verify surface over the reference's in-memory points (blsmi 0.6; include/blsmi.h "in-memory points") ---------------------------
 // Keys and signatures as the Go values hold them: bls.G2Projective = 36 x u64, bls.G1Projective = 18 x u64 (x, y, z; FQ = 6 LE u64 Montgomery

@@ -1521,3 +1521,70 @@ def check_batch_dev(group, d_pts, d_in_inf, n, d_status, jac=False, check=1, str
         raise ValueError("the in-memory form takes no flags: z == 0 is infinity")
     name = "blsmi_g1_check_batch_dev" if group == "g1" else "blsmi_g2_check_batch_dev"
     _check(_fn_0_14(name)(d_pts or 0, d_in_inf or 0, int(bool(jac)), int(check), d_status or 0, n, stream or 0), name[len("blsmi_"):])
+
+
+# ---- the wire format <-> in-memory points (blsmi 0.15) -----------------------------------------------------------------------------------
+# the argument types of the eight entry points of 0.15, as include/blsmi.h declares them (tests/test_wire_jac_cpu.py compares)
+ARGTYPES_0_15 = {
+    "blsmi_g1_decompress_batch_jac": [_u8p, C.c_int, _u64p, _u8p, _u8p, C.c_size_t],
+    "blsmi_g2_decompress_batch_jac": [_u8p, C.c_int, _u64p, _u8p, _u8p, C.c_size_t],
+    "blsmi_g1_compress_batch_jac": [_u64p, _u8p, C.c_size_t],
+    "blsmi_g2_compress_batch_jac": [_u64p, _u8p, C.c_size_t],
+    "blsmi_g1_decompress_batch_jac_dev": [_V, C.c_int, _V, _V, _V, C.c_size_t, _V],
+    "blsmi_g2_decompress_batch_jac_dev": [_V, C.c_int, _V, _V, _V, C.c_size_t, _V],
+    "blsmi_g1_compress_batch_jac_dev": [_V, _V, C.c_size_t, _V],
+    "blsmi_g2_compress_batch_jac_dev": [_V, _V, C.c_size_t, _V],
+}
+
+
+def _fn_0_15(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_15[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _decompress_jac(name, ib, jb, data, n, check):
+    a = _u8(data, ib * n) if n else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, n) * jb, dtype=np.uint8)
+    inf = np.zeros(max(1, n), dtype=np.uint8)
+    err = np.zeros(max(1, n), dtype=np.uint8)
+    _check(_fn_0_15(name)(_p8(a), int(check), out.ctypes.data_as(_u64p), _p8(inf), _p8(err), n), name[len("blsmi_"):])
+    return out[:n * jb].reshape(n, jb), inf[:n].astype(bool), err[:n].copy()
+
+
+def g1_decompress_batch_jac(data, n, check_subgroup=True):
+    """DecompressG1(b).ToProjective() of n 48-byte encodings -> ((n, 144) uint8 in-memory records, infinity flags, error codes); the flags and
+    codes are g1_decompress_batch's, the record of an infinity or of an encoding with an error is the reference's zero point (0, 1, 0)"""
+    return _decompress_jac("blsmi_g1_decompress_batch_jac", 48, 144, data, n, check_subgroup)
+
+
+def g2_decompress_batch_jac(data, n, check_subgroup=True):
+    return _decompress_jac("blsmi_g2_decompress_batch_jac", 96, 288, data, n, check_subgroup)
+
+
+def _compress_jac(name, jb, ob, jac, n):
+    a, pa = _j64(jac, jb * n)
+    out = np.zeros((max(1, n), ob), dtype=np.uint8)
+    _check(_fn_0_15(name)(pa, _p8(out.reshape(-1)), n), name[len("blsmi_"):])
+    return out[:n]
+
+
+def g1_compress_batch_jac(jac, n):
+    """CompressG1(p.ToAffine()) of n in-memory G1 points (144 bytes each, z == 0: infinity) -> (n, 48) uint8, one call and one launch"""
+    return _compress_jac("blsmi_g1_compress_batch_jac", 144, 48, jac, n)
+
+
+def g2_compress_batch_jac(jac, n):
+    return _compress_jac("blsmi_g2_compress_batch_jac", 288, 96, jac, n)
+
+
+def decompress_batch_jac_dev(group, d_in, n, d_out_jac, d_out_inf, d_err, check_subgroup=True, stream=0):
+    """device-pointer form (ints; d_out_inf may be 0): the records, flags and codes are in the caller's buffers when the call returns"""
+    name = "blsmi_g1_decompress_batch_jac_dev" if group == "g1" else "blsmi_g2_decompress_batch_jac_dev"
+    _check(_fn_0_15(name)(d_in or 0, int(check_subgroup), d_out_jac or 0, d_out_inf or 0, d_err or 0, n, stream or 0), name[len("blsmi_"):])
+
+
+def compress_batch_jac_dev(group, d_pts_jac, n, d_out, stream=0):
+    name = "blsmi_g1_compress_batch_jac_dev" if group == "g1" else "blsmi_g2_compress_batch_jac_dev"
+    _check(_fn_0_15(name)(d_pts_jac or 0, d_out or 0, n, stream or 0), name[len("blsmi_"):])

@@ -11,6 +11,7 @@ plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks.
 """
 from . import engine
 from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum, points_valid  # noqa: F401
+from ._groups import deserialize_objects, serialize_points, verify_serialized_randomized
 
 SIG_GROUP, PK_GROUP = 2, 1
 
@@ -363,3 +364,31 @@ def ValidatePublicKeys(pubs):
 
 def ValidateSignatures(sigs):
     return points_valid([s.s for s in sigs], SIG_GROUP)
+
+
+# ---- the wire format in batches (blsmi 0.15): 48-byte keys and 96-byte signatures <-> objects that hold in-memory points ----------------------
+def DeserializePublicKeys(blobs):
+    """[DeserializePublicKey(b) for b in blobs] in one library call -> (keys, errors): errors[i] is the decode error code (0: fine; the
+    messages: _groups._DECODE_ERRORS) and keys[i] is None where it is not 0.  The keys hold in-memory points: every batch call takes them as
+    they are."""
+    return deserialize_objects(blobs, PK_GROUP, PublicKey)
+
+
+def DeserializeSignatures(blobs):
+    return deserialize_objects(blobs, SIG_GROUP, Signature)
+
+
+def SerializePublicKeys(pubs):
+    """[pub.Serialize() for pub in pubs] in one library call: ToAffine and Compress on the device"""
+    return serialize_points([p.p for p in pubs], PK_GROUP)
+
+
+def SerializeSignatures(sigs):
+    return serialize_points([s.s for s in sigs], SIG_GROUP)
+
+
+def VerifySerializedBatchRandomized(msgs, pub_bytes, sig_bytes, block=0):
+    """VerifySerializedBatch's verdicts by VerifyBatchRandomizedLocate: the keys and signatures are deserialised (subgroup check included) into
+    in-memory points on the device and go through the combined check.  A tuple with an undecodable element gets False and sends only its own
+    block of `block` tuples (0: automatic; else even and at least 2) through the per-tuple path."""
+    return [bool(x) for x in verify_serialized_randomized(__name__.rsplit(".", 1)[-1], PK_GROUP, SIG_GROUP, msgs, pub_bytes, sig_bytes, block)[0]]

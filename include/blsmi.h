@@ -82,8 +82,9 @@ void blsmi_shutdown(void);
  * finds the bad tuples by blocks (blsmi_g?pubs_*verify*_batch_rlc_locate[_jac]); no existing prototype changes, no new option.  0.13 adds the grouped
  * randomised batch verification that finds the bad tuples by cells (blsmi_g?pubs_*verify*_batch_rlc_grouped_locate[_jac]); no existing prototype
  * changes, no new option.  0.14 adds the batch point validation (blsmi_g?_check_batch[_jac|_dev]: on-curve and subgroup status of points in either
- * form, no inversion, no square root) and the BLSMI_POINT_* status names; no existing prototype changes, no new option.  The string below still begins
- * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13 and 0.14 by the presence of
+ * form, no inversion, no square root) and the BLSMI_POINT_* status names; no existing prototype changes, no new option.  0.15 adds the conversions between the compressed wire format and the in-memory points
+ * (blsmi_g?_decompress_batch_jac[_dev], blsmi_g?_compress_batch_jac[_dev]); no existing prototype changes, no new option.  The string below still begins
+ * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14 and 0.15 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -805,6 +806,33 @@ int blsmi_g1_check_batch_jac(const uint64_t *pts_jac /* n*18 */, int check, uint
 int blsmi_g2_check_batch_jac(const uint64_t *pts_jac /* n*36 */, int check, uint8_t *status /* n */, size_t n);
 int blsmi_g1_check_batch_dev(const void *d_pts, const void *d_in_inf, int jac, int check, void *d_status, size_t n, void *stream);
 int blsmi_g2_check_batch_dev(const void *d_pts, const void *d_in_inf, int jac, int check, void *d_status, size_t n, void *stream);
+
+/* ---- the wire format <-> in-memory points (blsmi 0.15) ---------------------------------------------------------------------------------
+ * Deserialize and Serialize for the points as the Go values hold them (144 / 288 bytes, "in-memory points at the boundary" above), n at a
+ * time: what arrives compressed can go straight into any *_jac entry point, and what a *_jac entry point returned can leave compressed,
+ * without affine records visiting the host.  Each call is defined by the entry points that already exist:
+ *   decompress_batch_jac   DecompressG?(b).ToProjective().  err[i] and out_inf[i] (may be NULL) are exactly what blsmi_g?_decompress_batch
+ *           gives for the same bytes and the same check_subgroup (0 / 1 / 2; any other value: BLSMI_E_ARG).  out_jac[i] is the in-memory
+ *           form of that call's record: (x, y, 1) in Montgomery limbs for a usable finite point, and (0, 1, 0) -- the reference's
+ *           G?ProjectiveZero -- for a well-formed infinity encoding AND for every record with err != 0, so that a downstream *_jac call
+ *           gives a tuple with an undecodable element verdict 0 (z == 0) without reading err.
+ *   compress_batch_jac     CompressG?(p.ToAffine()).  out[i] is the bytes blsmi_g?_compress_batch gives for the record and flag that
+ *           blsmi_g?_jac_to_affine_batch gives for pts_jac[i]: z == 0 gives 0xc0 followed by zeros whatever x and y hold, a limb image not
+ *           below q reads as 0, and there is no curve test.  One kernel launch for every n, one lane per point; a wave whose points all
+ *           have z == 1 skips the inversion.
+ * n == 0 returns BLSMI_OK; a NULL required buffer with n > 0 is BLSMI_E_ARG before any device work.  The host forms run on ONE device: they
+ * are not sharded and do not join the request combiner.  The _dev forms take every buffer on one of the library's devices (stream as in
+ * blsmi_pairing_batch_dev); input and output must not overlap, and the caller's input is left untouched. */
+int blsmi_g1_decompress_batch_jac(const uint8_t *in /* n*48 */, int check_subgroup, uint64_t *out_jac /* n*18 */, uint8_t *out_inf /* n, may be NULL */,
+                                  uint8_t *err /* n */, size_t n);
+int blsmi_g2_decompress_batch_jac(const uint8_t *in /* n*96 */, int check_subgroup, uint64_t *out_jac /* n*36 */, uint8_t *out_inf /* n, may be NULL */,
+                                  uint8_t *err /* n */, size_t n);
+int blsmi_g1_compress_batch_jac(const uint64_t *pts_jac /* n*18 */, uint8_t *out /* n*48 */, size_t n);
+int blsmi_g2_compress_batch_jac(const uint64_t *pts_jac /* n*36 */, uint8_t *out /* n*96 */, size_t n);
+int blsmi_g1_decompress_batch_jac_dev(const void *d_in, int check_subgroup, void *d_out_jac, void *d_out_inf /* may be NULL */, void *d_err, size_t n, void *stream);
+int blsmi_g2_decompress_batch_jac_dev(const void *d_in, int check_subgroup, void *d_out_jac, void *d_out_inf /* may be NULL */, void *d_err, size_t n, void *stream);
+int blsmi_g1_compress_batch_jac_dev(const void *d_pts_jac, void *d_out, size_t n, void *stream);
+int blsmi_g2_compress_batch_jac_dev(const void *d_pts_jac, void *d_out, size_t n, void *stream);
 
 #ifdef __cplusplus
 }

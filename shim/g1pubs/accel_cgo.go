@@ -20,6 +20,7 @@ package g1pubs
 import "C"
 
 import (
+	"errors"
 	"strconv"
 	"unsafe"
 
@@ -553,6 +554,109 @@ func VerifyAggregateCommonWithDomainBatch(sigs []*Signature, committees [][]*Pub
 	ok := make([]byte, n)
 	must(C.blsmi_g1pubs_verify_aggregate_common_with_domain_batch_jac((*C.uint8_t)(unsafe.Pointer(&msgs[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
 		u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), u8(ok), nil, C.size_t(n)), "g1pubs_verify_aggregate_common_with_domain_batch_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// ---- the wire format in batches (blsmi 0.15; INTEGRATION.md 2m) --------------------------------------------------------------------------
+// Keys and signatures arrive and leave compressed (48 / 96 bytes, g1pubs/bls.go:18-20, 67-69).  Upstream deserialises one element per call on a
+// host core -- a square root plus the r * P subgroup walk -- and serialises through one Fq inversion per point; the functions below do either for
+// n elements in one library call, between the compressed bytes and the G?Projective structs as the Go heap holds them.
+
+// decodeErrors: the messages of upstream's Decompress* and subgroup check, by the error code of blsmi_g?_decompress_batch.
+var decodeErrors = [5]string{"", "unexpected compression mode", "unexpected information in compressed infinity", "point not on curve", "not in correct subgroup"}
+
+// DeserializePublicKeys is DeserializePublicKey (g1pubs/bls.go) for n keys, subgroup check included: out[i] is nil where errs[i] is not.
+func DeserializePublicKeys(b [][48]byte) ([]*PublicKey, []error) {
+	n := len(b)
+	out := make([]*PublicKey, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	pk := make([]C.uint64_t, 18*n)
+	ec := make([]byte, n)
+	must(C.blsmi_g1_decompress_batch_jac((*C.uint8_t)(unsafe.Pointer(&b[0])), 1, &pk[0], nil, u8(ec), C.size_t(n)), "g1_decompress_batch_jac")
+	for i := range out {
+		if ec[i] != 0 {
+			errs[i] = errors.New(decodeErrors[ec[i]])
+			continue
+		}
+		p := new(bls.G1Projective)
+		copy((*[18]C.uint64_t)(unsafe.Pointer(p))[:], pk[18*i:18*i+18])
+		out[i] = &PublicKey{p: p}
+	}
+	return out, errs
+}
+
+// DeserializeSignatures is DeserializeSignature for n signatures, the same way.
+func DeserializeSignatures(b [][96]byte) ([]*Signature, []error) {
+	n := len(b)
+	out := make([]*Signature, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	sg := make([]C.uint64_t, 36*n)
+	ec := make([]byte, n)
+	must(C.blsmi_g2_decompress_batch_jac((*C.uint8_t)(unsafe.Pointer(&b[0])), 1, &sg[0], nil, u8(ec), C.size_t(n)), "g2_decompress_batch_jac")
+	for i := range out {
+		if ec[i] != 0 {
+			errs[i] = errors.New(decodeErrors[ec[i]])
+			continue
+		}
+		p := new(bls.G2Projective)
+		copy((*[36]C.uint64_t)(unsafe.Pointer(p))[:], sg[36*i:36*i+36])
+		out[i] = &Signature{s: p}
+	}
+	return out, errs
+}
+
+// SerializePublicKeys is PublicKey.Serialize for n keys: the structs go over as they lie, the inversion and the compression run on the device.
+func SerializePublicKeys(pubs []*PublicKey) [][48]byte {
+	n := len(pubs)
+	out := make([][48]byte, n)
+	if n == 0 {
+		return out
+	}
+	pk := packKeys(pubs)
+	must(C.blsmi_g1_compress_batch_jac(u64(pk), (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(n)), "g1_compress_batch_jac")
+	return out
+}
+
+// SerializeSignatures is Signature.Serialize for n signatures.
+func SerializeSignatures(sigs []*Signature) [][96]byte {
+	n := len(sigs)
+	out := make([][96]byte, n)
+	if n == 0 {
+		return out
+	}
+	sg := packSigs(sigs)
+	must(C.blsmi_g2_compress_batch_jac(u64(sg), (*C.uint8_t)(unsafe.Pointer(&out[0])), C.size_t(n)), "g2_compress_batch_jac")
+	return out
+}
+
+// VerifySerializedBatchRandomized gives VerifySerializedBatch's verdicts by VerifyBatchRandomizedLocate: both inputs are deserialised on the
+// device, subgroup check included, and go through the combined check as the in-memory points they then are.  An element that does not
+// deserialise is the zero point there: its tuple is false and only its own block of `block` tuples (0: the library chooses; else even and at
+// least 2) goes through the per-tuple path.
+func VerifySerializedBatchRandomized(msgs [][]byte, pubs [][48]byte, sigs [][96]byte, block int) []bool {
+	n := len(msgs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	m, off := packMsgs(msgs)
+	pk := make([]C.uint64_t, 18*n)
+	sg := make([]C.uint64_t, 36*n)
+	ec := make([]byte, n)
+	must(C.blsmi_g1_decompress_batch_jac((*C.uint8_t)(unsafe.Pointer(&pubs[0])), 1, &pk[0], nil, u8(ec), C.size_t(n)), "g1_decompress_batch_jac")
+	must(C.blsmi_g2_decompress_batch_jac((*C.uint8_t)(unsafe.Pointer(&sigs[0])), 1, &sg[0], nil, u8(ec), C.size_t(n)), "g2_decompress_batch_jac")
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_batch_rlc_locate_jac(u8(m), &off[0], u64(pk), u64(sg), nil, C.size_t(block), u8(ok), nil, C.size_t(n), nil, nil),
+		"g1pubs_verify_batch_rlc_locate_jac")
 	for i := range ok {
 		out[i] = ok[i] != 0
 	}
