@@ -75,6 +75,21 @@ __device__ __forceinline__ void hash_prio() {
 #endif
 }
 
+// The drop of the lane-pair pairing kernels' yield (pair_kernels.inc: every wave enters at priority 1 and comes here once most of its work is done).
+// Only the wave in the even wave slot of its SIMD drops: on a grid of two waves per SIMD the slots are 0 and 1, and at equal priority the wave in
+// slot 0 is the one that leads (it left first on 1 024 of 1 024 SIMDs in every census, profiles/r16_wave_yield.log).  The wave in slot 1 keeps its
+// priority to its end, so the two do not fall back to arbitration by age once both have dropped: 16.64 -> 16.29 ms per step.  Where the slots say
+// nothing about age (a grid of many waves per slot) a wave that keeps priority 1 is what it was before the yield.  -D...=0: every wave drops (A/B).
+#ifndef BLSMI_PAIR_YIELD_YOUNGER_STAYS
+#define BLSMI_PAIR_YIELD_YOUNGER_STAYS 1
+#endif
+__device__ __forceinline__ void pair_yield_drop() {
+#if BLSMI_PAIR_YIELD_YOUNGER_STAYS
+    if ((__builtin_amdgcn_s_getreg(4) & 1) == 0)                               // HW_ID.WAVE_ID bit 0: a scalar condition
+#endif
+        __builtin_amdgcn_s_setprio(0);
+}
+
 template <int L_, int V_>
 struct Fp {
     static constexpr int L = L_, V = V_;

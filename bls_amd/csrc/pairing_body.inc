@@ -139,10 +139,14 @@ BLSMI_NOINLINE void ell2(Fp12S& f, const Fp2S& a0, const Fp2S& a1, const Fp2S& a
 // written ONCE for the single-lane, lane-pair and lane-quad loops: a doubling per bit; where the bit is set the line(s) go into f and an
 // addition follows; multiply-and-square; after the last bit one more doubling, whose line(s) go in unsquared.  The caller sets f to one
 // before and conjugates after (blsIsNegative, pairing.go:71-73).  (The lane-row loops keep a shape of their own, written out: row_body.inc.)
-template <class Dbl, class Add, class Mul, class MulSqr>
-BLSMI_DEV void x_bit_walk(Dbl dbl, Add add, Mul mul, MulSqr mul_sqr) {
+// `tick(done)` runs at the top of every bit with the number of bits already walked (0..61): wave-uniform, the loop index lives in a scalar
+// register (miller_loop<.., YIELD> lowers the wave's priority there; everyone else passes nothing).
+struct NoTick { BLSMI_DEV void operator()(int) const {} };
+template <class Dbl, class Add, class Mul, class MulSqr, class Tick = NoTick>
+BLSMI_DEV void x_bit_walk(Dbl dbl, Add add, Mul mul, MulSqr mul_sqr, Tick tick = Tick()) {
     const u64 xr = BLSMI_X_ABS >> 1;
     for (int i = 61; i >= 0; i--) {
+        tick(61 - i);
         dbl();
         if ((xr >> i) & 1) { mul(); add(); }
         mul_sqr();
@@ -186,7 +190,9 @@ BLSMI_DEV G2Proj lds_get_proj(const i32* l) {
         for (int i = 0; i < NL; i++) c[j].v[i] = l[(j * NL + i) * 64 + threadIdx.x];
     return r;
 }
-template <int NP, bool PRE0 = false, bool EXACT = true, bool PRE1 = false, class G1P, class G2P>
+// YIELD > 0 (the lane-pair kernels that run two waves per SIMD, pair_kernels.inc): the wave entered at s_setprio 1 and goes down to 0 once
+// YIELD bits are walked, so that the wave it shares the SIMD with -- still at 1 if it is behind -- catches up.
+template <int NP, bool PRE0 = false, bool EXACT = true, bool PRE1 = false, int YIELD = 0, class G1P, class G2P>
 BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], const i32* pre = nullptr, const i32* pre1 = nullptr, i32* lds_r = nullptr) {
     static_assert(NP == 1 || NP == 2, "one pair, or two pairs sharing the squarings");
     constexpr int LAST = NP - 1;
@@ -207,11 +213,15 @@ BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], con
     };
     Fp2S o0, o1, o2;
     int line = 0;
+    auto tick = [](int done) {
+        if constexpr (YIELD > 0) { if (done == YIELD) pair_yield_drop(); }
+        else (void)done;
+    };
     if constexpr (NP == 1) {
         x_bit_walk([&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else dbl_last(o0, o1, o2); },
                    [&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else add_last(o0, o1, o2); },
                    [&] { ell(f, o0, o1, o2, p[0].x, p[0].y); },
-                   [&] { ell_sqr(f, o0, o1, o2, p[0].x, p[0].y); });
+                   [&] { ell_sqr(f, o0, o1, o2, p[0].x, p[0].y); }, tick);
     } else {
         // both pairs' lines of a step are multiplied together first (ell2): 23 instead of 26 Fq2 products per step
         Fp2S n0, n1, n2;
@@ -221,7 +231,7 @@ BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], con
                    [&] { if (PRE0) load_line(pre, line++, o0, o1, o2); else add_step<EXACT>(r[0], q[0].x, q[0].y, o0, o1, o2);
                          if (PRE1) load_line(pre1, line1++, n0, n1, n2); else add_last(n0, n1, n2); },
                    [&] { ell2<false>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); },
-                   [&] { ell2<true>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); });
+                   [&] { ell2<true>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); }, tick);
     }
     fp12_conj_inplace(f);                                              // blsIsNegative (pairing.go:71-73)
 }
@@ -265,6 +275,10 @@ BLSMI_DEV void exp_by_x_loop(typename O::T& out, const typename O::T& f, u64 e) 
     O::conj(res);
     out = res;
 }
+// An ops struct may name a hook, O::before_exp_x(k), that runs before the chain's k-th ExpByX (k = 0..4): the lane-pair kernels' own struct
+// lowers the wave's priority at one of them (pair_kernels.inc: PairYieldOps).  A struct without the member gets nothing.
+template <class O, class = void> struct ExpXHook { static BLSMI_DEV void at(int) {} };
+template <class O> struct ExpXHook<O, decltype(O::before_exp_x(0))> { static BLSMI_DEV void at(int k) { O::before_exp_x(k); } };
 // pairing.go:79-129.  Computes r^(3(q^12-1)/r_order) in place; a non-invertible input (only 0)
 // maps to 0 where the reference returns nil.
 template <class O>
@@ -277,21 +291,21 @@ BLSMI_DEV void final_exp_chain(typename O::T& r) {
     O::mul(r, f2, r);
     const u64 x = BLSMI_X_ABS;
     O::cyc_sqr(y0, r);
-    O::exp_x(y1, y0, x);
-    O::exp_x(y2, y1, x >> 1);
+    ExpXHook<O>::at(0); O::exp_x(y1, y0, x);
+    ExpXHook<O>::at(1); O::exp_x(y2, y1, x >> 1);
     y3 = r; O::conj(y3);
     O::mul(y1, y1, y3);
     O::conj(y1);
     O::mul(y1, y1, y2);
-    O::exp_x(y2, y1, x);
-    O::exp_x(y3, y2, x);
+    ExpXHook<O>::at(2); O::exp_x(y2, y1, x);
+    ExpXHook<O>::at(3); O::exp_x(y3, y2, x);
     O::conj(y1);
     O::mul(y3, y3, y1);
     O::conj(y1);
     O::frob3(y1, y1);
     O::frob2(y2, y2);
     O::mul(y1, y1, y2);
-    O::exp_x(y2, y3, x);
+    ExpXHook<O>::at(4); O::exp_x(y2, y3, x);
     O::mul(y2, y2, y0);
     O::mul(y2, y2, r);
     O::mul(y1, y1, y2);
