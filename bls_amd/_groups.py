@@ -200,3 +200,15 @@ def committee_batch_args(committees, sigs):
     if all_in_memory(keys + sigs):
         return True, b"".join(p.jac for p in keys), len(keys), off, b"".join(s.jac for s in sigs)
     return False, b"".join(p.bytes_or_zero() for p in keys), len(keys), off, b"".join(s.bytes_or_zero() for s in sigs)
+
+
+def message_table(msgs):
+    """equal messages once: (table, the index of msgs[j] in it) -- what the grouped randomised calls take"""
+    at, table, idx = {}, [], []
+    for x in msgs:
+        x = bytes(x)
+        if x not in at:
+            at[x] = len(table)
+            table.append(x)
+        idx.append(at[x])
+    return table, idx

@@ -318,6 +318,7 @@ struct GroupKernels {
     Laid<BLSMI_K(k_g1_mul)> mul, mul_glv; BLSMI_K(k_g1_mul_u64) mul_u64; BLSMI_K(k_g1_mul_fixed) mul_fixed, mul_fixed_wave;
     BLSMI_K(k_g1_sum0) sum0; BLSMI_K(k_g1_sum0_jac) sum0_jac; BLSMI_K(k_g1_sum) sum; BLSMI_K(k_g1_sum_final) sum_final;
     Laid<BLSMI_K(k_g1_segsum_chunk)> segsum_chunk; BLSMI_K(k_g1_segsum_chunk_jac) segsum_chunk_jac; BLSMI_K(k_g1_segsum_chunk_u64) segsum_chunk_u64;
+    Laid<BLSMI_K(k_g1_segsum_chunk_u64)> segsum_chunk_u64_opt;              // the weighted pass 1 in the form the options choose (blsmi 0.16: rlc_host.hpp, agg_common_rlc); segsum_chunk_u64 stays the one-lane kernel of 0.11 to 0.13
     Laid<BLSMI_K(k_g1_segsum_fold)> segsum_fold; BLSMI_K(k_g1_segsum_final) segsum_final;
     BLSMI_K(k_g1_compress) compress; BLSMI_K(k_g1_decompress) decompress; BLSMI_K(k_g1_decompress_waves) decompress_waves; BLSMI_K(k_g1_jac_to_affine) jac_to_affine;
     Laid<BLSMI_K(k_g1_check)> check; Laid<BLSMI_K(k_g1_check_jac)> check_jac;   // point validation (k_check.hip): affine records, in-memory Jacobian records
@@ -326,6 +327,7 @@ struct GroupKernels {
     Laid<BLSMI_K(k_g1_msm_bucket_raw)> msm_bucket_raw; Laid<BLSMI_K(k_g1_msm_chunk2)> msm_chunk2; Laid<BLSMI_K(k_g1_msm_fold2)> msm_fold2; BLSMI_K(k_g1_msm_final2) msm_final2;
 #undef BLSMI_K
 };
+using SegsumU64Pass1 = decltype(GroupKernels::segsum_chunk_u64_opt);
 // The one place that decides which form of a kernel serves.  G1 has one lane per item throughout.  G2: `opt` families take the lane-pair
 // form when the options say so (pair_layout; BLSMI_LAYOUT=single: the one-lane kernel); `always` families exist in the lane-pair form
 // only and take it whatever the options say; every other family has one lane per item in both groups.  sum0_jac carries the name of sum0:
@@ -339,7 +341,7 @@ inline GroupKernels group_row(int group, bool pair_forms) {
         .gen = &Gens::g1, .fixed = &Gens::fixed1, .msm_shift = 3, .msm_raw_words = 48,
         .mul = one(KERNEL_OF(k_g1_mul)), .mul_glv = one(KERNEL_OF(k_g1_mul_glv)), .mul_u64 = KERNEL_OF(k_g1_mul_u64), .mul_fixed = KERNEL_OF(k_g1_mul_fixed), .mul_fixed_wave = KERNEL_OF(k_g1_mul_fixed_wave),
         .sum0 = KERNEL_OF(k_g1_sum0), .sum0_jac = kernel_named(k_g1_sum0_jac, "k_g1_sum0"), .sum = KERNEL_OF(k_g1_sum), .sum_final = KERNEL_OF(k_g1_sum_final),
-        .segsum_chunk = one(KERNEL_OF(k_g1_segsum_chunk)), .segsum_chunk_jac = KERNEL_OF(k_g1_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g1_segsum_chunk_u64), .segsum_fold = one(KERNEL_OF(k_g1_segsum_fold)), .segsum_final = KERNEL_OF(k_g1_segsum_final),
+        .segsum_chunk = one(KERNEL_OF(k_g1_segsum_chunk)), .segsum_chunk_jac = KERNEL_OF(k_g1_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g1_segsum_chunk_u64), .segsum_chunk_u64_opt = one(KERNEL_OF(k_g1_segsum_chunk_u64)), .segsum_fold = one(KERNEL_OF(k_g1_segsum_fold)), .segsum_final = KERNEL_OF(k_g1_segsum_final),
         .compress = KERNEL_OF(k_g1_compress), .decompress = KERNEL_OF(k_g1_decompress), .decompress_waves = KERNEL_OF(k_g1_decompress_waves), .jac_to_affine = KERNEL_OF(k_g1_jac_to_affine),
         .check = one(KERNEL_OF(k_g1_check)), .check_jac = one(KERNEL_OF(k_g1_check_jac)),
         .decompress_jac = KERNEL_OF(k_g1_decompress_jac), .compress_jac = KERNEL_OF(k_g1_compress_jac),
@@ -350,7 +352,7 @@ inline GroupKernels group_row(int group, bool pair_forms) {
         .gen = &Gens::g2, .fixed = &Gens::fixed2, .msm_shift = 2, .msm_raw_words = 244,
         .mul = opt(KERNEL_OF(k_g2_mul), KERNEL_OF(k_g2_mul_pair)), .mul_glv = opt(KERNEL_OF(k_g2_mul_glv), KERNEL_OF(k_g2_mul_glv_pair)), .mul_u64 = KERNEL_OF(k_g2_mul_u64), .mul_fixed = KERNEL_OF(k_g2_mul_fixed), .mul_fixed_wave = KERNEL_OF(k_g2_mul_fixed_wave),
         .sum0 = KERNEL_OF(k_g2_sum0), .sum0_jac = kernel_named(k_g2_sum0_jac, "k_g2_sum0"), .sum = KERNEL_OF(k_g2_sum), .sum_final = KERNEL_OF(k_g2_sum_final),
-        .segsum_chunk = always(KERNEL_OF(k_g2_segsum_chunk_pair)), .segsum_chunk_jac = KERNEL_OF(k_g2_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g2_segsum_chunk_u64), .segsum_fold = always(KERNEL_OF(k_g2_segsum_fold_pair)), .segsum_final = KERNEL_OF(k_g2_segsum_final),
+        .segsum_chunk = always(KERNEL_OF(k_g2_segsum_chunk_pair)), .segsum_chunk_jac = KERNEL_OF(k_g2_segsum_chunk_jac), .segsum_chunk_u64 = KERNEL_OF(k_g2_segsum_chunk_u64), .segsum_chunk_u64_opt = opt(KERNEL_OF(k_g2_segsum_chunk_u64), KERNEL_OF(k_g2_segsum_chunk_u64_pair)), .segsum_fold = always(KERNEL_OF(k_g2_segsum_fold_pair)), .segsum_final = KERNEL_OF(k_g2_segsum_final),
         .compress = KERNEL_OF(k_g2_compress), .decompress = KERNEL_OF(k_g2_decompress), .decompress_waves = KERNEL_OF(k_g2_decompress_waves), .jac_to_affine = KERNEL_OF(k_g2_jac_to_affine),
         .check = opt(KERNEL_OF(k_g2_check), KERNEL_OF(k_g2_check_pair)), .check_jac = opt(KERNEL_OF(k_g2_check_jac), KERNEL_OF(k_g2_check_jac_pair)),
         .decompress_jac = KERNEL_OF(k_g2_decompress_jac), .compress_jac = KERNEL_OF(k_g2_compress_jac),

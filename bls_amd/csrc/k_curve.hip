@@ -105,24 +105,9 @@ KERNEL k_mul_finish(const u8* good, const u8* pts, size_t pt_stride, int rec_wor
 }
 KERNEL2 k_g1_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_batch_body<FpS, 96>(pts, pt_stride, scalars, out, out_inf, n); }
 KERNEL k_g2_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_batch_body<Fp2S, 192>(pts, pt_stride, scalars, out, out_inf, n); }
-// 64-bit scalars (the randomised batch verification, verify_host.inc: rlc_shard): the fixed 4-bit window of mul_batch_body over 16 nibbles --
-// 60 doublings and 15 additions after the 14 of the table, uniform control flow for all 64 lanes.  A plain ladder, not the endomorphisms:
-// the hash points of the cofactor-power route and a caller's keys need not lie in the subgroup, and the product is exact for any curve point.
+#include "mul_u64.cuh"                  // mul_u64_jac: the 64-bit ladder, shared with k_msm_pair.hip
 // Affine output with one inversion per lane, as mul_batch_body: k_g1_jac_to_affine is the same inversion per lane behind a second launch
-// and a Jacobian buffer, so folding it in here saves the round trip.  Infinity is not special-cased: the caller flags it (zero records).
-template <class F>
-BLSMI_DEV Jac<F> mul_u64_jac(const Aff<F>& p, u64 k) {
-    Jac<F> tab[16];
-    tab[0] = jac_zero<F>();
-    tab[1] = to_jac(p);
-    for (int j = 2; j < 16; j++) tab[j] = jac_add_affine(tab[j - 1], p);
-    Jac<F> res = tab[(u32)(k >> 60)];
-    for (int nib = 14; nib >= 0; nib--) {
-        res = jac_double(res); res = jac_double(res); res = jac_double(res); res = jac_double(res);
-        res = jac_add(res, tab[(u32)(k >> (4 * nib)) & 15]);
-    }
-    return res;
-}
+// and a Jacobian buffer, so folding it in here saves the round trip.
 template <class F, int PB>
 __device__ void mul_u64_body(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) {
     const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;

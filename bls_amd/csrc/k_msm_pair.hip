@@ -14,6 +14,7 @@
 #include "pair_field.cuh"
 namespace P2 = blsmi::pairl;
 #include "pair_point_io.inc"
+#include "mul_u64.cuh"
 
 // G2 bucket accumulation of the MSM (msm.inc step 2) with a lane PAIR per bucket: half the point state per lane, two waves per
 // SIMD instead of one.  The record a pair leaves is the one-lane kernel's (jac_soa_store): coordinate c_par by lane par.
@@ -143,6 +144,28 @@ __global__ void __launch_bounds__(WG, 2) k_g2_segsum_chunk_pair(const u8* pts, c
         P2::G2AffP a = pair_load_g2(pts + (size_t)192 * i, par);
         if (in_inf && in_inf[i]) a.inf = -1;
         acc = jac_add_affine(acc, a);
+    }
+    if (c < nch) pair_soa_store(part, nch, c, par, acc);
+}
+// Weighted pass 1 (k_curve.hip: segsum_chunk_u64_body) in the lane-pair layout, for the randomised check of committee aggregates
+// (rlc_host.hpp: blsmi 0.16), whose weighted G2 sum -- hundreds to a few thousand points -- is on the critical path: a lane pair per
+// chunk runs the ladder of mul_u64_jac on the lane-pair Fq2, half the window table per lane, two waves per SIMD.  Chunks, marks (a bad
+// index: bad[seg] = 1; in_inf and a zero scalar contribute nothing) and the partial's record are the one-lane kernel's, so the fold and
+// final kernels read either.  As there the plan has chunks of one position: cnt > 1 is written as the arguments allow and is unused.
+__global__ void __launch_bounds__(WG, 2) k_g2_segsum_chunk_u64_pair(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo,
+                                                                    const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch) {
+    const int par = threadIdx.x & 1;
+    const size_t c = (size_t)blockIdx.x * (WG / 2) + (threadIdx.x >> 1);
+    const size_t cc = c < nch ? c : nch - 1;                               // both lanes of a pair stay active
+    const u64 lo = ch_lo[cc];
+    const u32 cnt = c < nch ? ch_cnt[cc] : 0;
+    P2::G2JacP acc = jac_zero<P2::Fp2S>();
+    for (u32 k = 0; k < cnt; k++) {
+        const u64 i = idx ? (u64)idx[lo + k] : lo + k;                     // (uniform per pair)
+        if (i >= npk) { if (!par) bad[ch_seg[cc]] = 1; continue; }
+        P2::G2AffP a = pair_load_g2(pts + (size_t)192 * i, par);
+        if (in_inf && in_inf[i]) a.inf = -1;
+        acc = jac_add(acc, mul_u64_jac<P2::Fp2S>(a, scalars[i]));
     }
     if (c < nch) pair_soa_store(part, nch, c, par, acc);
 }

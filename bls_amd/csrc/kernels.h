@@ -178,6 +178,7 @@ __global__ void k_g2_msm_fold_pair(const i32* src, i32* dst, size_t seg, size_t 
 __global__ void k_g2_msm_chunk2_pair(const i32* buckets, i32* out, int c, int K, size_t nb, size_t nct);
 __global__ void k_g2_msm_fold2_pair(const i32* src, i32* dst, int narr, int nwin, size_t len, int io);
 __global__ void k_g2_segsum_chunk_pair(const u8* pts, const u8* in_inf, size_t npk, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
+__global__ void k_g2_segsum_chunk_u64_pair(const u8* pts, const u8* in_inf, size_t npk, const u64* scalars, const u32* idx, const u64* ch_lo, const u32* ch_cnt, const u32* ch_seg, u8* bad, i32* part, size_t nch);
 __global__ void k_g2_segsum_fold_pair(const i32* src, size_t nsrc, const u64* ch_lo, const u32* ch_cnt, i32* dst, size_t nch);
 // msm.inc
 __global__ void k_msm_hist(const u8* scalars, size_t n, int c, int nwin, u32* hist);

@@ -744,4 +744,195 @@ BLSMI_API int blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac(const
 }
 #undef GLOC
 #undef GLOCJ
+
+// ---- committee aggregates, randomised (blsmi 0.16; include/blsmi.h "committee aggregates, randomised") --------------------------------
+// The batches of VerifyAggregateCommon of blsmi 0.9 (verify_host.inc: agg_common_batch_dev) under the grouped form's ONE equation: item j is
+// (sig_j, committee j of the registry, table[msg_idx[j]]), and with apk_j the committee's sum
+//     g1pubs: e(G1gen, sum_j r_j sig_j) == prod_g e(sum_{j in g} r_j apk_j, H(m_g))      g2pubs: e(sum_j r_j sig_j, G2gen) == prod_g e(H(m_g), sum_{j in g} r_j apk_j)
+// The m committee sums are one unweighted segmented sum over the registry (bad_code 1), on aux[1] beside the hash, written where the other
+// forms upload one key per tuple: c.dp, their flags (infinity, the empty committee, a bad index) in c.di.  From there c.dp holds m keys and
+// the stages of the grouped form run as they stand.  Two things are this driver's own.  Both weighted sums take the pass 1 the options
+// choose (GroupKernels::segsum_chunk_u64_opt: G2 a lane pair per ladder, k_g2_segsum_chunk_u64_pair) -- the sizes are hundreds to a few
+// thousand points, where one-lane ladders leave most SIMDs idle, and for g2pubs every Miller loop waits for the key side's.  And the
+// signature side is the weighted segmented sum over ONE segment [0, m), so that it runs that same pass 1; from RLC_MSM_BUCKET_MIN items
+// rlc_sig_sum's bucket route stays.  When the check fails, or anything is flagged, the m Verify()s of 0.9 run from what is on the device
+// (k_gather_records of the hash points per item, rlc_fallback_all): the verdicts are those of *_verify_aggregate_common*_batch.
+// One lease, one device, no request combiner, "rlc_min" not consulted.
+namespace {
+// Where the driver finds its inputs, everything on the leased device: the nh messages that are hashed, the registry and the committees'
+// indices (null: the positions).  On the host: which hashed message group g of the plan takes (null: g itself) and which item j takes.
+struct AggRlcIn {
+    const void* d_msgs; const void* d_off_or_domain; size_t nh;
+    const void* d_pks; bool pks_jac; size_t npk; const u32* d_idx;
+    const uint32_t* h_of_group; const uint32_t* h_of_item;
+};
+// sum_j r_j sig_j into c.sum / c.sflag and its Miller loop, on the side stream (as rlc_signature_side); `one`: the plan of the one segment
+int agg_rlc_signature_side(RlcCall& c, const SegPlan& one) {
+    hipStream_t st = tl_ctx->aux[0];
+    HIPCHK(hipStreamWaitEvent(st, tl_ctx->fork, 0));
+    OnStream on(st);
+    int rc;
+    if (c.n >= RLC_MSM_BUCKET_MIN) rc = rlc_sig_sum(c.k.sig(), c.ds.as<u8>(), c.dr.as<u64>(), c.n, c.sum.as<u8>(), c.sflag.as<i32>());
+    else {
+        HIPCHK(hipMemsetAsync(c.sflag.p, 0, sizeof(i32), st));             // (the segmented sum's flag is the word's low byte)
+        rc = segsum_dev(c.k.sig(), false, c.ds.p, nullptr, c.n, nullptr, one, c.sum.as<u8>(), c.sflag.as<u8>(), 1, st, c.dr.as<u64>(), &c.k.sig().segsum_chunk_u64_opt);
+    }
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(&c.sum_inf, c.sflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    return sig_side_start_dev(c.kind, c.sum.as<u8>(), c.ss);
+}
+// The call from the point where its inputs are on the device or on their way on the main stream: c.ds the m signatures, c.dr the scalars,
+// and what `in` names.  cplan: the committees' chunk plan; gp: the group plan of the m items.  Leaves the verdicts in c.dok, synchronised
+// up to the fallback's kernels; c.held() is valid.
+int agg_common_rlc_dev(RlcCall& c, const AggRlcIn& in, const SegPlan& cplan, const blsmi_route::GroupPlan& gp) {
+    const Kind& k = c.k;
+    const int kind = c.kind;
+    const Tuning& t = tune();
+    const size_t m = c.n, dg = gp.msg_of.size(), words = (size_t)12 * NL;
+    hipStream_t s = g_stream, side = tl_ctx->aux[1];
+    SegPlan gplan, splan;
+    const uint64_t whole[2] = {0, m};
+    try {
+        segsum_plan(gp.seg_off.data(), dg, segsum_chunk_of(m), gplan, 64, 1);
+        if (m < RLC_MSM_BUCKET_MIN) segsum_plan(whole, 1, segsum_chunk_of(m), splan, 64, 1);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t load = route_load(dg);
+    const AggregateRoute ar = aggregate_route(kind, dg, false, true, t, load);   // the layout an aggregate of d' records takes; always cleared hash points
+    const HashRoute hr = in.nh == dg ? ar.hash : aggregate_route(kind, in.nh, false, true, t, load).hash;
+    const u32 hw = (u32)(k.h_bytes / 4);
+    DBuf dx, h, hg, dhg, agg, ainf, gflags, fr0, fr1;
+    HIPCHK(dx.alloc(sizeof(uint32_t) * m)); HIPCHK(h.alloc((size_t)k.h_bytes * in.nh)); HIPCHK(agg.alloc((size_t)k.pk_bytes * dg)); HIPCHK(ainf.alloc(dg)); HIPCHK(gflags.alloc(dg));
+    HIPCHK(fr0.alloc(sizeof(i32) * words * ar.records)); HIPCHK(fr1.alloc(sizeof(i32) * words * ((ar.records + 1) / 2)));
+    HIPCHK(hipEventRecord(tl_ctx->fork, s));                               // the inputs are complete here: both side streams start behind it
+    // apk_j for every item on aux[1], while the messages are hashed; join[1] marks their arrival
+    HIPCHK(hipStreamWaitEvent(side, tl_ctx->fork, 0));
+    int rc = segsum_dev(k.pk(), in.pks_jac, in.d_pks, nullptr, in.npk, in.d_idx, cplan, c.dp.as<u8>(), c.di.as<u8>(), 1, side);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(tl_ctx->join[1], side));
+    c.has_inf = true;                                                      // c.di: a committee that is empty, sums to infinity or holds a bad index
+    HIPCHK(hipMemsetAsync(c.any.p, 0, sizeof(int), s));
+    HIPCHK(hipMemcpyAsync(dx.p, gp.perm.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice, s));
+    rc = hash_dev(kind, in.d_msgs, in.d_off_or_domain, h.as<u8>(), in.nh, s, hr);
+    if (rc) return rc;
+    const u8* hgp = h.as<u8>();                                            // one hash point per group, in group order
+    if (in.h_of_group) {
+        HIPCHK(hg.alloc((size_t)k.h_bytes * dg)); HIPCHK(dhg.alloc(sizeof(uint32_t) * dg));
+        HIPCHK(hipMemcpyAsync(dhg.p, in.h_of_group, sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+        launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)hw * dg), s, h.p, dhg.p, hg.p, hw, dg);
+        hgp = hg.as<u8>();
+    }
+    HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[1], 0));
+    rlc_flag_inputs(c);
+    // sum_{j in g} r_j apk_j for every group, on the main stream (the profile names the pass 1 there); a sum at infinity is flagged like an input
+    rc = segsum_dev(k.pk(), false, c.dp.p, nullptr, m, dx.as<u32>(), gplan, agg.as<u8>(), ainf.as<u8>(), 1, s, c.dr.as<u64>(), &k.pk().segsum_chunk_u64_opt);
+    if (rc) return rc;
+    launch_quiet(KERNEL_OF(k_flag_zero_records), nblocks(dg), s, agg.p, k.pk_bytes / 4, nullptr, 0, ainf.p, gflags.p, c.any.p, dg);
+    launch_miller1(kind == 0 ? hgp : agg.as<u8>(), kind == 0 ? agg.as<u8>() : hgp, fr0.as<i32>(), dg, s, ar, nullptr);
+    const i32* prod = prod_tree(fr0.as<i32>(), ar.records, fr1.as<i32>(), fr0.as<i32>(), s);
+    HIPCHK(hipGetLastError());
+    rc = agg_rlc_signature_side(c, splan); if (rc) return rc;
+    rc = rlc_check_total(c, prod, false); if (rc) return rc;
+    if (c.held()) { HIPCHK(hipMemsetAsync(c.dok.p, 1, m, s)); return BLSMI_OK; }
+    // the m Verify()s of the 0.9 call: every item's hash point from the hashed messages, then the pair stage of a batch of m
+    DBuf hfull, dhi;
+    HIPCHK(hfull.alloc((size_t)k.h_bytes * m)); HIPCHK(dhi.alloc(sizeof(uint32_t) * m));
+    HIPCHK(hipMemcpyAsync(dhi.p, in.h_of_item, sizeof(uint32_t) * m, hipMemcpyHostToDevice, s));
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)hw * m), s, h.p, dhi.p, hfull.p, hw, m);
+    return rlc_fallback_all(c, hfull.as<u8>(), verify_route(kind, m, false, false, t, route_load(m)));
+}
+int agg_common_rlc_host(int kind, const uint8_t* msgs, const uint64_t* off_or_domain, size_t d, const uint32_t* msg_idx, const uint8_t* pks, size_t npk, const uint32_t* idx,
+                        const uint64_t* seg_off, const uint8_t* sigs, const uint64_t* scalars, uint8_t* ok, uint8_t* ok_bitmap, size_t m, int* combined, int fmt = 0) {
+    if (combined) *combined = 0;
+    int rc = rlc_check_args(msgs && off_or_domain && msg_idx && sigs && seg_off && (pks || !npk) && (ok || ok_bitmap) && m <= 0xffffffffull, scalars, m);   // (m: the permutation is the 32-bit idx of the segmented sum)
+    if (rc || m == 0) return rc;
+    rc = segsum_check(npk, idx, seg_off, m); if (rc) return rc;
+    blsmi_route::GroupPlan gp;
+    std::vector<uint64_t> coff;
+    std::vector<uint8_t> cm;
+    rc = grouped_plan_and_messages(kind, msgs, off_or_domain, d, msg_idx, m, gp, coff, cm); if (rc) return rc;
+    RlcHostScratch hs;
+    rc = rlc_scalars_and_ok(hs, scalars, ok, !ok && ok_bitmap, m); if (rc) return rc;
+    { std::lock_guard<std::mutex> lk(g_mu); rc = ensure_init_default(); if (rc) return rc; }
+    CtxLease lease;
+    if (lease.rc) return lease.rc;
+    const size_t dg = gp.msg_of.size(), total = seg_off[m];
+    const void* hoff = kind == 2 ? (const void*)off_or_domain : (const void*)coff.data();
+    SegPlan cplan;
+    try { segsum_plan(seg_off, m, segsum_chunk_of(total), cplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    hipStream_t s = g_stream;
+    RlcCall c;
+    rc = rlc_begin(c, kind, m, hoff, dg); if (rc) return rc;            // (the d' messages some item refers to)
+    const bool pj = (fmt & FMT_PK_JAC) != 0;
+    const size_t pin = rec_bytes(c.k.pk_bytes, pj);
+    DBuf reg, dix;
+    HIPCHK(reg.alloc(pin * npk)); HIPCHK(dix.alloc(sizeof(uint32_t) * total));
+    // the registry as it is (in-memory records are summed as such: k_g?_segsum_chunk_jac), the indices, the signatures, the scalars, the messages
+    if (npk) HIPCHK(hipMemcpyAsync(reg.p, pks, pin * npk, hipMemcpyHostToDevice, s));
+    if (idx && total) HIPCHK(hipMemcpyAsync(dix.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, s));
+    rc = upload_points(c.k.sig(), (fmt & FMT_SIG_JAC) != 0, sigs, c.ds.p, m, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c.dr.p, scalars, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
+    rc = c.msgs.copy(cm.data(), hoff, s); if (rc) return rc;
+    const AggRlcIn in{c.msgs.m.p, c.msgs.off.p, dg, reg.p, pj, npk, idx ? dix.as<u32>() : nullptr, nullptr, gp.group_of.data()};
+    rc = agg_common_rlc_dev(c, in, cplan, gp); if (rc) return rc;
+    return rlc_finish(c, ok, ok_bitmap, combined);
+}
+// the _dev forms: every buffer on one of the library's devices; seg_off and msg_idx come back once for the two plans; every table entry is hashed
+template <int KIND>
+int agg_common_rlc_dev_api(const void* d_msgs, const void* d_off_or_domain, size_t d, const void* d_msg_idx, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off,
+                           const void* d_sigs, const uint64_t* scalars, void* d_ok, size_t m, int* combined, void* stream) {
+    if (combined) *combined = 0;
+    int rc = rlc_check_args(d_msgs && d_off_or_domain && d_msg_idx && d_seg_off && d_sigs && d_ok && (d_pks || !npk) && m <= 0xffffffffull, scalars, m);
+    if (rc || m == 0) return rc;
+    RlcHostScratch hs;
+    uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    hipStream_t s = g_stream;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> mi;
+    try { mi.resize(m); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    HIPCHK(hipMemcpyAsync(mi.data(), d_msg_idx, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
+    rc = segsum_fetch_offsets(d_seg_off, m, off); if (rc) return rc;       // (synchronises: msg_idx is here as well)
+    blsmi_route::GroupPlan gp;
+    SegPlan cplan;
+    try {
+        if (!blsmi_route::group_plan(mi.data(), m, d, gp)) return BLSMI_E_ARG;
+        segsum_plan(off.data(), m, segsum_chunk_of(off[m]), cplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const uint64_t no_msgs[1] = {0};
+    RlcCall c;
+    rc = rlc_begin(c, KIND, m, no_msgs, 0); if (rc) return rc;             // (the messages stay where the caller has them)
+    HIPCHK(hipMemcpyAsync(c.ds.p, d_sigs, (size_t)c.k.sig_bytes * m, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c.dr.p, scalars, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
+    const AggRlcIn in{d_msgs, d_off_or_domain, d, d_pks, false, npk, (const u32*)d_idx, gp.msg_of.data(), mi.data()};
+    rc = agg_common_rlc_dev(c, in, cplan, gp); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(d_ok, c.dok.p, m, hipMemcpyDeviceToDevice, s));
+    return rlc_finish(c, nullptr, nullptr, combined);
+}
+}  // namespace
+#define ACR_ARGS size_t d, const uint32_t* msg_idx, const uint8_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off, const uint8_t* sigs, const uint64_t* scalars, \
+                 uint8_t* ok, uint8_t* ok_bitmap, size_t m, int* combined
+#define ACR_ARGS_JAC size_t d, const uint32_t* msg_idx, const uint64_t* pks, size_t npk, const uint32_t* idx, const uint64_t* seg_off, const uint64_t* sigs, const uint64_t* scalars, \
+                     uint8_t* ok, uint8_t* ok_bitmap, size_t m, int* combined
+#define ACR_ARGS_DEV size_t d, const void* d_msg_idx, const void* d_pks, size_t npk, const void* d_idx, const void* d_seg_off, const void* d_sigs, const uint64_t* scalars, \
+                     void* d_ok, size_t m, int* combined, void* stream
+#define ACR(kind, ms, o) return agg_common_rlc_host(kind, ms, o, d, msg_idx, pks, npk, idx, seg_off, sigs, scalars, ok, ok_bitmap, m, combined)
+#define ACRJ(kind, ms, o) return agg_common_rlc_host(kind, ms, o, d, msg_idx, JACP(pks), npk, idx, seg_off, JACP(sigs), scalars, ok, ok_bitmap, m, combined, FMT_JAC)
+#define ACRD(kind, ms, o) return agg_common_rlc_dev_api<kind>(ms, o, d, d_msg_idx, d_pks, npk, d_idx, d_seg_off, d_sigs, scalars, d_ok, m, combined, stream)
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch_rlc(const uint8_t* msgs, const uint64_t* msg_off, ACR_ARGS) { ACR(0, msgs, msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_rlc(const uint8_t* msgs, const uint64_t* msg_off, ACR_ARGS) { ACR(1, msgs, msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc(const uint8_t* msgs32, const uint8_t domain[8], ACR_ARGS) { ACR(2, msgs32, reinterpret_cast<const uint64_t*>(domain)); }
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch_rlc_jac(const uint8_t* msgs, const uint64_t* msg_off, ACR_ARGS_JAC) { ACRJ(0, msgs, msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_rlc_jac(const uint8_t* msgs, const uint64_t* msg_off, ACR_ARGS_JAC) { ACRJ(1, msgs, msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac(const uint8_t* msgs32, const uint8_t domain[8], ACR_ARGS_JAC) { ACRJ(2, msgs32, reinterpret_cast<const uint64_t*>(domain)); }
+BLSMI_API int blsmi_g2pubs_verify_aggregate_common_batch_rlc_dev(const void* d_msgs, const void* d_msg_off, ACR_ARGS_DEV) { ACRD(0, d_msgs, d_msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_batch_rlc_dev(const void* d_msgs, const void* d_msg_off, ACR_ARGS_DEV) { ACRD(1, d_msgs, d_msg_off); }
+BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev(const void* d_msgs32, const void* d_domain, ACR_ARGS_DEV) { ACRD(2, d_msgs32, d_domain); }
+#undef ACR_ARGS
+#undef ACR_ARGS_JAC
+#undef ACR_ARGS_DEV
+#undef ACR
+#undef ACRJ
+#undef ACRD
 #undef JACP

@@ -1873,9 +1873,11 @@ void segsum_plan(const uint64_t* seg_off, size_t m, size_t K, SegPlan& p, size_t
 // by the copy: both stay alive until the caller synchronises).  jac: d_pts are in-memory Jacobian records (no d_in_inf).
 // d_out: m affine records, d_out_inf: m bytes (1 infinity, bad_code for a segment with an index >= npk, 0 otherwise).
 // d_scalars (may be null; affine points only): npk 64-bit weights -- segment j is then sum scalars[i] * pts[i] over its indices i, pass 1
-// running the ladder (k_g?_segsum_chunk_u64) over a plan whose first pass has chunks of one position.
+// running the ladder (k_g?_segsum_chunk_u64) over a plan whose first pass has chunks of one position.  u64_pass1 (may be null: the
+// one-lane kernel, as the forms of 0.11 to 0.13 and blsmi_g?_sum_segmented_u64 run it): the row's entry that runs the weighted pass 1
+// instead -- g.segsum_chunk_u64_opt, G2's lane-pair ladder unless the options say one lane.
 int segsum_dev(const GroupKernels& g, bool jac, const void* d_pts, const u8* d_in_inf, size_t npk, const u32* d_idx, const SegPlan& p, u8* d_out, u8* d_out_inf,
-               u8 bad_code, hipStream_t s, const u64* d_scalars = nullptr) {
+               u8 bad_code, hipStream_t s, const u64* d_scalars = nullptr, const SegsumU64Pass1* u64_pass1 = nullptr) {
     const size_t m = p.m;
     if (m == 0) return BLSMI_OK;
     const size_t words = (size_t)g.fq * NL + 1;
@@ -1890,8 +1892,9 @@ int segsum_dev(const GroupKernels& g, bool jac, const void* d_pts, const u8* d_i
     if (n1 && d_scalars) {
         if (jac) return BLSMI_E_ARG;
         const bool mark = tl_ctx && s == tl_ctx->stream;                   // (profile marks are events on the context's main stream)
-        if (mark) prof_mark(g.segsum_chunk_u64.name);
-        launch_quiet(g.segsum_chunk_u64, nblocks(n1), s, d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
+        const SegsumU64Pass1 pass1 = u64_pass1 ? *u64_pass1 : SegsumU64Pass1{g.segsum_chunk_u64, Layout::single};
+        if (mark) prof_mark(pass1.k.name);
+        launch_items_quiet(pass1, n1, s, d_pts, d_in_inf, npk, d_scalars, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
         if (mark) prof_mark(nullptr);
     } else if (n1) {
         if (jac) launch_quiet(g.segsum_chunk_jac, nblocks(n1), s, d_pts, npk, d_idx, at64(p.ch_lo), at32(p.ch_cnt), at32(p.ch_seg), bad.p, a.p, n1);
@@ -1911,7 +1914,7 @@ size_t segsum_chunk_of(size_t total) { const size_t K = tune().segsum_chunk; ret
 // host forms: everything checked here first, then one lease
 // weighted (not with jac): the _u64 forms, scalars are npk 64-bit weights
 int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m,
-                       uint8_t* out, uint8_t* out_inf, bool weighted = false, const uint64_t* scalars = nullptr) {
+                       uint8_t* out, uint8_t* out_inf, bool weighted = false, const uint64_t* scalars = nullptr, const SegsumU64Pass1* u64_pass1 = nullptr) {
     if (m == 0) return BLSMI_OK;
     if (!out || !out_inf || (npk && !pts) || (weighted && npk && !scalars)) return BLSMI_E_ARG;
     int rc = segsum_check(npk, idx, seg_off, m);
@@ -1928,7 +1931,7 @@ int sum_segmented_host(int group, bool jac, const uint8_t* pts, const uint8_t* i
     if (in_inf && !jac && npk) HIPCHK(hipMemcpyAsync(di.p, in_inf, npk, hipMemcpyHostToDevice, g_stream));
     if (idx && total) HIPCHK(hipMemcpyAsync(dx.p, idx, sizeof(uint32_t) * total, hipMemcpyHostToDevice, g_stream));
     rc = segsum_dev(g, jac, dp.p, (in_inf && !jac) ? di.as<u8>() : nullptr, npk, idx ? dx.as<u32>() : nullptr, plan, dout.as<u8>(), dinf.as<u8>(), 2, g_stream,
-                    weighted ? dsc.as<u64>() : nullptr);
+                    weighted ? dsc.as<u64>() : nullptr, u64_pass1);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, pb * m, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(out_inf, dinf.p, m, hipMemcpyDeviceToHost, g_stream));
@@ -1972,6 +1975,10 @@ BLSMI_API int blsmi_g1_sum_segmented_u64(const uint8_t* pts, const uint8_t* in_i
 }
 BLSMI_API int blsmi_g2_sum_segmented_u64(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint64_t* scalars, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
     return sum_segmented_host(2, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf, true, scalars);
+}
+// blsmi_g2_sum_segmented_u64 with pass 1 through the lane-pair ladder (k_g2_segsum_chunk_u64_pair) whatever the options say: the parity test's way to it
+BLSMI_API int blsmi_debug_g2_sum_segmented_u64_pair(const uint8_t* pts, const uint8_t* in_inf, size_t npk, const uint64_t* scalars, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
+    return sum_segmented_host(2, false, pts, in_inf, npk, idx, seg_off, m, out, out_inf, true, scalars, &group_kernels(2, true).segsum_chunk_u64_opt);
 }
 BLSMI_API int blsmi_g1_sum_segmented_jac(const uint64_t* pts_jac, size_t npk, const uint32_t* idx, const uint64_t* seg_off, size_t m, uint8_t* out, uint8_t* out_inf) {
     return sum_segmented_host(1, true, reinterpret_cast<const uint8_t*>(pts_jac), nullptr, npk, idx, seg_off, m, out, out_inf);

@@ -1268,7 +1268,7 @@ def g1pubs_verify_with_domain_batch_rlc_grouped_jac(msgs32, domain8, msg_idx, pk
     return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac", 2, True, msgs32, msg_idx, pks, sigs, None, scalars, domain8)
 
 
-def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf):
+def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf, fn_of=None):
     so, pidx, _keep = _seg_args(idx, seg_off)
     m = so.size - 1
     p = _u8(pts, pb * npk) if npk else np.zeros(1, np.uint8)
@@ -1276,7 +1276,7 @@ def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf):
     f = _u8(in_inf, npk) if in_inf is not None else None
     out = np.zeros(max(1, pb * m), dtype=np.uint8)
     oinf = np.zeros(max(1, m), dtype=np.uint8)
-    _check(_fn_0_11(name)(_p8(p), _p8(f), npk, pr if npk else None, pidx, so.ctypes.data_as(_u64p), m, _p8(out), _p8(oinf)), name[len("blsmi_"):])
+    _check((fn_of or _fn_0_11)(name)(_p8(p), _p8(f), npk, pr if npk else None, pidx, so.ctypes.data_as(_u64p), m, _p8(out), _p8(oinf)), name[len("blsmi_"):])
     return out[:pb * m].tobytes(), oinf[:m].copy()
 
 
@@ -1588,3 +1588,106 @@ def decompress_batch_jac_dev(group, d_in, n, d_out_jac, d_out_inf, d_err, check_
 def compress_batch_jac_dev(group, d_pts_jac, n, d_out, stream=0):
     name = "blsmi_g1_compress_batch_jac_dev" if group == "g1" else "blsmi_g2_compress_batch_jac_dev"
     _check(_fn_0_15(name)(d_pts_jac or 0, d_out or 0, n, stream or 0), name[len("blsmi_"):])
+
+
+# ---- committee aggregates, randomised (blsmi 0.16): many VerifyAggregateCommon under one pairing equation -----------------------------
+_A_HEAD = [_u8p, _u64p, C.c_size_t, _u32p]                                 # msgs, msg_off, d, msg_idx
+_A_HEAD_DOMAIN = [_u8p, _u8p, C.c_size_t, _u32p]                           # msgs32, domain, d, msg_idx
+_A_TAIL = [_u64p, _u8p, _u8p, C.c_size_t, C.POINTER(C.c_int)]              # scalars, ok, ok_bitmap, m, combined
+_A_HOST = [_u8p, C.c_size_t, _u32p, _u64p, _u8p] + _A_TAIL                 # pks, npk, idx, seg_off, sigs
+_A_JAC = [_u64p, C.c_size_t, _u32p, _u64p, _u64p] + _A_TAIL
+_A_DEV = [_V, _V, C.c_size_t, _V, _V, C.c_size_t, _V, _V, _V, _u64p, _V, C.c_size_t, C.POINTER(C.c_int), _V]
+# the argument types of the ten entry points of 0.16, as include/blsmi.h declares them (tests/test_agg_common_rlc_cpu.py compares)
+ARGTYPES_0_16 = {
+    "blsmi_g2pubs_verify_aggregate_common_batch_rlc": _A_HEAD + _A_HOST,
+    "blsmi_g1pubs_verify_aggregate_common_batch_rlc": _A_HEAD + _A_HOST,
+    "blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc": _A_HEAD_DOMAIN + _A_HOST,
+    "blsmi_g2pubs_verify_aggregate_common_batch_rlc_jac": _A_HEAD + _A_JAC,
+    "blsmi_g1pubs_verify_aggregate_common_batch_rlc_jac": _A_HEAD + _A_JAC,
+    "blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac": _A_HEAD_DOMAIN + _A_JAC,
+    "blsmi_g2pubs_verify_aggregate_common_batch_rlc_dev": _A_DEV,
+    "blsmi_g1pubs_verify_aggregate_common_batch_rlc_dev": _A_DEV,
+    "blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev": _A_DEV,
+    "blsmi_debug_g2_sum_segmented_u64_pair": _SUM_U64,
+}
+
+
+def _fn_0_16(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_16[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _agg_common_batch_rlc(name, kind, jac, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars, domain8=None):
+    """-> (ok, bitmap, combined); msgs: the table of d messages, msg_idx: one index into it per item, the registry and the committees as
+    _agg_common_batch takes them"""
+    so, pidx, _keep = _seg_args(idx, seg_off)
+    m = so.size - 1
+    ix, pix = _msg_idx(msg_idx, m)
+    pkb, sgb = (192, 96) if kind == 0 else (96, 192)
+    if domain8 is None:
+        buf, off = _msgs(msgs)
+        head = (_p8(buf), off.ctypes.data_as(_u64p))
+    else:
+        buf = _u8(b"".join(bytes(x) for x in msgs) or b"\0" * 32, 32 * max(len(msgs), 1))
+        off = _u8(domain8, 8)
+        head = (_p8(buf), _p8(off))
+    if jac:
+        p, pp = _j64(pks, pkb // 2 * 3 * npk)
+        s, ps = _j64(sigs, sgb // 2 * 3 * m)
+    else:
+        p = _u8(pks, pkb * npk) if npk else np.zeros(1, np.uint8)
+        s = _u8(sigs, sgb * m)
+        pp, ps = _p8(p), _p8(s)
+    r, pr = _scalars(scalars, m)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    bitmap = np.zeros(max(1, (m + 7) // 8), dtype=np.uint8)
+    comb = C.c_int(0)
+    _check(_fn_0_16(name)(*head, len(msgs), pix, pp, npk, pidx, so.ctypes.data_as(_u64p), ps, pr, _p8(ok), _p8(bitmap), m, C.byref(comb)), name[len("blsmi_"):])
+    return ok[:m].astype(bool), bitmap[:(m + 7) // 8].copy(), comb.value
+
+
+def g2pubs_verify_aggregate_common_batch_rlc(msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    """blsmi_g2pubs_verify_aggregate_common_batch_rlc -> (ok, bitmap, combined): item j is VerifyAggregateCommon(sigs[j], {pks[idx[k]] :
+    seg_off[j] <= k < seg_off[j + 1]}, msgs[msg_idx[j]]); one pairing equation for all m (combined == 1) or, when it fails, the verdicts of
+    g2pubs_verify_aggregate_common_batch (combined == 0).  scalars: m nonzero 64-bit integers, or None (the library draws them)."""
+    return _agg_common_batch_rlc("blsmi_g2pubs_verify_aggregate_common_batch_rlc", 0, False, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars)
+
+
+def g1pubs_verify_aggregate_common_batch_rlc(msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    return _agg_common_batch_rlc("blsmi_g1pubs_verify_aggregate_common_batch_rlc", 1, False, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars)
+
+
+def g1pubs_verify_aggregate_common_with_domain_batch_rlc(msgs32, domain8, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    return _agg_common_batch_rlc("blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc", 2, False, msgs32, msg_idx, pks, npk, idx, seg_off, sigs, scalars, domain8)
+
+
+def g2pubs_verify_aggregate_common_batch_rlc_jac(msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    """the same over in-memory keys (288 bytes) and signatures (144 bytes)"""
+    return _agg_common_batch_rlc("blsmi_g2pubs_verify_aggregate_common_batch_rlc_jac", 0, True, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars)
+
+
+def g1pubs_verify_aggregate_common_batch_rlc_jac(msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    return _agg_common_batch_rlc("blsmi_g1pubs_verify_aggregate_common_batch_rlc_jac", 1, True, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars)
+
+
+def g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac(msgs32, domain8, msg_idx, pks, npk, idx, seg_off, sigs, scalars=None):
+    return _agg_common_batch_rlc("blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac", 2, True, msgs32, msg_idx, pks, npk, idx, seg_off, sigs, scalars, domain8)
+
+
+def verify_aggregate_common_batch_rlc_dev(group, d_msgs, d_off_or_domain, d, d_msg_idx, d_pks, npk, d_idx, d_seg_off, d_sigs, d_ok, m, scalars=None, stream=0, domain=False):
+    """device-pointer forms (ints): group "g2pubs" / "g1pubs" (domain=True: d_msgs holds d*32 bytes, d_off_or_domain the 8-byte domain); the m
+    verdict bytes are in d_ok when the call returns; scalars stay on the host.  -> combined"""
+    name = "blsmi_g2pubs_verify_aggregate_common_batch_rlc_dev" if group == "g2pubs" else \
+        ("blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev" if domain else "blsmi_g1pubs_verify_aggregate_common_batch_rlc_dev")
+    r, pr = _scalars(scalars, m)
+    comb = C.c_int(0)
+    _check(_fn_0_16(name)(d_msgs or 0, d_off_or_domain or 0, d, d_msg_idx or 0, d_pks or 0, npk, d_idx or 0, d_seg_off or 0, d_sigs or 0, pr, d_ok or 0, m,
+                          C.byref(comb), stream or 0), name[len("blsmi_"):])
+    return comb.value
+
+
+def debug_g2_sum_segmented_u64_pair(pts, npk, scalars, idx, seg_off, in_inf=None):
+    """g2_sum_segmented_u64 with pass 1 through the lane-pair ladder (k_g2_segsum_chunk_u64_pair), for the parity test"""
+    return _sum_segmented_u64("blsmi_debug_g2_sum_segmented_u64_pair", 192, pts, npk, scalars, idx, seg_off, in_inf, _fn_0_16)

@@ -11,7 +11,7 @@ plus VerifyBatch, the batch form the one-tuple-per-call Go API lacks.
 """
 from . import engine
 from ._groups import DeserializeError, Point, all_in_memory, committee_batch_args, committee_sums, point_sum, points_valid  # noqa: F401
-from ._groups import deserialize_objects, serialize_points, verify_serialized_randomized
+from ._groups import deserialize_objects, message_table, serialize_points, verify_serialized_randomized
 
 SIG_GROUP, PK_GROUP = 2, 1
 
@@ -353,6 +353,36 @@ def VerifyAggregateCommonWithDomainBatch(sigs, committees, msgs32, domain8):
     fn = engine.g1pubs_verify_aggregate_common_with_domain_batch_jac if jac else engine.g1pubs_verify_aggregate_common_with_domain_batch
     ok, _ = fn(b"".join(bytes(x) for x in msgs32), domain8, keys, npk, None, off, sg)
     return [bool(x) for x in ok]
+
+
+def VerifyAggregateCommonBatchRandomized(sigs, committees, msgs, scalars=None):
+    """VerifyAggregateCommonBatch under ONE pairing equation with random 64-bit weights (scalars: m nonzero integers, or None to have them
+    drawn): one Miller loop per distinct message and one final exponentiation; equal messages are put into the table once here.  The
+    verdicts are VerifyAggregateCommonBatch's -- when the equation fails, or an item is flagged, they come from its m checks."""
+    m = len(sigs)
+    if not (len(committees) == len(msgs) == m) or (scalars is not None and len(scalars) != m):
+        raise ValueError("length mismatch")
+    if m == 0:
+        return []
+    table, idx = message_table(msgs)
+    jac, keys, npk, off, sg = committee_batch_args([[k.p for k in c] for c in committees], [s.s for s in sigs])
+    fn = engine.g1pubs_verify_aggregate_common_batch_rlc_jac if jac else engine.g1pubs_verify_aggregate_common_batch_rlc
+    return [bool(x) for x in fn(table, idx, keys, npk, None, off, sg, scalars)[0]]
+
+
+def VerifyAggregateCommonWithDomainBatchRandomized(sigs, committees, msgs32, domain8, scalars=None):
+    """VerifyAggregateCommonWithDomainBatch under one pairing equation (VerifyAggregateCommonBatchRandomized)"""
+    m = len(sigs)
+    if not (len(committees) == len(msgs32) == m) or (scalars is not None and len(scalars) != m):
+        raise ValueError("length mismatch")
+    if m == 0:
+        return []
+    if any(len(x) != 32 for x in msgs32):
+        raise ValueError("messages must be 32 bytes")
+    table, idx = message_table(msgs32)
+    jac, keys, npk, off, sg = committee_batch_args([[k.p for k in c] for c in committees], [s.s for s in sigs])
+    fn = engine.g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac if jac else engine.g1pubs_verify_aggregate_common_with_domain_batch_rlc
+    return [bool(x) for x in fn(table, domain8, idx, keys, npk, None, off, sg, scalars)[0]]
 
 
 def ValidatePublicKeys(pubs):

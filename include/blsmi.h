@@ -83,8 +83,10 @@ void blsmi_shutdown(void);
  * randomised batch verification that finds the bad tuples by cells (blsmi_g?pubs_*verify*_batch_rlc_grouped_locate[_jac]); no existing prototype
  * changes, no new option.  0.14 adds the batch point validation (blsmi_g?_check_batch[_jac|_dev]: on-curve and subgroup status of points in either
  * form, no inversion, no square root) and the BLSMI_POINT_* status names; no existing prototype changes, no new option.  0.15 adds the conversions between the compressed wire format and the in-memory points
- * (blsmi_g?_decompress_batch_jac[_dev], blsmi_g?_compress_batch_jac[_dev]); no existing prototype changes, no new option.  The string below still begins
- * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14 and 0.15 by the presence of
+ * (blsmi_g?_decompress_batch_jac[_dev], blsmi_g?_compress_batch_jac[_dev]); no existing prototype changes, no new option.  0.16 adds the randomised
+ * verification of many committee aggregates in one call (blsmi_g?pubs_verify_aggregate_common*_batch_rlc[_jac|_dev]) and
+ * blsmi_debug_g2_sum_segmented_u64_pair; no existing prototype changes, no new option.  The string below still begins
+ * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15 and 0.16 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -833,6 +835,72 @@ int blsmi_g1_decompress_batch_jac_dev(const void *d_in, int check_subgroup, void
 int blsmi_g2_decompress_batch_jac_dev(const void *d_in, int check_subgroup, void *d_out_jac, void *d_out_inf /* may be NULL */, void *d_err, size_t n, void *stream);
 int blsmi_g1_compress_batch_jac_dev(const void *d_pts_jac, void *d_out, size_t n, void *stream);
 int blsmi_g2_compress_batch_jac_dev(const void *d_pts_jac, void *d_out, size_t n, void *stream);
+
+/* ---- committee aggregates, randomised (blsmi 0.16) -----------------------------------------------------------------------------------
+ * "Verify multiple aggregate signatures": the batches of VerifyAggregateCommon of "committees" above under the ONE equation of the grouped
+ * randomised form.  A block's attestations, a slot's gossip aggregates: m signature sets (signature, committee of the registry, message),
+ * usually with far fewer distinct messages than sets.  Item j is
+ *   VerifyAggregateCommon(sig_j, {pks[idx[k]] : seg_off[j] <= k < seg_off[j + 1]}, table[msg_idx[j]])
+ * The message table and msg_idx are those of *_verify_batch_rlc_grouped: msgs with msg_off[d + 1] (with_domain: msgs32, d * 32 bytes, and
+ * the 8-byte domain), then msg_idx[m].  The registry pks[npk], idx (NULL: the positions k themselves) and seg_off[m + 1] are those of
+ * *_verify_aggregate_common_batch.  sigs: m records.  scalars: m nonzero 64-bit words, or NULL to have them drawn from the OS for this
+ * call.  ok: m verdict bytes, ok_bitmap: (m + 7) / 8 bytes, LSB first; either may be NULL, not both.  With apk_j the sum of committee j:
+ *     g1pubs: e(G1gen, sum_j r_j sig_j) == prod_g e(sum_{j in g} r_j apk_j, H(m_g))
+ *     g2pubs: e(sum_j r_j sig_j, G2gen) == prod_g e(H(m_g), sum_{j in g} r_j apk_j)
+ * one hash and one Miller loop per table entry some item refers to and ONE final exponentiation, where the 0.9 call runs m hashes, 2m
+ * Miller loops and m final exponentiations.  The committee sums run beside the hash as they do there; both weighted sums run a 64-bit
+ * ladder per item (G2: a lane pair per item by default, one lane under BLSMI_LAYOUT=single; the same points either way).
+ * Verdicts: ok[j] is exactly what *_verify_aggregate_common*_batch gives for the same inputs -- 0 for an empty committee, for one that
+ * sums to infinity, for the all-zero signature record and (the _dev forms) for a committee holding an index >= npk.  *combined (may be
+ * NULL) = 1 exactly when every verdict came from the one equation that held; otherwise the equation failed or a flagged item met it, and
+ * the m Verify()s of the 0.9 call ran from what was on the device (the check is not narrowed to blocks or cells here).
+ * Soundness: with an invalid item among them the equation holds with probability at most 2^-64 over the drawn scalars, keys and
+ * signatures in the prime-order subgroups (as Deserialize guarantees).  The weights are per ITEM also inside a message's group: with caller
+ * scalars r_a == r_b two items of one message may swap signatures unnoticed -- the caller's responsibility, as every caller scalar is.
+ *   - the host forms return BLSMI_E_ARG before any device work for: offsets that do not start at 0 or decrease, an index >= npk,
+ *     msg_idx[j] >= d (d = 0 with m > 0 included), a zero caller scalar, a NULL input with m > 0, both outputs NULL.
+ *     m = 0: BLSMI_OK, combined = 0.
+ *   - table entries with equal bytes are not merged; the host forms never hash an entry no item refers to.
+ *   - _jac: registry and signatures as the Go values hold them (G?Projective records, z == 0 is infinity), no infinity flags.
+ *   - _dev: every buffer on one of the library's devices, as the 0.9 _dev forms take them (affine records; d_msg_off / d_domain; d_ok: m
+ *     bytes), plus d_msg_idx (m u32).  scalars and combined stay on the host.  seg_off and msg_idx are read back once for the plans
+ *     (offsets that do not start at 0 or decrease, msg_idx[j] >= d: BLSMI_E_ARG); every table entry is hashed.
+ * "rlc_min" does NOT apply: calling this form is the caller's choice of the combined path, at any m.  The call takes one lease and runs on
+ * one device; it is not split and never joins the request combiner.  DESIGN.md 3q has the shapes at which it wins and loses against the
+ * 0.9 call. */
+int blsmi_g2pubs_verify_aggregate_common_batch_rlc(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* m */,
+                                                   const uint8_t *pks /* npk*192 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off /* m+1 */,
+                                                   const uint8_t *sigs /* m*96 */, const uint64_t *scalars /* m, may be NULL */,
+                                                   uint8_t *ok /* m, may be NULL */, uint8_t *ok_bitmap /* may be NULL */, size_t m, int *combined);
+int blsmi_g1pubs_verify_aggregate_common_batch_rlc(const uint8_t *msgs, const uint64_t *msg_off /* d+1 */, size_t d, const uint32_t *msg_idx /* m */,
+                                                   const uint8_t *pks /* npk*96 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off /* m+1 */,
+                                                   const uint8_t *sigs /* m*192 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t m, int *combined);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc(const uint8_t *msgs32 /* d*32 */, const uint8_t domain[8], size_t d, const uint32_t *msg_idx /* m */,
+                                                               const uint8_t *pks /* npk*96 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off /* m+1 */,
+                                                               const uint8_t *sigs /* m*192 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t m, int *combined);
+int blsmi_g2pubs_verify_aggregate_common_batch_rlc_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx,
+                                                       const uint64_t *pks /* npk*36 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off,
+                                                       const uint64_t *sigs /* m*18 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t m, int *combined);
+int blsmi_g1pubs_verify_aggregate_common_batch_rlc_jac(const uint8_t *msgs, const uint64_t *msg_off, size_t d, const uint32_t *msg_idx,
+                                                       const uint64_t *pks /* npk*18 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off,
+                                                       const uint64_t *sigs /* m*36 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t m, int *combined);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac(const uint8_t *msgs32, const uint8_t domain[8], size_t d, const uint32_t *msg_idx,
+                                                                   const uint64_t *pks /* npk*18 */, size_t npk, const uint32_t *idx, const uint64_t *seg_off,
+                                                                   const uint64_t *sigs /* m*36 */, const uint64_t *scalars, uint8_t *ok, uint8_t *ok_bitmap, size_t m, int *combined);
+int blsmi_g2pubs_verify_aggregate_common_batch_rlc_dev(const void *d_msgs, const void *d_msg_off, size_t d, const void *d_msg_idx, const void *d_pks, size_t npk,
+                                                       const void *d_idx, const void *d_seg_off, const void *d_sigs, const uint64_t *scalars /* host: m, may be NULL */,
+                                                       void *d_ok, size_t m, int *combined /* host */, void *stream);
+int blsmi_g1pubs_verify_aggregate_common_batch_rlc_dev(const void *d_msgs, const void *d_msg_off, size_t d, const void *d_msg_idx, const void *d_pks, size_t npk,
+                                                       const void *d_idx, const void *d_seg_off, const void *d_sigs, const uint64_t *scalars, void *d_ok, size_t m,
+                                                       int *combined, void *stream);
+int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev(const void *d_msgs32, const void *d_domain, size_t d, const void *d_msg_idx, const void *d_pks, size_t npk,
+                                                                   const void *d_idx, const void *d_seg_off, const void *d_sigs, const uint64_t *scalars, void *d_ok, size_t m,
+                                                                   int *combined, void *stream);
+/* For the parity tests: blsmi_g2_sum_segmented_u64 (arguments, checks and bytes) with pass 1 through the lane-pair ladder
+ * k_g2_segsum_chunk_u64_pair whatever BLSMI_LAYOUT says -- the kernel the call above takes by default. */
+int blsmi_debug_g2_sum_segmented_u64_pair(const uint8_t *pts /* npk*192 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk, const uint64_t *scalars /* npk */,
+                                          const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
+                                          uint8_t *out /* m*192 */, uint8_t *out_inf /* m */);
 
 #ifdef __cplusplus
 }

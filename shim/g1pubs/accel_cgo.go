@@ -560,6 +560,95 @@ func VerifyAggregateCommonWithDomainBatch(sigs []*Signature, committees [][]*Pub
 	return out
 }
 
+// messageTable puts equal messages into the table once: msgs[j] is table[idx[j]].
+func messageTable(msgs [][]byte) (table [][]byte, idx []uint32) {
+	at := make(map[string]uint32, len(msgs))
+	idx = make([]uint32, len(msgs))
+	for j, m := range msgs {
+		k, seen := at[string(m)]
+		if !seen {
+			k = uint32(len(table))
+			at[string(m)] = k
+			table = append(table, m)
+		}
+		idx[j] = k
+	}
+	return table, idx
+}
+
+// VerifyAggregateCommonBatchRandomized is VerifyAggregateCommonBatch under ONE pairing equation (blsmi 0.16; INTEGRATION.md 2n): the
+// library draws a random 64-bit weight per item, and one Miller loop per distinct message and one final exponentiation stand for the m
+// checks.  Equal messages are put into the table once here.  The verdicts are VerifyAggregateCommonBatch's: when the equation fails, or a
+// committee is empty or sums to infinity, they come from its m checks.
+func VerifyAggregateCommonBatchRandomized(sigs []*Signature, committees [][]*PublicKey, msgs [][]byte) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(committees) != n || len(msgs) != n {
+		panic("blsmi: VerifyAggregateCommonBatchRandomized: length mismatch")
+	}
+	seg := make([]C.uint64_t, n+1) // committee j = keys[seg[j]:seg[j+1]]: the idx = NULL form
+	var keys []*PublicKey
+	for j, c := range committees {
+		keys = append(keys, c...)
+		seg[j+1] = seg[j] + C.uint64_t(len(c))
+	}
+	table, msgIdx := messageTable(msgs)
+	m, off := packMsgs(table)
+	pk := packKeys(keys)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_aggregate_common_batch_rlc_jac(u8(m), &off[0], C.size_t(len(table)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])),
+		u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), nil, u8(ok), nil, C.size_t(n), nil), "g1pubs_verify_aggregate_common_batch_rlc_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
+// VerifyAggregateCommonWithDomainBatchRandomized is VerifyAggregateCommonWithDomainBatch under one pairing equation
+// (VerifyAggregateCommonBatchRandomized).
+func VerifyAggregateCommonWithDomainBatchRandomized(sigs []*Signature, committees [][]*PublicKey, msgs [][32]byte, domain [8]byte) []bool {
+	n := len(sigs)
+	out := make([]bool, n)
+	if n == 0 {
+		return out
+	}
+	if len(committees) != n || len(msgs) != n {
+		panic("blsmi: VerifyAggregateCommonWithDomainBatchRandomized: length mismatch")
+	}
+	seg := make([]C.uint64_t, n+1) // committee j = keys[seg[j]:seg[j+1]]: the idx = NULL form
+	var keys []*PublicKey
+	for j, c := range committees {
+		keys = append(keys, c...)
+		seg[j+1] = seg[j] + C.uint64_t(len(c))
+	}
+	at := make(map[[32]byte]uint32, n)
+	var table [][32]byte
+	msgIdx := make([]uint32, n)
+	for j, m := range msgs {
+		k, seen := at[m]
+		if !seen {
+			k = uint32(len(table))
+			at[m] = k
+			table = append(table, m)
+		}
+		msgIdx[j] = k
+	}
+	pk := packKeys(keys)
+	sg := packSigs(sigs)
+	ok := make([]byte, n)
+	must(C.blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac((*C.uint8_t)(unsafe.Pointer(&table[0])), (*C.uint8_t)(unsafe.Pointer(&domain[0])),
+		C.size_t(len(table)), (*C.uint32_t)(unsafe.Pointer(&msgIdx[0])), u64(pk), C.size_t(len(keys)), nil, &seg[0], u64(sg), nil, u8(ok), nil, C.size_t(n), nil),
+		"g1pubs_verify_aggregate_common_with_domain_batch_rlc_jac")
+	for i := range ok {
+		out[i] = ok[i] != 0
+	}
+	return out
+}
+
 // ---- the wire format in batches (blsmi 0.15; INTEGRATION.md 2m) --------------------------------------------------------------------------
 // Keys and signatures arrive and leave compressed (48 / 96 bytes, g1pubs/bls.go:18-20, 67-69).  Upstream deserialises one element per call on a
 // host core -- a square root plus the r * P subgroup walk -- and serialises through one Fq inversion per point; the functions below do either for
