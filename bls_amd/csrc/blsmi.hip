@@ -10,6 +10,7 @@
 #include "group_plan.h"
 #include "locate_plan.h"
 #include "cell_plan.h"
+#include "pprod_rlc_plan.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

@@ -117,6 +117,17 @@ __device__ void mul_u64_body(const u8* pts, const u64* scalars, u8* out, u8* out
 }
 KERNEL2 k_g1_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) { mul_u64_body<FpS, 96>(pts, scalars, out, out_inf, n); }
 KERNEL k_g2_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n) { mul_u64_body<Fp2S, 192>(pts, scalars, out, out_inf, n); }
+// k_g1_mul_u64 through an index (blsmi 0.17: the singleton groups of a randomised pairing-product batch): out[t] = scalars[i] * pts[i] for
+// i = idx[t], the scalar addressed like the point; a point whose flags[i] has bit 0 set (flags may be null) counts as infinity.  The host has
+// built the indices (pprod_rlc_plan.h: every one below the number of points).
+KERNEL2 k_g1_mul_u64_idx(const u8* pts, const u8* flags, const u64* scalars, const u32* idx, u8* out, u8* out_inf, size_t n) {
+    const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+    const size_t i = idx[t < n ? t : n - 1];
+    G1Aff p = load_aff<FpS>(pts + (size_t)96 * i);
+    if (flags && (flags[i] & 1)) p.inf = -1;
+    const G1Aff a = jac_to_affine(mul_u64_jac<FpS>(p, scalars[i]));
+    if (t < n) { store_aff(out + (size_t)96 * t, a); out_inf[t] = a.inf ? 1 : 0; }
+}
 // 64-bit scalars as the 32-byte big-endian records the bucket MSM's digit passes read (msm.inc: msm_digit)
 KERNEL k_scalar_u64_to_be32(const u64* r, u8* out, size_t n) {
     const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;

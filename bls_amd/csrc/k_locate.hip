@@ -80,3 +80,26 @@ KERNEL2 k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n) {
     const size_t r = (size_t)blockIdx.x * WG + threadIdx.x;
     if (r < n) dst[idx[r]] = src[r];
 }
+
+// The weights and flags of a randomised pairing-product batch (blsmi 0.17: blsmi_pairing_product_batch_rlc*, rlc_host.hpp), a lane per pair:
+// w[k] = r[item_of[k]], the scalar of the pair's item, addressed like the point as the weighted segmented sum wants it, and pflag[k] in the
+// form blsmi_pairing_product_batch takes its flags -- bit 0: P_k is at infinity (the caller's flag or the all-zero record), bit 1: its table
+// entry tab[group_of[k]] is the all-zero record.  The sums read bit 0 (any set bit leaves the pair out: a pair of a dropped group adds
+// nothing either way), the per-item path gets the byte as it is.  tab: the call's compacted table (16-byte aligned); g1 may be a caller's
+// buffer, read in 16-byte pieces where its address allows (the same for the whole grid).  The host has built item_of and group_of.
+KERNEL2 k_pprod_rlc_weights(const u8* g1, const u8* in_flags, const uint4* tab, const u32* group_of, const u32* item_of, const u64* r, u64* w, u8* pflag, size_t np) {
+    const size_t k = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (k >= np) return;
+    u32 a = 0, b = 0;
+    if ((reinterpret_cast<uintptr_t>(g1) & 15) == 0) {
+        const uint4* p = reinterpret_cast<const uint4*>(g1) + 6 * k;
+        for (int i = 0; i < 6; i++) { const uint4 v = p[i]; a |= v.x | v.y | v.z | v.w; }
+    } else {
+        const u32* p = reinterpret_cast<const u32*>(g1) + 24 * k;
+        for (int i = 0; i < 24; i++) a |= p[i];
+    }
+    const uint4* q = tab + (size_t)12 * group_of[k];
+    for (int i = 0; i < 12; i++) { const uint4 v = q[i]; b |= v.x | v.y | v.z | v.w; }
+    pflag[k] = (u8)(((in_flags ? in_flags[k] : 0) & 1) | (a ? 0 : 1) | (b ? 0 : 2));
+    w[k] = r[item_of[k]];
+}

@@ -66,6 +66,7 @@ __global__ void k_locate_cell_fail(const u8* flags, const u8* flags2, const u32*
 __global__ void k_gather_records16(const uint4* src, const u32* idx, uint4* dst, u32 q, size_t n);
 __global__ void k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
+__global__ void k_pprod_rlc_weights(const u8* g1, const u8* in_flags, const uint4* tab, const u32* group_of, const u32* item_of, const u64* r, u64* w, u8* pflag, size_t np);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);
@@ -141,6 +142,7 @@ __global__ void k_mul_finish(const u8* good, const u8* pts, size_t pt_stride, in
 __global__ void k_g1_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g1_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
+__global__ void k_g1_mul_u64_idx(const u8* pts, const u8* flags, const u64* scalars, const u32* idx, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_scalar_u64_to_be32(const u64* r, u8* out, size_t n);
 __global__ void k_glv_recode(const u8* scalars, int group, u8* rec, size_t n);

@@ -1,5 +1,5 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
-// ..._rlc_locate and ..._rlc_grouped_locate.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc and blsmi_pairing_product_batch_rlc*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -936,3 +936,189 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev(con
 #undef ACRJ
 #undef ACRD
 #undef JACP
+
+// ---- pairing products, randomised (blsmi 0.17; include/blsmi.h "pairing products, randomised") -------------------------------------------
+// The m equations of blsmi_pairing_product_batch under ONE: pair k = (P_k, table[q_idx[k]]) of item j(k), random nonzero 64-bit r_j,
+//     every item holds  <=  FE( prod_g Miller( sum_{k in g} r_j(k) P_k, Q_g ) ) == 1        (g: the table entries some pair refers to)
+// by bilinearity -- one Miller loop per entry referred to and one final exponentiation instead of np and m.  Stages, on the call's stream:
+//   1  the plan (pprod_rlc_plan.h): groups of pairs per entry, split into shared groups and singletons, compacted shared first
+//   2  k_pprod_rlc_weights: w_k = r_j(k) and the 0.10 flag byte of every pair (P_k infinite / its entry the all-zero record)
+//   3  shared groups: the weighted segmented G1 sum (segsum_dev with scalars); singletons: k_g1_mul_u64_idx, one lane each
+//   4  k_pprod_skip over the d' (S_g, Q_g): a sum at infinity or an all-zero entry runs its loop on the generators and is left out -- the
+//      pair(s) contribute 1, as in 0.10, and the call does NOT leave the combined path for it (an item {(P, Q), (-P, Q)} is legitimate)
+//   5  d' Miller loops in the layout a Pairing call of d' tuples takes, seg_prod_dev over one segment, one final exponentiation, is_one
+//   6  the equation held: every verdict is 1.  Otherwise blsmi_pairing_product_batch's own path (pprod_dev) over all m items from what is
+//      on the device, every pair's entry gathered from the compacted table (k_gather_records).
+// One lease, one device, never in the request combiner; "rlc_min" is not consulted.
+namespace {
+struct PprodRlcIn {
+    const u8* g1;            // np affine records on the device
+    bool own_g1;             // the call's own copy (the per-item path overwrites the records of skipped pairs)
+    const u8* flags;         // np caller flags on the device, or null
+    u8* tab;                 // the compacted table: d' affine records in the plan's group order, the call's own
+    const uint64_t* r;       // host: m nonzero scalars
+    const uint64_t* seg_off; // host: the items' offsets
+    size_t np, m;
+};
+// d_is_one: m verdict bytes on the device.  Synchronises the call's stream.
+int pprod_rlc_core(const PprodRlcIn& in, const blsmi_route::PprodRlcPlan& pl, void* d_is_one, bool* held) {
+    const size_t np = in.np, m = in.m, dg = pl.groups(), dsh = pl.shared(), dsi = pl.single.size(), ns = pl.perm.size(), words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    SegPlan splan, oplan, iplan;
+    const uint64_t whole[2] = {0, dg};
+    try {
+        segsum_plan(pl.seg_off.data(), dsh, segsum_chunk_of(ns), splan, 64, 1);
+        pprod_plan(whole, 1, oplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf dr, dw, pflag, dgo, dio, dperm, dsingle, S, sinf, skip, f, blob, prod, vals, one;
+    HIPCHK(dr.alloc(sizeof(uint64_t) * m)); HIPCHK(dw.alloc(sizeof(uint64_t) * np)); HIPCHK(pflag.alloc(np)); HIPCHK(dgo.alloc(sizeof(uint32_t) * np)); HIPCHK(dio.alloc(sizeof(uint32_t) * np));
+    HIPCHK(dperm.alloc(sizeof(uint32_t) * ns)); HIPCHK(dsingle.alloc(sizeof(uint32_t) * dsi)); HIPCHK(S.alloc((size_t)96 * dg)); HIPCHK(sinf.alloc(dg)); HIPCHK(skip.alloc(dg));
+    HIPCHK(f.alloc(sizeof(i32) * words * dg)); HIPCHK(blob.alloc(oplan.blob.size())); HIPCHK(vals.alloc(576)); HIPCHK(one.alloc(1));
+    HIPCHK(hipMemcpyAsync(dr.p, in.r, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dio.p, pl.item_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dgo.p, pl.group_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    if (ns) HIPCHK(hipMemcpyAsync(dperm.p, pl.perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, s));
+    if (dsi) HIPCHK(hipMemcpyAsync(dsingle.p, pl.single.data(), sizeof(uint32_t) * dsi, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(blob.p, oplan.blob.data(), oplan.blob.size(), hipMemcpyHostToDevice, s));
+    launch(KERNEL_OF(k_pprod_rlc_weights), nblocks(np), s, in.g1, in.flags, in.tab, dgo.p, dio.p, dr.p, dw.p, pflag.p, np);
+    prof_mark(nullptr);
+    // S_g = sum_{k in g} w_k P_k: the shared groups' into S[0, dsh), the singletons' behind them
+    int rc = segsum_dev(group_kernels(1), false, in.g1, pflag.as<u8>(), np, dperm.as<u32>(), splan, S.as<u8>(), sinf.as<u8>(), 1, s, dw.as<u64>());
+    if (rc) return rc;
+    if (dsi) {
+        launch(KERNEL_OF(k_g1_mul_u64_idx), nblocks(dsi), s, in.g1, pflag.p, dw.p, dsingle.p, S.as<u8>() + (size_t)96 * dsh, sinf.as<u8>() + dsh, dsi);
+        prof_mark(nullptr);
+    }
+    launch_quiet(KERNEL_OF(k_pprod_skip), nblocks(dg), s, S.p, in.tab, sinf.p, g_gens.g1, g_gens.g2, skip.p, dg);
+    launch_miller_tuples(S.as<u8>(), in.tab, f.as<i32>(), dg, s, pairing_layout(0, dg, tune(), route_load(dg)));
+    const Layout fe = pprod_fe_layout(1, route_load(dg));
+    HIPCHK(prod.alloc(fe == Layout::wave ? 576 : sizeof(i32) * words));
+    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of seg_prod_dev
+    rc = seg_prod_dev(f.as<i32>(), dg, skip.as<u8>(), oplan, blob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
+    if (rc) return rc;
+    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, 1, s);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    uint8_t verdict = 0;
+    HIPCHK(hipMemcpyAsync(&verdict, one.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *held = verdict == 1;
+    if (*held) {
+        HIPCHK(hipMemsetAsync(d_is_one, 1, m, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return BLSMI_OK;
+    }
+    // the per-item path of 0.10 over all m items: every pair's table entry from the compacted table (an all-zero entry's record now holds
+    // the generator: bit 1 of the pair's flag byte, written before, leaves the pair out all the same)
+    try { pprod_plan(in.seg_off, m, iplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf a, b;
+    HIPCHK(b.alloc((size_t)192 * np));
+    u8* g1 = const_cast<u8*>(in.g1);
+    if (!in.own_g1) { HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(hipMemcpyAsync(a.p, in.g1, (size_t)96 * np, hipMemcpyDeviceToDevice, s)); g1 = a.as<u8>(); }
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * np), s, in.tab, dgo.p, b.p, 48, np);
+    return pprod_dev(g1, b.as<u8>(), pflag.as<u8>(), np, iplan, nullptr, d_is_one, s);
+}
+int pprod_rlc_host(const uint8_t* g1, const uint8_t* inf_flags, const uint8_t* tab, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m,
+                   const uint64_t* scalars, uint8_t* is_one, int* combined, bool jac) {
+    if (combined) *combined = 0;
+    if (m == 0) return BLSMI_OK;
+    int rc = rlc_check_args(is_one && seg_off && (np == 0 || (g1 && tab)), scalars, m);
+    if (rc) return rc;
+    blsmi_route::PprodRlcPlan pl;
+    std::vector<uint8_t> packed;
+    const size_t qb = rec_bytes(192, jac);
+    try {
+        if (!blsmi_route::pprod_rlc_plan(seg_off, m, q_idx, np, nq, pl)) return BLSMI_E_ARG;
+        if (q_idx) {                                                       // only the entries some pair refers to travel, already in group order
+            packed.resize(qb * pl.groups());
+            for (size_t c = 0; c < pl.groups(); c++) memcpy(packed.data() + qb * c, tab + qb * pl.entry_of[c], qb);
+        }
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    if (np == 0) { memset(is_one, 1, m); if (combined) *combined = 1; return BLSMI_OK; }
+    RlcHostScratch hs;
+    uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    DBuf a, t, fl, dok;
+    HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(t.alloc((size_t)192 * pl.groups())); HIPCHK(fl.alloc(np)); HIPCHK(dok.alloc(m));
+    rc = upload_points(group_kernels(1), jac, g1, a.p, np, s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, q_idx ? packed.data() : tab, t.p, pl.groups(), s); if (rc) return rc;
+    if (inf_flags && !jac) HIPCHK(hipMemcpyAsync(fl.p, inf_flags, np, hipMemcpyHostToDevice, s));
+    bool held = false;
+    const PprodRlcIn in{a.as<u8>(), true, (inf_flags && !jac) ? fl.as<u8>() : nullptr, t.as<u8>(), scalars, seg_off, np, m};
+    rc = pprod_rlc_core(in, pl, dok.p, &held); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(is_one, dok.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (combined) *combined = held ? 1 : 0;
+    return BLSMI_OK;
+}
+// the _dev forms: seg_off and q_idx come back once for the plans; the table entries referred to are gathered; the caller's buffers stay untouched.
+// split == false: every group through the segmented sum (blsmi_debug_pairing_product_batch_rlc_dev_nosplit).
+int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m,
+                      const uint64_t* scalars, void* d_is_one, int* combined, void* stream, bool jac, bool split = true) {
+    if (combined) *combined = 0;
+    if (m == 0) return BLSMI_OK;
+    int rc = rlc_check_args(d_is_one && d_seg_off && (np == 0 || (d_g1 && d_tab)) && (d_q_idx || nq == np) && np <= 0xffffffffull, scalars, m);
+    if (rc) return rc;
+    RlcHostScratch hs;
+    uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_is_one);
+    UseStream us(stream);
+    hipStream_t s = g_stream;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> qi;
+    if (d_q_idx && np) {
+        try { qi.resize(np); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+        HIPCHK(hipMemcpyAsync(qi.data(), d_q_idx, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, s));
+    }
+    rc = segsum_fetch_offsets(d_seg_off, m, off); if (rc) return rc;       // (synchronises: q_idx is here as well)
+    blsmi_route::PprodRlcPlan pl;
+    try {
+        if (!blsmi_route::pprod_rlc_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, pl, split)) return BLSMI_E_ARG;
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    bool held = true;
+    if (np == 0) { HIPCHK(hipMemsetAsync(d_is_one, 1, m, s)); HIPCHK(hipStreamSynchronize(s)); }
+    else {
+        const size_t dg = pl.groups();
+        DBuf a, t, tj, dent;
+        HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
+        HIPCHK(hipMemcpyAsync(dent.p, pl.entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+        const u8* g1 = (const u8*)d_g1;
+        if (jac) {
+            HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(tj.alloc((size_t)288 * dg));
+            rc = jac_to_wire_dev(group_kernels(1), d_g1, a.p, nullptr, np, s); if (rc) return rc;
+            launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)72 * dg), s, d_tab, dent.p, tj.p, 72, dg);
+            rc = jac_to_wire_dev(group_kernels(2), tj.p, t.p, nullptr, dg, s); if (rc) return rc;
+            g1 = a.as<u8>();
+        } else launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, d_tab, dent.p, t.p, 48, dg);
+        const PprodRlcIn in{g1, jac, jac ? nullptr : (const u8*)d_inf_flags, t.as<u8>(), scalars, off.data(), np, m};
+        rc = pprod_rlc_core(in, pl, d_is_one, &held); if (rc) return rc;
+    }
+    if (combined) *combined = held ? 1 : 0;
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_pairing_product_batch_rlc(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np,
+                                              const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
+    return pprod_rlc_host(g1_aff, inf_flags, g2_tab, nq, q_idx, np, seg_off, m, scalars, is_one, combined, false);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np,
+                                                  const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
+    return pprod_rlc_host(reinterpret_cast<const uint8_t*>(g1_jac), nullptr, reinterpret_cast<const uint8_t*>(g2_tab_jac), nq, q_idx, np, seg_off, m, scalars, is_one, combined, true);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
+                                                  const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+    return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np,
+                                                      const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+    return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true);
+}
+// blsmi_pairing_product_batch_rlc_dev with the singleton groups sent through the weighted segmented sum as well: the other side of the
+// by-pass's criterion, kept so that tools/pprod_rlc_bench.py can measure it again
+BLSMI_API int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
+                                                                const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+    return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, false);
+}

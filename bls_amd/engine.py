@@ -1691,3 +1691,85 @@ def verify_aggregate_common_batch_rlc_dev(group, d_msgs, d_off_or_domain, d, d_m
 def debug_g2_sum_segmented_u64_pair(pts, npk, scalars, idx, seg_off, in_inf=None):
     """g2_sum_segmented_u64 with pass 1 through the lane-pair ladder (k_g2_segsum_chunk_u64_pair), for the parity test"""
     return _sum_segmented_u64("blsmi_debug_g2_sum_segmented_u64_pair", 192, pts, npk, scalars, idx, seg_off, in_inf, _fn_0_16)
+
+
+# ---- pairing products, randomised (blsmi 0.17): one equation for a batch of pairing products over a table of G2 points -------------
+_P_TAIL = [C.c_size_t, _u64p, C.c_size_t, _u64p, _u8p, C.POINTER(C.c_int)]    # np, seg_off, m, scalars, is_one, combined
+_P_DEV_TAIL = [C.c_size_t, _V, C.c_size_t, _u64p, _V, C.POINTER(C.c_int), _V]  # np, d_seg_off, m, scalars, d_is_one, combined, stream
+# the argument types of the five entry points of 0.17, as include/blsmi.h declares them (tests/test_pprod_rlc_cpu.py compares)
+ARGTYPES_0_17 = {
+    "blsmi_pairing_product_batch_rlc": [_u8p, _u8p, _u8p, C.c_size_t, _u32p] + _P_TAIL,
+    "blsmi_pairing_product_batch_rlc_jac": [_u64p, _u64p, C.c_size_t, _u32p] + _P_TAIL,
+    "blsmi_pairing_product_batch_rlc_dev": [_V, _V, _V, C.c_size_t, _V] + _P_DEV_TAIL,
+    "blsmi_pairing_product_batch_rlc_jac_dev": [_V, _V, C.c_size_t, _V] + _P_DEV_TAIL,
+    "blsmi_debug_pairing_product_batch_rlc_dev_nosplit": [_V, _V, _V, C.c_size_t, _V] + _P_DEV_TAIL,
+}
+
+
+def _fn_0_17(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_17[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars):
+    pb, qb = (144, 288) if jac else (96, 192)
+    a, t = _u8(g1), _u8(g2_tab)
+    if a.size % pb or t.size % qb:
+        raise ValueError("expected np*%d and nq*%d bytes, got %d and %d" % (pb, qb, a.size, t.size))
+    n, nq = a.size // pb, t.size // qb
+    so, m = _pprod_offsets(seg_off, n)
+    if q_idx is None:
+        if nq != n:
+            raise ValueError("without q_idx the table has one entry per pair: %d entries, %d pairs" % (nq, n))
+        ix, pix = None, None
+    else:
+        ix, pix = _msg_idx(q_idx, n)
+        if n == 0:                                                         # (a table without pairs: the pointer still says "indexed")
+            ix = np.zeros(1, dtype=np.uint32)
+            pix = ix.ctypes.data_as(_u32p)
+    r, pr = _scalars(scalars, m)
+    one = np.zeros(max(1, m), dtype=np.uint8)
+    comb = C.c_int(0)
+    if jac:
+        (a, pa), (t, pt) = _j64(a, pb * n), _j64(t, qb * nq)
+        rc = _fn_0_17(name)(pa, pt, nq, pix, n, so.ctypes.data_as(_u64p), m, pr, _p8(one), C.byref(comb))
+    else:
+        f = _u8(inf_flags, n) if inf_flags is not None else None
+        rc = _fn_0_17(name)(_p8(a), _p8(f), _p8(t), nq, pix, n, so.ctypes.data_as(_u64p), m, pr, _p8(one), C.byref(comb))
+    _check(rc, name[len("blsmi_"):])
+    return one[:m].copy(), comb.value
+
+
+def pairing_product_batch_rlc(g1_aff, g2_tab, q_idx, seg_off, inf_flags=None, scalars=None):
+    """blsmi_pairing_product_batch_rlc -> (is_one (m,) uint8, combined): pair k is (P_k, g2_tab[q_idx[k]]) (q_idx None: entry k), item j the
+    pairs seg_off[j] <= k < seg_off[j + 1]; the verdicts of pairing_product_batch on the expanded table, from one randomised equation
+    (combined == 1) or, when it fails, from the per-item path (combined == 0).  inf_flags[k] bit 0: P_k is the point at infinity.
+    scalars: m nonzero 64-bit integers, or None (the library draws them)."""
+    return _pprod_rlc("blsmi_pairing_product_batch_rlc", False, g1_aff, g2_tab, q_idx, seg_off, inf_flags, scalars)
+
+
+def pairing_product_batch_rlc_jac(g1_jac, g2_tab_jac, q_idx, seg_off, scalars=None):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _pprod_rlc("blsmi_pairing_product_batch_rlc_jac", True, g1_jac, g2_tab_jac, q_idx, seg_off, None, scalars)
+
+
+def pairing_product_batch_rlc_dev(d_g1, d_g2_tab, nq, d_q_idx, np_, d_seg_off, m, d_is_one, d_inf_flags=0, scalars=None, stream=0, nosplit=False):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_is_one when the call returns; scalars stay on the host.
+    nosplit: blsmi_debug_pairing_product_batch_rlc_dev_nosplit (the measurement of the singleton by-pass).  -> combined"""
+    name = "blsmi_debug_pairing_product_batch_rlc_dev_nosplit" if nosplit else "blsmi_pairing_product_batch_rlc_dev"
+    r, pr = _scalars(scalars, m)
+    comb = C.c_int(0)
+    _check(_fn_0_17(name)(d_g1 or 0, d_inf_flags or 0, d_g2_tab or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, d_is_one or 0, C.byref(comb), stream or 0),
+           name[len("blsmi_"):])
+    return comb.value
+
+
+def pairing_product_batch_rlc_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars=None, stream=0):
+    """device-pointer form over in-memory points (no flags: z == 0 is infinity) -> combined"""
+    name = "blsmi_pairing_product_batch_rlc_jac_dev"
+    r, pr = _scalars(scalars, m)
+    comb = C.c_int(0)
+    _check(_fn_0_17(name)(d_g1_jac or 0, d_g2_tab_jac or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, d_is_one or 0, C.byref(comb), stream or 0), name[len("blsmi_"):])
+    return comb.value

@@ -85,8 +85,10 @@ void blsmi_shutdown(void);
  * form, no inversion, no square root) and the BLSMI_POINT_* status names; no existing prototype changes, no new option.  0.15 adds the conversions between the compressed wire format and the in-memory points
  * (blsmi_g?_decompress_batch_jac[_dev], blsmi_g?_compress_batch_jac[_dev]); no existing prototype changes, no new option.  0.16 adds the randomised
  * verification of many committee aggregates in one call (blsmi_g?pubs_verify_aggregate_common*_batch_rlc[_jac|_dev]) and
- * blsmi_debug_g2_sum_segmented_u64_pair; no existing prototype changes, no new option.  The string below still begins
- * "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15 and 0.16 by the presence of
+ * blsmi_debug_g2_sum_segmented_u64_pair; no existing prototype changes, no new option.  0.17 adds the randomised pairing-product batches
+ * (blsmi_pairing_product_batch_rlc[_jac|_dev|_jac_dev]: one equation for a batch of pairing products, the pairs of one G2 table entry sharing
+ * one Miller loop) and blsmi_debug_pairing_product_batch_rlc_dev_nosplit; no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16 and 0.17 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -901,6 +903,60 @@ int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev(const void *d
 int blsmi_debug_g2_sum_segmented_u64_pair(const uint8_t *pts /* npk*192 */, const uint8_t *in_inf /* npk, may be NULL */, size_t npk, const uint64_t *scalars /* npk */,
                                           const uint32_t *idx /* seg_off[m], may be NULL */, const uint64_t *seg_off /* m+1 */, size_t m,
                                           uint8_t *out /* m*192 */, uint8_t *out_inf /* m */);
+
+/* ---- pairing products, randomised (blsmi 0.17) -----------------------------------------------------------------------------------------
+ * The m equations "item j is one" of blsmi_pairing_product_batch (Groth16 proofs, KZG openings, two-sided checks) under ONE randomised
+ * equation, for batches whose G2 points are mostly fixed.  Pair k is (P_k, g2_tab[q_idx[k]]): the G2 points come from a table of nq entries
+ * (q_idx NULL: pair k uses entry k, and nq must equal np); item j is the pairs seg_off[j] <= k < seg_off[j + 1], as in 0.10.  With random
+ * nonzero 64-bit r_j per item, item(k) the item of pair k and FE the final exponentiation,
+ *     every item j holds  <=  FE( prod_g Miller( sum_{k: q_idx[k] = g} r_item(k) * P_k , Q_g ) ) == FQ12One
+ * by bilinearity: ONE Miller loop per table entry some pair refers to, ONE final exponentiation and a 64-bit G1 ladder per pair, where the
+ * 0.10 call runs np Miller loops and m final exponentiations.
+ * Verdicts: is_one[j] is exactly what blsmi_pairing_product_batch gives item j with Q_k = g2_tab[q_idx[k]].  There is no out_fq12: the
+ * combined path never has per-item values.  *combined (may be NULL) = 1 exactly when every verdict came from the one equation that held;
+ * otherwise the equation failed and the 0.10 path ran over all m items from what is on the device (the table entries gathered per pair;
+ * the check is not narrowed to blocks here).
+ * Infinity follows 0.10: the pair contributes 1.  An infinite P_k (inf_flags[k] bit 0, the all-zero record, z == 0 in the _jac forms) adds
+ * nothing to its entry's sum; an infinite table entry (the all-zero record, z == 0) drops its group; a group whose weighted sum is the
+ * point at infinity contributes 1 and does NOT send the call to the per-item path -- unlike the signature forms, where a sum at infinity
+ * is suspicious: an item {(P, Q), (-P, Q)} is a legitimate equation.
+ * Scalars: m nonzero 64-bit words, or NULL to have them drawn from the OS for this call (as 0.8 and 0.16); a zero caller scalar is
+ * BLSMI_E_ARG; caller scalars are the caller's responsibility (two failing items whose values cancel under equal scalars pass unnoticed).
+ * Soundness: with an item that does not hold among them the equation holds with probability at most 2^-64 over the drawn scalars, for P_k
+ * in G1 and table entries in G2, both the prime-order subgroups (blsmi_g?_check_batch establishes that; a point outside them voids it).
+ *   - the host forms return BLSMI_E_ARG before any device work for: offsets that do not start at 0, that decrease or that do not end at
+ *     np; q_idx[k] >= nq; q_idx == NULL with nq != np; a zero scalar; a NULL input with np > 0; NULL is_one.
+ *   - m = 0: BLSMI_OK, combined = 0.  np = 0 with m > 0: every item is one, combined = 1.
+ *   - table entries with equal bytes are not merged; entries no pair refers to are never touched (the host forms do not upload them, the
+ *     _dev forms do not read them).
+ *   - _jac: points as the Go values hold them (g1_jac np*18 u64, g2_tab_jac nq*36 u64), no flags: z == 0 is infinity.
+ *   - _dev: every buffer on one of the library's devices (d_q_idx: np u32 or NULL, d_seg_off: (m + 1) u64, d_is_one: m bytes); scalars and
+ *     combined stay on the host; `stream` as in blsmi_pairing_batch_dev.  seg_off and q_idx are read back once for the plans (the same
+ *     errors, BLSMI_E_ARG, nothing written); the caller's buffers stay untouched.
+ * "rlc_min" does NOT apply: calling this form is the caller's choice of the combined path.  The call takes one lease and runs on one
+ * device; it is not split and never joins the request combiner.
+ * When to call it (one MI355X, points resident, against blsmi_pairing_product_batch_dev on the same pairs, median of 20; DESIGN.md 3r has
+ * the table and the stages).  All items valid, m x k pairs: 16 384 x 4 with three shared entries 10.2 against 12.6 ms, 65 536 x 4 the same
+ * way 24.3 against 42.1 ms, 16 384 x 2 with both entries shared 4.3 against 8.7 ms.  Do NOT call it with nothing shared (16 384 x 4 under
+ * q_idx == NULL: 11.8 against 12.1 ms, a tie within the spread), at a few thousand items or fewer (2 048 x 4: 5.4 against 3.3 ms -- the
+ * ladders and the one-value final exponentiation are a floor of about 4 ms), or where failing items are common: one bad item costs this
+ * call plus the whole 0.10 call (16 384 x 4: 22.7 against 12.1 ms). */
+int blsmi_pairing_product_batch_rlc(const uint8_t *g1_aff /* np*96 */, const uint8_t *inf_flags /* np, may be NULL: bit0 = P_k infinity */,
+                                    const uint8_t *g2_tab /* nq*192 */, size_t nq, const uint32_t *q_idx /* np, or NULL: pair k uses entry k and nq == np */,
+                                    size_t np, const uint64_t *seg_off /* m+1 */, size_t m,
+                                    const uint64_t *scalars /* m, may be NULL */, uint8_t *is_one /* m */, int *combined /* may be NULL */);
+int blsmi_pairing_product_batch_rlc_jac(const uint64_t *g1_jac /* np*18 */, const uint64_t *g2_tab_jac /* nq*36 */, size_t nq, const uint32_t *q_idx,
+                                        size_t np, const uint64_t *seg_off, size_t m, const uint64_t *scalars, uint8_t *is_one, int *combined);
+int blsmi_pairing_product_batch_rlc_dev(const void *d_g1_aff, const void *d_inf_flags, const void *d_g2_tab, size_t nq, const void *d_q_idx,
+                                        size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars /* host: m, may be NULL */,
+                                        void *d_is_one, int *combined /* host */, void *stream);
+int blsmi_pairing_product_batch_rlc_jac_dev(const void *d_g1_jac, const void *d_g2_tab_jac, size_t nq, const void *d_q_idx,
+                                            size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars, void *d_is_one, int *combined, void *stream);
+/* For the measurement of DESIGN.md 3r: blsmi_pairing_product_batch_rlc_dev (arguments, checks and verdicts) with the single-pair groups
+ * sent through the weighted segmented sum like the shared ones, instead of one lane each. */
+int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void *d_g1_aff, const void *d_inf_flags, const void *d_g2_tab, size_t nq, const void *d_q_idx,
+                                                      size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars, void *d_is_one, int *combined,
+                                                      void *stream);
 
 #ifdef __cplusplus
 }
