@@ -11,6 +11,7 @@
 #include "locate_plan.h"
 #include "cell_plan.h"
 #include "pprod_rlc_plan.h"
+#include "pprod_locate_plan.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

@@ -3,6 +3,7 @@
 // pairs of the block checks, the verdict byte of every block / cell, and the gathers / the scatter that move the tuples of the failing
 // ones into dense buffers for the per-tuple stage and their verdicts back.  The product of a block's Miller values with its signature
 // side's is k_fq12_mul_pairs_row (k_fq12_seg.hip).
+// Also here: the weights of the randomised pairing-product batches (blsmi 0.17) and the route of their block-locating form (blsmi 0.18).
 #include "tower.cuh"
 #include "device_io.cuh"
 
@@ -102,4 +103,33 @@ KERNEL2 k_pprod_rlc_weights(const u8* g1, const u8* in_flags, const uint4* tab, 
     for (int i = 0; i < 12; i++) { const uint4 v = q[i]; b |= v.x | v.y | v.z | v.w; }
     pflag[k] = (u8)(((in_flags ? in_flags[k] : 0) & 1) | (a ? 0 : 1) | (b ? 0 : 2));
     w[k] = r[item_of[k]];
+}
+
+// The cells of a block-locating pairing-product batch into block order (blsmi 0.18: blsmi_pairing_product_batch_rlc_locate*, rlc_host.hpp;
+// pprod_locate_plan.h has the slots), in one launch between the sums and the Miller loops: slot s gets the 96-byte sum of cell sum_of[s]
+// and the 192-byte record of compacted table entry entry_at[s] in dense arrays, and the skip rule of k_pprod_skip is applied on the way --
+// a sum at infinity (its flag byte, or the all-zero record: bit 0) or an all-zero entry (bit 1) leaves skip[s] != 0 and the generators in
+// the slot, so that the Miller kernels run on valid points and the block's product leaves the value out.  Sixteen lanes per slot, 16-byte
+// pieces: lanes 0..5 carry the sum, lanes 0..11 the entry, so the lanes of one record are neighbours and read it whole; the two ORs stay
+// inside the sixteen.  The host has built the indices (every sum_of[s] < nc, every entry_at[s] < ne; one beyond would be skipped, nothing
+// read); sums, tab, gen1, gen2, g1, g2 are 16-byte aligned.  No lane writes beyond slot nc - 1.
+KERNEL2 k_pprod_cell_route(const uint4* sums, const u8* s_inf, const uint4* tab, const u32* sum_of, const u32* entry_at, const uint4* gen1, const uint4* gen2,
+                           uint4* g1, uint4* g2, u8* skip, size_t nc, size_t ne) {
+    const u32 l = threadIdx.x & 15;
+    const size_t s = (size_t)blockIdx.x * (WG / 16) + (threadIdx.x >> 4);
+    const size_t ss = s < nc ? s : nc - 1;
+    const u32 c = sum_of[ss], e = entry_at[ss];
+    const bool in = c < nc && e < ne;
+    uint4 p = make_uint4(0, 0, 0, 0), q = make_uint4(0, 0, 0, 0);
+    if (in && l < 6) p = sums[(size_t)6 * c + l];
+    if (in && l < 12) q = tab[(size_t)12 * e + l];
+    u32 a = p.x | p.y | p.z | p.w, b = q.x | q.y | q.z | q.w;
+    a |= __shfl_xor(a, 1); a |= __shfl_xor(a, 2); a |= __shfl_xor(a, 4); a |= __shfl_xor(a, 8);
+    b |= __shfl_xor(b, 1); b |= __shfl_xor(b, 2); b |= __shfl_xor(b, 4); b |= __shfl_xor(b, 8);
+    const u8 f = (u8)(((!in || a == 0 || s_inf[c]) ? 1 : 0) | ((!in || b == 0) ? 2 : 0));
+    if (s >= nc) return;
+    if (f) { if (l < 6) p = gen1[l]; if (l < 12) q = gen2[l]; }
+    if (l < 6) g1[(size_t)6 * s + l] = p;
+    if (l < 12) g2[(size_t)12 * s + l] = q;
+    if (l == 0) skip[s] = f;
 }

@@ -67,6 +67,7 @@ __global__ void k_gather_records16(const uint4* src, const u32* idx, uint4* dst,
 __global__ void k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_pprod_rlc_weights(const u8* g1, const u8* in_flags, const uint4* tab, const u32* group_of, const u32* item_of, const u64* r, u64* w, u8* pflag, size_t np);
+__global__ void k_pprod_cell_route(const uint4* sums, const u8* s_inf, const uint4* tab, const u32* sum_of, const u32* entry_at, const uint4* gen1, const uint4* gen2, uint4* g1, uint4* g2, u8* skip, size_t nc, size_t ne);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);

@@ -1,5 +1,5 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
-// ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc and blsmi_pairing_product_batch_rlc*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -1018,20 +1018,142 @@ int pprod_rlc_core(const PprodRlcIn& in, const blsmi_route::PprodRlcPlan& pl, vo
     launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * np), s, in.tab, dgo.p, b.p, 48, np);
     return pprod_dev(g1, b.as<u8>(), pflag.as<u8>(), np, iplan, nullptr, d_is_one, s);
 }
+// ---- pairing products, randomised, that find the bad items by blocks (blsmi 0.18; include/blsmi.h under the same title) --------------------
+// The equation above with the m items cut into B contiguous blocks (pprod_locate_plan.h) and the sums taken per CELL -- (block, table entry)
+// with a pair of the block referring to the entry -- so that every block has a product of its own,
+//     V_b = prod_{c in b} Miller( sum_{k in c} r_j(k) P_k, Q_g(c) ),        total = prod_b V_b,
+// all of it there by the time the total is known: a failing call runs no second ladder, no second Miller loop.  Stages, on the call's stream:
+//   1  k_pprod_rlc_weights, as above
+//   2  multi-pair cells: the weighted segmented sum (idx = the plan's permutation, the cells as segments); one-pair cells: k_g1_mul_u64_idx
+//   3  k_pprod_cell_route: every cell's sum and its entry's record into dense arrays in block order, the skip rule on the way (one launch
+//      where two record gathers, a byte gather and k_pprod_skip would run)
+//   4  C Miller loops in the layout a Pairing call of C tuples takes: one value per cell in every layout
+//   5  seg_prod_dev over the blocks' slot borders: B block values, KEPT -- as a hand-off buffer, which the total's product reads, and as
+//      in-memory records where their final exponentiation (that of a pairing product of B items) runs in the wave layout; the total is a
+//      second, one-segment seg_prod_dev over the B values; one final exponentiation, is_one
+//   6  the total held: every verdict is 1
+//   7  it failed: B final exponentiations, B bytes to the host; the failing blocks' G1 records, flag bytes and per-pair table records
+//      gathered dense (the entry indices composed on the host), pprod_dev over them, the verdicts scattered over a verdict array preset to
+//      1.  The dense copies are the call's own: nothing of the caller's is written, no full copy of the G1 records is made.
+// One lease, one device, never in the request combiner; "rlc_min" is not consulted.  d_is_one: m verdict bytes on the device.  Synchronises.
+int pprod_locate_core(const PprodRlcIn& in, const blsmi_route::PprodLocatePlan& pl, void* d_is_one, bool* held, size_t* rechecked) {
+    const size_t np = in.np, m = in.m, C = pl.cells(), Cm = pl.multi(), Cs = pl.single.size(), ns = pl.perm.size(), B = pl.blocks(), dg = pl.entry_of.size();
+    const size_t words = (size_t)12 * NL;
+    hipStream_t s = g_stream;
+    *rechecked = 0;
+    SegPlan splan, bplan, oplan;
+    const uint64_t whole[2] = {0, B};
+    try {
+        segsum_plan(pl.cell_off.data(), Cm, segsum_chunk_of(ns), splan, 64, 1);
+        pprod_plan(pl.slot_off.data(), B, bplan);
+        pprod_plan(whole, 1, oplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const Layout feb = pprod_fe_layout(B, route_load(B)), fe = pprod_fe_layout(1, route_load(C));
+    DBuf dr, dw, pflag, dgo, dio, dperm, dsingle, dsum, dent, S, sinf, g1c, g2c, skip, f, bblob, oblob, bval, bmem, prod, vals, one;
+    HIPCHK(dr.alloc(sizeof(uint64_t) * m)); HIPCHK(dw.alloc(sizeof(uint64_t) * np)); HIPCHK(pflag.alloc(np)); HIPCHK(dgo.alloc(sizeof(uint32_t) * np)); HIPCHK(dio.alloc(sizeof(uint32_t) * np));
+    HIPCHK(dperm.alloc(sizeof(uint32_t) * ns)); HIPCHK(dsingle.alloc(sizeof(uint32_t) * Cs)); HIPCHK(dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(dent.alloc(sizeof(uint32_t) * C));
+    HIPCHK(S.alloc((size_t)96 * C)); HIPCHK(sinf.alloc(C)); HIPCHK(g1c.alloc((size_t)96 * C)); HIPCHK(g2c.alloc((size_t)192 * C)); HIPCHK(skip.alloc(C));
+    HIPCHK(f.alloc(sizeof(i32) * words * C)); HIPCHK(bblob.alloc(bplan.blob.size())); HIPCHK(oblob.alloc(oplan.blob.size()));
+    HIPCHK(bval.alloc(sizeof(i32) * words * B)); HIPCHK(bmem.alloc(feb == Layout::wave ? 576 * B : 1));
+    HIPCHK(prod.alloc(fe == Layout::wave ? 576 : sizeof(i32) * words)); HIPCHK(vals.alloc(576)); HIPCHK(one.alloc(1));
+    HIPCHK(hipMemcpyAsync(dr.p, in.r, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dio.p, pl.item_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dgo.p, pl.group_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    if (ns) HIPCHK(hipMemcpyAsync(dperm.p, pl.perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, s));
+    if (Cs) HIPCHK(hipMemcpyAsync(dsingle.p, pl.single.data(), sizeof(uint32_t) * Cs, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(oblob.p, oplan.blob.data(), oplan.blob.size(), hipMemcpyHostToDevice, s));
+    launch(KERNEL_OF(k_pprod_rlc_weights), nblocks(np), s, in.g1, in.flags, in.tab, dgo.p, dio.p, dr.p, dw.p, pflag.p, np);
+    prof_mark(nullptr);
+    // S_c = sum_{k in c} w_k P_k: the multi-pair cells' into S[0, Cm), the one-pair cells' behind them
+    int rc = segsum_dev(group_kernels(1), false, in.g1, pflag.as<u8>(), np, dperm.as<u32>(), splan, S.as<u8>(), sinf.as<u8>(), 1, s, dw.as<u64>());
+    if (rc) return rc;
+    if (Cs) {
+        launch(KERNEL_OF(k_g1_mul_u64_idx), nblocks(Cs), s, in.g1, pflag.p, dw.p, dsingle.p, S.as<u8>() + (size_t)96 * Cm, sinf.as<u8>() + Cm, Cs);
+        prof_mark(nullptr);
+    }
+    launch(KERNEL_OF(k_pprod_cell_route), tuple_blocks(Layout::row, C), s, S.p, sinf.p, in.tab, dsum.p, dent.p, g_gens.g1, g_gens.g2, g1c.p, g2c.p, skip.p, C, dg);
+    launch_miller_tuples(g1c.as<u8>(), g2c.as<u8>(), f.as<i32>(), C, s, pairing_layout(0, C, tune(), route_load(C)));
+    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of both seg_prod_dev
+    rc = seg_prod_dev(f.as<i32>(), C, skip.as<u8>(), bplan, bblob.as<u8>(), bval.as<i32>(), feb == Layout::wave ? bmem.as<u64>() : (u64*)nullptr, s);
+    if (rc) return rc;
+    rc = seg_prod_dev(bval.as<i32>(), B, nullptr, oplan, oblob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
+    if (rc) return rc;
+    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, 1, s);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    uint8_t verdict = 0;
+    HIPCHK(hipMemcpyAsync(&verdict, one.p, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *held = verdict == 1;
+    HIPCHK(hipMemsetAsync(d_is_one, 1, m, s));
+    if (*held) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }
+    // which blocks fail: their kept values through the final exponentiation a pairing product of B items takes
+    std::vector<uint8_t> fail;
+    blsmi_route::PprodLocateFailing ff;
+    try { fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf bvals, bone;
+    HIPCHK(bvals.alloc(576 * B)); HIPCHK(bone.alloc(B));
+    final_exp_values(feb, feb == Layout::wave ? bmem.p : bval.p, bvals.as<u64>(), bone.p, B, s);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fail.data(), bone.p, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    SegPlan iplan;
+    try {
+        for (uint8_t& b : fail) b = b == 1 ? 0 : 1;
+        blsmi_route::pprod_locate_failing(pl, in.seg_off, fail.data(), ff);
+        pprod_plan(ff.dense_off.data(), ff.items.size(), iplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t nre = ff.items.size(), npd = ff.pairs.size();
+    if (nre == 0) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }    // (cannot be: the total is the product of the block values)
+    // the failing blocks' items, dense, through blsmi_pairing_product_batch's own path; their verdicts back over the ones
+    DBuf ditems, dpairs, dents, a, b, fl, okd;
+    HIPCHK(ditems.alloc(sizeof(uint32_t) * nre)); HIPCHK(dpairs.alloc(sizeof(uint32_t) * npd)); HIPCHK(dents.alloc(sizeof(uint32_t) * npd));
+    HIPCHK(a.alloc((size_t)96 * npd)); HIPCHK(b.alloc((size_t)192 * npd)); HIPCHK(fl.alloc(npd)); HIPCHK(okd.alloc(nre));
+    HIPCHK(hipMemcpyAsync(ditems.p, ff.items.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    if (npd) {
+        HIPCHK(hipMemcpyAsync(dpairs.p, ff.pairs.data(), sizeof(uint32_t) * npd, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dents.p, ff.entries.data(), sizeof(uint32_t) * npd, hipMemcpyHostToDevice, s));
+        prof_mark(KERNEL_OF(k_gather_records16).name);                     // one segment: the gathers
+        if (reinterpret_cast<uintptr_t>(in.g1) & 15) launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)24 * npd), s, in.g1, dpairs.p, a.p, 24, npd);   // (a caller's buffer)
+        else launch_quiet(KERNEL_OF(k_gather_records16), nblocks((size_t)6 * npd), s, in.g1, dpairs.p, a.p, 6, npd);
+        launch_quiet(KERNEL_OF(k_gather_records16), nblocks((size_t)12 * npd), s, in.tab, dents.p, b.p, 12, npd);
+        launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(npd), s, pflag.p, dpairs.p, fl.p, npd);
+        prof_mark(nullptr);
+    }
+    rc = pprod_dev(a.as<u8>(), b.as<u8>(), fl.as<u8>(), npd, iplan, nullptr, okd.p, s);
+    if (rc) return rc;
+    launch(KERNEL_OF(k_scatter_bytes), nblocks(nre), s, okd.p, ditems.p, d_is_one, nre);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    *rechecked = nre;
+    return BLSMI_OK;
+}
+// what makes a call of the two functions below the block-locating form of 0.18: the caller's `block` (0: automatic) and where the number of
+// rechecked items goes (may be null)
+struct PprodLocate { size_t block; size_t* rechecked; };
 int pprod_rlc_host(const uint8_t* g1, const uint8_t* inf_flags, const uint8_t* tab, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m,
-                   const uint64_t* scalars, uint8_t* is_one, int* combined, bool jac) {
+                   const uint64_t* scalars, uint8_t* is_one, int* combined, bool jac, const PprodLocate* loc = nullptr) {
     if (combined) *combined = 0;
+    if (loc && loc->rechecked) *loc->rechecked = 0;
     if (m == 0) return BLSMI_OK;
-    int rc = rlc_check_args(is_one && seg_off && (np == 0 || (g1 && tab)), scalars, m);
+    int rc = rlc_check_args(is_one && seg_off && (np == 0 || (g1 && tab)) && (!loc || m <= 0xffffffffull), scalars, m);   // (loc: the items of the failing blocks are 32-bit indices)
     if (rc) return rc;
     blsmi_route::PprodRlcPlan pl;
+    blsmi_route::PprodLocatePlan lp;
+    const std::vector<uint32_t>& entry_of = loc ? lp.entry_of : pl.entry_of;
     std::vector<uint8_t> packed;
     const size_t qb = rec_bytes(192, jac);
     try {
-        if (!blsmi_route::pprod_rlc_plan(seg_off, m, q_idx, np, nq, pl)) return BLSMI_E_ARG;
+        if (!(loc ? blsmi_route::pprod_locate_plan(seg_off, m, q_idx, np, nq, loc->block ? loc->block : blsmi_route::pprod_locate_auto_block(m), lp)
+                  : blsmi_route::pprod_rlc_plan(seg_off, m, q_idx, np, nq, pl))) return BLSMI_E_ARG;
         if (q_idx) {                                                       // only the entries some pair refers to travel, already in group order
-            packed.resize(qb * pl.groups());
-            for (size_t c = 0; c < pl.groups(); c++) memcpy(packed.data() + qb * c, tab + qb * pl.entry_of[c], qb);
+            packed.resize(qb * entry_of.size());
+            for (size_t c = 0; c < entry_of.size(); c++) memcpy(packed.data() + qb * c, tab + qb * entry_of[c], qb);
         }
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     if (np == 0) { memset(is_one, 1, m); if (combined) *combined = 1; return BLSMI_OK; }
@@ -1041,25 +1163,28 @@ int pprod_rlc_host(const uint8_t* g1, const uint8_t* inf_flags, const uint8_t* t
     LOCK_AND_INIT();
     hipStream_t s = g_stream;
     DBuf a, t, fl, dok;
-    HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(t.alloc((size_t)192 * pl.groups())); HIPCHK(fl.alloc(np)); HIPCHK(dok.alloc(m));
+    HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(t.alloc((size_t)192 * entry_of.size())); HIPCHK(fl.alloc(np)); HIPCHK(dok.alloc(m));
     rc = upload_points(group_kernels(1), jac, g1, a.p, np, s); if (rc) return rc;
-    rc = upload_points(group_kernels(2), jac, q_idx ? packed.data() : tab, t.p, pl.groups(), s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, q_idx ? packed.data() : tab, t.p, entry_of.size(), s); if (rc) return rc;
     if (inf_flags && !jac) HIPCHK(hipMemcpyAsync(fl.p, inf_flags, np, hipMemcpyHostToDevice, s));
     bool held = false;
     const PprodRlcIn in{a.as<u8>(), true, (inf_flags && !jac) ? fl.as<u8>() : nullptr, t.as<u8>(), scalars, seg_off, np, m};
-    rc = pprod_rlc_core(in, pl, dok.p, &held); if (rc) return rc;
+    size_t nre = 0;
+    rc = loc ? pprod_locate_core(in, lp, dok.p, &held, &nre) : pprod_rlc_core(in, pl, dok.p, &held); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(is_one, dok.p, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (combined) *combined = held ? 1 : 0;
+    if (loc && loc->rechecked) *loc->rechecked = nre;
     return BLSMI_OK;
 }
 // the _dev forms: seg_off and q_idx come back once for the plans; the table entries referred to are gathered; the caller's buffers stay untouched.
 // split == false: every group through the segmented sum (blsmi_debug_pairing_product_batch_rlc_dev_nosplit).
 int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m,
-                      const uint64_t* scalars, void* d_is_one, int* combined, void* stream, bool jac, bool split = true) {
+                      const uint64_t* scalars, void* d_is_one, int* combined, void* stream, bool jac, bool split = true, const PprodLocate* loc = nullptr) {
     if (combined) *combined = 0;
+    if (loc && loc->rechecked) *loc->rechecked = 0;
     if (m == 0) return BLSMI_OK;
-    int rc = rlc_check_args(d_is_one && d_seg_off && (np == 0 || (d_g1 && d_tab)) && (d_q_idx || nq == np) && np <= 0xffffffffull, scalars, m);
+    int rc = rlc_check_args(d_is_one && d_seg_off && (np == 0 || (d_g1 && d_tab)) && (d_q_idx || nq == np) && np <= 0xffffffffull && (!loc || m <= 0xffffffffull), scalars, m);
     if (rc) return rc;
     RlcHostScratch hs;
     uint8_t* none = nullptr;
@@ -1075,16 +1200,20 @@ int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_t
     }
     rc = segsum_fetch_offsets(d_seg_off, m, off); if (rc) return rc;       // (synchronises: q_idx is here as well)
     blsmi_route::PprodRlcPlan pl;
+    blsmi_route::PprodLocatePlan lp;
+    const std::vector<uint32_t>& entry_of = loc ? lp.entry_of : pl.entry_of;
     try {
-        if (!blsmi_route::pprod_rlc_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, pl, split)) return BLSMI_E_ARG;
+        if (!(loc ? blsmi_route::pprod_locate_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, loc->block ? loc->block : blsmi_route::pprod_locate_auto_block(m), lp)
+                  : blsmi_route::pprod_rlc_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, pl, split))) return BLSMI_E_ARG;
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     bool held = true;
+    size_t nre = 0;
     if (np == 0) { HIPCHK(hipMemsetAsync(d_is_one, 1, m, s)); HIPCHK(hipStreamSynchronize(s)); }
     else {
-        const size_t dg = pl.groups();
+        const size_t dg = entry_of.size();
         DBuf a, t, tj, dent;
         HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
-        HIPCHK(hipMemcpyAsync(dent.p, pl.entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dent.p, entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
         const u8* g1 = (const u8*)d_g1;
         if (jac) {
             HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(tj.alloc((size_t)288 * dg));
@@ -1094,9 +1223,10 @@ int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_t
             g1 = a.as<u8>();
         } else launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, d_tab, dent.p, t.p, 48, dg);
         const PprodRlcIn in{g1, jac, jac ? nullptr : (const u8*)d_inf_flags, t.as<u8>(), scalars, off.data(), np, m};
-        rc = pprod_rlc_core(in, pl, d_is_one, &held); if (rc) return rc;
+        rc = loc ? pprod_locate_core(in, lp, d_is_one, &held, &nre) : pprod_rlc_core(in, pl, d_is_one, &held); if (rc) return rc;
     }
     if (combined) *combined = held ? 1 : 0;
+    if (loc && loc->rechecked) *loc->rechecked = nre;
     return BLSMI_OK;
 }
 }  // namespace
@@ -1121,4 +1251,27 @@ BLSMI_API int blsmi_pairing_product_batch_rlc_jac_dev(const void* d_g1_jac, cons
 BLSMI_API int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
                                                                 const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
     return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, false);
+}
+// the block-locating forms (blsmi 0.18): pprod_locate_core in place of pprod_rlc_core
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np,
+                                                     const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
+    const PprodLocate loc{block, rechecked};
+    return pprod_rlc_host(g1_aff, inf_flags, g2_tab, nq, q_idx, np, seg_off, m, scalars, is_one, combined, false, &loc);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np,
+                                                         const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
+    const PprodLocate loc{block, rechecked};
+    return pprod_rlc_host(reinterpret_cast<const uint8_t*>(g1_jac), nullptr, reinterpret_cast<const uint8_t*>(g2_tab_jac), nq, q_idx, np, seg_off, m, scalars, is_one, combined, true, &loc);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
+                                                         const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked,
+                                                         void* stream) {
+    const PprodLocate loc{block, rechecked};
+    return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, true, &loc);
+}
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np,
+                                                             const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked,
+                                                             void* stream) {
+    const PprodLocate loc{block, rechecked};
+    return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true, true, &loc);
 }

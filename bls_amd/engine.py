@@ -1713,7 +1713,8 @@ def _fn_0_17(name):
     return fn
 
 
-def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars):
+def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars, block=None):
+    """block None: the forms of 0.17 -> (is_one, combined); an integer: the block-locating forms of 0.18 -> (is_one, combined, rechecked)"""
     pb, qb = (144, 288) if jac else (96, 192)
     a, t = _u8(g1), _u8(g2_tab)
     if a.size % pb or t.size % qb:
@@ -1731,15 +1732,17 @@ def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars):
             pix = ix.ctypes.data_as(_u32p)
     r, pr = _scalars(scalars, m)
     one = np.zeros(max(1, m), dtype=np.uint8)
-    comb = C.c_int(0)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    fn = _fn_0_17(name) if block is None else _fn_0_18(name)
+    tail = (pr, _p8(one), C.byref(comb)) if block is None else (pr, block, _p8(one), C.byref(comb), C.byref(nre))
     if jac:
         (a, pa), (t, pt) = _j64(a, pb * n), _j64(t, qb * nq)
-        rc = _fn_0_17(name)(pa, pt, nq, pix, n, so.ctypes.data_as(_u64p), m, pr, _p8(one), C.byref(comb))
+        rc = fn(pa, pt, nq, pix, n, so.ctypes.data_as(_u64p), m, *tail)
     else:
         f = _u8(inf_flags, n) if inf_flags is not None else None
-        rc = _fn_0_17(name)(_p8(a), _p8(f), _p8(t), nq, pix, n, so.ctypes.data_as(_u64p), m, pr, _p8(one), C.byref(comb))
+        rc = fn(_p8(a), _p8(f), _p8(t), nq, pix, n, so.ctypes.data_as(_u64p), m, *tail)
     _check(rc, name[len("blsmi_"):])
-    return one[:m].copy(), comb.value
+    return (one[:m].copy(), comb.value) if block is None else (one[:m].copy(), comb.value, nre.value)
 
 
 def pairing_product_batch_rlc(g1_aff, g2_tab, q_idx, seg_off, inf_flags=None, scalars=None):
@@ -1773,3 +1776,62 @@ def pairing_product_batch_rlc_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, 
     comb = C.c_int(0)
     _check(_fn_0_17(name)(d_g1_jac or 0, d_g2_tab_jac or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, d_is_one or 0, C.byref(comb), stream or 0), name[len("blsmi_"):])
     return comb.value
+
+
+# ---- pairing products, randomised, that find the bad items by blocks (blsmi 0.18) ---------------------------------------------------
+_PL_TAIL = [C.c_size_t, _u64p, C.c_size_t, _u64p, C.c_size_t, _u8p, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]        # np, seg_off, m, scalars, block, is_one, combined, rechecked
+_PL_DEV_TAIL = [C.c_size_t, _V, C.c_size_t, _u64p, C.c_size_t, _V, C.POINTER(C.c_int), C.POINTER(C.c_size_t), _V]    # ..., d_is_one, combined, rechecked, stream
+# the argument types of the four entry points of 0.18, as include/blsmi.h declares them (tests/test_pprod_rlc_locate_cpu.py compares)
+ARGTYPES_0_18 = {
+    "blsmi_pairing_product_batch_rlc_locate": [_u8p, _u8p, _u8p, C.c_size_t, _u32p] + _PL_TAIL,
+    "blsmi_pairing_product_batch_rlc_locate_jac": [_u64p, _u64p, C.c_size_t, _u32p] + _PL_TAIL,
+    "blsmi_pairing_product_batch_rlc_locate_dev": [_V, _V, _V, C.c_size_t, _V] + _PL_DEV_TAIL,
+    "blsmi_pairing_product_batch_rlc_locate_jac_dev": [_V, _V, C.c_size_t, _V] + _PL_DEV_TAIL,
+}
+
+
+def _fn_0_18(name):
+    fn = getattr(_lib(), name)
+    fn.argtypes = ARGTYPES_0_18[name]
+    fn.restype = C.c_int
+    return fn
+
+
+def _block(block):
+    block = int(block)
+    if block < 0:
+        raise ValueError("block is 0 (automatic) or a number of items, got %d" % block)
+    return block
+
+
+def pairing_product_batch_rlc_locate(g1_aff, g2_tab, q_idx, seg_off, inf_flags=None, scalars=None, block=0):
+    """blsmi_pairing_product_batch_rlc_locate -> (is_one (m,) uint8, combined, rechecked): pairing_product_batch_rlc with the items cut into
+    blocks of `block` (0: automatic); when the one equation fails, only the items of the blocks whose own product is not one -- `rechecked`
+    of them -- go through the per-item path, every other item's verdict is 1."""
+    return _pprod_rlc("blsmi_pairing_product_batch_rlc_locate", False, g1_aff, g2_tab, q_idx, seg_off, inf_flags, scalars, _block(block))
+
+
+def pairing_product_batch_rlc_locate_jac(g1_jac, g2_tab_jac, q_idx, seg_off, scalars=None, block=0):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _pprod_rlc("blsmi_pairing_product_batch_rlc_locate_jac", True, g1_jac, g2_tab_jac, q_idx, seg_off, None, scalars, _block(block))
+
+
+def pairing_product_batch_rlc_locate_dev(d_g1, d_g2_tab, nq, d_q_idx, np_, d_seg_off, m, d_is_one, d_inf_flags=0, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_is_one when the call returns; scalars stay on the host.
+    -> (combined, rechecked)"""
+    name = "blsmi_pairing_product_batch_rlc_locate_dev"
+    r, pr = _scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _check(_fn_0_18(name)(d_g1 or 0, d_inf_flags or 0, d_g2_tab or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, _block(block), d_is_one or 0, C.byref(comb), C.byref(nre),
+                          stream or 0), name[len("blsmi_"):])
+    return comb.value, nre.value
+
+
+def pairing_product_batch_rlc_locate_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars=None, block=0, stream=0):
+    """device-pointer form over in-memory points (no flags: z == 0 is infinity) -> (combined, rechecked)"""
+    name = "blsmi_pairing_product_batch_rlc_locate_jac_dev"
+    r, pr = _scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _check(_fn_0_18(name)(d_g1_jac or 0, d_g2_tab_jac or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, _block(block), d_is_one or 0, C.byref(comb), C.byref(nre), stream or 0),
+           name[len("blsmi_"):])
+    return comb.value, nre.value

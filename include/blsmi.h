@@ -87,8 +87,10 @@ void blsmi_shutdown(void);
  * verification of many committee aggregates in one call (blsmi_g?pubs_verify_aggregate_common*_batch_rlc[_jac|_dev]) and
  * blsmi_debug_g2_sum_segmented_u64_pair; no existing prototype changes, no new option.  0.17 adds the randomised pairing-product batches
  * (blsmi_pairing_product_batch_rlc[_jac|_dev|_jac_dev]: one equation for a batch of pairing products, the pairs of one G2 table entry sharing
- * one Miller loop) and blsmi_debug_pairing_product_batch_rlc_dev_nosplit; no existing prototype changes, no new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16 and 0.17 by the presence of
+ * one Miller loop) and blsmi_debug_pairing_product_batch_rlc_dev_nosplit; no existing prototype changes, no new option.  0.18 adds the randomised pairing-product
+ * batches that find the bad items by blocks (blsmi_pairing_product_batch_rlc_locate[_jac|_dev|_jac_dev]); no existing prototype changes, no
+ * new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17 and 0.18 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -957,6 +959,52 @@ int blsmi_pairing_product_batch_rlc_jac_dev(const void *d_g1_jac, const void *d_
 int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void *d_g1_aff, const void *d_inf_flags, const void *d_g2_tab, size_t nq, const void *d_q_idx,
                                                       size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars, void *d_is_one, int *combined,
                                                       void *stream);
+
+/* ---- pairing products, randomised, that find the bad items by blocks (blsmi 0.18) -------------------------------------------------------
+ * blsmi_pairing_product_batch_rlc* above, for batches in which an item may fail: arguments, verdicts, infinity rules, scalars and the
+ * subgroup precondition are those of 0.17, and two arguments are added -- `block` after `scalars`, `rechecked` (host, may be NULL) after
+ * `combined`.  The m items are cut into B = ceil(m / block) contiguous blocks, the last one possibly shorter; block = 0 is automatic,
+ * max(64, ceil(m / 256)); any value >= 1 is legal (every cell below has a Miller loop of its own, no layout pairs two of them), and
+ * block >= m gives one block.  A CELL is (block b, table entry g) with at least one pair of block b referring to g; with
+ *     S_c = sum_{k in c} r_item(k) * P_k,        V_b = prod_{c in b} Miller(S_c, Q_g(c)),        total = prod_b V_b
+ * *combined (may be NULL) = 1 exactly when FE(total) == FQ12One: every verdict is 1 then and *rechecked = 0.  When the total fails, the B
+ * block values -- which exist by then: no second ladder, no second Miller loop -- are final-exponentiated; the items of the blocks whose
+ * value is one get verdict 1, and the items of the failing blocks, and only those, get the verdicts of blsmi_pairing_product_batch's own
+ * path.  *rechecked is the number of those items.
+ * Soundness: a block whose equation holds has a failing item with probability at most 2^-64 over the drawn scalars, because its weights
+ * are its own items'; caller scalars keep 0.17's caveat -- two failing items whose values cancel under equal scalars pass unnoticed, in one
+ * block or in two, because the total holds.  P_k and the table entries are in the prime-order subgroups, as in 0.17.
+ * Infinity, per cell: an infinite P_k adds nothing to its cell; an all-zero entry drops its cells; a cell whose sum is the point at
+ * infinity contributes 1; none of these sends anything to the per-item path; a block with no surviving cell, or with no pairs at all, has
+ * value one.
+ *   - BLSMI_E_ARG and m = 0 / np = 0 as in 0.17, answered on the host before any device work, with *rechecked = 0.  No `block` value is
+ *     refused.  m beyond 2^32 - 1 is BLSMI_E_ARG here (the items of the failing blocks are 32-bit indices).
+ *   - _dev: as in 0.17; the caller's buffers stay untouched (the recheck gathers the failing blocks' records into copies of its own).
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * When to call it (one MI355X, points resident, block = 0, the three calls alternating, median of 20 +- spread in ms; DESIGN.md 3s has the
+ * table and the stages): wherever blsmi_pairing_product_batch_rlc_dev is the right call and an item may fail.  One bad item, m x k pairs:
+ * 16 384 x 4 with three shared entries 12.5 +- 0.2 against 22.5 +- 0.3 for the 0.17 call (the 0.10 call alone: 11.9), 65 536 x 4 the same
+ * way 27.4 +- 0.8 against 66.7 +- 1.0 (0.10: 40.0), 16 384 x 2 with both entries shared 6.6 against 13.2 (0.10: 8.4); sixteen bad items in
+ * sixteen blocks cost 0.4 to 2.4 ms more.  All items valid it costs what the 0.17 call costs, within the spreads at the Groth16 shapes
+ * (10.2 against 10.2, 24.4 against 24.9) and 0.2 ms LESS at 16 384 x 2 (4.1 against 4.3: the sums' fold passes over 512 cells of 64 pairs are 0.4 ms
+ * shorter than over two groups of 16 384, and 512 Miller loops cost what two do, one latency-path launch of 0.7 ms).  What 0.17 says about batches with nothing shared and about a few
+ * thousand items or fewer holds here too (2 048 x 4 with one bad item: 7.7 against 3.3 ms for the 0.10 call), and at 16 384 x 4 a failing
+ * call is still 0.6 ms behind the 0.10 call alone.  The automatic block stays: at 65 536 x 4 with one bad item, block 64 / 256 / 1 024 /
+ * 4 096 give 29.2 / 28.2 / 28.9 / 31.1 ms, spreads 0.7 to 1.0. */
+int blsmi_pairing_product_batch_rlc_locate(const uint8_t *g1_aff /* np*96 */, const uint8_t *inf_flags /* np, may be NULL: bit0 = P_k infinity */,
+                                           const uint8_t *g2_tab /* nq*192 */, size_t nq, const uint32_t *q_idx /* np, or NULL: pair k uses entry k and nq == np */,
+                                           size_t np, const uint64_t *seg_off /* m+1 */, size_t m,
+                                           const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */,
+                                           uint8_t *is_one /* m */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_pairing_product_batch_rlc_locate_jac(const uint64_t *g1_jac /* np*18 */, const uint64_t *g2_tab_jac /* nq*36 */, size_t nq, const uint32_t *q_idx,
+                                               size_t np, const uint64_t *seg_off, size_t m, const uint64_t *scalars, size_t block,
+                                               uint8_t *is_one, int *combined, size_t *rechecked);
+int blsmi_pairing_product_batch_rlc_locate_dev(const void *d_g1_aff, const void *d_inf_flags, const void *d_g2_tab, size_t nq, const void *d_q_idx,
+                                               size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars /* host: m, may be NULL */, size_t block,
+                                               void *d_is_one, int *combined /* host */, size_t *rechecked /* host */, void *stream);
+int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void *d_g1_jac, const void *d_g2_tab_jac, size_t nq, const void *d_q_idx,
+                                                   size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars, size_t block,
+                                                   void *d_is_one, int *combined, size_t *rechecked, void *stream);
 
 #ifdef __cplusplus
 }
