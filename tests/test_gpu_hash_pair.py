@@ -40,14 +40,17 @@ def test_hash_g2_lane_pairs_against_the_latency_path_and_the_oracle():
     from bls_amd import engine
     from gpu_common import RC
     engine.init(0)
-    msgs = _msgs(2051) + [b"", b"\x00", b"a" * 55, b"a" * 56, b"a" * 119, b"a" * 120]      # SHA-256 padding boundaries with the 0x01 prefix
+    # SHA-256 padding boundaries: with the 0x01 prefix 54 / 118 bytes are the last that fit one / two blocks, 55 / 119 open the next one
+    # (every length 0 .. 200 on every route: tests/test_gpu_hash_lengths.py)
+    pinned = [b"", b"\x00", b"a" * 54, b"a" * 55, b"a" * 56, b"a" * 118, b"a" * 119, b"a" * 120]
+    msgs = _msgs(2051) + pinned
     try:
         engine.set_latency_threshold(0); x = engine.hash_g2_batch(msgs)        # lane pairs
         engine.set_latency_threshold(8192); y = engine.hash_g2_batch(msgs)     # SWU lanes + level program
     finally:
         engine.set_latency_threshold(8192)
     assert np.array_equal(x, y)
-    for i in list(range(0, len(msgs), 257)) + list(range(len(msgs) - 6, len(msgs))):
+    for i in list(range(0, 2051, 257)) + list(range(2051, len(msgs))):
         assert x[i].tobytes() == RC.hash_g2(msgs[i]), i
     one = None
     try:

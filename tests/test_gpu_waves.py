@@ -43,7 +43,8 @@ def test_hash_g2_with_domain_on_both_sides_of_the_wave_hand_over(eng):
     for i in (0, 5, 127):
         assert small[i].tobytes() == RC.hash_g2_with_domain(m32[i], dom)
     assert large[128].tobytes() == RC.hash_g2_with_domain(m32[128], dom)
-    # a message whose first candidates fail: whatever the round count, the eight waves must agree with the eight lanes -- 64 singles
+    # 64 singles: the eight waves agree with the eight lanes at the search counters these messages have, which are 5 at the most -- every
+    # one closes in the first round of either form.  The later rounds (counters 8 .. 25): tests/test_gpu_tai_search.py
     for i in range(64):
         assert eng.hash_g2_with_domain_batch([m32[i]], dom)[0].tobytes() == large[i].tobytes()
 
