@@ -942,14 +942,15 @@ BLSMI_API int blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev(con
 //     every item holds  <=  FE( prod_g Miller( sum_{k in g} r_j(k) P_k, Q_g ) ) == 1        (g: the table entries some pair refers to)
 // by bilinearity -- one Miller loop per entry referred to and one final exponentiation instead of np and m.  Stages, on the call's stream:
 //   1  the plan (pprod_rlc_plan.h): groups of pairs per entry, split into shared groups and singletons, compacted shared first
-//   2  k_pprod_rlc_weights: w_k = r_j(k) and the 0.10 flag byte of every pair (P_k infinite / its entry the all-zero record)
-//   3  shared groups: the weighted segmented G1 sum (segsum_dev with scalars); singletons: k_g1_mul_u64_idx, one lane each
-//   4  k_pprod_skip over the d' (S_g, Q_g): a sum at infinity or an all-zero entry runs its loop on the generators and is left out -- the
-//      pair(s) contribute 1, as in 0.10, and the call does NOT leave the combined path for it (an item {(P, Q), (-P, Q)} is legitimate)
-//   5  d' Miller loops in the layout a Pairing call of d' tuples takes, seg_prod_dev over one segment, one final exponentiation, is_one
-//   6  the equation held: every verdict is 1.  Otherwise blsmi_pairing_product_batch's own path (pprod_dev) over all m items from what is
-//      on the device, every pair's entry gathered from the compacted table (k_gather_records).
-// One lease, one device, never in the request combiner; "rlc_min" is not consulted.
+//   2  pprod_weighted_sums: k_pprod_rlc_weights, w_k = r_j(k) and the 0.10 flag byte of every pair (P_k infinite / its entry the all-zero
+//      record); shared groups: the weighted segmented G1 sum (segsum_dev with scalars); singletons: k_g1_mul_u64_idx, one lane each
+//   3  its own: k_pprod_skip over the d' (S_g, Q_g) -- a sum at infinity or an all-zero entry runs its loop on the generators and is left
+//      out: the pair(s) contribute 1, as in 0.10, and the call does NOT leave the combined path for it (an item {(P, Q), (-P, Q)} is
+//      legitimate) -- and d' Miller loops in the layout a Pairing call of d' tuples takes
+//   4  pprod_check_total: seg_prod_dev over one segment, one final exponentiation, is_one
+//   5  the equation held: every verdict is 1 (pprod_all_one).  Otherwise pprod_fallback_all: blsmi_pairing_product_batch's own path
+//      (pprod_dev) over all m items from what is on the device, every pair's entry gathered from the compacted table (k_gather_records).
+// One lease, one device, never in the request combiner; "rlc_min" is not consulted.  Stages 2 and 4 also serve the form of 0.18 below.
 namespace {
 struct PprodRlcIn {
     const u8* g1;            // np affine records on the device
@@ -960,156 +961,149 @@ struct PprodRlcIn {
     const uint64_t* seg_off; // host: the items' offsets
     size_t np, m;
 };
-// d_is_one: m verdict bytes on the device.  Synchronises the call's stream.
-int pprod_rlc_core(const PprodRlcIn& in, const blsmi_route::PprodRlcPlan& pl, void* d_is_one, bool* held) {
-    const size_t np = in.np, m = in.m, dg = pl.groups(), dsh = pl.shared(), dsi = pl.single.size(), ns = pl.perm.size(), words = (size_t)12 * NL;
+// What the weighted sums read of a plan, whichever form made it.  A SEGMENT is what gets one sum and one Miller loop -- a compacted group
+// of 0.17, a cell of 0.18 -- the multi-pair ones as segments of a permutation of their pairs, the one-pair ones as a list of pairs.
+struct PprodSegments { const uint32_t *item_of, *group_of, *perm, *single; const uint64_t* multi_off; size_t multi, nperm, nsingle; };   // multi_off: multi + 1 offsets into perm
+// (of a PprodRlcPlan with its seg_off, of a PprodLocatePlan with its cell_off)
+template <class Plan> PprodSegments pprod_segments(const Plan& p, const std::vector<uint64_t>& off) { return {p.item_of.data(), p.group_of.data(), p.perm.data(), p.single.data(), off.data(), off.size() - 1, p.perm.size(), p.single.size()}; }
+// What one such check keeps for the length of its call, the counterpart of RlcCall.  On the device: the scalars, the pairs' weights and flag
+// bytes, the plan's arrays, the segments' sums S with their infinity flags, the total's one-segment plan, product, final exponentiation and
+// verdict.  On the host: the two chunk plans, whose blobs the uploads read, and the verdict byte the last copy targets.  The rule written at
+// RlcCall holds: the struct stays where it is until the call has synchronised, and a buffer a later stage reads lives here or in the driver's frame.
+struct PprodCall {
+    PprodRlcIn in{};
+    SegPlan splan, oplan;
+    Layout fe{};                                                           // of the total's final exponentiation
+    DBuf dr, dw, pflag, dgo, dio, dperm, dsingle, S, sinf, oblob, prod, vals, one;
+    uint8_t verdict = 0;
+};
+// The plans, the buffers, the uploads, k_pprod_rlc_weights, and S = sum_{k in segment} w_k P_k for every segment.  nvals: the values the total
+// will be the product of (0.17: the groups' Miller values, 0.18: the blocks' products); load: what lays out its final exponentiation.
+int pprod_weighted_sums(PprodCall& c, const PprodRlcIn& in, const PprodSegments& g, size_t nvals, size_t load) {
+    c.in = in;
+    const size_t np = in.np, nsums = g.multi + g.nsingle;
     hipStream_t s = g_stream;
-    SegPlan splan, oplan, iplan;
-    const uint64_t whole[2] = {0, dg};
-    try {
-        segsum_plan(pl.seg_off.data(), dsh, segsum_chunk_of(ns), splan, 64, 1);
-        pprod_plan(whole, 1, oplan);
-    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    DBuf dr, dw, pflag, dgo, dio, dperm, dsingle, S, sinf, skip, f, blob, prod, vals, one;
-    HIPCHK(dr.alloc(sizeof(uint64_t) * m)); HIPCHK(dw.alloc(sizeof(uint64_t) * np)); HIPCHK(pflag.alloc(np)); HIPCHK(dgo.alloc(sizeof(uint32_t) * np)); HIPCHK(dio.alloc(sizeof(uint32_t) * np));
-    HIPCHK(dperm.alloc(sizeof(uint32_t) * ns)); HIPCHK(dsingle.alloc(sizeof(uint32_t) * dsi)); HIPCHK(S.alloc((size_t)96 * dg)); HIPCHK(sinf.alloc(dg)); HIPCHK(skip.alloc(dg));
-    HIPCHK(f.alloc(sizeof(i32) * words * dg)); HIPCHK(blob.alloc(oplan.blob.size())); HIPCHK(vals.alloc(576)); HIPCHK(one.alloc(1));
-    HIPCHK(hipMemcpyAsync(dr.p, in.r, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dio.p, pl.item_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dgo.p, pl.group_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-    if (ns) HIPCHK(hipMemcpyAsync(dperm.p, pl.perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, s));
-    if (dsi) HIPCHK(hipMemcpyAsync(dsingle.p, pl.single.data(), sizeof(uint32_t) * dsi, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(blob.p, oplan.blob.data(), oplan.blob.size(), hipMemcpyHostToDevice, s));
-    launch(KERNEL_OF(k_pprod_rlc_weights), nblocks(np), s, in.g1, in.flags, in.tab, dgo.p, dio.p, dr.p, dw.p, pflag.p, np);
+    const uint64_t whole[2] = {0, nvals};
+    try { segsum_plan(g.multi_off, g.multi, segsum_chunk_of(g.nperm), c.splan, 64, 1); pprod_plan(whole, 1, c.oplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    c.fe = pprod_fe_layout(1, load);
+    HIPCHK(c.dr.alloc(sizeof(uint64_t) * in.m)); HIPCHK(c.dw.alloc(sizeof(uint64_t) * np)); HIPCHK(c.pflag.alloc(np)); HIPCHK(c.dgo.alloc(sizeof(uint32_t) * np));
+    HIPCHK(c.dio.alloc(sizeof(uint32_t) * np)); HIPCHK(c.dperm.alloc(sizeof(uint32_t) * g.nperm)); HIPCHK(c.dsingle.alloc(sizeof(uint32_t) * g.nsingle));
+    HIPCHK(c.S.alloc((size_t)96 * nsums)); HIPCHK(c.sinf.alloc(nsums)); HIPCHK(c.oblob.alloc(c.oplan.blob.size()));
+    HIPCHK(c.prod.alloc(c.fe == Layout::wave ? 576 : sizeof(i32) * 12 * NL)); HIPCHK(c.vals.alloc(576)); HIPCHK(c.one.alloc(1));
+    HIPCHK(hipMemcpyAsync(c.dr.p, in.r, sizeof(uint64_t) * in.m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c.dio.p, g.item_of, sizeof(uint32_t) * np, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(c.dgo.p, g.group_of, sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    if (g.nperm) HIPCHK(hipMemcpyAsync(c.dperm.p, g.perm, sizeof(uint32_t) * g.nperm, hipMemcpyHostToDevice, s));
+    if (g.nsingle) HIPCHK(hipMemcpyAsync(c.dsingle.p, g.single, sizeof(uint32_t) * g.nsingle, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c.oblob.p, c.oplan.blob.data(), c.oplan.blob.size(), hipMemcpyHostToDevice, s));
+    launch(KERNEL_OF(k_pprod_rlc_weights), nblocks(np), s, in.g1, in.flags, in.tab, c.dgo.p, c.dio.p, c.dr.p, c.dw.p, c.pflag.p, np);
     prof_mark(nullptr);
-    // S_g = sum_{k in g} w_k P_k: the shared groups' into S[0, dsh), the singletons' behind them
-    int rc = segsum_dev(group_kernels(1), false, in.g1, pflag.as<u8>(), np, dperm.as<u32>(), splan, S.as<u8>(), sinf.as<u8>(), 1, s, dw.as<u64>());
-    if (rc) return rc;
-    if (dsi) {
-        launch(KERNEL_OF(k_g1_mul_u64_idx), nblocks(dsi), s, in.g1, pflag.p, dw.p, dsingle.p, S.as<u8>() + (size_t)96 * dsh, sinf.as<u8>() + dsh, dsi);
-        prof_mark(nullptr);
-    }
-    launch_quiet(KERNEL_OF(k_pprod_skip), nblocks(dg), s, S.p, in.tab, sinf.p, g_gens.g1, g_gens.g2, skip.p, dg);
-    launch_miller_tuples(S.as<u8>(), in.tab, f.as<i32>(), dg, s, pairing_layout(0, dg, tune(), route_load(dg)));
-    const Layout fe = pprod_fe_layout(1, route_load(dg));
-    HIPCHK(prod.alloc(fe == Layout::wave ? 576 : sizeof(i32) * words));
-    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of seg_prod_dev
-    rc = seg_prod_dev(f.as<i32>(), dg, skip.as<u8>(), oplan, blob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
-    if (rc) return rc;
-    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, 1, s);
+    // the multi-pair segments' sums into S[0, multi), the one-pair segments' behind them
+    int rc = segsum_dev(group_kernels(1), false, in.g1, c.pflag.as<u8>(), np, c.dperm.as<u32>(), c.splan, c.S.as<u8>(), c.sinf.as<u8>(), 1, s, c.dw.as<u64>());
+    if (rc || !g.nsingle) return rc;
+    launch(KERNEL_OF(k_g1_mul_u64_idx), nblocks(g.nsingle), s, in.g1, c.pflag.p, c.dw.p, c.dsingle.p, c.S.as<u8>() + (size_t)96 * g.multi, c.sinf.as<u8>() + g.multi, g.nsingle);
+    prof_mark(nullptr);
+    return BLSMI_OK;
+}
+// The total: the nvals values at src (skip: the ones left out, or null) multiplied as one segment, the final exponentiation, is_one, the byte back.
+// The caller has opened the profile segment of the segmented products (0.18 runs the blocks' products in it too).  Synchronises; *held: the equation held.
+int pprod_check_total(PprodCall& c, const i32* src, size_t nvals, const u8* skip, bool* held) {
+    hipStream_t s = g_stream;
+    const bool wave = c.fe == Layout::wave;
+    int rc = seg_prod_dev(src, nvals, skip, c.oplan, c.oblob.as<u8>(), wave ? (i32*)nullptr : c.prod.as<i32>(), wave ? c.prod.as<u64>() : (u64*)nullptr, s); if (rc) return rc;
+    final_exp_values(c.fe, c.prod.p, c.vals.as<u64>(), c.one.p, 1, s);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
-    uint8_t verdict = 0;
-    HIPCHK(hipMemcpyAsync(&verdict, one.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    *held = verdict == 1;
-    if (*held) {
-        HIPCHK(hipMemsetAsync(d_is_one, 1, m, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return BLSMI_OK;
-    }
-    // the per-item path of 0.10 over all m items: every pair's table entry from the compacted table (an all-zero entry's record now holds
-    // the generator: bit 1 of the pair's flag byte, written before, leaves the pair out all the same)
-    try { pprod_plan(in.seg_off, m, iplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    DBuf a, b;
-    HIPCHK(b.alloc((size_t)192 * np));
+    HIPCHK(hipMemcpyAsync(&c.verdict, c.one.p, 1, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    *held = c.verdict == 1;
+    return BLSMI_OK;
+}
+// every verdict is 1; sync: nothing follows on the stream
+int pprod_all_one(const PprodCall& c, void* d_is_one, bool sync) {
+    HIPCHK(hipMemsetAsync(d_is_one, 1, c.in.m, g_stream));
+    if (sync) HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+// 0.17, stage 5 when the equation failed: the per-item path of 0.10 over all m items, every pair's table entry from the compacted table (an
+// all-zero entry's record now holds the generator: bit 1 of the pair's flag byte, written before, leaves the pair out all the same)
+int pprod_fallback_all(PprodCall& c, void* d_is_one) {
+    const PprodRlcIn& in = c.in;
+    const size_t np = in.np;
+    hipStream_t s = g_stream;
+    SegPlan iplan; try { pprod_plan(in.seg_off, in.m, iplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf a, b; HIPCHK(b.alloc((size_t)192 * np));
     u8* g1 = const_cast<u8*>(in.g1);
     if (!in.own_g1) { HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(hipMemcpyAsync(a.p, in.g1, (size_t)96 * np, hipMemcpyDeviceToDevice, s)); g1 = a.as<u8>(); }
-    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * np), s, in.tab, dgo.p, b.p, 48, np);
-    return pprod_dev(g1, b.as<u8>(), pflag.as<u8>(), np, iplan, nullptr, d_is_one, s);
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * np), s, in.tab, c.dgo.p, b.p, 48, np);
+    return pprod_dev(g1, b.as<u8>(), c.pflag.as<u8>(), np, iplan, nullptr, d_is_one, s);
+}
+// d_is_one: m verdict bytes on the device.  Synchronises the call's stream.
+int pprod_rlc_core(const PprodRlcIn& in, const blsmi_route::PprodRlcPlan& pl, void* d_is_one, bool* held) {
+    const size_t dg = pl.groups();
+    hipStream_t s = g_stream;
+    PprodCall c; DBuf skip, f;
+    HIPCHK(skip.alloc(dg)); HIPCHK(f.alloc(sizeof(i32) * 12 * NL * dg));
+    int rc = pprod_weighted_sums(c, in, pprod_segments(pl, pl.seg_off), dg, route_load(dg)); if (rc) return rc;   // stage 2
+    launch_quiet(KERNEL_OF(k_pprod_skip), nblocks(dg), s, c.S.p, in.tab, c.sinf.p, g_gens.g1, g_gens.g2, skip.p, dg);   // stage 3
+    launch_miller_tuples(c.S.as<u8>(), in.tab, f.as<i32>(), dg, s, pairing_layout(0, dg, tune(), route_load(dg)));
+    prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of seg_prod_dev
+    rc = pprod_check_total(c, f.as<i32>(), dg, skip.as<u8>(), held); if (rc) return rc;   // stage 4
+    return *held ? pprod_all_one(c, d_is_one, true) : pprod_fallback_all(c, d_is_one);   // stage 5
 }
 // ---- pairing products, randomised, that find the bad items by blocks (blsmi 0.18; include/blsmi.h under the same title) --------------------
 // The equation above with the m items cut into B contiguous blocks (pprod_locate_plan.h) and the sums taken per CELL -- (block, table entry)
 // with a pair of the block referring to the entry -- so that every block has a product of its own,
 //     V_b = prod_{c in b} Miller( sum_{k in c} r_j(k) P_k, Q_g(c) ),        total = prod_b V_b,
 // all of it there by the time the total is known: a failing call runs no second ladder, no second Miller loop.  Stages, on the call's stream:
-//   1  k_pprod_rlc_weights, as above
-//   2  multi-pair cells: the weighted segmented sum (idx = the plan's permutation, the cells as segments); one-pair cells: k_g1_mul_u64_idx
-//   3  k_pprod_cell_route: every cell's sum and its entry's record into dense arrays in block order, the skip rule on the way (one launch
-//      where two record gathers, a byte gather and k_pprod_skip would run)
-//   4  C Miller loops in the layout a Pairing call of C tuples takes: one value per cell in every layout
-//   5  seg_prod_dev over the blocks' slot borders: B block values, KEPT -- as a hand-off buffer, which the total's product reads, and as
-//      in-memory records where their final exponentiation (that of a pairing product of B items) runs in the wave layout; the total is a
-//      second, one-segment seg_prod_dev over the B values; one final exponentiation, is_one
-//   6  the total held: every verdict is 1
-//   7  it failed: B final exponentiations, B bytes to the host; the failing blocks' G1 records, flag bytes and per-pair table records
-//      gathered dense (the entry indices composed on the host), pprod_dev over them, the verdicts scattered over a verdict array preset to
-//      1.  The dense copies are the call's own: nothing of the caller's is written, no full copy of the G1 records is made.
-// One lease, one device, never in the request combiner; "rlc_min" is not consulted.  d_is_one: m verdict bytes on the device.  Synchronises.
-int pprod_locate_core(const PprodRlcIn& in, const blsmi_route::PprodLocatePlan& pl, void* d_is_one, bool* held, size_t* rechecked) {
-    const size_t np = in.np, m = in.m, C = pl.cells(), Cm = pl.multi(), Cs = pl.single.size(), ns = pl.perm.size(), B = pl.blocks(), dg = pl.entry_of.size();
-    const size_t words = (size_t)12 * NL;
+//   1  pprod_weighted_sums, the cells as its segments (idx = the plan's permutation), behind the uploads of the cells' slots
+//   2  pprod_locate_failing_blocks --
+//      k_pprod_cell_route: every cell's sum and its entry's record into dense arrays in block order, the skip rule on the way (one launch
+//      where two record gathers, a byte gather and k_pprod_skip would run);
+//      C Miller loops in the layout a Pairing call of C tuples takes: one value per cell in every layout;
+//      seg_prod_dev over the blocks' slot borders: B block values, KEPT -- as a hand-off buffer, which the total's product reads, and as
+//      in-memory records where their final exponentiation (that of a pairing product of B items) runs in the wave layout;
+//      pprod_check_total over the B values (a second, one-segment seg_prod_dev), then every verdict is 1: the answer when the total held;
+//      it failed: B final exponentiations, B bytes to the host, the failing blocks' items and pairs (pprod_locate_failing)
+//   3  pprod_locate_recheck: the failing blocks' G1 records, flag bytes and per-pair table records gathered dense (the entry indices
+//      composed on the host), pprod_dev over them, the verdicts scattered over the ones.  The dense copies are the call's own: nothing of
+//      the caller's is written, no full copy of the G1 records is made.
+// One lease, one device, never in the request combiner; "rlc_min" is not consulted.
+// what the driver keeps of the cells, uploaded ahead of the first kernel: the blocks' chunk plan with its blob, every slot's cell and table entry
+struct PprodCellBufs { SegPlan bplan; DBuf bblob, dsum, dent; };
+// Stage 2.  *held: the total held, and every verdict is 1.  Otherwise ff has the items and pairs of the failing blocks, and the verdict
+// array is preset to 1 for the recheck to scatter over.  Synchronises.
+int pprod_locate_failing_blocks(PprodCall& c, const blsmi_route::PprodLocatePlan& pl, const PprodCellBufs& b, void* d_is_one, bool* held, blsmi_route::PprodLocateFailing& ff) {
+    const size_t C = pl.cells(), B = pl.blocks(), words = (size_t)12 * NL;
     hipStream_t s = g_stream;
-    *rechecked = 0;
-    SegPlan splan, bplan, oplan;
-    const uint64_t whole[2] = {0, B};
-    try {
-        segsum_plan(pl.cell_off.data(), Cm, segsum_chunk_of(ns), splan, 64, 1);
-        pprod_plan(pl.slot_off.data(), B, bplan);
-        pprod_plan(whole, 1, oplan);
-    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    const Layout feb = pprod_fe_layout(B, route_load(B)), fe = pprod_fe_layout(1, route_load(C));
-    DBuf dr, dw, pflag, dgo, dio, dperm, dsingle, dsum, dent, S, sinf, g1c, g2c, skip, f, bblob, oblob, bval, bmem, prod, vals, one;
-    HIPCHK(dr.alloc(sizeof(uint64_t) * m)); HIPCHK(dw.alloc(sizeof(uint64_t) * np)); HIPCHK(pflag.alloc(np)); HIPCHK(dgo.alloc(sizeof(uint32_t) * np)); HIPCHK(dio.alloc(sizeof(uint32_t) * np));
-    HIPCHK(dperm.alloc(sizeof(uint32_t) * ns)); HIPCHK(dsingle.alloc(sizeof(uint32_t) * Cs)); HIPCHK(dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(dent.alloc(sizeof(uint32_t) * C));
-    HIPCHK(S.alloc((size_t)96 * C)); HIPCHK(sinf.alloc(C)); HIPCHK(g1c.alloc((size_t)96 * C)); HIPCHK(g2c.alloc((size_t)192 * C)); HIPCHK(skip.alloc(C));
-    HIPCHK(f.alloc(sizeof(i32) * words * C)); HIPCHK(bblob.alloc(bplan.blob.size())); HIPCHK(oblob.alloc(oplan.blob.size()));
+    const Layout feb = pprod_fe_layout(B, route_load(B));
+    DBuf g1c, g2c, skip, f, bval, bmem, bvals, bone;
+    HIPCHK(g1c.alloc((size_t)96 * C)); HIPCHK(g2c.alloc((size_t)192 * C)); HIPCHK(skip.alloc(C)); HIPCHK(f.alloc(sizeof(i32) * words * C));
     HIPCHK(bval.alloc(sizeof(i32) * words * B)); HIPCHK(bmem.alloc(feb == Layout::wave ? 576 * B : 1));
-    HIPCHK(prod.alloc(fe == Layout::wave ? 576 : sizeof(i32) * words)); HIPCHK(vals.alloc(576)); HIPCHK(one.alloc(1));
-    HIPCHK(hipMemcpyAsync(dr.p, in.r, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dio.p, pl.item_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dgo.p, pl.group_of.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-    if (ns) HIPCHK(hipMemcpyAsync(dperm.p, pl.perm.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, s));
-    if (Cs) HIPCHK(hipMemcpyAsync(dsingle.p, pl.single.data(), sizeof(uint32_t) * Cs, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(bblob.p, bplan.blob.data(), bplan.blob.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(oblob.p, oplan.blob.data(), oplan.blob.size(), hipMemcpyHostToDevice, s));
-    launch(KERNEL_OF(k_pprod_rlc_weights), nblocks(np), s, in.g1, in.flags, in.tab, dgo.p, dio.p, dr.p, dw.p, pflag.p, np);
-    prof_mark(nullptr);
-    // S_c = sum_{k in c} w_k P_k: the multi-pair cells' into S[0, Cm), the one-pair cells' behind them
-    int rc = segsum_dev(group_kernels(1), false, in.g1, pflag.as<u8>(), np, dperm.as<u32>(), splan, S.as<u8>(), sinf.as<u8>(), 1, s, dw.as<u64>());
-    if (rc) return rc;
-    if (Cs) {
-        launch(KERNEL_OF(k_g1_mul_u64_idx), nblocks(Cs), s, in.g1, pflag.p, dw.p, dsingle.p, S.as<u8>() + (size_t)96 * Cm, sinf.as<u8>() + Cm, Cs);
-        prof_mark(nullptr);
-    }
-    launch(KERNEL_OF(k_pprod_cell_route), tuple_blocks(Layout::row, C), s, S.p, sinf.p, in.tab, dsum.p, dent.p, g_gens.g1, g_gens.g2, g1c.p, g2c.p, skip.p, C, dg);
+    launch(KERNEL_OF(k_pprod_cell_route), tuple_blocks(Layout::row, C), s, c.S.p, c.sinf.p, c.in.tab, b.dsum.p, b.dent.p, g_gens.g1, g_gens.g2, g1c.p, g2c.p, skip.p, C, pl.entry_of.size());
     launch_miller_tuples(g1c.as<u8>(), g2c.as<u8>(), f.as<i32>(), C, s, pairing_layout(0, C, tune(), route_load(C)));
     prof_mark(KERNEL_OF(k_fq12_seg_prod_row).name);                        // one segment: the passes of both seg_prod_dev
-    rc = seg_prod_dev(f.as<i32>(), C, skip.as<u8>(), bplan, bblob.as<u8>(), bval.as<i32>(), feb == Layout::wave ? bmem.as<u64>() : (u64*)nullptr, s);
-    if (rc) return rc;
-    rc = seg_prod_dev(bval.as<i32>(), B, nullptr, oplan, oblob.as<u8>(), fe == Layout::wave ? (i32*)nullptr : prod.as<i32>(), fe == Layout::wave ? prod.as<u64>() : (u64*)nullptr, s);
-    if (rc) return rc;
-    final_exp_values(fe, prod.p, vals.as<u64>(), one.p, 1, s);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    uint8_t verdict = 0;
-    HIPCHK(hipMemcpyAsync(&verdict, one.p, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    *held = verdict == 1;
-    HIPCHK(hipMemsetAsync(d_is_one, 1, m, s));
-    if (*held) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }
+    int rc = seg_prod_dev(f.as<i32>(), C, skip.as<u8>(), b.bplan, b.bblob.as<u8>(), bval.as<i32>(), feb == Layout::wave ? bmem.as<u64>() : (u64*)nullptr, s);
+    if (!rc) rc = pprod_check_total(c, bval.as<i32>(), B, nullptr, held);
+    if (!rc) rc = pprod_all_one(c, d_is_one, *held);
+    if (rc || *held) return rc;
     // which blocks fail: their kept values through the final exponentiation a pairing product of B items takes
-    std::vector<uint8_t> fail;
-    blsmi_route::PprodLocateFailing ff;
-    try { fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    DBuf bvals, bone;
+    std::vector<uint8_t> fail; try { fail.resize(B); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     HIPCHK(bvals.alloc(576 * B)); HIPCHK(bone.alloc(B));
     final_exp_values(feb, feb == Layout::wave ? bmem.p : bval.p, bvals.as<u64>(), bone.p, B, s);
     prof_mark(nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(fail.data(), bone.p, B, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    SegPlan iplan;
+    HIPCHK(hipMemcpyAsync(fail.data(), bone.p, B, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
     try {
-        for (uint8_t& b : fail) b = b == 1 ? 0 : 1;
-        blsmi_route::pprod_locate_failing(pl, in.seg_off, fail.data(), ff);
-        pprod_plan(ff.dense_off.data(), ff.items.size(), iplan);
+        for (uint8_t& x : fail) x = x == 1 ? 0 : 1;
+        blsmi_route::pprod_locate_failing(pl, c.in.seg_off, fail.data(), ff);
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    return BLSMI_OK;
+}
+// Stage 3: the failing blocks' items, dense, through blsmi_pairing_product_batch's own path; their verdicts back over the ones.  Synchronises.
+int pprod_locate_recheck(PprodCall& c, const blsmi_route::PprodLocateFailing& ff, void* d_is_one) {
+    const PprodRlcIn& in = c.in;
     const size_t nre = ff.items.size(), npd = ff.pairs.size();
-    if (nre == 0) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }    // (cannot be: the total is the product of the block values)
-    // the failing blocks' items, dense, through blsmi_pairing_product_batch's own path; their verdicts back over the ones
+    hipStream_t s = g_stream;
+    SegPlan iplan; try { pprod_plan(ff.dense_off.data(), nre, iplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     DBuf ditems, dpairs, dents, a, b, fl, okd;
     HIPCHK(ditems.alloc(sizeof(uint32_t) * nre)); HIPCHK(dpairs.alloc(sizeof(uint32_t) * npd)); HIPCHK(dents.alloc(sizeof(uint32_t) * npd));
     HIPCHK(a.alloc((size_t)96 * npd)); HIPCHK(b.alloc((size_t)192 * npd)); HIPCHK(fl.alloc(npd)); HIPCHK(okd.alloc(nre));
@@ -1121,95 +1115,115 @@ int pprod_locate_core(const PprodRlcIn& in, const blsmi_route::PprodLocatePlan& 
         if (reinterpret_cast<uintptr_t>(in.g1) & 15) launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)24 * npd), s, in.g1, dpairs.p, a.p, 24, npd);   // (a caller's buffer)
         else launch_quiet(KERNEL_OF(k_gather_records16), nblocks((size_t)6 * npd), s, in.g1, dpairs.p, a.p, 6, npd);
         launch_quiet(KERNEL_OF(k_gather_records16), nblocks((size_t)12 * npd), s, in.tab, dents.p, b.p, 12, npd);
-        launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(npd), s, pflag.p, dpairs.p, fl.p, npd);
+        launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(npd), s, c.pflag.p, dpairs.p, fl.p, npd);
         prof_mark(nullptr);
     }
-    rc = pprod_dev(a.as<u8>(), b.as<u8>(), fl.as<u8>(), npd, iplan, nullptr, okd.p, s);
-    if (rc) return rc;
+    int rc = pprod_dev(a.as<u8>(), b.as<u8>(), fl.as<u8>(), npd, iplan, nullptr, okd.p, s); if (rc) return rc;
     launch(KERNEL_OF(k_scatter_bytes), nblocks(nre), s, okd.p, ditems.p, d_is_one, nre);
     prof_mark(nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    *rechecked = nre;
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(s));
     return BLSMI_OK;
 }
-// what makes a call of the two functions below the block-locating form of 0.18: the caller's `block` (0: automatic) and where the number of
-// rechecked items goes (may be null)
-struct PprodLocate { size_t block; size_t* rechecked; };
+// d_is_one: m verdict bytes on the device.  Synchronises.
+int pprod_locate_core(const PprodRlcIn& in, const blsmi_route::PprodLocatePlan& pl, void* d_is_one, bool* held, size_t* rechecked) {
+    const size_t C = pl.cells();
+    hipStream_t s = g_stream;
+    *rechecked = 0;
+    PprodCall c; PprodCellBufs b;
+    blsmi_route::PprodLocateFailing ff;
+    try { pprod_plan(pl.slot_off.data(), pl.blocks(), b.bplan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    HIPCHK(b.dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(b.dent.alloc(sizeof(uint32_t) * C)); HIPCHK(b.bblob.alloc(b.bplan.blob.size()));
+    HIPCHK(hipMemcpyAsync(b.dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(b.dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.bblob.p, b.bplan.blob.data(), b.bplan.blob.size(), hipMemcpyHostToDevice, s));
+    int rc = pprod_weighted_sums(c, in, pprod_segments(pl, pl.cell_off), pl.blocks(), route_load(C)); if (rc) return rc;   // stage 1
+    rc = pprod_locate_failing_blocks(c, pl, b, d_is_one, held, ff);        // stage 2
+    if (rc || *held) return rc;
+    if (ff.items.empty()) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }   // (cannot be: the total is the product of the block values)
+    rc = pprod_locate_recheck(c, ff, d_is_one);                            // stage 3
+    if (!rc) *rechecked = ff.items.size();
+    return rc;
+}
+// what makes a call of the two functions below the block-locating form of 0.18 (on): the caller's `block` (0: automatic) and where the
+// number of rechecked items goes (may be null)
+struct PprodLocate { bool on = false; size_t block = 0; size_t* rechecked = nullptr; };
+// *combined and the locating form's *rechecked (either may be null): zero when a call begins, the call's own when it succeeds
+void pprod_report(int* combined, const PprodLocate& loc, bool held, size_t nre) { if (combined) *combined = held ? 1 : 0; if (loc.rechecked) *loc.rechecked = nre; }
+// The plan of the form a call takes, decided once, and that form's driver.
+struct PprodPlans {
+    bool locate = false;
+    blsmi_route::PprodRlcPlan pl; blsmi_route::PprodLocatePlan lp;
+    // false: what the plan functions refuse (BLSMI_E_ARG).  split == false: blsmi_debug_pairing_product_batch_rlc_dev_nosplit.  May throw bad_alloc.
+    bool build(const uint64_t* seg_off, size_t m, const uint32_t* q_idx, size_t np, size_t nq, bool split, const PprodLocate& loc) {
+        locate = loc.on;
+        return locate ? blsmi_route::pprod_locate_plan(seg_off, m, q_idx, np, nq, loc.block ? loc.block : blsmi_route::pprod_locate_auto_block(m), lp)
+                      : blsmi_route::pprod_rlc_plan(seg_off, m, q_idx, np, nq, pl, split);
+    }
+    const std::vector<uint32_t>& entry_of() const { return locate ? lp.entry_of : pl.entry_of; }
+    // *nre: the items the per-item path saw after the block equations (0.17: none)
+    int run(const PprodRlcIn& in, void* d_is_one, bool* held, size_t* nre) const { return locate ? pprod_locate_core(in, lp, d_is_one, held, nre) : pprod_rlc_core(in, pl, d_is_one, held); }
+};
 int pprod_rlc_host(const uint8_t* g1, const uint8_t* inf_flags, const uint8_t* tab, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m,
-                   const uint64_t* scalars, uint8_t* is_one, int* combined, bool jac, const PprodLocate* loc = nullptr) {
-    if (combined) *combined = 0;
-    if (loc && loc->rechecked) *loc->rechecked = 0;
+                   const uint64_t* scalars, uint8_t* is_one, int* combined, bool jac, const PprodLocate& loc = {}) {
+    pprod_report(combined, loc, false, 0);
     if (m == 0) return BLSMI_OK;
-    int rc = rlc_check_args(is_one && seg_off && (np == 0 || (g1 && tab)) && (!loc || m <= 0xffffffffull), scalars, m);   // (loc: the items of the failing blocks are 32-bit indices)
+    int rc = rlc_check_args(is_one && seg_off && (np == 0 || (g1 && tab)) && (!loc.on || m <= 0xffffffffull), scalars, m);   // (the items of the failing blocks are 32-bit indices)
     if (rc) return rc;
-    blsmi_route::PprodRlcPlan pl;
-    blsmi_route::PprodLocatePlan lp;
-    const std::vector<uint32_t>& entry_of = loc ? lp.entry_of : pl.entry_of;
-    std::vector<uint8_t> packed;
+    PprodPlans plans; std::vector<uint8_t> packed;
     const size_t qb = rec_bytes(192, jac);
     try {
-        if (!(loc ? blsmi_route::pprod_locate_plan(seg_off, m, q_idx, np, nq, loc->block ? loc->block : blsmi_route::pprod_locate_auto_block(m), lp)
-                  : blsmi_route::pprod_rlc_plan(seg_off, m, q_idx, np, nq, pl))) return BLSMI_E_ARG;
+        if (!plans.build(seg_off, m, q_idx, np, nq, true, loc)) return BLSMI_E_ARG;
         if (q_idx) {                                                       // only the entries some pair refers to travel, already in group order
+            const std::vector<uint32_t>& entry_of = plans.entry_of();
             packed.resize(qb * entry_of.size());
             for (size_t c = 0; c < entry_of.size(); c++) memcpy(packed.data() + qb * c, tab + qb * entry_of[c], qb);
         }
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    if (np == 0) { memset(is_one, 1, m); if (combined) *combined = 1; return BLSMI_OK; }
-    RlcHostScratch hs;
-    uint8_t* none = nullptr;
+    if (np == 0) { memset(is_one, 1, m); pprod_report(combined, loc, true, 0); return BLSMI_OK; }
+    RlcHostScratch hs; uint8_t* none = nullptr;
     rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
     LOCK_AND_INIT();
     hipStream_t s = g_stream;
+    const size_t dg = plans.entry_of().size();
     DBuf a, t, fl, dok;
-    HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(t.alloc((size_t)192 * entry_of.size())); HIPCHK(fl.alloc(np)); HIPCHK(dok.alloc(m));
+    HIPCHK(a.alloc((size_t)96 * np)); HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(fl.alloc(np)); HIPCHK(dok.alloc(m));
     rc = upload_points(group_kernels(1), jac, g1, a.p, np, s); if (rc) return rc;
-    rc = upload_points(group_kernels(2), jac, q_idx ? packed.data() : tab, t.p, entry_of.size(), s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, q_idx ? packed.data() : tab, t.p, dg, s); if (rc) return rc;
     if (inf_flags && !jac) HIPCHK(hipMemcpyAsync(fl.p, inf_flags, np, hipMemcpyHostToDevice, s));
-    bool held = false;
+    bool held = false; size_t nre = 0;
     const PprodRlcIn in{a.as<u8>(), true, (inf_flags && !jac) ? fl.as<u8>() : nullptr, t.as<u8>(), scalars, seg_off, np, m};
-    size_t nre = 0;
-    rc = loc ? pprod_locate_core(in, lp, dok.p, &held, &nre) : pprod_rlc_core(in, pl, dok.p, &held); if (rc) return rc;
+    rc = plans.run(in, dok.p, &held, &nre); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(is_one, dok.p, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (combined) *combined = held ? 1 : 0;
-    if (loc && loc->rechecked) *loc->rechecked = nre;
+    pprod_report(combined, loc, held, nre);
     return BLSMI_OK;
 }
 // the _dev forms: seg_off and q_idx come back once for the plans; the table entries referred to are gathered; the caller's buffers stay untouched.
 // split == false: every group through the segmented sum (blsmi_debug_pairing_product_batch_rlc_dev_nosplit).
 int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m,
-                      const uint64_t* scalars, void* d_is_one, int* combined, void* stream, bool jac, bool split = true, const PprodLocate* loc = nullptr) {
-    if (combined) *combined = 0;
-    if (loc && loc->rechecked) *loc->rechecked = 0;
+                      const uint64_t* scalars, void* d_is_one, int* combined, void* stream, bool jac, bool split = true, const PprodLocate& loc = {}) {
+    pprod_report(combined, loc, false, 0);
     if (m == 0) return BLSMI_OK;
-    int rc = rlc_check_args(d_is_one && d_seg_off && (np == 0 || (d_g1 && d_tab)) && (d_q_idx || nq == np) && np <= 0xffffffffull && (!loc || m <= 0xffffffffull), scalars, m);
+    int rc = rlc_check_args(d_is_one && d_seg_off && (np == 0 || (d_g1 && d_tab)) && (d_q_idx || nq == np) && np <= 0xffffffffull && (!loc.on || m <= 0xffffffffull), scalars, m);
     if (rc) return rc;
-    RlcHostScratch hs;
-    uint8_t* none = nullptr;
+    RlcHostScratch hs; uint8_t* none = nullptr;
     rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
     LOCK_AND_INIT_AT(d_is_one);
     UseStream us(stream);
     hipStream_t s = g_stream;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> qi;
+    std::vector<uint64_t> off; std::vector<uint32_t> qi;
     if (d_q_idx && np) {
         try { qi.resize(np); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
         HIPCHK(hipMemcpyAsync(qi.data(), d_q_idx, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, s));
     }
     rc = segsum_fetch_offsets(d_seg_off, m, off); if (rc) return rc;       // (synchronises: q_idx is here as well)
-    blsmi_route::PprodRlcPlan pl;
-    blsmi_route::PprodLocatePlan lp;
-    const std::vector<uint32_t>& entry_of = loc ? lp.entry_of : pl.entry_of;
+    PprodPlans plans;
     try {
-        if (!(loc ? blsmi_route::pprod_locate_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, loc->block ? loc->block : blsmi_route::pprod_locate_auto_block(m), lp)
-                  : blsmi_route::pprod_rlc_plan(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, pl, split))) return BLSMI_E_ARG;
+        if (!plans.build(off.data(), m, d_q_idx ? qi.data() : nullptr, np, nq, split, loc)) return BLSMI_E_ARG;
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
-    bool held = true;
-    size_t nre = 0;
+    bool held = true; size_t nre = 0;
     if (np == 0) { HIPCHK(hipMemsetAsync(d_is_one, 1, m, s)); HIPCHK(hipStreamSynchronize(s)); }
     else {
+        const std::vector<uint32_t>& entry_of = plans.entry_of();
         const size_t dg = entry_of.size();
         DBuf a, t, tj, dent;
         HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
@@ -1223,55 +1237,39 @@ int pprod_rlc_dev_api(const void* d_g1, const void* d_inf_flags, const void* d_t
             g1 = a.as<u8>();
         } else launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, d_tab, dent.p, t.p, 48, dg);
         const PprodRlcIn in{g1, jac, jac ? nullptr : (const u8*)d_inf_flags, t.as<u8>(), scalars, off.data(), np, m};
-        rc = loc ? pprod_locate_core(in, lp, d_is_one, &held, &nre) : pprod_rlc_core(in, pl, d_is_one, &held); if (rc) return rc;
+        rc = plans.run(in, d_is_one, &held, &nre); if (rc) return rc;
     }
-    if (combined) *combined = held ? 1 : 0;
-    if (loc && loc->rechecked) *loc->rechecked = nre;
+    pprod_report(combined, loc, held, nre);
     return BLSMI_OK;
 }
 }  // namespace
-BLSMI_API int blsmi_pairing_product_batch_rlc(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np,
-                                              const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
+BLSMI_API int blsmi_pairing_product_batch_rlc(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
     return pprod_rlc_host(g1_aff, inf_flags, g2_tab, nq, q_idx, np, seg_off, m, scalars, is_one, combined, false);
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np,
-                                                  const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
+BLSMI_API int blsmi_pairing_product_batch_rlc_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m, const uint64_t* scalars, uint8_t* is_one, int* combined) {
     return pprod_rlc_host(reinterpret_cast<const uint8_t*>(g1_jac), nullptr, reinterpret_cast<const uint8_t*>(g2_tab_jac), nq, q_idx, np, seg_off, m, scalars, is_one, combined, true);
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
-                                                  const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+BLSMI_API int blsmi_pairing_product_batch_rlc_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
     return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false);
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np,
-                                                      const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+BLSMI_API int blsmi_pairing_product_batch_rlc_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
     return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true);
 }
 // blsmi_pairing_product_batch_rlc_dev with the singleton groups sent through the weighted segmented sum as well: the other side of the
 // by-pass's criterion, kept so that tools/pprod_rlc_bench.py can measure it again
-BLSMI_API int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
-                                                                const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
+BLSMI_API int blsmi_debug_pairing_product_batch_rlc_dev_nosplit(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, void* d_is_one, int* combined, void* stream) {
     return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, false);
 }
 // the block-locating forms (blsmi 0.18): pprod_locate_core in place of pprod_rlc_core
-BLSMI_API int blsmi_pairing_product_batch_rlc_locate(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np,
-                                                     const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
-    const PprodLocate loc{block, rechecked};
-    return pprod_rlc_host(g1_aff, inf_flags, g2_tab, nq, q_idx, np, seg_off, m, scalars, is_one, combined, false, &loc);
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate(const uint8_t* g1_aff, const uint8_t* inf_flags, const uint8_t* g2_tab, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
+    return pprod_rlc_host(g1_aff, inf_flags, g2_tab, nq, q_idx, np, seg_off, m, scalars, is_one, combined, false, {true, block, rechecked});
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np,
-                                                         const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
-    const PprodLocate loc{block, rechecked};
-    return pprod_rlc_host(reinterpret_cast<const uint8_t*>(g1_jac), nullptr, reinterpret_cast<const uint8_t*>(g2_tab_jac), nq, q_idx, np, seg_off, m, scalars, is_one, combined, true, &loc);
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac(const uint64_t* g1_jac, const uint64_t* g2_tab_jac, size_t nq, const uint32_t* q_idx, size_t np, const uint64_t* seg_off, size_t m, const uint64_t* scalars, size_t block, uint8_t* is_one, int* combined, size_t* rechecked) {
+    return pprod_rlc_host(reinterpret_cast<const uint8_t*>(g1_jac), nullptr, reinterpret_cast<const uint8_t*>(g2_tab_jac), nq, q_idx, np, seg_off, m, scalars, is_one, combined, true, {true, block, rechecked});
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_locate_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np,
-                                                         const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked,
-                                                         void* stream) {
-    const PprodLocate loc{block, rechecked};
-    return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, true, &loc);
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_dev(const void* d_g1_aff, const void* d_inf_flags, const void* d_g2_tab, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked, void* stream) {
+    return pprod_rlc_dev_api(d_g1_aff, d_inf_flags, d_g2_tab, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, false, true, {true, block, rechecked});
 }
-BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np,
-                                                             const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked,
-                                                             void* stream) {
-    const PprodLocate loc{block, rechecked};
-    return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true, true, &loc);
+BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked, void* stream) {
+    return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true, true, {true, block, rechecked});
 }

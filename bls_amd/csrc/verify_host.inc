@@ -2176,11 +2176,9 @@ int pprod_dev(u8* d_g1, u8* d_g2, const u8* d_flags, size_t np, const SegPlan& p
     HIPCHK(hipStreamSynchronize(s));
     return BLSMI_OK;
 }
-// the offsets of a product: from 0, non-decreasing, ending at np
+// the offsets of a product: from 0, non-decreasing, ending at np (pprod_rlc_plan.h has the rule; a null pointer fails it)
 int pprod_check(const uint64_t* seg_off, size_t m, size_t np) {
-    if (!seg_off || seg_off[0] != 0) return BLSMI_E_ARG;
-    for (size_t j = 0; j < m; j++) if (seg_off[j + 1] < seg_off[j]) return BLSMI_E_ARG;
-    return seg_off[m] == np ? BLSMI_OK : BLSMI_E_ARG;
+    return blsmi_route::pprod_rlc_offsets_valid(seg_off, m, np) ? BLSMI_OK : BLSMI_E_ARG;
 }
 int pprod_host(const uint8_t* g1, const uint8_t* g2, const uint8_t* inf_flags, size_t np, const uint64_t* seg_off, size_t m, uint64_t* out_fq12, uint8_t* is_one, bool jac) {
     if (m == 0) return BLSMI_OK;

@@ -1191,9 +1191,11 @@ ARGTYPES_0_11 = {
 }
 
 
-def _fn_0_11(name):
+def _fn(name):
+    """the entry point `name` of 0.11 and later, with the argument types its ARGTYPES_0_NN table (here and below) gives it"""
+    tables = (ARGTYPES_0_11, ARGTYPES_0_12, ARGTYPES_0_13, ARGTYPES_0_14, ARGTYPES_0_15, ARGTYPES_0_16, ARGTYPES_0_17, ARGTYPES_0_18)
     fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_11[name]
+    fn.argtypes = next(t[name] for t in tables if name in t)
     fn.restype = C.c_int
     return fn
 
@@ -1237,7 +1239,7 @@ def _verify_batch_rlc_grouped(name, kind, jac, msgs, msg_idx, pks, sigs, inf_fla
     n = len(msg_idx)
     ix, pix = _msg_idx(msg_idx, n)
     head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
-    _check(_fn_0_11(name)(*head, len(msgs), pix, *mid, pr, _p8(ok), _p8(bitmap), n, C.byref(comb)), name[len("blsmi_"):])
+    _check(_fn(name)(*head, len(msgs), pix, *mid, pr, _p8(ok), _p8(bitmap), n, C.byref(comb)), name[len("blsmi_"):])
     return ok.astype(bool), bitmap, comb.value
 
 
@@ -1268,7 +1270,7 @@ def g1pubs_verify_with_domain_batch_rlc_grouped_jac(msgs32, domain8, msg_idx, pk
     return _verify_batch_rlc_grouped("blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac", 2, True, msgs32, msg_idx, pks, sigs, None, scalars, domain8)
 
 
-def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf, fn_of=None):
+def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf):
     so, pidx, _keep = _seg_args(idx, seg_off)
     m = so.size - 1
     p = _u8(pts, pb * npk) if npk else np.zeros(1, np.uint8)
@@ -1276,7 +1278,7 @@ def _sum_segmented_u64(name, pb, pts, npk, scalars, idx, seg_off, in_inf, fn_of=
     f = _u8(in_inf, npk) if in_inf is not None else None
     out = np.zeros(max(1, pb * m), dtype=np.uint8)
     oinf = np.zeros(max(1, m), dtype=np.uint8)
-    _check((fn_of or _fn_0_11)(name)(_p8(p), _p8(f), npk, pr if npk else None, pidx, so.ctypes.data_as(_u64p), m, _p8(out), _p8(oinf)), name[len("blsmi_"):])
+    _check(_fn(name)(_p8(p), _p8(f), npk, pr if npk else None, pidx, so.ctypes.data_as(_u64p), m, _p8(out), _p8(oinf)), name[len("blsmi_"):])
     return out[:pb * m].tobytes(), oinf[:m].copy()
 
 
@@ -1368,10 +1370,7 @@ def _verify_batch_rlc_locate(name, kind, jac, msgs, pks, sigs, inf_flags, scalar
         raise ValueError("block must not be negative")
     head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
     rechecked = C.c_size_t(0)
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_12[name]
-    fn.restype = C.c_int
-    _check(fn(*head, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
+    _check(_fn(name)(*head, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
     return ok.astype(bool), bitmap, comb.value, rechecked.value
 
 
@@ -1424,10 +1423,7 @@ def _verify_batch_rlc_grouped_locate(name, kind, jac, msgs, msg_idx, pks, sigs, 
     ix, pix = _msg_idx(msg_idx, n)
     head, mid, pr, ok, bitmap, comb, _keep = _rlc_marshal(kind, jac, msgs, n, pks, sigs, inf_flags, scalars, domain8)
     rechecked = C.c_size_t(0)
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_13[name]
-    fn.restype = C.c_int
-    _check(fn(*head, len(msgs), pix, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
+    _check(_fn(name)(*head, len(msgs), pix, *mid, pr, block, _p8(ok), _p8(bitmap), n, C.byref(comb), C.byref(rechecked)), name[len("blsmi_"):])
     return ok.astype(bool), bitmap, comb.value, rechecked.value
 
 
@@ -1473,18 +1469,11 @@ ARGTYPES_0_14 = {
 }
 
 
-def _fn_0_14(name):
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_14[name]
-    fn.restype = C.c_int
-    return fn
-
-
 def _check_batch(name, pb, pts, n, in_inf, check):
     a = _u8(pts, pb * n) if n else np.zeros(1, np.uint8)
     f = _u8(in_inf, n) if in_inf is not None else None
     status = np.zeros(max(1, n), dtype=np.uint8)
-    _check(_fn_0_14(name)(_p8(a), _p8(f), int(check), _p8(status), n), name[len("blsmi_"):])
+    _check(_fn(name)(_p8(a), _p8(f), int(check), _p8(status), n), name[len("blsmi_"):])
     return status[:n].copy()
 
 
@@ -1501,7 +1490,7 @@ def g2_check_batch(pts, n, in_inf=None, check=1):
 def _check_batch_jac(name, jb, jac, n, check):
     a, pa = _j64(jac, jb * n)
     status = np.zeros(max(1, n), dtype=np.uint8)
-    _check(_fn_0_14(name)(pa, int(check), _p8(status), n), name[len("blsmi_"):])
+    _check(_fn(name)(pa, int(check), _p8(status), n), name[len("blsmi_"):])
     return status[:n].copy()
 
 
@@ -1520,7 +1509,7 @@ def check_batch_dev(group, d_pts, d_in_inf, n, d_status, jac=False, check=1, str
     if jac and d_in_inf:
         raise ValueError("the in-memory form takes no flags: z == 0 is infinity")
     name = "blsmi_g1_check_batch_dev" if group == "g1" else "blsmi_g2_check_batch_dev"
-    _check(_fn_0_14(name)(d_pts or 0, d_in_inf or 0, int(bool(jac)), int(check), d_status or 0, n, stream or 0), name[len("blsmi_"):])
+    _check(_fn(name)(d_pts or 0, d_in_inf or 0, int(bool(jac)), int(check), d_status or 0, n, stream or 0), name[len("blsmi_"):])
 
 
 # ---- the wire format <-> in-memory points (blsmi 0.15) -----------------------------------------------------------------------------------
@@ -1537,19 +1526,12 @@ ARGTYPES_0_15 = {
 }
 
 
-def _fn_0_15(name):
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_15[name]
-    fn.restype = C.c_int
-    return fn
-
-
 def _decompress_jac(name, ib, jb, data, n, check):
     a = _u8(data, ib * n) if n else np.zeros(1, np.uint8)
     out = np.zeros(max(1, n) * jb, dtype=np.uint8)
     inf = np.zeros(max(1, n), dtype=np.uint8)
     err = np.zeros(max(1, n), dtype=np.uint8)
-    _check(_fn_0_15(name)(_p8(a), int(check), out.ctypes.data_as(_u64p), _p8(inf), _p8(err), n), name[len("blsmi_"):])
+    _check(_fn(name)(_p8(a), int(check), out.ctypes.data_as(_u64p), _p8(inf), _p8(err), n), name[len("blsmi_"):])
     return out[:n * jb].reshape(n, jb), inf[:n].astype(bool), err[:n].copy()
 
 
@@ -1566,7 +1548,7 @@ def g2_decompress_batch_jac(data, n, check_subgroup=True):
 def _compress_jac(name, jb, ob, jac, n):
     a, pa = _j64(jac, jb * n)
     out = np.zeros((max(1, n), ob), dtype=np.uint8)
-    _check(_fn_0_15(name)(pa, _p8(out.reshape(-1)), n), name[len("blsmi_"):])
+    _check(_fn(name)(pa, _p8(out.reshape(-1)), n), name[len("blsmi_"):])
     return out[:n]
 
 
@@ -1582,12 +1564,12 @@ def g2_compress_batch_jac(jac, n):
 def decompress_batch_jac_dev(group, d_in, n, d_out_jac, d_out_inf, d_err, check_subgroup=True, stream=0):
     """device-pointer form (ints; d_out_inf may be 0): the records, flags and codes are in the caller's buffers when the call returns"""
     name = "blsmi_g1_decompress_batch_jac_dev" if group == "g1" else "blsmi_g2_decompress_batch_jac_dev"
-    _check(_fn_0_15(name)(d_in or 0, int(check_subgroup), d_out_jac or 0, d_out_inf or 0, d_err or 0, n, stream or 0), name[len("blsmi_"):])
+    _check(_fn(name)(d_in or 0, int(check_subgroup), d_out_jac or 0, d_out_inf or 0, d_err or 0, n, stream or 0), name[len("blsmi_"):])
 
 
 def compress_batch_jac_dev(group, d_pts_jac, n, d_out, stream=0):
     name = "blsmi_g1_compress_batch_jac_dev" if group == "g1" else "blsmi_g2_compress_batch_jac_dev"
-    _check(_fn_0_15(name)(d_pts_jac or 0, d_out or 0, n, stream or 0), name[len("blsmi_"):])
+    _check(_fn(name)(d_pts_jac or 0, d_out or 0, n, stream or 0), name[len("blsmi_"):])
 
 
 # ---- committee aggregates, randomised (blsmi 0.16): many VerifyAggregateCommon under one pairing equation -----------------------------
@@ -1610,13 +1592,6 @@ ARGTYPES_0_16 = {
     "blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev": _A_DEV,
     "blsmi_debug_g2_sum_segmented_u64_pair": _SUM_U64,
 }
-
-
-def _fn_0_16(name):
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_16[name]
-    fn.restype = C.c_int
-    return fn
 
 
 def _agg_common_batch_rlc(name, kind, jac, msgs, msg_idx, pks, npk, idx, seg_off, sigs, scalars, domain8=None):
@@ -1644,7 +1619,7 @@ def _agg_common_batch_rlc(name, kind, jac, msgs, msg_idx, pks, npk, idx, seg_off
     ok = np.zeros(max(1, m), dtype=np.uint8)
     bitmap = np.zeros(max(1, (m + 7) // 8), dtype=np.uint8)
     comb = C.c_int(0)
-    _check(_fn_0_16(name)(*head, len(msgs), pix, pp, npk, pidx, so.ctypes.data_as(_u64p), ps, pr, _p8(ok), _p8(bitmap), m, C.byref(comb)), name[len("blsmi_"):])
+    _check(_fn(name)(*head, len(msgs), pix, pp, npk, pidx, so.ctypes.data_as(_u64p), ps, pr, _p8(ok), _p8(bitmap), m, C.byref(comb)), name[len("blsmi_"):])
     return ok[:m].astype(bool), bitmap[:(m + 7) // 8].copy(), comb.value
 
 
@@ -1683,14 +1658,14 @@ def verify_aggregate_common_batch_rlc_dev(group, d_msgs, d_off_or_domain, d, d_m
         ("blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc_dev" if domain else "blsmi_g1pubs_verify_aggregate_common_batch_rlc_dev")
     r, pr = _scalars(scalars, m)
     comb = C.c_int(0)
-    _check(_fn_0_16(name)(d_msgs or 0, d_off_or_domain or 0, d, d_msg_idx or 0, d_pks or 0, npk, d_idx or 0, d_seg_off or 0, d_sigs or 0, pr, d_ok or 0, m,
+    _check(_fn(name)(d_msgs or 0, d_off_or_domain or 0, d, d_msg_idx or 0, d_pks or 0, npk, d_idx or 0, d_seg_off or 0, d_sigs or 0, pr, d_ok or 0, m,
                           C.byref(comb), stream or 0), name[len("blsmi_"):])
     return comb.value
 
 
 def debug_g2_sum_segmented_u64_pair(pts, npk, scalars, idx, seg_off, in_inf=None):
     """g2_sum_segmented_u64 with pass 1 through the lane-pair ladder (k_g2_segsum_chunk_u64_pair), for the parity test"""
-    return _sum_segmented_u64("blsmi_debug_g2_sum_segmented_u64_pair", 192, pts, npk, scalars, idx, seg_off, in_inf, _fn_0_16)
+    return _sum_segmented_u64("blsmi_debug_g2_sum_segmented_u64_pair", 192, pts, npk, scalars, idx, seg_off, in_inf)
 
 
 # ---- pairing products, randomised (blsmi 0.17): one equation for a batch of pairing products over a table of G2 points -------------
@@ -1704,13 +1679,6 @@ ARGTYPES_0_17 = {
     "blsmi_pairing_product_batch_rlc_jac_dev": [_V, _V, C.c_size_t, _V] + _P_DEV_TAIL,
     "blsmi_debug_pairing_product_batch_rlc_dev_nosplit": [_V, _V, _V, C.c_size_t, _V] + _P_DEV_TAIL,
 }
-
-
-def _fn_0_17(name):
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_17[name]
-    fn.restype = C.c_int
-    return fn
 
 
 def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars, block=None):
@@ -1733,7 +1701,7 @@ def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars, block=
     r, pr = _scalars(scalars, m)
     one = np.zeros(max(1, m), dtype=np.uint8)
     comb, nre = C.c_int(0), C.c_size_t(0)
-    fn = _fn_0_17(name) if block is None else _fn_0_18(name)
+    fn = _fn(name)
     tail = (pr, _p8(one), C.byref(comb)) if block is None else (pr, block, _p8(one), C.byref(comb), C.byref(nre))
     if jac:
         (a, pa), (t, pt) = _j64(a, pb * n), _j64(t, qb * nq)
@@ -1743,6 +1711,16 @@ def _pprod_rlc(name, jac, g1, g2_tab, q_idx, seg_off, inf_flags, scalars, block=
         rc = fn(_p8(a), _p8(f), _p8(t), nq, pix, n, so.ctypes.data_as(_u64p), m, *tail)
     _check(rc, name[len("blsmi_"):])
     return (one[:m].copy(), comb.value) if block is None else (one[:m].copy(), comb.value, nre.value)
+
+
+def _pprod_rlc_dev(name, points, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream, block=None):
+    """the device-pointer forms; points: (d_g1, d_inf_flags, d_g2_tab) or, for in-memory points, (d_g1_jac, d_g2_tab_jac).  block None: the
+    forms of 0.17 -> combined; the caller's `block`: those of 0.18 -> (combined, rechecked)"""
+    r, pr = _scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    out = (d_is_one or 0, C.byref(comb)) if block is None else (_block(block), d_is_one or 0, C.byref(comb), C.byref(nre))
+    _check(_fn(name)(*(p or 0 for p in points), nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, *out, stream or 0), name[len("blsmi_"):])
+    return comb.value if block is None else (comb.value, nre.value)
 
 
 def pairing_product_batch_rlc(g1_aff, g2_tab, q_idx, seg_off, inf_flags=None, scalars=None):
@@ -1762,20 +1740,12 @@ def pairing_product_batch_rlc_dev(d_g1, d_g2_tab, nq, d_q_idx, np_, d_seg_off, m
     """device-pointer form (ints) over affine records; the m verdict bytes are in d_is_one when the call returns; scalars stay on the host.
     nosplit: blsmi_debug_pairing_product_batch_rlc_dev_nosplit (the measurement of the singleton by-pass).  -> combined"""
     name = "blsmi_debug_pairing_product_batch_rlc_dev_nosplit" if nosplit else "blsmi_pairing_product_batch_rlc_dev"
-    r, pr = _scalars(scalars, m)
-    comb = C.c_int(0)
-    _check(_fn_0_17(name)(d_g1 or 0, d_inf_flags or 0, d_g2_tab or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, d_is_one or 0, C.byref(comb), stream or 0),
-           name[len("blsmi_"):])
-    return comb.value
+    return _pprod_rlc_dev(name, (d_g1, d_inf_flags, d_g2_tab), nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream)
 
 
 def pairing_product_batch_rlc_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars=None, stream=0):
     """device-pointer form over in-memory points (no flags: z == 0 is infinity) -> combined"""
-    name = "blsmi_pairing_product_batch_rlc_jac_dev"
-    r, pr = _scalars(scalars, m)
-    comb = C.c_int(0)
-    _check(_fn_0_17(name)(d_g1_jac or 0, d_g2_tab_jac or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, d_is_one or 0, C.byref(comb), stream or 0), name[len("blsmi_"):])
-    return comb.value
+    return _pprod_rlc_dev("blsmi_pairing_product_batch_rlc_jac_dev", (d_g1_jac, d_g2_tab_jac), nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream)
 
 
 # ---- pairing products, randomised, that find the bad items by blocks (blsmi 0.18) ---------------------------------------------------
@@ -1788,13 +1758,6 @@ ARGTYPES_0_18 = {
     "blsmi_pairing_product_batch_rlc_locate_dev": [_V, _V, _V, C.c_size_t, _V] + _PL_DEV_TAIL,
     "blsmi_pairing_product_batch_rlc_locate_jac_dev": [_V, _V, C.c_size_t, _V] + _PL_DEV_TAIL,
 }
-
-
-def _fn_0_18(name):
-    fn = getattr(_lib(), name)
-    fn.argtypes = ARGTYPES_0_18[name]
-    fn.restype = C.c_int
-    return fn
 
 
 def _block(block):
@@ -1819,19 +1782,9 @@ def pairing_product_batch_rlc_locate_jac(g1_jac, g2_tab_jac, q_idx, seg_off, sca
 def pairing_product_batch_rlc_locate_dev(d_g1, d_g2_tab, nq, d_q_idx, np_, d_seg_off, m, d_is_one, d_inf_flags=0, scalars=None, block=0, stream=0):
     """device-pointer form (ints) over affine records; the m verdict bytes are in d_is_one when the call returns; scalars stay on the host.
     -> (combined, rechecked)"""
-    name = "blsmi_pairing_product_batch_rlc_locate_dev"
-    r, pr = _scalars(scalars, m)
-    comb, nre = C.c_int(0), C.c_size_t(0)
-    _check(_fn_0_18(name)(d_g1 or 0, d_inf_flags or 0, d_g2_tab or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, _block(block), d_is_one or 0, C.byref(comb), C.byref(nre),
-                          stream or 0), name[len("blsmi_"):])
-    return comb.value, nre.value
+    return _pprod_rlc_dev("blsmi_pairing_product_batch_rlc_locate_dev", (d_g1, d_inf_flags, d_g2_tab), nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream, block)
 
 
 def pairing_product_batch_rlc_locate_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars=None, block=0, stream=0):
     """device-pointer form over in-memory points (no flags: z == 0 is infinity) -> (combined, rechecked)"""
-    name = "blsmi_pairing_product_batch_rlc_locate_jac_dev"
-    r, pr = _scalars(scalars, m)
-    comb, nre = C.c_int(0), C.c_size_t(0)
-    _check(_fn_0_18(name)(d_g1_jac or 0, d_g2_tab_jac or 0, nq, d_q_idx or 0, np_, d_seg_off or 0, m, pr, _block(block), d_is_one or 0, C.byref(comb), C.byref(nre), stream or 0),
-           name[len("blsmi_"):])
-    return comb.value, nre.value
+    return _pprod_rlc_dev("blsmi_pairing_product_batch_rlc_locate_jac_dev", (d_g1_jac, d_g2_tab_jac), nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream, block)
