@@ -68,6 +68,11 @@ __global__ void k_gather_bytes(const u8* src, const u32* idx, u8* dst, size_t n)
 __global__ void k_scatter_bytes(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_pprod_rlc_weights(const u8* g1, const u8* in_flags, const uint4* tab, const u32* group_of, const u32* item_of, const u64* r, u64* w, u8* pflag, size_t np);
 __global__ void k_pprod_cell_route(const uint4* sums, const u8* s_inf, const uint4* tab, const u32* sum_of, const u32* entry_at, const uint4* gen1, const uint4* gen2, uint4* g1, uint4* g2, u8* skip, size_t nc, size_t ne);
+// k_fr.hip
+__global__ void k_fr_wsum_u64(const u8* vals, size_t ncol, const u64* w, const u64* ch_lo, const u32* ch_cnt, u32* part, size_t nch);
+__global__ void k_fr_wsum_fold(const u32* part, const u64* seg_ch, size_t cols, u8* out, size_t nout);
+__global__ void k_g2_neg_records(const u8* src, const u32* idx, u8* dst, size_t n);
+__global__ void k_groth16_recheck_pairs(const uint4* proofs, const uint4* alpha, const uint4* L, const u8* L_inf, const uint4* tab, const u32* items, size_t m, uint4* g1, uint4* g2, u8* flags, size_t nre);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);
@@ -143,8 +148,8 @@ __global__ void k_mul_finish(const u8* good, const u8* pts, size_t pt_stride, in
 __global__ void k_g1_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);
 __global__ void k_g1_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
-__global__ void k_g1_mul_u64_idx(const u8* pts, const u8* flags, const u64* scalars, const u32* idx, u8* out, u8* out_inf, size_t n);
 __global__ void k_g2_mul_u64(const u8* pts, const u64* scalars, u8* out, u8* out_inf, size_t n);
+__global__ void k_g1_mul_u64_idx(const u8* pts, const u8* flags, const u64* scalars, const u32* idx, u8* out, u8* out_inf, size_t n);
 __global__ void k_scalar_u64_to_be32(const u64* r, u8* out, size_t n);
 __global__ void k_glv_recode(const u8* scalars, int group, u8* rec, size_t n);
 __global__ void k_g1_mul_glv(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n);

@@ -93,6 +93,23 @@ inline bool pprod_locate_plan(const uint64_t* seg_off, size_t m, const uint32_t*
     return true;
 }
 
+// x further cells behind the own cells of EVERY block, whose sums the weighted sums do not make (blsmi 0.19: a Groth16 batch's alpha and
+// gamma cells, folded in the scalar field): cell i of block b takes sum index C + i * B + b, C the cells before the call, and compacted
+// entry d' + i, where entries[i] joins entry_of.  The pairs, their permutation and the one-pair list stay as they are.
+inline void pprod_locate_append_cells(PprodLocatePlan& p, const uint32_t* entries, size_t x) {
+    const size_t B = p.blocks(), C = p.cells(), dg = p.entry_of.size();
+    std::vector<uint32_t> sum_of, entry_at;
+    std::vector<uint64_t> slot_off(1, 0);
+    sum_of.reserve(C + x * B); entry_at.reserve(C + x * B); slot_off.reserve(B + 1);
+    for (size_t b = 0; b < B; b++) {
+        for (uint64_t s = p.slot_off[b]; s < p.slot_off[b + 1]; s++) { sum_of.push_back(p.sum_of[s]); entry_at.push_back(p.entry_at[s]); }
+        for (size_t i = 0; i < x; i++) { sum_of.push_back((uint32_t)(C + i * B + b)); entry_at.push_back((uint32_t)(dg + i)); }
+        slot_off.push_back(sum_of.size());
+    }
+    p.entry_of.insert(p.entry_of.end(), entries, entries + x);
+    p.sum_of.swap(sum_of); p.entry_at.swap(entry_at); p.slot_off.swap(slot_off);
+}
+
 // What the recheck of the failing blocks reads, given one byte per block (not zero: the block's value was not one), everything ascending:
 struct PprodLocateFailing {
     std::vector<uint32_t> items;      // the items of the failing blocks: where the dense verdicts are scattered to

@@ -1,5 +1,6 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
-// ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*,
+// blsmi_fr_wsum_segmented_u64* and blsmi_groth16_verify_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -963,9 +964,10 @@ struct PprodRlcIn {
 };
 // What the weighted sums read of a plan, whichever form made it.  A SEGMENT is what gets one sum and one Miller loop -- a compacted group
 // of 0.17, a cell of 0.18 -- the multi-pair ones as segments of a permutation of their pairs, the one-pair ones as a list of pairs.
-struct PprodSegments { const uint32_t *item_of, *group_of, *perm, *single; const uint64_t* multi_off; size_t multi, nperm, nsingle; };   // multi_off: multi + 1 offsets into perm
+struct PprodSegments { const uint32_t *item_of, *group_of, *perm, *single; const uint64_t* multi_off; size_t multi, nperm, nsingle, extra; };   // multi_off: multi + 1 offsets into perm
+// (extra: sums the weighted sums do not make -- room for them behind their own in S and sinf, filled by the driver before the stage that reads them)
 // (of a PprodRlcPlan with its seg_off, of a PprodLocatePlan with its cell_off)
-template <class Plan> PprodSegments pprod_segments(const Plan& p, const std::vector<uint64_t>& off) { return {p.item_of.data(), p.group_of.data(), p.perm.data(), p.single.data(), off.data(), off.size() - 1, p.perm.size(), p.single.size()}; }
+template <class Plan> PprodSegments pprod_segments(const Plan& p, const std::vector<uint64_t>& off, size_t extra = 0) { return {p.item_of.data(), p.group_of.data(), p.perm.data(), p.single.data(), off.data(), off.size() - 1, p.perm.size(), p.single.size(), extra}; }
 // What one such check keeps for the length of its call, the counterpart of RlcCall.  On the device: the scalars, the pairs' weights and flag
 // bytes, the plan's arrays, the segments' sums S with their infinity flags, the total's one-segment plan, product, final exponentiation and
 // verdict.  On the host: the two chunk plans, whose blobs the uploads read, and the verdict byte the last copy targets.  The rule written at
@@ -988,7 +990,7 @@ int pprod_weighted_sums(PprodCall& c, const PprodRlcIn& in, const PprodSegments&
     c.fe = pprod_fe_layout(1, load);
     HIPCHK(c.dr.alloc(sizeof(uint64_t) * in.m)); HIPCHK(c.dw.alloc(sizeof(uint64_t) * np)); HIPCHK(c.pflag.alloc(np)); HIPCHK(c.dgo.alloc(sizeof(uint32_t) * np));
     HIPCHK(c.dio.alloc(sizeof(uint32_t) * np)); HIPCHK(c.dperm.alloc(sizeof(uint32_t) * g.nperm)); HIPCHK(c.dsingle.alloc(sizeof(uint32_t) * g.nsingle));
-    HIPCHK(c.S.alloc((size_t)96 * nsums)); HIPCHK(c.sinf.alloc(nsums)); HIPCHK(c.oblob.alloc(c.oplan.blob.size()));
+    HIPCHK(c.S.alloc((size_t)96 * (nsums + g.extra))); HIPCHK(c.sinf.alloc(nsums + g.extra)); HIPCHK(c.oblob.alloc(c.oplan.blob.size()));
     HIPCHK(c.prod.alloc(c.fe == Layout::wave ? 576 : sizeof(i32) * 12 * NL)); HIPCHK(c.vals.alloc(576)); HIPCHK(c.one.alloc(1));
     HIPCHK(hipMemcpyAsync(c.dr.p, in.r, sizeof(uint64_t) * in.m, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c.dio.p, g.item_of, sizeof(uint32_t) * np, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(c.dgo.p, g.group_of, sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
@@ -1098,6 +1100,16 @@ int pprod_locate_failing_blocks(PprodCall& c, const blsmi_route::PprodLocatePlan
     } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
     return BLSMI_OK;
 }
+// The end of a recheck, whoever gathered the dense pairs (a, b, fl: npd of them, the call's own; iplan: the dense items over them):
+// blsmi_pairing_product_batch's own path, the verdicts okd scattered to d_is_one[d_items[.]].  Synchronises.
+int pprod_recheck_dense(u8* a, u8* b, const u8* fl, size_t npd, const SegPlan& iplan, const u32* d_items, void* okd, void* d_is_one) {
+    hipStream_t s = g_stream;
+    int rc = pprod_dev(a, b, fl, npd, iplan, nullptr, okd, s); if (rc) return rc;
+    launch(KERNEL_OF(k_scatter_bytes), nblocks(iplan.m), s, okd, d_items, d_is_one, iplan.m);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
 // Stage 3: the failing blocks' items, dense, through blsmi_pairing_product_batch's own path; their verdicts back over the ones.  Synchronises.
 int pprod_locate_recheck(PprodCall& c, const blsmi_route::PprodLocateFailing& ff, void* d_is_one) {
     const PprodRlcIn& in = c.in;
@@ -1118,11 +1130,7 @@ int pprod_locate_recheck(PprodCall& c, const blsmi_route::PprodLocateFailing& ff
         launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(npd), s, c.pflag.p, dpairs.p, fl.p, npd);
         prof_mark(nullptr);
     }
-    int rc = pprod_dev(a.as<u8>(), b.as<u8>(), fl.as<u8>(), npd, iplan, nullptr, okd.p, s); if (rc) return rc;
-    launch(KERNEL_OF(k_scatter_bytes), nblocks(nre), s, okd.p, ditems.p, d_is_one, nre);
-    prof_mark(nullptr);
-    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(s));
-    return BLSMI_OK;
+    return pprod_recheck_dense(a.as<u8>(), b.as<u8>(), fl.as<u8>(), npd, iplan, ditems.as<u32>(), okd.p, d_is_one);
 }
 // d_is_one: m verdict bytes on the device.  Synchronises.
 int pprod_locate_core(const PprodRlcIn& in, const blsmi_route::PprodLocatePlan& pl, void* d_is_one, bool* held, size_t* rechecked) {
@@ -1272,4 +1280,293 @@ BLSMI_API int blsmi_pairing_product_batch_rlc_locate_dev(const void* d_g1_aff, c
 }
 BLSMI_API int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void* d_g1_jac, const void* d_g2_tab_jac, size_t nq, const void* d_q_idx, size_t np, const void* d_seg_off, size_t m, const uint64_t* scalars, size_t block, void* d_is_one, int* combined, size_t* rechecked, void* stream) {
     return pprod_rlc_dev_api(d_g1_jac, nullptr, d_g2_tab_jac, nq, d_q_idx, np, d_seg_off, m, scalars, d_is_one, combined, stream, true, true, {true, block, rechecked});
+}
+
+// ---- arithmetic mod r: the weighted segmented fold of scalars (blsmi 0.19; include/blsmi.h "scalar-field folds") ---------------------------
+// out[s][0] = sum of the weights of segment s, out[s][1 + i] = sum_j w_j vals[j][i] mod r: k_fr_wsum_u64 over a chunk plan -- every chunk
+// the rows of one segment that one workgroup folds -- leaves twelve unreduced words per (chunk, column); k_fr_wsum_fold adds a segment's
+// chunks and reduces once per output.  Always both launches, whatever the segments' lengths: the result does not depend on the plan.
+namespace {
+struct FrWsumPlan { size_t cols = 1, ntile = 1; std::vector<uint64_t> ch_lo, seg_ch; std::vector<uint32_t> ch_cnt; };
+// Rows per chunk: sixteen steps of the workgroup's R = 256 / min(ncol + 1, 256) rows, doubled while that leaves more than 2^16 chunks.
+void fr_wsum_plan(const uint64_t* seg_off, size_t nseg, size_t ncol, FrWsumPlan& p) {
+    p.cols = ncol + 1;
+    const size_t cw = std::min<size_t>(p.cols, 256);
+    p.ntile = (p.cols + cw - 1) / cw;
+    uint64_t rows = 256 / cw * 16;
+    while (seg_off[nseg] / rows > ((uint64_t)1 << 16) && rows < ((uint64_t)1 << 28)) rows *= 2;
+    p.ch_lo.clear(); p.ch_cnt.clear(); p.seg_ch.assign(1, 0);
+    for (size_t j = 0; j < nseg; j++) {
+        for (uint64_t a = seg_off[j]; a < seg_off[j + 1]; a += rows) { p.ch_lo.push_back(a); p.ch_cnt.push_back((uint32_t)std::min<uint64_t>(rows, seg_off[j + 1] - a)); }
+        p.seg_ch.push_back(p.ch_lo.size());
+    }
+}
+// The fold on the device, on s, not synchronised; the plan stays alive until the caller has.  d_w: one weight per row; d_out: nseg * cols scalars.
+int fr_wsum_dev(const FrWsumPlan& p, const void* d_vals, size_t ncol, const void* d_w, size_t nseg, void* d_out, hipStream_t s) {
+    const size_t nch = p.ch_lo.size(), nout = nseg * p.cols;
+    if (nout == 0) return BLSMI_OK;
+    DBuf dlo, dcnt, dseg, part;
+    HIPCHK(dlo.alloc(sizeof(uint64_t) * nch)); HIPCHK(dcnt.alloc(sizeof(uint32_t) * nch)); HIPCHK(dseg.alloc(sizeof(uint64_t) * (nseg + 1)));
+    HIPCHK(part.alloc(sizeof(uint32_t) * 12 * p.cols * nch));
+    if (nch) {
+        HIPCHK(hipMemcpyAsync(dlo.p, p.ch_lo.data(), sizeof(uint64_t) * nch, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dcnt.p, p.ch_cnt.data(), sizeof(uint32_t) * nch, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(dseg.p, p.seg_ch.data(), sizeof(uint64_t) * (nseg + 1), hipMemcpyHostToDevice, s));
+    const bool mark = tl_ctx && s == tl_ctx->stream;                       // (profile marks are events on the context's main stream)
+    if (mark) prof_mark(KERNEL_OF(k_fr_wsum_u64).name);                    // one segment: both passes
+    if (nch) launch_quiet_sized(KERNEL_OF(k_fr_wsum_u64), nch * p.ntile, 256, s, d_vals, ncol, d_w, dlo.p, dcnt.p, part.p, nch);
+    launch_quiet_sized(KERNEL_OF(k_fr_wsum_fold), (nout + 255) / 256, 256, s, part.p, dseg.p, p.cols, d_out, nout);
+    if (mark) prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+// what both forms refuse: a column count or a row count beyond 32 bits (the accumulator's bound is 2^32 rows)
+bool fr_wsum_sizes_ok(size_t ncol, uint64_t n) { return ncol <= 0xffffffffull && n <= 0xffffffffull; }
+}  // namespace
+BLSMI_API int blsmi_fr_wsum_segmented_u64(const uint8_t* vals, size_t ncol, const uint64_t* weights, const uint64_t* seg_off, size_t nseg, uint8_t* out) {
+    if (nseg == 0) return BLSMI_OK;
+    if (!seg_off || !out || seg_off[0] != 0) return BLSMI_E_ARG;
+    for (size_t j = 0; j < nseg; j++) if (seg_off[j + 1] < seg_off[j]) return BLSMI_E_ARG;
+    const uint64_t n = seg_off[nseg];
+    if (!fr_wsum_sizes_ok(ncol, n) || (n && !weights) || (n && ncol && !vals)) return BLSMI_E_ARG;
+    FrWsumPlan plan;
+    try { fr_wsum_plan(seg_off, nseg, ncol, plan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    DBuf dv, dw, dout;
+    HIPCHK(dv.alloc((size_t)32 * ncol * n)); HIPCHK(dw.alloc(sizeof(uint64_t) * n)); HIPCHK(dout.alloc((size_t)32 * plan.cols * nseg));
+    if (n && ncol) HIPCHK(hipMemcpyAsync(dv.p, vals, (size_t)32 * ncol * n, hipMemcpyHostToDevice, s));
+    if (n) HIPCHK(hipMemcpyAsync(dw.p, weights, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    int rc = fr_wsum_dev(plan, dv.p, ncol, dw.p, nseg, dout.p, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)32 * plan.cols * nseg, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_fr_wsum_segmented_u64_dev(const void* d_vals, size_t ncol, const void* d_weights, const void* d_seg_off, size_t nseg, void* d_out, void* stream) {
+    if (nseg == 0) return BLSMI_OK;
+    if (!d_seg_off || !d_out || ncol > 0xffffffffull) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    std::vector<uint64_t> off;
+    int rc = segsum_fetch_offsets(d_seg_off, nseg, off); if (rc) return rc;
+    const uint64_t n = off[nseg];
+    if (!fr_wsum_sizes_ok(ncol, n) || (n && !d_weights) || (n && ncol && !d_vals)) return BLSMI_E_ARG;
+    FrWsumPlan plan;
+    try { fr_wsum_plan(off.data(), nseg, ncol, plan); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    rc = fr_wsum_dev(plan, d_vals, ncol, d_weights, nseg, d_out, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+
+// ---- Groth16 batches with the public inputs folded in Fr (blsmi 0.19; include/blsmi.h "Groth16") ----------------------------------------
+// m proofs of one circuit under the block equations of 0.18.  Item j holds when e(A_j, B_j) e(alpha, -beta) e(L_j, -gamma) e(C_j, -delta) = 1,
+// L_j = IC_0 + sum_i a_ji IC_i -- the key's three G2 points are negated once (k_g2_neg_records), no proof point is.  With the weights r_j,
+//     sum_j r_j L_j = t IC_0 + sum_i s_i IC_i,        t = sum_j r_j,    s_i = sum_j r_j a_ji mod r        (the sums over a block)
+// so that a block needs nin + 1 scalars from the fold above and nin + 2 full-width ladders, whatever its length.  Stages:
+//   1  the plan of 0.18 over two pairs per item, (A_j, B_j) and (C_j, -delta): the blocks' singleton cells and delta cells, and two further
+//      cells per block appended to it (pprod_locate_append_cells): alpha against -beta, the folded point against -gamma
+//   2  pprod_weighted_sums, unchanged, with room for the 2 B sums it does not make
+//   3  its own: fr_wsum_dev over the inputs with the blocks as segments; B (nin + 2) ladders over gathered key points (t_b alpha, t_b IC_0,
+//      s_bi IC_i: mul_dev_core); the alpha cells copied, the gamma cells by the segmented sum, into those places
+//   4  pprod_locate_failing_blocks, unchanged: route, Miller loops, block products, total, final exponentiation; the failing blocks
+//   5  groth16_recheck for their items only: inputs mod r (the fold again, a segment per item, weight one), the ladders and the segmented
+//      sum for L_j, the four pairs dense (k_groth16_recheck_pairs), pprod_recheck_dense.
+// One lease, one device, never in the request combiner.
+namespace {
+struct Groth16In {
+    const u8* vk_g1;         // alpha, IC_0 .. IC_nin: affine, 16-byte aligned
+    const u8* g1;            // A_j, C_j interleaved: 2 m affine records, 16-byte aligned
+    const u8* tab;           // B_0 .. B_{m - 1}, -delta, -beta, -gamma: the call's own, affine
+    const u8* inputs;        // m * nin scalars (not read when nin == 0)
+    const uint64_t* r;       // host: m nonzero scalars
+    size_t nin, m, block;    // block: resolved, >= 1
+};
+const uint32_t GROTH16_KEY_ORDER[3] = {2, 0, 1};                           // vk_g2 is beta, gamma, delta; the table's tail is -delta, -beta, -gamma
+// records i of src (idx null: the first n) as n dense records of `bytes` bytes (a multiple of 16), whatever src's alignment
+void groth16_gather(const void* src, const DBuf& idx, void* dst, size_t bytes, size_t n, hipStream_t s) {
+    if (reinterpret_cast<uintptr_t>(src) & 15) launch_quiet(KERNEL_OF(k_gather_records), nblocks(bytes / 4 * n), s, src, idx.p, dst, bytes / 4, n);
+    else launch_quiet(KERNEL_OF(k_gather_records16), nblocks(bytes / 16 * n), s, src, idx.p, dst, bytes / 16, n);
+}
+// Stage 5.  items: the proofs of the failing blocks, ascending.  Synchronises.
+int groth16_recheck(const Groth16In& in, const std::vector<uint32_t>& items, void* d_ok) {
+    const size_t nre = items.size(), cols = in.nin + 1, nl = nre * cols;
+    hipStream_t s = g_stream;
+    const GroupKernels& g = group_kernels(1);
+    std::vector<uint64_t> ones, roff, loff, ioff; std::vector<uint32_t> lp;
+    FrWsumPlan rp; SegPlan lplan, iplan;
+    try {
+        ones.assign(nre, 1); roff.resize(nre + 1); loff.resize(nre + 1); ioff.resize(nre + 1); lp.resize(nl);
+        for (size_t t = 0; t <= nre; t++) { roff[t] = t; loff[t] = t * cols; ioff[t] = 4 * t; }
+        for (size_t k = 0; k < nl; k++) lp[k] = (uint32_t)(1 + k % cols);
+        fr_wsum_plan(roff.data(), nre, in.nin, rp); segsum_plan(loff.data(), nre, segsum_chunk_of(nl), lplan); pprod_plan(ioff.data(), nre, iplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf ditems, rows, dones, rout, dlp, lpts, lout, linf, L, Linf, a, b, fl, okd;
+    HIPCHK(ditems.alloc(sizeof(uint32_t) * nre)); HIPCHK(rows.alloc((size_t)32 * in.nin * nre)); HIPCHK(dones.alloc(sizeof(uint64_t) * nre)); HIPCHK(rout.alloc((size_t)32 * nl));
+    HIPCHK(dlp.alloc(sizeof(uint32_t) * nl)); HIPCHK(lpts.alloc((size_t)96 * nl)); HIPCHK(lout.alloc((size_t)96 * nl)); HIPCHK(linf.alloc(nl));
+    HIPCHK(L.alloc((size_t)96 * nre)); HIPCHK(Linf.alloc(nre)); HIPCHK(a.alloc((size_t)96 * 4 * nre)); HIPCHK(b.alloc((size_t)192 * 4 * nre)); HIPCHK(fl.alloc(4 * nre)); HIPCHK(okd.alloc(nre));
+    HIPCHK(hipMemcpyAsync(ditems.p, items.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dones.p, ones.data(), sizeof(uint64_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dlp.p, lp.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+    prof_mark(KERNEL_OF(k_gather_records16).name);                         // one segment: the gathers
+    if (in.nin) groth16_gather(in.inputs, ditems, rows.p, (size_t)32 * in.nin, nre, s);
+    groth16_gather(in.vk_g1, dlp, lpts.p, 96, nl, s);
+    prof_mark(nullptr);
+    int rc = fr_wsum_dev(rp, rows.p, in.nin, dones.p, nre, rout.p, s); if (rc) return rc;   // every row: 1, a_1 mod r, .., a_nin mod r
+    rc = mul_dev_core(g, lpts.as<u8>(), rout.as<u8>(), lout.as<u8>(), linf.as<u8>(), nl, s); if (rc) return rc;
+    rc = segsum_dev(g, false, lout.p, linf.as<u8>(), nl, nullptr, lplan, L.as<u8>(), Linf.as<u8>(), 1, s); if (rc) return rc;
+    launch(KERNEL_OF(k_groth16_recheck_pairs), tuple_blocks(Layout::row, 4 * nre), s, in.g1, in.vk_g1, L.p, Linf.p, in.tab, ditems.p, in.m, a.p, b.p, fl.p, nre);
+    prof_mark(nullptr);
+    return pprod_recheck_dense(a.as<u8>(), b.as<u8>(), fl.as<u8>(), 4 * nre, iplan, ditems.as<u32>(), okd.p, d_ok);
+}
+// d_ok: m verdict bytes on the device.  Synchronises.
+int groth16_core(const Groth16In& in, void* d_ok, bool* held, size_t* rechecked) {
+    const size_t m = in.m, nin = in.nin, np = 2 * m, cols = nin + 1;
+    hipStream_t s = g_stream;
+    const GroupKernels& g = group_kernels(1);
+    *rechecked = 0;
+    std::vector<uint64_t> seg_off, boff, goff; std::vector<uint32_t> q_idx, lpt, lsc;
+    blsmi_route::PprodLocatePlan pl; blsmi_route::PprodLocateFailing ff;
+    FrWsumPlan fp; SegPlan gplan;
+    PprodCall c; PprodCellBufs b;
+    size_t C0 = 0, B = 0, nl = 0;
+    try {
+        seg_off.resize(m + 1); q_idx.resize(np);
+        for (size_t j = 0; j < m; j++) { seg_off[j] = 2 * j; q_idx[2 * j] = (uint32_t)j; q_idx[2 * j + 1] = (uint32_t)m; }
+        seg_off[m] = np;
+        if (!blsmi_route::pprod_locate_plan(seg_off.data(), m, q_idx.data(), np, m + 1, in.block, pl)) return BLSMI_E_ARG;   // stage 1
+        C0 = pl.cells(); B = pl.blocks(); nl = B * (nin + 2);
+        const uint32_t further[2] = {(uint32_t)(m + 1), (uint32_t)(m + 2)};
+        blsmi_route::pprod_locate_append_cells(pl, further, 2);
+        boff.resize(B + 1); goff.resize(B + 1); lpt.resize(nl); lsc.resize(nl);
+        for (size_t k = 0; k < B; k++) {
+            boff[k] = pl.item_lo(k); goff[k] = k * cols;
+            lpt[k] = 0; lsc[k] = (uint32_t)(k * cols);                     // t_b alpha
+            for (size_t i = 0; i < cols; i++) { lpt[B + k * cols + i] = (uint32_t)(1 + i); lsc[B + k * cols + i] = (uint32_t)(k * cols + i); }   // t_b IC_0, s_bi IC_i
+        }
+        boff[B] = m; goff[B] = B * cols;
+        fr_wsum_plan(boff.data(), B, nin, fp); segsum_plan(goff.data(), B, segsum_chunk_of(B * cols), gplan); pprod_plan(pl.slot_off.data(), B, b.bplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t C = pl.cells(), dg = pl.entry_of.size();
+    DBuf t, dent, fout, dlp, dls, lpts, lscal, lout, linf;
+    HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
+    HIPCHK(b.dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(b.dent.alloc(sizeof(uint32_t) * C)); HIPCHK(b.bblob.alloc(b.bplan.blob.size()));
+    HIPCHK(fout.alloc((size_t)32 * cols * B)); HIPCHK(dlp.alloc(sizeof(uint32_t) * nl)); HIPCHK(dls.alloc(sizeof(uint32_t) * nl));
+    HIPCHK(lpts.alloc((size_t)96 * nl)); HIPCHK(lscal.alloc((size_t)32 * nl)); HIPCHK(lout.alloc((size_t)96 * nl)); HIPCHK(linf.alloc(nl));
+    HIPCHK(hipMemcpyAsync(dent.p, pl.entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(b.dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.bblob.p, b.bplan.blob.data(), b.bplan.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dlp.p, lpt.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dls.p, lsc.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, in.tab, dent.p, t.p, 48, dg);   // the table in the plan's order
+    const PprodRlcIn pin{in.g1, false, nullptr, t.as<u8>(), in.r, seg_off.data(), np, m};
+    int rc = pprod_weighted_sums(c, pin, pprod_segments(pl, pl.cell_off, 2 * B), B, route_load(C)); if (rc) return rc;   // stage 2
+    rc = fr_wsum_dev(fp, in.inputs, nin, c.dr.p, B, fout.p, s); if (rc) return rc;   // stage 3
+    groth16_gather(in.vk_g1, dlp, lpts.p, 96, nl, s);
+    groth16_gather(fout.p, dls, lscal.p, 32, nl, s);
+    rc = mul_dev_core(g, lpts.as<u8>(), lscal.as<u8>(), lout.as<u8>(), linf.as<u8>(), nl, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c.S.as<u8>() + (size_t)96 * C0, lout.p, (size_t)96 * B, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c.sinf.as<u8>() + C0, linf.p, B, hipMemcpyDeviceToDevice, s));
+    rc = segsum_dev(g, false, lout.as<u8>() + (size_t)96 * B, linf.as<u8>() + B, B * cols, nullptr, gplan, c.S.as<u8>() + (size_t)96 * (C0 + B), c.sinf.as<u8>() + C0 + B, 1, s);
+    if (rc) return rc;
+    rc = pprod_locate_failing_blocks(c, pl, b, d_ok, held, ff);             // stage 4
+    if (rc || *held) return rc;
+    if (ff.items.empty()) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }   // (cannot be: the total is the product of the block values)
+    rc = groth16_recheck(in, ff.items, d_ok);                               // stage 5
+    if (!rc) *rechecked = ff.items.size();
+    return rc;
+}
+// What every form checks before any device work; m beyond 2^31 - 1 is refused (the pairs A_j, C_j are 32-bit indices), nin beyond 2^20.
+int groth16_check_args(bool pointers_ok, size_t nin, bool inputs_ok, size_t m, const uint64_t* scalars) {
+    if (m > 0x7ffffffeull || nin > ((size_t)1 << 20) || !pointers_ok || (nin && !inputs_ok)) return BLSMI_E_ARG;
+    return rlc_check_args(true, scalars, m);
+}
+void groth16_report(int* combined, size_t* rechecked, bool held, size_t nre) { if (combined) *combined = held ? 1 : 0; if (rechecked) *rechecked = nre; }
+// -beta, -gamma, -delta behind the B_j: the table's tail from the key's three affine records on the device
+int groth16_key_tail(const void* d_vk_g2_aff, u8* d_tab, size_t m, hipStream_t s) {
+    DBuf order; HIPCHK(order.alloc(sizeof(GROTH16_KEY_ORDER)));
+    HIPCHK(hipMemcpyAsync(order.p, GROTH16_KEY_ORDER, sizeof(GROTH16_KEY_ORDER), hipMemcpyHostToDevice, s));
+    launch_quiet(KERNEL_OF(k_g2_neg_records), 1, s, d_vk_g2_aff, order.p, d_tab + (size_t)192 * m, 3);
+    return BLSMI_OK;
+}
+int groth16_host(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t nin, const uint8_t* proof_g1, const uint8_t* proof_g2, const uint8_t* inputs, size_t m,
+                 const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = groth16_check_args(vk_g1 && vk_g2 && proof_g1 && proof_g2 && ok, nin, inputs != nullptr, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    DBuf vk1, vk2, g1, tab, din, dok;
+    HIPCHK(vk1.alloc((size_t)96 * (nin + 2))); HIPCHK(vk2.alloc(192 * 3)); HIPCHK(g1.alloc((size_t)96 * 2 * m)); HIPCHK(tab.alloc((size_t)192 * (m + 3)));
+    HIPCHK(din.alloc((size_t)32 * nin * m)); HIPCHK(dok.alloc(m));
+    rc = upload_points(group_kernels(1), jac, vk_g1, vk1.p, nin + 2, s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, vk_g2, vk2.p, 3, s); if (rc) return rc;
+    rc = upload_points(group_kernels(1), jac, proof_g1, g1.p, 2 * m, s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, proof_g2, tab.p, m, s); if (rc) return rc;
+    if (nin) HIPCHK(hipMemcpyAsync(din.p, inputs, (size_t)32 * nin * m, hipMemcpyHostToDevice, s));
+    rc = groth16_key_tail(vk2.p, tab.as<u8>(), m, s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const Groth16In in{vk1.as<u8>(), g1.as<u8>(), tab.as<u8>(), din.as<u8>(), scalars, nin, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = groth16_core(in, dok.p, &held, &nre); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ok, dok.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+// the _dev forms: the B_j and the negated key points go into a table of the call's own; affine records that are 16-byte aligned are read in place
+int groth16_dev_api(const void* d_vk_g1, const void* d_vk_g2, size_t nin, const void* d_proof_g1, const void* d_proof_g2, const void* d_inputs, size_t m,
+                    const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = groth16_check_args(d_vk_g1 && d_vk_g2 && d_proof_g1 && d_proof_g2 && d_ok, nin, d_inputs != nullptr, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    hipStream_t s = g_stream;
+    DBuf vk1, vk2, g1, tab;
+    HIPCHK(tab.alloc((size_t)192 * (m + 3)));
+    const u8 *pvk1 = (const u8*)d_vk_g1, *pg1 = (const u8*)d_proof_g1; const void* pvk2 = d_vk_g2;
+    // a G1 buffer of the call's own: in-memory records converted, or a caller's affine records that are not 16-byte aligned copied
+    auto own_g1 = [&](DBuf& d, const u8*& p, size_t n) -> int {
+        if (!jac && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return BLSMI_OK;
+        HIPCHK(d.alloc((size_t)96 * n));
+        if (jac) { int rc = jac_to_wire_dev(group_kernels(1), p, d.p, nullptr, n, s); if (rc) return rc; }
+        else HIPCHK(hipMemcpyAsync(d.p, p, (size_t)96 * n, hipMemcpyDeviceToDevice, s));
+        p = d.as<u8>();
+        return BLSMI_OK;
+    };
+    rc = own_g1(vk1, pvk1, nin + 2); if (rc) return rc;
+    rc = own_g1(g1, pg1, 2 * m); if (rc) return rc;
+    if (jac) {
+        HIPCHK(vk2.alloc(192 * 3));
+        rc = jac_to_wire_dev(group_kernels(2), d_vk_g2, vk2.p, nullptr, 3, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(2), d_proof_g2, tab.p, nullptr, m, s); if (rc) return rc;
+        pvk2 = vk2.p;
+    } else HIPCHK(hipMemcpyAsync(tab.p, d_proof_g2, (size_t)192 * m, hipMemcpyDeviceToDevice, s));
+    rc = groth16_key_tail(pvk2, tab.as<u8>(), m, s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const Groth16In in{pvk1, pg1, tab.as<u8>(), (const u8*)d_inputs, scalars, nin, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = groth16_core(in, d_ok, &held, &nre); if (rc) return rc;
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_groth16_verify_batch(const uint8_t* vk_g1, const uint8_t* vk_g2, size_t nin, const uint8_t* proof_g1, const uint8_t* proof_g2, const uint8_t* inputs, size_t m,
+                                         const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked) {
+    return groth16_host(vk_g1, vk_g2, nin, proof_g1, proof_g2, inputs, m, scalars, block, ok, combined, rechecked, false);
+}
+BLSMI_API int blsmi_groth16_verify_batch_jac(const uint64_t* vk_g1_jac, const uint64_t* vk_g2_jac, size_t nin, const uint64_t* proof_g1_jac, const uint64_t* proof_g2_jac, const uint8_t* inputs, size_t m,
+                                             const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked) {
+    return groth16_host(reinterpret_cast<const uint8_t*>(vk_g1_jac), reinterpret_cast<const uint8_t*>(vk_g2_jac), nin, reinterpret_cast<const uint8_t*>(proof_g1_jac),
+                        reinterpret_cast<const uint8_t*>(proof_g2_jac), inputs, m, scalars, block, ok, combined, rechecked, true);
+}
+BLSMI_API int blsmi_groth16_verify_batch_dev(const void* d_vk_g1, const void* d_vk_g2, size_t nin, const void* d_proof_g1, const void* d_proof_g2, const void* d_inputs, size_t m,
+                                             const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
+    return groth16_dev_api(d_vk_g1, d_vk_g2, nin, d_proof_g1, d_proof_g2, d_inputs, m, scalars, block, d_ok, combined, rechecked, stream, false);
+}
+BLSMI_API int blsmi_groth16_verify_batch_jac_dev(const void* d_vk_g1_jac, const void* d_vk_g2_jac, size_t nin, const void* d_proof_g1_jac, const void* d_proof_g2_jac, const void* d_inputs, size_t m,
+                                                 const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
+    return groth16_dev_api(d_vk_g1_jac, d_vk_g2_jac, nin, d_proof_g1_jac, d_proof_g2_jac, d_inputs, m, scalars, block, d_ok, combined, rechecked, stream, true);
 }

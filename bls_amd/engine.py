@@ -1193,7 +1193,7 @@ ARGTYPES_0_11 = {
 
 def _fn(name):
     """the entry point `name` of 0.11 and later, with the argument types its ARGTYPES_0_NN table (here and below) gives it"""
-    tables = (ARGTYPES_0_11, ARGTYPES_0_12, ARGTYPES_0_13, ARGTYPES_0_14, ARGTYPES_0_15, ARGTYPES_0_16, ARGTYPES_0_17, ARGTYPES_0_18)
+    tables = (ARGTYPES_0_11, ARGTYPES_0_12, ARGTYPES_0_13, ARGTYPES_0_14, ARGTYPES_0_15, ARGTYPES_0_16, ARGTYPES_0_17, ARGTYPES_0_18, ARGTYPES_0_19)
     fn = getattr(_lib(), name)
     fn.argtypes = next(t[name] for t in tables if name in t)
     fn.restype = C.c_int
@@ -1788,3 +1788,99 @@ def pairing_product_batch_rlc_locate_dev(d_g1, d_g2_tab, nq, d_q_idx, np_, d_seg
 def pairing_product_batch_rlc_locate_jac_dev(d_g1_jac, d_g2_tab_jac, nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars=None, block=0, stream=0):
     """device-pointer form over in-memory points (no flags: z == 0 is infinity) -> (combined, rechecked)"""
     return _pprod_rlc_dev("blsmi_pairing_product_batch_rlc_locate_jac_dev", (d_g1_jac, d_g2_tab_jac), nq, d_q_idx, np_, d_seg_off, m, d_is_one, scalars, stream, block)
+
+
+# ---- scalar-field folds and Groth16 batches (blsmi 0.19) ------------------------------------------------------------------------------
+_G16_TAIL = [_u8p, C.c_size_t, _u64p, C.c_size_t, _u8p, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]                  # inputs, m, scalars, block, ok, combined, rechecked
+_G16_DEV_TAIL = [_V, C.c_size_t, _u64p, C.c_size_t, _V, C.POINTER(C.c_int), C.POINTER(C.c_size_t), _V]              # d_inputs, m, scalars, block, d_ok, combined, rechecked, stream
+# the argument types of the six entry points of 0.19, as include/blsmi.h declares them (tests/test_groth16_cpu.py compares)
+ARGTYPES_0_19 = {
+    "blsmi_fr_wsum_segmented_u64": [_u8p, C.c_size_t, _u64p, _u64p, C.c_size_t, _u8p],
+    "blsmi_fr_wsum_segmented_u64_dev": [_V, C.c_size_t, _V, _V, C.c_size_t, _V, _V],
+    "blsmi_groth16_verify_batch": [_u8p, _u8p, C.c_size_t, _u8p, _u8p] + _G16_TAIL,
+    "blsmi_groth16_verify_batch_jac": [_u64p, _u64p, C.c_size_t, _u64p, _u64p] + _G16_TAIL,
+    "blsmi_groth16_verify_batch_dev": [_V, _V, C.c_size_t, _V, _V] + _G16_DEV_TAIL,
+    "blsmi_groth16_verify_batch_jac_dev": [_V, _V, C.c_size_t, _V, _V] + _G16_DEV_TAIL,
+}
+
+
+def fr_wsum_segmented_u64(vals, ncol, weights, seg_off):
+    """blsmi_fr_wsum_segmented_u64 -> (nseg, ncol + 1, 32) uint8: per segment of rows the sum of its 64-bit weights and, per column, the
+    weighted sum of its scalars mod r, every output fully reduced.  vals: n * ncol scalars of 32 big-endian bytes, row-major (any 256-bit
+    value); weights: n integers below 2^64; seg_off: nseg + 1 offsets from 0 to n."""
+    ncol = int(ncol)
+    if ncol < 0:
+        raise ValueError("ncol is a number of columns, got %d" % ncol)
+    so = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64))
+    if so.ndim != 1 or so.size < 1 or int(so[0]) != 0 or np.any(so[1:] < so[:-1]):
+        raise ValueError("seg_off: nseg + 1 offsets from 0, non-decreasing")
+    nseg, n = so.size - 1, int(so[-1])
+    v = _u8(vals, 32 * ncol * n)
+    w = np.ascontiguousarray(np.asarray([int(x) for x in weights], dtype=np.uint64))
+    if w.shape != (n,):
+        raise ValueError("need one weight per row: %d rows, %d weights" % (n, w.size))
+    out = np.zeros((nseg, ncol + 1, 32), dtype=np.uint8)
+    _check(_fn("blsmi_fr_wsum_segmented_u64")(_p8(v), ncol, w.ctypes.data_as(_u64p) if n else None, so.ctypes.data_as(_u64p), nseg, _p8(out.reshape(-1))),
+           "fr_wsum_segmented_u64")
+    return out
+
+
+def fr_wsum_segmented_u64_dev(d_vals, ncol, d_weights, d_seg_off, nseg, d_out, stream=0):
+    """device-pointer form (ints); the nseg * (ncol + 1) scalars are in d_out when the call returns"""
+    _check(_fn("blsmi_fr_wsum_segmented_u64_dev")(d_vals or 0, ncol, d_weights or 0, d_seg_off or 0, nseg, d_out or 0, stream or 0), "fr_wsum_segmented_u64_dev")
+
+
+def _groth16(name, jac, vk_g1, vk_g2, proof_g1, proof_g2, inputs, nin, scalars, block):
+    pb, qb = (144, 288) if jac else (96, 192)
+    nin = int(nin)
+    if nin < 0:
+        raise ValueError("nin is a number of public inputs, got %d" % nin)
+    k1, k2 = _u8(vk_g1, pb * (nin + 2)), _u8(vk_g2, qb * 3)
+    a, b = _u8(proof_g1), _u8(proof_g2)
+    if b.size % qb or a.size != 2 * pb * (b.size // qb):
+        raise ValueError("expected m*%d bytes of B_j and 2*m*%d bytes of A_j, C_j, got %d and %d" % (qb, pb, b.size, a.size))
+    m = b.size // qb
+    x = _u8(inputs if inputs is not None else b"", 32 * nin * m)
+    r, pr = _scalars(scalars, m)
+    block = _block(block)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    fn = _fn(name)
+    if jac:
+        (k1, pk1), (k2, pk2), (a, pa), (b, pb_) = _j64(k1, k1.size), _j64(k2, k2.size), _j64(a, a.size), _j64(b, b.size)
+    else:
+        pk1, pk2, pa, pb_ = _p8(k1), _p8(k2), _p8(a), _p8(b)
+    _check(fn(pk1, pk2, nin, pa, pb_, _p8(x), m, pr, block, _p8(ok), C.byref(comb), C.byref(nre)), name[len("blsmi_"):])
+    return ok[:m].copy(), comb.value, nre.value
+
+
+def groth16_verify_batch(vk_g1, vk_g2, proof_g1, proof_g2, inputs, nin, scalars=None, block=0):
+    """blsmi_groth16_verify_batch -> (ok (m,) uint8, combined, rechecked): m Groth16 proofs of one circuit with nin public inputs.  vk_g1:
+    alpha, IC_0 .. IC_nin (96 bytes each); vk_g2: beta, gamma, delta (192 each); proof_g1: A_j, C_j interleaved; proof_g2: B_j; inputs: m * nin
+    scalars of 32 big-endian bytes, item-major (None when nin == 0).  ok[j] is the verdict of pairing_product_batch on (A_j, B_j),
+    (-alpha, beta), (-L_j, gamma), (-C_j, delta); scalars and block as pairing_product_batch_rlc_locate."""
+    return _groth16("blsmi_groth16_verify_batch", False, vk_g1, vk_g2, proof_g1, proof_g2, inputs, nin, scalars, block)
+
+
+def groth16_verify_batch_jac(vk_g1_jac, vk_g2_jac, proof_g1_jac, proof_g2_jac, inputs, nin, scalars=None, block=0):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _groth16("blsmi_groth16_verify_batch_jac", True, vk_g1_jac, vk_g2_jac, proof_g1_jac, proof_g2_jac, inputs, nin, scalars, block)
+
+
+def _groth16_dev(name, d_vk_g1, d_vk_g2, nin, d_proof_g1, d_proof_g2, d_inputs, m, d_ok, scalars, block, stream):
+    r, pr = _scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _check(_fn(name)(d_vk_g1 or 0, d_vk_g2 or 0, nin, d_proof_g1 or 0, d_proof_g2 or 0, d_inputs or 0, m, pr, _block(block), d_ok or 0, C.byref(comb), C.byref(nre), stream or 0),
+           name[len("blsmi_"):])
+    return comb.value, nre.value
+
+
+def groth16_verify_batch_dev(d_vk_g1, d_vk_g2, nin, d_proof_g1, d_proof_g2, d_inputs, m, d_ok, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_ok when the call returns; scalars stay on the host.
+    -> (combined, rechecked)"""
+    return _groth16_dev("blsmi_groth16_verify_batch_dev", d_vk_g1, d_vk_g2, nin, d_proof_g1, d_proof_g2, d_inputs, m, d_ok, scalars, block, stream)
+
+
+def groth16_verify_batch_jac_dev(d_vk_g1_jac, d_vk_g2_jac, nin, d_proof_g1_jac, d_proof_g2_jac, d_inputs, m, d_ok, scalars=None, block=0, stream=0):
+    """device-pointer form over in-memory points -> (combined, rechecked)"""
+    return _groth16_dev("blsmi_groth16_verify_batch_jac_dev", d_vk_g1_jac, d_vk_g2_jac, nin, d_proof_g1_jac, d_proof_g2_jac, d_inputs, m, d_ok, scalars, block, stream)

@@ -89,8 +89,10 @@ void blsmi_shutdown(void);
  * (blsmi_pairing_product_batch_rlc[_jac|_dev|_jac_dev]: one equation for a batch of pairing products, the pairs of one G2 table entry sharing
  * one Miller loop) and blsmi_debug_pairing_product_batch_rlc_dev_nosplit; no existing prototype changes, no new option.  0.18 adds the randomised pairing-product
  * batches that find the bad items by blocks (blsmi_pairing_product_batch_rlc_locate[_jac|_dev|_jac_dev]); no existing prototype changes, no
- * new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17 and 0.18 by the presence of
+ * new option.  0.19 adds arithmetic mod r -- the weighted segmented fold of scalars (blsmi_fr_wsum_segmented_u64[_dev]) -- and the Groth16
+ * batches that fold their public inputs with it (blsmi_groth16_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new
+ * option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18 and 0.19 by the presence of
  * those symbols. */
 const char *blsmi_version(void);
 
@@ -1005,6 +1007,64 @@ int blsmi_pairing_product_batch_rlc_locate_dev(const void *d_g1_aff, const void 
 int blsmi_pairing_product_batch_rlc_locate_jac_dev(const void *d_g1_jac, const void *d_g2_tab_jac, size_t nq, const void *d_q_idx,
                                                    size_t np, const void *d_seg_off, size_t m, const uint64_t *scalars, size_t block,
                                                    void *d_is_one, int *combined, size_t *rechecked, void *stream);
+
+/* ---- scalar-field folds and Groth16 batches (blsmi 0.19) ---------------------------------------------------------------------------------
+ * Arithmetic mod r on the device, r the order of G1, G2 and GT:
+ *     out[s][0] = sum_{j in segment s} w_j;        out[s][1 + i] = sum_{j in segment s} w_j * vals[j][i] mod r        (i < ncol)
+ * vals: n * ncol scalars, row-major, 32-byte big-endian (the library's scalar format); ANY 256-bit value is taken mod r.  weights: n 64-bit
+ * words; a zero weight is allowed.  seg_off: nseg + 1 offsets from 0, non-decreasing, n = seg_off[nseg]; an empty segment gives zeros.
+ * out: nseg * (ncol + 1) scalars, 32-byte big-endian, every one fully reduced (< r).  One pass over vals: every lane adds unreduced
+ * 64 x 256-bit products into twelve 32-bit words, the lanes of a (segment, column) meet with the carries resolved, and there is one
+ * reduction mod r per output, not one per row; the result does not depend on how the rows were cut into workgroups.
+ *   - BLSMI_E_ARG before any device work: NULL seg_off or out; offsets that do not start at 0 or that decrease; n or ncol beyond
+ *     2^32 - 1 (the accumulator's bound); NULL weights with n > 0; NULL vals with n * ncol > 0.  nseg = 0: BLSMI_OK, nothing written.
+ *   - _dev: every buffer on one of the library's devices (d_vals 4-byte aligned; read in 16-byte pieces where its address allows);
+ *     seg_off is read back once (the same errors); `stream` as in blsmi_pairing_batch_dev; the caller's inputs stay untouched. */
+int blsmi_fr_wsum_segmented_u64(const uint8_t *vals /* n*ncol*32 */, size_t ncol, const uint64_t *weights /* n */, const uint64_t *seg_off /* nseg+1 */,
+                                size_t nseg, uint8_t *out /* nseg*(ncol+1)*32 */);
+int blsmi_fr_wsum_segmented_u64_dev(const void *d_vals, size_t ncol, const void *d_weights, const void *d_seg_off, size_t nseg, void *d_out, void *stream);
+/* m Groth16 proofs of one circuit with nin public inputs, from the verifying key, the proofs and the inputs themselves: no L_j is asked of
+ * the caller.  vk_g1: alpha, IC_0 .. IC_nin ((nin + 2) records); vk_g2: beta, gamma, delta (3 records); proof_g1: A_j, C_j (2 m records:
+ * A_0, C_0, A_1, C_1, ...); proof_g2: B_j (m records); inputs: m * nin scalars, 32-byte big-endian, item-major, taken mod r (NULL allowed
+ * when nin == 0).  scalars / block / ok / combined / rechecked exactly as blsmi_pairing_product_batch_rlc_locate.
+ * Verdicts: ok[j] is exactly is_one[j] of blsmi_pairing_product_batch on the four pairs (A_j, B_j), (-alpha, beta), (-L_j, gamma),
+ * (-C_j, delta), with L_j = IC_0 + sum_i (a_ji mod r) * IC_i computed as blsmi_g1_msm computes it.  Infinity (the all-zero affine record,
+ * z == 0 in an in-memory record) follows blsmi_pairing_product_batch: the pair contributes 1; an all-zero vk_g2 entry drops its pairs.
+ * The path that holds: per block b of the 0.18 rule (block = 0: max(64, ceil(m / 256))), with the weights r_j,
+ *     sum_{j in b} r_j * L_j = t_b * IC_0 + sum_i s_bi * IC_i,        t_b = sum_{j in b} r_j,        s_bi = sum_{j in b} r_j * a_ji mod r
+ * -- the fold above over the inputs, the blocks as its segments -- so a block costs nin + 2 full-width ladders (t_b * alpha among them)
+ * whatever its length, r_j * A_j goes against its private B_j, sum r_j * C_j against delta, and the blocks' products, the total and one
+ * final exponentiation are those of 0.18.  On this path no L_j exists and no item pays a full-width ladder.  When the total fails the
+ * block values are final-exponentiated, and for the items of the failing blocks, and only those, L_j is built (nin + 1 ladders each and a
+ * segmented sum) and the four pairs go through blsmi_pairing_product_batch's own path; *rechecked is the number of those items.
+ * Soundness: the fold is the same group element as sum r_j * L_j only for IC_i of order r, so 0.17's precondition applies to every key
+ * and proof point: they lie in the prime-order subgroups (blsmi_g?_check_batch establishes that).  Under it a block whose equation holds
+ * has a failing item with probability at most 2^-64 over the drawn scalars; caller scalars carry 0.17's caveat.
+ *   - BLSMI_E_ARG before any device work: a NULL key or proof pointer with m > 0; NULL inputs with m * nin > 0; NULL ok; a zero caller
+ *     scalar; m beyond 2^31 - 2 (the pairs A_j, C_j are 32-bit indices; 2^32 - 1 and beyond included); nin beyond 2^20.
+ *   - m = 0: BLSMI_OK, *combined = 0.  *rechecked = 0 on every early return.  No `block` value is refused.
+ *   - _jac: points as G1Projective / G2Projective records (144 / 288 bytes); _dev: everything but scalars / combined / rechecked resident
+ *     on one of the library's devices, `stream` as in blsmi_pairing_batch_dev; the caller's buffers stay untouched.
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * When to call it (one MI355X, everything resident, block = 0, against the composite a caller had before -- blsmi_g1_mul_batch_dev over m * nin
+ * IC records, blsmi_g1_sum_segmented_dev for the L_j, blsmi_pairing_product_batch_rlc_locate_dev -- the two alternating, median of 20 +-
+ * spread in ms; DESIGN.md 3t has the table and the stages): for any batch the 0.18 call would serve when the L_j do not exist yet.  All
+ * valid, m x nin: 16 384 x 8 11.8 +- 0.1 against 18.4 +- 0.4, 65 536 x 8 23.3 +- 0.4 against 55.7 +- 1.0, 16 384 x 1 10.6 against 15.8; one
+ * bad input: 15.8 against 21.5 and 28.5 against 58.3.  The fold itself takes 0.06 ms at 65 536 x 8.  What 0.17 says about a few thousand
+ * items or fewer holds here too: 2 048 x 8 takes 6.4 ms (the composite 8.2), behind a per-item check on L_j that already exist. */
+int blsmi_groth16_verify_batch(const uint8_t *vk_g1 /* (nin+2)*96 */, const uint8_t *vk_g2 /* 3*192 */, size_t nin, const uint8_t *proof_g1 /* 2m*96 */,
+                               const uint8_t *proof_g2 /* m*192 */, const uint8_t *inputs /* m*nin*32 */, size_t m,
+                               const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */,
+                               uint8_t *ok /* m */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_groth16_verify_batch_jac(const uint64_t *vk_g1_jac /* (nin+2)*18 */, const uint64_t *vk_g2_jac /* 3*36 */, size_t nin, const uint64_t *proof_g1_jac /* 2m*18 */,
+                                   const uint64_t *proof_g2_jac /* m*36 */, const uint8_t *inputs, size_t m, const uint64_t *scalars, size_t block,
+                                   uint8_t *ok, int *combined, size_t *rechecked);
+int blsmi_groth16_verify_batch_dev(const void *d_vk_g1, const void *d_vk_g2, size_t nin, const void *d_proof_g1, const void *d_proof_g2, const void *d_inputs, size_t m,
+                                   const uint64_t *scalars /* host: m, may be NULL */, size_t block, void *d_ok, int *combined /* host */,
+                                   size_t *rechecked /* host */, void *stream);
+int blsmi_groth16_verify_batch_jac_dev(const void *d_vk_g1_jac, const void *d_vk_g2_jac, size_t nin, const void *d_proof_g1_jac, const void *d_proof_g2_jac,
+                                       const void *d_inputs, size_t m, const uint64_t *scalars, size_t block, void *d_ok, int *combined, size_t *rechecked,
+                                       void *stream);
 
 #ifdef __cplusplus
 }
