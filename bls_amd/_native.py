@@ -178,19 +178,58 @@ def load():
     if alt:
         _prefer_torch_hip_runtime()
         _lib = C.CDLL(os.path.abspath(alt))
-        _lib.blsmi_version.restype = C.c_char_p
         return _lib
     if not os.path.exists(SO_PATH):
         raise NativeError("bls_amd/libblsmi.so is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     _prefer_torch_hip_runtime()
     _lib = C.CDLL(SO_PATH)
-    _lib.blsmi_version.restype = C.c_char_p
     return _lib
+
+
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "long long": C.c_longlong, "float": C.c_float,
+            "uint8_t": C.c_uint8, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_signatures = None
+
+
+def _ctype(spelling, proto):
+    """One parameter or return type of include/blsmi.h as ctypes has it; a spelling this table does not know is an error, never a guess."""
+    t = " ".join(spelling.replace("*", " * ").split())
+    if t.startswith("const "):
+        t = t[len("const "):]
+    if t in _SCALARS:
+        return _SCALARS[t]
+    if t in ("void *", "char *", "void * *"):
+        return {"void *": C.c_void_p, "char *": C.c_char_p, "void * *": C.POINTER(C.c_void_p)}[t]
+    if t.endswith(" *") and t[:-2] in _SCALARS:
+        return C.POINTER(_SCALARS[t[:-2]])
+    raise NativeError("include/blsmi.h: cannot read the type `%s` in `%s`" % (spelling.strip(), proto))
+
+
+def signatures():
+    """{name: (restype, [argtypes])} of every prototype in include/blsmi.h (parsed once): what bls_amd.engine binds the entry points with."""
+    global _signatures
+    if _signatures is None:
+        import re
+        txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+        table = {}
+        for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?[\s\*])(blsmi_\w+)\s*\(([^;{}()]*)\)\s*;", txt, flags=re.M):
+            proto = " ".join(("%s%s(%s)" % (ret, name, params)).split())
+            args = []
+            for a in ([] if params.strip() == "void" else params.split(",")):
+                arr = re.fullmatch(r"\s*(.*?)\s*\w+\s*\[\d*\]\s*", a, flags=re.S)   # `const uint8_t sig[96]` is a pointer
+                named = re.fullmatch(r"\s*(.*?[\s\*])\w+\s*", a, flags=re.S)
+                if not arr and not named:
+                    raise NativeError("include/blsmi.h: cannot read the parameter `%s` in `%s`" % (a.strip(), proto))
+                args.append(_ctype(arr.group(1) + " *" if arr else named.group(1), proto))
+            table[name] = (None if ret.strip() == "void" else _ctype(ret, proto), args)
+        missed = set(re.findall(r"\b(blsmi_[a-z0-9_]+)\s*\(", txt)) - set(table)
+        if missed:                                             # a declaration of a shape the expression above does not cover
+            raise NativeError("include/blsmi.h: cannot read the prototype of %s" % ", ".join(sorted(missed)))
+        _signatures = table
+    return _signatures
 
 
 def declared_symbols():
     """Entry points declared in include/blsmi.h."""
-    import re
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"\b(blsmi_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(signatures())

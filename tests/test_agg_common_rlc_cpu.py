@@ -13,15 +13,14 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from oracle import pyref as P
 from oracle import refcpu as RC
-from test_rlc_grouped_cpu import _header_params, grouped_holds
+from test_rlc_grouped_cpu import grouped_holds
 
 E_ARG = -3
 HOST = ["blsmi_g2pubs_verify_aggregate_common_batch_rlc", "blsmi_g1pubs_verify_aggregate_common_batch_rlc", "blsmi_g1pubs_verify_aggregate_common_with_domain_batch_rlc"]
 SYMS = HOST + [s + "_jac" for s in HOST] + [s + "_dev" for s in HOST] + ["blsmi_debug_g2_sum_segmented_u64_pair"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64),
-          "const uint32_t *": C.POINTER(C.c_uint32), "size_t": C.c_size_t, "int *": C.POINTER(C.c_int), "const void *": C.c_void_p, "void *": C.c_void_p}
 
 
 @pytest.fixture(scope="module")
@@ -40,8 +39,7 @@ def test_declared_exported_and_typed(lib, tmp_path):
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
         want = [CTYPES[t] for t in _header_params(header, s)]
-        assert engine.ARGTYPES_0_16[s] == want, s
-    assert set(engine.ARGTYPES_0_16) == set(SYMS)
+        assert bound_argtypes(s) == want, s
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("committee aggregates, randomised (blsmi 0.16)"):])
     for phrase in ("ok[j] is exactly what *_verify_aggregate_common*_batch gives for the same inputs", "\"rlc_min\" does NOT apply", "one device", "request combiner",
                    "BLSMI_E_ARG before any device work", "at most 2^-64 over the drawn scalars", "in the prime-order subgroups", "both outputs NULL"):
@@ -64,8 +62,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     moff = (C.c_uint64 * 3)(0, 4, 8)
     dom = (C.c_uint8 * 8)()
     for name in HOST + [s + "_jac" for s in HOST]:
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_16[name], C.c_int
+        fn = engine._fn(name)
         jac = name.endswith("_jac")
         u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
         pts = C.cast(w64, u64p) if jac else C.cast(buf, u8p)
@@ -99,8 +96,7 @@ def test_argument_checks_come_before_any_device_work(lib):
         assert call(msg_idx=(), seg=(0,), idx=None, m=0, head=(None, None), pks=None, sigs=None, null_msg_idx=True, null_seg=True, want_ok=False, d=0, npk=0) == (0, 0), \
             (name, "m = 0, nothing else")
     for name in (s + "_dev" for s in HOST):                                      # what the _dev forms can refuse without a device
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_16[name], C.c_int
+        fn = engine._fn(name)
         comb = C.c_int(7)
         a = C.addressof(buf)
         assert fn(a, a, 2, a, a, 4, a, a, a, (C.c_uint64 * 2)(3, 0), a, 2, C.byref(comb), None) == E_ARG and comb.value == 0, (name, "a zero scalar")

@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from groth16_cases import BAD_INPUT, BAD_TWO, EDGE_INPUTS, M, R, Groth16Case, edges_for, is_one
 from oracle import pyref as P
 from oracle import refcpu as RC
 from pprod_rlc_locate_common import blocks_of, fq12_prod, rechecked_of
-from test_pprod_rlc_locate_cpu import CTYPES, PINNED
-from test_rlc_grouped_cpu import _header_params
+from test_pprod_rlc_locate_cpu import PINNED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -3
@@ -42,8 +42,7 @@ def test_declared_exported_and_typed(lib, tmp_path):
     assert exported == set(declared)                                             # nm -D exports equal the header's names
     for s in FOLD + FOUR:
         assert s in declared and s in exported and hasattr(lib, s), s
-        assert engine.ARGTYPES_0_19[s] == [CTYPES[t] for t in _header_params(header, s)], s
-    assert set(engine.ARGTYPES_0_19) == set(FOLD + FOUR)
+        assert bound_argtypes(s) == [CTYPES[t] for t in _header_params(header, s)], s
     twin = _header_params(header, "blsmi_pairing_product_batch_rlc_locate")     # scalars / block / ok / combined / rechecked as the 0.18 call has them
     assert _header_params(header, FOUR[0])[-5:] == twin[-5:]
     for w in ("fr_wsum_segmented_u64", "fr_wsum_segmented_u64_dev", "groth16_verify_batch", "groth16_verify_batch_jac", "groth16_verify_batch_dev", "groth16_verify_batch_jac_dev"):
@@ -71,8 +70,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
     a = C.addressof(buf)
     for name in FOUR:
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_19[name], C.c_int
+        fn = engine._fn(name)
         dev = name.endswith("_dev")
         pts = a if dev else (C.cast(w64, u64p) if name.endswith("_jac") else C.cast(buf, u8p))
         inp = a if dev else C.cast(buf, u8p)
@@ -95,8 +93,7 @@ def test_argument_checks_come_before_any_device_work(lib):
             assert call(m=0, block=block) == (0, 0, 0), (name, "m = 0")
             assert call(vk1=None, vk2=None, pg1=None, pg2=None, inputs=None, ok=None, m=0, block=block) == (0, 0, 0), (name, "m = 0, nothing else")
             assert call(ok=None, block=block, want_nre=False)[:2] == (E_ARG, 0), (name, "rechecked may be NULL")
-    fold = lib.blsmi_fr_wsum_segmented_u64
-    fold.argtypes, fold.restype = engine.ARGTYPES_0_19[FOLD[0]], C.c_int
+    fold = engine._fn(FOLD[0])
     vals, w, out = C.cast(buf, u8p), C.cast(w64, u64p), C.cast(buf, u8p)
     off = lambda *o: (C.c_uint64 * len(o))(*o)                                    # noqa: E731
     assert fold(vals, 2, w, None, 1, out) == E_ARG                               # seg_off NULL
@@ -107,8 +104,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     assert fold(None, 2, w, off(0, 3), 1, out) == E_ARG                          # vals NULL with rows and columns
     assert fold(vals, 1, w, off(0, 1 << 32), 1, out) == E_ARG                    # more rows than the accumulator is sized for
     assert fold(None, 0, None, None, 0, None) == 0                               # nseg = 0
-    fold_dev = lib.blsmi_fr_wsum_segmented_u64_dev
-    fold_dev.argtypes, fold_dev.restype = engine.ARGTYPES_0_19[FOLD[1]], C.c_int
+    fold_dev = engine._fn(FOLD[1])
     assert fold_dev(a, 2, a, None, 1, a, None) == E_ARG and fold_dev(a, 2, a, a, 1, None, None) == E_ARG and fold_dev(None, 0, None, None, 0, None, None) == 0
 
 

@@ -15,14 +15,13 @@ import pytest
 import group_edges as G
 import point_check_cases as K
 from bls_amd import _native, engine, g1pubs, g2pubs
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from gpu_common import P
 
 E_ARG = -3
 GROUPS = (1, 2)
 FORMS = ("affine", "jacobian")
 SYMS = ["blsmi_g1_check_batch", "blsmi_g2_check_batch", "blsmi_g1_check_batch_jac", "blsmi_g2_check_batch_jac", "blsmi_g1_check_batch_dev", "blsmi_g2_check_batch_dev"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64), "size_t": C.c_size_t,
-          "int": C.c_int, "const void *": C.c_void_p, "void *": C.c_void_p}
 
 
 @pytest.fixture(scope="module")
@@ -147,16 +146,6 @@ def test_cuts_hold_every_status_and_end_on_a_bad_record():
 
 
 # ---- the ABI surface -------------------------------------------------------------------------------------------------------------------
-def _header_params(header, name):
-    m = re.search(r"\bint %s\s*\(([^;]*?)\);" % name, header, flags=re.S)
-    assert m, name
-    out = []
-    for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","):
-        a = " ".join(a.split())
-        out.append(a[:a.rindex("*") + 1] if "*" in a else a.rsplit(" ", 1)[0])
-    return out
-
-
 def test_declared_exported_and_typed(lib, tmp_path):
     declared = _native.declared_symbols()
     header = open(_native.HEADER).read()
@@ -164,8 +153,7 @@ def test_declared_exported_and_typed(lib, tmp_path):
     exported = set(re.findall(r" T (blsmi_\w+)", subprocess.run(["nm", "-D", _native.SO_PATH], capture_output=True, text=True, check=True).stdout))
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
-        assert engine.ARGTYPES_0_14[s] == [CTYPES[t] for t in _header_params(header, s)], s
-    assert set(engine.ARGTYPES_0_14) == set(SYMS)
+        assert bound_argtypes(s) == [CTYPES[t] for t in _header_params(header, s)], s
     assert header.index("point validation (blsmi 0.14)") > header.index("pairing products (blsmi 0.10)")      # appended: the last section
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("point validation (blsmi 0.14)"):])
     for phrase in ("IsOnCurve", "IsInCorrectSubgroupAssumingOnCurve", "is read as 0", "AS THAT POINT", "z == 0", "in_inf", "not consulted", "BLSMI_E_ARG",
@@ -190,9 +178,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     a8, a64, s8 = C.cast(buf, C.POINTER(C.c_uint8)), C.cast(buf, C.POINTER(C.c_uint64)), C.cast(st, C.POINTER(C.c_uint8))
     v = C.c_void_p
     for name in SYMS:
-        fn = getattr(lib, name)
-        fn.argtypes = engine.ARGTYPES_0_14[name]
-        fn.restype = C.c_int
+        fn = engine._fn(name)
         if name.endswith("_dev"):
             def call(pts, status, check, n, fn=fn, jac=0, flags=None):
                 return fn(v(pts), v(flags), jac, check, v(status), n, None)

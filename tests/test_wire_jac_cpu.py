@@ -14,14 +14,13 @@ import pytest
 import group_edges as G
 import wire_jac_cases as W
 from bls_amd import _groups, _native, engine, g1pubs, g2pubs
+from cabi_common import CTYPES, _header_params, bound_argtypes
 from gpu_common import P
 
 E_ARG = -3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ["blsmi_g1_decompress_batch_jac", "blsmi_g2_decompress_batch_jac", "blsmi_g1_compress_batch_jac", "blsmi_g2_compress_batch_jac",
         "blsmi_g1_decompress_batch_jac_dev", "blsmi_g2_decompress_batch_jac_dev", "blsmi_g1_compress_batch_jac_dev", "blsmi_g2_compress_batch_jac_dev"]
-CTYPES = {"const uint8_t *": C.POINTER(C.c_uint8), "uint8_t *": C.POINTER(C.c_uint8), "const uint64_t *": C.POINTER(C.c_uint64), "uint64_t *": C.POINTER(C.c_uint64),
-          "size_t": C.c_size_t, "int": C.c_int, "const void *": C.c_void_p, "void *": C.c_void_p}
 
 
 @pytest.fixture(scope="module")
@@ -31,16 +30,6 @@ def lib():
 
 
 # ---- the ABI surface -------------------------------------------------------------------------------------------------------------------
-def _header_params(header, name):
-    m = re.search(r"\bint %s\s*\(([^;]*?)\);" % name, header, flags=re.S)
-    assert m, name
-    out = []
-    for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","):
-        a = " ".join(a.split())
-        out.append(a[:a.rindex("*") + 1] if "*" in a else a.rsplit(" ", 1)[0])
-    return out
-
-
 def test_declared_exported_and_typed(lib, tmp_path):
     declared = _native.declared_symbols()
     header = open(_native.HEADER).read()
@@ -48,8 +37,7 @@ def test_declared_exported_and_typed(lib, tmp_path):
     exported = set(re.findall(r" T (blsmi_\w+)", subprocess.run(["nm", "-D", _native.SO_PATH], capture_output=True, text=True, check=True).stdout))
     for s in SYMS:
         assert s in declared and s in exported and hasattr(lib, s), s
-        assert engine.ARGTYPES_0_15[s] == [CTYPES[t] for t in _header_params(header, s)], s
-    assert set(engine.ARGTYPES_0_15) == set(SYMS)
+        assert bound_argtypes(s) == [CTYPES[t] for t in _header_params(header, s)], s
     assert _header_params(header, "blsmi_g1_decompress_batch_jac") == ["const uint8_t *", "int", "uint64_t *", "uint8_t *", "uint8_t *", "size_t"]
     assert _header_params(header, "blsmi_g2_compress_batch_jac_dev") == ["const void *", "void *", "size_t", "void *"]
     assert header.index("in-memory points (blsmi 0.15)") > header.index("point validation (blsmi 0.14)")      # appended: the last section
@@ -75,9 +63,7 @@ def test_argument_checks_come_before_any_device_work(lib):
     o8, o64 = C.cast(out, C.POINTER(C.c_uint8)), C.cast(out, C.POINTER(C.c_uint64))
     v = C.c_void_p
     for name in SYMS:
-        fn = getattr(lib, name)
-        fn.argtypes = engine.ARGTYPES_0_15[name]
-        fn.restype = C.c_int
+        fn = engine._fn(name)
         dev = name.endswith("_dev")
         if "decompress" in name:
             def call(src, dst, err, n, check=1, inf=None, fn=fn, dev=dev):
