@@ -12,6 +12,11 @@
 #pragma once
 #include "curve.cuh"
 
+// waves per SIMD the kernels around the G1 ladder declare (k_g1_mul_glv, k_g1_mul_add_glv)
+#ifndef BLSMI_GLV_WAVES
+#define BLSMI_GLV_WAVES 2
+#endif
+
 namespace blsmi {
 
 // ---- multi-word integers (little-endian u32 words in registers) -------------------------------------------------------------

@@ -179,9 +179,6 @@ KERNEL k_glv_recode(const u8* scalars, int group, u8* rec, size_t n) {
 #pragma unroll
     for (int i = 0; i < 16; i++) o[i] = __builtin_bswap32(w[15 - i]);
 }
-#ifndef BLSMI_GLV_WAVES
-#define BLSMI_GLV_WAVES 2
-#endif
 __global__ void __launch_bounds__(WG, BLSMI_GLV_WAVES) k_g1_mul_glv(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_glv_body<FpS, 96>(pts, pt_stride, scalars, out, out_inf, n); }
 KERNEL k_g2_mul_glv(const u8* pts, size_t pt_stride, const u8* scalars, u8* out, u8* out_inf, size_t n) { mul_glv_body<Fp2S, 192>(pts, pt_stride, scalars, out, out_inf, n); }
 

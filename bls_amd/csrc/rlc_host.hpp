@@ -1,6 +1,6 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
 // ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*,
-// blsmi_fr_wsum_segmented_u64* and blsmi_groth16_verify_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// blsmi_fr_wsum_segmented_u64*, blsmi_groth16_verify_batch*, blsmi_g1_mul_add_batch* and blsmi_kzg_verify_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -1569,4 +1569,258 @@ BLSMI_API int blsmi_groth16_verify_batch_dev(const void* d_vk_g1, const void* d_
 BLSMI_API int blsmi_groth16_verify_batch_jac_dev(const void* d_vk_g1_jac, const void* d_vk_g2_jac, size_t nin, const void* d_proof_g1_jac, const void* d_proof_g2_jac, const void* d_inputs, size_t m,
                                                  const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
     return groth16_dev_api(d_vk_g1_jac, d_vk_g2_jac, nin, d_proof_g1_jac, d_proof_g2_jac, d_inputs, m, scalars, block, d_ok, combined, rechecked, stream, true);
+}
+
+// ---- KZG batches with the values folded in Fr (blsmi 0.20; include/blsmi.h "KZG") -----------------------------------------------------------
+// out_j = A_j + [k_j mod r] B_j, a lane per item (k_g1_mul_add_glv, k_kzg.hip): the endomorphism ladder, one mixed addition, one inversion.
+namespace {
+// a stride of affine G1 records: 0 (one common record) or at least a record, in whole words
+bool mul_add_stride_ok(size_t stride) { return stride == 0 || (stride >= 96 && stride % 4 == 0); }
+// the bytes n records `stride` apart span
+size_t mul_add_span(size_t stride, size_t n) { return stride * (n - 1) + 96; }
+// on s, not synchronised
+int mul_add_dev_core(const u8* d_a, size_t a_stride, const u8* d_b, size_t b_stride, const u8* d_scalars, u8* d_out, size_t out_stride, u8* d_out_inf, size_t n, hipStream_t s) {
+    launch(KERNEL_OF(k_g1_mul_add_glv), nblocks(n), s, d_a, a_stride, d_b, b_stride, d_scalars, d_out, out_stride, d_out_inf, n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_g1_mul_add_batch(const uint8_t* a, size_t a_stride, const uint8_t* b, size_t b_stride, const uint8_t* scalars, uint8_t* out, uint8_t* out_inf, size_t n) {
+    if (n == 0) return BLSMI_OK;
+    if (!a || !b || !scalars || !out || !out_inf || !mul_add_stride_ok(a_stride) || !mul_add_stride_ok(b_stride) || n > 0xffffffffull) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t ab = mul_add_span(a_stride, n), bb = mul_add_span(b_stride, n);
+    DBuf da, db, ds, dout, dinf;
+    HIPCHK(da.alloc(ab)); HIPCHK(db.alloc(bb)); HIPCHK(ds.alloc((size_t)32 * n)); HIPCHK(dout.alloc((size_t)96 * n)); HIPCHK(dinf.alloc(n));
+    HIPCHK(hipMemcpyAsync(da.p, a, ab, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(db.p, b, bb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ds.p, scalars, (size_t)32 * n, hipMemcpyHostToDevice, s));
+    int rc = mul_add_dev_core(da.as<u8>(), a_stride, db.as<u8>(), b_stride, ds.as<u8>(), dout.as<u8>(), 96, dinf.as<u8>(), n, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)96 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_inf, dinf.p, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_g1_mul_add_batch_dev(const void* d_a, size_t a_stride, const void* d_b, size_t b_stride, const void* d_scalars, void* d_out, void* d_out_inf, size_t n, void* stream) {
+    if (n == 0) return BLSMI_OK;
+    if (!d_a || !d_b || !d_scalars || !d_out || !d_out_inf || !mul_add_stride_ok(a_stride) || !mul_add_stride_ok(b_stride) || n > 0xffffffffull) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    int rc = mul_add_dev_core((const u8*)d_a, a_stride, (const u8*)d_b, b_stride, (const u8*)d_scalars, (u8*)d_out, 96, (u8*)d_out_inf, n, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+
+// m openings under the block equations of 0.18.  Item j holds when e(C_j - y_j G + z_j pi_j, H) e(pi_j, -tau H) = 1 -- tau H is negated once
+// (k_g2_neg_records), no proof is.  With W_j = C_j + z_j pi_j and the weights r_j, over a block b,
+//     sum_j r_j (W_j - y_j G) = sum_j r_j W_j - s_b G,        s_b = sum_j r_j y_j mod r,
+// so that a block needs one scalar from the fold and one full-width ladder over -G, whatever its length; no y_j G exists on the path that
+// holds.  Stages:
+//   1  the plan of 0.18 over two pairs per item, (W_j, H) and (pi_j, -tau H): per block an H cell and a -tau H cell, and one further cell
+//      per block appended to it (pprod_locate_append_cells) against H again: s_b (-G).  Three Miller loops per block.
+//   2  the lift, its own: k_g1_mul_add_glv writes W_j = C_j + z_j pi_j into the even records of the interleaved (W_j, pi_j) buffer, read from
+//      where C_j and pi_j lie; k_kzg_place_proofs copies pi_j beside it
+//   3  pprod_weighted_sums, unchanged, with room for the B sums it does not make
+//   4  its own: fr_wsum_dev over y with one column and the blocks as segments; B ladders of s_b over copies of -G (mul_dev_core), written
+//      straight into those places -- s_b = 0 gives the infinity record and its flag, and the route leaves the cell out
+//   5  pprod_locate_failing_blocks, unchanged: route, Miller loops, block products, total, final exponentiation; the failing blocks
+//   6  kzg_recheck for their items only: y_j mod r (the fold again, a segment per item, weight one), y_j (-G) ladders, the two-point
+//      segmented sum with the W_j already there, the two pairs dense (k_kzg_recheck_pairs), pprod_recheck_dense.  The lift runs once.
+// One lease, one device, never in the request combiner.
+namespace {
+struct KzgIn {
+    const u8* g;             // G: one affine record, 4-byte aligned
+    u8* wp;                  // (W_j, pi_j) interleaved: 2 m affine records, the call's own, 16-byte aligned; the lift has filled it
+    const u8* tab;           // H, -tau H: the call's own, affine
+    const u8* y;             // m scalars, 4-byte aligned
+    const uint64_t* r;       // host: m nonzero scalars
+    size_t m, block;         // block: resolved, >= 1
+};
+// [k] (-G) for the n scalars k in column 1 of the fold's output d_fold (rows of two), as n affine records at d_out with their infinity bytes
+// (the buffers and the index vector are the driver's: they outlive the stream's work)
+struct KzgLadderBufs { std::vector<uint32_t> col; DBuf idx, scal, pts; };
+int kzg_neg_g_ladders(const KzgIn& in, const void* d_fold, size_t n, u8* d_out, u8* d_out_inf, KzgLadderBufs& lb, hipStream_t s) {
+    DBuf &idx = lb.idx, &scal = lb.scal, &pts = lb.pts;
+    try { lb.col.resize(n); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    for (size_t k = 0; k < n; k++) lb.col[k] = (uint32_t)(2 * k + 1);
+    HIPCHK(idx.alloc(sizeof(uint32_t) * n)); HIPCHK(scal.alloc((size_t)32 * n)); HIPCHK(pts.alloc((size_t)96 * n));
+    HIPCHK(hipMemcpyAsync(idx.p, lb.col.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    groth16_gather(d_fold, idx, scal.p, 32, n, s);
+    launch_quiet(KERNEL_OF(k_kzg_neg_g1_copies), nblocks(n), s, in.g, pts.p, n);
+    return mul_dev_core(group_kernels(1), pts.as<u8>(), scal.as<u8>(), d_out, d_out_inf, n, s);
+}
+// Stage 6.  items: the openings of the failing blocks, ascending.  Synchronises.
+int kzg_recheck(const KzgIn& in, const PprodCall& c, const std::vector<uint32_t>& items, void* d_ok) {
+    const size_t nre = items.size();
+    hipStream_t s = g_stream;
+    const GroupKernels& g = group_kernels(1);
+    std::vector<uint64_t> ones, roff, zoff; std::vector<uint32_t> wi, zi;
+    FrWsumPlan rp; SegPlan zplan, iplan;
+    try {
+        ones.assign(nre, 1); roff.resize(nre + 1); zoff.resize(nre + 1); wi.resize(nre); zi.resize(2 * nre);
+        for (size_t t = 0; t <= nre; t++) { roff[t] = t; zoff[t] = 2 * t; }
+        for (size_t t = 0; t < nre; t++) { wi[t] = 2 * items[t]; zi[2 * t] = (uint32_t)t; zi[2 * t + 1] = (uint32_t)(nre + t); }
+        fr_wsum_plan(roff.data(), nre, 1, rp); segsum_plan(zoff.data(), nre, segsum_chunk_of(2 * nre), zplan); pprod_plan(zoff.data(), nre, iplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf ditems, dwi, dzi, rows, dones, rout, Z, zinf, P, Pinf, a, b, fl, okd; KzgLadderBufs lb;
+    HIPCHK(ditems.alloc(sizeof(uint32_t) * nre)); HIPCHK(dwi.alloc(sizeof(uint32_t) * nre)); HIPCHK(dzi.alloc(sizeof(uint32_t) * 2 * nre));
+    HIPCHK(rows.alloc((size_t)32 * nre)); HIPCHK(dones.alloc(sizeof(uint64_t) * nre)); HIPCHK(rout.alloc((size_t)64 * nre));
+    HIPCHK(Z.alloc((size_t)96 * 2 * nre)); HIPCHK(zinf.alloc(2 * nre)); HIPCHK(P.alloc((size_t)96 * nre)); HIPCHK(Pinf.alloc(nre));
+    HIPCHK(a.alloc((size_t)96 * 2 * nre)); HIPCHK(b.alloc((size_t)192 * 2 * nre)); HIPCHK(fl.alloc(2 * nre)); HIPCHK(okd.alloc(nre));
+    HIPCHK(hipMemcpyAsync(ditems.p, items.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dwi.p, wi.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dzi.p, zi.data(), sizeof(uint32_t) * 2 * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dones.p, ones.data(), sizeof(uint64_t) * nre, hipMemcpyHostToDevice, s));
+    prof_mark(KERNEL_OF(k_gather_records16).name);                         // one segment: the gathers
+    groth16_gather(in.y, ditems, rows.p, 32, nre, s);
+    groth16_gather(in.wp, dwi, Z.p, 96, nre, s);                           // W_j, with the flag byte its pair got (bit 0: at infinity)
+    launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(nre), s, c.pflag.p, dwi.p, zinf.p, nre);
+    prof_mark(nullptr);
+    int rc = fr_wsum_dev(rp, rows.p, 1, dones.p, nre, rout.p, s); if (rc) return rc;   // every row: 1, y_j mod r
+    rc = kzg_neg_g_ladders(in, rout.p, nre, Z.as<u8>() + (size_t)96 * nre, zinf.as<u8>() + nre, lb, s); if (rc) return rc;
+    rc = segsum_dev(g, false, Z.p, zinf.as<u8>(), 2 * nre, dzi.as<u32>(), zplan, P.as<u8>(), Pinf.as<u8>(), 1, s); if (rc) return rc;
+    launch(KERNEL_OF(k_kzg_recheck_pairs), tuple_blocks(Layout::row, 2 * nre), s, P.p, Pinf.p, in.wp, in.tab, ditems.p, in.m, a.p, b.p, fl.p, nre);
+    prof_mark(nullptr);
+    return pprod_recheck_dense(a.as<u8>(), b.as<u8>(), fl.as<u8>(), 2 * nre, iplan, ditems.as<u32>(), okd.p, d_ok);
+}
+// d_ok: m verdict bytes on the device.  Synchronises.
+int kzg_core(const KzgIn& in, void* d_ok, bool* held, size_t* rechecked) {
+    const size_t m = in.m, np = 2 * m;
+    hipStream_t s = g_stream;
+    *rechecked = 0;
+    std::vector<uint64_t> seg_off, boff; std::vector<uint32_t> q_idx;
+    blsmi_route::PprodLocatePlan pl; blsmi_route::PprodLocateFailing ff;
+    FrWsumPlan fp;
+    PprodCall c; PprodCellBufs b;
+    size_t C0 = 0, B = 0;
+    try {
+        seg_off.resize(m + 1); q_idx.resize(np);
+        for (size_t j = 0; j < m; j++) { seg_off[j] = 2 * j; q_idx[2 * j] = 0; q_idx[2 * j + 1] = 1; }
+        seg_off[m] = np;
+        if (!blsmi_route::pprod_locate_plan(seg_off.data(), m, q_idx.data(), np, 2, in.block, pl)) return BLSMI_E_ARG;   // stage 1
+        C0 = pl.cells(); B = pl.blocks();
+        const uint32_t further[1] = {0};                                   // H again: the cell of s_b (-G)
+        blsmi_route::pprod_locate_append_cells(pl, further, 1);
+        boff.resize(B + 1);
+        for (size_t k = 0; k < B; k++) boff[k] = pl.item_lo(k);
+        boff[B] = m;
+        fr_wsum_plan(boff.data(), B, 1, fp); pprod_plan(pl.slot_off.data(), B, b.bplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t C = pl.cells(), dg = pl.entry_of.size();
+    DBuf t, dent, fout; KzgLadderBufs lb;
+    HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
+    HIPCHK(b.dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(b.dent.alloc(sizeof(uint32_t) * C)); HIPCHK(b.bblob.alloc(b.bplan.blob.size()));
+    HIPCHK(fout.alloc((size_t)64 * B));
+    HIPCHK(hipMemcpyAsync(dent.p, pl.entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(b.dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.bblob.p, b.bplan.blob.data(), b.bplan.blob.size(), hipMemcpyHostToDevice, s));
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, in.tab, dent.p, t.p, 48, dg);   // the table in the plan's order
+    const PprodRlcIn pin{in.wp, true, nullptr, t.as<u8>(), in.r, seg_off.data(), np, m};
+    int rc = pprod_weighted_sums(c, pin, pprod_segments(pl, pl.cell_off, B), B, route_load(C)); if (rc) return rc;   // stage 3
+    rc = fr_wsum_dev(fp, in.y, 1, c.dr.p, B, fout.p, s); if (rc) return rc;   // stage 4: every block: t_b, s_b
+    rc = kzg_neg_g_ladders(in, fout.p, B, c.S.as<u8>() + (size_t)96 * C0, c.sinf.as<u8>() + C0, lb, s); if (rc) return rc;
+    rc = pprod_locate_failing_blocks(c, pl, b, d_ok, held, ff);             // stage 5
+    if (rc || *held) return rc;
+    if (ff.items.empty()) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }   // (cannot be: the total is the product of the block values)
+    rc = kzg_recheck(in, c, ff.items, d_ok);                                // stage 6
+    if (!rc) *rechecked = ff.items.size();
+    return rc;
+}
+// What every form checks before any device work; m beyond 2^31 - 2 is refused (the pairs W_j, pi_j are 32-bit indices).
+int kzg_check_args(bool pointers_ok, size_t m, const uint64_t* scalars) {
+    if (m > 0x7ffffffeull || !pointers_ok) return BLSMI_E_ARG;
+    return rlc_check_args(true, scalars, m);
+}
+const uint32_t KZG_TAU_H[1] = {1};                                        // srs_g2 is H, tau H
+// H and -tau H, the call's table, from the key's two affine records on the device (4-byte aligned)
+int kzg_table(const void* d_srs_g2_aff, u8* d_tab, hipStream_t s) {
+    DBuf order; HIPCHK(order.alloc(sizeof KZG_TAU_H));
+    HIPCHK(hipMemcpyAsync(order.p, KZG_TAU_H, sizeof KZG_TAU_H, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_tab, d_srs_g2_aff, 192, hipMemcpyDeviceToDevice, s));
+    launch_quiet(KERNEL_OF(k_g2_neg_records), 1, s, d_srs_g2_aff, order.p, d_tab + 192, 1);
+    return BLSMI_OK;
+}
+// Stage 2: W_j = C_j + z_j pi_j and pi_j into the interleaved buffer.  d_c, d_p: m affine records each, 4-byte aligned.
+int kzg_lift(const u8* d_c, const u8* d_p, const u8* d_z, u8* d_wp, size_t m, hipStream_t s) {
+    DBuf winf; HIPCHK(winf.alloc(m));                                      // (the sums read the all-zero record; released in stream order)
+    int rc = mul_add_dev_core(d_c, 96, d_p, 96, d_z, d_wp, 192, winf.as<u8>(), m, s); if (rc) return rc;
+    launch_quiet(KERNEL_OF(k_kzg_place_proofs), nblocks((size_t)24 * m), s, d_p, d_wp, m);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int kzg_host(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* commitments, const uint8_t* proofs, const uint8_t* z, const uint8_t* y, size_t m,
+             const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = kzg_check_args(srs_g1 && srs_g2 && commitments && proofs && z && y && ok, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    DBuf g, k2, dc, dp, dz, dy, wp, tab, dok;
+    HIPCHK(g.alloc(96)); HIPCHK(k2.alloc(192 * 2)); HIPCHK(dc.alloc((size_t)96 * m)); HIPCHK(dp.alloc((size_t)96 * m)); HIPCHK(dz.alloc((size_t)32 * m)); HIPCHK(dy.alloc((size_t)32 * m));
+    HIPCHK(wp.alloc((size_t)192 * m)); HIPCHK(tab.alloc(192 * 2)); HIPCHK(dok.alloc(m));
+    rc = upload_points(group_kernels(1), jac, srs_g1, g.p, 1, s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, srs_g2, k2.p, 2, s); if (rc) return rc;
+    rc = upload_points(group_kernels(1), jac, commitments, dc.p, m, s); if (rc) return rc;
+    rc = upload_points(group_kernels(1), jac, proofs, dp.p, m, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)32 * m, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dy.p, y, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    rc = kzg_table(k2.p, tab.as<u8>(), s); if (rc) return rc;
+    rc = kzg_lift(dc.as<u8>(), dp.as<u8>(), dz.as<u8>(), wp.as<u8>(), m, s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const KzgIn in{g.as<u8>(), wp.as<u8>(), tab.as<u8>(), dy.as<u8>(), scalars, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = kzg_core(in, dok.p, &held, &nre); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ok, dok.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+// the _dev forms: affine records are read where they lie, whatever their alignment (the lift reads words); in-memory records are converted
+int kzg_dev_api(const void* d_srs_g1, const void* d_srs_g2, const void* d_commitments, const void* d_proofs, const void* d_z, const void* d_y, size_t m,
+                const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = kzg_check_args(d_srs_g1 && d_srs_g2 && d_commitments && d_proofs && d_z && d_y && d_ok, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    hipStream_t s = g_stream;
+    DBuf g, k2, dc, dp, wp, tab;
+    HIPCHK(wp.alloc((size_t)192 * m)); HIPCHK(tab.alloc(192 * 2));
+    const u8 *pg = (const u8*)d_srs_g1, *pc = (const u8*)d_commitments, *pp = (const u8*)d_proofs; const void* pk2 = d_srs_g2;
+    if (jac) {
+        HIPCHK(g.alloc(96)); HIPCHK(k2.alloc(192 * 2)); HIPCHK(dc.alloc((size_t)96 * m)); HIPCHK(dp.alloc((size_t)96 * m));
+        rc = jac_to_wire_dev(group_kernels(1), d_srs_g1, g.p, nullptr, 1, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(2), d_srs_g2, k2.p, nullptr, 2, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(1), d_commitments, dc.p, nullptr, m, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(1), d_proofs, dp.p, nullptr, m, s); if (rc) return rc;
+        pg = g.as<u8>(); pk2 = k2.p; pc = dc.as<u8>(); pp = dp.as<u8>();
+    }
+    rc = kzg_table(pk2, tab.as<u8>(), s); if (rc) return rc;
+    rc = kzg_lift(pc, pp, (const u8*)d_z, wp.as<u8>(), m, s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const KzgIn in{pg, wp.as<u8>(), tab.as<u8>(), (const u8*)d_y, scalars, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = kzg_core(in, d_ok, &held, &nre); if (rc) return rc;
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_kzg_verify_batch(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* commitments, const uint8_t* proofs, const uint8_t* z, const uint8_t* y, size_t m,
+                                     const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked) {
+    return kzg_host(srs_g1, srs_g2, commitments, proofs, z, y, m, scalars, block, ok, combined, rechecked, false);
+}
+BLSMI_API int blsmi_kzg_verify_batch_jac(const uint64_t* srs_g1_jac, const uint64_t* srs_g2_jac, const uint64_t* commitments_jac, const uint64_t* proofs_jac, const uint8_t* z, const uint8_t* y, size_t m,
+                                         const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked) {
+    return kzg_host(reinterpret_cast<const uint8_t*>(srs_g1_jac), reinterpret_cast<const uint8_t*>(srs_g2_jac), reinterpret_cast<const uint8_t*>(commitments_jac),
+                    reinterpret_cast<const uint8_t*>(proofs_jac), z, y, m, scalars, block, ok, combined, rechecked, true);
+}
+BLSMI_API int blsmi_kzg_verify_batch_dev(const void* d_srs_g1, const void* d_srs_g2, const void* d_commitments, const void* d_proofs, const void* d_z, const void* d_y, size_t m,
+                                         const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
+    return kzg_dev_api(d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, scalars, block, d_ok, combined, rechecked, stream, false);
+}
+BLSMI_API int blsmi_kzg_verify_batch_jac_dev(const void* d_srs_g1_jac, const void* d_srs_g2_jac, const void* d_commitments_jac, const void* d_proofs_jac, const void* d_z, const void* d_y, size_t m,
+                                             const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
+    return kzg_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, scalars, block, d_ok, combined, rechecked, stream, true);
 }

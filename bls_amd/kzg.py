@@ -1,0 +1,93 @@
+"""KZG batches (blsmi 0.20): blsmi_kzg_verify_batch[_jac|_dev|_jac_dev] and the G1 lift blsmi_g1_mul_add_batch[_dev] they are built on,
+over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
+happens in the HIP kernels; a missing library or device raises, nothing falls back."""
+import ctypes as C
+
+import numpy as np
+
+from . import engine as _e
+
+
+def _stride(stride, what):
+    stride = int(stride)
+    if stride != 0 and (stride < 96 or stride % 4):
+        raise ValueError("%s is 0 (one common record) or a multiple of 4 that is at least 96, got %d" % (what, stride))
+    return stride
+
+
+def _strided(x, stride, n, what):
+    """n affine G1 records `stride` bytes apart as a byte array of exactly the span they cover"""
+    a = _e._u8(x)
+    need = stride * (n - 1) + 96 if n else 0
+    if a.size != need:
+        raise ValueError("%s: expected %d bytes (%d records %d apart), got %d" % (what, need, n, stride, a.size))
+    return a
+
+
+def g1_mul_add_batch(a, b, scalars, n, a_stride=96, b_stride=96):
+    """blsmi_g1_mul_add_batch -> (out (n, 96) uint8, inf (n,) bool): out[j] = A_j + (k_j mod r) * B_j.  a, b: affine records a_stride /
+    b_stride bytes apart (0: one common record), exactly the bytes the n records span; scalars: n values of 32 big-endian bytes, any
+    256-bit value.  Every B_j lies in the prime-order subgroup (see engine.g1_mul_batch); A_j may be any curve point."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n is a number of items, got %d" % n)
+    a_stride, b_stride = _stride(a_stride, "a_stride"), _stride(b_stride, "b_stride")
+    pa, pb = _strided(a, a_stride, n, "a"), _strided(b, b_stride, n, "b")
+    k = _e._u8(scalars, 32 * n)
+    out = np.zeros((n, 96), dtype=np.uint8)
+    inf = np.zeros(n, dtype=np.uint8)
+    _e._call("blsmi_g1_mul_add_batch", _e._p8(pa), a_stride, _e._p8(pb), b_stride, _e._p8(k), _e._p8(out.reshape(-1)), _e._p8(inf), n)
+    return out, inf.astype(bool)
+
+
+def g1_mul_add_batch_dev(d_a, a_stride, d_b, b_stride, d_scalars, d_out, d_out_inf, n, stream=0):
+    """device-pointer form (ints); the n dense records are in d_out and the infinity bytes in d_out_inf when the call returns"""
+    _e._call("blsmi_g1_mul_add_batch_dev", d_a, _stride(a_stride, "a_stride"), d_b, _stride(b_stride, "b_stride"), d_scalars, d_out, d_out_inf, n, stream)
+
+
+def _verify(name, jac, srs_g1, srs_g2, commitments, proofs, z, y, scalars, block):
+    pb, qb = (144, 288) if jac else (96, 192)
+    g, h = _e._u8(srs_g1, pb), _e._u8(srs_g2, 2 * qb)
+    c, p = _e._u8(commitments), _e._u8(proofs)
+    if c.size % pb or p.size != c.size:
+        raise ValueError("expected m*%d bytes of C_j and as many of pi_j, got %d and %d" % (pb, c.size, p.size))
+    m = c.size // pb
+    zz, yy = _e._u8(z, 32 * m), _e._u8(y, 32 * m)
+    pr = _e._scalars(scalars, m)
+    block = _e._block(block)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    g, h, c, p = (_e._recs(v, v.size, jac) for v in (g, h, c, p))
+    _e._call(name, g, h, c, p, _e._p8(zz), _e._p8(yy), m, pr, block, _e._p8(ok), C.byref(comb), C.byref(nre))
+    return ok[:m].copy(), comb.value, nre.value
+
+
+def verify_batch(srs_g1, srs_g2, commitments, proofs, z, y, scalars=None, block=0):
+    """blsmi_kzg_verify_batch -> (ok (m,) uint8, combined, rechecked): m KZG openings under one key.  srs_g1: G (96 bytes); srs_g2: H, tau H
+    (192 each); commitments: C_j; proofs: pi_j (96 each); z, y: m scalars of 32 big-endian bytes each, any value taken mod r.  ok[j] is the
+    verdict of engine.pairing_product_batch on (C_j + z_j pi_j - y_j G, H), (pi_j, -tau H); scalars and block as
+    engine.pairing_product_batch_rlc_locate."""
+    return _verify("blsmi_kzg_verify_batch", False, srs_g1, srs_g2, commitments, proofs, z, y, scalars, block)
+
+
+def verify_batch_jac(srs_g1_jac, srs_g2_jac, commitments_jac, proofs_jac, z, y, scalars=None, block=0):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _verify("blsmi_kzg_verify_batch_jac", True, srs_g1_jac, srs_g2_jac, commitments_jac, proofs_jac, z, y, scalars, block)
+
+
+def _verify_dev(name, d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, d_ok, scalars, block, stream):
+    pr = _e._scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _e._call(name, d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, pr, _e._block(block), d_ok, C.byref(comb), C.byref(nre), stream)
+    return comb.value, nre.value
+
+
+def verify_batch_dev(d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, d_ok, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_ok when the call returns; scalars stay on the host.
+    -> (combined, rechecked)"""
+    return _verify_dev("blsmi_kzg_verify_batch_dev", d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, d_ok, scalars, block, stream)
+
+
+def verify_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, d_ok, scalars=None, block=0, stream=0):
+    """device-pointer form over in-memory points -> (combined, rechecked)"""
+    return _verify_dev("blsmi_kzg_verify_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, d_ok, scalars, block, stream)

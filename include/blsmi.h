@@ -91,9 +91,10 @@ void blsmi_shutdown(void);
  * batches that find the bad items by blocks (blsmi_pairing_product_batch_rlc_locate[_jac|_dev|_jac_dev]); no existing prototype changes, no
  * new option.  0.19 adds arithmetic mod r -- the weighted segmented fold of scalars (blsmi_fr_wsum_segmented_u64[_dev]) -- and the Groth16
  * batches that fold their public inputs with it (blsmi_groth16_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new
- * option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18 and 0.19 by the presence of
- * those symbols. */
+ * option.  0.20 adds the lift out = A + k * B in G1 (blsmi_g1_mul_add_batch[_dev]) and the KZG batches that fold their values mod r
+ * (blsmi_kzg_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19 and 0.20 by the presence
+ * of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -1065,6 +1066,68 @@ int blsmi_groth16_verify_batch_dev(const void *d_vk_g1, const void *d_vk_g2, siz
 int blsmi_groth16_verify_batch_jac_dev(const void *d_vk_g1_jac, const void *d_vk_g2_jac, size_t nin, const void *d_proof_g1_jac, const void *d_proof_g2_jac,
                                        const void *d_inputs, size_t m, const uint64_t *scalars, size_t block, void *d_ok, int *combined, size_t *rechecked,
                                        void *stream);
+
+/* ---- the G1 lift and KZG batches (blsmi 0.20) ----------------------------------------------------------------------------------------------
+ * out[j] = A_j + (k_j mod r) * B_j in G1, one lane per item in ONE kernel (k_g1_mul_add_glv): the endomorphism ladder of
+ * blsmi_g1_mul_batch on B_j, one mixed addition of A_j into its Jacobian result, and the one inversion the ladder pays anyway -- no second
+ * launch, no second trip through affine records.  a, b: affine records a_stride / b_stride bytes apart -- 0: one common record; otherwise a
+ * multiple of 4 that is at least 96 -- so that points interleaved with other data are read where they lie; scalars: n values of 32
+ * big-endian bytes, ANY 256-bit value is taken mod r.  out: n dense records; out_inf[j] = 1 and the all-zero record for a result at infinity.
+ * As blsmi_g1_mul_batch, every B_j lies in the prime-order subgroup (blsmi_g1_check_batch establishes that); A_j may be any curve point.
+ * The all-zero record is the point at infinity on either side; A_j = k_j * B_j (the addition is a doubling) and A_j = -k_j * B_j are served.
+ *   - BLSMI_E_ARG before any device work: a NULL pointer with n > 0, a stride that is neither 0 nor a multiple of 4 from 96 up, n beyond
+ *     2^32 - 1.  n = 0: BLSMI_OK.
+ *   - _dev: every buffer on one of the library's devices, 4-byte aligned; `stream` as in blsmi_pairing_batch_dev; the inputs stay untouched. */
+int blsmi_g1_mul_add_batch(const uint8_t *a /* n records a_stride apart */, size_t a_stride, const uint8_t *b, size_t b_stride,
+                           const uint8_t *scalars /* n*32 */, uint8_t *out /* n*96 */, uint8_t *out_inf /* n */, size_t n);
+int blsmi_g1_mul_add_batch_dev(const void *d_a, size_t a_stride, const void *d_b, size_t b_stride, const void *d_scalars, void *d_out, void *d_out_inf,
+                               size_t n, void *stream);
+/* m KZG openings under one key, from the commitments, the evaluation points, the values and the proofs themselves: no point
+ * P_j = C_j - y_j * G + z_j * pi_j is asked of the caller.  srs_g1: G (1 record); srs_g2: H, tau * H (2 records); commitments: C_j (m
+ * records); proofs: pi_j (m records); z, y: m scalars each, 32-byte big-endian, any value taken mod r.  scalars / block / ok / combined /
+ * rechecked exactly as blsmi_pairing_product_batch_rlc_locate.
+ * Verdicts: ok[j] is exactly is_one[j] of blsmi_pairing_product_batch on the two pairs (P_j, H), (pi_j, -tau * H), with
+ * P_j = C_j + (z_j mod r) * pi_j - (y_j mod r) * G.  Infinity (the all-zero affine record, z == 0 in an in-memory record) follows
+ * blsmi_pairing_product_batch: the pair contributes 1; an all-zero srs_g2 entry drops its pairs.
+ * The path that holds: W_j = C_j + z_j * pi_j by the lift above (one endomorphism ladder per item: z_j differs per item), written straight
+ * into the interleaved (W_j, pi_j) array of the two pairs; then per block b of the 0.18 rule (block = 0: max(64, ceil(m / 256))), with the
+ * weights r_j,
+ *     sum_{j in b} r_j * P_j = sum_{j in b} r_j * W_j - s_b * G,        s_b = sum_{j in b} r_j * y_j mod r
+ * -- the 0.19 fold over one column, the blocks as its segments -- so a block costs the two 64-bit weighted sums of 0.18, ONE full-width
+ * ladder (s_b over -G; s_b = 0 gives infinity and the cell is left out) and three Miller loops: sum r_j * W_j against H, s_b * (-G) against
+ * H, sum r_j * pi_j against -tau * H; the blocks' products, the total and one final exponentiation are those of 0.18.  On this path no
+ * y_j * G exists.  When the total fails the block values are final-exponentiated, and for the items of the failing blocks, and only those,
+ * P_j is built from the W_j already there (y_j mod r by the fold, one ladder over -G and a two-point sum each; the lift never runs twice) and
+ * the two pairs go through blsmi_pairing_product_batch's own path; *rechecked is the number of those items.
+ * Soundness: the fold and the lift give the same group elements as the per-item points only for G and pi_j of order r, so 0.17's
+ * precondition applies to every key, commitment and proof point: they lie in the prime-order subgroups (blsmi_g?_check_batch establishes
+ * that).  Under it a block whose equation holds has a failing item with probability at most 2^-64 over the drawn scalars; caller scalars
+ * carry 0.17's caveat.
+ *   - BLSMI_E_ARG before any device work: a NULL key, point, scalar-array or ok pointer with m > 0; a zero caller scalar; m beyond
+ *     2^31 - 2 (the pairs W_j, pi_j are 32-bit indices; 2^32 - 1 and beyond included).
+ *   - m = 0: BLSMI_OK, *combined = 0.  *rechecked = 0 on every early return.  No `block` value is refused.
+ *   - _jac: points as G1Projective / G2Projective records (144 / 288 bytes); _dev: everything but scalars / combined / rechecked resident
+ *     on one of the library's devices (4-byte aligned), `stream` as in blsmi_pairing_batch_dev; the caller's buffers stay untouched.
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * When to call it (one MI355X, everything resident, block = 0, against the composite a caller had before -- blsmi_g1_mul_batch_dev for
+ * z_j * pi_j and, with d_pts = NULL, for (r - y_j) * G, blsmi_g1_sum_segmented_dev over the three points,
+ * blsmi_pairing_product_batch_rlc_locate_dev -- the two alternating, median of 20 +- spread in ms; DESIGN.md 3u has the table and the
+ * stages): for any batch the 0.18 call would serve when the P_j do not exist yet.  All valid: 16 384 openings 7.1 +- 0.1 against
+ * 10.6 +- 0.6, 65 536 11.9 +- 1.6 against 24.1 +- 0.4; one bad value: 10.8 against 13.1 and 14.4 against 26.6.  What 0.17 says about a few
+ * thousand items or fewer holds here too: at 2 048 the call takes 6.5 ms and the composite 5.9. */
+int blsmi_kzg_verify_batch(const uint8_t *srs_g1 /* 96 */, const uint8_t *srs_g2 /* 2*192 */, const uint8_t *commitments /* m*96 */,
+                           const uint8_t *proofs /* m*96 */, const uint8_t *z /* m*32 */, const uint8_t *y /* m*32 */, size_t m,
+                           const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */,
+                           uint8_t *ok /* m */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_kzg_verify_batch_jac(const uint64_t *srs_g1_jac /* 18 */, const uint64_t *srs_g2_jac /* 2*36 */, const uint64_t *commitments_jac /* m*18 */,
+                               const uint64_t *proofs_jac /* m*18 */, const uint8_t *z, const uint8_t *y, size_t m, const uint64_t *scalars, size_t block,
+                               uint8_t *ok, int *combined, size_t *rechecked);
+int blsmi_kzg_verify_batch_dev(const void *d_srs_g1, const void *d_srs_g2, const void *d_commitments, const void *d_proofs, const void *d_z, const void *d_y, size_t m,
+                               const uint64_t *scalars /* host: m, may be NULL */, size_t block, void *d_ok, int *combined /* host */,
+                               size_t *rechecked /* host */, void *stream);
+int blsmi_kzg_verify_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_commitments_jac, const void *d_proofs_jac,
+                                   const void *d_z, const void *d_y, size_t m, const uint64_t *scalars, size_t block, void *d_ok, int *combined, size_t *rechecked,
+                                   void *stream);
 
 #ifdef __cplusplus
 }
