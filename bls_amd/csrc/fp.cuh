@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace blsmi {
 
@@ -97,6 +98,14 @@ struct Fp {
 };
 using FpS = Fp<1, VSTORE>;             // storage type: (near-)normalised limbs, |value| <= VSTORE q / VU
 using FpC = Fp<1, VU>;                 // canonical: limbs in [0,2^LB), value in [0,q)
+using FpR = Fp<1, VRED>;               // reduced: what fp_reduce returns.  Sums of a few FpR still multiply in one pass where sums of FpS do not (28-bit limbs)
+// The type the pairing's Fq12 values travel in between operations: with 28-bit limbs the reduced type -- every Fq12 result is value-reduced
+// anyway, and remembering it saves the operand reductions of the next operation -- with 27-bit limbs, where nothing is ever reduced, FpS.
+#ifdef BLSMI_LIMBS28
+using FpW = FpR;
+#else
+using FpW = FpS;
+#endif
 
 }  // namespace blsmi
 #include "tower_fwd.cuh"
@@ -199,17 +208,28 @@ BLSMI_DEV Fp<1, VRED> fp_reduce(const Fp<L, V>& x) {
     const Fp<L, V>& y = x;
     const float top = (float)y.v[NL - 1] * (float)(1 << LB) + (float)y.v[NL - 2];
     const i32 k = (i32)floorf(top * BLSMI_Q_TOP2_INV);
+    // The carry travels in 32 bits and joins the limb BEFORE the multiply-add: |k| <= VMAX / VU + 1 and q_i < 2^LB, so the carry out of a
+    // column, floor((y_i + c - k q_i) / 2^LB), is below 2^(31 - LB) + VMAX / VU + 2 < 2^13 in magnitude, and y_i + c, at most
+    // LMAX (2^LB + 64) + 2^13, stays inside int32.  One sign-extended addend per multiply-add and a 32-bit funnel shift for the carry
+    // (5 instructions a limb, two of them 8-byte encodings) instead of a 64-bit add and a 64-bit shift (6 and three); same integers.
+    static_assert((i64)LMAX * ((1ll << LB) + 64) + (1ll << 13) < (1ll << 31), "limb plus carry must fit int32");
+    static_assert((1 << (31 - LB)) + VMAX / VU + 2 < (1 << 13), "carry bound");
     Fp<1, VRED> r;
-    i64 c = 0;
+    i32 c = 0;
 #pragma unroll
     for (int i = 0; i < NL - 1; i++) {
-        c += (i64)y.v[i] - (i64)k * C_Q[i];
-        r.v[i] = (i32)c & MASK;
-        c >>= LB;
+        const i64 s = (i64)(y.v[i] + c) - (i64)k * C_Q[i];
+        r.v[i] = (i32)s & MASK;
+        c = (i32)(s >> LB);
     }
-    c += (i64)y.v[NL - 1] - (i64)k * C_Q[NL - 1];
-    r.v[NL - 1] = (i32)c;
+    r.v[NL - 1] = (i32)((i64)(y.v[NL - 1] + c) - (i64)k * C_Q[NL - 1]);
     return r;
+}
+// fp_reduced(x): x in the reduced type FpR with the least work -- a value already inside the bound is only normalised, every other one is
+// value-reduced.  The bound travels in the type from here on; FpR widens to FpS through fp_relabel and nothing narrows.
+template <int L, int V>
+BLSMI_DEV Fp<1, VRED> fp_reduced(const Fp<L, V>& x) {
+    if constexpr (V <= VRED) return fp_relabel<1, VRED>(fp_norm(x)); else return fp_reduce(x);
 }
 // fp_fit<VT>(x): x itself when its value bound is at most VT, else its reduction -- how products make their operands fit
 template <int VT, int L, int V>

@@ -14,6 +14,12 @@ template <int L_, int V_> struct Fp12 { static constexpr int L = L_, V = V_; Fp6
 using Fp2S = Fp2<FpS::L, FpS::V>;
 using Fp6S = Fp6<FpS::L, FpS::V>;
 using Fp12S = Fp12<FpS::L, FpS::V>;
+using Fp2R = Fp2<FpR::L, FpR::V>;                    // every coefficient value-reduced (fp.cuh: FpR); Fp*W: what the pairing's values travel in (FpW)
+using Fp6R = Fp6<FpR::L, FpR::V>;
+using Fp12R = Fp12<FpR::L, FpR::V>;
+using Fp2W = Fp2<FpW::L, FpW::V>;
+using Fp6W = Fp6<FpW::L, FpW::V>;
+using Fp12W = Fp12<FpW::L, FpW::V>;
 
 BLSMI_DEV i32 lane_odd() { return -(i32)(threadIdx.x & 1); }                       // all-ones on odd lanes
 BLSMI_DEV i32 bfi(i32 mask, i32 a, i32 b) {                                            // (a & mask) | (b & ~mask) in one VALU op
@@ -48,6 +54,7 @@ template <int K, int L, int V> BLSMI_DEV auto fp2_muls(const Fp2<L, V>& a) { ret
 template <int L, int V> BLSMI_DEV auto fp2_conj(const Fp2<L, V>& a) { return wrap(fp_cneg(lane_odd(), a.c)); }
 template <int L, int V> BLSMI_DEV auto fp2_norm(const Fp2<L, V>& a) { return wrap(fp_norm(a.c)); }
 template <int L, int V> BLSMI_DEV Fp2S fp2_store(const Fp2<L, V>& a) { return wrap(fp_store(a.c)); }
+template <int L, int V> BLSMI_DEV Fp2R fp2_reduced(const Fp2<L, V>& a) { return wrap(fp_reduced(a.c)); }
 template <int L, int V> BLSMI_DEV bool fp2_is_zero(const Fp2<L, V>& a) {
     const int z = fp_is_zero(a.c) ? 1 : 0;
     return (z & __shfl_xor(z, 1)) != 0;

@@ -27,6 +27,7 @@ template <int K, int L, int V> BLSMI_DEV auto fp2_muls(const Fp2<L, V>& a) { ret
 template <int L, int V> BLSMI_DEV auto fp2_conj(const Fp2<L, V>& a) { return make_fp2(a.c0, fp_neg(a.c1)); }
 template <int L, int V> BLSMI_DEV auto fp2_norm(const Fp2<L, V>& a) { return make_fp2(fp_norm(a.c0), fp_norm(a.c1)); }
 template <int L, int V> BLSMI_DEV Fp2S fp2_store(const Fp2<L, V>& a) { Fp2S r; r.c0 = fp_store(a.c0); r.c1 = fp_store(a.c1); return r; }
+template <int L, int V> BLSMI_DEV Fp2R fp2_reduced(const Fp2<L, V>& a) { Fp2R r; r.c0 = fp_reduced(a.c0); r.c1 = fp_reduced(a.c1); return r; }
 template <int L, int V> BLSMI_DEV bool fp2_is_zero(const Fp2<L, V>& a) { return fp_is_zero(a.c0) & fp_is_zero(a.c1); }
 template <int La, int Va, int Lb, int Vb> BLSMI_DEV bool fp2_eq(const Fp2<La, Va>& a, const Fp2<Lb, Vb>& b) { return fp2_is_zero(fp2_sub(a, b)); }
 template <int L, int V> BLSMI_DEV Fp2<L, V> fp2_select(i32 m, const Fp2<L, V>& a, const Fp2<L, V>& b) { Fp2<L, V> r; r.c0 = fp_select(m, a.c0, b.c0); r.c1 = fp_select(m, a.c1, b.c1); return r; }

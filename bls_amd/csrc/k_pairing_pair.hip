@@ -48,15 +48,17 @@ __global__ void __launch_bounds__(WG, BLSMI_PAIR_WAVES) k_debug_pairl(int op, co
         if (t0 < n) pair_rec_store<3>(out, t, par, reinterpret_cast<const FpS*>(&r));
     } else {
         P2::Fp12S x, y, r; pair_rec_load<6>(reinterpret_cast<FpS*>(&x), a, t, par); y = x; if (b) pair_rec_load<6>(reinterpret_cast<FpS*>(&y), b, t, par);
+        const P2::Fp12W xw = P2::fp12_work(x), yw = P2::fp12_work(y);   // the out-of-line routines take and return the working type
+        P2::Fp12W rw = xw;
         switch (op) {
-            case BLSMI_OP_FQ12_MUL: P2::nf_fp12_mul(r, x, y); break;
-            case BLSMI_OP_FQ12_SQR: P2::nf_fp12_sqr(r, x); break;
-            case BLSMI_OP_FQ12_INV: P2::nf_fp12_inv(r, x); break;
-            case BLSMI_OP_FQ12_FROB1: P2::nf_fp12_frob1(r, x); break;
-            case BLSMI_OP_FQ12_FROB2: P2::nf_fp12_frob2(r, x); break;
-            case BLSMI_OP_FQ12_FROB3: P2::nf_fp12_frob3(r, x); break;
-            case BLSMI_OP_FQ12_CYCLO_SQR: P2::nf_fp12_cyc_sqr(r, x); break;
-            case BLSMI_OP_FQ12_CYCLO_RUN16: r = P2::cyc_sqr_run(x, 16); break;
+            case BLSMI_OP_FQ12_MUL: P2::nf_fp12_mul(rw, xw, yw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_SQR: P2::nf_fp12_sqr(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_INV: P2::nf_fp12_inv(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_FROB1: P2::nf_fp12_frob1(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_FROB2: P2::nf_fp12_frob2(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_FROB3: P2::nf_fp12_frob3(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_CYCLO_SQR: P2::nf_fp12_cyc_sqr(rw, xw); r = P2::fp12_widen(rw); break;
+            case BLSMI_OP_FQ12_CYCLO_RUN16: r = P2::fp12_widen(P2::cyc_sqr_run(xw, 16)); break;
             case BLSMI_OP_FQ12_MUL_BY_014: r = P2::fp12_store(P2::fp12_mul_by_014(x, y.c0.c0, y.c0.c1, y.c0.c2)); break;
             default: {
                 const P2::LinePair m = P2::line_pair_product(y.c0.c0, y.c0.c1, y.c0.c2, y.c1.c0, y.c1.c1, y.c1.c2);

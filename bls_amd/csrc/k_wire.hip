@@ -215,7 +215,7 @@ KERNEL k_debug_fq(int op, const u64* a, const u64* b, u64* out, u8* flag, size_t
     if (t >= n) return;
     const FpS x = load_m384(a + 6 * t);
     FpS y = fp_zero();
-    if (op == BLSMI_OP_FQ_MUL || op == BLSMI_OP_FQ_ADD || op == BLSMI_OP_FQ_SUB || op == BLSMI_OP_FQ_CMP) y = load_m384(b + 6 * t);
+    if (op == BLSMI_OP_FQ_MUL || op == BLSMI_OP_FQ_ADD || op == BLSMI_OP_FQ_SUB || op == BLSMI_OP_FQ_CMP || op == BLSMI_OP_FQ_LAZY) y = load_m384(b + 6 * t);
     FpS r = fp_zero();
     bool ok = true;
     int code = -1;
@@ -236,6 +236,15 @@ KERNEL k_debug_fq(int op, const u64* a, const u64* b, u64* out, u8* flag, size_t
         case BLSMI_OP_FQ_NEG: r = fp_store(fp_neg(x)); break;
         case BLSMI_OP_FQ_INV: r = fp_inv(x); ok = !fp_is_zero(x); break;
         case BLSMI_OP_FQ_SQRT: r = fp_sqrt(x, ok); break;
+        case BLSMI_OP_FQ_LAZY: {                                                                     // fp_reduce at the bounds the types allow: (1029 xy + 4x)(4y - 1029 xy)
+            // 343 p by three un-normalised multiples of 7 (limbs up to LMAX), tripled, plus / minus four times a stored value: limbs at
+            // 7 (2^LB + 64), values near +-1 500 q -- three quarters of VMAX as typed -- into a value reduction each, then one product
+            const auto p = fp_mul(x, y);
+            const auto big = fp_muls<3>(fp_norm(fp_muls<7>(fp_norm(fp_muls<7>(fp_norm(fp_muls<7>(p)))))));
+            const auto hi = fp_add(big, fp_muls<4>(x)), lo = fp_sub(fp_muls<4>(y), big);
+            static_assert(decltype(hi)::L == 7 && decltype(lo)::L == 7 && 4 * decltype(hi)::V > 3 * VMAX, "the chain reaches the bounds it is here for");
+            r = fp_store(fp_mul(fp_reduce(hi), fp_reduce(lo))); break;
+        }
     }
     store_m384(out + 6 * t, r);
     if (flag) flag[t] = code >= 0 ? (u8)code : (ok ? 1 : 0);

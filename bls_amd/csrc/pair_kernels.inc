@@ -39,11 +39,11 @@ BLSMI_DEV void pair_yield_enter() {
 struct PairYieldOps : P2::Fp12Ops {
     static BLSMI_DEV void before_exp_x(int k) { if (k == PAIR_YIELD_FE_EXP_X) pair_yield_drop(); }
 };
-BLSMI_DEV void final_exponentiation_yield(P2::Fp12S& f) {
+BLSMI_DEV void final_exponentiation_yield(P2::Fp12W& f) {                // on the chain's own type: the kernels below convert what they load once
 #if BLSMI_PAIR_YIELD
     P2::final_exp_chain<PairYieldOps>(f);
 #else
-    P2::final_exponentiation(f);
+    P2::final_exp_chain<P2::Fp12Ops>(f);
 #endif
 }
 
@@ -146,9 +146,9 @@ KERNEL_PAIR k_final_exp_pair(const i32* fbuf, u64* out, size_t n, int mode) {
     const size_t tt = t < n ? t : n - 1;
     const WaveCensus census;
     pair_yield_enter();
-    P2::Fp12S f = pair_load12(fbuf, n, tt, par);
+    P2::Fp12W f = P2::fp12_work(pair_load12(fbuf, n, tt, par));
     if (mode == 0) final_exponentiation_yield(f);
-    const FpS* c = reinterpret_cast<const FpS*>(&f);
+    const FpW* c = reinterpret_cast<const FpW*>(&f);
     for (int j = 0; j < 6; j++) {
         u32 w[12];
         fp_to_mont384_words(c[j], w);
@@ -226,7 +226,7 @@ KERNEL_PAIR k_final_exp_is_one_pair(const i32* fbuf, const u8* inf_flags, u8* ok
     const size_t tt = t < n ? t : n - 1;
     const WaveCensus census;
     pair_yield_enter();
-    P2::Fp12S f = pair_load12(fbuf, n, tt, par);
+    P2::Fp12W f = P2::fp12_work(pair_load12(fbuf, n, tt, par));
     final_exponentiation_yield(f);
     const bool one = P2::fp12_eq(f, P2::fp12_one());
     if (t < n && par == 0) ok[t] = (one && !(inf_flags && inf_flags[t])) ? 1 : 0;

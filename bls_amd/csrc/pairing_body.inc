@@ -7,14 +7,16 @@ struct G2Proj { Fp2S x, y, z; };
 // lane's scratch (a few hundred dword accesses against >10^4 VALU instructions per call), inside a
 // call everything is in registers.  One copy of each body serves every kernel, which keeps each
 // body's register allocation tractable and the code small.
-BLSMI_NOINLINE void nf_fp12_mul(Fp12S& r, const Fp12S& a, const Fp12S& b) { r = fp12_store(fp12_mul(a, b)); }
-BLSMI_NOINLINE void nf_fp12_sqr(Fp12S& r, const Fp12S& a) { r = fp12_store(fp12_sqr(a)); }
-BLSMI_NOINLINE void nf_fp12_cyc_sqr(Fp12S& r, const Fp12S& a) { r = fp12_cyclotomic_sqr(a); }
-BLSMI_NOINLINE void nf_fp12_inv(Fp12S& r, const Fp12S& a) { r = fp12_store(fp12_inv(a)); }
-BLSMI_NOINLINE void nf_fp12_frob1(Fp12S& r, const Fp12S& a) { r = fp12_store(fp12_frob<1>(a)); }
-BLSMI_NOINLINE void nf_fp12_frob2(Fp12S& r, const Fp12S& a) { r = fp12_store(fp12_frob<2>(a)); }
-BLSMI_NOINLINE void nf_fp12_frob3(Fp12S& r, const Fp12S& a) { r = fp12_store(fp12_frob<3>(a)); }
-BLSMI_DEV void fp12_conj_inplace(Fp12S& a) { a.c1 = fp6_store(fp6_neg(a.c1)); }
+// The operands and results are of the working type (tower_body.inc: Fp12W -- with 28-bit limbs every coefficient carries the reduced bound
+// its last value reduction left, so each coefficient is reduced once per operation, on the way out, and never again as an operand).
+BLSMI_NOINLINE void nf_fp12_mul(Fp12W& r, const Fp12W& a, const Fp12W& b) { r = fp12_work(fp12_mul(a, b)); }
+BLSMI_NOINLINE void nf_fp12_sqr(Fp12W& r, const Fp12W& a) { r = fp12_work(fp12_sqr(a)); }
+BLSMI_NOINLINE void nf_fp12_cyc_sqr(Fp12W& r, const Fp12W& a) { r = fp12_cyclotomic_sqr(a); }
+BLSMI_NOINLINE void nf_fp12_inv(Fp12W& r, const Fp12W& a) { r = fp12_work(fp12_inv(a)); }
+BLSMI_NOINLINE void nf_fp12_frob1(Fp12W& r, const Fp12W& a) { r = fp12_work(fp12_frob<1>(a)); }
+BLSMI_NOINLINE void nf_fp12_frob2(Fp12W& r, const Fp12W& a) { r = fp12_work(fp12_frob<2>(a)); }
+BLSMI_NOINLINE void nf_fp12_frob3(Fp12W& r, const Fp12W& a) { r = fp12_work(fp12_frob<3>(a)); }
+BLSMI_DEV void fp12_conj_inplace(Fp12W& a) { a.c1 = fp6_work(fp6_neg(a.c1)); }
 
 // g2.go:655-708
 BLSMI_NOINLINE void doubling_step(G2Proj& r, Fp2S& o0, Fp2S& o1, Fp2S& o2) {
@@ -68,7 +70,10 @@ BLSMI_DEV void doubling_step_h_i(G2Proj& r, Fp2S& o0, Fp2S& o1, Fp2S& o2) {
     const auto B = fp2_norm(fp2_sqr(r.y));
     const auto X2 = fp2_norm(fp2_sqr(r.x));
     const auto H = fp2_norm(fp2_dbl(fp2_mul(r.y, r.z)));
-    const auto E = fp2_norm(fp2_muls<12>(fp2_norm(fp2_mul_nr(fp2_norm(fp2_sqr(r.z))))));
+    // E is trimmed where it is made (28-bit limbs: value-reduced, 72 -> 5 half-q): G = B + 3E and E then square as they are and B - E stores
+    // without a reduction -- two reductions a step (E, Y3) instead of four (G and E before their squares, Y3, B - E).  The running point
+    // itself gains nothing from the reduced type: X, Y, Z multiply in one pass under the storage bound already.
+    const auto E = fp2_trim(fp2_muls<12>(fp2_norm(fp2_mul_nr(fp2_norm(fp2_sqr(r.z))))));
     const auto F = fp2_norm(fp2_muls<3>(E));
     const auto G = fp2_norm(fp2_add(B, F));
     const auto nx = fp2_norm(fp2_dbl(fp2_mul(A, fp2_norm(fp2_sub(B, F)))));
@@ -109,30 +114,33 @@ template <bool EXACT> BLSMI_DEV void add_step(G2Proj& r, const Fp2S& qx, const F
     if constexpr (EXACT) addition_step(r, qx, qy, o0, o1, o2); else addition_step_h(r, qx, qy, o0, o1, o2);
 }
 // pairing.go:28-39: f *= line evaluated at P (sparse 014 multiplication)
-BLSMI_NOINLINE void ell(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
+BLSMI_NOINLINE void ell(Fp12W& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
     const auto c0 = fp2_mul_fp(o0, py);
     const auto c1 = fp2_mul_fp(o1, px);
-    f = fp12_store(fp12_mul_by_014(f, o2, c1, c0));
+    // f enters the product under the storage bound on purpose: read as reduced it saves one operand reduction (13 multiply-adds) and
+    // the body then spills 416 instead of 240 bytes a lane (200 against 118 scratch accesses), which every Miller kernel's frame inherits.
+    // Six calls a loop; ell_sqr, at 62, is where the reduced operand pays.
+    f = fp12_work(fp12_mul_by_014(fp12_widen(f), o2, c1, c0));
 }
 
 // f = (f * line(P))^2 in one call: the 180-word accumulator crosses the call boundary once per iteration.  (Expanded in line at the loop's
 // one call site, so that f would be a local of the kernel, it was measured slower: k_miller1h_pair 9.83 against 9.31 ms -- the kernel
 // then spills 3 072 instead of 1 664 bytes a lane.)
-BLSMI_NOINLINE void ell_sqr(Fp12S& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
+BLSMI_NOINLINE void ell_sqr(Fp12W& f, const Fp2S& o0, const Fp2S& o1, const Fp2S& o2, const FpS& px, const FpS& py) {
     const auto c0 = fp2_mul_fp(o0, py);
     const auto c1 = fp2_mul_fp(o1, px);
-    const Fp12S g = fp12_store(fp12_mul_by_014(f, o2, c1, c0));
-    f = fp12_store(fp12_sqr(g));
+    const Fp12W g = fp12_work(fp12_mul_by_014(f, o2, c1, c0));
+    f = fp12_work(fp12_sqr(g));
 }
 
 // two lines (one per pair of a 2-pair loop) multiplied into f as one 5-coefficient element; SQR: followed by f^2
 template <bool SQR>
-BLSMI_NOINLINE void ell2(Fp12S& f, const Fp2S& a0, const Fp2S& a1, const Fp2S& a2, const FpS& ax, const FpS& ay,
+BLSMI_NOINLINE void ell2(Fp12W& f, const Fp2S& a0, const Fp2S& a1, const Fp2S& a2, const FpS& ax, const FpS& ay,
                          const Fp2S& b0, const Fp2S& b1, const Fp2S& b2, const FpS& bx, const FpS& by) {
     // line value of (o0, o1, o2) at P: o2 + (o1 P.x) v + (o0 P.y) v w   (pairing.go:28-39)
     const LinePair m = line_pair_product(a2, fp2_mul_fp(a1, ax), fp2_mul_fp(a0, ay), b2, fp2_mul_fp(b1, bx), fp2_mul_fp(b0, by));
-    const Fp12S g = fp12_store(fp12_mul_by_line_pair(f, m));
-    if (SQR) f = fp12_store(fp12_sqr(g)); else f = g;
+    const Fp12W g = fp12_work(fp12_mul_by_line_pair(f, m));
+    if (SQR) f = fp12_work(fp12_sqr(g)); else f = g;
 }
 
 // The walk over the bits of |x| >> 1 below its leading one (pairing.go:41-70; g2.go:650-801 runs the same walk to prepare a point),
@@ -193,14 +201,14 @@ BLSMI_DEV G2Proj lds_get_proj(const i32* l) {
 // YIELD > 0 (the lane-pair kernels that run two waves per SIMD, pair_kernels.inc): the wave entered at s_setprio 1 and goes down to 0 once
 // YIELD bits are walked, so that the wave it shares the SIMD with -- still at 1 if it is behind -- catches up.
 template <int NP, bool PRE0 = false, bool EXACT = true, bool PRE1 = false, int YIELD = 0, class G1P, class G2P>
-BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], const i32* pre = nullptr, const i32* pre1 = nullptr, i32* lds_r = nullptr) {
+BLSMI_DEV void miller_loop(Fp12S& out, const G1P (&p)[NP], const G2P (&q)[NP], const i32* pre = nullptr, const i32* pre1 = nullptr, i32* lds_r = nullptr) {
     static_assert(NP == 1 || NP == 2, "one pair, or two pairs sharing the squarings");
     constexpr int LAST = NP - 1;
     constexpr bool PRE_LAST = NP == 1 ? PRE0 : PRE1;                       // the last pair's lines come from a table: it has no running point
     G2Proj r[NP];
 #pragma unroll
     for (int k = 0; k < NP; k++) { r[k].x = q[k].x; r[k].y = q[k].y; r[k].z = fp2_one(); }
-    f = fp12_one();
+    Fp12W f = fp12_work(fp12_one());                                   // the accumulator, in the working type from the first line to the last
     const bool in_lds = !EXACT && !PRE_LAST && lds_r != nullptr;           // the last pair's running point in LDS, its doubling step in line (see lds_put_proj)
     if (in_lds) lds_put_proj(lds_r, r[LAST]);
     auto dbl_last = [&](Fp2S& a0, Fp2S& a1, Fp2S& a2) {
@@ -234,6 +242,7 @@ BLSMI_DEV void miller_loop(Fp12S& f, const G1P (&p)[NP], const G2P (&q)[NP], con
                    [&] { ell2<true>(f, o0, o1, o2, p[0].x, p[0].y, n0, n1, n2, p[1].x, p[1].y); }, tick);
     }
     fp12_conj_inplace(f);                                              // blsIsNegative (pairing.go:71-73)
+    out = fp12_widen(f);
 }
 // the 68 triples of one G2 point, in loop order, written by every lane that calls it (identical values)
 BLSMI_DEV void prepare_lines(const Fp2S& qx, const Fp2S& qy, i32* table) {
@@ -313,17 +322,17 @@ BLSMI_DEV void final_exp_chain(typename O::T& r) {
     O::mul(r, y1, y3);
 }
 
-BLSMI_DEV Fp12S cyc_sqr_run(const Fp12S& g, int m) {
-    CycCompressed c = cyc_compress(g);
+BLSMI_DEV Fp12W cyc_sqr_run(const Fp12W& g, int m) {
+    CycCompressedW c = cyc_compress(g);
     for (int j = 0; j < m; j++) c = cyc_compressed_sqr(c);
     Fp2S num, den;
     cyc_z1_fraction(c, num, den);
-    return cyc_decompress(c, fp2_store(fp2_mul(num, fp2_store(fp2_inv(den)))));
+    return cyc_decompress(c, fp2_mul(num, fp2_store(fp2_inv(den))));
 }
-BLSMI_NOINLINE void exp_by_x(Fp12S& out, const Fp12S& f, u64 e);
+BLSMI_NOINLINE void exp_by_x(Fp12W& out, const Fp12W& f, u64 e);
 // one tuple per lane / per lane pair: the out-of-line routines above; inside exp_by_x the squarings are expanded in line
 struct Fp12Ops {
-    using T = Fp12S;
+    using T = Fp12W;
     static constexpr int MIN_RUN = 12;
     static BLSMI_DEV void inv(T& r, const T& a) { nf_fp12_inv(r, a); }
     static BLSMI_DEV void mul(T& r, const T& a, const T& b) { nf_fp12_mul(r, a, b); }
@@ -336,6 +345,11 @@ struct Fp12Ops {
     static BLSMI_DEV void conj(T& a) { fp12_conj_inplace(a); }
     static BLSMI_DEV void exp_x(T& r, const T& a, u64 e) { exp_by_x(r, a, e); }
 };
-BLSMI_NOINLINE void exp_by_x(Fp12S& out, const Fp12S& f, u64 e) { exp_by_x_loop<Fp12Ops>(out, f, e); }
-BLSMI_DEV void final_exponentiation(Fp12S& r) { final_exp_chain<Fp12Ops>(r); }
+BLSMI_NOINLINE void exp_by_x(Fp12W& out, const Fp12W& f, u64 e) { exp_by_x_loop<Fp12Ops>(out, f, e); }
+// a value of the storage type (what a kernel loads) through the chain: converted once on the way in, widened on the way out
+BLSMI_DEV void final_exponentiation(Fp12S& r) {
+    Fp12W w = fp12_work(r);
+    final_exp_chain<Fp12Ops>(w);
+    r = fp12_widen(w);
+}
 

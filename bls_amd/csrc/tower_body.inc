@@ -34,6 +34,23 @@ template <int La, int Va, int Lb, int Vb> BLSMI_DEV auto fp6_sub(const Fp6<La, V
 template <int L, int V> BLSMI_DEV auto fp6_neg(const Fp6<L, V>& a) { return make_fp6(fp2_neg(a.c0), fp2_neg(a.c1), fp2_neg(a.c2)); }
 template <int L, int V> BLSMI_DEV auto fp6_norm(const Fp6<L, V>& a) { return make_fp6(fp2_norm(a.c0), fp2_norm(a.c1), fp2_norm(a.c2)); }
 template <int L, int V> BLSMI_DEV Fp6S fp6_store(const Fp6<L, V>& a) { Fp6S r; r.c0 = fp2_store(a.c0); r.c1 = fp2_store(a.c1); r.c2 = fp2_store(a.c2); return r; }
+template <int L, int V> BLSMI_DEV Fp6R fp6_reduced(const Fp6<L, V>& a) { Fp6R r; r.c0 = fp2_reduced(a.c0); r.c1 = fp2_reduced(a.c1); r.c2 = fp2_reduced(a.c2); return r; }
+// fp2_as<F2>(x): x in the type F2 a routine's values travel in -- the reduced type (fp_reduced) or the storage type (fp_store)
+template <class F2, int L, int V> BLSMI_DEV F2 fp2_as(const Fp2<L, V>& a) {
+    static_assert(std::is_same<F2, Fp2R>::value || std::is_same<F2, Fp2S>::value, "the reduced or the storage type");
+    if constexpr (std::is_same<F2, Fp2R>::value) return fp2_reduced(a); else return fp2_store(a);
+}
+template <int L, int V> BLSMI_DEV Fp2W fp2_work(const Fp2<L, V>& a) { return fp2_as<Fp2W>(a); }
+// fp2_trim(x): a small multiple that is about to be used several times -- with 28-bit limbs value-reduced once, here, instead of once per
+// use; with 27-bit limbs, where no use would reduce it, only normalised
+template <int L, int V> BLSMI_DEV auto fp2_trim(const Fp2<L, V>& a) {
+#ifdef BLSMI_LIMBS28
+    return fp2_reduced(a);
+#else
+    return fp2_norm(a);
+#endif
+}
+template <int L, int V> BLSMI_DEV Fp6W fp6_work(const Fp6<L, V>& a) { Fp6W r; r.c0 = fp2_work(a.c0); r.c1 = fp2_work(a.c1); r.c2 = fp2_work(a.c2); return r; }
 BLSMI_DEV Fp6S fp6_zero() { Fp6S r; r.c0 = fp2_zero(); r.c1 = fp2_zero(); r.c2 = fp2_zero(); return r; }
 BLSMI_DEV Fp6S fp6_one() { Fp6S r; r.c0 = fp2_one(); r.c1 = fp2_zero(); r.c2 = fp2_zero(); return r; }
 // fq6.go:34-37: multiply by v
@@ -100,6 +117,11 @@ BLSMI_DEV auto fp6_frob(const Fp6<L, V>& a) {
 // Fq12
 // ------------------------------------------------------------------------------------------------
 template <int L, int V> BLSMI_DEV Fp12S fp12_store(const Fp12<L, V>& a) { Fp12S r; r.c0 = fp6_store(a.c0); r.c1 = fp6_store(a.c1); return r; }
+template <int L, int V> BLSMI_DEV Fp12R fp12_reduced(const Fp12<L, V>& a) { Fp12R r; r.c0 = fp6_reduced(a.c0); r.c1 = fp6_reduced(a.c1); return r; }
+template <int L, int V> BLSMI_DEV Fp12W fp12_work(const Fp12<L, V>& a) { Fp12W r; r.c0 = fp6_work(a.c0); r.c1 = fp6_work(a.c1); return r; }
+template <int L2, int V2, int L, int V>
+BLSMI_DEV Fp12<L2, V2> fp12_relabel(const Fp12<L, V>& a) { Fp12<L2, V2> r; r.c0 = fp6_relabel<L2, V2>(a.c0); r.c1 = fp6_relabel<L2, V2>(a.c1); return r; }
+BLSMI_DEV Fp12S fp12_widen(const Fp12W& a) { return fp12_relabel<FpS::L, FpS::V>(a); }       // the working type as the storage type: same limbs, wider promise
 BLSMI_DEV Fp12S fp12_one() { Fp12S r; r.c0 = fp6_one(); r.c1 = fp6_zero(); return r; }
 template <int L, int V> BLSMI_DEV auto fp12_conj(const Fp12<L, V>& a) { return make_fp12(a.c0, fp6_neg(a.c1)); }   // fq12.go:27-29
 // fq12.go:198-213
@@ -197,20 +219,21 @@ BLSMI_DEV auto fp4_sqr(const Fp2<La, Va>& a, const Fp2<Lb, Vb>& b) {
 #endif
 }
 // outputs are 3t -+ 2z with z an input: the representation doubles per squaring, so each output is
-// value-reduced (fp_store) -- the only place in the pairing where a reduction is inherent.
-BLSMI_DEV Fp12S fp12_cyclotomic_sqr(const Fp12S& f) {
-    const Fp2S z0 = f.c0.c0, z4 = f.c0.c1, z3 = f.c0.c2, z2 = f.c1.c0, z1 = f.c1.c1, z5 = f.c1.c2;
-    Fp12S r;
+// value-reduced -- the only place in the pairing where a reduction is inherent.  The values travel in the working type (Fp12W: with 28-bit
+// limbs the reduced bound those six reductions guarantee), so the Karatsuba sums z + z' and z + xi z' inside fp4_sqr multiply as they are.
+BLSMI_DEV Fp12W fp12_cyclotomic_sqr(const Fp12W& f) {
+    const Fp2W z0 = f.c0.c0, z4 = f.c0.c1, z3 = f.c0.c2, z2 = f.c1.c0, z1 = f.c1.c1, z5 = f.c1.c2;
+    Fp12W r;
     const auto a = fp4_sqr(z0, z1);
-    r.c0.c0 = fp2_store(fp2_add(fp2_dbl(fp2_sub(a.first, z0)), a.first));
-    r.c1.c1 = fp2_store(fp2_add(fp2_dbl(fp2_add(a.second, z1)), a.second));
+    r.c0.c0 = fp2_work(fp2_add(fp2_dbl(fp2_sub(a.first, z0)), a.first));
+    r.c1.c1 = fp2_work(fp2_add(fp2_dbl(fp2_add(a.second, z1)), a.second));
     const auto b = fp4_sqr(z2, z3);
     const auto c = fp4_sqr(z4, z5);
-    r.c0.c1 = fp2_store(fp2_add(fp2_dbl(fp2_sub(b.first, z4)), b.first));
-    r.c1.c2 = fp2_store(fp2_add(fp2_dbl(fp2_add(b.second, z5)), b.second));
+    r.c0.c1 = fp2_work(fp2_add(fp2_dbl(fp2_sub(b.first, z4)), b.first));
+    r.c1.c2 = fp2_work(fp2_add(fp2_dbl(fp2_add(b.second, z5)), b.second));
     const auto t3n = fp2_mul_nr(c.second);
-    r.c1.c0 = fp2_store(fp2_add(fp2_dbl(fp2_add(t3n, z2)), t3n));
-    r.c0.c2 = fp2_store(fp2_add(fp2_dbl(fp2_sub(c.first, z3)), c.first));
+    r.c1.c0 = fp2_work(fp2_add(fp2_dbl(fp2_add(t3n, z2)), t3n));
+    r.c0.c2 = fp2_work(fp2_add(fp2_dbl(fp2_sub(c.first, z3)), c.first));
     return r;
 }
 // ---- compressed cyclotomic squaring (Karabina): the squaring above maps (z2, z3, z4, z5) to their successors without
@@ -218,35 +241,41 @@ BLSMI_DEV Fp12S fp12_cyclotomic_sqr(const Fp12S& f) {
 // three -- and z0, z1 are recovered afterwards from the relation that defines the cyclotomic subgroup:
 //   z1 = (xi z5^2 + 3 z4^2 - 2 z3) / (4 z2)        (z1 = 2 z4 z5 / z3 when z2 = 0; 0 for the unit, where z3 = 0 too)
 //   z0 = (2 z1^2 + z2 z5 - 3 z3 z4) xi + 1
-struct CycCompressed { Fp2S z2, z3, z4, z5; };
-BLSMI_DEV CycCompressed cyc_compress(const Fp12S& f) {
-    CycCompressed c; c.z4 = f.c0.c1; c.z3 = f.c0.c2; c.z2 = f.c1.c0; c.z5 = f.c1.c2; return c;
+// F2 is the type the four coefficients travel in: Fp2W for the lane / lane-pair chain, Fp2S where a layout brings its own squaring
+// (quad_body.inc) and only recovers z0, z1 here.
+template <class F2> struct CycCompressedT { F2 z2, z3, z4, z5; };
+using CycCompressed = CycCompressedT<Fp2S>;
+using CycCompressedW = CycCompressedT<Fp2W>;
+BLSMI_DEV CycCompressedW cyc_compress(const Fp12W& f) {
+    CycCompressedW c; c.z4 = f.c0.c1; c.z3 = f.c0.c2; c.z2 = f.c1.c0; c.z5 = f.c1.c2; return c;
 }
-BLSMI_DEV CycCompressed cyc_compressed_sqr(const CycCompressed& g) {
-    CycCompressed r;
+BLSMI_DEV CycCompressedW cyc_compressed_sqr(const CycCompressedW& g) {
+    CycCompressedW r;
     const auto b = fp4_sqr(g.z2, g.z3);
     const auto c = fp4_sqr(g.z4, g.z5);
-    r.z4 = fp2_store(fp2_add(fp2_dbl(fp2_sub(b.first, g.z4)), b.first));
-    r.z5 = fp2_store(fp2_add(fp2_dbl(fp2_add(b.second, g.z5)), b.second));
+    r.z4 = fp2_work(fp2_add(fp2_dbl(fp2_sub(b.first, g.z4)), b.first));
+    r.z5 = fp2_work(fp2_add(fp2_dbl(fp2_add(b.second, g.z5)), b.second));
     const auto t3n = fp2_mul_nr(c.second);
-    r.z2 = fp2_store(fp2_add(fp2_dbl(fp2_add(t3n, g.z2)), t3n));
-    r.z3 = fp2_store(fp2_add(fp2_dbl(fp2_sub(c.first, g.z3)), c.first));
+    r.z2 = fp2_work(fp2_add(fp2_dbl(fp2_add(t3n, g.z2)), t3n));
+    r.z3 = fp2_work(fp2_add(fp2_dbl(fp2_sub(c.first, g.z3)), c.first));
     return r;
 }
 // numerator and denominator of z1 (the denominator is replaced by 1 when both z2 and z3 vanish)
-BLSMI_DEV void cyc_z1_fraction(const CycCompressed& g, Fp2S& num, Fp2S& den) {
+template <class F2>
+BLSMI_DEV void cyc_z1_fraction(const CycCompressedT<F2>& g, Fp2S& num, Fp2S& den) {
     const i32 z2zero = fp2_is_zero(g.z2) ? -1 : 0;
     const Fp2S n_reg = fp2_store(fp2_sub(fp2_add(fp2_mul_nr(fp2_sqr(g.z5)), fp2_muls<3>(fp2_sqr(g.z4))), fp2_dbl(g.z3)));
     const Fp2S n_alt = fp2_store(fp2_dbl(fp2_mul(g.z4, g.z5)));
     const Fp2S d_reg = fp2_store(fp2_muls<4>(g.z2));
     num = fp2_select(z2zero, n_alt, n_reg);
-    den = fp2_select(z2zero, g.z3, d_reg);
+    den = fp2_select(z2zero, fp2_relabel<FpS::L, FpS::V>(g.z3), d_reg);
     den = fp2_select(fp2_is_zero(den) ? -1 : 0, fp2_one(), den);
 }
-BLSMI_DEV Fp12S cyc_decompress(const CycCompressed& g, const Fp2S& z1) {
-    const Fp2S z0 = fp2_store(fp2_add(fp2_mul_nr(fp2_sub(fp2_add(fp2_dbl(fp2_sqr(z1)), fp2_mul(g.z2, g.z5)), fp2_muls<3>(fp2_mul(g.z3, g.z4)))), fp2_one()));
-    Fp12S r;
-    r.c0.c0 = z0; r.c0.c1 = g.z4; r.c0.c2 = g.z3; r.c1.c0 = g.z2; r.c1.c1 = z1; r.c1.c2 = g.z5;
+template <class F2, int L1, int V1>
+BLSMI_DEV Fp12<F2::L, F2::V> cyc_decompress(const CycCompressedT<F2>& g, const Fp2<L1, V1>& z1) {
+    const F2 z0 = fp2_as<F2>(fp2_add(fp2_mul_nr(fp2_sub(fp2_add(fp2_dbl(fp2_sqr(z1)), fp2_mul(g.z2, g.z5)), fp2_muls<3>(fp2_mul(g.z3, g.z4)))), fp2_one()));
+    Fp12<F2::L, F2::V> r;
+    r.c0.c0 = z0; r.c0.c1 = g.z4; r.c0.c2 = g.z3; r.c1.c0 = g.z2; r.c1.c1 = fp2_as<F2>(z1); r.c1.c2 = g.z5;
     return r;
 }
 template <int La, int Va, int Lb, int Vb>

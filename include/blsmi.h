@@ -637,6 +637,7 @@ int blsmi_g2_compress_batch(const uint8_t *pts, const uint8_t *in_inf, uint8_t *
 enum blsmi_debug_op {
     BLSMI_OP_FQ_MUL = 1, BLSMI_OP_FQ_SQR, BLSMI_OP_FQ_ADD, BLSMI_OP_FQ_SUB, BLSMI_OP_FQ_NEG, BLSMI_OP_FQ_INV, BLSMI_OP_FQ_SQRT,
     BLSMI_OP_FQ_DBL /* DoubleAssign fq.go:140-143 */, BLSMI_OP_FQ_CMP /* Cmp fq.go:134-137: flag = 0/1/2 for a <,=,> b */, BLSMI_OP_FQ_PARITY /* fq.go:269-273: flag */,
+    BLSMI_OP_FQ_LAZY /* (1029 ab + 4a)(4b - 1029 ab): sums and small multiples grown to the limb and value bounds of the device's lazy Fq type, value-reduced, multiplied */,
     BLSMI_OP_FQ2_MUL = 16, BLSMI_OP_FQ2_SQR, BLSMI_OP_FQ2_INV, BLSMI_OP_FQ2_MUL_NR, BLSMI_OP_FQ2_SQRT, BLSMI_OP_FQ2_SQRT_ANY /* either root */, BLSMI_OP_FQ2_PARITY /* fq2.go:256-260: flag */,
     BLSMI_OP_FQ6_MUL = 32, BLSMI_OP_FQ6_SQR, BLSMI_OP_FQ6_INV, BLSMI_OP_FQ6_FROB1,
     BLSMI_OP_FQ6_MUL_BY_1 /* fq6.go:40-57, c1 = b[0..1] */, BLSMI_OP_FQ6_MUL_BY_01 /* fq6.go:60-90, (c0, c1) = b[0..3] */,
