@@ -144,6 +144,33 @@ def x_zero_points(group):
     return g2_scan(0, None, 3) + g2_scan(None, 0, 3)
 
 
+CURVE_ORDER = {1: P.G1_COFACTOR * P.R_ORDER, 2: P.G2_COFACTOR * P.R_ORDER}          # #E(Fq), #E'(Fq2)
+LOW_ORDERS = {1: (3, 11), 2: (13, 23)}                                             # small primes that divide the cofactors (11^2, 13^2, 23^2 do too)
+
+
+@functools.lru_cache(maxsize=None)
+def low_order_point(group, ell, seed=7100):
+    """a curve point of order exactly ell (a prime factor of the cofactor), by the Python oracle's double-and-add: a seeded curve point
+    times #E / ell^v (ell^v the whole power of ell in #E) has order ell^j; while its multiple by ell is finite, take that instead.  The
+    seed's stream is drawn from until the first multiple is finite.  (Not [#E / ell] Q: the 11-part of E(Fq) is Z/11 x Z/11 -- the curve
+    has all of E[11] over Fq -- so #E / 11 = 11 (...) kills every point.)"""
+    assert CURVE_ORDER[group] % ell == 0
+    xs = P.XORShift(seed + 100 * group + ell)
+    F = FIELD[group]
+    m = CURVE_ORDER[group]
+    while m % ell == 0:
+        m //= ell
+    while True:
+        x = P.rand_int(xs, Q) if group == 1 else (P.rand_int(xs, Q), P.rand_int(xs, Q))
+        pt = P.g1_from_x(x, False) if group == 1 else P.g2_from_x(x, False)
+        low = None if pt is None else P.jac_to_affine(F, P.affine_mul(F, pt, m))
+        while low is not None:
+            up = P.jac_to_affine(F, P.affine_mul(F, low, ell))
+            if up is None:
+                return low
+            low = up
+
+
 def g2_scan(a, b, n, start=1):
     """n points of E' with x = (a, t) (b None) or x = (t, b) (a None), t scanned upwards from `start`"""
     out, t = [], start
