@@ -12,6 +12,7 @@
 #include "cell_plan.h"
 #include "pprod_rlc_plan.h"
 #include "pprod_locate_plan.h"
+#include "fr.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>
@@ -194,6 +195,8 @@ struct Device {
     ncclComm_t comm = nullptr;
     hipStream_t coll_stream = nullptr;
     Workspace coll;
+    // evaluation domains of blsmi_fr_eval_batch* (rlc_host.hpp: fr_domain_table), [log2n][order]: built on first use, kept until blsmi_shutdown
+    u32* fr_dom[17][2] = {};
 };
 Device g_dev[MAX_DEV];
 int g_ndev = 0;
@@ -783,6 +786,7 @@ BLSMI_API void blsmi_shutdown(void) {
             c.stream = nullptr;
         }
         if (dv.gens.g1) { (void)hipFree(dv.gens.g1); (void)hipFree(dv.gens.g2); (void)hipFree(dv.gens.lines); (void)hipFree(dv.gens.lines_pair); (void)hipFree(dv.gens.lat); (void)hipFree(dv.gens.fixed1); (void)hipFree(dv.gens.fixed2); dv.gens = Gens{}; }
+        for (auto& per_k : dv.fr_dom) for (u32*& t : per_k) if (t) { (void)hipFree(t); t = nullptr; }
         hipMemPool_t pool;
         if (hipDeviceGetDefaultMemPool(&pool, dv.id) == hipSuccess) (void)hipMemPoolTrimTo(pool, 0);
     }

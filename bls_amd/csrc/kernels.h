@@ -77,6 +77,11 @@ __global__ void k_g1_mul_add_glv(const u8* a, size_t a_stride, const u8* b, size
 __global__ void k_kzg_neg_g1_copies(const u8* src, u8* dst, size_t n);
 __global__ void k_kzg_place_proofs(const u32* src, u32* dst, size_t n);
 __global__ void k_kzg_recheck_pairs(const uint4* P, const u8* P_inf, const uint4* wp, const uint4* tab, const u32* items, size_t m, uint4* g1, uint4* g2, u8* flags, size_t nre);
+// k_fr_eval.hip
+__global__ void k_fr_mul(const u8* a, const u8* b, u8* out, size_t n);
+__global__ void k_fr_inv(const u8* a, u8* out, size_t n);
+__global__ void k_fr_bary_prod(const u8* z, const u32* tab, u32 log2n, u8* D, u32* hit, size_t m);
+__global__ void k_fr_bary_sum(const u8* polys, const u8* z, const u32* tab, u32 log2n, const u8* Dinv, const u32* hit, u8* y, u8* noncanon, size_t m);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);

@@ -1,6 +1,7 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
 // ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*,
-// blsmi_fr_wsum_segmented_u64*, blsmi_groth16_verify_batch*, blsmi_g1_mul_add_batch* and blsmi_kzg_verify_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// blsmi_fr_wsum_segmented_u64*, blsmi_groth16_verify_batch*, blsmi_g1_mul_add_batch*, blsmi_kzg_verify_batch*, blsmi_fr_mul_batch*, blsmi_fr_inv_batch*,
+// blsmi_fr_eval_batch* and blsmi_kzg_verify_blob_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -1749,11 +1750,17 @@ int kzg_lift(const u8* d_c, const u8* d_p, const u8* d_z, u8* d_wp, size_t m, hi
     HIPCHK(hipGetLastError());
     return BLSMI_OK;
 }
+// The values of a blob batch (blsmi 0.21, below): y_j = p_j(z_j) is not given but evaluated into the call's own buffer, from m polynomials
+// in evaluation form; everything after that is the same call.  polys / noncanon: host pointers in kzg_host, device pointers in kzg_dev_api.
+struct KzgBlob { const void* polys; unsigned log2n; int order; void* noncanon; };
+bool fr_eval_shape_ok(unsigned log2n, int order, size_t m);
+int fr_eval_dev_core(const void* d_polys, unsigned log2n, int order, const void* d_z, void* d_y, void* d_noncanon, size_t m, hipStream_t s);
 int kzg_host(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* commitments, const uint8_t* proofs, const uint8_t* z, const uint8_t* y, size_t m,
-             const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked, bool jac) {
+             const uint64_t* scalars, size_t block, uint8_t* ok, int* combined, size_t* rechecked, bool jac, const KzgBlob* blob = nullptr) {
     groth16_report(combined, rechecked, false, 0);
     if (m == 0) return BLSMI_OK;
-    int rc = kzg_check_args(srs_g1 && srs_g2 && commitments && proofs && z && y && ok, m, scalars); if (rc) return rc;
+    int rc = kzg_check_args(srs_g1 && srs_g2 && commitments && proofs && z && (blob ? blob->polys != nullptr : y != nullptr) && ok, m, scalars); if (rc) return rc;
+    if (blob && !fr_eval_shape_ok(blob->log2n, blob->order, m)) return BLSMI_E_ARG;
     RlcHostScratch hs; uint8_t* none = nullptr;
     rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
     LOCK_AND_INIT();
@@ -1765,23 +1772,32 @@ int kzg_host(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* commit
     rc = upload_points(group_kernels(2), jac, srs_g2, k2.p, 2, s); if (rc) return rc;
     rc = upload_points(group_kernels(1), jac, commitments, dc.p, m, s); if (rc) return rc;
     rc = upload_points(group_kernels(1), jac, proofs, dp.p, m, s); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)32 * m, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dy.p, y, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    DBuf dpolys, dnc;
+    if (blob) {
+        const size_t pbytes = ((size_t)32 << blob->log2n) * m;
+        HIPCHK(dpolys.alloc(pbytes)); if (blob->noncanon) HIPCHK(dnc.alloc(m));
+        HIPCHK(hipMemcpyAsync(dpolys.p, blob->polys, pbytes, hipMemcpyHostToDevice, s));
+        rc = fr_eval_dev_core(dpolys.p, blob->log2n, blob->order, dz.p, dy.p, dnc.p, m, s); if (rc) return rc;
+    } else HIPCHK(hipMemcpyAsync(dy.p, y, (size_t)32 * m, hipMemcpyHostToDevice, s));
     rc = kzg_table(k2.p, tab.as<u8>(), s); if (rc) return rc;
     rc = kzg_lift(dc.as<u8>(), dp.as<u8>(), dz.as<u8>(), wp.as<u8>(), m, s); if (rc) return rc;
     bool held = false; size_t nre = 0;
     const KzgIn in{g.as<u8>(), wp.as<u8>(), tab.as<u8>(), dy.as<u8>(), scalars, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
     rc = kzg_core(in, dok.p, &held, &nre); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ok, dok.p, m, hipMemcpyDeviceToHost, s));
+    if (blob && blob->noncanon) HIPCHK(hipMemcpyAsync(blob->noncanon, dnc.p, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     groth16_report(combined, rechecked, held, nre);
     return BLSMI_OK;
 }
 // the _dev forms: affine records are read where they lie, whatever their alignment (the lift reads words); in-memory records are converted
 int kzg_dev_api(const void* d_srs_g1, const void* d_srs_g2, const void* d_commitments, const void* d_proofs, const void* d_z, const void* d_y, size_t m,
-                const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream, bool jac) {
+                const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream, bool jac, const KzgBlob* blob = nullptr) {
     groth16_report(combined, rechecked, false, 0);
     if (m == 0) return BLSMI_OK;
-    int rc = kzg_check_args(d_srs_g1 && d_srs_g2 && d_commitments && d_proofs && d_z && d_y && d_ok, m, scalars); if (rc) return rc;
+    int rc = kzg_check_args(d_srs_g1 && d_srs_g2 && d_commitments && d_proofs && d_z && (blob ? blob->polys != nullptr : d_y != nullptr) && d_ok, m, scalars); if (rc) return rc;
+    if (blob && !fr_eval_shape_ok(blob->log2n, blob->order, m)) return BLSMI_E_ARG;
     RlcHostScratch hs; uint8_t* none = nullptr;
     rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
     LOCK_AND_INIT_AT(d_ok);
@@ -1797,6 +1813,12 @@ int kzg_dev_api(const void* d_srs_g1, const void* d_srs_g2, const void* d_commit
         rc = jac_to_wire_dev(group_kernels(1), d_commitments, dc.p, nullptr, m, s); if (rc) return rc;
         rc = jac_to_wire_dev(group_kernels(1), d_proofs, dp.p, nullptr, m, s); if (rc) return rc;
         pg = g.as<u8>(); pk2 = k2.p; pc = dc.as<u8>(); pp = dp.as<u8>();
+    }
+    DBuf dy;
+    if (blob) {
+        HIPCHK(dy.alloc((size_t)32 * m));
+        rc = fr_eval_dev_core(blob->polys, blob->log2n, blob->order, d_z, dy.p, blob->noncanon, m, s); if (rc) return rc;
+        d_y = dy.p;
     }
     rc = kzg_table(pk2, tab.as<u8>(), s); if (rc) return rc;
     rc = kzg_lift(pc, pp, (const u8*)d_z, wp.as<u8>(), m, s); if (rc) return rc;
@@ -1823,4 +1845,137 @@ BLSMI_API int blsmi_kzg_verify_batch_dev(const void* d_srs_g1, const void* d_srs
 BLSMI_API int blsmi_kzg_verify_batch_jac_dev(const void* d_srs_g1_jac, const void* d_srs_g2_jac, const void* d_commitments_jac, const void* d_proofs_jac, const void* d_z, const void* d_y, size_t m,
                                              const uint64_t* scalars, size_t block, void* d_ok, int* combined, size_t* rechecked, void* stream) {
     return kzg_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, scalars, block, d_ok, combined, rechecked, stream, true);
+}
+
+// ---- polynomial evaluation in Fr and KZG blob batches (blsmi 0.21; include/blsmi.h "polynomial evaluation") ------------------------------
+// The scalar field proper: fr.h (Montgomery product, Fermat inversion, the evaluation domains) under the kernels of k_fr_eval.hip.
+namespace {
+std::mutex g_fr_dom_mu;
+// The table of the domain of size 2^log2n in `order` on the leased device: N + 1 Montgomery elements, the roots in position order and N^-1
+// (fr.h: domain_table).  Built on the host on first use and uploaded, one allocation per (device, log2n, order), at most 2 MiB + 32 bytes
+// each; kept until blsmi_shutdown (Device::fr_dom) -- a per-device constant as the generators are: blsmi_trim leaves it, blsmi_held_bytes
+// does not count it.
+int fr_domain_table(unsigned log2n, int order, const u32** out) {
+    std::lock_guard<std::mutex> lk(g_fr_dom_mu);
+    u32*& slot = tl_ctx->dev->fr_dom[log2n][order];
+    if (!slot) {
+        const size_t n = ((size_t)1 << log2n) + 1;
+        std::vector<blsmi_fr::Fr> t;
+        try { t.resize(n); } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+        blsmi_fr::domain_table(log2n, order, t.data());
+        u32* d = nullptr;
+        HIPCHK(hipMalloc(&d, n * sizeof(blsmi_fr::Fr)));
+        if (hipMemcpy(d, t.data(), n * sizeof(blsmi_fr::Fr), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return BLSMI_E_HIP; }
+        slot = d;
+    }
+    *out = slot;
+    return BLSMI_OK;
+}
+// what every evaluation refuses before any device work: a domain beyond 2^16, an order that is neither, m beyond 32 bits, m N 32 bytes
+// beyond a size_t
+bool fr_eval_shape_ok(unsigned log2n, int order, size_t m) {
+    if (log2n > blsmi_fr::MAX_LOG2N || (order != 0 && order != 1) || m > 0xffffffffull) return false;
+    return m <= (SIZE_MAX >> (log2n + 5));
+}
+constexpr size_t FR_EVAL_MAX_GRID = (size_t)1 << 20;                        // workgroups of an evaluation launch; each strides over the polynomials
+// y_j = p_j(z_j) on s, not synchronised: the three launches, one profile segment each.  d_noncanon may be null.
+int fr_eval_dev_core(const void* d_polys, unsigned log2n, int order, const void* d_z, void* d_y, void* d_noncanon, size_t m, hipStream_t s) {
+    const u32* tab = nullptr;
+    int rc = fr_domain_table(log2n, order, &tab); if (rc) return rc;
+    DBuf D, Dinv, hit;
+    HIPCHK(D.alloc((size_t)32 * m)); HIPCHK(Dinv.alloc((size_t)32 * m)); HIPCHK(hit.alloc(sizeof(uint32_t) * m));
+    const size_t grid = std::min(m, FR_EVAL_MAX_GRID);
+    launch_sized(KERNEL_OF(k_fr_bary_prod), grid, 256, s, d_z, tab, log2n, D.p, hit.p, m);
+    launch_sized(KERNEL_OF(k_fr_inv), (m + 255) / 256, 256, s, D.p, Dinv.p, m);
+    launch_sized(KERNEL_OF(k_fr_bary_sum), grid, 256, s, d_polys, d_z, tab, log2n, Dinv.p, hit.p, d_y, d_noncanon, m);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+// a lane per element, on s, not synchronised; d_b null: the inverses of a, else the products
+int fr_lanes_dev_core(const void* d_a, const void* d_b, void* d_out, size_t n, hipStream_t s) {
+    if (d_b) launch_sized(KERNEL_OF(k_fr_mul), (n + 255) / 256, 256, s, d_a, d_b, d_out, n);
+    else launch_sized(KERNEL_OF(k_fr_inv), (n + 255) / 256, 256, s, d_a, d_out, n);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int fr_lanes_host(const uint8_t* a, const uint8_t* b, bool two, uint8_t* out, size_t n) {
+    if (n == 0) return BLSMI_OK;
+    if (!a || (two && !b) || !out || n > 0xffffffffull) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    DBuf da, db, dout;
+    HIPCHK(da.alloc((size_t)32 * n)); HIPCHK(dout.alloc((size_t)32 * n));
+    HIPCHK(hipMemcpyAsync(da.p, a, (size_t)32 * n, hipMemcpyHostToDevice, s));
+    if (two) { HIPCHK(db.alloc((size_t)32 * n)); HIPCHK(hipMemcpyAsync(db.p, b, (size_t)32 * n, hipMemcpyHostToDevice, s)); }
+    int rc = fr_lanes_dev_core(da.p, two ? db.p : nullptr, dout.p, n, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)32 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+int fr_lanes_dev_api(const void* d_a, const void* d_b, bool two, void* d_out, size_t n, void* stream) {
+    if (n == 0) return BLSMI_OK;
+    if (!d_a || (two && !d_b) || !d_out || n > 0xffffffffull) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_out);
+    UseStream us(stream);
+    int rc = fr_lanes_dev_core(d_a, two ? d_b : nullptr, d_out, n, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_fr_mul_batch(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) { return fr_lanes_host(a, b, true, out, n); }
+BLSMI_API int blsmi_fr_mul_batch_dev(const void* d_a, const void* d_b, void* d_out, size_t n, void* stream) { return fr_lanes_dev_api(d_a, d_b, true, d_out, n, stream); }
+BLSMI_API int blsmi_fr_inv_batch(const uint8_t* a, uint8_t* out, size_t n) { return fr_lanes_host(a, nullptr, false, out, n); }
+BLSMI_API int blsmi_fr_inv_batch_dev(const void* d_a, void* d_out, size_t n, void* stream) { return fr_lanes_dev_api(d_a, nullptr, false, d_out, n, stream); }
+BLSMI_API int blsmi_fr_eval_batch(const uint8_t* polys, unsigned log2n, int order, const uint8_t* z, uint8_t* y, uint8_t* noncanon, size_t m) {
+    if (m == 0) return BLSMI_OK;
+    if (!polys || !z || !y || !fr_eval_shape_ok(log2n, order, m)) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t pbytes = ((size_t)32 << log2n) * m;
+    DBuf dp, dz, dy, dnc;
+    HIPCHK(dp.alloc(pbytes)); HIPCHK(dz.alloc((size_t)32 * m)); HIPCHK(dy.alloc((size_t)32 * m)); if (noncanon) HIPCHK(dnc.alloc(m));
+    HIPCHK(hipMemcpyAsync(dp.p, polys, pbytes, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dz.p, z, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    int rc = fr_eval_dev_core(dp.p, log2n, order, dz.p, dy.p, dnc.p, m, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(y, dy.p, (size_t)32 * m, hipMemcpyDeviceToHost, s));
+    if (noncanon) HIPCHK(hipMemcpyAsync(noncanon, dnc.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_fr_eval_batch_dev(const void* d_polys, unsigned log2n, int order, const void* d_z, void* d_y, void* d_noncanon, size_t m, void* stream) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_polys || !d_z || !d_y || !fr_eval_shape_ok(log2n, order, m)) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_y);
+    UseStream us(stream);
+    int rc = fr_eval_dev_core(d_polys, log2n, order, d_z, d_y, d_noncanon, m, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+// m blobs: y_j = p_j(z_j) by the evaluation above into the call's own buffer, then blsmi_kzg_verify_batch* as it is (kzg_host / kzg_dev_api,
+// kzg_core unchanged).
+BLSMI_API int blsmi_kzg_verify_blob_batch(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* polys, unsigned log2n, int order, const uint8_t* commitments,
+                                          const uint8_t* proofs, const uint8_t* z, size_t m, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* noncanon,
+                                          int* combined, size_t* rechecked) {
+    const KzgBlob blob{polys, log2n, order, noncanon};
+    return kzg_host(srs_g1, srs_g2, commitments, proofs, z, nullptr, m, scalars, block, ok, combined, rechecked, false, &blob);
+}
+BLSMI_API int blsmi_kzg_verify_blob_batch_jac(const uint64_t* srs_g1_jac, const uint64_t* srs_g2_jac, const uint8_t* polys, unsigned log2n, int order,
+                                              const uint64_t* commitments_jac, const uint64_t* proofs_jac, const uint8_t* z, size_t m, const uint64_t* scalars, size_t block,
+                                              uint8_t* ok, uint8_t* noncanon, int* combined, size_t* rechecked) {
+    const KzgBlob blob{polys, log2n, order, noncanon};
+    return kzg_host(reinterpret_cast<const uint8_t*>(srs_g1_jac), reinterpret_cast<const uint8_t*>(srs_g2_jac), reinterpret_cast<const uint8_t*>(commitments_jac),
+                    reinterpret_cast<const uint8_t*>(proofs_jac), z, nullptr, m, scalars, block, ok, combined, rechecked, true, &blob);
+}
+BLSMI_API int blsmi_kzg_verify_blob_batch_dev(const void* d_srs_g1, const void* d_srs_g2, const void* d_polys, unsigned log2n, int order, const void* d_commitments,
+                                              const void* d_proofs, const void* d_z, size_t m, const uint64_t* scalars, size_t block, void* d_ok, void* d_noncanon,
+                                              int* combined, size_t* rechecked, void* stream) {
+    const KzgBlob blob{d_polys, log2n, order, d_noncanon};
+    return kzg_dev_api(d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, nullptr, m, scalars, block, d_ok, combined, rechecked, stream, false, &blob);
+}
+BLSMI_API int blsmi_kzg_verify_blob_batch_jac_dev(const void* d_srs_g1_jac, const void* d_srs_g2_jac, const void* d_polys, unsigned log2n, int order,
+                                                  const void* d_commitments_jac, const void* d_proofs_jac, const void* d_z, size_t m, const uint64_t* scalars, size_t block,
+                                                  void* d_ok, void* d_noncanon, int* combined, size_t* rechecked, void* stream) {
+    const KzgBlob blob{d_polys, log2n, order, d_noncanon};
+    return kzg_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, nullptr, m, scalars, block, d_ok, combined, rechecked, stream, true, &blob);
 }

@@ -1,11 +1,12 @@
 """KZG batches (blsmi 0.20): blsmi_kzg_verify_batch[_jac|_dev|_jac_dev] and the G1 lift blsmi_g1_mul_add_batch[_dev] they are built on,
-over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
+and the blob batches that evaluate their polynomials first (blsmi 0.21: blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]), over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
 happens in the HIP kernels; a missing library or device raises, nothing falls back."""
 import ctypes as C
 
 import numpy as np
 
 from . import engine as _e
+from . import fr as _fr
 
 
 def _stride(stride, what):
@@ -91,3 +92,55 @@ def verify_batch_dev(d_srs_g1, d_srs_g2, d_commitments, d_proofs, d_z, d_y, m, d
 def verify_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, d_ok, scalars=None, block=0, stream=0):
     """device-pointer form over in-memory points -> (combined, rechecked)"""
     return _verify_dev("blsmi_kzg_verify_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, d_y, m, d_ok, scalars, block, stream)
+
+
+def _verify_blob(name, jac, srs_g1, srs_g2, polys, log2n, order, commitments, proofs, z, scalars, block, noncanon):
+    pb, qb = (144, 288) if jac else (96, 192)
+    log2n, order = _fr._shape(log2n, order)
+    g, h = _e._u8(srs_g1, pb), _e._u8(srs_g2, 2 * qb)
+    c, p = _e._u8(commitments), _e._u8(proofs)
+    if c.size % pb or p.size != c.size:
+        raise ValueError("expected m*%d bytes of C_j and as many of pi_j, got %d and %d" % (pb, c.size, p.size))
+    m = c.size // pb
+    zz, pp = _e._u8(z, 32 * m), _e._u8(polys, (32 << log2n) * m)
+    pr = _e._scalars(scalars, m)
+    block = _e._block(block)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    nc = np.zeros(max(1, m), dtype=np.uint8) if noncanon else None
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    g, h, c, p = (_e._recs(v, v.size, jac) for v in (g, h, c, p))
+    _e._call(name, g, h, _e._p8(pp), log2n, order, c, p, _e._p8(zz), m, pr, block, _e._p8(ok), _e._p8(nc), C.byref(comb), C.byref(nre))
+    return ok[:m].copy(), (nc[:m].astype(bool) if noncanon else None), comb.value, nre.value
+
+
+def verify_blob_batch(srs_g1, srs_g2, polys, log2n, commitments, proofs, z, order=1, scalars=None, block=0, noncanon=True):
+    """blsmi_kzg_verify_blob_batch -> (ok (m,) uint8, noncanon (m,) bool or None, combined, rechecked): m KZG blob proofs under one key.
+    polys: m polynomials of N = 2^log2n values each (32 big-endian bytes, any value taken mod r) over the N-th roots of unity -- order 1:
+    bit-reversed, the blob layout; order 0: position i holds w^i --; the rest as verify_batch, whose verdict on (C_j, pi_j, z_j, p_j(z_j))
+    ok[j] is.  noncanon[j]: one of blob j's values was >= r, for the caller to reject (noncanon=False: not asked for).  z is an input:
+    deriving it by Fiat-Shamir stays the caller's."""
+    return _verify_blob("blsmi_kzg_verify_blob_batch", False, srs_g1, srs_g2, polys, log2n, order, commitments, proofs, z, scalars, block, noncanon)
+
+
+def verify_blob_batch_jac(srs_g1_jac, srs_g2_jac, polys, log2n, commitments_jac, proofs_jac, z, order=1, scalars=None, block=0, noncanon=True):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _verify_blob("blsmi_kzg_verify_blob_batch_jac", True, srs_g1_jac, srs_g2_jac, polys, log2n, order, commitments_jac, proofs_jac, z, scalars, block, noncanon)
+
+
+def _verify_blob_dev(name, d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitments, d_proofs, d_z, m, d_ok, d_noncanon, scalars, block, stream):
+    log2n, order = _fr._shape(log2n, order)
+    pr = _e._scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _e._call(name, d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitments, d_proofs, d_z, m, pr, _e._block(block), d_ok, d_noncanon, C.byref(comb), C.byref(nre), stream)
+    return comb.value, nre.value
+
+
+def verify_blob_batch_dev(d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitments, d_proofs, d_z, m, d_ok, d_noncanon=0, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_ok (and the m flags in d_noncanon, unless 0) when the
+    call returns; scalars stay on the host.  -> (combined, rechecked)"""
+    return _verify_blob_dev("blsmi_kzg_verify_blob_batch_dev", d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitments, d_proofs, d_z, m, d_ok, d_noncanon, scalars, block, stream)
+
+
+def verify_blob_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon=0, scalars=None, block=0, stream=0):
+    """device-pointer form over in-memory points -> (combined, rechecked)"""
+    return _verify_blob_dev("blsmi_kzg_verify_blob_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon, scalars, block, stream)

@@ -92,9 +92,12 @@ void blsmi_shutdown(void);
  * new option.  0.19 adds arithmetic mod r -- the weighted segmented fold of scalars (blsmi_fr_wsum_segmented_u64[_dev]) -- and the Groth16
  * batches that fold their public inputs with it (blsmi_groth16_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new
  * option.  0.20 adds the lift out = A + k * B in G1 (blsmi_g1_mul_add_batch[_dev]) and the KZG batches that fold their values mod r
- * (blsmi_kzg_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19 and 0.20 by the presence
- * of those symbols. */
+ * (blsmi_kzg_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  0.21 adds the scalar field proper --
+ * products and inverses mod r (blsmi_fr_mul_batch[_dev], blsmi_fr_inv_batch[_dev]) --, the evaluation of polynomials in evaluation form
+ * (blsmi_fr_eval_batch[_dev]) and the KZG blob batches that evaluate their blobs with it (blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]);
+ * no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19, 0.20 and 0.21 by the
+ * presence of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -1129,6 +1132,77 @@ int blsmi_kzg_verify_batch_dev(const void *d_srs_g1, const void *d_srs_g2, const
 int blsmi_kzg_verify_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_commitments_jac, const void *d_proofs_jac,
                                    const void *d_z, const void *d_y, size_t m, const uint64_t *scalars, size_t block, void *d_ok, int *combined, size_t *rechecked,
                                    void *stream);
+
+/* ---- polynomial evaluation in Fr and KZG blob batches (blsmi 0.21) ---------------------------------------------------------------------------
+ * The scalar field proper on the device: Montgomery products and inverses mod r (the order of G1, G2 and GT), a lane per element.
+ * a, b, out: n scalars of 32 big-endian bytes; ANY 256-bit value is taken mod r, every output is fully reduced; the inverse of 0 mod r
+ * (0, r, 2 r) is 0.
+ *   - BLSMI_E_ARG before any device work: a NULL pointer with n > 0, n beyond 2^32 - 1.  n = 0: BLSMI_OK, nothing is written.
+ *   - _dev: every buffer on one of the library's devices, 4-byte aligned; `stream` as in blsmi_pairing_batch_dev; the inputs stay untouched
+ *     (out may be an input's buffer: a lane reads its element before it writes it). */
+int blsmi_fr_mul_batch(const uint8_t *a /* n*32 */, const uint8_t *b /* n*32 */, uint8_t *out /* n*32 */, size_t n);
+int blsmi_fr_mul_batch_dev(const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
+int blsmi_fr_inv_batch(const uint8_t *a /* n*32 */, uint8_t *out /* n*32 */, size_t n);
+int blsmi_fr_inv_batch_dev(const void *d_a, void *d_out, size_t n, void *stream);
+/* y[j] = p_j(z_j) for m polynomials in EVALUATION form: polynomial j is its N = 2^log2n values over the N-th roots of unity, 32 big-endian
+ * bytes each, log2n <= 16.  The domain is w^0 .. w^(N-1), w = 7^((r - 1) / N) mod r (log2n = 12: 0x564c0a11...a5d36306, the root of
+ * EIP-4844).  order = 0: the value at position i belongs to w^i; order = 1: to w^bitrev(i), i's log2n bits reversed -- the layout of a
+ * blob.  z: m points; y: m values, fully reduced.  ANY 256-bit value or point is taken mod r like every scalar of the library;
+ * noncanon (may be NULL): noncanon[j] = 1 when any of polynomial j's N values was >= r, else 0 -- for the caller to reject.
+ * By the barycentric formula p(z) = (z^N - 1) / N * sum_i f_i w_i / (z - w_i), one workgroup per polynomial and ONE inversion per
+ * polynomial, in three launches: k_fr_bary_prod (the product of the z - w_i), k_fr_inv, k_fr_bary_sum.  Where z_j is a root of the domain
+ * (after reduction: w_i + r is w_i) the answer is the value at that position mod r, read directly.
+ * The domain's table (N + 1 elements, 32 bytes each) is built once per (device, log2n, order) at the first call that needs it and kept
+ * until blsmi_shutdown: it is a per-device constant, so blsmi_trim does not release it and blsmi_held_bytes does not count it.
+ *   - BLSMI_E_ARG before any device work: NULL polys, z or y with m > 0; log2n > 16; order neither 0 nor 1; m beyond 2^32 - 1; m * N * 32
+ *     beyond a size_t.  m = 0: BLSMI_OK, nothing is written.
+ *   - _dev: every buffer on one of the library's devices, 4-byte aligned (polys is read in 16-byte pieces when it is 16-byte aligned, byte
+ *     by byte otherwise); `stream` as in blsmi_pairing_batch_dev; the inputs stay untouched.
+ * One lease, one device, never in the request combiner. */
+int blsmi_fr_eval_batch(const uint8_t *polys /* m*N*32 */, unsigned log2n, int order, const uint8_t *z /* m*32 */, uint8_t *y /* m*32 */,
+                        uint8_t *noncanon /* m, may be NULL */, size_t m);
+int blsmi_fr_eval_batch_dev(const void *d_polys, unsigned log2n, int order, const void *d_z, void *d_y, void *d_noncanon /* may be NULL */, size_t m,
+                            void *stream);
+/* m KZG blob proofs under one key: blsmi_kzg_verify_batch for a caller who holds the polynomial and not its value.  polys / log2n / order as
+ * blsmi_fr_eval_batch; srs_g1, srs_g2, commitments, proofs, z, scalars / block / ok / combined / rechecked exactly as blsmi_kzg_verify_batch.
+ * y_j = p_j(z_j) is computed by the evaluation above into the call's own buffer; everything after that IS blsmi_kzg_verify_batch:
+ * ok[j] is exactly its verdict on (C_j, pi_j, z_j, p_j(z_j)), with its infinity rules, its block equations, its recheck and its
+ * soundness precondition (every key, commitment and proof point in the prime-order subgroups).  A non-canonical value is taken mod r; it is
+ * reported in noncanon (may be NULL) as blsmi_fr_eval_batch reports it, for the caller to reject -- ok[j] does not depend on it.
+ * Deriving z_j by Fiat-Shamir (SHA-256 over the blob and the commitment, EIP-4844's compute_challenge) stays the caller's: z is an input.
+ *   - BLSMI_E_ARG before any device work: a NULL key, polys, point, z or ok pointer with m > 0; log2n > 16; order neither 0 nor 1; a zero
+ *     caller scalar; m beyond 2^31 - 2 (2^32 - 1 and beyond included); m * N * 32 beyond a size_t.
+ *   - m = 0: BLSMI_OK, *combined = 0, nothing else is written.  *rechecked = 0 on every early return.  No `block` value is refused.
+ *   - _jac / _dev as blsmi_kzg_verify_batch; polys, z, ok and noncanon are then device buffers, 4-byte aligned; the caller's buffers stay
+ *     untouched.
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * What it does not change: the floor of 0.17 (a call costs a few milliseconds whatever m) and the lift of 0.20 (one ladder per item)
+ * remain under it -- the evaluation is added in front of blsmi_kzg_verify_batch, nothing of that call is removed or made cheaper.
+ * Measured (one MI355X, everything resident, N = 4 096, block = 0, the legs alternating, median of 20 +- spread in ms; DESIGN.md 3v and
+ * profiles/r21_blob_eval.log have the table): (a) the evaluation, its three kernels
+ * in brackets (k_fr_bary_prod, k_fr_inv, k_fr_bary_sum); (b) a device-to-device copy of the same m * N * 32 bytes; (c)
+ * blsmi_kzg_verify_batch_dev on the same openings with y given; (d) this call.
+ *     m = 8:      (a) 0.71 +- 0.17 (0.04, 0.51, 0.14)   (b) 0.02   (a) / (b) 32    (c) 6.16 +- 0.27   (d) 6.80 +- 0.22   (d) - (c) 0.64
+ *     m = 64:     (a) 0.65 +- 0.01 (0.04, 0.45, 0.14)   (b) 0.03   (a) / (b) 26    (c) 6.32 +- 0.02   (d) 6.88 +- 0.04   (d) - (c) 0.56
+ *     m = 1 024:  (a) 0.93 +- 0.03 (0.10, 0.45, 0.36)   (b) 0.05   (a) / (b) 17    (c) 6.49 +- 0.13   (d) 7.39 +- 0.08   (d) - (c) 0.90
+ *     m = 4 096:  (a) 2.01 +- 0.02 (0.31, 0.46, 1.21)   (b) 0.21   (a) / (b) 9.8   (c) 6.90 +- 0.08   (d) 8.87 +- 0.08   (d) - (c) 1.97
+ * The evaluation is bound by the multiplier, not by HBM (9.8 times the copy at 512 MB of blobs), and up to a thousand blobs by the one
+ * inversion's latency (k_fr_inv: 0.45 ms for one element as for 65 536).  At NONE of the measured m is the evaluation the larger part of the
+ * call: at 4 096 blobs the pairings' side -- the lift, the sums, three Miller loops per block, the final exponentiation -- still takes 3.4
+ * times as long, and up to a thousand blobs seven to ten times. */
+int blsmi_kzg_verify_blob_batch(const uint8_t *srs_g1 /* 96 */, const uint8_t *srs_g2 /* 2*192 */, const uint8_t *polys /* m*N*32 */, unsigned log2n, int order,
+                                const uint8_t *commitments /* m*96 */, const uint8_t *proofs /* m*96 */, const uint8_t *z /* m*32 */, size_t m,
+                                const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */, uint8_t *ok /* m */,
+                                uint8_t *noncanon /* m, may be NULL */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_kzg_verify_blob_batch_jac(const uint64_t *srs_g1_jac /* 18 */, const uint64_t *srs_g2_jac /* 2*36 */, const uint8_t *polys, unsigned log2n, int order,
+                                    const uint64_t *commitments_jac /* m*18 */, const uint64_t *proofs_jac /* m*18 */, const uint8_t *z, size_t m,
+                                    const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *noncanon, int *combined, size_t *rechecked);
+int blsmi_kzg_verify_blob_batch_dev(const void *d_srs_g1, const void *d_srs_g2, const void *d_polys, unsigned log2n, int order, const void *d_commitments,
+                                    const void *d_proofs, const void *d_z, size_t m, const uint64_t *scalars /* host: m, may be NULL */, size_t block,
+                                    void *d_ok, void *d_noncanon /* may be NULL */, int *combined /* host */, size_t *rechecked /* host */, void *stream);
+int blsmi_kzg_verify_blob_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_polys, unsigned log2n, int order,
+                                        const void *d_commitments_jac, const void *d_proofs_jac, const void *d_z, size_t m, const uint64_t *scalars, size_t block,
+                                        void *d_ok, void *d_noncanon, int *combined, size_t *rechecked, void *stream);
 
 #ifdef __cplusplus
 }
