@@ -12,7 +12,7 @@
 #include "cell_plan.h"
 #include "pprod_rlc_plan.h"
 #include "pprod_locate_plan.h"
-#include "fr.h"
+#include "fr_ntt.h"
 #include <functional>
 #include <mutex>
 #include <condition_variable>

@@ -33,6 +33,16 @@ KERNEL2 k_kzg_neg_g1_copies(const u8* src, u8* dst, size_t n) {
     store_g1(dst + (size_t)96 * i, g);
 }
 
+// Minus each of the n G1 records at src (4-byte aligned; the all-zero record stays all-zero), a lane per record: the key records -[tau^i] G
+// over which a cell batch runs the ladders of its folded coefficients (blsmi 0.22: rlc_host.hpp, cell_core).
+KERNEL2 k_kzg_neg_g1_records(const u8* src, u8* dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    G1Aff g = load_g1(src + (size_t)96 * i);
+    g.y = fp_store(fp_neg(g.y));
+    store_g1(dst + (size_t)96 * i, g);
+}
+
 // The proofs beside the lifted points: record j of src (96 bytes, 4-byte aligned) to the second half of the 192-byte slot j of dst -- (W_j,
 // pi_j) interleaved is the G1 array of the two pairs per item.  A lane per 32-bit word.
 KERNEL2 k_kzg_place_proofs(const u32* src, u32* dst, size_t n) {

@@ -73,8 +73,10 @@ __global__ void k_fr_wsum_u64(const u8* vals, size_t ncol, const u64* w, const u
 __global__ void k_fr_wsum_fold(const u32* part, const u64* seg_ch, size_t cols, u8* out, size_t nout);
 __global__ void k_g2_neg_records(const u8* src, const u32* idx, u8* dst, size_t n);
 __global__ void k_groth16_recheck_pairs(const uint4* proofs, const uint4* alpha, const uint4* L, const u8* L_inf, const uint4* tab, const u32* items, size_t m, uint4* g1, uint4* g2, u8* flags, size_t nre);
+// k_kzg.hip
 __global__ void k_g1_mul_add_glv(const u8* a, size_t a_stride, const u8* b, size_t b_stride, const u8* scalars, u8* out, size_t out_stride, u8* out_inf, size_t n);
 __global__ void k_kzg_neg_g1_copies(const u8* src, u8* dst, size_t n);
+__global__ void k_kzg_neg_g1_records(const u8* src, u8* dst, size_t n);
 __global__ void k_kzg_place_proofs(const u32* src, u32* dst, size_t n);
 __global__ void k_kzg_recheck_pairs(const uint4* P, const u8* P_inf, const uint4* wp, const uint4* tab, const u32* items, size_t m, uint4* g1, uint4* g2, u8* flags, size_t nre);
 // k_fr_eval.hip
@@ -82,6 +84,8 @@ __global__ void k_fr_mul(const u8* a, const u8* b, u8* out, size_t n);
 __global__ void k_fr_inv(const u8* a, u8* out, size_t n);
 __global__ void k_fr_bary_prod(const u8* z, const u32* tab, u32 log2n, u8* D, u32* hit, size_t m);
 __global__ void k_fr_bary_sum(const u8* polys, const u8* z, const u32* tab, u32 log2n, const u8* Dinv, const u32* hit, u8* y, u8* noncanon, size_t m);
+// k_fr_ntt.hip
+__global__ void k_fr_coset_interp(const u8* vals, const u8* shifts, const u8* hinv, const u32* tab, u32 log2n, int order, u8* coeffs, u8* shift_pow, u8* flags, size_t m);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);

@@ -1,7 +1,7 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
 // ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*,
 // blsmi_fr_wsum_segmented_u64*, blsmi_groth16_verify_batch*, blsmi_g1_mul_add_batch*, blsmi_kzg_verify_batch*, blsmi_fr_mul_batch*, blsmi_fr_inv_batch*,
-// blsmi_fr_eval_batch* and blsmi_kzg_verify_blob_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// blsmi_fr_eval_batch*, blsmi_kzg_verify_blob_batch*, blsmi_fr_coset_interp_batch* and blsmi_kzg_verify_cell_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -1978,4 +1978,266 @@ BLSMI_API int blsmi_kzg_verify_blob_batch_jac_dev(const void* d_srs_g1_jac, cons
                                                   void* d_ok, void* d_noncanon, int* combined, size_t* rechecked, void* stream) {
     const KzgBlob blob{d_polys, log2n, order, d_noncanon};
     return kzg_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_commitments_jac, d_proofs_jac, d_z, nullptr, m, scalars, block, d_ok, combined, rechecked, stream, true, &blob);
+}
+
+// ==== coset interpolation in Fr and KZG cell batches (blsmi 0.22; include/blsmi.h under the same title) =====================================
+// From the n = 2^log2n values of a polynomial over the coset h <w> the n coefficients of its interpolant: k_fr_inv over the shifts, then
+// k_fr_coset_interp (k_fr_ntt.hip; fr_ntt.h).  The twiddles are the order-0 domain table of 0.21, one per (device, log2n).
+namespace {
+// what every interpolation refuses before any device work: n beyond 2^10, an order that is neither, m beyond 32 bits, m n 32 bytes beyond a
+// size_t
+bool fr_interp_shape_ok(unsigned log2n, int order, size_t m) {
+    if (log2n > blsmi_fr::NTT_MAX_LOG2N || (order != 0 && order != 1) || m > 0xffffffffull) return false;
+    return m <= (SIZE_MAX >> (log2n + 5));
+}
+// items a workgroup of k_fr_coset_interp holds at once: its tile of 512 elements, a lane per item at n = 1
+size_t fr_interp_group(unsigned log2n) { return log2n == 0 ? 256 : log2n > 9 ? 1 : (size_t)512 >> log2n; }
+// on s, not synchronised: the two launches, one profile segment each.  d_shift_pow, d_flags may be null.
+int fr_interp_dev_core(const void* d_vals, unsigned log2n, int order, const void* d_shifts, void* d_coeffs, void* d_shift_pow, void* d_flags, size_t m, hipStream_t s) {
+    const u32* tab = nullptr;
+    int rc = fr_domain_table(log2n, 0, &tab); if (rc) return rc;
+    DBuf hinv;
+    HIPCHK(hinv.alloc((size_t)32 * m));
+    const size_t per = fr_interp_group(log2n), grid = std::min((m + per - 1) / per, FR_EVAL_MAX_GRID);
+    launch_sized(KERNEL_OF(k_fr_inv), (m + 255) / 256, 256, s, d_shifts, hinv.p, m);
+    launch_sized(KERNEL_OF(k_fr_coset_interp), grid, 256, s, d_vals, d_shifts, hinv.p, tab, log2n, order, d_coeffs, d_shift_pow, d_flags, m);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_fr_coset_interp_batch(const uint8_t* vals, unsigned log2n, int order, const uint8_t* shifts, uint8_t* coeffs, uint8_t* shift_pow, uint8_t* flags, size_t m) {
+    if (m == 0) return BLSMI_OK;
+    if (!vals || !shifts || !coeffs || !fr_interp_shape_ok(log2n, order, m)) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t vbytes = ((size_t)32 << log2n) * m;
+    DBuf dv, dh, dc, dsp, dfl;
+    HIPCHK(dv.alloc(vbytes)); HIPCHK(dh.alloc((size_t)32 * m)); HIPCHK(dc.alloc(vbytes));
+    if (shift_pow) HIPCHK(dsp.alloc((size_t)32 * m));
+    if (flags) HIPCHK(dfl.alloc(m));
+    HIPCHK(hipMemcpyAsync(dv.p, vals, vbytes, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dh.p, shifts, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    int rc = fr_interp_dev_core(dv.p, log2n, order, dh.p, dc.p, dsp.p, dfl.p, m, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(coeffs, dc.p, vbytes, hipMemcpyDeviceToHost, s));
+    if (shift_pow) HIPCHK(hipMemcpyAsync(shift_pow, dsp.p, (size_t)32 * m, hipMemcpyDeviceToHost, s));
+    if (flags) HIPCHK(hipMemcpyAsync(flags, dfl.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_fr_coset_interp_batch_dev(const void* d_vals, unsigned log2n, int order, const void* d_shifts, void* d_coeffs, void* d_shift_pow, void* d_flags, size_t m, void* stream) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_vals || !d_shifts || !d_coeffs || !fr_interp_shape_ok(log2n, order, m)) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_coeffs);
+    UseStream us(stream);
+    int rc = fr_interp_dev_core(d_vals, log2n, order, d_shifts, d_coeffs, d_shift_pow, d_flags, m, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+
+// m cells under the block equations of 0.18.  Cell j -- the n values of a polynomial over h_j <w> -- holds when
+//     e(C_j + h_j^n pi_j - sum_i c_ji [tau^i] G, H) e(pi_j, -[tau^n] H) = 1,        c_j the coefficients of the interpolant,
+// which is the opening of 0.20 with z_j := h_j^n, y_j G := sum_i c_ji [tau^i] G and tau H := tau^n H.  With W_j = C_j + h_j^n pi_j and the
+// weights r_j, over a block b,
+//     sum_j r_j (W_j - sum_i c_ji [tau^i] G) = sum_j r_j W_j - sum_i s_bi [tau^i] G,        s_bi = sum_j r_j c_ji mod r,
+// so that a block needs n scalars from the fold and n full-width ladders over the negated key records, whatever its length.  Stages:
+//   1  the interpolation above into the call's own buffers (the drivers below): coeffs, shift_pow, flags
+//   2  kzg_lift with z := shift_pow, kzg_table, as they are
+//   3  the plan of 0.18 over two pairs per item, and one further cell per block appended to it against H, as kzg_core
+//   4  pprod_weighted_sums, unchanged
+//   5  its own: fr_wsum_dev over coeffs with n columns and the blocks as segments; the n key records negated once (k_kzg_neg_g1_records);
+//      B n ladders of s_bi over gathered records (mul_dev_core), a segmented sum per block into the appended cells -- a block whose s_bi are
+//      all 0 yields the infinity record and its flag, and the route leaves the cell out
+//   6  pprod_locate_failing_blocks, unchanged
+//   7  cell_recheck for the items of failing blocks only: n ladders c_ji (-[tau^i] G) per item, the segmented sum with the W_j already there
+//      into dense P_j, k_kzg_recheck_pairs, pprod_recheck_dense.  The lift and the interpolation run once.
+// One lease, one device, never in the request combiner.
+namespace {
+struct CellIn {
+    const u8* key;           // [tau^0] G .. [tau^(n-1)] G: n affine records, 4-byte aligned
+    u8* wp;                  // (W_j, pi_j) interleaved: 2 m affine records, the call's own, 16-byte aligned; the lift has filled it
+    const u8* tab;           // H, -[tau^n] H: the call's own, affine
+    const u8* coeffs;        // m * n scalars, fully reduced, the call's own
+    const uint64_t* r;       // host: m nonzero scalars
+    size_t n, m, block;      // block: resolved, >= 1
+};
+// Stage 7.  items: the cells of the failing blocks, ascending; negkey: the n negated key records.  Synchronises.
+int cell_recheck(const CellIn& in, const PprodCall& c, const u8* negkey, const std::vector<uint32_t>& items, void* d_ok) {
+    const size_t nre = items.size(), n = in.n, nl = nre * n;
+    hipStream_t s = g_stream;
+    const GroupKernels& g = group_kernels(1);
+    std::vector<uint64_t> zoff, ioff; std::vector<uint32_t> wi, zi, lp;
+    SegPlan zplan, iplan;
+    try {
+        zoff.resize(nre + 1); ioff.resize(nre + 1); wi.resize(nre); zi.resize(nre + nl); lp.resize(nl);
+        for (size_t t = 0; t <= nre; t++) { zoff[t] = t * (n + 1); ioff[t] = 2 * t; }
+        for (size_t t = 0; t < nre; t++) {
+            wi[t] = 2 * items[t];
+            zi[t * (n + 1)] = (uint32_t)t;                                  // W_j, then the item's n ladders
+            for (size_t i = 0; i < n; i++) { zi[t * (n + 1) + 1 + i] = (uint32_t)(nre + t * n + i); lp[t * n + i] = (uint32_t)i; }
+        }
+        segsum_plan(zoff.data(), nre, segsum_chunk_of(nre + nl), zplan); pprod_plan(ioff.data(), nre, iplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    DBuf ditems, dwi, dzi, dlp, rows, lpts, Z, zinf, P, Pinf, a, b, fl, okd;
+    HIPCHK(ditems.alloc(sizeof(uint32_t) * nre)); HIPCHK(dwi.alloc(sizeof(uint32_t) * nre)); HIPCHK(dzi.alloc(sizeof(uint32_t) * (nre + nl))); HIPCHK(dlp.alloc(sizeof(uint32_t) * nl));
+    HIPCHK(rows.alloc((size_t)32 * nl)); HIPCHK(lpts.alloc((size_t)96 * nl));
+    HIPCHK(Z.alloc((size_t)96 * (nre + nl))); HIPCHK(zinf.alloc(nre + nl)); HIPCHK(P.alloc((size_t)96 * nre)); HIPCHK(Pinf.alloc(nre));
+    HIPCHK(a.alloc((size_t)96 * 2 * nre)); HIPCHK(b.alloc((size_t)192 * 2 * nre)); HIPCHK(fl.alloc(2 * nre)); HIPCHK(okd.alloc(nre));
+    HIPCHK(hipMemcpyAsync(ditems.p, items.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dwi.p, wi.data(), sizeof(uint32_t) * nre, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dzi.p, zi.data(), sizeof(uint32_t) * (nre + nl), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dlp.p, lp.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+    prof_mark(KERNEL_OF(k_gather_records16).name);                         // one segment: the gathers
+    groth16_gather(in.coeffs, ditems, rows.p, (size_t)32 * n, nre, s);     // the items' coefficient rows: n scalars each
+    groth16_gather(negkey, dlp, lpts.p, 96, nl, s);
+    groth16_gather(in.wp, dwi, Z.p, 96, nre, s);                           // W_j, with the flag byte its pair got (bit 0: at infinity)
+    launch_quiet(KERNEL_OF(k_gather_bytes), nblocks(nre), s, c.pflag.p, dwi.p, zinf.p, nre);
+    prof_mark(nullptr);
+    int rc = mul_dev_core(g, lpts.as<u8>(), rows.as<u8>(), Z.as<u8>() + (size_t)96 * nre, zinf.as<u8>() + nre, nl, s); if (rc) return rc;
+    rc = segsum_dev(g, false, Z.p, zinf.as<u8>(), nre + nl, dzi.as<u32>(), zplan, P.as<u8>(), Pinf.as<u8>(), 1, s); if (rc) return rc;
+    launch(KERNEL_OF(k_kzg_recheck_pairs), tuple_blocks(Layout::row, 2 * nre), s, P.p, Pinf.p, in.wp, in.tab, ditems.p, in.m, a.p, b.p, fl.p, nre);
+    prof_mark(nullptr);
+    return pprod_recheck_dense(a.as<u8>(), b.as<u8>(), fl.as<u8>(), 2 * nre, iplan, ditems.as<u32>(), okd.p, d_ok);
+}
+// d_ok: m verdict bytes on the device.  Synchronises.
+int cell_core(const CellIn& in, void* d_ok, bool* held, size_t* rechecked) {
+    const size_t m = in.m, n = in.n, np = 2 * m, cols = n + 1;
+    hipStream_t s = g_stream;
+    const GroupKernels& g = group_kernels(1);
+    *rechecked = 0;
+    std::vector<uint64_t> seg_off, boff, goff; std::vector<uint32_t> q_idx, lpt, lsc;
+    blsmi_route::PprodLocatePlan pl; blsmi_route::PprodLocateFailing ff;
+    FrWsumPlan fp; SegPlan gplan;
+    PprodCall c; PprodCellBufs b;
+    size_t C0 = 0, B = 0, nl = 0;
+    try {
+        seg_off.resize(m + 1); q_idx.resize(np);
+        for (size_t j = 0; j < m; j++) { seg_off[j] = 2 * j; q_idx[2 * j] = 0; q_idx[2 * j + 1] = 1; }
+        seg_off[m] = np;
+        if (!blsmi_route::pprod_locate_plan(seg_off.data(), m, q_idx.data(), np, 2, in.block, pl)) return BLSMI_E_ARG;   // stage 3
+        C0 = pl.cells(); B = pl.blocks(); nl = B * n;
+        const uint32_t further[1] = {0};                                   // H again: the cell of -sum_i s_bi [tau^i] G
+        blsmi_route::pprod_locate_append_cells(pl, further, 1);
+        boff.resize(B + 1); goff.resize(B + 1); lpt.resize(nl); lsc.resize(nl);
+        for (size_t k = 0; k < B; k++) {
+            boff[k] = pl.item_lo(k); goff[k] = k * n;
+            for (size_t i = 0; i < n; i++) { lpt[k * n + i] = (uint32_t)i; lsc[k * n + i] = (uint32_t)(k * cols + 1 + i); }   // s_bi (-[tau^i] G)
+        }
+        boff[B] = m; goff[B] = nl;
+        fr_wsum_plan(boff.data(), B, n, fp); segsum_plan(goff.data(), B, segsum_chunk_of(nl), gplan); pprod_plan(pl.slot_off.data(), B, b.bplan);
+    } catch (const std::bad_alloc&) { return BLSMI_E_NOMEM; }
+    const size_t C = pl.cells(), dg = pl.entry_of.size();
+    DBuf t, dent, fout, negkey, dlp, dls, lpts, lscal, lout, linf;
+    HIPCHK(t.alloc((size_t)192 * dg)); HIPCHK(dent.alloc(sizeof(uint32_t) * dg));
+    HIPCHK(b.dsum.alloc(sizeof(uint32_t) * C)); HIPCHK(b.dent.alloc(sizeof(uint32_t) * C)); HIPCHK(b.bblob.alloc(b.bplan.blob.size()));
+    HIPCHK(fout.alloc((size_t)32 * cols * B)); HIPCHK(negkey.alloc((size_t)96 * n)); HIPCHK(dlp.alloc(sizeof(uint32_t) * nl)); HIPCHK(dls.alloc(sizeof(uint32_t) * nl));
+    HIPCHK(lpts.alloc((size_t)96 * nl)); HIPCHK(lscal.alloc((size_t)32 * nl)); HIPCHK(lout.alloc((size_t)96 * nl)); HIPCHK(linf.alloc(nl));
+    HIPCHK(hipMemcpyAsync(dent.p, pl.entry_of.data(), sizeof(uint32_t) * dg, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.dsum.p, pl.sum_of.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(b.dent.p, pl.entry_at.data(), sizeof(uint32_t) * C, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.bblob.p, b.bplan.blob.data(), b.bplan.blob.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dlp.p, lpt.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dls.p, lsc.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+    launch_quiet(KERNEL_OF(k_gather_records), nblocks((size_t)48 * dg), s, in.tab, dent.p, t.p, 48, dg);   // the table in the plan's order
+    launch_quiet(KERNEL_OF(k_kzg_neg_g1_records), nblocks(n), s, in.key, negkey.p, n);
+    const PprodRlcIn pin{in.wp, true, nullptr, t.as<u8>(), in.r, seg_off.data(), np, m};
+    int rc = pprod_weighted_sums(c, pin, pprod_segments(pl, pl.cell_off, B), B, route_load(C)); if (rc) return rc;   // stage 4
+    rc = fr_wsum_dev(fp, in.coeffs, n, c.dr.p, B, fout.p, s); if (rc) return rc;   // stage 5: every block: t_b, s_b0 .. s_b(n-1)
+    groth16_gather(negkey.p, dlp, lpts.p, 96, nl, s);
+    groth16_gather(fout.p, dls, lscal.p, 32, nl, s);
+    rc = mul_dev_core(g, lpts.as<u8>(), lscal.as<u8>(), lout.as<u8>(), linf.as<u8>(), nl, s); if (rc) return rc;
+    rc = segsum_dev(g, false, lout.p, linf.as<u8>(), nl, nullptr, gplan, c.S.as<u8>() + (size_t)96 * C0, c.sinf.as<u8>() + C0, 1, s); if (rc) return rc;
+    rc = pprod_locate_failing_blocks(c, pl, b, d_ok, held, ff);             // stage 6
+    if (rc || *held) return rc;
+    if (ff.items.empty()) { HIPCHK(hipStreamSynchronize(s)); return BLSMI_OK; }   // (cannot be: the total is the product of the block values)
+    rc = cell_recheck(in, c, negkey.as<u8>(), ff.items, d_ok);              // stage 7
+    if (!rc) *rechecked = ff.items.size();
+    return rc;
+}
+// What every form checks before any device work, in the order the header lists it.
+int cell_check_args(bool pointers_ok, unsigned log2n, int order, size_t m, const uint64_t* scalars) {
+    if (!pointers_ok || log2n > blsmi_fr::NTT_MAX_LOG2N || (order != 0 && order != 1) || m > 0x7ffffffeull || m > (SIZE_MAX >> (log2n + 5))) return BLSMI_E_ARG;
+    return rlc_check_args(true, scalars, m);
+}
+int cell_host(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* vals, unsigned log2n, int order, const uint8_t* shifts, const uint8_t* commitments,
+              const uint8_t* proofs, size_t m, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* flags, int* combined, size_t* rechecked, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = cell_check_args(srs_g1 && srs_g2 && vals && shifts && commitments && proofs && ok, log2n, order, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t n = (size_t)1 << log2n, vbytes = (size_t)32 * n * m;
+    DBuf g, k2, dc, dp, dv, dh, co, sp, dfl, wp, tab, dok;
+    HIPCHK(g.alloc((size_t)96 * n)); HIPCHK(k2.alloc(192 * 2)); HIPCHK(dc.alloc((size_t)96 * m)); HIPCHK(dp.alloc((size_t)96 * m)); HIPCHK(dv.alloc(vbytes)); HIPCHK(dh.alloc((size_t)32 * m));
+    HIPCHK(co.alloc(vbytes)); HIPCHK(sp.alloc((size_t)32 * m)); if (flags) HIPCHK(dfl.alloc(m));
+    HIPCHK(wp.alloc((size_t)192 * m)); HIPCHK(tab.alloc(192 * 2)); HIPCHK(dok.alloc(m));
+    rc = upload_points(group_kernels(1), jac, srs_g1, g.p, n, s); if (rc) return rc;
+    rc = upload_points(group_kernels(2), jac, srs_g2, k2.p, 2, s); if (rc) return rc;
+    rc = upload_points(group_kernels(1), jac, commitments, dc.p, m, s); if (rc) return rc;
+    rc = upload_points(group_kernels(1), jac, proofs, dp.p, m, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(dv.p, vals, vbytes, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dh.p, shifts, (size_t)32 * m, hipMemcpyHostToDevice, s));
+    rc = fr_interp_dev_core(dv.p, log2n, order, dh.p, co.p, sp.p, dfl.p, m, s); if (rc) return rc;   // stage 1
+    rc = kzg_lift(dc.as<u8>(), dp.as<u8>(), sp.as<u8>(), wp.as<u8>(), m, s); if (rc) return rc;      // stage 2
+    rc = kzg_table(k2.p, tab.as<u8>(), s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const CellIn in{g.as<u8>(), wp.as<u8>(), tab.as<u8>(), co.as<u8>(), scalars, n, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = cell_core(in, dok.p, &held, &nre); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ok, dok.p, m, hipMemcpyDeviceToHost, s));
+    if (flags) HIPCHK(hipMemcpyAsync(flags, dfl.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+// the _dev forms: affine records are read where they lie, whatever their alignment; in-memory records are converted
+int cell_dev_api(const void* d_srs_g1, const void* d_srs_g2, const void* d_vals, unsigned log2n, int order, const void* d_shifts, const void* d_commitments,
+                 const void* d_proofs, size_t m, const uint64_t* scalars, size_t block, void* d_ok, void* d_flags, int* combined, size_t* rechecked, void* stream, bool jac) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = cell_check_args(d_srs_g1 && d_srs_g2 && d_vals && d_shifts && d_commitments && d_proofs && d_ok, log2n, order, m, scalars); if (rc) return rc;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    hipStream_t s = g_stream;
+    const size_t n = (size_t)1 << log2n;
+    DBuf g, k2, dc, dp, co, sp, wp, tab;
+    HIPCHK(co.alloc((size_t)32 * n * m)); HIPCHK(sp.alloc((size_t)32 * m)); HIPCHK(wp.alloc((size_t)192 * m)); HIPCHK(tab.alloc(192 * 2));
+    const u8 *pg = (const u8*)d_srs_g1, *pc = (const u8*)d_commitments, *pp = (const u8*)d_proofs; const void* pk2 = d_srs_g2;
+    if (jac) {
+        HIPCHK(g.alloc((size_t)96 * n)); HIPCHK(k2.alloc(192 * 2)); HIPCHK(dc.alloc((size_t)96 * m)); HIPCHK(dp.alloc((size_t)96 * m));
+        rc = jac_to_wire_dev(group_kernels(1), d_srs_g1, g.p, nullptr, n, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(2), d_srs_g2, k2.p, nullptr, 2, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(1), d_commitments, dc.p, nullptr, m, s); if (rc) return rc;
+        rc = jac_to_wire_dev(group_kernels(1), d_proofs, dp.p, nullptr, m, s); if (rc) return rc;
+        pg = g.as<u8>(); pk2 = k2.p; pc = dc.as<u8>(); pp = dp.as<u8>();
+    }
+    rc = fr_interp_dev_core(d_vals, log2n, order, d_shifts, co.p, sp.p, d_flags, m, s); if (rc) return rc;   // stage 1
+    rc = kzg_lift(pc, pp, sp.as<u8>(), wp.as<u8>(), m, s); if (rc) return rc;                                // stage 2
+    rc = kzg_table(pk2, tab.as<u8>(), s); if (rc) return rc;
+    bool held = false; size_t nre = 0;
+    const CellIn in{pg, wp.as<u8>(), tab.as<u8>(), co.as<u8>(), scalars, n, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = cell_core(in, d_ok, &held, &nre); if (rc) return rc;
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_kzg_verify_cell_batch(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* vals, unsigned log2n, int order, const uint8_t* shifts,
+                                          const uint8_t* commitments, const uint8_t* proofs, size_t m, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* flags,
+                                          int* combined, size_t* rechecked) {
+    return cell_host(srs_g1, srs_g2, vals, log2n, order, shifts, commitments, proofs, m, scalars, block, ok, flags, combined, rechecked, false);
+}
+BLSMI_API int blsmi_kzg_verify_cell_batch_jac(const uint64_t* srs_g1_jac, const uint64_t* srs_g2_jac, const uint8_t* vals, unsigned log2n, int order, const uint8_t* shifts,
+                                              const uint64_t* commitments_jac, const uint64_t* proofs_jac, size_t m, const uint64_t* scalars, size_t block, uint8_t* ok,
+                                              uint8_t* flags, int* combined, size_t* rechecked) {
+    return cell_host(reinterpret_cast<const uint8_t*>(srs_g1_jac), reinterpret_cast<const uint8_t*>(srs_g2_jac), vals, log2n, order, shifts,
+                     reinterpret_cast<const uint8_t*>(commitments_jac), reinterpret_cast<const uint8_t*>(proofs_jac), m, scalars, block, ok, flags, combined, rechecked, true);
+}
+BLSMI_API int blsmi_kzg_verify_cell_batch_dev(const void* d_srs_g1, const void* d_srs_g2, const void* d_vals, unsigned log2n, int order, const void* d_shifts,
+                                              const void* d_commitments, const void* d_proofs, size_t m, const uint64_t* scalars, size_t block, void* d_ok, void* d_flags,
+                                              int* combined, size_t* rechecked, void* stream) {
+    return cell_dev_api(d_srs_g1, d_srs_g2, d_vals, log2n, order, d_shifts, d_commitments, d_proofs, m, scalars, block, d_ok, d_flags, combined, rechecked, stream, false);
+}
+BLSMI_API int blsmi_kzg_verify_cell_batch_jac_dev(const void* d_srs_g1_jac, const void* d_srs_g2_jac, const void* d_vals, unsigned log2n, int order, const void* d_shifts,
+                                                  const void* d_commitments_jac, const void* d_proofs_jac, size_t m, const uint64_t* scalars, size_t block, void* d_ok,
+                                                  void* d_flags, int* combined, size_t* rechecked, void* stream) {
+    return cell_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_vals, log2n, order, d_shifts, d_commitments_jac, d_proofs_jac, m, scalars, block, d_ok, d_flags, combined, rechecked, stream, true);
 }

@@ -1,5 +1,6 @@
 """KZG batches (blsmi 0.20): blsmi_kzg_verify_batch[_jac|_dev|_jac_dev] and the G1 lift blsmi_g1_mul_add_batch[_dev] they are built on,
-and the blob batches that evaluate their polynomials first (blsmi 0.21: blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]), over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
+and the blob batches that evaluate their polynomials first (blsmi 0.21: blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]), and the cell
+batches that interpolate their cells over a coset first (blsmi 0.22: blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]), over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
 happens in the HIP kernels; a missing library or device raises, nothing falls back."""
 import ctypes as C
 
@@ -144,3 +145,73 @@ def verify_blob_batch_dev(d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitmen
 def verify_blob_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon=0, scalars=None, block=0, stream=0):
     """device-pointer form over in-memory points -> (combined, rechecked)"""
     return _verify_blob_dev("blsmi_kzg_verify_blob_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon, scalars, block, stream)
+
+
+_R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+
+def cell_shifts(log2_cells, log2n):
+    """the shifts of the 2^log2_cells cells of 2^log2n values each that make up an EIP-7594 extended blob, as (cells, 32) uint8: cell k is the
+    coset h_k <w_n> in bit-reversed order (order = 1) with h_k = w_N^bitrev(k), N = cells * n, k's log2_cells bits reversed -- position i of
+    cell k is roots_of_unity_brp[n k + i].  Pure Python, big integers."""
+    log2_cells, log2n = int(log2_cells), int(log2n)
+    if log2_cells < 0 or log2n < 0 or log2_cells + log2n > 32:
+        raise ValueError("log2_cells + log2n is 0 .. 32, got %d + %d" % (log2_cells, log2n))
+    w = pow(7, (_R - 1) >> (log2_cells + log2n), _R)
+    out = np.zeros((1 << log2_cells, 32), dtype=np.uint8)
+    for k in range(1 << log2_cells):
+        rev = int(format(k, "0%db" % log2_cells)[::-1], 2) if log2_cells else 0
+        out[k] = np.frombuffer(pow(w, rev, _R).to_bytes(32, "big"), dtype=np.uint8)
+    return out
+
+
+def _verify_cell(name, jac, srs_g1, srs_g2, vals, log2n, order, shifts, commitments, proofs, scalars, block, flags):
+    pb, qb = (144, 288) if jac else (96, 192)
+    log2n, order = _fr._interp_shape(log2n, order)
+    g, h = _e._u8(srs_g1, pb << log2n), _e._u8(srs_g2, 2 * qb)
+    c, p = _e._u8(commitments), _e._u8(proofs)
+    if c.size % pb or p.size != c.size:
+        raise ValueError("expected m*%d bytes of C_j and as many of pi_j, got %d and %d" % (pb, c.size, p.size))
+    m = c.size // pb
+    hh, vv = _e._u8(shifts, 32 * m), _e._u8(vals, (32 << log2n) * m)
+    pr = _e._scalars(scalars, m)
+    block = _e._block(block)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    fl = np.zeros(max(1, m), dtype=np.uint8) if flags else None
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    g, h, c, p = (_e._recs(v, v.size, jac) for v in (g, h, c, p))
+    _e._call(name, g, h, _e._p8(vv), log2n, order, _e._p8(hh), c, p, m, pr, block, _e._p8(ok), _e._p8(fl), C.byref(comb), C.byref(nre))
+    return ok[:m].copy(), (fl[:m].copy() if flags else None), comb.value, nre.value
+
+
+def verify_cell_batch(srs_g1, srs_g2, vals, log2n, shifts, commitments, proofs, order=1, scalars=None, block=0, flags=True):
+    """blsmi_kzg_verify_cell_batch -> (ok (m,) uint8, flags (m,) uint8 or None, combined, rechecked): m KZG cell proofs under one key.
+    srs_g1: [tau^0] G .. [tau^(n-1)] G, n = 2^log2n; srs_g2: H, [tau^n] H; vals: m cells of n values each (32 big-endian bytes, any value
+    taken mod r) over the cosets shifts[j] <w> -- order 1: bit-reversed, a cell as it arrives; order 0: position i is the value at h w^i --;
+    the rest as verify_batch.  flags[j]: bit 0 a value or the shift was >= r, bit 1 the shift is 0 mod r, for the caller to reject
+    (flags=False: not asked for)."""
+    return _verify_cell("blsmi_kzg_verify_cell_batch", False, srs_g1, srs_g2, vals, log2n, order, shifts, commitments, proofs, scalars, block, flags)
+
+
+def verify_cell_batch_jac(srs_g1_jac, srs_g2_jac, vals, log2n, shifts, commitments_jac, proofs_jac, order=1, scalars=None, block=0, flags=True):
+    """the same over in-memory points (144 / 288 bytes each, z == 0: infinity)"""
+    return _verify_cell("blsmi_kzg_verify_cell_batch_jac", True, srs_g1_jac, srs_g2_jac, vals, log2n, order, shifts, commitments_jac, proofs_jac, scalars, block, flags)
+
+
+def _verify_cell_dev(name, d_srs_g1, d_srs_g2, d_vals, log2n, order, d_shifts, d_commitments, d_proofs, m, d_ok, d_flags, scalars, block, stream):
+    log2n, order = _fr._interp_shape(log2n, order)
+    pr = _e._scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _e._call(name, d_srs_g1, d_srs_g2, d_vals, log2n, order, d_shifts, d_commitments, d_proofs, m, pr, _e._block(block), d_ok, d_flags, C.byref(comb), C.byref(nre), stream)
+    return comb.value, nre.value
+
+
+def verify_cell_batch_dev(d_srs_g1, d_srs_g2, d_vals, log2n, order, d_shifts, d_commitments, d_proofs, m, d_ok, d_flags=0, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over affine records; the m verdict bytes are in d_ok (and the m flags in d_flags, unless 0) when the call
+    returns; scalars stay on the host.  -> (combined, rechecked)"""
+    return _verify_cell_dev("blsmi_kzg_verify_cell_batch_dev", d_srs_g1, d_srs_g2, d_vals, log2n, order, d_shifts, d_commitments, d_proofs, m, d_ok, d_flags, scalars, block, stream)
+
+
+def verify_cell_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_vals, log2n, order, d_shifts, d_commitments_jac, d_proofs_jac, m, d_ok, d_flags=0, scalars=None, block=0, stream=0):
+    """device-pointer form over in-memory points -> (combined, rechecked)"""
+    return _verify_cell_dev("blsmi_kzg_verify_cell_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_vals, log2n, order, d_shifts, d_commitments_jac, d_proofs_jac, m, d_ok, d_flags, scalars, block, stream)

@@ -95,9 +95,11 @@ void blsmi_shutdown(void);
  * (blsmi_kzg_verify_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  0.21 adds the scalar field proper --
  * products and inverses mod r (blsmi_fr_mul_batch[_dev], blsmi_fr_inv_batch[_dev]) --, the evaluation of polynomials in evaluation form
  * (blsmi_fr_eval_batch[_dev]) and the KZG blob batches that evaluate their blobs with it (blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]);
- * no existing prototype changes, no new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19, 0.20 and 0.21 by the
- * presence of those symbols. */
+ * no existing prototype changes, no new option.  0.22 adds the interpolation of a polynomial from its values over a coset
+ * (blsmi_fr_coset_interp_batch[_dev]) and the KZG cell batches that interpolate their cells with it
+ * (blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19, 0.20, 0.21 and 0.22 by
+ * the presence of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -1203,6 +1205,77 @@ int blsmi_kzg_verify_blob_batch_dev(const void *d_srs_g1, const void *d_srs_g2, 
 int blsmi_kzg_verify_blob_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_polys, unsigned log2n, int order,
                                         const void *d_commitments_jac, const void *d_proofs_jac, const void *d_z, size_t m, const uint64_t *scalars, size_t block,
                                         void *d_ok, void *d_noncanon, int *combined, size_t *rechecked, void *stream);
+
+/* ==== coset interpolation in Fr and KZG cell batches (blsmi 0.22) ==============================================================================
+ * coeffs[j] = the n = 2^log2n coefficients of the polynomial I_j with deg I_j < n that takes the values vals[j] over the COSET h_j <w>:
+ * w = 7^((r - 1) / n) mod r, the root of the domains of blsmi_fr_eval_batch; order = 0: the value at position i belongs to h_j w^i;
+ * order = 1: to h_j w^bitrev(i), i's log2n bits reversed -- a cell of EIP-7594 as it arrives (n = 64, h_k = w_8192^bitrev_7(k) for cell k).
+ * vals: n values per item, 32 big-endian bytes each; shifts: the m values h_j.  ANY 256-bit value or shift is taken mod r like every scalar
+ * of the library.  coeffs[j][i] is the coefficient of X^i: natural order, fully reduced.  shift_pow (may be NULL): shift_pow[j] = h_j^n mod r.
+ * flags (may be NULL): bit 0 of flags[j] is set when a value or the shift of item j was >= r, bit 1 when h_j = 0 mod r -- for the caller to
+ * reject.  h_j = 0 mod r is NOT refused: no coset exists then, and the formula runs with 0^-1 = 0 (as blsmi_fr_inv_batch) and 0^0 = 1, so
+ * that c_j0 = a_j0 and c_ji = 0 for i > 0; the caller rejects by the flag.
+ * With a_j the inverse DFT of the values over w, the factor 1 / n included, c_ji = h_j^(-i) a_ji.  Two launches: k_fr_inv over the m shifts,
+ * then k_fr_coset_interp: a workgroup holds 512 / n items in LDS (n = 1 024: one), log2n stages of butterflies, a scaling by the powers of
+ * h_j^-1.  The twiddles are the order-0 domain table of blsmi_fr_eval_batch of size n, kept until blsmi_shutdown as that call says.
+ *   - log2n <= 10.
+ *   - BLSMI_E_ARG before any device work: NULL vals, shifts or coeffs with m > 0; log2n > 10; order neither 0 nor 1; m beyond 2^32 - 1;
+ *     m * n * 32 beyond a size_t.  m = 0: BLSMI_OK, nothing is written.
+ *   - coeffs must not overlap vals: a workgroup reads all of its items before it writes any, but several items share a workgroup and
+ *     workgroups do not wait for each other.
+ *   - _dev: every buffer on one of the library's devices, 4-byte aligned (vals is read in 16-byte pieces when it is 16-byte aligned, byte by
+ *     byte otherwise); `stream` as in blsmi_pairing_batch_dev; the inputs stay untouched.
+ * One lease, one device, never in the request combiner. */
+int blsmi_fr_coset_interp_batch(const uint8_t *vals /* m*n*32 */, unsigned log2n, int order, const uint8_t *shifts /* m*32 */, uint8_t *coeffs /* m*n*32 */,
+                                uint8_t *shift_pow /* m*32, may be NULL */, uint8_t *flags /* m, may be NULL */, size_t m);
+int blsmi_fr_coset_interp_batch_dev(const void *d_vals, unsigned log2n, int order, const void *d_shifts, void *d_coeffs, void *d_shift_pow /* may be NULL */,
+                                    void *d_flags /* may be NULL */, size_t m, void *stream);
+/* m KZG cell proofs under one key: cell j is the n = 2^log2n values of the polynomial committed to by C_j over the coset h_j <w>, with ONE
+ * proof pi_j for all of them (EIP-7594: n = 64, order = 1).  vals / log2n / order / shifts as blsmi_fr_coset_interp_batch; srs_g1: the key's
+ * [tau^0] G .. [tau^(n-1)] G; srs_g2: H and [tau^n] H; scalars / block / ok / combined / rechecked exactly as blsmi_kzg_verify_batch.
+ * The cell holds when e(C_j - [I_j(tau)] G, H) = e(pi_j, [tau^n - h_j^n] H).  ok[j] is exactly is_one[j] of blsmi_pairing_product_batch on
+ * (P_j, H), (pi_j, -[tau^n] H) with
+ *     P_j = C_j + (h_j^n mod r) pi_j - sum_i c_ji [tau^i] G,        c_j the coefficients blsmi_fr_coset_interp_batch gives,
+ * with the infinity rules, the block equations, the recheck and the soundness precondition (every key, commitment and proof point in the
+ * prime-order subgroups) of blsmi_kzg_verify_batch: this is that call's equation with z_j := h_j^n, y_j G := sum_i c_ji [tau^i] G and
+ * tau H := [tau^n] H.  Over a block the coefficients are folded first, s_bi = sum_j r_j c_ji mod r, so that a block costs n full-width
+ * ladders over the negated key records and one segmented sum, whatever its length; no [I_j(tau)] G exists on the path that holds.
+ * flags (may be NULL) as blsmi_fr_coset_interp_batch reports them, for the caller to reject -- ok[j] does not depend on them.
+ *   - BLSMI_E_ARG before any device work: a NULL key, vals, shifts, point or ok pointer with m > 0; log2n > 10; order neither 0 nor 1; a zero
+ *     caller scalar; m beyond 2^31 - 2 (2^32 - 1 and beyond included); m * n * 32 beyond a size_t.
+ *   - m = 0: BLSMI_OK, *combined = 0, nothing else is written.  *rechecked = 0 on every early return.  No `block` value is refused.
+ *   - _jac / _dev as blsmi_kzg_verify_batch; vals, shifts, ok and flags are then device buffers, 4-byte aligned; the caller's buffers stay
+ *     untouched.
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * What it does not change: the floor of 0.17 and the lift of 0.20 remain under it -- the interpolation, the n-column fold and B * n ladders
+ * (B blocks) are added to blsmi_kzg_verify_batch's work, nothing of that call is removed or made cheaper.
+ * Measured (one MI355X, everything resident, n = 64, order 1, block = 0, the legs alternating, median of 20 +- spread in ms; DESIGN.md 3w and
+ * profiles/r22_cell.log have the table): (a) the interpolation, its two kernels in brackets (k_fr_inv, k_fr_coset_interp); (b) a
+ * device-to-device copy of the same m * n * 32 bytes; (c) blsmi_kzg_verify_batch_dev on m openings over the same key points; (d) this call,
+ * every cell valid; (e) this call with one value spoiled (a block of 64 cells is rechecked).
+ *     m = 128:     (a) 0.52 +- 0.15 (0.45, 0.05)   (b) 0.02   (a) / (b) 22   (c) 6.21 +- 0.23   (d)  7.14 +- 0.11   (d) - (c) 0.93   (e) 12.57 +- 0.20
+ *     m = 1 024:   (a) 0.52 +- 0.16 (0.45, 0.06)   (b) 0.03   (a) / (b) 21   (c) 6.44 +- 0.16   (d)  7.43 +- 0.11   (d) - (c) 0.99   (e) 12.92 +- 0.32
+ *     m = 8 192:   (a) 0.61 +- 0.01 (0.45, 0.15)   (b) 0.03   (a) / (b) 24   (c) 6.70 +- 0.08   (d) 11.74 +- 0.16   (d) - (c) 5.04   (e) 17.13 +- 0.19
+ *     m = 16 384:  (a) 0.76 +- 0.02 (0.46, 0.29)   (b) 0.03   (a) / (b) 24   (c) 7.16 +- 0.25   (d)  9.77 +- 0.10   (d) - (c) 2.62   (e) 15.27 +- 0.10
+ * The interpolation is bound by the one inversion's latency (k_fr_inv: 0.45 ms for 128 shifts as for 16 384), not by HBM.  The B * n key
+ * ladders are the largest single addition but never more than the rest of the call: 0.8 ms up to 1 024 cells, 2.2 ms of 9.8 at 16 384 (256
+ * blocks, 16 384 ladders, k_g1_mul_glv), and 4.8 ms of 11.7 at 8 192 -- 8 192 ladders are the most that the wave-per-scalar ladder of small
+ * calls still takes (k_lat:mul1), so that 8 192 cells cost MORE than 16 384.  One spoiled value costs 5.4 ms whatever m: 64 cells are
+ * rechecked with 64 ladders each. */
+int blsmi_kzg_verify_cell_batch(const uint8_t *srs_g1 /* n*96: [tau^0]G .. [tau^(n-1)]G */, const uint8_t *srs_g2 /* 2*192: H, [tau^n]H */,
+                                const uint8_t *vals /* m*n*32 */, unsigned log2n, int order, const uint8_t *shifts /* m*32 */,
+                                const uint8_t *commitments /* m*96 */, const uint8_t *proofs /* m*96 */, size_t m,
+                                const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */, uint8_t *ok /* m */,
+                                uint8_t *flags /* m, may be NULL */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_kzg_verify_cell_batch_jac(const uint64_t *srs_g1_jac /* n*18 */, const uint64_t *srs_g2_jac /* 2*36 */, const uint8_t *vals, unsigned log2n, int order,
+                                    const uint8_t *shifts, const uint64_t *commitments_jac /* m*18 */, const uint64_t *proofs_jac /* m*18 */, size_t m,
+                                    const uint64_t *scalars, size_t block, uint8_t *ok, uint8_t *flags, int *combined, size_t *rechecked);
+int blsmi_kzg_verify_cell_batch_dev(const void *d_srs_g1, const void *d_srs_g2, const void *d_vals, unsigned log2n, int order, const void *d_shifts,
+                                    const void *d_commitments, const void *d_proofs, size_t m, const uint64_t *scalars /* host: m, may be NULL */, size_t block,
+                                    void *d_ok, void *d_flags /* may be NULL */, int *combined /* host */, size_t *rechecked /* host */, void *stream);
+int blsmi_kzg_verify_cell_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_vals, unsigned log2n, int order, const void *d_shifts,
+                                        const void *d_commitments_jac, const void *d_proofs_jac, size_t m, const uint64_t *scalars, size_t block,
+                                        void *d_ok, void *d_flags, int *combined, size_t *rechecked, void *stream);
 
 #ifdef __cplusplus
 }
