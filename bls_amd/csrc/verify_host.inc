@@ -584,6 +584,7 @@ bool has_duplicates_sorted(const uint8_t* msgs, const uint64_t* off, size_t n) {
         return c ? c < 0 : la < lb;
     };
     std::sort(idx.begin(), idx.end(), less);
+    if (n && off[idx[0] + 1] == off[idx[0]]) return true;                 // the first comparison is against nil: an empty message sorts first
     for (size_t i = 1; i < n; i++) if (!less(idx[i - 1], idx[i])) return true;
     return false;
 }

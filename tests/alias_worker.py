@@ -55,7 +55,7 @@ def main():
     i_bad = per + per // 3                                                           # a row of device 1's shard
     bad = allpk.copy(); bad[192 * i_bad:192 * (i_bad + 1)] = pks[(i_bad + 1) % nk]
     ck["aggregate_wrong_key_in_device_1_shard"] = eng.g2pubs_verify_aggregate(packed, bad, agg) is False
-    dup = list(msgs); dup[n - 1] = dup[123]                                          # duplicate across the first and the last device
+    dup = list(msgs); dup[n - 1] = dup[123]                                          # duplicate across the first and the last device (agg signs the original messages, so the equation fails as well; the rule alone: test_gpu_dup_rule.py)
     ck["aggregate_duplicate_across_first_and_last_device"] = eng.g2pubs_verify_aggregate(dup, allpk, agg) is False
     small = eng.g1_sum(sigs[:3].reshape(-1), 3)
     ck["aggregate_small_oracle"] = eng.g2pubs_verify_aggregate(msgs[:3], allpk[:192 * 3], small) is True and RC.g2pubs.verify_aggregate(small, [pks[i].tobytes() for i in range(3)], msgs[:3]) is True

@@ -44,7 +44,7 @@ def main():
     for d in (0, ndev // 2, ndev - 1):                                      # a wrong key in the first, a middle and the last device's shard
         bad = allpk.copy(); i = d * per + per // 3; bad[i] = pkj[(i + 1) % nk]
         ck["wrong_key_in_shard_%d" % d] = eng.g2pubs_verify_aggregate_jac(packed, bad.reshape(-1), aggj) is False
-    dup = list(msgs); dup[n - 1] = dup[7]                                   # the same message on the first and the last device
+    dup = list(msgs); dup[n - 1] = dup[7]                                   # the same message on the first and the last device (aggj signs the original messages, so the equation fails as well; the rule alone: test_gpu_dup_rule.py)
     ck["duplicate_across_first_and_last_device"] = eng.g2pubs_verify_aggregate_jac(dup, allpk.reshape(-1), aggj) is False
     # a prefix small enough for the oracle, same keys / signatures: the verdict is the reference's
     m = 5

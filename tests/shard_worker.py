@@ -56,7 +56,7 @@ def main():
         ck[grp + "_aggregate_true"] = va(ms, b"".join(pk2), agg) is True
         sw = list(pk2); sw[150], sw[151] = sw[151], sw[150]
         ck[grp + "_aggregate_swapped"] = va(ms, b"".join(sw), agg) is False
-        dup = list(ms); dup[199] = dup[3]
+        dup = list(ms); dup[199] = dup[3]                    # (agg signs the original messages: the equation fails as well; the rule alone: dup_rule_worker.py)
         ck[grp + "_aggregate_duplicate"] = va(dup, b"".join(pk2), agg) is False
         infk = list(pk2); infk[180] = bytes(len(pk2[0]))
         ck[grp + "_aggregate_inf_key"] = va(ms, b"".join(infk), agg) is False

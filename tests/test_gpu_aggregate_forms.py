@@ -208,7 +208,8 @@ def test_aggregate_partial_finished_by_the_oracle(eng, pkgs, kind, n):
 @pytest.mark.parametrize("kind", ["g2pubs", "g1pubs"])
 def test_host_form_device_screen_at_4097(eng, kind):
     """Above DUP_INLINE_MAX = 4 096 the host form screens for duplicates on the device.  Oracle-made signatures over 4 097 distinct
-    messages verify; with message 4096 set equal to message 0 the reference's rule says False whatever the signature."""
+    messages verify; with message 4096 set equal to message 0 the reference's rule says False -- with the old aggregate, where the pairing
+    equation fails as well, and with position 4096 signed again, where the rule alone rejects (test_gpu_dup_rule.py: the whole corpus)."""
     n, nk = 4097, 16
     o, host, g2 = (RC.g2pubs, eng.g2pubs_verify_aggregate, True) if kind == "g2pubs" else (RC.g1pubs, eng.g1pubs_verify_aggregate, False)
     xs = P.XORShift(4097)
@@ -226,3 +227,6 @@ def test_host_form_device_screen_at_4097(eng, kind):
     dup = list(msgs); dup[4096] = dup[0]
     assert sorted(dup)[0] == sorted(dup)[1] or len(set(dup)) < n           # the reference's rule: equal neighbours after sorting
     assert host(dup, keys, agg) is False
+    sigs[4096] = o.sign(dup[4096], sks[4096 % nk])                         # a correct aggregate of the messages as they stand
+    assert o.verify(dup[4096], pks[4096 % nk], sigs[4096]) is True
+    assert host(dup, keys, (RC.g1_sum if g2 else RC.g2_sum)(b"".join(sigs), n)) is False

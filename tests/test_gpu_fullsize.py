@@ -136,7 +136,8 @@ def test_config4_verify_aggregate_1m(eng):
     # one corrupted public key (swap two signers) must flip the verdict
     bad = all_pks.copy(); bad[12345] = all_pks[12346]
     assert eng.g2pubs_verify_aggregate(msgs, bad.reshape(-1), agg) is False
-    # a duplicated message is rejected on the host before any device work (g2pubs/bls.go:245-261)
+    # a duplicated message gives False (g2pubs/bls.go:245-261) -- here under the aggregate of the original messages, so the pairing equation
+    # fails as well and this does not show which of the two rejected; test_gpu_dup_rule.py has the cases where the rule alone decides
     dup = list(msgs); dup[999] = dup[5]
     assert eng.g2pubs_verify_aggregate(dup, all_pks.reshape(-1), agg) is False
 
@@ -206,7 +207,8 @@ def test_config5_g1pubs_256k(eng):
 def test_config5_literal_g1pubs_256k_verify_aggregate(eng):
     """BASELINE configs[4] as worded: "g1pubs path (G2 pubkeys, G1 sigs): 256k aggregate verify" -- ONE
     (*Signature).VerifyAggregate over 262 144 distinct messages (g1pubs/bls.go:252-282): true, one swapped pair of keys
-    -> false, a duplicated message -> false.  Exercises the k_miller1 + Fq12 product tree path with G2 hashes at size."""
+    -> false, a duplicated message -> false (under the aggregate of the original messages: the equation fails there too; the rule on its
+    own is test_gpu_dup_rule.py's).  Exercises the k_miller1 + Fq12 product tree path with G2 hashes at size."""
     n = 262144
     nk = 256
     sk = scalars(nk, 55)

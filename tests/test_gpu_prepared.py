@@ -154,7 +154,7 @@ def test_verify_aggregate_with_prepared_keys(eng, n):
     bad = idx.copy(); bad[n // 2] = (bad[n // 2] + 1) % 6
     assert prepared(msgs, bad, agg) is False and plain(msgs, bad, agg) is False
     dup = list(msgs); dup[n - 1] = dup[1]
-    assert prepared(dup, idx, agg) is False                                # duplicate message (g2pubs/bls.go:245-261)
+    assert prepared(dup, idx, agg) is False                                # duplicate message (g2pubs/bls.go:245-261); agg signs the original messages, so the equation fails too -- the rule alone: test_gpu_dup_rule.py
     infk = idx.copy(); infk[n - 2] = 6
     assert prepared(msgs, infk, agg) is False and plain(msgs, infk, agg) is False
     assert prepared(msgs, idx, bytes(96)) is False
@@ -215,7 +215,7 @@ def test_library_owned_tables_and_the_host_form(eng):
     agg = eng.g1_sum(sigs.reshape(-1), n)
     assert eng.g2pubs_verify_aggregate_prepared(msgs, pk, idx, agg) is True
     assert eng.g2pubs_verify_aggregate_prepared(msgs, pk, bad, agg) is False
-    dup = list(msgs); dup[5] = dup[6]
+    dup = list(msgs); dup[5] = dup[6]                                      # (agg signs the original messages: not the rule alone, see test_gpu_dup_rule.py)
     assert eng.g2pubs_verify_aggregate_prepared(dup, pk, idx, agg) is False
     assert eng.g2pubs_verify_aggregate_prepared(msgs[:6], pk, None, eng.g1_sum(sigs[:6].reshape(-1), 6)) is (list(idx[:6]) == list(range(6)))
     pk.close()
