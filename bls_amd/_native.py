@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libblsmi.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "blsmi.h")
 # translation units of libblsmi.so: the host side + one unit per kernel family, compiled in parallel
-_UNITS = ["blsmi.hip", "k_pairing_pair.hip", "k_fe_pair.hip", "k_pairing_quad.hip", "k_pairing_row.hip", "k_fq12_seg.hip", "k_prepared_pair.hip", "k_pairing_single.hip", "k_fe_single.hip", "k_fq12_single.hip", "k_hash.hip", "k_wire.hip", "k_check.hip", "k_hash_pair.hip", "k_hash_quad.hip", "k_curve.hip", "k_msm_pair.hip", "k_lat.hip", "k_util.hip", "k_locate.hip", "k_fr.hip", "k_kzg.hip", "k_fr_eval.hip", "k_fr_ntt.hip"]
+_UNITS = ["blsmi.hip", "k_pairing_pair.hip", "k_fe_pair.hip", "k_pairing_quad.hip", "k_pairing_row.hip", "k_fq12_seg.hip", "k_prepared_pair.hip", "k_pairing_single.hip", "k_fe_single.hip", "k_fq12_single.hip", "k_hash.hip", "k_wire.hip", "k_check.hip", "k_hash_pair.hip", "k_hash_quad.hip", "k_curve.hip", "k_msm_pair.hip", "k_lat.hip", "k_util.hip", "k_locate.hip", "k_fr.hip", "k_kzg.hip", "k_fr_eval.hip", "k_fr_ntt.hip", "k_kzg_fs.hip"]
 LAT_BIN = os.path.join(CSRC, "lat_programs.z")            # level programs of the latency path (gen_lat.py), zlib-compressed, embedded into blsmi.hip.o
 BUILD_DIR = os.path.join(CSRC, "build")
 # -Werror=pass-failed: a kernel that misses its declared waves-per-SIMD (a shared device function that outgrew the register budget)
@@ -26,7 +26,7 @@ _LIMBS28_UNITS = () if os.environ.get("BLSMI_BUILD_LIMBS27") else ("k_pairing_pa
 
 # rough compile cost in seconds (scheduling order only)
 _COST = {"k_fe_single.hip": 45, "k_hash.hip": 40, "k_curve.hip": 50, "k_pairing_quad.hip": 45, "k_pairing_row.hip": 15, "k_pairing_single.hip": 40, "k_pairing_pair.hip": 32, "k_wire.hip": 30, "k_check.hip": 30,
-         "k_fq12_single.hip": 30, "k_fe_pair.hip": 17, "k_hash_pair.hip": 17, "k_prepared_pair.hip": 16, "blsmi.hip": 5, "k_msm_pair.hip": 13, "k_lat.hip": 8, "k_util.hip": 20, "k_fq12_seg.hip": 7, "k_locate.hip": 6, "k_fr.hip": 6, "k_kzg.hip": 25, "k_fr_eval.hip": 6, "k_fr_ntt.hip": 6}
+         "k_fq12_single.hip": 30, "k_fe_pair.hip": 17, "k_hash_pair.hip": 17, "k_prepared_pair.hip": 16, "blsmi.hip": 5, "k_msm_pair.hip": 13, "k_lat.hip": 8, "k_util.hip": 20, "k_fq12_seg.hip": 7, "k_locate.hip": 6, "k_fr.hip": 6, "k_kzg.hip": 25, "k_fr_eval.hip": 6, "k_fr_ntt.hip": 6, "k_kzg_fs.hip": 8}
 
 
 def _unit_flags(u):

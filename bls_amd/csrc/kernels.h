@@ -86,6 +86,11 @@ __global__ void k_fr_bary_prod(const u8* z, const u32* tab, u32 log2n, u8* D, u3
 __global__ void k_fr_bary_sum(const u8* polys, const u8* z, const u32* tab, u32 log2n, const u8* Dinv, const u32* hit, u8* y, u8* noncanon, size_t m);
 // k_fr_ntt.hip
 __global__ void k_fr_coset_interp(const u8* vals, const u8* shifts, const u8* hinv, const u32* tab, u32 log2n, int order, u8* coeffs, u8* shift_pow, u8* flags, size_t m);
+// k_kzg_fs.hip
+__global__ void k_kzg_fs_lane(const u8* polys, u32 log2n, const u8* comm, u8* z, size_t m);
+__global__ void k_kzg_fs_split(const u8* polys, u32 log2n, const u8* comm, u8* z, size_t m);
+__global__ void k_kzg_wire_status(const u8* err, const u8* noncanon, u8* status, u8* pts, u8* y, size_t m);
+__global__ void k_kzg_wire_verdicts(const u8* status, u8* ok, size_t m);
 // k_hash_quad.hip
 __global__ void k_clear_h2_quad(const i32* jbuf, u8* good, u8* out, size_t n);
 __global__ void k_hash_g1_finish_quad(const u8* pts, u8* good, u8* out, size_t n);

@@ -1,7 +1,8 @@
 // rlc_host.hpp -- host orchestration of the randomised (small-exponent) batch verifications: blsmi_g?pubs_*verify*_batch_rlc, ..._rlc_grouped,
 // ..._rlc_locate, ..._rlc_grouped_locate, the committee aggregates' ..._common*_batch_rlc, blsmi_pairing_product_batch_rlc* and ..._rlc_locate*,
 // blsmi_fr_wsum_segmented_u64*, blsmi_groth16_verify_batch*, blsmi_g1_mul_add_batch*, blsmi_kzg_verify_batch*, blsmi_fr_mul_batch*, blsmi_fr_inv_batch*,
-// blsmi_fr_eval_batch*, blsmi_kzg_verify_blob_batch*, blsmi_fr_coset_interp_batch* and blsmi_kzg_verify_cell_batch*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
+// blsmi_fr_eval_batch*, blsmi_kzg_verify_blob_batch*, blsmi_fr_coset_interp_batch*, blsmi_kzg_verify_cell_batch*, blsmi_kzg_blob_challenge_batch* and
+// blsmi_kzg_verify_blob_batch_wire*.  Included by blsmi.hip after verify_host.inc, whose aggregate, segmented-sum and pairing-product machinery it calls.  The
 // forms are built from one set of stages (RlcCall and the rlc_* functions below); each driver writes out only the stages that are its own.
 // Host code only, no kernel in it -- hence not an .inc: the digest of the kernel sources that dates the committed counters (bench.py:
 // source_digest) takes every .inc it does not list by name, and a change here cannot make a counter stale.
@@ -2240,4 +2241,142 @@ BLSMI_API int blsmi_kzg_verify_cell_batch_jac_dev(const void* d_srs_g1_jac, cons
                                                   const void* d_commitments_jac, const void* d_proofs_jac, size_t m, const uint64_t* scalars, size_t block, void* d_ok,
                                                   void* d_flags, int* combined, size_t* rechecked, void* stream) {
     return cell_dev_api(d_srs_g1_jac, d_srs_g2_jac, d_vals, log2n, order, d_shifts, d_commitments_jac, d_proofs_jac, m, scalars, block, d_ok, d_flags, combined, rechecked, stream, true);
+}
+
+// ==== Fiat-Shamir challenge and KZG blob batches from wire bytes (blsmi 0.23; include/blsmi.h under the same title) ===========================
+// z_j = SHA-256("FSBLOBVERIFY_V1_" || N as 16 bytes || blob_j || commitment_j) mod r by k_kzg_fs.hip (the layout and the reduction: sha256_fs.h),
+// and EIP-4844's verify_blob_kzg_proof_batch composed from it: the challenge, beside it on the lease's side stream ONE k_g1_decompress launch
+// over the 2 m compressed points with the subgroup test, the evaluation of 0.21 with its noncanon flags, k_kzg_wire_status, and kzg_core of
+// 0.20 unchanged; k_kzg_wire_verdicts takes the verdict of every item with status != 0 back.  The decompression writes AFFINE records -- all
+// zero for infinity and for a point it refuses --, which is what the lift reads: no further pass.
+namespace {
+enum KzgFsForm : int { FS_LANE = 0, FS_SPLIT = 1 };
+constexpr int KZG_FS_DEFAULT = FS_SPLIT;                                    // the criterion and the measurement
+bool kzg_fs_shape_ok(unsigned log2n, size_t m) { return fr_eval_shape_ok(log2n, 1, m); }
+// on s, not synchronised; one launch, one profile segment
+int kzg_fs_dev_core(const void* d_polys, unsigned log2n, const void* d_comm48, void* d_z, size_t m, int form, hipStream_t s) {
+    const size_t wgs = (m + 63) / 64;
+    if (form == FS_SPLIT) launch_sized(KERNEL_OF(k_kzg_fs_split), wgs, 128, s, d_polys, log2n, d_comm48, d_z, m);
+    else launch_sized(KERNEL_OF(k_kzg_fs_lane), wgs, 64, s, d_polys, log2n, d_comm48, d_z, m);
+    prof_mark(nullptr);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int kzg_fs_dev_api(const void* d_polys, unsigned log2n, const void* d_comm48, void* d_z, size_t m, int form, void* stream) {
+    if (m == 0) return BLSMI_OK;
+    if (!d_polys || !d_comm48 || !d_z || !kzg_fs_shape_ok(log2n, m) || (form != FS_LANE && form != FS_SPLIT)) return BLSMI_E_ARG;
+    LOCK_AND_INIT_AT(d_z);
+    UseStream us(stream);
+    int rc = kzg_fs_dev_core(d_polys, log2n, d_comm48, d_z, m, form, g_stream); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return BLSMI_OK;
+}
+// The call with everything on the device: d_g the key's G, d_k2 its H and tau H (affine records), the blobs and the 48-byte points where
+// they lie (4-byte aligned).  d_status may be null.  Leaves the verdicts in d_ok, NOT synchronised behind the last kernel.
+int kzg_wire_core(const u8* d_g, const void* d_k2, const void* d_polys, unsigned log2n, const void* d_c48, const void* d_p48, size_t m, const uint64_t* scalars, size_t block,
+                  void* d_ok, void* d_status, bool overlap, bool* held, size_t* nre) {
+    hipStream_t s = g_stream;
+    DBuf in48, pts, pinf, perr, dz, dy, dnc, st, wp, tab;
+    HIPCHK(in48.alloc((size_t)96 * m)); HIPCHK(pts.alloc((size_t)192 * m)); HIPCHK(pinf.alloc(2 * m)); HIPCHK(perr.alloc(2 * m));
+    HIPCHK(dz.alloc((size_t)32 * m)); HIPCHK(dy.alloc((size_t)32 * m)); HIPCHK(dnc.alloc(m)); HIPCHK(wp.alloc((size_t)192 * m)); HIPCHK(tab.alloc(192 * 2));
+    if (!d_status) { HIPCHK(st.alloc(m)); d_status = st.p; }
+    // the 2 m points in one buffer: the commitments, then the proofs
+    HIPCHK(hipMemcpyAsync(in48.p, d_c48, (size_t)48 * m, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(in48.as<u8>() + (size_t)48 * m, d_p48, (size_t)48 * m, hipMemcpyDeviceToDevice, s));
+    const GroupKernels& g1 = group_kernels(1);
+    if (overlap) {                                                         // stage 2 beside stage 1: the hash fills few waves
+        HIPCHK(tl_ctx->ensure_aux());
+        hipStream_t side = tl_ctx->aux[0];
+        HIPCHK(hipEventRecord(tl_ctx->fork, s));
+        HIPCHK(hipStreamWaitEvent(side, tl_ctx->fork, 0));
+        launch_quiet(g1.decompress, nblocks(2 * m), side, in48.p, 1, pts.p, pinf.p, perr.p, 2 * m);
+        HIPCHK(hipEventRecord(tl_ctx->join[0], side));
+    } else launch(g1.decompress, nblocks(2 * m), s, in48.p, 1, pts.p, pinf.p, perr.p, 2 * m);
+    int rc = kzg_fs_dev_core(d_polys, log2n, d_c48, dz.p, m, KZG_FS_DEFAULT, s);                             // stage 1
+    if (!rc) rc = fr_eval_dev_core(d_polys, log2n, 1, dz.p, dy.p, dnc.p, m, s);                              // stage 3
+    if (overlap) {                                                         // the join comes on every path: an error leaves no kernel writing the call's buffers
+        if (rc) { (void)hipStreamSynchronize(tl_ctx->aux[0]); return rc; }
+        HIPCHK(hipStreamWaitEvent(s, tl_ctx->join[0], 0));
+    } else if (rc) return rc;
+    launch_quiet(KERNEL_OF(k_kzg_wire_status), nblocks(m), s, perr.p, dnc.p, d_status, pts.p, dy.p, m);
+    rc = kzg_table(d_k2, tab.as<u8>(), s); if (rc) return rc;
+    rc = kzg_lift(pts.as<u8>(), pts.as<u8>() + (size_t)96 * m, dz.as<u8>(), wp.as<u8>(), m, s); if (rc) return rc;
+    const KzgIn in{d_g, wp.as<u8>(), tab.as<u8>(), dy.as<u8>(), scalars, m, block ? block : blsmi_route::pprod_locate_auto_block(m)};
+    rc = kzg_core(in, d_ok, held, nre); if (rc) return rc;                                                   // stage 4
+    launch_quiet(KERNEL_OF(k_kzg_wire_verdicts), nblocks(m), s, d_status, d_ok, m);
+    HIPCHK(hipGetLastError());
+    return BLSMI_OK;
+}
+int kzg_wire_dev_api(const void* d_srs_g1, const void* d_srs_g2, const void* d_polys, unsigned log2n, const void* d_c48, const void* d_p48, size_t m, const uint64_t* scalars,
+                     size_t block, void* d_ok, void* d_status, int* combined, size_t* rechecked, void* stream, bool overlap) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = kzg_check_args(d_srs_g1 && d_srs_g2 && d_polys && d_c48 && d_p48 && d_ok, m, scalars); if (rc) return rc;
+    if (!kzg_fs_shape_ok(log2n, m)) return BLSMI_E_ARG;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT_AT(d_ok);
+    UseStream us(stream);
+    bool held = false; size_t nre = 0;
+    rc = kzg_wire_core((const u8*)d_srs_g1, d_srs_g2, d_polys, log2n, d_c48, d_p48, m, scalars, block, d_ok, d_status, overlap, &held, &nre); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+}  // namespace
+BLSMI_API int blsmi_kzg_blob_challenge_batch(const uint8_t* polys, unsigned log2n, const uint8_t* commitments48, uint8_t* z, size_t m) {
+    if (m == 0) return BLSMI_OK;
+    if (!polys || !commitments48 || !z || !kzg_fs_shape_ok(log2n, m)) return BLSMI_E_ARG;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t pbytes = ((size_t)32 << log2n) * m;
+    DBuf dp, dc, dz;
+    HIPCHK(dp.alloc(pbytes)); HIPCHK(dc.alloc((size_t)48 * m)); HIPCHK(dz.alloc((size_t)32 * m));
+    HIPCHK(hipMemcpyAsync(dp.p, polys, pbytes, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dc.p, commitments48, (size_t)48 * m, hipMemcpyHostToDevice, s));
+    int rc = kzg_fs_dev_core(dp.p, log2n, dc.p, dz.p, m, KZG_FS_DEFAULT, s); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(z, dz.p, (size_t)32 * m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_kzg_blob_challenge_batch_dev(const void* d_polys, unsigned log2n, const void* d_commitments48, void* d_z, size_t m, void* stream) {
+    return kzg_fs_dev_api(d_polys, log2n, d_commitments48, d_z, m, KZG_FS_DEFAULT, stream);
+}
+BLSMI_API int blsmi_debug_kzg_blob_challenge_form_dev(const void* d_polys, unsigned log2n, const void* d_commitments48, void* d_z, size_t m, int form, void* stream) {
+    return kzg_fs_dev_api(d_polys, log2n, d_commitments48, d_z, m, form, stream);
+}
+BLSMI_API int blsmi_kzg_verify_blob_batch_wire(const uint8_t* srs_g1, const uint8_t* srs_g2, const uint8_t* polys, unsigned log2n, const uint8_t* commitments48,
+                                               const uint8_t* proofs48, size_t m, const uint64_t* scalars, size_t block, uint8_t* ok, uint8_t* status, int* combined,
+                                               size_t* rechecked) {
+    groth16_report(combined, rechecked, false, 0);
+    if (m == 0) return BLSMI_OK;
+    int rc = kzg_check_args(srs_g1 && srs_g2 && polys && commitments48 && proofs48 && ok, m, scalars); if (rc) return rc;
+    if (!kzg_fs_shape_ok(log2n, m)) return BLSMI_E_ARG;
+    RlcHostScratch hs; uint8_t* none = nullptr;
+    rc = rlc_scalars_and_ok(hs, scalars, none, false, m); if (rc) return rc;
+    LOCK_AND_INIT();
+    hipStream_t s = g_stream;
+    const size_t pbytes = ((size_t)32 << log2n) * m;
+    DBuf g, k2, dpolys, dc, dp, dok, dst;
+    HIPCHK(g.alloc(96)); HIPCHK(k2.alloc(192 * 2)); HIPCHK(dpolys.alloc(pbytes)); HIPCHK(dc.alloc((size_t)48 * m)); HIPCHK(dp.alloc((size_t)48 * m));
+    HIPCHK(dok.alloc(m)); HIPCHK(dst.alloc(m));
+    HIPCHK(hipMemcpyAsync(g.p, srs_g1, 96, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(k2.p, srs_g2, 192 * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dpolys.p, polys, pbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dc.p, commitments48, (size_t)48 * m, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dp.p, proofs48, (size_t)48 * m, hipMemcpyHostToDevice, s));
+    bool held = false; size_t nre = 0;
+    rc = kzg_wire_core(g.as<u8>(), k2.p, dpolys.p, log2n, dc.p, dp.p, m, scalars, block, dok.p, dst.p, true, &held, &nre); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ok, dok.p, m, hipMemcpyDeviceToHost, s));
+    if (status) HIPCHK(hipMemcpyAsync(status, dst.p, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    groth16_report(combined, rechecked, held, nre);
+    return BLSMI_OK;
+}
+BLSMI_API int blsmi_kzg_verify_blob_batch_wire_dev(const void* d_srs_g1, const void* d_srs_g2, const void* d_polys, unsigned log2n, const void* d_commitments48,
+                                                   const void* d_proofs48, size_t m, const uint64_t* scalars, size_t block, void* d_ok, void* d_status, int* combined,
+                                                   size_t* rechecked, void* stream) {
+    return kzg_wire_dev_api(d_srs_g1, d_srs_g2, d_polys, log2n, d_commitments48, d_proofs48, m, scalars, block, d_ok, d_status, combined, rechecked, stream, true);
+}
+BLSMI_API int blsmi_debug_kzg_verify_blob_batch_wire_dev_serial(const void* d_srs_g1, const void* d_srs_g2, const void* d_polys, unsigned log2n, const void* d_commitments48,
+                                                                const void* d_proofs48, size_t m, const uint64_t* scalars, size_t block, void* d_ok, void* d_status,
+                                                                int* combined, size_t* rechecked, void* stream) {
+    return kzg_wire_dev_api(d_srs_g1, d_srs_g2, d_polys, log2n, d_commitments48, d_proofs48, m, scalars, block, d_ok, d_status, combined, rechecked, stream, false);
 }

@@ -1,6 +1,8 @@
 """KZG batches (blsmi 0.20): blsmi_kzg_verify_batch[_jac|_dev|_jac_dev] and the G1 lift blsmi_g1_mul_add_batch[_dev] they are built on,
 and the blob batches that evaluate their polynomials first (blsmi 0.21: blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]), and the cell
-batches that interpolate their cells over a coset first (blsmi 0.22: blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]), over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
+batches that interpolate their cells over a coset first (blsmi 0.22: blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]), and the Fiat-Shamir
+challenge of a blob proof with the blob batches from wire bytes that derive it (blsmi 0.23: blsmi_kzg_blob_challenge_batch[_dev],
+blsmi_kzg_verify_blob_batch_wire[_dev]), over the same binder as bls_amd.engine (engine._fn / engine._call: the types come from include/blsmi.h).  Host code only: every computation
 happens in the HIP kernels; a missing library or device raises, nothing falls back."""
 import ctypes as C
 
@@ -119,7 +121,7 @@ def verify_blob_batch(srs_g1, srs_g2, polys, log2n, commitments, proofs, z, orde
     polys: m polynomials of N = 2^log2n values each (32 big-endian bytes, any value taken mod r) over the N-th roots of unity -- order 1:
     bit-reversed, the blob layout; order 0: position i holds w^i --; the rest as verify_batch, whose verdict on (C_j, pi_j, z_j, p_j(z_j))
     ok[j] is.  noncanon[j]: one of blob j's values was >= r, for the caller to reject (noncanon=False: not asked for).  z is an input:
-    deriving it by Fiat-Shamir stays the caller's."""
+    deriving it by Fiat-Shamir stays the caller's here; verify_blob_batch_wire derives it on the device."""
     return _verify_blob("blsmi_kzg_verify_blob_batch", False, srs_g1, srs_g2, polys, log2n, order, commitments, proofs, z, scalars, block, noncanon)
 
 
@@ -145,6 +147,61 @@ def verify_blob_batch_dev(d_srs_g1, d_srs_g2, d_polys, log2n, order, d_commitmen
 def verify_blob_batch_jac_dev(d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon=0, scalars=None, block=0, stream=0):
     """device-pointer form over in-memory points -> (combined, rechecked)"""
     return _verify_blob_dev("blsmi_kzg_verify_blob_batch_jac_dev", d_srs_g1_jac, d_srs_g2_jac, d_polys, log2n, order, d_commitments_jac, d_proofs_jac, d_z, m, d_ok, d_noncanon, scalars, block, stream)
+
+
+def blob_challenge_batch(polys, log2n, commitments48):
+    """blsmi_kzg_blob_challenge_batch -> z (m, 32) uint8: z[j] = SHA-256("FSBLOBVERIFY_V1_" || N as 16 big-endian bytes || blob_j ||
+    commitment_j) mod r, EIP-4844's compute_challenge.  polys: m blobs of N = 2^log2n values of 32 bytes; commitments48: m compressed
+    commitments.  The bytes are hashed as they are: nothing is decoded or validated."""
+    log2n, _ = _fr._shape(log2n, 1)
+    c = _e._u8(commitments48)
+    if c.size % 48:
+        raise ValueError("expected m*48 bytes of compressed commitments, got %d" % c.size)
+    m = c.size // 48
+    pp = _e._u8(polys, (32 << log2n) * m)
+    z = np.zeros((m, 32), dtype=np.uint8)
+    _e._call("blsmi_kzg_blob_challenge_batch", _e._p8(pp), log2n, _e._p8(c), _e._p8(z.reshape(-1)), m)
+    return z
+
+
+def blob_challenge_batch_dev(d_polys, log2n, d_commitments48, d_z, m, stream=0):
+    """device-pointer form (ints); the m challenges are in d_z when the call returns"""
+    log2n, _ = _fr._shape(log2n, 1)
+    _e._call("blsmi_kzg_blob_challenge_batch_dev", d_polys, log2n, d_commitments48, d_z, m, stream)
+
+
+def verify_blob_batch_wire(srs_g1, srs_g2, polys, log2n, commitments48, proofs48, scalars=None, block=0, status=True):
+    """blsmi_kzg_verify_blob_batch_wire -> (ok (m,) uint8, status (m,) uint8 or None, combined, rechecked): EIP-4844's
+    verify_blob_kzg_proof_batch from the bytes its caller holds.  polys: m blobs of N = 2^log2n values (32 big-endian bytes, the blob's
+    own order); commitments48, proofs48: m compressed points each; the key, scalars and block as verify_blob_batch.  status[j] = errC |
+    errPi << 3 | noncanon << 6 (the error codes of engine.g1_decompress_batch); ok[j] = 1 exactly when status[j] == 0 and verify_batch's
+    verdict on (C_j, pi_j, z_j, p_j(z_j)) is 1, z_j being blob_challenge_batch's.  status=False: not asked for."""
+    log2n, _ = _fr._shape(log2n, 1)
+    g, h = _e._u8(srs_g1, 96), _e._u8(srs_g2, 2 * 192)
+    c, p = _e._u8(commitments48), _e._u8(proofs48)
+    if c.size % 48 or p.size != c.size:
+        raise ValueError("expected m*48 bytes of C_j and as many of pi_j, got %d and %d" % (c.size, p.size))
+    m = c.size // 48
+    pp = _e._u8(polys, (32 << log2n) * m)
+    pr = _e._scalars(scalars, m)
+    block = _e._block(block)
+    ok = np.zeros(max(1, m), dtype=np.uint8)
+    st = np.zeros(max(1, m), dtype=np.uint8) if status else None
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _e._call("blsmi_kzg_verify_blob_batch_wire", _e._p8(g), _e._p8(h), _e._p8(pp), log2n, _e._p8(c), _e._p8(p), m, pr, block, _e._p8(ok), _e._p8(st),
+             C.byref(comb), C.byref(nre))
+    return ok[:m].copy(), (st[:m].copy() if status else None), comb.value, nre.value
+
+
+def verify_blob_batch_wire_dev(d_srs_g1, d_srs_g2, d_polys, log2n, d_commitments48, d_proofs48, m, d_ok, d_status=0, scalars=None, block=0, stream=0):
+    """device-pointer form (ints) over the key's affine records; the m verdict bytes are in d_ok (and the m status bytes in d_status, unless
+    0) when the call returns; scalars stay on the host.  -> (combined, rechecked)"""
+    log2n, _ = _fr._shape(log2n, 1)
+    pr = _e._scalars(scalars, m)
+    comb, nre = C.c_int(0), C.c_size_t(0)
+    _e._call("blsmi_kzg_verify_blob_batch_wire_dev", d_srs_g1, d_srs_g2, d_polys, log2n, d_commitments48, d_proofs48, m, pr, _e._block(block), d_ok, d_status,
+             C.byref(comb), C.byref(nre), stream)
+    return comb.value, nre.value
 
 
 _R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001

@@ -97,9 +97,12 @@ void blsmi_shutdown(void);
  * (blsmi_fr_eval_batch[_dev]) and the KZG blob batches that evaluate their blobs with it (blsmi_kzg_verify_blob_batch[_jac|_dev|_jac_dev]);
  * no existing prototype changes, no new option.  0.22 adds the interpolation of a polynomial from its values over a coset
  * (blsmi_fr_coset_interp_batch[_dev]) and the KZG cell batches that interpolate their cells with it
- * (blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  The string below
- * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19, 0.20, 0.21 and 0.22 by
- * the presence of those symbols. */
+ * (blsmi_kzg_verify_cell_batch[_jac|_dev|_jac_dev]); no existing prototype changes, no new option.  0.23 adds the Fiat-Shamir challenge of
+ * a blob proof (blsmi_kzg_blob_challenge_batch[_dev]) and the KZG blob batches from wire bytes that derive it, decompress their points and
+ * apply EIP-4844's verdict rules (blsmi_kzg_verify_blob_batch_wire[_dev]), with blsmi_debug_kzg_blob_challenge_form_dev and
+ * blsmi_debug_kzg_verify_blob_batch_wire_dev_serial; no existing prototype changes, no new option.  The string below
+ * still begins "blsmi 0.10": a caller that binds by hand tells 0.11, 0.12, 0.13, 0.14, 0.15, 0.16, 0.17, 0.18, 0.19, 0.20, 0.21, 0.22 and 0.23
+ * by the presence of those symbols. */
 const char *blsmi_version(void);
 
 /* Page-locked ("pinned") host memory for the buffers handed to the host entry points below.  Optional: every entry point takes
@@ -1171,7 +1174,8 @@ int blsmi_fr_eval_batch_dev(const void *d_polys, unsigned log2n, int order, cons
  * ok[j] is exactly its verdict on (C_j, pi_j, z_j, p_j(z_j)), with its infinity rules, its block equations, its recheck and its
  * soundness precondition (every key, commitment and proof point in the prime-order subgroups).  A non-canonical value is taken mod r; it is
  * reported in noncanon (may be NULL) as blsmi_fr_eval_batch reports it, for the caller to reject -- ok[j] does not depend on it.
- * Deriving z_j by Fiat-Shamir (SHA-256 over the blob and the commitment, EIP-4844's compute_challenge) stays the caller's: z is an input.
+ * Deriving z_j by Fiat-Shamir (SHA-256 over the blob and the commitment, EIP-4844's compute_challenge) stays the caller's: z is an input
+ * HERE.  blsmi_kzg_verify_blob_batch_wire (0.23, below) derives it on the device, from the bytes a caller of the EIP function holds.
  *   - BLSMI_E_ARG before any device work: a NULL key, polys, point, z or ok pointer with m > 0; log2n > 16; order neither 0 nor 1; a zero
  *     caller scalar; m beyond 2^31 - 2 (2^32 - 1 and beyond included); m * N * 32 beyond a size_t.
  *   - m = 0: BLSMI_OK, *combined = 0, nothing else is written.  *rechecked = 0 on every early return.  No `block` value is refused.
@@ -1276,6 +1280,76 @@ int blsmi_kzg_verify_cell_batch_dev(const void *d_srs_g1, const void *d_srs_g2, 
 int blsmi_kzg_verify_cell_batch_jac_dev(const void *d_srs_g1_jac, const void *d_srs_g2_jac, const void *d_vals, unsigned log2n, int order, const void *d_shifts,
                                         const void *d_commitments_jac, const void *d_proofs_jac, size_t m, const uint64_t *scalars, size_t block,
                                         void *d_ok, void *d_flags, int *combined, size_t *rechecked, void *stream);
+
+/* ==== Fiat-Shamir challenge and KZG blob batches from wire bytes (blsmi 0.23) ==================================================================
+ * z[j] = SHA-256(D_j) mod r as 32 big-endian bytes, fully reduced, with
+ *     D_j = "FSBLOBVERIFY_V1_" || N as 16 big-endian bytes || blob_j as it lies || commitment_j as it lies,        N = 2^log2n,
+ * EIP-4844's compute_challenge.  polys: m blobs of N values of 32 bytes; commitments48: m compressed commitments of 48 bytes.  The bytes are
+ * hashed AS THEY ARE: nothing is decoded, reduced or validated here, so a non-canonical value or an undecodable commitment changes only the
+ * digest.  The digest can be >= r and >= 2 r: up to two subtractions.  D_j is 32 N + 80 bytes, N / 2 + 2 compression blocks (N = 1: 2); the
+ * blocks are built from word loads (bls_amd/csrc/sha256_fs.h has the layout), 16-byte loads where a block lies whole in a 16-byte aligned
+ * blob.  One launch of k_kzg_fs_split: a workgroup of two waves serves 64 blobs, one wave on the message schedule of block i + 1 while the
+ * other runs the rounds of block i (k_kzg_fs_lane, one lane per blob doing both, is kept for comparison behind
+ * blsmi_debug_kzg_blob_challenge_form_dev, form 0; form 1 is the default; any other form: BLSMI_E_ARG).
+ *   - log2n <= 16.
+ *   - BLSMI_E_ARG before any device work: NULL polys, commitments48 or z with m > 0; log2n > 16; m beyond 2^32 - 1; m * N * 32 beyond a
+ *     size_t.  m = 0: BLSMI_OK, nothing is written.
+ *   - _dev: every buffer on one of the library's devices, 4-byte aligned; `stream` as in blsmi_pairing_batch_dev; the inputs stay untouched.
+ * One lease, one device, never in the request combiner. */
+int blsmi_kzg_blob_challenge_batch(const uint8_t *polys /* m*N*32 */, unsigned log2n, const uint8_t *commitments48 /* m*48 */, uint8_t *z /* m*32 */, size_t m);
+int blsmi_kzg_blob_challenge_batch_dev(const void *d_polys, unsigned log2n, const void *d_commitments48, void *d_z, size_t m, void *stream);
+int blsmi_debug_kzg_blob_challenge_form_dev(const void *d_polys, unsigned log2n, const void *d_commitments48, void *d_z, size_t m, int form /* 0: k_kzg_fs_lane, 1: k_kzg_fs_split */,
+                                            void *stream);
+/* EIP-4844's verify_blob_kzg_proof_batch: m blob proofs under one key from the three byte strings a caller of that function holds per item
+ * -- the blob (N = 2^log2n values of 32 big-endian bytes in the blob's own, bit-reversed order: order = 1 of blsmi_fr_eval_batch, not a
+ * parameter), the 48-byte compressed commitment, the 48-byte compressed proof.  srs_g1, srs_g2, scalars / block / combined / rechecked as
+ * blsmi_kzg_verify_blob_batch (the key is its affine records).  Stages, the buffers being the call's own:
+ *     1  z_j by blsmi_kzg_blob_challenge_batch_dev
+ *     2  beside it, on the lease's side stream, ONE k_g1_decompress launch over the 2 m compressed points with the subgroup test
+ *        (check = 1 of blsmi_g1_decompress_batch), into AFFINE records: the form the lift of 0.20 reads, no further pass
+ *     3  y_j = p_j(z_j) by blsmi_fr_eval_batch_dev, with noncanon
+ *     4  blsmi_kzg_verify_batch_dev's check, unchanged
+ * status (may be NULL): status[j] = errC | errPi << 3 | noncanon << 6, errC and errPi the codes of blsmi_g1_decompress_batch (0 .. 4) for the
+ * commitment and the proof, noncanon as blsmi_fr_eval_batch reports it.  ok[j] = 1 EXACTLY when status[j] == 0 and blsmi_kzg_verify_batch's
+ * verdict on (C_j, pi_j, z_j, p_j(z_j)) is 1.  A well-formed infinity (0xc0, then zeros) is a VALID point, as in the EIP: the zero blob with
+ * C = pi = infinity has ok = 1.  A point that does not decode is never taken for infinity: the zero blob with 48 bytes of 0xff for both points
+ * has ok = 0.  A value >= r is rejected (status 0x40) although z_j and a proof made for it may hold mod r.
+ * An item with status != 0 is CLEARED before stage 4 -- both points to infinity, y_j to 0: the item that holds trivially -- so that it fails
+ * no block: *combined = 1 exactly when the combined check over the items with status 0 held (then ok[j] = (status[j] == 0) for every j),
+ * and *rechecked counts the items, cleared ones included, of the blocks in which an item with status 0 fails, as blsmi_kzg_verify_batch counts
+ * them.  A caller who wants "the whole batch is valid" tests *combined AND every status byte, or every ok byte.
+ *   - BLSMI_E_ARG before any device work: a NULL key, polys, point or ok pointer with m > 0; log2n > 16; a zero caller scalar; m beyond
+ *     2^31 - 2 (2^32 - 1 and beyond included); m * N * 32 beyond a size_t.
+ *   - m = 0: BLSMI_OK, *combined = 0, nothing else is written.  *rechecked = 0 on every early return.  No `block` value is refused.
+ *   - _dev: every buffer but scalars, combined and rechecked on one of the library's devices, 4-byte aligned; `stream` as in
+ *     blsmi_pairing_batch_dev; the caller's buffers stay untouched.  blsmi_debug_kzg_verify_blob_batch_wire_dev_serial is the same call
+ *     with stage 2 on the main stream, in front of stage 1: the leg the overlap is measured against.
+ * "rlc_min" does NOT apply.  The call takes one lease and runs on one device; it is not split and never joins the request combiner.
+ * What it does not change: blsmi_kzg_verify_blob_batch and everything under it -- the floor of 0.17, the lift of 0.20, the evaluation of
+ * 0.21 -- stay as they are; the hash, the decompression and two byte kernels are added in front.  There is no Go shim and no multi-device
+ * split for these calls.
+ * Measured (one MI355X, everything resident, N = 4 096, block = 0, every item valid, median of 20 +- spread in ms; DESIGN.md 3x and
+ * profiles/r23_blob_wire.log have the tables): (a) the challenge, k_kzg_fs_split; (A) the same by k_kzg_fs_lane, the two alternating; (b) a
+ * device-to-device copy of the same m * N * 32 bytes; (h) hashlib.sha256 over the same blobs on 1 / 16 host threads; (c)
+ * blsmi_kzg_verify_blob_batch_dev given z and the affine points; (d) this call; (e) its _serial twin.
+ *     m = 8:      (a) 4.10 +- 0.03   (A) 7.39 +- 0.24   (b) 0.02   (h) 0.46 / 0.41    (c) 6.85 +- 0.31   (d) 11.04 +- 0.48   (e) 12.64 +- 0.47
+ *     m = 64:     (a) 4.11 +- 0.03   (A) 7.84 +- 0.05   (b) 0.03   (h) 3.67 / 2.78    (c) 6.86 +- 0.20   (d) 11.07 +- 0.05   (e) 12.69 +- 0.07
+ *     m = 1 024:  (a) 4.16 +- 0.03   (A) 7.88 +- 0.04   (b) 0.15   (h) 61.4 / 34.7    (c) 7.38 +- 0.43   (d) 12.50 +- 1.19   (e) 13.19 +- 0.07
+ *     m = 4 096:  (a) 4.23 +- 0.02   (A) 8.11 +- 0.03   (b) 0.32   (h) 241 / 147      (c) 8.87 +- 0.17   (d) 14.28 +- 1.14   (e) 14.77 +- 0.13
+ * The challenge has a floor of 4.1 ms whatever m: one blob is 2 050 dependent compressions and a wave costs the same with one lane as with 64.
+ * BELOW ABOUT 70 BLOBS THE HOST'S HASH IS THE BETTER CHOICE (8 blobs: 0.46 ms on one thread); from a few hundred blobs the device is, 57
+ * times at 4 096.  (d) - (c), what the wire call adds, is 4.2 to 5.4 ms; the side stream saves 1.6 ms up to 64 blobs and is never slower
+ * beyond the spread. */
+int blsmi_kzg_verify_blob_batch_wire(const uint8_t *srs_g1 /* 96 */, const uint8_t *srs_g2 /* 2*192 */, const uint8_t *polys /* m*N*32 */, unsigned log2n,
+                                     const uint8_t *commitments48 /* m*48 */, const uint8_t *proofs48 /* m*48 */, size_t m,
+                                     const uint64_t *scalars /* m, may be NULL */, size_t block /* 0 = automatic */, uint8_t *ok /* m */,
+                                     uint8_t *status /* m, may be NULL */, int *combined /* may be NULL */, size_t *rechecked /* may be NULL */);
+int blsmi_kzg_verify_blob_batch_wire_dev(const void *d_srs_g1, const void *d_srs_g2, const void *d_polys, unsigned log2n, const void *d_commitments48,
+                                         const void *d_proofs48, size_t m, const uint64_t *scalars /* host: m, may be NULL */, size_t block, void *d_ok,
+                                         void *d_status /* may be NULL */, int *combined /* host */, size_t *rechecked /* host */, void *stream);
+int blsmi_debug_kzg_verify_blob_batch_wire_dev_serial(const void *d_srs_g1, const void *d_srs_g2, const void *d_polys, unsigned log2n, const void *d_commitments48,
+                                                      const void *d_proofs48, size_t m, const uint64_t *scalars, size_t block, void *d_ok, void *d_status,
+                                                      int *combined, size_t *rechecked, void *stream);
 
 #ifdef __cplusplus
 }
